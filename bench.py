@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the SinDDM multi-scale diffusion hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): diffusion steps/sec at the finest scale + images/sec of a full multi-scale sample.
 One "step" = one reverse diffusion step (p_sample: SinDDMNet forward + fused reverse-step kernel + noise draw) for
 the whole per-GPU batch at the finest pyramid scale.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, and the result line
+(`value`, `ms_per_step`, ...).  --dump-outputs DIR writes what the last timed step computed (rank 0's chains; at most
+64 MB, see dump_outputs) as DIR/x_last_step.npy; with the same arguments the inputs are the same in every run.
+Everything else below -- the roofline pass, the elementwise kernels, full samples, cpu_baseline, fp32_mfma_path, the
+nested records and the training legs -- runs with --full only (the --no-* options then leave parts out).
+
 EVERY N runs the SAME headline workload: **C3** (seascape 6-scale pyramid, T=1000, finest scale 411x512 -- the largest
 single-GPU configuration of BASELINE.json, its "roofline run") at 64 chains PER GPU (weak scaling: value(N) / value(1) is
-the speed-up of the sample-batch sharding).  Nested at every N under the same keys: `c4_strong` / `c5_strong` = the two
+the speed-up of the sample-batch sharding).  With --full, nested at every N under the same keys: `c4_strong` / `c5_strong` = the two
 configurations BASELINE shards over 8 GPUs at their FIXED global batch (C4: 128 chains, C5: 32) split over the N ranks
 (N = 1: the whole batch on the one GPU), the C2 record (balloons 5 scales, 186x248, batch 16), and at N = 1 the
 training step (SURVEY 8(d) secondary metric) and `strong_scaling_n1` (the 1/8 shard of C4 / C5 next to the full batch:
@@ -75,6 +81,12 @@ def parse():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--fp32-convs", action="store_true",
                     help="A/B only: every net launches with SINDDM_DIM_FP32_CONVS (3x3 convs on the fp32 matrix pipe instead of conv_wh)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement (roofline pass, elementwise kernels, full samples, cpu_baseline, "
+                         "fp32-MFMA A/B, C2, strong-scaling records, training; the --no-* options trim this set). "
+                         "Default: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -91,7 +103,9 @@ def _respawn(args):
         raise SystemExit(f"bench.py --gpus {args.gpus}: this node exposes only {have} GPU(s)")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a child process, not an exec: this process has already asked the runtime for its devices
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
 
 
 class Ctx:
@@ -272,9 +286,10 @@ def _traffic(cfg_name):
         return None, None, None
 
 
-def steps_leg(ctx, lib, cfg_name, B, steps, warmup, seed, global_batch=None, fp32_convs=None):
-    """Finest-scale reverse steps of one config: the timed region + the roofline of the dominant kernel.  B = chains of
-    THIS rank; global_batch = chains of the whole job (strong scaling: ranks may differ by one)."""
+def steps_leg(ctx, lib, cfg_name, B, steps, warmup, seed, global_batch=None, fp32_convs=None, roofline=True):
+    """Finest-scale reverse steps of one config: the timed region (+ the roofline of the dominant kernel).  B = chains of
+    THIS rank; global_batch = chains of the whole job (strong scaling: ranks may differ by one).  The state it returns
+    ends with the chains as the last timed step left them."""
     from sinddm_amd.configs import CONFIGS, build_diffusion
     cfg = CONFIGS[cfg_name]
     torch.manual_seed(seed + ctx.rank)
@@ -300,15 +315,35 @@ def steps_leg(ctx, lib, cfg_name, B, steps, warmup, seed, global_batch=None, fp3
     img = d._run_steps(img, s, t_seq[warmup:warmup + steps])
     ctx.barrier()
     dt = time.perf_counter() - t0
-    # the headline region above carries no instrumentation; the roofline comes from a SECOND, untimed pass over the same
-    # steps with HIP events around every MFMA conv launch (on the launch stream)
+    dt_rank = dt
+    dt = ctx.max_over_ranks(dt_rank)
+    dt_min = ctx.min_over_ranks(dt_rank)
+    assert os.environ.get("SINDDM_BENCH_NOFINITE") == "1" or torch.isfinite(img).all()   # (timing-ablation builds)
+    G = global_batch if global_batch is not None else ctx.world * B
+    rec = {"workload": f"{cfg_name}: {n_scales}-scale pyramid, T={cfg['T']}, finest scale {H}x{W}, "
+                       + (f"global batch {G} over {ctx.world} GPU(s)" if global_batch is not None else f"batch {B} per GPU") + ", dim=160",
+           "value": round(G * steps / dt, 3), "ms_per_step": round(dt / steps * 1e3, 4),
+           "ms_per_step_rank_min_max": [round(dt_min / steps * 1e3, 4), round(dt / steps * 1e3, 4)],
+           "pixel_steps_per_sec": round(G * H * W * steps / dt, 1),
+           "steps_per_sec_per_gpu": round(steps / dt, 4), "batch_per_gpu": B, "global_batch": G, "finest_hw": [H, W], "scale": s}
+    if roofline:
+        # (_run_steps returns new buffers: the pass leaves `img`, the timed steps' result, as it is)
+        rec["roofline"] = roofline_pass(ctx, lib, d, img, s, t_seq[warmup:warmup + steps], cfg_name, B * H * W, dt)
+    return rec, (net, d, cfg, H, W, s, total_t, img)
+
+
+def roofline_pass(ctx, lib, d, img, s, t_run, cfg_name, px, dt):
+    """The roofline of the dominant kernel from a SECOND, untimed pass over the timed steps `t_run` (the timed region
+    carries no instrumentation) with HIP events around every MFMA conv launch (on the launch stream).  px = pixels of
+    this rank's batch, dt = the timed region's seconds (slowest rank)."""
+    steps = len(t_run)
     lib.sinddm_prof_begin()
     t0p = time.perf_counter()
     two = d.two_streams
     d.two_streams = False          # (one stream in the instrumented pass: the per-launch event times of two overlapping half-batches would add up to more than the step -- ADVICE r4)
     try:
         with _PowerSampler() as power:
-            img = d._run_steps(img, s, t_seq[warmup:warmup + steps])
+            img = d._run_steps(img, s, t_run)
             ctx.barrier()
     finally:
         d.two_streams = two
@@ -320,11 +355,7 @@ def steps_leg(ctx, lib, cfg_name, B, steps, warmup, seed, global_batch=None, fp3
         if g_n:
             mix[name] = {"launches": int(g_n), "avg_launch_ms": round(g_ms / g_n, 4)}
     all_ms, all_n, all_fl, all_ex = _prof(lib, 0, 1)          # every MFMA convolution of the step
-    dt_rank = dt
-    dt = ctx.max_over_ranks(dt_rank)
-    dt_min = ctx.min_over_ranks(dt_rank)
     assert os.environ.get("SINDDM_BENCH_NOFINITE") == "1" or torch.isfinite(img).all()   # (timing-ablation builds)
-    px = B * H * W
     avg_launch_ms = dom_ms / max(1, dom_n)
     algorithmic = dom_fl / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
     executed = dom_ex / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
@@ -397,15 +428,7 @@ def steps_leg(ctx, lib, cfg_name, B, steps, warmup, seed, global_batch=None, fp3
                     "achieved": None, "peak": None, "unit": "TFLOP/s", "frac": None,
                     "flops_counted": "binary16 and fp32 MFMA launches in one step: no single peak applies (see kernel_mix)"}
     roofline.update(common)
-    G = global_batch if global_batch is not None else ctx.world * B
-    rec = {"workload": f"{cfg_name}: {n_scales}-scale pyramid, T={cfg['T']}, finest scale {H}x{W}, "
-                       + (f"global batch {G} over {ctx.world} GPU(s)" if global_batch is not None else f"batch {B} per GPU") + ", dim=160",
-           "value": round(G * steps / dt, 3), "ms_per_step": round(dt / steps * 1e3, 4),
-           "ms_per_step_rank_min_max": [round(dt_min / steps * 1e3, 4), round(dt / steps * 1e3, 4)],
-           "pixel_steps_per_sec": round(G * H * W * steps / dt, 1),
-           "steps_per_sec_per_gpu": round(steps / dt, 4), "batch_per_gpu": B, "global_batch": G, "finest_hw": [H, W], "scale": s,
-           "roofline": roofline}
-    return rec, (net, d, cfg, H, W, s, total_t)
+    return roofline
 
 
 def elementwise_leg(d, B, H, W, s, total_t, dev):
@@ -689,46 +712,39 @@ def cpu_leg(cfg, n_scales, B, H, W, s, total_t):
     return rec
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        _respawn(args)
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X (no CPU fallback of the hot path exists)")
-    ctx = Ctx(args)
-    from sinddm_amd import _lib
+def dump_outputs(dirname, img, seed):
+    """`img` = the chains as the last timed step left them, what the sampler call hands its caller, as
+    DIR/x_last_step.npy (float32, B x 3 x H x W).  Kept under 64 MB: a batch larger than that is represented by a fixed
+    choice of whole chains (a permutation seeded with --seed, in ascending order), e.g. 25 of C3's 64."""
+    import numpy as np
+    per_chain = img[0].numel() * 4
+    keep = min(img.shape[0], (64 * 10 ** 6 - 4096) // per_chain)
+    if keep < 1:
+        raise SystemExit(f"bench.py --dump-outputs: one chain alone is {per_chain} bytes, more than 64 MB")
+    if keep < img.shape[0]:
+        pick = torch.randperm(img.shape[0], generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+        img = img[pick.to(img.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "x_last_step.npy"), img.float().cpu().numpy())
+
+
+def per_gpu_batch(name):
     from sinddm_amd.configs import CONFIGS
-    lib = _lib.load()
-    if args.fp32_convs:
-        from sinddm_amd.models import SinDDMNet
-        SinDDMNet.fp32_convs = True          # class attribute: every net of this process (a per-call option of the C ABI, no library state)
+    c = CONFIGS[name]
+    return c["batch"] if name in ("C1", "C2", "C3") else max(1, c["batch"] // 8)   # C4/C5 are 8-GPU configs
 
+
+def full_legs(args, ctx, lib, head, state, cfg_name, B, G, sizes):
+    """--full: every measurement besides the headline steps, as the keys they add to the result line."""
+    from sinddm_amd.configs import CONFIGS
     from sinddm_amd.dist import shard_sizes
-
-    def per_gpu_batch(name):
-        c = CONFIGS[name]
-        return c["batch"] if name in ("C1", "C2", "C3") else max(1, c["batch"] // 8)   # C4/C5 are 8-GPU configs
+    net, d, cfg, H, W, s, total_t = state
+    strong = G is not None
 
     def brief(rec):
         return {k: rec[k] for k in ("workload", "value", "ms_per_step", "ms_per_step_rank_min_max", "pixel_steps_per_sec",
                                     "batch_per_gpu", "global_batch")} | {"frac": rec["roofline"]["frac"]}
 
-    # ONE headline workload at every N (VERDICT r4 item 2): C3 at its BASELINE batch PER GPU (weak scaling), so that
-    # value(N) / value(1) is a speed-up.  --global-batch makes the headline a strong-scaling run of --config (default C4).
-    strong = args.global_batch is not None
-    cfg_name = args.config or ("C4" if strong else "C3")
-    if strong:
-        G = args.global_batch
-        sizes = shard_sizes(G, ctx.world)
-        if min(sizes) < 1:
-            raise SystemExit(f"bench.py: global batch {G} leaves a rank of {ctx.world} without a chain (use --global-batch / --batch)")
-        B = sizes[ctx.rank]
-    else:
-        G, sizes = None, None
-        B = args.batch or per_gpu_batch(cfg_name)
-    if ctx.comm_world != ctx.world:
-        raise SystemExit(f"bench.py: communicator of {ctx.comm_world} ranks but --gpus {ctx.world}")
-    head, (net, d, cfg, H, W, s, total_t) = steps_leg(ctx, lib, cfg_name, B, args.steps, args.warmup, args.seed, G)
     head["elementwise"] = elementwise_leg(d, B, H, W, s, total_t, ctx.dev)
     full = None if args.no_full else full_sample_leg(ctx, d, cfg, B, sizes)
     cpu = None
@@ -783,7 +799,7 @@ def main():
 
     c2 = None
     if cfg_name != "C2" and not args.no_c2:
-        c2, (net2, d2, cfg2, H2, W2, s2, tt2) = steps_leg(ctx, lib, "C2", per_gpu_batch("C2"), 20, 3, args.seed)
+        c2, (net2, d2, cfg2, H2, W2, s2, tt2, _) = steps_leg(ctx, lib, "C2", per_gpu_batch("C2"), 20, 3, args.seed)
         c2["elementwise"] = elementwise_leg(d2, per_gpu_batch("C2"), H2, W2, s2, tt2, ctx.dev)
         if not args.no_full:
             c2["full_sample"] = full_sample_leg(ctx, d2, cfg2, per_gpu_batch("C2"))
@@ -794,6 +810,49 @@ def main():
     if ctx.rank == 0 and ctx.world == 1 and not args.no_train:
         train = train_leg(ctx)
         train["train_loop"] = train_loop_leg(ctx)
+    return {"full_sample": full, "roofline": head["roofline"], "fp32_mfma_path": fp32_path, "elementwise": head["elementwise"],
+            "cpu_baseline": cpu, "c2": c2, "train": train} | nested
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        _respawn(args)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X (no CPU fallback of the hot path exists)")
+    ctx = Ctx(args)
+    from sinddm_amd import _lib
+    lib = _lib.load()
+    if args.fp32_convs:
+        from sinddm_amd.models import SinDDMNet
+        SinDDMNet.fp32_convs = True          # class attribute: every net of this process (a per-call option of the C ABI, no library state)
+
+    from sinddm_amd.dist import shard_sizes
+
+    # ONE headline workload at every N (VERDICT r4 item 2): C3 at its BASELINE batch PER GPU (weak scaling), so that
+    # value(N) / value(1) is a speed-up.  --global-batch makes the headline a strong-scaling run of --config (default C4).
+    strong = args.global_batch is not None
+    cfg_name = args.config or ("C4" if strong else "C3")
+    if strong:
+        G = args.global_batch
+        sizes = shard_sizes(G, ctx.world)
+        if min(sizes) < 1:
+            raise SystemExit(f"bench.py: global batch {G} leaves a rank of {ctx.world} without a chain (use --global-batch / --batch)")
+        B = sizes[ctx.rank]
+    else:
+        G, sizes = None, None
+        B = args.batch or per_gpu_batch(cfg_name)
+    if ctx.comm_world != ctx.world:
+        raise SystemExit(f"bench.py: communicator of {ctx.comm_world} ranks but --gpus {ctx.world}")
+    head, (net, d, cfg, H, W, s, total_t, img) = steps_leg(ctx, lib, cfg_name, B, args.steps, args.warmup, args.seed, G,
+                                                          roofline=args.full)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, img, args.seed)
+    del img
+    # the kernel the dim -> dim 3x3 convs of the headline step take (the library's own rule, asked for this shape)
+    wh = lib.sinddm_debug_infer_path(net.dim_arg, B, H, W) == 8
+    extra = full_legs(args, ctx, lib, head, (net, d, cfg, H, W, s, total_t), cfg_name, B, G, sizes) if args.full else {}
+    del net, d
 
     if ctx.rank == 0:
         line = {
@@ -805,17 +864,13 @@ def main():
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": ("f32 (3x3 convs: binary16 hi/lo split products -- Winograd-domain GEMMs with all 4 MFMA terms, fp32 accumulate; "
                       "fp32-equivalent, error vs float64 = the fp32 oracle's: tests/test_gpu_h2.py; everything else fp32)"
-                      if "conv_wh_kernel" in head["roofline"]["kernel_mix"] else
-                      ("f32 (3x3 convs: binary16 hi/lo split products, 3 MFMA terms, fp32 accumulate -- fp32-equivalent, "
-                       "tests/test_gpu_h2.py; everything else fp32)" if "conv_h2_kernel" in head["roofline"]["kernel_mix"] else "f32")),
+                      if wh else "f32"),
             "data": "synthetic (closed-form weights of the dim=160 architecture, torch.randn noise/images)",
             "config": {"workload": head["workload"], "batch_per_gpu": B, "global_batch": head["global_batch"],
                        "shards": sizes, "finest_hw": [H, W], "scale": s,
                        "parallelism": f"independent chains over {ctx.world} GPU(s), one all-gather of the images"},
-            "full_sample": full, "roofline": head["roofline"], "fp32_mfma_path": fp32_path, "elementwise": head["elementwise"],
-            "cpu_baseline": cpu, "c2": c2, "train": train,
         }
-        line.update(nested)
+        line.update(extra)
         print(json.dumps(line), flush=True)
     if ctx.dist_on:
         ctx.td.destroy_process_group()

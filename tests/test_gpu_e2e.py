@@ -302,7 +302,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
         env.pop(k, None)
     env.update(SINDDM_BENCH_BACKEND="gloo", SINDDM_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--config", "C1", "--batch", "1",
-                        "--steps", "3", "--warmup", "1", "--no-cpu", "--no-c2", "--no-train"], capture_output=True,
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-c2", "--no-train"], capture_output=True,
                        text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -326,7 +326,7 @@ def test_bench_strong_scaling_c4_two_ranks():
         env.pop(k, None)
     env.update(SINDDM_BENCH_BACKEND="gloo", SINDDM_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--global-batch", "9", "--steps", "2",
-                        "--warmup", "1", "--no-cpu", "--no-c2", "--no-train", "--no-strong"], capture_output=True,
+                        "--warmup", "1", "--full", "--no-cpu", "--no-c2", "--no-train", "--no-strong"], capture_output=True,
                        text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -356,7 +356,7 @@ def test_bench_default_workload_is_the_same_at_every_n():
     lines = {}
     for n in (1, 2):
         r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1",
-                            "--no-cpu", "--no-c2", "--no-train", "--no-full", "--no-ab"] + (["--no-strong"] if n == 2 else []),
+                            "--full", "--no-cpu", "--no-c2", "--no-train", "--no-full", "--no-ab"] + (["--no-strong"] if n == 2 else []),
                            capture_output=True, text=True, env=env, timeout=1500)
         assert r.returncode == 0, r.stderr[-2000:]
         lines[n] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -370,6 +370,36 @@ def test_bench_default_workload_is_the_same_at_every_n():
     # N = 1 carries the strong-scaling records under the keys an N > 1 line uses: the FULL global batch on the one GPU
     assert a["c4_strong"]["global_batch"] == 128 and a["c4_strong"]["n_gpus"] == 1 and a["c4_strong"]["scaling"] == "strong"
     assert a["c5_strong"]["global_batch"] == 32 and a["c5_strong"]["value"] > 0
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_reproducibly(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps, prints the headline keys and none of --full's records, and
+    --dump-outputs writes the last timed step's chains; two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--config", "C1", "--batch", "2",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert not {"roofline", "full_sample", "cpu_baseline", "fp32_mfma_path", "c2", "train", "c4_strong"} & set(line)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) / line["value"] < 1e-3
+        assert sorted(os.listdir(out)) == ["x_last_step.npy"]
+        x = np.load(out / "x_last_step.npy")
+        assert x.dtype == np.float32 and x.shape == (2, 3, 94, 126) and np.isfinite(x).all()
+        dumps.append(x)
+    np.testing.assert_allclose(dumps[0], dumps[1], rtol=0, atol=1e-5)
 
 
 def test_integration_option_b_snippet():

@@ -72,7 +72,7 @@ def test_bench_torchrun_branch_with_rccl_group():
     env = _env(_port())
     env["SINDDM_BENCH_FORCE_DIST"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--batch", "2",
-                        "--steps", "3", "--warmup", "1", "--no-cpu", "--no-train", "--no-strong", "--no-c2"],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-train", "--no-strong", "--no-c2"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -299,6 +299,26 @@ def test_bench_refuses_missing_gpus():
     assert "exposes only" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_stays_under_64mb(tmp_path):
+    """bench.py --dump-outputs: a C3 batch of 64 chains (161 MB) is written as a fixed, seeded choice of whole chains that
+    fits in 64 MB; a small batch is written whole."""
+    import importlib.util
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("sinddm_bench", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    img = torch.randn(64, 3, 411, 512)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img, 1234)
+    a, b = (np.load(tmp_path / d / "x_last_step.npy") for d in ("a", "b"))
+    assert os.path.getsize(tmp_path / "a" / "x_last_step.npy") <= 64 * 10 ** 6
+    assert a.dtype == np.float32 and a.shape[1:] == (3, 411, 512) and 16 <= a.shape[0] < 64 and np.array_equal(a, b)
+    rows = [int(np.flatnonzero((img.numpy() == r).all(axis=(1, 2, 3)))[0]) for r in a]
+    assert rows == sorted(rows) and len(set(rows)) == len(rows)
+    bench.dump_outputs(str(tmp_path / "c"), img[:3], 1234)
+    assert np.array_equal(np.load(tmp_path / "c" / "x_last_step.npy"), img[:3].numpy())
+
+
 def test_save_image_single_image_is_not_padded(tmp_path):
     """torchvision.utils.save_image writes a single (3,H,W) / (1,3,H,W) image as it is -- no grid frame
     (reference trainer.py:283-285 writes the final unbatched samples this way); batches get the 2-px grid."""

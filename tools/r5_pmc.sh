@@ -1,9 +1,10 @@
 #!/bin/bash
-# round 5 PMC passes (separate runs, --kernel-trace only): tools/r5_pmc.sh <tag>   -> gpurun_out/pmc_<tag>_{c3,c2}_{sq1,grbm,fetch,write}
+# round 5 PMC passes (separate runs, --kernel-trace only): tools/r5_pmc.sh <tag>   -> $OUT/pmc_<tag>_{c3,c2}_{sq1,grbm,fetch,write}
+OUT=${OUT:-out}   # output folder, relative to the repository root
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-r05}
-mkdir -p $ROOT/gpurun_out; cd /tmp; export TMPDIR=/tmp
+mkdir -p $ROOT/$OUT; cd /tmp; export TMPDIR=/tmp
 run() { cfg=$1; n=$2; shift 2
-  timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d $ROOT/gpurun_out/pmc_${TAG}_${cfg}_$n -o pmc --output-format csv -- python $ROOT/bench.py --config ${cfg^^} --steps 2 --warmup 1 --no-full --no-cpu --no-c2 --no-train --no-strong --no-ab > $ROOT/gpurun_out/pmc_${TAG}_${cfg}_$n.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" -d $ROOT/$OUT/pmc_${TAG}_${cfg}_$n -o pmc --output-format csv -- python $ROOT/bench.py --full --config ${cfg^^} --steps 2 --warmup 1 --no-full --no-cpu --no-c2 --no-train --no-strong --no-ab > $ROOT/$OUT/pmc_${TAG}_${cfg}_$n.log 2>&1
   echo "pass $cfg $n rc=$?"; }
 for cfg in c3 c2; do
   run $cfg sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES
@@ -12,7 +13,7 @@ for cfg in c3 c2; do
   run $cfg fetch FETCH_SIZE
   run $cfg write WRITE_SIZE
   cd $ROOT
-  python tools/pmc_summary.py gpurun_out/pmc_${TAG}_${cfg}_ sq1 sq2 grbm fetch write 2>&1 | cut -c1-600 > gpurun_out/${TAG}_pmc_${cfg}_summary.txt
+  python tools/pmc_summary.py $OUT/pmc_${TAG}_${cfg}_ sq1 sq2 grbm fetch write 2>&1 | cut -c1-600 > $OUT/${TAG}_pmc_${cfg}_summary.txt
   cd /tmp
 done
-cd $ROOT; python tools/traffic_from_pmc.py gpurun_out/pmc_${TAG}_ $TAG > gpurun_out/${TAG}_traffic.json; tail -5 gpurun_out/${TAG}_pmc_c3_summary.txt | cut -c1-300
+cd $ROOT; python tools/traffic_from_pmc.py $OUT/pmc_${TAG}_ $TAG > $OUT/${TAG}_traffic.json; tail -5 $OUT/${TAG}_pmc_c3_summary.txt | cut -c1-300
