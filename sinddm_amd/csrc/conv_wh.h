@@ -18,13 +18,15 @@
 //     2-D input transform as packed fp32 on channel pairs, x 2^s (per-sample scale from the tensor's running max), split, written
 //     to LDS as the A fragments of the 24 frequency GEMMs: [f][tile group of 16][k group: piece x channel half][tile][8 x f16]
 //     (48 KB, double buffered);
-//   * M phase (waves 0..5): wave w owns frequencies 4w .. 4w+3 of all 32 tiles x 80 channels (4 x 2 x 5 accumulator tiles =
-//     160 registers); its U fragments come straight from L2 into registers one frequency (5 column tiles) ahead.
+//   * M phase (waves 0..5): wave w owns the frequency column j = w, f = 6 i + w (i = 0..3), of all 32 tiles x 80 channels
+//     (4 x 2 x 5 accumulator tiles = 160 registers); its U fragments come straight from L2 into registers one frequency
+//     (5 column tiles) ahead.
 //   One LDS-only barrier per chunk.  The chunks of a workgroup's items form one stream (round 6): during an item's last multiply
 //   the service waves already produce the next item's first chunk.
-// Epilogue: per 16-channel column tile the waves exchange their frequencies through LDS ([f][co][tile], ONE buffer placed beside
-// the V buffer that holds the next item's first chunk); thread = (tile, channel) gathers 24 values, inverse transform A^T M A,
-// scale, bias, GELU / GELU' / residual, 16-byte stores.
+// Epilogue: each multiplying wave applies the vertical A^T (4 -> 2 rows) to its own four accumulator sets in registers, then
+// per pass of two 16-channel column tiles (3 passes: 2 + 2 + 1) the waves exchange the two rows through LDS ([r][j][co][tile],
+// ONE buffer placed beside the V buffer that holds the next item's first chunk); thread = (tile, channel) gathers 12 values per
+// column tile, horizontal A^T, scale, bias, GELU / GELU' / residual, 16-byte stores.
 //
 // Replaces nn.Conv2d(dim, dim_out, 3, padding=1) [+ GELU] / nn.Conv2d(dim_out, dim_out, 3, padding=1) [+ residual] of
 // SinDDMConvBlock (reference SinDDM/models.py:63-65,79-80) -- inference, training forward and (with transposed, tap-flipped weight
@@ -69,7 +71,7 @@ constexpr int WH_PS = 408;                     // plane stride (floats): 10 x 40
 constexpr int WH_RAW = 16 * WH_PS * 4;         // bytes of one raw buffer: 26 112
 constexpr int WH_V = 24 * 2 * 64 * 16;         // bytes of one V buffer: 49 152
 constexpr int WH_XS = 36;                      // tile stride of the epilogue's exchange rows (32 + 4: conflict-free 16-byte writes)
-constexpr int WH_X = 24 * 16 * WH_XS * 4;      // one exchange buffer [f][co][tile]: 55 296
+constexpr int WH_X = 2 * 6 * 32 * WH_XS * 4;  // one exchange buffer [row r][frequency j][co: two column tiles][tile]: 55 296
 // LDS map (round 6): [raw tile 26 112][region of 137 728: V buffer A at 0, V buffer B at its end; the epilogue's ONE exchange
 // buffer lies at 0 or behind buffer A -- wherever the V fragments of the NEXT item's first chunk are not (they are written
 // during this item's last multiply)]
@@ -206,7 +208,7 @@ __device__ __forceinline__ float wh_dpp_shl2(float old, float src) {      // lan
 }
 
 // ---- the kernel ------------------------------------------------------------------------------------------------
-// Roles: waves 0..5 multiply (frequencies 4w .. 4w+3), waves 6 and 7 are the service waves: they request the raw tiles
+// Roles: waves 0..5 multiply (frequencies w, 6 + w, 12 + w, 18 + w), waves 6 and 7 are the service waves: they request the raw tiles
 // (HBM-latency LDS-DMA) and run the input transform.  Vector memory returns in order per wave, so a wave that waits for U
 // fragments out of L2 must not have tile requests in its queue: with the DMA in the multiplying waves every U refill
 // queued behind a tile request waited out the HBM round trip (first version: 12 700 cycles per chunk instead of ~2 500).
@@ -247,9 +249,11 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
     const int t_rdB = (((sv & 1) * 8 + 4 * t_q) * WH_PS + 2 * t_tr * WH_RS + 4 * t_tc + 4) * 4;      // + plane k + row rr: patch columns 1..4
     const int t_rdE = (((sv & 1) * 8 + 4 * t_q) * WH_PS + 2 * t_tr * WH_RS + (t_tc == 7 ? 36 : 3)) * 4; // the row end's halo column
     const int t_wr0 = ((t_mg * 64 + (sv & 1) * 16 + t_t16) * 16) + t_q * 8;                  // + (i * 6 + j) * 2048 + piece * 512
-    // M-phase role: frequencies 4 wv + (0..3).  V fragment of (f, mg, piece): lane (tile l16, k group kq) reads the 16 bytes of
-    // channel half kq & 1 -- the same bytes for kq and kq + 2 (LDS broadcast): K = 32 = [V | V] against [U_hi | U_lo]
-    const int f0 = 4 * (service_rt ? 0 : wv);
+    // M-phase role: the column j = wv of the 4 x 6 frequency grid, f = 6 fi + wv (fi = vertical frequency 0..3): the vertical
+    // inverse transform then combines the wave's own accumulators.  V fragment of (f, mg, piece): lane (tile l16, k group kq)
+    // reads the 16 bytes of channel half kq & 1 -- the same bytes for kq and kq + 2 (LDS broadcast): K = 32 = [V | V] against
+    // [U_hi | U_lo]
+    const int fj = service_rt ? 0 : wv;
     const int a_rd = ((kq & 1) * 16 + l16) * 16;
 
     // persistent: XCD `xcd` owns a contiguous range of tiles; its (tile, co block) items go round-robin over its workgroups, so
@@ -433,21 +437,22 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
         const __amdgpu_buffer_rsrc_t rsw =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w3), 0, 0x7FFFFFF0, 0x00020000);
         const int wlane = lane * 16;
-        const int wbase = ((cb * nch) * 24 + f0) * 5 * 1024;            // + c * 24 * 5120 + (fi * 5 + n) * 1024
+        const int wbase = ((cb * nch) * 24 + fj) * 5 * 1024;            // + c * 24 * 5120 + (6 fi * 5 + n) * 1024
         h16x8 ur[10];                                                    // ring: two frequencies (10 column tiles) ahead
         auto load_u = [&](int c, int fi, int n, int slot) {
-            const int so = wbase + (c * 24 * 5 + fi * 5 + n) * 1024;
+            const int so = wbase + (c * 24 * 5 + fi * 30 + n) * 1024;
             ur[slot] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, wlane, so, 0));
         };
         auto multiply = [&](int c, const unsigned char* vb) {
-            const unsigned char* A = vb + f0 * 2048 + a_rd;
+            const unsigned char* A = vb + fj * 2048 + a_rd;
             wh_static_for<4>([&](auto FI) {
                 constexpr int fi = decltype(FI)::value;
+                constexpr int fo = fi * 6 * 2048;                       // (f = 6 fi + fj: at most 38 400 bytes, an immediate offset)
                 h16x8 ah0, ah1, al0, al1;
-                ah0 = *reinterpret_cast<const h16x8*>(A + fi * 2048);
-                ah1 = *reinterpret_cast<const h16x8*>(A + fi * 2048 + 1024);
-                al0 = *reinterpret_cast<const h16x8*>(A + fi * 2048 + 512);
-                al1 = *reinterpret_cast<const h16x8*>(A + fi * 2048 + 1024 + 512);
+                ah0 = *reinterpret_cast<const h16x8*>(A + fo);
+                ah1 = *reinterpret_cast<const h16x8*>(A + fo + 1024);
+                al0 = *reinterpret_cast<const h16x8*>(A + fo + 512);
+                al1 = *reinterpret_cast<const h16x8*>(A + fo + 1024 + 512);
                 wh_static_for<5>([&](auto NN) {
                     constexpr int n = decltype(NN)::value;
                     constexpr int slot = (fi & 1) * 5 + n;
@@ -474,7 +479,7 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
             });
         };
 
-        // the epilogue's operands of all five passes are requested up front (one exposed round trip per item, not five); thread =
+        // the epilogue's operands of all five column tiles are requested up front (one exposed round trip per item, not one per pass); thread =
         // (tile t = tid & 31, co16 = tid >> 5)
         const int e_t = tid & 31, e_co = tid >> 5;
         const int e_tr = e_t >> 3, e_tc = e_t & 7;
@@ -553,69 +558,84 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
         g += nch;
         WH_SEG(16);
 
-        // ---- epilogue: per column tile n the multiplying waves hand their frequencies over through LDS: ONE exchange buffer,
-        // beside the V buffer that already holds the next item's first chunk (buffer g & 1) ----
-        // writer: acc[fi][mg][n] = D[tile = mg*16 + 4 kq + r][co = l16]  ->  X[f][co][tile]
-        // reader: thread = (tile t = tid & 31, co16 = tid >> 5)
-        const int e_wr = ((f0 * 16 + l16) * WH_XS + 4 * kq) * 4;    // X[f][co][tile (stride 36)] byte offsets: writer (f0, co = l16, tile 4 kq)
-        const int e_rd = (e_co * WH_XS + e_t) * 4;                  // reader (f = 0, co16, tile)
+        // ---- epilogue: the multiplying waves apply the vertical A^T to their own frequency column in registers, then hand the
+        // two rows over through LDS, two column tiles per pass (3 passes): ONE exchange buffer, beside the V buffer that already
+        // holds the next item's first chunk (buffer g & 1) ----
+        // writer: acc[r][mg][n] = row r of D[tile = mg*16 + 4 kq + 0..3][co = l16] at horizontal frequency fj  ->  X[r][fj][co][tile]
+        // reader: thread = (tile t = tid & 31, co16 = tid >> 5), once per column tile of the pass
+        const int e_wr = ((fj * 32 + l16) * WH_XS + 4 * kq) * 4;    // X[r][j][co 32][tile (stride 36)] byte offsets: writer (r = 0, fj, co = l16, tile 4 kq)
+        const int e_rd = (e_co * WH_XS + e_t) * 4;                  // reader (r = 0, j = 0, co16, tile)
         float amax = 0.f;
         WH_SEG(17);
-        wh_static_for<5>([&](auto NN) {
-            constexpr int n = decltype(NN)::value;
+        if constexpr (!service) {
+            // vertical A^T (F(2,3)), in place: y0 = (m0 + m1) + m2 -> acc[0], y1 = (m1 - m2) - m3 -> acc[1]
+#pragma unroll
+            for (int mg = 0; mg < 2; ++mg)
+#pragma unroll
+                for (int n = 0; n < 5; ++n) {
+                    acc[0][mg][n] = acc[0][mg][n] + acc[1][mg][n] + acc[2][mg][n];
+                    acc[1][mg][n] = acc[1][mg][n] - acc[2][mg][n] - acc[3][mg][n];
+                }
+        }
+        wh_static_for<3>([&](auto PS) {
+            constexpr int n0 = 2 * decltype(PS)::value;           // column tiles n0, n0 + 1 (the last pass: 4 alone)
+            constexpr int nn = n0 + 2 <= 5 ? 2 : 1;
             unsigned char* X = sV + ((g & 1) ? 0 : WH_V);
             if constexpr (!service) {
 #pragma unroll
-                for (int fi = 0; fi < 4; ++fi)
+                for (int r = 0; r < 2; ++r)
 #pragma unroll
-                    for (int g = 0; g < 2; ++g)
-                        *reinterpret_cast<f32x4*>(X + e_wr + fi * (16 * WH_XS * 4) + g * 64) = acc[fi][g][n];
+                    for (int nl = 0; nl < nn; ++nl)
+#pragma unroll
+                        for (int mg = 0; mg < 2; ++mg)
+                            *reinterpret_cast<f32x4*>(X + e_wr + (r * 6 * 32 + nl * 16) * (WH_XS * 4) + mg * 64) = acc[r][mg][n0 + nl];
             }
             wh_barrier();
-            WH_SEG(18 + n);
-            float m[24];
+            WH_SEG(18 + decltype(PS)::value);
+            float q[nn][2][6];
 #pragma unroll
-            for (int f = 0; f < 24; ++f) m[f] = *reinterpret_cast<const float*>(X + e_rd + f * (16 * WH_XS * 4));
-            wh_barrier();                                 // (every wave holds its 24 values: the buffer is free for the next pass / the next item's V)
-            // vertical A^T (F(2,3)): y0 = m0 + m1 + m2, y1 = m1 - m2 - m3
-            float q[2][6];
+            for (int nl = 0; nl < nn; ++nl)
 #pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                q[0][j] = m[j] + m[6 + j] + m[12 + j];
-                q[1][j] = m[6 + j] - m[12 + j] - m[18 + j];
-            }
-            const int co = cb * WH_COB + n * 16 + e_co;
-            const float k = ek[n];
-            const float bv = ebv[n];
+                for (int r = 0; r < 2; ++r)
 #pragma unroll
-            for (int pp = 0; pp < 2; ++pp) {
-                // horizontal A^T (F(4,3)): [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
-                const float* z = q[pp];
-                const float s12 = z[1] + z[2], d12 = z[1] - z[2], s34 = z[3] + z[4], d34 = z[3] - z[4];
-                f32x4 v{z[0] + s12 + s34, d12 + 2.f * d34, s12 + 4.f * s34, d12 + 8.f * d34 + z[5]};
-                const int y = ey + pp;
-                if ((WH_ABL & 16) && v[0] != 123.456f) continue;
-                if (y < H && ex < W) {
-                    const size_t o = ((size_t)b * p.Cout + co) * HW + (size_t)y * W + ex;
-                    v = v * k + bv;
-                    if (p.out_pre) *reinterpret_cast<f32x4*>(p.out_pre + o) = v;
-                    if (p.act == 1) v = gelu_erf4(v);
-                    else if (p.act == 2) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(p.aux + o);
+                    for (int j = 0; j < 6; ++j)
+                        q[nl][r][j] = *reinterpret_cast<const float*>(X + e_rd + ((r * 6 + j) * 32 + nl * 16) * (WH_XS * 4));
+            wh_barrier();                                 // (every wave holds its values: the buffer is free for the next pass / the next item's V)
+            wh_static_for<nn>([&](auto NL) {
+                constexpr int n = n0 + decltype(NL)::value;
+                const int co = cb * WH_COB + n * 16 + e_co;
+                const float k = ek[n];
+                const float bv = ebv[n];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] *= gelu_erf_grad(a[e]);
+                for (int pp = 0; pp < 2; ++pp) {
+                    // horizontal A^T (F(4,3)): [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
+                    const float* z = q[decltype(NL)::value][pp];
+                    const float s12 = z[1] + z[2], d12 = z[1] - z[2], s34 = z[3] + z[4], d34 = z[3] - z[4];
+                    f32x4 v{z[0] + s12 + s34, d12 + 2.f * d34, s12 + 4.f * s34, d12 + 8.f * d34 + z[5]};
+                    const int y = ey + pp;
+                    if ((WH_ABL & 16) && v[0] != 123.456f) continue;
+                    if (y < H && ex < W) {
+                        const size_t o = ((size_t)b * p.Cout + co) * HW + (size_t)y * W + ex;
+                        v = v * k + bv;
+                        if (p.out_pre) *reinterpret_cast<f32x4*>(p.out_pre + o) = v;
+                        if (p.act == 1) v = gelu_erf4(v);
+                        else if (p.act == 2) {
+                            const f32x4 a = *reinterpret_cast<const f32x4*>(p.aux + o);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] *= gelu_erf_grad(a[e]);
+                        }
+                        v += rsd[n][pp];
+                        if (ex + 4 > Wt) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = ex + e < Wt ? v[e] : 0.0f;
+                        }
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(v[e]));
+                        if ((WH_NT & 4) && big_out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.out + o));
+                        else *reinterpret_cast<f32x4*>(p.out + o) = v;
                     }
-                    v += rsd[n][pp];
-                    if (ex + 4 > Wt) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = ex + e < Wt ? v[e] : 0.0f;
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(v[e]));
-                    if ((WH_NT & 4) && big_out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.out + o));
-                    else *reinterpret_cast<f32x4*>(p.out + o) = v;
                 }
-            }
+            });
         });
         if (p.amax_out) amax_publish(amax, p.amax_out + (size_t)b * AMAX_STRIDE);
         WH_SEG(23);

@@ -39,7 +39,7 @@ try:
             nch = 10 if jl in (2, 3, 4, 5) else 5
             chunks = [d0(3 + c, 2 + c) for c in range(nch)]
             print(f"  wave {w}: item {d0(23, 0):.0f} | prologue wait {d0(1, 0):.0f} T0 {d0(2, 1):.0f} | chunks {' '.join('%.0f' % v for v in chunks)} |"
-                  f" -> epilogue start {d0(17, 2 + nch):.0f} | passes {' '.join('%.0f' % d0(18 + k, 17 + k) for k in range(5))} | tail {d0(23, 22):.0f}"
+                  f" -> epilogue start {d0(17, 2 + nch):.0f} | passes {' '.join('%.0f' % d0(18 + k, 17 + k) for k in range(3))} | tail {d0(23, 20):.0f}"
                   + (f" | chunk3: stage+wait {d0(24, 5):.0f} T {d0(25, 24):.0f} barrier {d0(6, 25):.0f}" if w == 6 else f" | chunk3: multiply {d0(25, 5):.0f} barrier {d0(6, 25):.0f}"))
 finally:
     shutil.copy("/tmp/lib_keep.so", os.path.join(ROOT, "sinddm_amd", "libsinddm_hip.so"))
