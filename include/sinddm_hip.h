@@ -116,7 +116,7 @@ int sinddm_reverse_step(const float* x_t, const float* eps, const float* x_tilde
  * = the body of p_sample_loop / p_sample_via_scale_loop (reference SinDDM/models.py:462-487,501-547).  The N(0,1)
  * draws z_i of models.py:455 are generated INSIDE the step kernel (Philox4x32-10 + Box-Muller; stream = (seed,
  * stream_id0 + i, element index)) -- the reference never seeds its generator, so only the distribution is contract;
- * callers that must inject recorded noise use sinddm_net_forward + sinddm_reverse_step per step instead.
+ * callers that must inject recorded noise pass it to sinddm_sample_chain_ex (below) as one step-major buffer.
  *   x       (B,3,H,W) state in; x_alt same-size scratch: the states ping-pong, *result_in_alt tells where x_n is
  *   eps     (B,3,H,W) scratch;  coefs / t_list: HOST arrays of n_steps entries;  ws as for sinddm_net_forward  */
 int sinddm_sample_chain(const float* params, const float* packed, float* x, float* x_alt, float* eps,
@@ -132,6 +132,28 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
                          const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
                          int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
                          void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/);
+
+/* Options of a run of reverse steps.  Every pointer is a DEVICE pointer, 16-byte aligned, or NULL.
+ *   edit_w / edit_c  the ROI edit of sinddm_reverse_step_edit (below), applied to EVERY step of the call: x_recon becomes
+ *                    edit_w[p] * x_recon + edit_c[ch][p]; shared by all B samples.  Both or neither.
+ *   noise            the N(0,1) draws of the run, step-major: step i of the call adds sigma_i * noise[i*B*3*H*W + e] to
+ *                    element e of the (B,3,H,W) state instead of drawing from Philox (`seed` / `stream_id0` are then
+ *                    ignored).  Steps whose sigma is 0 (t == 0) read nothing, but keep their slot. */
+typedef struct sinddm_chain_opts {
+    const float* edit_w;   /* HW floats or NULL            (both or neither)                    */
+    const float* edit_c;   /* 3*HW floats or NULL                                               */
+    const float* noise;    /* n_steps * B*3*H*W floats, step-major, or NULL -> in-kernel Philox */
+} sinddm_chain_opts;
+
+/* sinddm_sample_chain2 with options; opts = NULL (or all members NULL) is sinddm_sample_chain2 itself, bit for bit.
+ * sinddm_sample_chain and sinddm_sample_chain2 are thin wrappers over this entry.  The two-stream split, the workspace
+ * layout and the results do not depend on the options: a split run reads each half-batch's own part of `noise`.
+ * SINDDM_E_BADARG: edit_w without edit_c (or the reverse), a pointer that is not 16-byte aligned. */
+int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                           const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                           int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                           void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                           const sinddm_chain_opts* opts /*host, may be NULL*/);
 
 /* out[i] ~ N(0,1) from the same counter-based generator (the sampler's initial / re-noise draws, models.py:467,518) */
 int sinddm_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);

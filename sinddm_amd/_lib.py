@@ -22,7 +22,8 @@ ABI_SYMBOLS = (
     "sinddm_debug_block_train", "sinddm_debug_infer_path", "sinddm_debug_train_path",
     "sinddm_train_workspace_bytes", "sinddm_packed_bwd_count", "sinddm_pack_weights_bwd",
     "sinddm_net_forward_train", "sinddm_net_backward", "sinddm_l1_loss_fwd_bwd", "sinddm_adam_ema_step",
-    "sinddm_cond_embed", "sinddm_cond_stride", "sinddm_sample_chain", "sinddm_sample_chain2", "sinddm_normal_fill",
+    "sinddm_cond_embed", "sinddm_cond_stride", "sinddm_sample_chain", "sinddm_sample_chain2", "sinddm_sample_chain_ex",
+    "sinddm_normal_fill",
 )
 
 
@@ -38,6 +39,11 @@ class StepCoefs(C.Structure):
                 ("gamma_t", C.c_float), ("gamma_tm1", C.c_float),
                 ("sqrt_ac_tm1", C.c_float), ("sqrt_ac_t", C.c_float), ("sqrt_1m_ac_t", C.c_float),
                 ("sqrt_1m_ac_tm1_mvar", C.c_float), ("sigma", C.c_float)]
+
+
+class ChainOpts(C.Structure):
+    """Mirror of `sinddm_chain_opts` (include/sinddm_hip.h): device pointers or None."""
+    _fields_ = [("edit_w", C.c_void_p), ("edit_c", C.c_void_p), ("noise", C.c_void_p)]
 
 
 class SinddmError(RuntimeError):
@@ -81,6 +87,8 @@ def load() -> C.CDLL:
                                     i, i, i, i, p, sz, p, C.POINTER(C.c_int)]),
         "sinddm_sample_chain2": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
                                      i, i, i, i, p, sz, p, p, C.POINTER(C.c_int)]),
+        "sinddm_sample_chain_ex": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
+                                       i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts)]),
         "sinddm_normal_fill": (i, [p, i64, C.c_uint64, C.c_uint64, p]),
         "sinddm_upsample_bilinear": (i, [p, p, i, i, i, i, i, p]),
         "sinddm_prof_begin": (i, []),

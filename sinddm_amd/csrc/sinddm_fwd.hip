@@ -824,15 +824,38 @@ __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned
     z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
 }
 
+// The three tails of a sampler-run step share two compile-time options (sinddm_sample_chain_ex); the plain instantiations
+// <false, false> are the kernels the chain always ran:
+//   EDIT   the ROI edit of reverse_step_kernel<true>: w = ew[p], c = ec[ch * HW + p], shared by all samples
+//   NOISE  z is READ from `nz` (this step's B_total*3*HW recorded draws) at the element's flat index inside the whole batch
+//          instead of drawn from Philox; steps with sigma == 0 read nothing
+template <bool EDIT, bool NOISE>
 __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                const float* __restrict__ xtil, float* __restrict__ out,
                                                                sinddm_step_coefs k, long long n, unsigned long long seed,
-                                                               unsigned long long step) {
+                                                               unsigned long long step, const float* __restrict__ ew,
+                                                               const float* __restrict__ ec, const float* __restrict__ nz,
+                                                               int chw, int hw) {
     const long long n4 = (n + 3) >> 2;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k.sigma != 0.0f) philox_normal4(seed, step, (unsigned long long)q, z);
         const long long i0 = q << 2;
+        if (k.sigma != 0.0f) {
+            if (NOISE) {                        // (a step's slice starts at a multiple of n floats: not 16-byte aligned in general)
+                for (int j = 0; j < 4 && i0 + j < n; ++j) z[j] = nz[i0 + j];
+            } else {
+                philox_normal4(seed, step, (unsigned long long)q, z);
+            }
+        }
+        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
+        if (EDIT) {
+            int r = (int)(i0 % chw);            // index inside the sample; the quad may run over a plane's or a sample's end
+            for (int j = 0; j < 4 && i0 + j < n; ++j) {
+                w[j] = ew[r % hw];
+                c[j] = ec[r];
+                r = r + 1 == chw ? 0 : r + 1;
+            }
+        }
         if (i0 + 3 < n) {
             const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
             const f32x4 e = *reinterpret_cast<const f32x4*>(eps + i0);
@@ -840,11 +863,11 @@ __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __re
             if (k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
             f32x4 o;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = reverse_step_mean(k, x[j], e[j], xb[j], 1.f, 0.f, false) + k.sigma * z[j];
+            for (int j = 0; j < 4; ++j) o[j] = reverse_step_mean(k, x[j], e[j], xb[j], w[j], c[j], EDIT) + k.sigma * z[j];
             *reinterpret_cast<f32x4*>(out + i0) = o;
         } else {
             for (int j = 0; i0 + j < n; ++j)
-                out[i0 + j] = reverse_step_mean(k, xt[i0 + j], eps[i0 + j], k.mode != 0 ? xtil[i0 + j] : 0.f, 1.f, 0.f, false) +
+                out[i0 + j] = reverse_step_mean(k, xt[i0 + j], eps[i0 + j], k.mode != 0 ? xtil[i0 + j] : 0.f, w[j], c[j], EDIT) +
                               k.sigma * z[j];
         }
     }
@@ -852,13 +875,18 @@ __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __re
 
 // final 1x1 conv (-> eps) + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
 // four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
-// path): eps never goes to memory.
+// path): eps never goes to memory.  EDIT / NOISE: a thread's four pixels are contiguous and 16-byte aligned in the maps and
+// in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller), so both are read as f32x4.
+template <bool EDIT, bool NOISE>
 __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const float* __restrict__ a, const float* __restrict__ w,
                                                                       const float* __restrict__ bias,
                                                                       const float* __restrict__ xt,
                                                                       const float* __restrict__ xtil, float* __restrict__ out,
                                                                       sinddm_step_coefs k, int C, int HW,
-                                                                      unsigned long long seed, unsigned long long step, int b0) {
+                                                                      unsigned long long seed, unsigned long long step, int b0,
+                                                                      const float* __restrict__ ew,
+                                                                      const float* __restrict__ ec,
+                                                                      const float* __restrict__ nz) {
     const int b = blockIdx.y;
     const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (p >= HW) return;
@@ -871,17 +899,29 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
         e[1] += w[C + c] * v;
         e[2] += w[2 * C + c] * v;
     }
+    f32x4 mw{1.f, 1.f, 1.f, 1.f};
+    if (EDIT) mw = *reinterpret_cast<const f32x4*>(ew + p);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + p;
+        const long long ig = i0 + (long long)b0 * 3 * HW;           // flat index inside the whole batch: the noise key
         float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k.sigma != 0.0f) philox_normal4(seed, step, (unsigned long long)((i0 + (long long)b0 * 3 * HW) >> 2), z);
+        if (k.sigma != 0.0f) {
+            if (NOISE) {
+                const f32x4 zv = *reinterpret_cast<const f32x4*>(nz + ig);
+                z[0] = zv[0]; z[1] = zv[1]; z[2] = zv[2]; z[3] = zv[3];
+            } else {
+                philox_normal4(seed, step, (unsigned long long)(ig >> 2), z);
+            }
+        }
         const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
         f32x4 xb{0.f, 0.f, 0.f, 0.f};
         if (k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
+        f32x4 mc{0.f, 0.f, 0.f, 0.f};
+        if (EDIT) mc = *reinterpret_cast<const f32x4*>(ec + (size_t)c * HW + p);
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = reverse_step_mean(k, x[j], e[c][j], xb[j], 1.f, 0.f, false) + k.sigma * z[j];
+        for (int j = 0; j < 4; ++j) o[j] = reverse_step_mean(k, x[j], e[c][j], xb[j], mw[j], mc[j], EDIT) + k.sigma * z[j];
         *reinterpret_cast<f32x4*>(out + i0) = o;
     }
 }
@@ -889,11 +929,14 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
 // standalone N(0,1) fill from the same generator (tests; initial / re-noise draws of the sampler)
 // the same for padded workspace rows (pitch Wp, true width W): a thread owns a padded quad of a row; the boundary tensors
 // (x_t, x-tilde, x_{t-1}) are plain, so its up to four pixels sit at an unaligned flat index and their N(0,1) draws -- keyed
-// on the FLAT quad index like everywhere else -- come from up to two Philox calls
+// on the FLAT quad index like everywhere else -- come from up to two Philox calls.  EDIT / NOISE: the maps and the recorded
+// draws are plain tensors as well: scalar reads at the unaligned flat index, like x_t.
+template <bool EDIT, bool NOISE>
 __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
     const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ xt,
     const float* __restrict__ xtil, float* __restrict__ out, sinddm_step_coefs k, int C, int H, int W, int Wp,
-    unsigned long long seed, unsigned long long step, int b0) {
+    unsigned long long seed, unsigned long long step, int b0, const float* __restrict__ ew, const float* __restrict__ ec,
+    const float* __restrict__ nz) {
     const int b = blockIdx.y;
     const int qpr = Wp >> 2;
     const int q = blockIdx.x * 256 + threadIdx.x;
@@ -917,7 +960,7 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
         const long long ig = i0 + (long long)b0 * 3 * HW;          // flat index inside the whole batch: the noise key
         const int r0 = (int)(ig & 3);
         float za[4] = {0.f, 0.f, 0.f, 0.f}, zb[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k.sigma != 0.0f) {
+        if (!NOISE && k.sigma != 0.0f) {
             philox_normal4(seed, step, (unsigned long long)(ig >> 2), za);
             if (r0 != 0) philox_normal4(seed, step, (unsigned long long)(ig >> 2) + 1ull, zb);
         }
@@ -929,8 +972,15 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
                 z = r0 == 1 ? z8[j + 1] : z;
                 z = r0 == 2 ? z8[j + 2] : z;
                 z = r0 == 3 ? z8[j + 3] : z;
+                if (NOISE) z = k.sigma != 0.0f ? nz[ig + j] : 0.f;
+                float mw = 1.f, mc = 0.f;
+                if (EDIT) {
+                    const int pp = y * W + x + j;
+                    mw = ew[pp];
+                    mc = ec[(size_t)c * HW + pp];
+                }
                 const float xb = k.mode != 0 ? xtil[i0 + j] : 0.f;
-                out[i0 + j] = reverse_step_mean(k, xt[i0 + j], e[c][j], xb, 1.f, 0.f, false) + k.sigma * z;
+                out[i0 + j] = reverse_step_mean(k, xt[i0 + j], e[c][j], xb, mw, mc, EDIT) + k.sigma * z;
             }
         }
     }
@@ -1031,7 +1081,22 @@ struct ChainStep {
     sinddm_step_coefs coefs;
     unsigned long long seed, stream_id;
     int b0;            // index of this call's first sample inside the whole batch (the noise is keyed on the whole batch's flat index)
+    const float* edit_w;   // ROI edit maps (HW / 3*HW floats, shared by the batch) or both NULL
+    const float* edit_c;
+    const float* noise;    // this step's recorded draws for the WHOLE batch (B_total*3*HW floats) or NULL -> Philox
 };
+
+// one of the four instantiations of a tail kernel: bit 0 = EDIT, bit 1 = NOISE
+#define SINDDM_TAIL_LAUNCH(KERNEL, variant, grid, st, ...)                                                        \
+    do {                                                                                                         \
+        switch (variant) {                                                                                       \
+            case 0: hipLaunchKernelGGL((KERNEL<false, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
+            case 1: hipLaunchKernelGGL((KERNEL<true, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;       \
+            case 2: hipLaunchKernelGGL((KERNEL<false, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;       \
+            default: hipLaunchKernelGGL((KERNEL<true, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;       \
+        }                                                                                                        \
+    } while (0)
+static int tail_variant(const float* edit_w, const float* noise) { return (edit_w ? 1 : 0) | (noise ? 2 : 0); }
 
 int conv3x3_path(int cout, int cin, int coblks, int B, int H, int W) {
     if (!wino_enabled() || cout % 4 != 0) return 0;
@@ -1251,8 +1316,9 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     if (padded) {
         const unsigned gx = (unsigned)((H * (Wp / 4) + 255) / 256);
         if (cs && cs->x_next)
-            hipLaunchKernelGGL(final_conv_reverse_step_pitch_kernel, dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w,
-                               params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, H, W, Wp, cs->seed, cs->stream_id, cs->b0);
+            SINDDM_TAIL_LAUNCH(final_conv_reverse_step_pitch_kernel, tail_variant(cs->edit_w, cs->noise), dim3(gx, B), st, cur,
+                               params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, H, W, Wp,
+                               cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise);
         else
             hipLaunchKernelGGL(final_conv1x1_pitch_kernel, dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w,
                                params + P.fin_b, out, P.half, H, W, Wp);
@@ -1260,9 +1326,9 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         return 0;
     }
     if (cs && cs->x_next && HW % 4 == 0) {
-        hipLaunchKernelGGL(final_conv_reverse_step_kernel, dim3((HW / 4 + 255) / 256, B), dim3(256), 0, st, cur,
-                           params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, HW, cs->seed,
-                           cs->stream_id, cs->b0);
+        SINDDM_TAIL_LAUNCH(final_conv_reverse_step_kernel, tail_variant(cs->edit_w, cs->noise), dim3((HW / 4 + 255) / 256, B),
+                           st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, HW,
+                           cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise);
         SINDDM_LAUNCH_CHECK();
         return 0;
     }
@@ -1400,11 +1466,19 @@ int sinddm_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t stream_id,
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
-int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                         const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                         void* aux_stream, int* result_in_alt) {
+int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                           const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                           uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                           void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
     if (!params || !packed || !x || !x_alt || !eps || !coefs || !t_list || !ws || n_steps < 0 || B <= 0 || H <= 0 || W <= 0)
+        return SINDDM_E_BADARG;
+    const float* edit_w = opts ? opts->edit_w : nullptr;
+    const float* edit_c = opts ? opts->edit_c : nullptr;
+    const float* noise = opts ? opts->noise : nullptr;
+    if ((edit_w == nullptr) != (edit_c == nullptr)) return SINDDM_E_BADARG;
+    if (edit_w && (long long)CHANNELS * H * W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;      // (the maps are indexed with ints)
+    // (the plain fused tail reads the maps and the draws as 16-byte vectors)
+    if (((reinterpret_cast<uintptr_t>(edit_w) | reinterpret_cast<uintptr_t>(edit_c) | reinterpret_cast<uintptr_t>(noise)) & 15) != 0)
         return SINDDM_E_BADARG;
     NetPlan p = make_plan(dim);
     if (!p.ok) return SINDDM_E_BADSHAPE;
@@ -1484,13 +1558,15 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
                 cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail ? nxt + o : nullptr; cs.coefs = coefs[i];
                 cs.seed = (unsigned long long)seed; cs.stream_id = (unsigned long long)(stream_id0 + (uint64_t)i);
                 cs.b0 = h ? Bh[0] : 0;
+                cs.edit_w = edit_w; cs.edit_c = edit_c; cs.noise = noise ? noise + (size_t)i * (size_t)n : nullptr;
                 rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
                                       h ? sx : st, nullptr, &cs);
             }
             if (rc) break;
             if (!fuse_tail) {
-                hipLaunchKernelGGL(reverse_step_rng_kernel, dim3((unsigned)bx), dim3(256), 0, st, cur, eps, x_tilde, nxt, coefs[i],
-                                   n, (unsigned long long)seed, (unsigned long long)(stream_id0 + (uint64_t)i));
+                SINDDM_TAIL_LAUNCH(reverse_step_rng_kernel, tail_variant(edit_w, noise), dim3((unsigned)bx), st, cur, eps, x_tilde,
+                                   nxt, coefs[i], n, (unsigned long long)seed, (unsigned long long)(stream_id0 + (uint64_t)i),
+                                   edit_w, edit_c, noise ? noise + (size_t)i * (size_t)n : nullptr, CHANNELS * H * W, H * W);
                 if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
             }
             float* t_ = cur; cur = nxt; nxt = t_;
@@ -1514,12 +1590,20 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
     return 0;
 }
 
+int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                         const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                         void* aux_stream, int* result_in_alt) {
+    return sinddm_sample_chain_ex(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
+                                  H, W, ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr);
+}
+
 int sinddm_sample_chain(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
                         const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                         int* result_in_alt) {
-    return sinddm_sample_chain2(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
-                                H, W, ws, ws_bytes, stream, nullptr, result_in_alt);
+    return sinddm_sample_chain_ex(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
+                                  H, W, ws, ws_bytes, stream, nullptr, result_in_alt, nullptr);
 }
 
 int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,

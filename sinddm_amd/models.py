@@ -81,6 +81,11 @@ def _workspace(device: torch.device, nbytes: int, tag: str = "fwd") -> torch.Ten
     return ws
 
 
+# Byte budget of one noise buffer of a `chain_noise` run (MultiScaleGaussianDiffusion._run_steps): the steps of a run are
+# cut into pieces whose recorded draws fit.  1 GiB is 6 steps of C3's finest scale at batch 64 (161 MB per step) and the
+# whole 521-step run of C2's 67x90 scale at batch 16 (1.2 MB per step).
+CHAIN_NOISE_BYTES = 1 << 30
+
 _AUX: Dict[int, "torch.cuda.Stream"] = {}
 
 
@@ -423,6 +428,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # run of reverse steps (('chain', s, seed, [t...]): the in-kernel draws are sinddm_normal_fill(seed, i)) is logged
         self.draw_log = None
         self.two_streams = True       # coarse scales as two half-batches on two streams (sinddm_sample_chain2)
+        self.chain_noise = False      # True: runs with a `noise_fn` take the chain call too (draws handed over as buffers)
+        self.chain_guided = True      # False: ROI-guided runs take the step-by-step route (A/B measurements, bisecting)
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -521,7 +528,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
     def roi_edit_maps(self, scale: int, H: int, W: int, device, eta: float = 0.8):
         """The reference's sequential ROI blends `x[box] = eta * patch + (1 - eta) * x[box]` over all boxes
         (models.py:291-298) composed into ONE per-pixel affine map x -> w * x + c (w: (H,W), c: (3,H,W)); this is
-        what the fused reverse-step kernel applies (`sinddm_reverse_step_edit`).  Cached per (scale, size, boxes)."""
+        what the step kernels apply (`sinddm_sample_chain_ex` with edit maps; `sinddm_reverse_step_edit` on the
+        step-by-step route).  Cached per (scale, size, boxes)."""
         key = (int(scale), int(H), int(W), float(eta), tuple(tuple(int(v) for v in bb) for bb in self.roi_bbs),
                id(self.roi_target_patch[scale]))
         if self._roi_cache.get("key") == key:
@@ -578,7 +586,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         with torch.no_grad():
             eps = self._eps(x, t, int(t[0]), s)
             x_recon, x_t_mix = self.predict_start_from_noise(x, t=t, s=s, noise=eps)
-            self._dump_x_recon(x_recon, int(t[0]), int(s))                  # models.py:360-366
+            if self.save_interm:                                            # models.py:360-366
+                self._dump_x_recon(x_recon, int(t[0]), int(s))
         if self._clip_active(int(t[0]), int(s)):                            # models.py:367-421
             x_recon = self._clip_guidance(x_recon, int(t[0]), int(s), clip_denoised)
         elif self.roi_guided_sampling and (s < self.n_scales - 1):         # models.py:430-431
@@ -624,14 +633,18 @@ class MultiScaleGaussianDiffusion(nn.Module):
 
     def _run_steps(self, img: torch.Tensor, s: int, t_seq) -> torch.Tensor:
         """The reverse steps `t_seq` of scale s (the loop bodies of models.py:477-485,536-546).  Production path: ONE
-        library call for the whole run -- the per-step scalars come from a prebuilt table, the states ping-pong between
-        two buffers, the N(0,1) draws of models.py:455 are generated inside the step kernel (sinddm_sample_chain), and
-        Python is not entered between steps.  Injected noise (`noise_fn`, parity tests), ROI guidance, intermediate
-        dumps and foreign denoisers take the step-by-step path."""
+        library call for the whole run (sinddm_sample_chain_ex) -- the per-step scalars come from a prebuilt table, the
+        states ping-pong between two buffers, the N(0,1) draws of models.py:455 are generated inside the step kernel,
+        and Python is not entered between steps.  ROI guidance (every scale but the finest) rides the same call: its
+        edit maps go to the fused step kernels (`chain_guided = False` sends it down the step-by-step route).  Injected
+        noise (`noise_fn`) takes the step-by-step path, which the parity fixtures pin, unless `chain_noise` is set: then
+        the same draws, fetched in the same order, are handed to the chain call as buffers of at most
+        CHAIN_NOISE_BYTES.  CLIP guidance, intermediate dumps, foreign denoisers and CPU tensors are step by step."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
-        fast = (self.noise_fn is None and isinstance(self.denoise_fn, SinDDMNet) and not self.save_interm
-                and not self.clip_guided_sampling and not (self.roi_guided_sampling and s < self.n_scales - 1)
+        roi = bool(self.roi_guided_sampling and s < self.n_scales - 1)     # models.py:430-431
+        fast = ((self.noise_fn is None or self.chain_noise) and isinstance(self.denoise_fn, SinDDMNet)
+                and not self.save_interm and not self.clip_guided_sampling and (self.chain_guided or not roi)
                 and len(t_seq) > 0 and img.is_cuda and img.dtype == torch.float32 and img.dim() == 4
                 and img.shape[1] == self.channels == 3)
         if not fast:
@@ -661,19 +674,45 @@ class MultiScaleGaussianDiffusion(nn.Module):
             xt = xt.contiguous()
         packed = net.packed_weights()
         ws = _workspace(x.device, lib.sinddm_workspace_bytes(net.dim, B, H, W))
+        opts = _lib.ChainOpts()
+        if roi:
+            ew, ec = self.roi_edit_maps(s, H, W, x.device)                 # (cached on self: alive for the call)
+            opts.edit_w, opts.edit_c = _lib.ptr(ew), _lib.ptr(ec)
+        aux = _aux_stream(x.device) if self.two_streams else None
+        # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
+
+        def chain(i0, k, seed, noise):
+            nonlocal x, x_alt
+            opts.noise = _lib.ptr(noise)
+            in_alt = C.c_int(0)
+            _lib.check(lib.sinddm_sample_chain_ex(
+                _lib.ptr(net.flat_params), _lib.ptr(packed), _lib.ptr(x), _lib.ptr(x_alt), _lib.ptr(eps), _lib.ptr(xt),
+                C.cast(C.addressof(coefs) + i0 * C.sizeof(_lib.StepCoefs), C.POINTER(_lib.StepCoefs)),
+                C.cast(C.addressof(tl) + i0 * C.sizeof(C.c_int), C.POINTER(C.c_int)), k, float(s), seed, 0, net.dim_arg,
+                B, H, W, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts)),
+                "sinddm_sample_chain_ex")
+            if in_alt.value:
+                x, x_alt = x_alt, x
+
+        if self.noise_fn is not None:
+            # recorded noise: pieces of as many steps as fit the byte budget; each piece's draws are fetched exactly as the
+            # step-by-step loop fetches them (one `_draw("step", ...)` per step, t = 0 included, in step order) and the
+            # next piece continues from the buffer the previous one ended in
+            per = max(1, int(CHAIN_NOISE_BYTES) // (x.numel() * x.element_size()))
+            for i0 in range(0, n, per):
+                k = min(per, n - i0)
+                noise = torch.empty((k,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+                for j in range(k):
+                    noise[j].copy_(self._draw("step", x.shape, s, t_seq[i0 + j], x.device))
+                chain(i0, k, 0, noise)
+            return x
         # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
         # sample, seeding only the CUDA generator (torch.cuda.manual_seed) does not
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
         if self.draw_log is not None:
             self.draw_log.append(("chain", s, seed, list(t_seq)))
-        in_alt = C.c_int(0)
-        # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
-        _lib.check(lib.sinddm_sample_chain2(_lib.ptr(net.flat_params), _lib.ptr(packed), _lib.ptr(x), _lib.ptr(x_alt),
-                                            _lib.ptr(eps), _lib.ptr(xt), coefs, tl, n, float(s), seed, 0, net.dim_arg, B, H, W,
-                                            ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device),
-                                            _aux_stream(x.device) if self.two_streams else None, C.byref(in_alt)),
-                   "sinddm_sample_chain2")
-        return x_alt if in_alt.value else x
+        chain(0, n, seed, None)
+        return x
 
     def _eps(self, x, t_dev, t_host, s):
         if isinstance(self.denoise_fn, SinDDMNet):

@@ -415,7 +415,9 @@ class MultiscaleTrainer(object):
                             batch_size=4, scale_mul=(1, 1), save_images=True):
         """ROI guided generation (trainer.py:436-454): at every scale but the finest the predicted clean image is
         pulled (eta = 0.8) towards a patch of the training image inside the given boxes; the blend runs inside the
-        fused reverse-step kernel (`sinddm_reverse_step_edit`)."""
+        step kernels of the sampler's chain call (`sinddm_sample_chain_ex` with edit maps: one library call per scale,
+        step noise from the in-kernel Philox stream).  With a `noise_fn`, or with `ema_model.chain_guided = False`,
+        the run goes step by step through `sinddm_reverse_step_edit`."""
         from .functions import extract_patch
         em = self.ema_model
         em.roi_guided_sampling = True
