@@ -35,6 +35,12 @@ extern "C" {
                                         * kernels) instead of the binary16 hi/lo kernel (conv_wh.h): for A/B measurements and
                                         * parity tests of the two paths; results agree to fp32 rounding (tests/test_gpu_h2.py) */
 
+/* Receptive radius of SinDDMNet in pixels: per block depthwise 5x5 (2) + 3x3 (1) + 3x3 (1) = 4, four blocks = 16; the
+ * 1x1 convolutions add nothing.  The zero-padded network evaluated on an image extended by a wrapped halo of this many
+ * pixels equals, on the centre, the network with circular padding in every layer (tests/test_tile_host.py):
+ * the halo width of tileable sampling (sinddm_wrap_halo, sinddm_sample_chain_tile). */
+#define SINDDM_TILE_HALO 16
+
 #define SINDDM_E_BADARG   (-1)  /* null pointer / non-positive size            */
 #define SINDDM_E_BADSHAPE (-2)  /* dim/channels not supported by the kernels   */
 #define SINDDM_E_WORKSPACE (-3) /* workspace too small (see *_workspace_bytes) */
@@ -169,6 +175,44 @@ int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_
 /* F.interpolate(in, size=(H,W), mode='bilinear') (align_corners=False)  models.py:567 */
 int sinddm_upsample_bilinear(const float* in, float* out, int BC, int h, int w, int H, int W,
                              void* stream);
+
+/* ---- tileable sampling: wrap-around borders per axis ---------------------------------------- */
+/* No convolution kernel knows circular padding.  A wrapped axis is instead EXTENDED by a halo of wrapped pixels on both
+ * sides; the zero padding of the kernels then only reaches pixels of the halo that are thrown away (SINDDM_TILE_HALO).
+ * No reference line: the reference gets the same network by setting padding_mode='circular' on its nn.Conv2d's.
+ *
+ * sinddm_wrap_halo: ext is (BC, H + 2 halo_y, W + 2 halo_x), its centre the (BC,H,W) image.
+ *   src != NULL  (BC,H,W): ext = circular pad of src -- centre and halo are written (F.pad(mode='circular'), except that
+ *                a halo may be wider than the image: the index is a true modulo)
+ *   src == NULL  the centre of ext is valid; only the halo is refreshed, in place:
+ *                ext[y][x] = ext[halo_y + mod(y - halo_y, H)][halo_x + mod(x - halo_x, W)]
+ *                (reads centre elements only, writes halo elements only: no race)
+ * A zero halo on an axis leaves that axis alone.  SINDDM_E_BADARG: ext NULL, a negative halo, non-positive sizes. */
+int sinddm_wrap_halo(float* ext, const float* src, int BC, int H, int W, int halo_y, int halo_x, void* stream);
+
+/* sinddm_upsample_bilinear with wrap-around on the flagged axes: there the source coordinate s*(dst+0.5)-0.5 is NOT
+ * clamped at 0, i0 = floor(f), weight = f - i0, and both taps are taken modulo the source size -- the interpolation of
+ * the periodic continuation of `in`.  wrap_y = wrap_x = 0 is sinddm_upsample_bilinear itself, bit for bit. */
+int sinddm_upsample_bilinear_wrap(const float* in, float* out, int BC, int h, int w, int H, int W, int wrap_y, int wrap_x,
+                                  void* stream);
+
+/* sinddm_sample_chain_ex on an image whose wrapped axes carry a halo.  H, W are the CENTRE size; every image buffer --
+ * x, x_alt, eps, x_tilde, opts->edit_w, opts->edit_c and every step of opts->noise -- has the EXTENDED size
+ * (B,3,H + 2 halo_y, W + 2 halo_x), and ws >= sinddm_workspace_bytes(dim, B, H + 2 halo_y, W + 2 halo_x).  The call runs
+ * the steps of sinddm_sample_chain_ex on the extended shape and refreshes the halo of every step's output from its
+ * centre (one sinddm_wrap_halo launch per step and half-batch, on that half-batch's stream); on entry it refreshes the
+ * halo of x itself.  x_tilde and the edit maps are only read: they must ARRIVE wrapped (sinddm_wrap_halo with src).  The
+ * centre of the result is the chain of the circularly padded network; its halo is the wrapped centre.
+ *   halo_y / halo_x  0 (axis not wrapped) or >= SINDDM_TILE_HALO; anything else: SINDDM_E_BADARG.
+ *   (0, 0) is sinddm_sample_chain_ex itself: the same launches, the same numbers.
+ * In-kernel Philox noise is keyed on the flat index of the EXTENDED tensor and the draws of halo elements are discarded:
+ * a tiled run and a plain run of one seed are unrelated.  With caller-supplied noise the halo of a step's slice is never
+ * used.  Results with and without aux_stream are identical, as for sinddm_sample_chain_ex. */
+int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                             const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                             int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                             void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                             const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x);
 
 /* ---- training ------------------------------------------------------------------------------ */
 /* Scratch for one training forward+backward of a (B,3,H,W) batch: saved activations (about

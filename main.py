@@ -14,6 +14,8 @@ ranks as independent chains and all-gathered (RCCL over xGMI):
 `style_transfer` / `harmonization` (reference main.py:296-322) drive `MultiscaleTrainer.image2image`; `roi`
 (main.py:257-294) drives `roi_guided_sampling` -- the reference picks the boxes with a cv2 GUI, here they come from
 `--roi_target y x h w` and `--roi_bbs y x h w [y x h w ...]` (finest-scale pixel coordinates).
+`--tile {none,x,y,xy}` (no reference flag) samples with borders that wrap around on the named axes: tileable textures,
+cylindrical panoramas (`--tile x --scale_mul 1 4`).  All five modes honour it.
 The CLIP-guided modes (clip_content, clip_style_*, clip_roi; main.py:153-255) are not wired to the command line: CLIP
 itself is outside this build.  Their drivers exist (`MultiscaleTrainer.clip_sampling` / `clip_roi_sampling`, the guidance
 branch of `p_mean_variance`) and take any scorer with the reference's ClipExtractor interface.
@@ -57,6 +59,9 @@ def build_parser():
             kw["nargs"] = nargs
         p.add_argument("--" + name, **kw)
     p.add_argument("--sample_limited_t", action="store_true")
+    # no reference flag (there: padding_mode='circular' on the nn.Conv2d's): borders that wrap around on the x axis (360-degree
+    # panoramas), the y axis or both (seamlessly tileable textures) -- MultiScaleGaussianDiffusion.tile
+    p.add_argument("--tile", choices=("none", "x", "y", "xy"), default="none")
     return p
 
 
@@ -113,6 +118,8 @@ def main():
         save_and_sample_every=args.save_and_sample_every, avg_window=args.avg_window,
         sched_milestones=sched_milestones, results_folder=results_folder, device=device)
 
+    # a sampling option (training is unchanged): every mode below samples with the EMA model
+    trainer.ema_model.tile = ("y" in args.tile, "x" in args.tile)
     if args.load_milestone > 0:
         trainer.load(milestone=args.load_milestone)
     if args.mode == 'train':

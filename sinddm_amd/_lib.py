@@ -23,12 +23,13 @@ ABI_SYMBOLS = (
     "sinddm_train_workspace_bytes", "sinddm_packed_bwd_count", "sinddm_pack_weights_bwd",
     "sinddm_net_forward_train", "sinddm_net_backward", "sinddm_l1_loss_fwd_bwd", "sinddm_adam_ema_step",
     "sinddm_cond_embed", "sinddm_cond_stride", "sinddm_sample_chain", "sinddm_sample_chain2", "sinddm_sample_chain_ex",
-    "sinddm_normal_fill",
+    "sinddm_normal_fill", "sinddm_wrap_halo", "sinddm_upsample_bilinear_wrap", "sinddm_sample_chain_tile",
 )
 
 
 ABI_VERSION = 3               # SINDDM_ABI_VERSION of include/sinddm_hip.h this binding was written against
 DIM_FP32_CONVS = 0x10000     # SINDDM_DIM_FP32_CONVS of include/sinddm_hip.h: option bit of every `dim` argument
+TILE_HALO = 16               # SINDDM_TILE_HALO of include/sinddm_hip.h: the network's receptive radius = halo of a wrapped axis
 
 
 class StepCoefs(C.Structure):
@@ -89,6 +90,10 @@ def load() -> C.CDLL:
                                      i, i, i, i, p, sz, p, p, C.POINTER(C.c_int)]),
         "sinddm_sample_chain_ex": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
                                        i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts)]),
+        "sinddm_sample_chain_tile": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
+                                         i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i]),
+        "sinddm_wrap_halo": (i, [p, p, i, i, i, i, i, p]),
+        "sinddm_upsample_bilinear_wrap": (i, [p, p, i, i, i, i, i, i, i, p]),
         "sinddm_normal_fill": (i, [p, i64, C.c_uint64, C.c_uint64, p]),
         "sinddm_upsample_bilinear": (i, [p, p, i, i, i, i, i, p]),
         "sinddm_prof_begin": (i, []),

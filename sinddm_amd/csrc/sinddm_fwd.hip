@@ -995,28 +995,83 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ 
     }
 }
 
+// one axis of the bilinear source lookup: taps i0 / i1 and the weight of i1
+//   !WRAP  ATen area_pixel_compute_source_index(align_corners=False): max(scale*(dst+0.5)-0.5, 0), fp32
+//          explicitly ONE rounding (fma), which is what ATen's compiled CPU/GPU kernels do: at source coordinates of
+//          several hundred a two-rounding evaluation moves the interpolation weight by up to an ulp of the coordinate
+//          (3e-5 abs on the 364x1092 scale of config C5; fixture g8:hash_8x776_to_11x1092)
+//   WRAP   the periodic continuation of the source (tileable sampling): the coordinate is NOT clamped at 0 (the first
+//          output pixels interpolate between the last and the first source pixel) and both taps are taken modulo n
+template <bool WRAP>
+__device__ __forceinline__ void upsample_axis(float scale, int dst, int n, int& i0, int& i1, float& lam) {
+    float f = fmaf(scale, (float)dst + 0.5f, -0.5f);
+    if (WRAP) {
+        const float fl = floorf(f);
+        lam = f - fl;
+        i0 = (int)fl % n;
+        if (i0 < 0) i0 += n;
+        i1 = i0 + 1 == n ? 0 : i0 + 1;
+    } else {
+        f = f < 0.0f ? 0.0f : f;
+        i0 = (int)f; if (i0 > n - 1) i0 = n - 1;
+        i1 = i0 + 1 < n ? i0 + 1 : n - 1;
+        lam = f - (float)i0;
+    }
+}
+
+template <bool WRAP_Y, bool WRAP_X>
 __global__ __launch_bounds__(256) void upsample_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                                 int h, int w, int H, int W, float sy, float sx) {
     const int bc = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= H * W) return;
     const int oy = p / W, ox = p - oy * W;
-    // ATen area_pixel_compute_source_index(align_corners=False): max(scale*(dst+0.5)-0.5, 0), fp32
-    // explicitly ONE rounding (fma), which is what ATen's compiled CPU/GPU kernels do: at source coordinates of
-    // several hundred a two-rounding evaluation moves the interpolation weight by up to an ulp of the coordinate
-    // (3e-5 abs on the 364x1092 scale of config C5; fixture g8:hash_8x776_to_11x1092)
-    float fy = fmaf(sy, (float)oy + 0.5f, -0.5f);
-    fy = fy < 0.0f ? 0.0f : fy;
-    float fx = fmaf(sx, (float)ox + 0.5f, -0.5f);
-    fx = fx < 0.0f ? 0.0f : fx;
-    int iy0 = (int)fy; if (iy0 > h - 1) iy0 = h - 1;
-    int ix0 = (int)fx; if (ix0 > w - 1) ix0 = w - 1;
-    const int iy1 = iy0 + 1 < h ? iy0 + 1 : h - 1;
-    const int ix1 = ix0 + 1 < w ? ix0 + 1 : w - 1;
-    const float ly = fy - (float)iy0, lx = fx - (float)ix0;
+    int iy0, iy1, ix0, ix1;
+    float ly, lx;
+    upsample_axis<WRAP_Y>(sy, oy, h, iy0, iy1, ly);
+    upsample_axis<WRAP_X>(sx, ox, w, ix0, ix1, lx);
     const float* s = in + (size_t)bc * h * w;
     const float tl = s[iy0 * w + ix0], tr = s[iy0 * w + ix1], bl = s[iy1 * w + ix0], br = s[iy1 * w + ix1];
     out[(size_t)bc * H * W + p] = (1.0f - ly) * ((1.0f - lx) * tl + lx * tr) + ly * ((1.0f - lx) * bl + lx * br);
+}
+
+// ---- tileable sampling: the wrapped halo of an extended image (sinddm_wrap_halo) ----------------------------------------
+// ext: [BC][H + 2 hy][W + 2 hx], centre = the image.  A thread owns VEC consecutive floats of an extended row and copies
+// them from the centre pixel they wrap to: from `src` ([BC][H][W]; centre and halo are written) or, src == nullptr, from
+// ext's own centre (only halo elements are written, only centre elements are read: in place without a race).
+// VEC = 4 needs W % 4 == 0, hx % 4 == 0 and 16-byte aligned bases: then a quad lies wholly inside or wholly outside the
+// centre, and its source quad is contiguous, aligned and does not run over the image's edge.  (no __restrict__: in place)
+template <int VEC>
+__global__ __launch_bounds__(256) void wrap_halo_kernel(float* ext, const float* src, long long nq, int H, int W, int hy,
+                                                        int hx) {
+    const int He = H + 2 * hy, We = W + 2 * hx, qpr = We / VEC;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+        const long long row = q / qpr;
+        const int x = (int)(q - row * qpr) * VEC;
+        const long long bc = row / He;
+        const int y = (int)(row - bc * He);
+        if (!src && y >= hy && y < hy + H && x >= hx && x < hx + W) continue;      // centre: valid already
+        int cy = (y - hy) % H, cx = (x - hx) % W;                                   // true modulo: a halo may be wider than the image
+        if (cy < 0) cy += H;
+        if (cx < 0) cx += W;
+        const float* s = src ? src + ((size_t)bc * H + cy) * W + cx : ext + ((size_t)bc * He + hy + cy) * We + hx + cx;
+        float* d = ext + ((size_t)bc * He + y) * We + x;
+        if (VEC == 4) *reinterpret_cast<f32x4*>(d) = *reinterpret_cast<const f32x4*>(s);
+        else *d = *s;
+    }
+}
+
+int wrap_halo_launch(float* ext, const float* src, int BC, int H, int W, int hy, int hx, hipStream_t st) {
+    if (hy == 0 && hx == 0 && !src) return 0;                                       // nothing to refresh
+    const bool vec = W % 4 == 0 && hx % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(ext) | reinterpret_cast<uintptr_t>(src)) & 15) == 0;
+    const long long nq = (long long)BC * (H + 2 * hy) * ((W + 2 * hx) / (vec ? 4 : 1));
+    long long bx = (nq + 255) / 256;
+    if (bx > 8192) bx = 8192;
+    if (vec) hipLaunchKernelGGL(wrap_halo_kernel<4>, dim3((unsigned)bx), dim3(256), 0, st, ext, src, nq, H, W, hy, hx);
+    else hipLaunchKernelGGL(wrap_halo_kernel<1>, dim3((unsigned)bx), dim3(256), 0, st, ext, src, nq, H, W, hy, hx);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
 }
 
 // =====================================================================================
@@ -1466,12 +1521,18 @@ int sinddm_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t stream_id,
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
-int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                           const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                           uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                           void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
-    if (!params || !packed || !x || !x_alt || !eps || !coefs || !t_list || !ws || n_steps < 0 || B <= 0 || H <= 0 || W <= 0)
+// The body of sinddm_sample_chain_ex (halo_y = halo_x = 0) and of sinddm_sample_chain_tile.  Hc x Wc is the CENTRE size; the
+// steps run on the extended shape H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo,
+// the halo of every step's output is refreshed from its centre (wrap_halo_launch, per half-batch on its own stream), and
+// that of `x` once on entry: the zero padding of the convolutions then never reaches the centre (SINDDM_TILE_HALO).
+static int sample_chain_impl(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                             const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                             uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
+                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
+    if (!params || !packed || !x || !x_alt || !eps || !coefs || !t_list || !ws || n_steps < 0 || B <= 0 || Hc <= 0 || Wc <= 0)
         return SINDDM_E_BADARG;
+    const bool tiled = halo_y != 0 || halo_x != 0;
+    const int H = Hc + 2 * halo_y, W = Wc + 2 * halo_x;
     const float* edit_w = opts ? opts->edit_w : nullptr;
     const float* edit_c = opts ? opts->edit_c : nullptr;
     const float* noise = opts ? opts->noise : nullptr;
@@ -1526,6 +1587,7 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
     float* cur = x;
     float* nxt = x_alt;
     int rc = 0;
+    if (tiled) rc = wrap_halo_launch(x, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st);     // (ordered before both halves: ev_go)
     for (int i0 = 0; i0 < n_steps && rc == 0;) {
         // a run: up to CHAIN_COND_ROWS steps whose t is an arithmetic progression (the sampler's always is)
         int len = 1, dt = 0;
@@ -1561,6 +1623,8 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
                 cs.edit_w = edit_w; cs.edit_c = edit_c; cs.noise = noise ? noise + (size_t)i * (size_t)n : nullptr;
                 rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
                                       h ? sx : st, nullptr, &cs);
+                if (tiled && fuse_tail && rc == 0)
+                    rc = wrap_halo_launch(nxt + o, nullptr, Bh[h] * CHANNELS, Hc, Wc, halo_y, halo_x, h ? sx : st);
             }
             if (rc) break;
             if (!fuse_tail) {
@@ -1568,6 +1632,7 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
                                    nxt, coefs[i], n, (unsigned long long)seed, (unsigned long long)(stream_id0 + (uint64_t)i),
                                    edit_w, edit_c, noise ? noise + (size_t)i * (size_t)n : nullptr, CHANNELS * H * W, H * W);
                 if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
+                if (tiled && (rc = wrap_halo_launch(nxt, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st)) != 0) break;
             }
             float* t_ = cur; cur = nxt; nxt = t_;
         }
@@ -1588,6 +1653,24 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
     if (rc) return rc;
     if (result_in_alt) *result_in_alt = (cur == x_alt) ? 1 : 0;
     return 0;
+}
+
+int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                           const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                           uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                           void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0);
+}
+
+int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                             const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                             uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
+    if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
+    if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x);
 }
 
 int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1709,10 +1792,30 @@ int sinddm_prof_end3(int kind, double* ms_total, int64_t* launches, double* flop
 int sinddm_upsample_bilinear(const float* in, float* out, int BC, int h, int w, int H, int W, void* stream) {
     if (!in || !out || BC <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
     const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-    hipLaunchKernelGGL(upsample_bilinear_kernel, dim3((H * W + 255) / 256, BC), dim3(256), 0,
+    hipLaunchKernelGGL((upsample_bilinear_kernel<false, false>), dim3((H * W + 255) / 256, BC), dim3(256), 0,
                        static_cast<hipStream_t>(stream), in, out, h, w, H, W, sy, sx);
     SINDDM_LAUNCH_CHECK();
     return 0;
+}
+
+int sinddm_upsample_bilinear_wrap(const float* in, float* out, int BC, int h, int w, int H, int W, int wrap_y, int wrap_x,
+                                  void* stream) {
+    if (!in || !out || BC <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const dim3 grid((H * W + 255) / 256, BC);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (wrap_y && wrap_x) hipLaunchKernelGGL((upsample_bilinear_kernel<true, true>), grid, dim3(256), 0, st, in, out, h, w, H, W, sy, sx);
+    else if (wrap_y) hipLaunchKernelGGL((upsample_bilinear_kernel<true, false>), grid, dim3(256), 0, st, in, out, h, w, H, W, sy, sx);
+    else if (wrap_x) hipLaunchKernelGGL((upsample_bilinear_kernel<false, true>), grid, dim3(256), 0, st, in, out, h, w, H, W, sy, sx);
+    else hipLaunchKernelGGL((upsample_bilinear_kernel<false, false>), grid, dim3(256), 0, st, in, out, h, w, H, W, sy, sx);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sinddm_wrap_halo(float* ext, const float* src, int BC, int H, int W, int halo_y, int halo_x, void* stream) {
+    if (!ext || BC <= 0 || H <= 0 || W <= 0 || halo_y < 0 || halo_x < 0 || halo_y > (1 << 20) || halo_x > (1 << 20))
+        return SINDDM_E_BADARG;
+    return wrap_halo_launch(ext, src, BC, H, W, halo_y, halo_x, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

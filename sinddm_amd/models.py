@@ -8,6 +8,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
   q_sample / p_losses mix    -> sinddm_q_sample           (models.py:570-590)
   p_sample tail              -> sinddm_reverse_step       (models.py:306-352,433-459)
   inter-scale upsample       -> sinddm_upsample_bilinear  (models.py:567)
+  tileable sampling (`tile`) -> sinddm_sample_chain_tile / sinddm_wrap_halo / sinddm_upsample_bilinear_wrap
+                                (no reference line: padding_mode='circular' on its nn.Conv2d's)
 
 There is no CPU / eager-PyTorch fallback: tensors must live on a ROCm device and the shared
 library must be built, otherwise calls raise.
@@ -430,6 +432,12 @@ class MultiScaleGaussianDiffusion(nn.Module):
         self.two_streams = True       # coarse scales as two half-batches on two streams (sinddm_sample_chain2)
         self.chain_noise = False      # True: runs with a `noise_fn` take the chain call too (draws handed over as buffers)
         self.chain_guided = True      # False: ROI-guided runs take the step-by-step route (A/B measurements, bisecting)
+        # tileable sampling: (wrap_y, wrap_x) -- on a wrapped axis the sample's borders wrap around, i.e. the network is
+        # evaluated as if every convolution padded circularly there (the reference: padding_mode='circular' on its
+        # nn.Conv2d's).  The convolution kernels only know zero padding: the image is extended by a wrapped halo of
+        # _lib.TILE_HALO pixels (the network's receptive radius) and the centre is kept.  A sampling option: training is
+        # unchanged.
+        self.tile = (False, False)
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -631,6 +639,24 @@ class MultiScaleGaussianDiffusion(nn.Module):
             cache[key] = tab
         return tab
 
+    def _tile_halo(self) -> Tuple[int, int]:
+        """(halo_y, halo_x) in pixels of the `tile` setting: _lib.TILE_HALO on a wrapped axis, 0 elsewhere."""
+        wy, wx = self.tile
+        return (_lib.TILE_HALO if wy else 0, _lib.TILE_HALO if wx else 0)
+
+    @staticmethod
+    def _wrap_pad(t: torch.Tensor, hy: int, hx: int) -> torch.Tensor:
+        """(..., H, W) -> (..., H + 2 hy, W + 2 hx): the circular pad of the last two axes (sinddm_wrap_halo)."""
+        lib = _lib.load()
+        t = t.contiguous()
+        if t.dtype != torch.float32:
+            raise _lib.SinddmError("fp32 only")
+        H, W = int(t.shape[-2]), int(t.shape[-1])
+        ext = torch.empty(tuple(t.shape[:-2]) + (H + 2 * hy, W + 2 * hx), dtype=t.dtype, device=t.device)
+        _lib.check(lib.sinddm_wrap_halo(_lib.ptr(ext), _lib.ptr(t), t.numel() // (H * W), H, W, hy, hx,
+                                        _lib.stream_ptr(t.device)), "sinddm_wrap_halo")
+        return ext
+
     def _run_steps(self, img: torch.Tensor, s: int, t_seq) -> torch.Tensor:
         """The reverse steps `t_seq` of scale s (the loop bodies of models.py:477-485,536-546).  Production path: ONE
         library call for the whole run (sinddm_sample_chain_ex) -- the per-step scalars come from a prebuilt table, the
@@ -639,7 +665,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
         edit maps go to the fused step kernels (`chain_guided = False` sends it down the step-by-step route).  Injected
         noise (`noise_fn`) takes the step-by-step path, which the parity fixtures pin, unless `chain_noise` is set: then
         the same draws, fetched in the same order, are handed to the chain call as buffers of at most
-        CHAIN_NOISE_BYTES.  CLIP guidance, intermediate dumps, foreign denoisers and CPU tensors are step by step."""
+        CHAIN_NOISE_BYTES.  CLIP guidance, intermediate dumps, foreign denoisers and CPU tensors are step by step.
+        With `tile` set the run works on the sample extended by the wrapped halo (sinddm_sample_chain_tile: the state,
+        x-tilde, the edit maps and the noise buffers all have the extended size) and returns the centre; the in-kernel
+        draws are keyed on the extended index, so a tiled and a plain run of one seed are unrelated.  The step-by-step
+        route extends each network input instead (`_eps`) and steps the centre: it is the cross-check of the tiled chain."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
         roi = bool(self.roi_guided_sampling and s < self.n_scales - 1)     # models.py:430-431
@@ -654,7 +684,10 @@ class MultiScaleGaussianDiffusion(nn.Module):
             return img
         lib = _lib.load()
         net = self.denoise_fn
-        x = img.contiguous().clone()
+        hy, hx = self._tile_halo()
+        tiled = bool(hy or hx)
+        Hc, Wc = int(img.shape[2]), int(img.shape[3])              # the sample's own size; H, W below: the buffers' size
+        x = self._wrap_pad(img, hy, hx) if tiled else img.contiguous().clone()
         x_alt = torch.empty_like(x)
         eps = torch.empty_like(x)
         B, Cc, H, W = x.shape
@@ -667,16 +700,18 @@ class MultiScaleGaussianDiffusion(nn.Module):
             xt = self.img_prev_upsample
             if xt is None:
                 raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
-            if xt.shape != x.shape or xt.dtype != x.dtype or xt.device != x.device:
+            if xt.shape != img.shape or xt.dtype != x.dtype or xt.device != x.device:
                 # (the library takes raw pointers: a mismatching x-tilde would be read out of bounds)
                 raise _lib.SinddmError(f"img_prev_upsample {tuple(xt.shape)} {xt.dtype} {xt.device} does not match the "
-                                       f"running sample {tuple(x.shape)} {x.dtype} {x.device}")
-            xt = xt.contiguous()
+                                       f"running sample {tuple(img.shape)} {x.dtype} {x.device}")
+            xt = self._wrap_pad(xt, hy, hx) if tiled else xt.contiguous()
         packed = net.packed_weights()
         ws = _workspace(x.device, lib.sinddm_workspace_bytes(net.dim, B, H, W))
         opts = _lib.ChainOpts()
         if roi:
-            ew, ec = self.roi_edit_maps(s, H, W, x.device)                 # (cached on self: alive for the call)
+            ew, ec = self.roi_edit_maps(s, Hc, Wc, x.device)               # (cached on self: alive for the call)
+            if tiled:                                                      # (locals of this frame: alive for the call)
+                ew, ec = self._wrap_pad(ew, hy, hx), self._wrap_pad(ec, hy, hx)
             opts.edit_w, opts.edit_c = _lib.ptr(ew), _lib.ptr(ec)
         aux = _aux_stream(x.device) if self.two_streams else None
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
@@ -685,12 +720,14 @@ class MultiScaleGaussianDiffusion(nn.Module):
             nonlocal x, x_alt
             opts.noise = _lib.ptr(noise)
             in_alt = C.c_int(0)
-            _lib.check(lib.sinddm_sample_chain_ex(
-                _lib.ptr(net.flat_params), _lib.ptr(packed), _lib.ptr(x), _lib.ptr(x_alt), _lib.ptr(eps), _lib.ptr(xt),
-                C.cast(C.addressof(coefs) + i0 * C.sizeof(_lib.StepCoefs), C.POINTER(_lib.StepCoefs)),
-                C.cast(C.addressof(tl) + i0 * C.sizeof(C.c_int), C.POINTER(C.c_int)), k, float(s), seed, 0, net.dim_arg,
-                B, H, W, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts)),
-                "sinddm_sample_chain_ex")
+            args = (_lib.ptr(net.flat_params), _lib.ptr(packed), _lib.ptr(x), _lib.ptr(x_alt), _lib.ptr(eps), _lib.ptr(xt),
+                    C.cast(C.addressof(coefs) + i0 * C.sizeof(_lib.StepCoefs), C.POINTER(_lib.StepCoefs)),
+                    C.cast(C.addressof(tl) + i0 * C.sizeof(C.c_int), C.POINTER(C.c_int)), k, float(s), seed, 0, net.dim_arg,
+                    B, Hc, Wc, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts))
+            if tiled:
+                _lib.check(lib.sinddm_sample_chain_tile(*args, hy, hx), "sinddm_sample_chain_tile")
+            else:
+                _lib.check(lib.sinddm_sample_chain_ex(*args), "sinddm_sample_chain_ex")
             if in_alt.value:
                 x, x_alt = x_alt, x
 
@@ -701,20 +738,32 @@ class MultiScaleGaussianDiffusion(nn.Module):
             per = max(1, int(CHAIN_NOISE_BYTES) // (x.numel() * x.element_size()))
             for i0 in range(0, n, per):
                 k = min(per, n - i0)
-                noise = torch.empty((k,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+                # (tiled: the draws have the sample's own size and fill the centre of their slot; the halo of a slot is
+                # never used -- the halo of a step's output is overwritten with its wrapped centre)
+                noise = (torch.zeros if tiled else torch.empty)((k,) + tuple(x.shape), dtype=x.dtype, device=x.device)
                 for j in range(k):
-                    noise[j].copy_(self._draw("step", x.shape, s, t_seq[i0 + j], x.device))
+                    noise[j][:, :, hy:hy + Hc, hx:hx + Wc].copy_(self._draw("step", img.shape, s, t_seq[i0 + j], x.device))
                 chain(i0, k, 0, noise)
-            return x
+            return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
         # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
         # sample, seeding only the CUDA generator (torch.cuda.manual_seed) does not
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
         if self.draw_log is not None:
-            self.draw_log.append(("chain", s, seed, list(t_seq)))
+            # (tiled: draw i of the run is sinddm_normal_fill(seed, i) over the EXTENDED (B,3,H+2hy,W+2hx) tensor)
+            self.draw_log.append(("chain_tile", s, seed, list(t_seq), (hy, hx)) if tiled else ("chain", s, seed, list(t_seq)))
         chain(0, n, seed, None)
-        return x
+        return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
 
     def _eps(self, x, t_dev, t_host, s):
+        hy, hx = self._tile_halo()
+        if hy or hx:
+            # tileable sampling, step by step: the zero-padded network on the input extended by its wrapped halo equals,
+            # on the centre, the circularly padded network (the halo is the receptive radius)
+            Hc, Wc = int(x.shape[-2]), int(x.shape[-1])
+            return self._eps_plain(self._wrap_pad(x, hy, hx), t_dev, t_host, s)[:, :, hy:hy + Hc, hx:hx + Wc].contiguous()
+        return self._eps_plain(x, t_dev, t_host, s)
+
+    def _eps_plain(self, x, t_dev, t_host, s):
         if isinstance(self.denoise_fn, SinDDMNet):
             return self.denoise_fn.infer(x, None if t_dev is None else t_dev, int(t_host), float(s))
         if t_dev is None:
@@ -834,12 +883,18 @@ class MultiScaleGaussianDiffusion(nn.Module):
         return image_size
 
     def upsample(self, img: torch.Tensor, size) -> torch.Tensor:
-        """F.interpolate(img, size, mode='bilinear') on the HIP kernel (models.py:567)."""
+        """F.interpolate(img, size, mode='bilinear') on the HIP kernel (models.py:567); on an axis `tile` wraps, the
+        interpolation of the image's periodic continuation (sinddm_upsample_bilinear_wrap)."""
         lib = _lib.load()
         img = img.contiguous()
         B, Cc, h, w = img.shape
         H, W = int(size[0]), int(size[1])
         out = torch.empty((B, Cc, H, W), dtype=img.dtype, device=img.device)
+        if any(self.tile):
+            _lib.check(lib.sinddm_upsample_bilinear_wrap(_lib.ptr(img), _lib.ptr(out), B * Cc, h, w, H, W,
+                                                         int(bool(self.tile[0])), int(bool(self.tile[1])),
+                                                         _lib.stream_ptr(img.device)), "sinddm_upsample_bilinear_wrap")
+            return out
         _lib.check(lib.sinddm_upsample_bilinear(_lib.ptr(img), _lib.ptr(out), B * Cc, h, w, H, W,
                                                 _lib.stream_ptr(img.device)), "sinddm_upsample_bilinear")
         return out
