@@ -214,6 +214,46 @@ int sinddm_sample_chain_tile(const float* params, const float* packed, float* x,
                              void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
                              const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x);
 
+/* ---- known-region conditioning: inpainting / outpainting inside the step ------------------------ */
+/* Some pixels of the sample are KNOWN (a mask m in [0,1], 1 = known, and the known image k0 of this scale) and the rest is
+ * generated to fit them: RePaint-style replacement (no reference line: the reference's harmonization only pastes the
+ * original back after the last step).  After every reverse step t -> t-1 the known pixels are overwritten with the
+ * forward-diffused known image of the noise level t-1, inside the step kernel.  Per element (p pixel, ch channel, `plain`
+ * what the step writes without the option, z the step's own N(0,1) draw -- one draw per element serves both branches):
+ *     target = mode == 1 ? gamma_tm1 * x_tilde + (1 - gamma_tm1) * k0[ch][p] : k0[ch][p]     (models.py:583-585 at t-1)
+ *     kept   = keep_a * target + keep_b * z                                                  (models.py:574-575 at t-1)
+ *     out    = m[p] * kept + (1 - m[p]) * plain               exact at m == 0 (`plain`) and at m == 1 (`kept`)
+ * keep_a / keep_b = sqrt_alphas_cumprod[t-1] / sqrt_one_minus_alphas_cumprod[t-1] for t > 0 and (1, 0) for t == 0.  The keep
+ * target is not clamped.  z is drawn when sigma != 0 OR keep_b != 0.  An ROI edit may be on as well: it acts on x_recon,
+ * the keep on the output.  RePaint's resampling jumps (stepping back up in t and down again) are NOT part of this. */
+typedef struct sinddm_keep_opts {
+    const float* mask;   /* device, HW floats, 16-byte aligned        */
+    const float* x0;     /* device, 3*HW floats, 16-byte aligned      */
+    const float* ab;     /* HOST, 2*n_steps floats: (keep_a, keep_b) per step */
+} sinddm_keep_opts;
+
+/* sinddm_sample_chain_tile with known-region conditioning on EVERY step of the call; keep = NULL (or mask = x0 = NULL: `ab`
+ * is then ignored) is sinddm_sample_chain_tile itself: the same launches, the same numbers.  mask / x0 are shared by all B
+ * samples; under a halo they have the EXTENDED size and must ARRIVE wrapped, like opts->edit_w / edit_c.  Step i of the
+ * call uses (ab[2 i], ab[2 i + 1]).  With opts->noise a step reads its slot when sigma != 0 or keep_b != 0.  The two-stream
+ * split, the workspace and the results with / without aux_stream do not depend on `keep`.
+ * SINDDM_E_BADARG (before any device work): mask without x0 (or the reverse), maps without ab, a device pointer that is
+ * not 16-byte aligned; SINDDM_E_BADSHAPE: 3*(H + 2 halo_y)*(W + 2 halo_x) >= 2^31 (the maps are indexed with ints). */
+int sinddm_sample_chain_keep(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                             const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                             int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                             void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                             const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                             const sinddm_keep_opts* keep /*host, may be NULL*/);
+
+/* sinddm_reverse_step / sinddm_reverse_step_edit with the same replacement, noise supplied by the caller: the step-by-step
+ * route and the cross-check of the chain call.  keep_m: HW floats, keep_x0: C*HW floats (both required, shared by all B
+ * samples); edit_w / edit_c: both or neither. */
+int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                             const sinddm_step_coefs* coefs /*host*/, const float* edit_w, const float* edit_c /*both or neither, may be NULL*/,
+                             const float* keep_m, const float* keep_x0, float keep_a, float keep_b,
+                             int B, int C, int HW, void* stream);
+
 /* ---- training ------------------------------------------------------------------------------ */
 /* Scratch for one training forward+backward of a (B,3,H,W) batch: saved activations (about
  * 1843 floats per pixel per sample at dim=160) + backward scratch. */

@@ -16,6 +16,10 @@ ranks as independent chains and all-gathered (RCCL over xGMI):
 `--roi_target y x h w` and `--roi_bbs y x h w [y x h w ...]` (finest-scale pixel coordinates).
 `--tile {none,x,y,xy}` (no reference flag) samples with borders that wrap around on the named axes: tileable textures,
 cylindrical panoramas (`--tile x --scale_mul 1 4`).  All five modes honour it.
+`inpaint` and `outpaint` (no reference modes) keep some pixels exactly and generate the rest to fit, by replacing the
+known region after every reverse step inside the step kernels: `--mode inpaint --mask_path FILE [--soft_mask]` fills the
+black part of the mask (white = keep the training image's pixel; the file is brought to the finest scale's size);
+`--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.
 The CLIP-guided modes (clip_content, clip_style_*, clip_roi; main.py:153-255) are not wired to the command line: CLIP
 itself is outside this build.  Their drivers exist (`MultiscaleTrainer.clip_sampling` / `clip_roi_sampling`, the guidance
 branch of `p_mean_variance`) and take any scorer with the reference's ClipExtractor interface.
@@ -48,6 +52,8 @@ _FLAGS = [
     ("device_num", 0, int, None), ("omega", 0, float, None), ("loss_factor", 1, float, None),
     # non-interactive stand-ins for the cv2.selectROI dialogs of the reference's `roi` mode
     ("roi_target", None, int, "+"), ("roi_bbs", None, int, "+"),
+    # known-region sampling: the mask file of `inpaint`, the placement of the training image on the canvas of `outpaint`
+    ("mask_path", None, str, None), ("anchor", [0.5, 0.5], float, 2),
 ]
 
 
@@ -61,6 +67,7 @@ def build_parser():
     p.add_argument("--sample_limited_t", action="store_true")
     # no reference flag (there: padding_mode='circular' on the nn.Conv2d's): borders that wrap around on the x axis (360-degree
     # panoramas), the y axis or both (seamlessly tileable textures) -- MultiScaleGaussianDiffusion.tile
+    p.add_argument("--soft_mask", action="store_true")    # inpaint: blend with the area-averaged mask at coarse scales
     p.add_argument("--tile", choices=("none", "x", "y", "xy"), default="none")
     return p
 
@@ -146,10 +153,22 @@ def main():
         bbs = [list(args.roi_bbs[i:i + 4]) for i in range(0, len(args.roi_bbs), 4)]
         trainer.roi_guided_sampling(custom_t_list=sample_t_list, target_roi=list(args.roi_target), roi_bb_list=bbs,
                                     save_unbatched=True, batch_size=args.sample_batch_size, scale_mul=scale_mul)
+    elif args.mode == 'inpaint':
+        if not args.mask_path:
+            raise SystemExit("--mode inpaint needs --mask_path FILE (white = keep the training image's pixel, black = fill)")
+        import numpy as np
+        from PIL import Image
+        h, w = ms_diffusion.image_sizes[n_scales - 1]
+        known = np.asarray(Image.open(args.mask_path).convert("L").resize((w, h), Image.NEAREST)) > 127
+        trainer.inpaint(torch.from_numpy(known.astype(np.float32)), batch_size=args.sample_batch_size,
+                        hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True)
+    elif args.mode == 'outpaint':
+        trainer.outpaint(scale_mul, anchor=tuple(args.anchor), batch_size=args.sample_batch_size,
+                         custom_t_list=sample_t_list, save_unbatched=True)
     else:
         raise NotImplementedError(
-            f"mode {args.mode!r}: train, sample, style_transfer, harmonization and roi are built for MI355X; the CLIP-guided "
-            "modes of the reference need CLIP autograd and are out of scope (SURVEY.md section 8)")
+            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint and outpaint are built for MI355X; "
+            "the CLIP-guided modes of the reference need CLIP autograd and are out of scope (SURVEY.md section 8)")
     if world > 1:
         td.destroy_process_group()
 

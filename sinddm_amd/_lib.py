@@ -24,6 +24,7 @@ ABI_SYMBOLS = (
     "sinddm_net_forward_train", "sinddm_net_backward", "sinddm_l1_loss_fwd_bwd", "sinddm_adam_ema_step",
     "sinddm_cond_embed", "sinddm_cond_stride", "sinddm_sample_chain", "sinddm_sample_chain2", "sinddm_sample_chain_ex",
     "sinddm_normal_fill", "sinddm_wrap_halo", "sinddm_upsample_bilinear_wrap", "sinddm_sample_chain_tile",
+    "sinddm_sample_chain_keep", "sinddm_reverse_step_keep",
 )
 
 
@@ -45,6 +46,12 @@ class StepCoefs(C.Structure):
 class ChainOpts(C.Structure):
     """Mirror of `sinddm_chain_opts` (include/sinddm_hip.h): device pointers or None."""
     _fields_ = [("edit_w", C.c_void_p), ("edit_c", C.c_void_p), ("noise", C.c_void_p)]
+
+
+class KeepOpts(C.Structure):
+    """Mirror of `sinddm_keep_opts` (include/sinddm_hip.h): `mask` / `x0` device pointers, `ab` a HOST array of
+    (keep_a, keep_b) per step of the call."""
+    _fields_ = [("mask", C.c_void_p), ("x0", C.c_void_p), ("ab", C.POINTER(C.c_float))]
 
 
 class SinddmError(RuntimeError):
@@ -92,6 +99,10 @@ def load() -> C.CDLL:
                                        i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts)]),
         "sinddm_sample_chain_tile": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
                                          i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i]),
+        "sinddm_sample_chain_keep": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
+                                         i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i,
+                                         C.POINTER(KeepOpts)]),
+        "sinddm_reverse_step_keep": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, p, p, f, f, i, i, i, p]),
         "sinddm_wrap_halo": (i, [p, p, i, i, i, i, i, p]),
         "sinddm_upsample_bilinear_wrap": (i, [p, p, i, i, i, i, i, i, i, p]),
         "sinddm_normal_fill": (i, [p, i64, C.c_uint64, C.c_uint64, p]),

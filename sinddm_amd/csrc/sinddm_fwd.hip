@@ -775,24 +775,42 @@ __device__ __forceinline__ float reverse_step_mean(const sinddm_step_coefs& k, f
     return k.clip ? fminf(fmaxf(xp, -1.0f), 1.0f) : xp;                           // models.py:347-348
 }
 
+// KEEP: known-region conditioning (inpainting / outpainting; RePaint-style replacement, no reference line).  Where the mask
+// m(p) is 1 the step's output is replaced by a sample of q(x_{t-1} | known image k0) -- SinDDM's blurred forward process
+// at t-1 -- built from the SAME draw z the step uses (one Gaussian per pixel in either branch); in between the two are
+// blended.  `plain` is what the step writes without the option, `xb` x-tilde (0 in mode 0), ka / kb the forward scalars
+// sqrt(ac[t-1]) / sqrt(1 - ac[t-1]) ((1, 0) at t == 0).  Written so that m == 0 gives `plain` and m == 1 gives `kept`
+// exactly; the keep target is not clamped.
+__device__ __forceinline__ float keep_blend(const sinddm_step_coefs& k, float plain, float z, float xb, float m, float k0,
+                                            float ka, float kb) {
+    const float target = k.mode == 1 ? k.gamma_tm1 * xb + (1.0f - k.gamma_tm1) * k0 : k0;
+    const float kept = ka * target + kb * z;
+    return m * kept + (1.0f - m) * plain;
+}
+
 // EDIT: the predicted clean image is replaced by  w(p) * x_recon + c(ch, p)  before the re-blur mix / clamps --
 // the ROI-guided sampling of the reference (models.py:291-298,430-431) written as a per-pixel affine map
 // (sequential `eta*patch + (1-eta)*x` blends over possibly overlapping boxes compose into one such map).
-template <bool EDIT>
+// KEEP: see keep_blend; km = the mask (hw floats), kx = the known image (chw floats), both shared by all samples like the
+// edit maps.  EDIT and KEEP may be on together: the edit acts on x_recon, the keep on the output.
+template <bool EDIT, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                            const float* __restrict__ xtil, const float* __restrict__ z,
                                                            float* __restrict__ out, sinddm_step_coefs k, long long n,
                                                            const float* __restrict__ ew, const float* __restrict__ ec,
-                                                           int chw, int hw) {
+                                                           int chw, int hw, const float* __restrict__ km,
+                                                           const float* __restrict__ kx, float ka, float kb) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float w = 1.0f, c = 0.0f;
+        const int q = (EDIT || KEEP) ? (int)(i % chw) : 0;
         if (EDIT) {
-            const int q = (int)(i % chw);
             w = ew[q % hw];
             c = ec[q];
         }
-        const float mean = reverse_step_mean(k, xt[i], eps[i], k.mode != 0 ? xtil[i] : 0.0f, w, c, EDIT);
-        out[i] = mean + k.sigma * z[i];                                           // models.py:459
+        const float xb = k.mode != 0 ? xtil[i] : 0.0f;
+        const float mean = reverse_step_mean(k, xt[i], eps[i], xb, w, c, EDIT);
+        const float o = mean + k.sigma * z[i];                                    // models.py:459
+        out[i] = KEEP ? keep_blend(k, o, z[i], xb, km[q % hw], kx[q], ka, kb) : o;
     }
 }
 
@@ -824,23 +842,26 @@ __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned
     z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
 }
 
-// The three tails of a sampler-run step share two compile-time options (sinddm_sample_chain_ex); the plain instantiations
-// <false, false> are the kernels the chain always ran:
-//   EDIT   the ROI edit of reverse_step_kernel<true>: w = ew[p], c = ec[ch * HW + p], shared by all samples
+// The three tails of a sampler-run step share three compile-time options (sinddm_sample_chain_ex / _keep); the plain
+// instantiations <false, false, false> are the kernels the chain always ran:
+//   EDIT   the ROI edit of reverse_step_kernel<true, *>: w = ew[p], c = ec[ch * HW + p], shared by all samples
 //   NOISE  z is READ from `nz` (this step's B_total*3*HW recorded draws) at the element's flat index inside the whole batch
-//          instead of drawn from Philox; steps with sigma == 0 read nothing
-template <bool EDIT, bool NOISE>
+//          instead of drawn from Philox; steps with sigma == 0 (and, under KEEP, kb == 0) read nothing
+//   KEEP   the known-region replacement of keep_blend on the step's output: m = km[p], k0 = kx[ch * HW + p], shared by all
+//          samples and read like the edit maps; z is drawn (or read) when sigma != 0 OR kb != 0
+template <bool EDIT, bool NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                const float* __restrict__ xtil, float* __restrict__ out,
                                                                sinddm_step_coefs k, long long n, unsigned long long seed,
                                                                unsigned long long step, const float* __restrict__ ew,
                                                                const float* __restrict__ ec, const float* __restrict__ nz,
-                                                               int chw, int hw) {
+                                                               int chw, int hw, const float* __restrict__ km,
+                                                               const float* __restrict__ kx, float ka, float kb) {
     const long long n4 = (n + 3) >> 2;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         const long long i0 = q << 2;
-        if (k.sigma != 0.0f) {
+        if (k.sigma != 0.0f || (KEEP && kb != 0.0f)) {
             if (NOISE) {                        // (a step's slice starts at a multiple of n floats: not 16-byte aligned in general)
                 for (int j = 0; j < 4 && i0 + j < n; ++j) z[j] = nz[i0 + j];
             } else {
@@ -856,6 +877,15 @@ __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __re
                 r = r + 1 == chw ? 0 : r + 1;
             }
         }
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
+        if (KEEP) {
+            int r = (int)(i0 % chw);
+            for (int j = 0; j < 4 && i0 + j < n; ++j) {
+                m[j] = km[r % hw];
+                k0[j] = kx[r];
+                r = r + 1 == chw ? 0 : r + 1;
+            }
+        }
         if (i0 + 3 < n) {
             const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
             const f32x4 e = *reinterpret_cast<const f32x4*>(eps + i0);
@@ -863,12 +893,17 @@ __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __re
             if (k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
             f32x4 o;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = reverse_step_mean(k, x[j], e[j], xb[j], w[j], c[j], EDIT) + k.sigma * z[j];
+            for (int j = 0; j < 4; ++j) {
+                o[j] = reverse_step_mean(k, x[j], e[j], xb[j], w[j], c[j], EDIT) + k.sigma * z[j];
+                if (KEEP) o[j] = keep_blend(k, o[j], z[j], xb[j], m[j], k0[j], ka, kb);
+            }
             *reinterpret_cast<f32x4*>(out + i0) = o;
         } else {
-            for (int j = 0; i0 + j < n; ++j)
-                out[i0 + j] = reverse_step_mean(k, xt[i0 + j], eps[i0 + j], k.mode != 0 ? xtil[i0 + j] : 0.f, w[j], c[j], EDIT) +
-                              k.sigma * z[j];
+            for (int j = 0; i0 + j < n; ++j) {
+                const float xb = k.mode != 0 ? xtil[i0 + j] : 0.f;
+                const float o = reverse_step_mean(k, xt[i0 + j], eps[i0 + j], xb, w[j], c[j], EDIT) + k.sigma * z[j];
+                out[i0 + j] = KEEP ? keep_blend(k, o, z[j], xb, m[j], k0[j], ka, kb) : o;
+            }
         }
     }
 }
@@ -876,8 +911,9 @@ __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __re
 // final 1x1 conv (-> eps) + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
 // four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
 // path): eps never goes to memory.  EDIT / NOISE: a thread's four pixels are contiguous and 16-byte aligned in the maps and
-// in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller), so both are read as f32x4.
-template <bool EDIT, bool NOISE>
+// in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller), so both are read as f32x4; so are
+// the KEEP mask and known image.
+template <bool EDIT, bool NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const float* __restrict__ a, const float* __restrict__ w,
                                                                       const float* __restrict__ bias,
                                                                       const float* __restrict__ xt,
@@ -886,7 +922,9 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
                                                                       unsigned long long seed, unsigned long long step, int b0,
                                                                       const float* __restrict__ ew,
                                                                       const float* __restrict__ ec,
-                                                                      const float* __restrict__ nz) {
+                                                                      const float* __restrict__ nz,
+                                                                      const float* __restrict__ km,
+                                                                      const float* __restrict__ kx, float ka, float kb) {
     const int b = blockIdx.y;
     const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (p >= HW) return;
@@ -901,12 +939,14 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
     }
     f32x4 mw{1.f, 1.f, 1.f, 1.f};
     if (EDIT) mw = *reinterpret_cast<const f32x4*>(ew + p);
+    f32x4 mk{0.f, 0.f, 0.f, 0.f};
+    if (KEEP) mk = *reinterpret_cast<const f32x4*>(km + p);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + p;
         const long long ig = i0 + (long long)b0 * 3 * HW;           // flat index inside the whole batch: the noise key
         float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k.sigma != 0.0f) {
+        if (k.sigma != 0.0f || (KEEP && kb != 0.0f)) {
             if (NOISE) {
                 const f32x4 zv = *reinterpret_cast<const f32x4*>(nz + ig);
                 z[0] = zv[0]; z[1] = zv[1]; z[2] = zv[2]; z[3] = zv[3];
@@ -922,6 +962,11 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = reverse_step_mean(k, x[j], e[c][j], xb[j], mw[j], mc[j], EDIT) + k.sigma * z[j];
+        if (KEEP) {
+            const f32x4 k0 = *reinterpret_cast<const f32x4*>(kx + (size_t)c * HW + p);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = keep_blend(k, o[j], z[j], xb[j], mk[j], k0[j], ka, kb);
+        }
         *reinterpret_cast<f32x4*>(out + i0) = o;
     }
 }
@@ -930,13 +975,13 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
 // the same for padded workspace rows (pitch Wp, true width W): a thread owns a padded quad of a row; the boundary tensors
 // (x_t, x-tilde, x_{t-1}) are plain, so its up to four pixels sit at an unaligned flat index and their N(0,1) draws -- keyed
 // on the FLAT quad index like everywhere else -- come from up to two Philox calls.  EDIT / NOISE: the maps and the recorded
-// draws are plain tensors as well: scalar reads at the unaligned flat index, like x_t.
-template <bool EDIT, bool NOISE>
+// draws are plain tensors as well: scalar reads at the unaligned flat index, like x_t; the KEEP maps likewise.
+template <bool EDIT, bool NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
     const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ xt,
     const float* __restrict__ xtil, float* __restrict__ out, sinddm_step_coefs k, int C, int H, int W, int Wp,
     unsigned long long seed, unsigned long long step, int b0, const float* __restrict__ ew, const float* __restrict__ ec,
-    const float* __restrict__ nz) {
+    const float* __restrict__ nz, const float* __restrict__ km, const float* __restrict__ kx, float ka, float kb) {
     const int b = blockIdx.y;
     const int qpr = Wp >> 2;
     const int q = blockIdx.x * 256 + threadIdx.x;
@@ -954,13 +999,14 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
         e[2] += w[2 * C + c] * v;
     }
     const int nv = W - x;                                   // valid pixels of the quad (>= 1)
+    const bool draw = k.sigma != 0.0f || (KEEP && kb != 0.0f);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + (long long)y * W + x;
         const long long ig = i0 + (long long)b0 * 3 * HW;          // flat index inside the whole batch: the noise key
         const int r0 = (int)(ig & 3);
         float za[4] = {0.f, 0.f, 0.f, 0.f}, zb[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!NOISE && k.sigma != 0.0f) {
+        if (!NOISE && draw) {
             philox_normal4(seed, step, (unsigned long long)(ig >> 2), za);
             if (r0 != 0) philox_normal4(seed, step, (unsigned long long)(ig >> 2) + 1ull, zb);
         }
@@ -972,15 +1018,16 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
                 z = r0 == 1 ? z8[j + 1] : z;
                 z = r0 == 2 ? z8[j + 2] : z;
                 z = r0 == 3 ? z8[j + 3] : z;
-                if (NOISE) z = k.sigma != 0.0f ? nz[ig + j] : 0.f;
+                if (NOISE) z = draw ? nz[ig + j] : 0.f;
                 float mw = 1.f, mc = 0.f;
+                const int pp = y * W + x + j;
                 if (EDIT) {
-                    const int pp = y * W + x + j;
                     mw = ew[pp];
                     mc = ec[(size_t)c * HW + pp];
                 }
                 const float xb = k.mode != 0 ? xtil[i0 + j] : 0.f;
-                out[i0 + j] = reverse_step_mean(k, xt[i0 + j], e[c][j], xb, mw, mc, EDIT) + k.sigma * z;
+                const float o = reverse_step_mean(k, xt[i0 + j], e[c][j], xb, mw, mc, EDIT) + k.sigma * z;
+                out[i0 + j] = KEEP ? keep_blend(k, o, z, xb, km[pp], kx[(size_t)c * HW + pp], ka, kb) : o;
             }
         }
     }
@@ -1139,19 +1186,28 @@ struct ChainStep {
     const float* edit_w;   // ROI edit maps (HW / 3*HW floats, shared by the batch) or both NULL
     const float* edit_c;
     const float* noise;    // this step's recorded draws for the WHOLE batch (B_total*3*HW floats) or NULL -> Philox
+    const float* keep_m;   // known-region mask / known image (HW / 3*HW floats, shared by the batch) or both NULL
+    const float* keep_x0;
+    float keep_a, keep_b;  // this step's forward scalars of the known image (sinddm_keep_opts::ab)
 };
 
-// one of the four instantiations of a tail kernel: bit 0 = EDIT, bit 1 = NOISE
-#define SINDDM_TAIL_LAUNCH(KERNEL, variant, grid, st, ...)                                                        \
-    do {                                                                                                         \
-        switch (variant) {                                                                                       \
-            case 0: hipLaunchKernelGGL((KERNEL<false, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-            case 1: hipLaunchKernelGGL((KERNEL<true, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;       \
-            case 2: hipLaunchKernelGGL((KERNEL<false, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;       \
-            default: hipLaunchKernelGGL((KERNEL<true, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;       \
-        }                                                                                                        \
+// one of the eight instantiations of a tail kernel: bit 0 = EDIT, bit 1 = NOISE, bit 2 = KEEP
+#define SINDDM_TAIL_LAUNCH(KERNEL, variant, grid, st, ...)                                                             \
+    do {                                                                                                              \
+        switch (variant) {                                                                                            \
+            case 0: hipLaunchKernelGGL((KERNEL<false, false, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
+            case 1: hipLaunchKernelGGL((KERNEL<true, false, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;     \
+            case 2: hipLaunchKernelGGL((KERNEL<false, true, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;     \
+            case 3: hipLaunchKernelGGL((KERNEL<true, true, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
+            case 4: hipLaunchKernelGGL((KERNEL<false, false, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;     \
+            case 5: hipLaunchKernelGGL((KERNEL<true, false, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
+            case 6: hipLaunchKernelGGL((KERNEL<false, true, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
+            default: hipLaunchKernelGGL((KERNEL<true, true, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
+        }                                                                                                             \
     } while (0)
-static int tail_variant(const float* edit_w, const float* noise) { return (edit_w ? 1 : 0) | (noise ? 2 : 0); }
+static int tail_variant(const float* edit_w, const float* noise, const float* keep_m) {
+    return (edit_w ? 1 : 0) | (noise ? 2 : 0) | (keep_m ? 4 : 0);
+}
 
 int conv3x3_path(int cout, int cin, int coblks, int B, int H, int W) {
     if (!wino_enabled() || cout % 4 != 0) return 0;
@@ -1371,9 +1427,10 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     if (padded) {
         const unsigned gx = (unsigned)((H * (Wp / 4) + 255) / 256);
         if (cs && cs->x_next)
-            SINDDM_TAIL_LAUNCH(final_conv_reverse_step_pitch_kernel, tail_variant(cs->edit_w, cs->noise), dim3(gx, B), st, cur,
-                               params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, H, W, Wp,
-                               cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise);
+            SINDDM_TAIL_LAUNCH(final_conv_reverse_step_pitch_kernel, tail_variant(cs->edit_w, cs->noise, cs->keep_m), dim3(gx, B),
+                               st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, H, W,
+                               Wp, cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise, cs->keep_m, cs->keep_x0,
+                               cs->keep_a, cs->keep_b);
         else
             hipLaunchKernelGGL(final_conv1x1_pitch_kernel, dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w,
                                params + P.fin_b, out, P.half, H, W, Wp);
@@ -1381,9 +1438,10 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         return 0;
     }
     if (cs && cs->x_next && HW % 4 == 0) {
-        SINDDM_TAIL_LAUNCH(final_conv_reverse_step_kernel, tail_variant(cs->edit_w, cs->noise), dim3((HW / 4 + 255) / 256, B),
-                           st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, HW,
-                           cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise);
+        SINDDM_TAIL_LAUNCH(final_conv_reverse_step_kernel, tail_variant(cs->edit_w, cs->noise, cs->keep_m),
+                           dim3((HW / 4 + 255) / 256, B), st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next,
+                           cs->coefs, P.half, HW, cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise, cs->keep_m,
+                           cs->keep_x0, cs->keep_a, cs->keep_b);
         SINDDM_LAUNCH_CHECK();
         return 0;
     }
@@ -1494,8 +1552,8 @@ int sinddm_reverse_step(const float* x_t, const float* eps, const float* x_tilde
     if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
     long long bx = (n + 255) / 256;
     if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL(reverse_step_kernel<false>, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, eps, x_tilde, noise, out, *coefs, (long long)n, nullptr, nullptr, 1, 1);
+    hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, eps, x_tilde, noise, out, *coefs, (long long)n, nullptr, nullptr, 1, 1, nullptr, nullptr, 1.0f, 0.0f);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }
@@ -1521,14 +1579,16 @@ int sinddm_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t stream_id,
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
-// The body of sinddm_sample_chain_ex (halo_y = halo_x = 0) and of sinddm_sample_chain_tile.  Hc x Wc is the CENTRE size; the
+// The body of sinddm_sample_chain_ex (halo_y = halo_x = 0), of sinddm_sample_chain_tile (keep = NULL) and of
+// sinddm_sample_chain_keep.  Hc x Wc is the CENTRE size; the
 // steps run on the extended shape H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo,
 // the halo of every step's output is refreshed from its centre (wrap_halo_launch, per half-batch on its own stream), and
 // that of `x` once on entry: the zero padding of the convolutions then never reaches the centre (SINDDM_TILE_HALO).
 static int sample_chain_impl(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                              uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
-                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
+                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
+                             const sinddm_keep_opts* keep) {
     if (!params || !packed || !x || !x_alt || !eps || !coefs || !t_list || !ws || n_steps < 0 || B <= 0 || Hc <= 0 || Wc <= 0)
         return SINDDM_E_BADARG;
     const bool tiled = halo_y != 0 || halo_x != 0;
@@ -1536,10 +1596,15 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     const float* edit_w = opts ? opts->edit_w : nullptr;
     const float* edit_c = opts ? opts->edit_c : nullptr;
     const float* noise = opts ? opts->noise : nullptr;
-    if ((edit_w == nullptr) != (edit_c == nullptr)) return SINDDM_E_BADARG;
-    if (edit_w && (long long)CHANNELS * H * W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;      // (the maps are indexed with ints)
+    const float* keep_m = keep ? keep->mask : nullptr;
+    const float* keep_x0 = keep ? keep->x0 : nullptr;
+    const float* keep_ab = keep_m ? keep->ab : nullptr;        // HOST: (keep_a, keep_b) per step
+    if ((edit_w == nullptr) != (edit_c == nullptr) || (keep_m == nullptr) != (keep_x0 == nullptr)) return SINDDM_E_BADARG;
+    if (keep_m && !keep_ab) return SINDDM_E_BADARG;
+    if ((edit_w || keep_m) && (long long)CHANNELS * H * W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;      // (the maps are indexed with ints)
     // (the plain fused tail reads the maps and the draws as 16-byte vectors)
-    if (((reinterpret_cast<uintptr_t>(edit_w) | reinterpret_cast<uintptr_t>(edit_c) | reinterpret_cast<uintptr_t>(noise)) & 15) != 0)
+    if (((reinterpret_cast<uintptr_t>(edit_w) | reinterpret_cast<uintptr_t>(edit_c) | reinterpret_cast<uintptr_t>(noise) |
+          reinterpret_cast<uintptr_t>(keep_m) | reinterpret_cast<uintptr_t>(keep_x0)) & 15) != 0)
         return SINDDM_E_BADARG;
     NetPlan p = make_plan(dim);
     if (!p.ok) return SINDDM_E_BADSHAPE;
@@ -1621,6 +1686,8 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                 cs.seed = (unsigned long long)seed; cs.stream_id = (unsigned long long)(stream_id0 + (uint64_t)i);
                 cs.b0 = h ? Bh[0] : 0;
                 cs.edit_w = edit_w; cs.edit_c = edit_c; cs.noise = noise ? noise + (size_t)i * (size_t)n : nullptr;
+                cs.keep_m = keep_m; cs.keep_x0 = keep_x0;
+                if (keep_m) { cs.keep_a = keep_ab[2 * i]; cs.keep_b = keep_ab[2 * i + 1]; }
                 rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
                                       h ? sx : st, nullptr, &cs);
                 if (tiled && fuse_tail && rc == 0)
@@ -1628,9 +1695,11 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
             }
             if (rc) break;
             if (!fuse_tail) {
-                SINDDM_TAIL_LAUNCH(reverse_step_rng_kernel, tail_variant(edit_w, noise), dim3((unsigned)bx), st, cur, eps, x_tilde,
-                                   nxt, coefs[i], n, (unsigned long long)seed, (unsigned long long)(stream_id0 + (uint64_t)i),
-                                   edit_w, edit_c, noise ? noise + (size_t)i * (size_t)n : nullptr, CHANNELS * H * W, H * W);
+                SINDDM_TAIL_LAUNCH(reverse_step_rng_kernel, tail_variant(edit_w, noise, keep_m), dim3((unsigned)bx), st, cur, eps,
+                                   x_tilde, nxt, coefs[i], n, (unsigned long long)seed,
+                                   (unsigned long long)(stream_id0 + (uint64_t)i), edit_w, edit_c,
+                                   noise ? noise + (size_t)i * (size_t)n : nullptr, CHANNELS * H * W, H * W, keep_m, keep_x0,
+                                   keep_m ? keep_ab[2 * i] : 1.0f, keep_m ? keep_ab[2 * i + 1] : 0.0f);
                 if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
                 if (tiled && (rc = wrap_halo_launch(nxt, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st)) != 0) break;
             }
@@ -1660,17 +1729,26 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
                            uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                            void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr);
 }
 
 int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
+    return sinddm_sample_chain_keep(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
+                                    H, W, ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr);
+}
+
+int sinddm_sample_chain_keep(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                             const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                             uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
+                             const sinddm_keep_opts* keep) {
     if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
     if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep);
 }
 
 int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1699,8 +1777,29 @@ int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_
     const long long n = (long long)B * C * HW;
     long long bx = (n + 255) / 256;
     if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL(reverse_step_kernel<true>, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, eps, x_tilde, noise, out, *coefs, n, edit_w, edit_c, C * HW, HW);
+    hipLaunchKernelGGL((reverse_step_kernel<true, false>), dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, eps, x_tilde, noise, out, *coefs, n, edit_w, edit_c, C * HW, HW, nullptr, nullptr, 1.0f, 0.0f);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                             const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, const float* keep_m,
+                             const float* keep_x0, float keep_a, float keep_b, int B, int C, int HW, void* stream) {
+    if (!x_t || !eps || !noise || !out || !coefs || !keep_m || !keep_x0 || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
+    if ((edit_w == nullptr) != (edit_c == nullptr)) return SINDDM_E_BADARG;
+    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
+    if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
+    const long long n = (long long)B * C * HW;
+    long long bx = (n + 255) / 256;
+    if (bx > 8192) bx = 8192;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (edit_w)
+        hipLaunchKernelGGL((reverse_step_kernel<true, true>), dim3((unsigned)bx), dim3(256), 0, st, x_t, eps, x_tilde, noise, out,
+                           *coefs, n, edit_w, edit_c, C * HW, HW, keep_m, keep_x0, keep_a, keep_b);
+    else
+        hipLaunchKernelGGL((reverse_step_kernel<false, true>), dim3((unsigned)bx), dim3(256), 0, st, x_t, eps, x_tilde, noise, out,
+                           *coefs, n, nullptr, nullptr, C * HW, HW, keep_m, keep_x0, keep_a, keep_b);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }

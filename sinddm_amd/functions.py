@@ -134,6 +134,50 @@ def stat_from_bbs(image: torch.Tensor, bb):                              # funct
     return [torch.mean(reg, dim=(2, 3), keepdim=True), torch.std(reg, dim=(2, 3), keepdim=True)]
 
 
+# ---- helpers of known-region sampling (MultiscaleTrainer.inpaint / outpaint; no reference counterpart) --------------
+def _area_weights(n_out: int, n_in: int) -> np.ndarray:
+    """(n_out, n_in) float64: row i holds the share of input pixel j in output pixel i's footprint [i r, (i + 1) r),
+    r = n_in / n_out.  The overlaps are integers in units of 1 / n_out, so a pixel is in the footprint or not -- no
+    rounding decides it -- and every row sums to 1."""
+    i = np.arange(n_out, dtype=np.int64)[:, None]
+    j = np.arange(n_in, dtype=np.int64)[None, :]
+    overlap = np.minimum((i + 1) * n_in, (j + 1) * n_out) - np.maximum(i * n_in, j * n_out)
+    return np.maximum(overlap, 0).astype(np.float64) / float(n_in)
+
+
+def keep_mask_pyramid(mask, sizes, hard: bool = True) -> List[torch.Tensor]:
+    """A full-resolution {0,1} mask (H, W), 1 = known, brought to every scale by area averaging: one fp32 (h, w) tensor
+    per entry of `sizes` ((h, w) pairs), on the mask's device.  `hard` keeps a pixel only if its whole footprint is known
+    (average >= 1 - 1e-6; the smallest share of a footprint pixel is 1 / H): a coarse pixel that mixes known and unknown
+    content is generated, never pinned.  hard=False returns the averages (the step kernels blend with them)."""
+    m = torch.as_tensor(mask)
+    if m.dim() != 2:
+        raise ValueError(f"keep_mask_pyramid: mask must be (H, W), got {tuple(m.shape)}")
+    device = m.device
+    full = m.detach().to("cpu", torch.float64).numpy()
+    out = []
+    for h, w in sizes:
+        h, w = int(h), int(w)
+        if h > full.shape[0] or w > full.shape[1]:
+            raise ValueError(f"keep_mask_pyramid: scale {(h, w)} is larger than the mask {full.shape}")
+        avg = _area_weights(h, full.shape[0]) @ full @ _area_weights(w, full.shape[1]).T
+        if hard:
+            avg = (avg >= 1.0 - 1e-6).astype(np.float64)
+        out.append(torch.from_numpy(np.clip(avg, 0.0, 1.0).astype(np.float32)).to(device))
+    return out
+
+
+def outpaint_offset(canvas, image, anchor=(0.5, 0.5)) -> Tuple[int, int]:
+    """Top-left corner (y, x) of an (h, w) image placed on an (H, W) canvas: int(anchor * (canvas - image)) per axis;
+    anchor (0, 0) = top left, (0.5, 0.5) = centred, (1, 1) = bottom right."""
+    for a, big, small in zip(anchor, canvas, image):
+        if not 0.0 <= float(a) <= 1.0:
+            raise ValueError(f"outpaint: anchor {tuple(anchor)} outside [0, 1]")
+        if int(big) < int(small):
+            raise ValueError(f"outpaint: canvas {tuple(canvas)} smaller than the image {tuple(image)} (scale_mul < 1)")
+    return int(float(anchor[0]) * (int(canvas[0]) - int(image[0]))), int(float(anchor[1]) * (int(canvas[1]) - int(image[1])))
+
+
 def _disk(radius: int) -> np.ndarray:
     """skimage.morphology.disk: (2r+1)^2 footprint of the pixels within Euclidean distance r."""
     yy, xx = np.mgrid[-radius:radius + 1, -radius:radius + 1]

@@ -8,6 +8,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
   q_sample / p_losses mix    -> sinddm_q_sample           (models.py:570-590)
   p_sample tail              -> sinddm_reverse_step       (models.py:306-352,433-459)
   inter-scale upsample       -> sinddm_upsample_bilinear  (models.py:567)
+  known pixels (`keep_maps`) -> sinddm_sample_chain_keep / sinddm_reverse_step_keep   (no reference line: RePaint-style
+                                replacement of the known region after every reverse step)
   tileable sampling (`tile`) -> sinddm_sample_chain_tile / sinddm_wrap_halo / sinddm_upsample_bilinear_wrap
                                 (no reference line: padding_mode='circular' on its nn.Conv2d's)
 
@@ -438,6 +440,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # _lib.TILE_HALO pixels (the network's receptive radius) and the centre is kept.  A sampling option: training is
         # unchanged.
         self.tile = (False, False)
+        # known-region conditioning (inpainting / outpainting): None or {s: (mask (H,W), x0 (3,H,W))}, fp32, on the sample's
+        # device.  At a scale with an entry every reverse step overwrites the pixels whose mask is 1 with the
+        # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
+        # values between 0 and 1 blend.  A sampling option, like `tile`; not available with CLIP guidance.
+        self.keep_maps = None
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -639,6 +646,39 @@ class MultiScaleGaussianDiffusion(nn.Module):
             cache[key] = tab
         return tab
 
+    def _keep_ab_table(self) -> np.ndarray:
+        """(T, 2) fp32: row t = (keep_a, keep_b) of the step t -> t-1, the forward scalars of the known image at t-1:
+        (sqrt_alphas_cumprod[t-1], sqrt_one_minus_alphas_cumprod[t-1]) for t > 0 and (1, 0) for t == 0."""
+        h = self._host()
+        cache = getattr(self, "_keep_ab_cache", None)
+        if cache is None or cache[0] != self._host_ver:
+            ab = np.empty((self.num_timesteps, 2), dtype=np.float32)
+            ab[0] = (1.0, 0.0)
+            ab[1:, 0] = h['sqrt_alphas_cumprod'][:-1]
+            ab[1:, 1] = h['sqrt_one_minus_alphas_cumprod'][:-1]
+            cache = (self._host_ver, ab)
+            self._keep_ab_cache = cache
+        return cache[1]
+
+    def _keep_entry(self, s: int, img: torch.Tensor):
+        """The (mask, x0) pair of `keep_maps` for scale s, checked against the running sample (the library takes raw
+        pointers: a mismatching map would be read out of bounds), or None."""
+        if self.keep_maps is None:
+            return None
+        if self.clip_guided_sampling:
+            raise NotImplementedError("keep_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and "
+                                      "has no known-region replacement")
+        entry = self.keep_maps.get(int(s))
+        if entry is None:
+            return None
+        m, k0 = entry
+        H, W = int(img.shape[-2]), int(img.shape[-1])
+        for name, t, shape in (("mask", m, (H, W)), ("x0", k0, (int(img.shape[1]), H, W))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != img.device:
+                raise _lib.SinddmError(f"keep_maps[{int(s)}] {name} {tuple(t.shape)} {t.dtype} {t.device} does not match the "
+                                       f"running sample {tuple(img.shape)} {img.dtype} {img.device} (expected {shape} float32)")
+        return m.contiguous(), k0.contiguous()
+
     def _tile_halo(self) -> Tuple[int, int]:
         """(halo_y, halo_x) in pixels of the `tile` setting: _lib.TILE_HALO on a wrapped axis, 0 elsewhere."""
         wy, wx = self.tile
@@ -669,9 +709,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
         With `tile` set the run works on the sample extended by the wrapped halo (sinddm_sample_chain_tile: the state,
         x-tilde, the edit maps and the noise buffers all have the extended size) and returns the centre; the in-kernel
         draws are keyed on the extended index, so a tiled and a plain run of one seed are unrelated.  The step-by-step
-        route extends each network input instead (`_eps`) and steps the centre: it is the cross-check of the tiled chain."""
+        route extends each network input instead (`_eps`) and steps the centre: it is the cross-check of the tiled chain.
+        With `keep_maps` set the scale's mask and known image (wrapped like the edit maps when tiled) and the per-step
+        forward scalars go to sinddm_sample_chain_keep: still one call, with ROI maps, `chain_noise` and two streams alike;
+        the step-by-step route replaces through sinddm_reverse_step_keep."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
+        keep = self._keep_entry(s, img)
         roi = bool(self.roi_guided_sampling and s < self.n_scales - 1)     # models.py:430-431
         fast = ((self.noise_fn is None or self.chain_noise) and isinstance(self.denoise_fn, SinDDMNet)
                 and not self.save_interm and not self.clip_guided_sampling and (self.chain_guided or not roi)
@@ -713,6 +757,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
             if tiled:                                                      # (locals of this frame: alive for the call)
                 ew, ec = self._wrap_pad(ew, hy, hx), self._wrap_pad(ec, hy, hx)
             opts.edit_w, opts.edit_c = _lib.ptr(ew), _lib.ptr(ec)
+        kopts = None
+        if keep is not None:
+            km, kx = (self._wrap_pad(keep[0], hy, hx), self._wrap_pad(keep[1], hy, hx)) if tiled else keep
+            ab_tab = self._keep_ab_table()
+            ab = (C.c_float * (2 * n))(*[float(v) for t in t_seq for v in ab_tab[t]])
+            kopts = _lib.KeepOpts()
+            kopts.mask, kopts.x0 = _lib.ptr(km), _lib.ptr(kx)
         aux = _aux_stream(x.device) if self.two_streams else None
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
 
@@ -724,7 +775,10 @@ class MultiScaleGaussianDiffusion(nn.Module):
                     C.cast(C.addressof(coefs) + i0 * C.sizeof(_lib.StepCoefs), C.POINTER(_lib.StepCoefs)),
                     C.cast(C.addressof(tl) + i0 * C.sizeof(C.c_int), C.POINTER(C.c_int)), k, float(s), seed, 0, net.dim_arg,
                     B, Hc, Wc, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts))
-            if tiled:
+            if kopts is not None:
+                kopts.ab = C.cast(C.addressof(ab) + 2 * i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
+                _lib.check(lib.sinddm_sample_chain_keep(*args, hy, hx, C.byref(kopts)), "sinddm_sample_chain_keep")
+            elif tiled:
                 _lib.check(lib.sinddm_sample_chain_tile(*args, hy, hx), "sinddm_sample_chain_tile")
             else:
                 _lib.check(lib.sinddm_sample_chain_ex(*args), "sinddm_sample_chain_ex")
@@ -773,6 +827,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
     def _p_sample_host_t(self, x: torch.Tensor, t: int, s: int, clip_denoised: bool = True,
                          repeat_noise: bool = False) -> torch.Tensor:
         """One reverse step with the timestep known on the host: net forward + ONE fused kernel."""
+        keep = self._keep_entry(s, x)                                       # (raises under CLIP guidance)
         if self.clip_guided_sampling:
             if self.clip_model is None or self.guidance_sub_iters is None or self.stop_guidance is None:
                 raise RuntimeError("clip_guided_sampling is set but clip_model / guidance_sub_iters / stop_guidance are not: "
@@ -797,6 +852,17 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
             xt = xt.contiguous()
         out = torch.empty_like(x)
+        if keep is not None:
+            B_, C_, H_, W_ = x.shape
+            ew = ec = None
+            if self.roi_guided_sampling and s < self.n_scales - 1:
+                ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
+            ka, kb = (float(v) for v in self._keep_ab_table()[int(t)])
+            _lib.check(lib.sinddm_reverse_step_keep(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
+                                                    C.byref(k), _lib.ptr(ew), _lib.ptr(ec), _lib.ptr(keep[0]),
+                                                    _lib.ptr(keep[1]), ka, kb, B_, C_, H_ * W_,
+                                                    _lib.stream_ptr(x.device)), "sinddm_reverse_step_keep")
+            return out
         if self.roi_guided_sampling and s < self.n_scales - 1:             # models.py:430-431
             B_, C_, H_, W_ = x.shape
             ew, ec = self.roi_edit_maps(s, H_, W_, x.device)

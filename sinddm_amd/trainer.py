@@ -434,6 +434,59 @@ class MultiscaleTrainer(object):
         finally:
             em.roi_guided_sampling = False
 
+    # ---- known-region sampling: some pixels are given, the rest is generated to fit (no reference counterpart) ----
+    def _sample_kept(self, keep_maps, tag, **kw):
+        em = self.ema_model
+        em.keep_maps = keep_maps
+        try:
+            return self.sample_scales(custom_sample=False, image_name='', start_noise=True,
+                                      desc=f'{tag}_{str(datetime.datetime.now()).replace(":", "_")}', **kw)
+        finally:
+            em.keep_maps = None
+
+    @torch.no_grad()
+    def inpaint(self, mask, batch_size=16, hard=True, custom_t_list=None, save_unbatched=False, save_images=True):
+        """Fill a hole in the training image: `mask` is (H, W) at the finest scale's size, 1 = keep the training image's
+        pixel, 0 = generate.  At every scale the known image is that scale's training image and the mask comes from
+        `functions.keep_mask_pyramid` (`hard`: a coarse pixel is kept only if its whole footprint is known); after every
+        reverse step the known pixels are overwritten with the forward-diffused training image of that noise level, inside
+        the step kernels (`ema_model.keep_maps` -> sinddm_sample_chain_keep: one library call per scale).  RePaint's
+        resampling jumps are not built.  Returns the per-scale batches and writes PNGs like `sample_scales`."""
+        from .functions import keep_mask_pyramid
+        em = self.ema_model
+        m = torch.as_tensor(mask)
+        if tuple(m.shape) != tuple(em.image_sizes[self.n_scales - 1]):
+            raise ValueError(f'inpaint: mask {tuple(m.shape)} is not the finest scale {tuple(em.image_sizes[self.n_scales - 1])}')
+        masks = keep_mask_pyramid(m, [em.image_sizes[s] for s in range(self.n_scales)], hard=hard)
+        maps = {s: (masks[s].to(self.device).contiguous(), self.data_list[s][0][0].contiguous())
+                for s in range(self.n_scales)}
+        return self._sample_kept(maps, 'inpaint', batch_size=batch_size, custom_t_list=custom_t_list,
+                                 save_unbatched=save_unbatched, save_images=save_images)
+
+    @torch.no_grad()
+    def outpaint(self, scale_mul, anchor=(0.5, 0.5), batch_size=16, custom_t_list=None, save_unbatched=False,
+                 save_images=True):
+        """Grow the canvas around the training image: at every scale the sample has `target_size(s, scale_mul)`, the
+        scale's own training image sits unresampled at int(anchor * (canvas - image)) and is kept (mask 1 on that
+        rectangle), the rest is generated.  `scale_mul` < 1 on an axis is a ValueError."""
+        from .functions import outpaint_offset
+        em = self.ema_model
+        if min(float(scale_mul[0]), float(scale_mul[1])) < 1:
+            raise ValueError(f'outpaint: scale_mul {tuple(scale_mul)} < 1 would crop the known image')
+        maps = {}
+        for s in range(self.n_scales):
+            img = self.data_list[s][0][0]
+            h, w = int(img.shape[1]), int(img.shape[2])
+            Hc, Wc = em.target_size(s, scale_mul)
+            y0, x0 = outpaint_offset((Hc, Wc), (h, w), anchor)
+            k0 = torch.zeros((img.shape[0], Hc, Wc), dtype=torch.float32, device=img.device)
+            m = torch.zeros((Hc, Wc), dtype=torch.float32, device=img.device)
+            k0[:, y0:y0 + h, x0:x0 + w] = img
+            m[y0:y0 + h, x0:x0 + w] = 1.0
+            maps[s] = (m, k0)
+        return self._sample_kept(maps, 'outpaint', scale_mul=tuple(scale_mul), batch_size=batch_size,
+                                 custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images)
+
     # ---- CLIP-driven modes of the reference.  CLIP itself (clip/, text2live_util/) is not part of this build; the
     # driver takes any `clip_model` with the interface the reference uses: get_text_embedding(text, template=...),
     # zero_grad(), calculate_clip_loss(image in [0,1], embedding) (differentiable), cfg["n_aug"] ----
