@@ -246,6 +246,36 @@ int sinddm_sample_chain_keep(const float* params, const float* packed, float* x,
                              const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep /*host, may be NULL*/);
 
+/* ---- per-sample noise seeds: a sample is reproducible at any batch size, position and rank count --------------- */
+/* The noise contract.  A sample b has a seed sigma_b, 0 <= sigma_b < 2^63, held on the device as 8 bytes.  For stream id j the
+ * N(0,1) draw of element e of sample b is ELEMENT e OF sinddm_normal_fill(out, 3*H*W, sigma_b, j): e is the flat index inside
+ * the sample's own (3,H,W) tensor (the EXTENDED size under a halo; halo draws are discarded as before).  It is the generator
+ * of sinddm_sample_chain (Philox4x32-10, Box-Muller, four normals per quad) with two changes: the quad index restarts at
+ * every sample, and the key is the sample's seed.  The draws of a sample therefore do not depend on the batch it is in, on
+ * its position, on the two-stream split or on the process that runs it; a batch-of-one sinddm_sample_chain_ex with
+ * seed = sigma already follows the contract.  The sampler lays its stream ids out per pyramid scale s as (s << 32) | k:
+ * k = 0 the initial draw, k = 1 the re-noise draw, k = 2 + i the step at position i of the scale's run.
+ *
+ * sinddm_normal_fill_samples: B slices of n floats; slice b (at out + b*n, unaligned when n % 4 != 0) is
+ * sinddm_normal_fill(n, seeds[b], stream_id).  The sampler's initial / re-noise draws, and the per-step draws of its
+ * step-by-step route.  SINDDM_E_BADARG: out / seeds NULL, seeds not 8-byte aligned, B <= 0, n <= 0. */
+int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* seeds /*device, B*/,
+                               uint64_t stream_id, void* stream);
+
+/* sinddm_sample_chain_keep with per-sample seeds.  sample_seeds = NULL is sinddm_sample_chain_keep itself (that entry is a
+ * thin wrapper over this one): the same launches, the same numbers.  With seeds, step i of the call adds to element e of
+ * sample b  sigma_i * (element e of sinddm_normal_fill(3*H*W, sample_seeds[b], stream_id0 + i))  -- H, W the extended size
+ * under a halo -- and `seed` is ignored.  opts->noise still wins over both.  ROI maps, halo, keep and the two-stream split
+ * work as before (the second half-batch reads its own part of sample_seeds); results with / without aux_stream are
+ * identical.  SINDDM_E_BADARG (before any device work): sample_seeds not 8-byte aligned. */
+int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                              const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                              int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                              void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                              const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                              const sinddm_keep_opts* keep /*host, may be NULL*/,
+                              const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/);
+
 /* sinddm_reverse_step / sinddm_reverse_step_edit with the same replacement, noise supplied by the caller: the step-by-step
  * route and the cross-check of the chain call.  keep_m: HW floats, keep_x0: C*HW floats (both required, shared by all B
  * samples); edit_w / edit_c: both or neither. */

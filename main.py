@@ -20,6 +20,10 @@ cylindrical panoramas (`--tile x --scale_mul 1 4`).  All five modes honour it.
 known region after every reverse step inside the step kernels: `--mode inpaint --mask_path FILE [--soft_mask]` fills the
 black part of the mask (white = keep the training image's pixel; the file is brought to the finest scale's size);
 `--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.
+`--seeds S [S ...]` (one per sample of the batch) or `--seed_base N` (seeds N ... N + batch - 1) give every sample its own
+noise seed (no reference flag: the reference never seeds its generator): the image of a seed is the same at any batch size,
+position in the batch and number of GPUs.  `--vary_from_scale S` keeps the given seeds below scale S and derives fresh
+ones per sample from S on: `--seeds 17 17 17 17 --vary_from_scale 3` makes four variations of one coarse layout.
 The CLIP-guided modes (clip_content, clip_style_*, clip_roi; main.py:153-255) are not wired to the command line: CLIP
 itself is outside this build.  Their drivers exist (`MultiscaleTrainer.clip_sampling` / `clip_roi_sampling`, the guidance
 branch of `p_mean_variance`) and take any scorer with the reference's ClipExtractor interface.
@@ -69,11 +73,36 @@ def build_parser():
     # panoramas), the y axis or both (seamlessly tileable textures) -- MultiScaleGaussianDiffusion.tile
     p.add_argument("--soft_mask", action="store_true")    # inpaint: blend with the area-averaged mask at coarse scales
     p.add_argument("--tile", choices=("none", "x", "y", "xy"), default="none")
+    # no reference flags: per-sample noise seeds (MultiScaleGaussianDiffusion.sample_seeds) of every sampling mode
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--seeds", type=int, nargs="+", default=None)
+    g.add_argument("--seed_base", type=int, default=None)
+    p.add_argument("--vary_from_scale", type=int, default=None)
     return p
 
 
+def parse_args(argv=None):
+    """Parse the command line and resolve the seed flags: `args.seeds` becomes the list of `sample_batch_size` seeds (or
+    stays None)."""
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.seed_base is not None:
+        args.seeds = [args.seed_base + b for b in range(args.sample_batch_size)]
+    if args.seeds is not None:
+        if len(args.seeds) != args.sample_batch_size:
+            p.error(f"--seeds: {len(args.seeds)} seeds for --sample_batch_size {args.sample_batch_size}")
+        if min(args.seeds) < 0 or max(args.seeds) >= 2 ** 63:
+            p.error("--seeds / --seed_base: a seed must be in [0, 2^63)")
+    elif args.vary_from_scale is not None:
+        p.error("--vary_from_scale needs --seeds or --seed_base")
+    if args.vary_from_scale is not None and args.vary_from_scale < 0:
+        p.error("--vary_from_scale must be >= 0")
+    return args
+
+
 def main():
-    args = build_parser().parse_args()
+    args = parse_args()
+    seed_kw = dict(seeds=args.seeds, vary_from_scale=args.vary_from_scale)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     td = None
     if world > 1:
@@ -132,10 +161,11 @@ def main():
     if args.mode == 'train':
         trainer.train()
         trainer.sample_scales(scale_mul=(1, 1), custom_sample=True, image_name=args.image_name,
-                              batch_size=args.sample_batch_size, custom_t_list=sample_t_list)
+                              batch_size=args.sample_batch_size, custom_t_list=sample_t_list, **seed_kw)
     elif args.mode == 'sample':
         trainer.sample_scales(scale_mul=scale_mul, custom_sample=True, image_name=args.image_name,
-                              batch_size=args.sample_batch_size, custom_t_list=sample_t_list, save_unbatched=True)
+                              batch_size=args.sample_batch_size, custom_t_list=sample_t_list, save_unbatched=True,
+                              **seed_kw)
     elif args.mode in ('style_transfer', 'harmonization'):                 # reference main.py:296-322
         i2i_folder = os.path.join(args.dataset_folder, 'i2i')
         start_s = n_scales - 1                                             # start the diffusion at the last scale
@@ -146,13 +176,14 @@ def main():
         trainer.image2image(input_folder=i2i_folder, input_file=args.input_image, mask=args.harm_mask,
                             hist_ref_path=f'{args.dataset_folder}scale_{start_s}/', batch_size=args.sample_batch_size,
                             image_name=args.image_name, start_s=start_s, custom_t=custom_t, scale_mul=(1, 1),
-                            device=device, use_hist=use_hist, save_unbatched=True, auto_scale=50000, mode=args.mode)
+                            device=device, use_hist=use_hist, save_unbatched=True, auto_scale=50000, mode=args.mode,
+                            **seed_kw)
     elif args.mode == 'roi':                                               # reference main.py:257-294
         if not args.roi_target or len(args.roi_target) != 4 or not args.roi_bbs or len(args.roi_bbs) % 4:
             raise SystemExit("--mode roi needs --roi_target y x h w and --roi_bbs y x h w [y x h w ...]")
         bbs = [list(args.roi_bbs[i:i + 4]) for i in range(0, len(args.roi_bbs), 4)]
         trainer.roi_guided_sampling(custom_t_list=sample_t_list, target_roi=list(args.roi_target), roi_bb_list=bbs,
-                                    save_unbatched=True, batch_size=args.sample_batch_size, scale_mul=scale_mul)
+                                    save_unbatched=True, batch_size=args.sample_batch_size, scale_mul=scale_mul, **seed_kw)
     elif args.mode == 'inpaint':
         if not args.mask_path:
             raise SystemExit("--mode inpaint needs --mask_path FILE (white = keep the training image's pixel, black = fill)")
@@ -161,10 +192,10 @@ def main():
         h, w = ms_diffusion.image_sizes[n_scales - 1]
         known = np.asarray(Image.open(args.mask_path).convert("L").resize((w, h), Image.NEAREST)) > 127
         trainer.inpaint(torch.from_numpy(known.astype(np.float32)), batch_size=args.sample_batch_size,
-                        hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True)
+                        hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
     elif args.mode == 'outpaint':
         trainer.outpaint(scale_mul, anchor=tuple(args.anchor), batch_size=args.sample_batch_size,
-                         custom_t_list=sample_t_list, save_unbatched=True)
+                         custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
     else:
         raise NotImplementedError(
             f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint and outpaint are built for MI355X; "

@@ -24,7 +24,7 @@ ABI_SYMBOLS = (
     "sinddm_net_forward_train", "sinddm_net_backward", "sinddm_l1_loss_fwd_bwd", "sinddm_adam_ema_step",
     "sinddm_cond_embed", "sinddm_cond_stride", "sinddm_sample_chain", "sinddm_sample_chain2", "sinddm_sample_chain_ex",
     "sinddm_normal_fill", "sinddm_wrap_halo", "sinddm_upsample_bilinear_wrap", "sinddm_sample_chain_tile",
-    "sinddm_sample_chain_keep", "sinddm_reverse_step_keep",
+    "sinddm_sample_chain_keep", "sinddm_reverse_step_keep", "sinddm_normal_fill_samples", "sinddm_sample_chain_seeds",
 )
 
 
@@ -102,6 +102,10 @@ def load() -> C.CDLL:
         "sinddm_sample_chain_keep": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
                                          i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i,
                                          C.POINTER(KeepOpts)]),
+        "sinddm_sample_chain_seeds": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
+                                          i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i,
+                                          C.POINTER(KeepOpts), p]),
+        "sinddm_normal_fill_samples": (i, [p, i, i64, p, C.c_uint64, p]),
         "sinddm_reverse_step_keep": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, p, p, f, f, i, i, i, p]),
         "sinddm_wrap_halo": (i, [p, p, i, i, i, i, i, p]),
         "sinddm_upsample_bilinear_wrap": (i, [p, p, i, i, i, i, i, i, i, p]),

@@ -849,6 +849,13 @@ __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned
 //          instead of drawn from Philox; steps with sigma == 0 (and, under KEEP, kb == 0) read nothing
 //   KEEP   the known-region replacement of keep_blend on the step's output: m = km[p], k0 = kx[ch * HW + p], shared by all
 //          samples and read like the edit maps; z is drawn (or read) when sigma != 0 OR kb != 0
+// Per-sample seeds (sinddm_sample_chain_seeds) are NOT a template flag: `sseeds` (device, one 64-bit seed per sample of THIS
+// launch, or NULL) is selected once per block.  With it the Philox key of sample b is sseeds[b] and the counter is the quad
+// index INSIDE the sample's own (3,H,W) tensor -- element e of the sample gets element e of sinddm_normal_fill(3HW, sseeds[b],
+// step) -- instead of (seed, quad index inside the whole batch).  NULL leaves every number as it was.  The two fused tails
+// own one sample per block (blockIdx.y), so the select is a scalar load and a scalar move; the unfused tail, which strides
+// over the flat batch, has a per-sample sibling (reverse_step_rng_samples_kernel) because a sample's quads then no longer
+// coincide with the flat quads.
 template <bool EDIT, bool NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                const float* __restrict__ xtil, float* __restrict__ out,
@@ -924,10 +931,14 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
                                                                       const float* __restrict__ ec,
                                                                       const float* __restrict__ nz,
                                                                       const float* __restrict__ km,
-                                                                      const float* __restrict__ kx, float ka, float kb) {
+                                                                      const float* __restrict__ kx, float ka, float kb,
+                                                                      const unsigned long long* __restrict__ sseeds) {
     const int b = blockIdx.y;
     const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (p >= HW) return;
+    // the noise key: (seed, index inside the whole batch), or with per-sample seeds (sseeds[b], index inside the sample)
+    const unsigned long long key = sseeds ? sseeds[b] : seed;
+    const long long kofs = sseeds ? -(long long)b * 3 * HW : (long long)b0 * 3 * HW;
     const float* src = a + (size_t)b * C * HW + p;
     f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
 #pragma unroll 8
@@ -944,14 +955,14 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + p;
-        const long long ig = i0 + (long long)b0 * 3 * HW;           // flat index inside the whole batch: the noise key
+        const long long ig = i0 + (long long)b0 * 3 * HW;           // flat index inside the whole batch (recorded draws)
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         if (k.sigma != 0.0f || (KEEP && kb != 0.0f)) {
             if (NOISE) {
                 const f32x4 zv = *reinterpret_cast<const f32x4*>(nz + ig);
                 z[0] = zv[0]; z[1] = zv[1]; z[2] = zv[2]; z[3] = zv[3];
             } else {
-                philox_normal4(seed, step, (unsigned long long)(ig >> 2), z);
+                philox_normal4(key, step, (unsigned long long)((i0 + kofs) >> 2), z);
             }
         }
         const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
@@ -981,7 +992,8 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
     const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ xt,
     const float* __restrict__ xtil, float* __restrict__ out, sinddm_step_coefs k, int C, int H, int W, int Wp,
     unsigned long long seed, unsigned long long step, int b0, const float* __restrict__ ew, const float* __restrict__ ec,
-    const float* __restrict__ nz, const float* __restrict__ km, const float* __restrict__ kx, float ka, float kb) {
+    const float* __restrict__ nz, const float* __restrict__ km, const float* __restrict__ kx, float ka, float kb,
+    const unsigned long long* __restrict__ sseeds) {
     const int b = blockIdx.y;
     const int qpr = Wp >> 2;
     const int q = blockIdx.x * 256 + threadIdx.x;
@@ -989,6 +1001,10 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
     const int y = q / qpr, x = (q - y * qpr) * 4;
     const size_t HWp = (size_t)H * Wp;
     const long long HW = (long long)H * W;
+    // the noise key (as in final_conv_reverse_step_kernel): (seed, index inside the whole batch), or with per-sample seeds
+    // (sseeds[b], index inside the sample)
+    const unsigned long long key = sseeds ? sseeds[b] : seed;
+    const long long kofs = sseeds ? -(long long)b * 3 * HW : (long long)b0 * 3 * HW;
     const float* src = a + (size_t)b * C * HWp + (size_t)y * Wp + x;
     f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
 #pragma unroll 8
@@ -1003,12 +1019,13 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + (long long)y * W + x;
-        const long long ig = i0 + (long long)b0 * 3 * HW;          // flat index inside the whole batch: the noise key
-        const int r0 = (int)(ig & 3);
+        const long long ig = i0 + (long long)b0 * 3 * HW;          // flat index inside the whole batch (recorded draws)
+        const long long ik = i0 + kofs;                             // the noise key's index
+        const int r0 = (int)(ik & 3);
         float za[4] = {0.f, 0.f, 0.f, 0.f}, zb[4] = {0.f, 0.f, 0.f, 0.f};
         if (!NOISE && draw) {
-            philox_normal4(seed, step, (unsigned long long)(ig >> 2), za);
-            if (r0 != 0) philox_normal4(seed, step, (unsigned long long)(ig >> 2) + 1ull, zb);
+            philox_normal4(key, step, (unsigned long long)(ik >> 2), za);
+            if (r0 != 0) philox_normal4(key, step, (unsigned long long)(ik >> 2) + 1ull, zb);
         }
         const float z8[8] = {za[0], za[1], za[2], za[3], zb[0], zb[1], zb[2], zb[3]};
 #pragma unroll
@@ -1039,6 +1056,91 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ 
         float z[4];
         philox_normal4(seed, step, (unsigned long long)q, z);
         for (int j = 0; j < 4 && (q << 2) + j < n; ++j) out[(q << 2) + j] = z[j];
+    }
+}
+// B slices of n floats (sinddm_normal_fill_samples): slice b (blockIdx.y) is philox_normal_kernel(n, seeds[b], step).  The
+// quad index restarts at every slice; a slice starts at b*n floats -- unaligned when n % 4 != 0 -- so the stores are scalar
+// and the last quad of a slice is cut at the slice's end.
+__global__ __launch_bounds__(256) void philox_normal_samples_kernel(float* __restrict__ out, long long n,
+                                                                    const unsigned long long* __restrict__ seeds,
+                                                                    unsigned long long step) {
+    const unsigned long long key = seeds[blockIdx.y];
+    float* __restrict__ o = out + (long long)blockIdx.y * n;
+    const long long n4 = (n + 3) >> 2;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
+        float z[4];
+        philox_normal4(key, step, (unsigned long long)q, z);
+        for (int j = 0; j < 4 && (q << 2) + j < n; ++j) o[(q << 2) + j] = z[j];
+    }
+}
+
+// reverse_step_rng_kernel with per-sample seeds (the unfused tail of sinddm_sample_chain_seeds; recorded noise wins over
+// seeds, so there is no NOISE variant).  That kernel strides over the quads of the FLAT batch; here a block row (blockIdx.y)
+// owns one sample and walks the quads of the sample's own (3,H,W) tensor: quad q of sample b holds elements 4q .. 4q+3 of
+// the sample and the draws philox_normal4(sseeds[b], step, q).  When chw % 4 != 0 a sample starts at an address that is
+// not 16-byte aligned (scalar loads and stores), and its last quad is partial: the elements past chw belong to the next
+// sample, which draws them from its own key, so they are neither computed nor written here.
+template <bool EDIT, bool KEEP>
+__global__ __launch_bounds__(256) void reverse_step_rng_samples_kernel(
+    const float* __restrict__ xt, const float* __restrict__ eps, const float* __restrict__ xtil, float* __restrict__ out,
+    sinddm_step_coefs k, unsigned long long step, const unsigned long long* __restrict__ sseeds, const float* __restrict__ ew,
+    const float* __restrict__ ec, int chw, int hw, const float* __restrict__ km, const float* __restrict__ kx, float ka,
+    float kb) {
+    const unsigned long long key = sseeds[blockIdx.y];
+    const long long base = (long long)blockIdx.y * chw;
+    const int n4 = (int)(((long long)chw + 3) >> 2);
+    const bool vec = (chw & 3) == 0;                      // every sample then starts on a 16-byte boundary, like the batch
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < n4; q += gridDim.x * 256) {
+        const int r0 = q << 2;                              // index inside the sample
+        const int nv = chw - r0 < 4 ? chw - r0 : 4;         // elements of this quad that belong to the sample (>= 1)
+        const long long i0 = base + r0;
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (k.sigma != 0.0f || (KEEP && kb != 0.0f)) philox_normal4(key, step, (unsigned long long)q, z);
+        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
+        if (EDIT || KEEP) {
+            for (int j = 0; j < nv; ++j) {
+                const int r = r0 + j;
+                if (EDIT) {
+                    w[j] = ew[r % hw];
+                    c[j] = ec[r];
+                }
+                if (KEEP) {
+                    m[j] = km[r % hw];
+                    k0[j] = kx[r];
+                }
+            }
+        }
+        // ONE evaluation for both layouts -- the unrolled four-element form of reverse_step_rng_kernel's 16-byte path, so that the
+        // seeded run rounds like the run that is fed the same numbers as a buffer; only the loads and stores differ
+        f32x4 x{0.f, 0.f, 0.f, 0.f}, e{0.f, 0.f, 0.f, 0.f}, xb{0.f, 0.f, 0.f, 0.f};
+        if (vec) {
+            x = *reinterpret_cast<const f32x4*>(xt + i0);
+            e = *reinterpret_cast<const f32x4*>(eps + i0);
+            if (k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j < nv) {
+                    x[j] = xt[i0 + j];
+                    e[j] = eps[i0 + j];
+                    if (k.mode != 0) xb[j] = xtil[i0 + j];
+                }
+            }
+        }
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o[j] = reverse_step_mean(k, x[j], e[j], xb[j], w[j], c[j], EDIT) + k.sigma * z[j];
+            if (KEEP) o[j] = keep_blend(k, o[j], z[j], xb[j], m[j], k0[j], ka, kb);
+        }
+        if (vec) {
+            *reinterpret_cast<f32x4*>(out + i0) = o;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < nv) out[i0 + j] = o[j];
+        }
     }
 }
 
@@ -1189,6 +1291,7 @@ struct ChainStep {
     const float* keep_m;   // known-region mask / known image (HW / 3*HW floats, shared by the batch) or both NULL
     const float* keep_x0;
     float keep_a, keep_b;  // this step's forward scalars of the known image (sinddm_keep_opts::ab)
+    const unsigned long long* sseeds;   // per-sample seeds of THIS call's samples (device) or NULL -> (seed, b0)
 };
 
 // one of the eight instantiations of a tail kernel: bit 0 = EDIT, bit 1 = NOISE, bit 2 = KEEP
@@ -1430,7 +1533,7 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
             SINDDM_TAIL_LAUNCH(final_conv_reverse_step_pitch_kernel, tail_variant(cs->edit_w, cs->noise, cs->keep_m), dim3(gx, B),
                                st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, H, W,
                                Wp, cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise, cs->keep_m, cs->keep_x0,
-                               cs->keep_a, cs->keep_b);
+                               cs->keep_a, cs->keep_b, cs->sseeds);
         else
             hipLaunchKernelGGL(final_conv1x1_pitch_kernel, dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w,
                                params + P.fin_b, out, P.half, H, W, Wp);
@@ -1441,7 +1544,7 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         SINDDM_TAIL_LAUNCH(final_conv_reverse_step_kernel, tail_variant(cs->edit_w, cs->noise, cs->keep_m),
                            dim3((HW / 4 + 255) / 256, B), st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next,
                            cs->coefs, P.half, HW, cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise, cs->keep_m,
-                           cs->keep_x0, cs->keep_a, cs->keep_b);
+                           cs->keep_x0, cs->keep_a, cs->keep_b, cs->sseeds);
         SINDDM_LAUNCH_CHECK();
         return 0;
     }
@@ -1568,6 +1671,18 @@ int sinddm_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t stream_id,
     return 0;
 }
 
+int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, void* stream) {
+    if (!out || !seeds || B <= 0 || n <= 0 || (reinterpret_cast<uintptr_t>(seeds) & 7) != 0) return SINDDM_E_BADARG;
+    if (B > 65535) return SINDDM_E_BADSHAPE;                                   // (one grid row per slice)
+    long long bx = ((n + 3) / 4 + 255) / 256;
+    if (bx > 8192) bx = 8192;
+    hipLaunchKernelGGL(philox_normal_samples_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), out, (long long)n, reinterpret_cast<const unsigned long long*>(seeds),
+                       (unsigned long long)stream_id);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
 // sampler runs whose dim -> dim conv launches carry between LO and HI (8x32 tile, 80-channel block) items per CU AND leave
 // at least 4 % of their last round of items empty are run as two half-batches on two streams (sinddm_sample_chain2).
 // Below LO a half-batch falls onto the one-m-tile kernels (C2 48x64 at batch 16: -3.5 %); launches that fill their rounds
@@ -1579,8 +1694,8 @@ int sinddm_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t stream_id,
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
-// The body of sinddm_sample_chain_ex (halo_y = halo_x = 0), of sinddm_sample_chain_tile (keep = NULL) and of
-// sinddm_sample_chain_keep.  Hc x Wc is the CENTRE size; the
+// The body of sinddm_sample_chain_ex (halo_y = halo_x = 0), of sinddm_sample_chain_tile (keep = NULL), of
+// sinddm_sample_chain_keep (sample_seeds = NULL) and of sinddm_sample_chain_seeds.  Hc x Wc is the CENTRE size; the
 // steps run on the extended shape H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo,
 // the halo of every step's output is refreshed from its centre (wrap_halo_launch, per half-batch on its own stream), and
 // that of `x` once on entry: the zero padding of the convolutions then never reaches the centre (SINDDM_TILE_HALO).
@@ -1588,7 +1703,8 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                              uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                             const sinddm_keep_opts* keep) {
+                             const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
+    if ((reinterpret_cast<uintptr_t>(sample_seeds) & 7) != 0) return SINDDM_E_BADARG;
     if (!params || !packed || !x || !x_alt || !eps || !coefs || !t_list || !ws || n_steps < 0 || B <= 0 || Hc <= 0 || Wc <= 0)
         return SINDDM_E_BADARG;
     const bool tiled = halo_y != 0 || halo_x != 0;
@@ -1602,6 +1718,9 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     if ((edit_w == nullptr) != (edit_c == nullptr) || (keep_m == nullptr) != (keep_x0 == nullptr)) return SINDDM_E_BADARG;
     if (keep_m && !keep_ab) return SINDDM_E_BADARG;
     if ((edit_w || keep_m) && (long long)CHANNELS * H * W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;      // (the maps are indexed with ints)
+    // per-sample seeds: recorded draws win over them, as they win over `seed`; the kernels then never see the array
+    const unsigned long long* sseeds = noise ? nullptr : reinterpret_cast<const unsigned long long*>(sample_seeds);
+    if (sseeds && ((long long)CHANNELS * H * W > 0x7fffffffLL || B > 65535)) return SINDDM_E_BADSHAPE;  // (per-sample quads are ints)
     // (the plain fused tail reads the maps and the draws as 16-byte vectors)
     if (((reinterpret_cast<uintptr_t>(edit_w) | reinterpret_cast<uintptr_t>(edit_c) | reinterpret_cast<uintptr_t>(noise) |
           reinterpret_cast<uintptr_t>(keep_m) | reinterpret_cast<uintptr_t>(keep_x0)) & 15) != 0)
@@ -1620,7 +1739,7 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     // in a partly filled round and pays its fixed ramp / drain, and each step is a chain of 16 dependent launches.  The
     // chains of the batch are independent, so with a second stream the batch runs as TWO half-batches whose launches
     // overlap: the tail round of one fills with the other's items.  Same numbers either way (the noise is keyed on the
-    // whole batch's flat index: ChainStep::b0).
+    // whole batch's flat index: ChainStep::b0; with per-sample seeds the second half gets its own part of the array).
     const long long items = (long long)B * ((fwd_pitch(p, W) + 31) / 32) * ((H + 7) / 8) * 2;
     const long long ncu = wino2_cu_count();
     const long long rounds = (items + ncu - 1) / ncu;
@@ -1688,13 +1807,30 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                 cs.edit_w = edit_w; cs.edit_c = edit_c; cs.noise = noise ? noise + (size_t)i * (size_t)n : nullptr;
                 cs.keep_m = keep_m; cs.keep_x0 = keep_x0;
                 if (keep_m) { cs.keep_a = keep_ab[2 * i]; cs.keep_b = keep_ab[2 * i + 1]; }
+                cs.sseeds = sseeds ? sseeds + (h ? Bh[0] : 0) : nullptr;
                 rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
                                       h ? sx : st, nullptr, &cs);
                 if (tiled && fuse_tail && rc == 0)
                     rc = wrap_halo_launch(nxt + o, nullptr, Bh[h] * CHANNELS, Hc, Wc, halo_y, halo_x, h ? sx : st);
             }
             if (rc) break;
-            if (!fuse_tail) {
+            if (!fuse_tail && sseeds) {
+                const int chw = CHANNELS * H * W;
+                unsigned gx = (unsigned)(((chw + 3) / 4 + 255) / 256);
+                if (gx > 8192) gx = 8192;
+                const unsigned long long sid = (unsigned long long)(stream_id0 + (uint64_t)i);
+                const float ka = keep_m ? keep_ab[2 * i] : 1.0f, kb = keep_m ? keep_ab[2 * i + 1] : 0.0f;
+#define SINDDM_SEEDED_TAIL(E, K)                                                                                          \
+    hipLaunchKernelGGL((reverse_step_rng_samples_kernel<E, K>), dim3(gx, (unsigned)B), dim3(256), 0, st, cur, eps, x_tilde, nxt,  \
+                       coefs[i], sid, sseeds, edit_w, edit_c, chw, H * W, keep_m, keep_x0, ka, kb)
+                if (edit_w && keep_m) SINDDM_SEEDED_TAIL(true, true);
+                else if (edit_w) SINDDM_SEEDED_TAIL(true, false);
+                else if (keep_m) SINDDM_SEEDED_TAIL(false, true);
+                else SINDDM_SEEDED_TAIL(false, false);
+#undef SINDDM_SEEDED_TAIL
+                if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
+                if (tiled && (rc = wrap_halo_launch(nxt, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st)) != 0) break;
+            } else if (!fuse_tail) {
                 SINDDM_TAIL_LAUNCH(reverse_step_rng_kernel, tail_variant(edit_w, noise, keep_m), dim3((unsigned)bx), st, cur, eps,
                                    x_tilde, nxt, coefs[i], n, (unsigned long long)seed,
                                    (unsigned long long)(stream_id0 + (uint64_t)i), edit_w, edit_c,
@@ -1729,7 +1865,7 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
                            uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                            void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1745,10 +1881,19 @@ int sinddm_sample_chain_keep(const float* params, const float* packed, float* x,
                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep) {
+    return sinddm_sample_chain_seeds(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
+                                     H, W, ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr);
+}
+
+int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
+                              const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
     if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
     if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds);
 }
 
 int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,

@@ -68,13 +68,22 @@ def gather_batch(local: torch.Tensor, global_batch: int, force: bool = False, pa
 
 
 def seed_for_rank(base_seed: int) -> int:
-    """Every rank draws its own noise stream (seed + rank)."""
+    """Every rank draws its own noise stream (seed + rank).  Unseeded runs only: with per-sample seeds
+    (`shard_seeds`) the noise does not depend on the rank."""
     return int(base_seed) + rank()
 
 
 def shard_offset(global_batch: int) -> int:
     """Global index of this rank's first sample."""
     return sum(shard_sizes(global_batch, world_size())[:rank()])
+
+
+def shard_seeds(seeds):
+    """This rank's part of the GLOBAL list of per-sample noise seeds: seeds[shard_offset : shard_offset + local_batch], the
+    samples `gather_batch` puts back at those positions.  The whole list on a single process."""
+    seeds = list(seeds)
+    o = shard_offset(len(seeds))
+    return seeds[o:o + local_batch(len(seeds))]
 
 
 def allreduce_sum_(t: torch.Tensor, force: bool = False) -> torch.Tensor:

@@ -12,6 +12,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
                                 replacement of the known region after every reverse step)
   tileable sampling (`tile`) -> sinddm_sample_chain_tile / sinddm_wrap_halo / sinddm_upsample_bilinear_wrap
                                 (no reference line: padding_mode='circular' on its nn.Conv2d's)
+  per-sample noise seeds     -> sinddm_sample_chain_seeds / sinddm_normal_fill_samples   (`sample_seeds`; no reference
+                                line: the reference never seeds its generator)
 
 There is no CPU / eager-PyTorch fallback: tensors must live on a ROCm device and the shared
 library must be built, otherwise calls raise.
@@ -89,6 +91,68 @@ def _workspace(device: torch.device, nbytes: int, tag: str = "fwd") -> torch.Ten
 # cut into pieces whose recorded draws fit.  1 GiB is 6 steps of C3's finest scale at batch 64 (161 MB per step) and the
 # whole 521-step run of C2's 67x90 scale at batch 16 (1.2 MB per step).
 CHAIN_NOISE_BYTES = 1 << 30
+
+# ---- per-sample noise seeds (include/sinddm_hip.h "the noise contract") -------------------------------------
+SEED_LIMIT = 1 << 63          # a sample seed is a Python int in [0, 2^63): 8 bytes on the device
+_STREAM_KINDS = {"init": 0, "renoise": 1, "step": 2}
+
+
+def noise_stream_id(s: int, kind: str, i: int = 0) -> int:
+    """Stream id of one draw of a seeded sample: (s << 32) | k with k = 0 the initial draw of p_sample_loop at scale s,
+    k = 1 the re-noise draw of p_sample_via_scale_loop, k = 2 + i the reverse step at position i of the scale's run (counted
+    from the run's first step).  The ONE owner of this layout: the fused route hands noise_stream_id(s, "step", 0) to the
+    library as stream_id0, the step-by-step route asks for every position."""
+    k = _STREAM_KINDS[kind]
+    s, i = int(s), int(i)
+    if kind != "step" and i != 0:
+        raise ValueError(f"the {kind!r} draw of a scale has no position")
+    if not (0 <= s < (1 << 31)) or not (0 <= i < (1 << 32) - 2):
+        raise ValueError(f"noise_stream_id: scale {s} / position {i} out of range")
+    return (s << 32) | (k + i)
+
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x: int) -> int:
+    """One output of splitmix64 (Steele, Lea, Flood 2014) for the state x: a bijection of the 64-bit integers."""
+    z = (int(x) + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _check_seed_row(row, what: str = "sample_seeds"):
+    out = []
+    for v in row:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: a seed must be an int, got {v!r}")
+        v = int(v)
+        if not 0 <= v < SEED_LIMIT:
+            raise ValueError(f"{what}: seed {v} is outside [0, 2^63)")
+        out.append(v)
+    return out
+
+
+def vary_seeds(seeds, from_scale: int, n_scales: int):
+    """The 2-D [n_scales][B] form of `sample_seeds` for SinGAN-style variations: scales below `from_scale` keep `seeds`,
+    every scale from `from_scale` on uses derived seeds -- same coarse structure, fresh fine detail.  Sample b's derived seed
+    is splitmix64(seeds[b] ^ splitmix64(b + 1)) >> 1 (63 bits); should it equal the derived seed of an earlier sample of the
+    row, splitmix64 is applied again until it does not.  So the result is a pure function of (seeds, from_scale, n_scales),
+    and derived seeds are distinct for distinct b even when the given seeds are equal."""
+    seeds = _check_seed_row(seeds, "vary_seeds")
+    from_scale, n_scales = int(from_scale), int(n_scales)
+    if not 0 <= from_scale <= n_scales:
+        raise ValueError(f"vary_seeds: from_scale {from_scale} is outside [0, {n_scales}]")
+    derived, used = [], set()
+    for b, v in enumerate(seeds):
+        z = _splitmix64(v ^ _splitmix64(b + 1))
+        while (z >> 1) in used:
+            z = _splitmix64(z)
+        used.add(z >> 1)
+        derived.append(z >> 1)
+    return [list(seeds) if s < from_scale else list(derived) for s in range(n_scales)]
+
 
 _AUX: Dict[int, "torch.cuda.Stream"] = {}
 
@@ -445,6 +509,12 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
         # values between 0 and 1 blend.  A sampling option, like `tile`; not available with CLIP guidance.
         self.keep_maps = None
+        # per-sample noise seeds: None (the draws come from torch's generators, as ever), a sequence of B ints in [0, 2^63)
+        # (one seed per sample, used at every scale) or a [n_scales][B] nested sequence (row s at scale s; `vary_seeds`).
+        # With seeds every N(0,1) draw of sample b -- initial, re-noise, every reverse step -- is a function of
+        # (seed of b, noise_stream_id, element index inside the sample) alone: the sample does not depend on its batch, its
+        # position in it, the two-stream split or the rank that runs it.  Not together with `noise_fn`.
+        self.sample_seeds = None
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -460,7 +530,53 @@ class MultiScaleGaussianDiffusion(nn.Module):
             self._host_tabs, self._host_ver = h, ver
         return self._host_tabs
 
-    def _draw(self, kind: str, shape, s: int, t: int, device) -> torch.Tensor:
+    def _seeds_for(self, s: int, B: int):
+        """The B seeds of scale s from `sample_seeds` (validated), or None when unset."""
+        ss = self.sample_seeds
+        if ss is None:
+            return None
+        if self.noise_fn is not None:
+            raise ValueError("sample_seeds and noise_fn are both set: two noise sources")
+        if isinstance(ss, (torch.Tensor, np.ndarray)):
+            ss = ss.tolist()
+        ss = list(ss)
+        if len(ss) > 0 and isinstance(ss[0], (list, tuple, np.ndarray, torch.Tensor)):
+            if len(ss) != self.n_scales:
+                raise ValueError(f"sample_seeds has {len(ss)} rows for {self.n_scales} scales")
+            row = ss[min(int(s), self.n_scales - 1)]        # (custom sizes past the pyramid sample with the finest scale's row)
+            row = row.tolist() if isinstance(row, (np.ndarray, torch.Tensor)) else list(row)
+        else:
+            row = ss
+        if len(row) != int(B):
+            raise ValueError(f"sample_seeds holds {len(row)} seeds for a batch of {int(B)}")
+        return _check_seed_row(row)
+
+    def _seeded_normal(self, seeds, shape, sid: int, device) -> torch.Tensor:
+        """(B, ...) N(0,1): slice b = sinddm_normal_fill(numel per sample, seeds[b], sid)."""
+        lib = _lib.load()
+        shape = tuple(int(v) for v in shape)
+        z = torch.empty(shape, dtype=torch.float32, device=device)
+        sd = torch.tensor(seeds, dtype=torch.int64, device=device)
+        _lib.check(lib.sinddm_normal_fill_samples(_lib.ptr(z), shape[0], z.numel() // shape[0], _lib.ptr(sd), int(sid),
+                                                  _lib.stream_ptr(z.device)), "sinddm_normal_fill_samples")
+        return z
+
+    def _draw(self, kind: str, shape, s: int, t: int, device, pos: int = 0) -> torch.Tensor:
+        """One N(0,1) draw of the sampler: `kind` 'init' / 'renoise' / 'step' (`pos` = the step's position in its run)."""
+        seeds = self._seeds_for(s, shape[0])
+        if seeds is not None:
+            sid = noise_stream_id(s, kind, pos)
+            hy, hx = self._tile_halo()
+            if kind == "step" and (hy or hx):
+                # the tiled chain draws over the EXTENDED sample and discards the halo's draws: take the centre
+                H, W = int(shape[-2]), int(shape[-1])
+                z = self._seeded_normal(seeds, tuple(shape[:-2]) + (H + 2 * hy, W + 2 * hx), sid, device)
+                z = z[..., hy:hy + H, hx:hx + W].contiguous()
+            else:
+                z = self._seeded_normal(seeds, shape, sid, device)
+            if self.draw_log is not None:
+                self.draw_log.append((kind, int(s), int(t), z.clone()))
+            return z
         if self.noise_fn is not None:
             return self.noise_fn(kind, tuple(shape), int(s), int(t), device).contiguous()
         z = torch.randn(tuple(shape), device=device)
@@ -618,7 +734,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 x_t_mix = x_tm1_mix if ((not self.reblurring) or s == 0) else x_t_mix.clamp(-1., 1.)
             return self.q_posterior(x_start=x_tm1_mix, x_t_mix=x_t_mix, x_t=x, t=t, s=s)
 
-    def _p_sample_guided(self, x, t_host: int, s: int, clip_denoised: bool, repeat_noise: bool):
+    def _p_sample_guided(self, x, t_host: int, s: int, clip_denoised: bool, repeat_noise: bool, step_pos: int = 0):
         """p_sample (models.py:449-459) through p_mean_variance in eager torch ops: the path of CLIP-guided steps (the
         fused reverse-step kernel has no place for an external autograd call between x_recon and the posterior)."""
         t = torch.full((x.shape[0],), int(t_host), device=x.device, dtype=torch.long)
@@ -626,7 +742,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
         if repeat_noise:
             z = noise_like(x.shape, x.device, True)
         else:
-            z = self._draw("step", x.shape, s, t_host, x.device)
+            z = self._draw("step", x.shape, s, t_host, x.device, step_pos)
         nonzero = 0.0 if t_host == 0 else 1.0
         return mean + nonzero * (0.5 * logvar).exp() * z
 
@@ -712,9 +828,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
         route extends each network input instead (`_eps`) and steps the centre: it is the cross-check of the tiled chain.
         With `keep_maps` set the scale's mask and known image (wrapped like the edit maps when tiled) and the per-step
         forward scalars go to sinddm_sample_chain_keep: still one call, with ROI maps, `chain_noise` and two streams alike;
-        the step-by-step route replaces through sinddm_reverse_step_keep."""
+        the step-by-step route replaces through sinddm_reverse_step_keep.
+        With `sample_seeds` set the call is sinddm_sample_chain_seeds: sample b's step at position i of the run draws
+        sinddm_normal_fill(3 H W, seed_b, noise_stream_id(s, 'step', i)) inside the step kernel, and no seed is taken from
+        torch's generator; the step-by-step route fills the same numbers through sinddm_normal_fill_samples."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
+        sseeds = self._seeds_for(s, img.shape[0])
         keep = self._keep_entry(s, img)
         roi = bool(self.roi_guided_sampling and s < self.n_scales - 1)     # models.py:430-431
         fast = ((self.noise_fn is None or self.chain_noise) and isinstance(self.denoise_fn, SinDDMNet)
@@ -722,8 +842,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 and len(t_seq) > 0 and img.is_cuda and img.dtype == torch.float32 and img.dim() == 4
                 and img.shape[1] == self.channels == 3)
         if not fast:
-            for i in t_seq:
-                img = self._p_sample_host_t(img, i, s)
+            for pos, i in enumerate(t_seq):
+                img = self._p_sample_host_t(img, i, s, step_pos=pos)
                 self._dump_interm(img, s, f'output_t-{i:03}_s-{s}.png')
             return img
         lib = _lib.load()
@@ -767,16 +887,20 @@ class MultiScaleGaussianDiffusion(nn.Module):
         aux = _aux_stream(x.device) if self.two_streams else None
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
 
-        def chain(i0, k, seed, noise):
+        def chain(i0, k, seed, noise, sid0=0, seeds_dev=None):
             nonlocal x, x_alt
             opts.noise = _lib.ptr(noise)
             in_alt = C.c_int(0)
             args = (_lib.ptr(net.flat_params), _lib.ptr(packed), _lib.ptr(x), _lib.ptr(x_alt), _lib.ptr(eps), _lib.ptr(xt),
                     C.cast(C.addressof(coefs) + i0 * C.sizeof(_lib.StepCoefs), C.POINTER(_lib.StepCoefs)),
-                    C.cast(C.addressof(tl) + i0 * C.sizeof(C.c_int), C.POINTER(C.c_int)), k, float(s), seed, 0, net.dim_arg,
+                    C.cast(C.addressof(tl) + i0 * C.sizeof(C.c_int), C.POINTER(C.c_int)), k, float(s), seed, sid0, net.dim_arg,
                     B, Hc, Wc, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts))
             if kopts is not None:
                 kopts.ab = C.cast(C.addressof(ab) + 2 * i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
+            if seeds_dev is not None:
+                _lib.check(lib.sinddm_sample_chain_seeds(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
+                                                         _lib.ptr(seeds_dev)), "sinddm_sample_chain_seeds")
+            elif kopts is not None:
                 _lib.check(lib.sinddm_sample_chain_keep(*args, hy, hx, C.byref(kopts)), "sinddm_sample_chain_keep")
             elif tiled:
                 _lib.check(lib.sinddm_sample_chain_tile(*args, hy, hx), "sinddm_sample_chain_tile")
@@ -798,6 +922,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 for j in range(k):
                     noise[j][:, :, hy:hy + Hc, hx:hx + Wc].copy_(self._draw("step", img.shape, s, t_seq[i0 + j], x.device))
                 chain(i0, k, 0, noise)
+            return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
+        if sseeds is not None:
+            if self.draw_log is not None:
+                # (draw i of sample b is sinddm_normal_fill(3 H W, seeds[b], noise_stream_id(s, 'step', i)), over the
+                # extended size when tiled)
+                self.draw_log.append(("chain_seeds", s, list(sseeds), list(t_seq)))
+            chain(0, n, 0, None, noise_stream_id(s, "step", 0), torch.tensor(sseeds, dtype=torch.int64, device=x.device))
             return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
         # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
         # sample, seeding only the CUDA generator (torch.cuda.manual_seed) does not
@@ -825,15 +956,16 @@ class MultiScaleGaussianDiffusion(nn.Module):
         return self.denoise_fn(x, t_dev, scale=s)                           # plug point, models.py:356
 
     def _p_sample_host_t(self, x: torch.Tensor, t: int, s: int, clip_denoised: bool = True,
-                         repeat_noise: bool = False) -> torch.Tensor:
-        """One reverse step with the timestep known on the host: net forward + ONE fused kernel."""
+                         repeat_noise: bool = False, step_pos: int = 0) -> torch.Tensor:
+        """One reverse step with the timestep known on the host: net forward + ONE fused kernel.  `step_pos`: the step's
+        position in its run -- with `sample_seeds` it selects the draw (noise_stream_id(s, 'step', step_pos))."""
         keep = self._keep_entry(s, x)                                       # (raises under CLIP guidance)
         if self.clip_guided_sampling:
             if self.clip_model is None or self.guidance_sub_iters is None or self.stop_guidance is None:
                 raise RuntimeError("clip_guided_sampling is set but clip_model / guidance_sub_iters / stop_guidance are not: "
                                    "CLIP is outside this build -- assign any object with zero_grad() and a differentiable "
                                    "calculate_clip_loss(image, text_embedds) (reference models.py:193-220, 367-421)")
-            return self._p_sample_guided(x.contiguous(), int(t), int(s), clip_denoised, repeat_noise)
+            return self._p_sample_guided(x.contiguous(), int(t), int(s), clip_denoised, repeat_noise, step_pos)
         lib = _lib.load()
         x = x.contiguous()
         eps = self._eps(x, None, t, s)
@@ -843,7 +975,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
         if repeat_noise:
             z = noise_like(x.shape, x.device, True).contiguous()
         else:
-            z = self._draw("step", x.shape, s, t, x.device)
+            z = self._draw("step", x.shape, s, t, x.device, step_pos)
         k = self.step_coefs(t, s, clip_denoised)
         xt = None
         if k.mode != 0:

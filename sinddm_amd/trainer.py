@@ -291,11 +291,15 @@ class MultiscaleTrainer(object):
     @torch.no_grad()
     def sample_scales(self, scale_mul=None, batch_size=16, custom_sample=False, custom_image_size_idxs=None,
                       custom_scales=None, image_name='', start_noise=True, custom_t_list=None, desc=None,
-                      save_unbatched=True, save_images=True) -> List[torch.Tensor]:
+                      save_unbatched=True, save_images=True, seeds=None, vary_from_scale=None) -> List[torch.Tensor]:
         """Drive the sampler over all scales (behaviour of reference trainer.py:226-285).  Under torch.distributed the
         batch is sharded over ranks as independent chains and gathered with one all-gather per scale (RCCL over xGMI
-        on MI355X); returns the list of per-scale (global) sample batches."""
+        on MI355X); returns the list of per-scale (global) sample batches.
+        `seeds`: the GLOBAL list of `batch_size` per-sample noise seeds (`ema_model.sample_seeds` for the duration of the
+        call; a rank takes the seeds of its own shard, so the gathered batch holds the images a single process makes, in
+        the same order).  `vary_from_scale` = S: scales >= S use seeds derived per sample (`models.vary_seeds`)."""
         em = self.ema_model
+        local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=True)
         # --- what to run: one (scale, size index, start timestep) triple per stage ---
         scales = list(range(self.n_scales)) if custom_scales is None else list(custom_scales)
         size_idx = list(range(self.n_scales)) if custom_image_size_idxs is None else list(custom_image_size_idxs)
@@ -320,26 +324,49 @@ class MultiscaleTrainer(object):
                              'without chains (every rank must join the all-gather)')
         mine = sdist.local_batch(batch_size)
         per_scale, cur, shown = [], None, None
-        for stage, s in enumerate(scales):
-            if stage > 0:
-                cur = em.sample_via_scale(mine, cur, s=s, scale_mul=stretch, custom_sample=custom_sample,
-                                          custom_img_size_idx=size_idx[stage], custom_t=t_starts[int(s) - 1])
-            elif start_noise:
-                cur = em.sample(batch_size=mine, scale_0_size=first_size, s=s)
-            else:                                   # start from the training image of that scale instead of noise
-                seed_img = Image.open(self.input_paths[s] + '/' + image_name).convert('RGB')
-                cur = image_to_tensor(seed_img).repeat(mine, 1, 1, 1).to(self.device)
-            whole = sdist.gather_batch(cur, batch_size)          # identity on a single process
-            per_scale.append(whole)
-            if writer:
-                shown = (whole + 1) * 0.5
-                save_image(shown, str(out_dir / t_tag) + f'_out_s{stage}_{tag}_sm_{stretch[0]}_{stretch[1]}.png', nrow=4)
+        prev_seeds = em.sample_seeds
+        if local_seeds is not None:
+            em.sample_seeds = local_seeds
+        try:
+            for stage, s in enumerate(scales):
+                if stage > 0:
+                    cur = em.sample_via_scale(mine, cur, s=s, scale_mul=stretch, custom_sample=custom_sample,
+                                              custom_img_size_idx=size_idx[stage], custom_t=t_starts[int(s) - 1])
+                elif start_noise:
+                    cur = em.sample(batch_size=mine, scale_0_size=first_size, s=s)
+                else:                                   # start from the training image of that scale instead of noise
+                    seed_img = Image.open(self.input_paths[s] + '/' + image_name).convert('RGB')
+                    cur = image_to_tensor(seed_img).repeat(mine, 1, 1, 1).to(self.device)
+                whole = sdist.gather_batch(cur, batch_size)          # identity on a single process
+                per_scale.append(whole)
+                if writer:
+                    shown = (whole + 1) * 0.5
+                    save_image(shown, str(out_dir / t_tag) + f'_out_s{stage}_{tag}_sm_{stretch[0]}_{stretch[1]}.png', nrow=4)
+        finally:
+            em.sample_seeds = prev_seeds
         if writer and save_unbatched and shown is not None:
             single_dir = Path(str(self.results_folder / f'final_samples_unbatched_{tag}'))
             single_dir.mkdir(parents=True, exist_ok=True)
             for b, one in enumerate(shown):
                 save_image(one, str(single_dir / t_tag) + f'_out_b{b}.png')
         return per_scale
+
+    def _local_seeds(self, seeds, vary_from_scale, batch_size, sharded):
+        """`ema_model.sample_seeds` of a driver call: None without `seeds`; else the global list (checked against
+        `batch_size`), expanded per scale when `vary_from_scale` is given, and -- for the drivers that shard the batch over
+        ranks -- cut to this rank's samples.  The variation is derived from the GLOBAL position, before the cut."""
+        from .models import _check_seed_row, vary_seeds
+        if seeds is None:
+            if vary_from_scale is not None:
+                raise ValueError('vary_from_scale needs seeds')
+            return None
+        seeds = _check_seed_row(list(seeds), 'seeds')
+        if len(seeds) != int(batch_size):
+            raise ValueError(f'{len(seeds)} seeds for batch_size={int(batch_size)}')
+        rows = [seeds] if vary_from_scale is None else vary_seeds(seeds, vary_from_scale, self.n_scales)
+        if sharded:
+            rows = [sdist.shard_seeds(r) for r in rows]
+        return rows[0] if vary_from_scale is None else rows
 
     # ---- application drivers of the reference that run entirely on the hot path (SURVEY 8(f) row 4) ----
     def _i2i_source(self, input_folder, input_file, mask, hist_ref_path, image_name, use_hist, auto_scale, mode, device):
@@ -366,14 +393,16 @@ class MultiscaleTrainer(object):
     @torch.no_grad()
     def image2image(self, input_folder='', input_file='', mask='', hist_ref_path='', image_name='', start_s=1,
                     custom_t=None, batch_size=16, scale_mul=(1, 1), device=None, use_hist=False, save_unbatched=True,
-                    auto_scale=None, mode=None, save_images=True):
+                    auto_scale=None, mode=None, save_images=True, seeds=None, vary_from_scale=None):
         """Harmonization / style transfer (behaviour of reference trainer.py:287-362): the input image is re-noised at
         scale `start_s` to `custom_t[start_s]` and denoised through the remaining scales by the trained model; in
         harmonization mode the result is pasted into the input through the dilated mask.  Returns the per-scale sample
-        batches (the reference only writes PNGs)."""
+        batches (the reference only writes PNGs).  `seeds` / `vary_from_scale`: as in `sample_scales` (this driver does
+        not shard the batch: every process runs all `batch_size` chains)."""
         import os
         device = self.device if device is None else device
         em = self.ema_model
+        local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=False)
         t_starts = em.num_timesteps_ideal if custom_t is None else custom_t
         src, keep = self._i2i_source(input_folder, input_file, mask, hist_ref_path, image_name, use_hist, auto_scale,
                                      mode, device)
@@ -389,19 +418,25 @@ class MultiscaleTrainer(object):
             out_dir.mkdir(parents=True, exist_ok=True)
         last = self.n_scales - 1
         outs, shown = [], None
-        for s in range(start_s, self.n_scales):
-            # target size of this scale: the (possibly shrunk) input divided by scale_factor^(scales still to go)
-            hw = src_hw / (self.scale_factor ** (last - s))
-            target = (int(hw[0].item()), int(hw[1].item()))
-            outs.append(em.sample_via_scale(batch_size, batch if not outs else outs[-1], s=s, custom_t=t_starts[s],
-                                            scale_mul=scale_mul, custom_image_size=target))
-            shown = (outs[-1] + 1) * 0.5
-            if s == last:
-                shown = keep * shown + (1 - keep) * ((batch + 1) * 0.5).clamp_(0.0, 1.0)
-            if save_images:
-                stem = input_file.rsplit(".", 1)[0]
-                save_image(shown, str(out_dir / f'{stem}_i2i_s_{s}_t_{t_tag}_hist_{"on" if use_hist else "off"}_{stamp}.png'),
-                           nrow=4)
+        prev_seeds = em.sample_seeds
+        if local_seeds is not None:
+            em.sample_seeds = local_seeds
+        try:
+            for s in range(start_s, self.n_scales):
+                # target size of this scale: the (possibly shrunk) input divided by scale_factor^(scales still to go)
+                hw = src_hw / (self.scale_factor ** (last - s))
+                target = (int(hw[0].item()), int(hw[1].item()))
+                outs.append(em.sample_via_scale(batch_size, batch if not outs else outs[-1], s=s, custom_t=t_starts[s],
+                                                scale_mul=scale_mul, custom_image_size=target))
+                shown = (outs[-1] + 1) * 0.5
+                if s == last:
+                    shown = keep * shown + (1 - keep) * ((batch + 1) * 0.5).clamp_(0.0, 1.0)
+                if save_images:
+                    stem = input_file.rsplit(".", 1)[0]
+                    save_image(shown, str(out_dir / f'{stem}_i2i_s_{s}_t_{t_tag}_hist_{"on" if use_hist else "off"}_{stamp}.png'),
+                               nrow=4)
+        finally:
+            em.sample_seeds = prev_seeds
         if save_images and save_unbatched:
             single_dir = Path(str(self.results_folder / f'unbatched_i2i_s{start_s}_t_{t_tag}_{stamp}'))
             single_dir.mkdir(parents=True, exist_ok=True)
@@ -412,7 +447,7 @@ class MultiscaleTrainer(object):
 
     @torch.no_grad()
     def roi_guided_sampling(self, custom_t_list=None, target_roi=None, roi_bb_list=None, save_unbatched=False,
-                            batch_size=4, scale_mul=(1, 1), save_images=True):
+                            batch_size=4, scale_mul=(1, 1), save_images=True, seeds=None, vary_from_scale=None):
         """ROI guided generation (trainer.py:436-454): at every scale but the finest the predicted clean image is
         pulled (eta = 0.8) towards a patch of the training image inside the given boxes; the blend runs inside the
         step kernels of the sampler's chain call (`sinddm_sample_chain_ex` with edit maps: one library call per scale,
@@ -430,7 +465,8 @@ class MultiscaleTrainer(object):
             return self.sample_scales(scale_mul=scale_mul, custom_sample=False, image_name='', batch_size=batch_size,
                                       custom_t_list=custom_t_list,
                                       desc=f'roi_{str(datetime.datetime.now()).replace(":", "_")}',
-                                      save_unbatched=save_unbatched, start_noise=True, save_images=save_images)
+                                      save_unbatched=save_unbatched, start_noise=True, save_images=save_images,
+                                      seeds=seeds, vary_from_scale=vary_from_scale)
         finally:
             em.roi_guided_sampling = False
 
@@ -445,7 +481,8 @@ class MultiscaleTrainer(object):
             em.keep_maps = None
 
     @torch.no_grad()
-    def inpaint(self, mask, batch_size=16, hard=True, custom_t_list=None, save_unbatched=False, save_images=True):
+    def inpaint(self, mask, batch_size=16, hard=True, custom_t_list=None, save_unbatched=False, save_images=True,
+                seeds=None, vary_from_scale=None):
         """Fill a hole in the training image: `mask` is (H, W) at the finest scale's size, 1 = keep the training image's
         pixel, 0 = generate.  At every scale the known image is that scale's training image and the mask comes from
         `functions.keep_mask_pyramid` (`hard`: a coarse pixel is kept only if its whole footprint is known); after every
@@ -461,11 +498,12 @@ class MultiscaleTrainer(object):
         maps = {s: (masks[s].to(self.device).contiguous(), self.data_list[s][0][0].contiguous())
                 for s in range(self.n_scales)}
         return self._sample_kept(maps, 'inpaint', batch_size=batch_size, custom_t_list=custom_t_list,
-                                 save_unbatched=save_unbatched, save_images=save_images)
+                                 save_unbatched=save_unbatched, save_images=save_images, seeds=seeds,
+                                 vary_from_scale=vary_from_scale)
 
     @torch.no_grad()
     def outpaint(self, scale_mul, anchor=(0.5, 0.5), batch_size=16, custom_t_list=None, save_unbatched=False,
-                 save_images=True):
+                 save_images=True, seeds=None, vary_from_scale=None):
         """Grow the canvas around the training image: at every scale the sample has `target_size(s, scale_mul)`, the
         scale's own training image sits unresampled at int(anchor * (canvas - image)) and is kept (mask 1 on that
         rectangle), the rest is generated.  `scale_mul` < 1 on an axis is a ValueError."""
@@ -485,7 +523,8 @@ class MultiscaleTrainer(object):
             m[y0:y0 + h, x0:x0 + w] = 1.0
             maps[s] = (m, k0)
         return self._sample_kept(maps, 'outpaint', scale_mul=tuple(scale_mul), batch_size=batch_size,
-                                 custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images)
+                                 custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
+                                 seeds=seeds, vary_from_scale=vary_from_scale)
 
     # ---- CLIP-driven modes of the reference.  CLIP itself (clip/, text2live_util/) is not part of this build; the
     # driver takes any `clip_model` with the interface the reference uses: get_text_embedding(text, template=...),
