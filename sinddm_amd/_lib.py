@@ -77,6 +77,9 @@ def load() -> C.CDLL:
         raise SinddmError(str(e)) from None
     lib = C.CDLL(LIB_PATH)
     p, i, i64, f, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+    # what every sinddm_sample_chain* entry starts with: params .. stream, aux_stream, result_in_alt
+    chain = [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64, i, i, i, i, p, sz, p, p,
+             C.POINTER(C.c_int)]
     sig = {
         "sinddm_abi_version": (i, []),
         "sinddm_param_count": (i64, [i]),
@@ -91,20 +94,12 @@ def load() -> C.CDLL:
         "sinddm_q_sample": (i, [p, p, p, p, p, p, p, p, i, i, i64, p]),
         "sinddm_reverse_step": (i, [p, p, p, p, p, C.POINTER(StepCoefs), i64, p]),
         "sinddm_reverse_step_edit": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, p]),
-        "sinddm_sample_chain": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
-                                    i, i, i, i, p, sz, p, C.POINTER(C.c_int)]),
-        "sinddm_sample_chain2": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
-                                     i, i, i, i, p, sz, p, p, C.POINTER(C.c_int)]),
-        "sinddm_sample_chain_ex": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
-                                       i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts)]),
-        "sinddm_sample_chain_tile": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
-                                         i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i]),
-        "sinddm_sample_chain_keep": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
-                                         i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i,
-                                         C.POINTER(KeepOpts)]),
-        "sinddm_sample_chain_seeds": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64,
-                                          i, i, i, i, p, sz, p, p, C.POINTER(C.c_int), C.POINTER(ChainOpts), i, i,
-                                          C.POINTER(KeepOpts), p]),
+        "sinddm_sample_chain": (i, chain[:-2] + [C.POINTER(C.c_int)]),                      # (no aux_stream)
+        "sinddm_sample_chain2": (i, chain),
+        "sinddm_sample_chain_ex": (i, chain + [C.POINTER(ChainOpts)]),
+        "sinddm_sample_chain_tile": (i, chain + [C.POINTER(ChainOpts), i, i]),
+        "sinddm_sample_chain_keep": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts)]),
+        "sinddm_sample_chain_seeds": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p]),
         "sinddm_normal_fill_samples": (i, [p, i, i64, p, C.c_uint64, p]),
         "sinddm_reverse_step_keep": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, p, p, f, f, i, i, i, p]),
         "sinddm_wrap_halo": (i, [p, p, i, i, i, i, i, p]),

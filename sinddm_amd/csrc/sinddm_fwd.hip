@@ -5,6 +5,8 @@
 #include "conv_wino4.h"
 #include "conv_wh.h"
 #include "internal.h"
+#include "step_tail.h"
+#include <type_traits>
 namespace sinddm {
 
 ConvProfiler& conv_profiler() {
@@ -250,6 +252,18 @@ struct CondArgs {
     float* emb_out;      // optional [B][64] sinusoidal embedding
     float* mvec_out;     // optional [B][4][32] per-block mlp outputs
 };
+// the plan's part of the arguments: parameter offsets and the row layout (the caller adds t, scale and the outputs)
+static CondArgs cond_args(const NetPlan& P, const float* params) {
+    CondArgs ca{};
+    ca.params = params; ca.cond_stride = P.cond_stride;
+    ca.tm0_w = P.tm0_w; ca.tm0_b = P.tm0_b; ca.tm2_w = P.tm2_w; ca.tm2_b = P.tm2_b;
+    for (int l = 0; l < 4; ++l) {
+        ca.mlp_w[l] = P.blk[l].mlp_w; ca.mlp_b[l] = P.blk[l].mlp_b;
+        ca.tr_w[l] = P.blk[l].tr_w; ca.tr_b[l] = P.blk[l].tr_b;
+        ca.cin[l] = P.blk[l].cin; ca.coff[l] = P.blk[l].cond_off;
+    }
+    return ca;
+}
 
 __global__ __launch_bounds__(128) void cond_kernel(CondArgs a) {
     __shared__ float emb[64];
@@ -748,401 +762,7 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
 }
 
-// EDIT: the predicted clean image is replaced by  w(p) * x_recon + c(ch, p)  before the re-blur mix / clamps --
-// the ROI-guided sampling of the reference (models.py:291-298,430-431) written as a per-pixel affine map
-// (sequential `eta*patch + (1-eta)*x` blends over possibly overlapping boxes compose into one such map).
-// x_{t-1} mean of one element: predict_start_from_noise + p_mean_variance (normal branch) + q_posterior
-// (reference SinDDM/models.py:306-352,433-447); `w`, `c` = ROI edit map (1, 0 without ROI guidance)
-__device__ __forceinline__ float reverse_step_mean(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c,
-                                                   bool edit) {
-    float x0 = k.sqrt_recip_ac_t * x - k.sqrt_recipm1_ac_t * e;                   // models.py:308-309
-    if (k.mode == 0) {
-        if (edit) x0 = w * x0 + c;              // x_recon and x_t_mix are the same tensor here (models.py:311-312)
-        const float x0c = k.clip ? fminf(fmaxf(x0, -1.0f), 1.0f) : x0;
-        return k.coef1_t * x0c + k.coef2_t * x;                                   // models.py:324-327
-    }
-    float xp = (x0 - k.gamma_t * xb) / (1.0f - k.gamma_t);                        // models.py:315-316
-    if (edit) xp = w * xp + c;
-    if (k.mode == 1) {
-        float mix = k.gamma_tm1 * xb + (1.0f - k.gamma_tm1) * xp;                 // models.py:435-436
-        float x0c = x0;
-        if (k.clip) {
-            mix = fminf(fmaxf(mix, -1.0f), 1.0f);
-            x0c = fminf(fmaxf(x0, -1.0f), 1.0f);
-        }
-        return k.sqrt_ac_tm1 * mix + k.sqrt_1m_ac_tm1_mvar * (x - k.sqrt_ac_t * x0c) / k.sqrt_1m_ac_t;  // :342-345
-    }
-    return k.clip ? fminf(fmaxf(xp, -1.0f), 1.0f) : xp;                           // models.py:347-348
-}
-
-// KEEP: known-region conditioning (inpainting / outpainting; RePaint-style replacement, no reference line).  Where the mask
-// m(p) is 1 the step's output is replaced by a sample of q(x_{t-1} | known image k0) -- SinDDM's blurred forward process
-// at t-1 -- built from the SAME draw z the step uses (one Gaussian per pixel in either branch); in between the two are
-// blended.  `plain` is what the step writes without the option, `xb` x-tilde (0 in mode 0), ka / kb the forward scalars
-// sqrt(ac[t-1]) / sqrt(1 - ac[t-1]) ((1, 0) at t == 0).  Written so that m == 0 gives `plain` and m == 1 gives `kept`
-// exactly; the keep target is not clamped.
-__device__ __forceinline__ float keep_blend(const sinddm_step_coefs& k, float plain, float z, float xb, float m, float k0,
-                                            float ka, float kb) {
-    const float target = k.mode == 1 ? k.gamma_tm1 * xb + (1.0f - k.gamma_tm1) * k0 : k0;
-    const float kept = ka * target + kb * z;
-    return m * kept + (1.0f - m) * plain;
-}
-
-// EDIT: the predicted clean image is replaced by  w(p) * x_recon + c(ch, p)  before the re-blur mix / clamps --
-// the ROI-guided sampling of the reference (models.py:291-298,430-431) written as a per-pixel affine map
-// (sequential `eta*patch + (1-eta)*x` blends over possibly overlapping boxes compose into one such map).
-// KEEP: see keep_blend; km = the mask (hw floats), kx = the known image (chw floats), both shared by all samples like the
-// edit maps.  EDIT and KEEP may be on together: the edit acts on x_recon, the keep on the output.
-template <bool EDIT, bool KEEP>
-__global__ __launch_bounds__(256) void reverse_step_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
-                                                           const float* __restrict__ xtil, const float* __restrict__ z,
-                                                           float* __restrict__ out, sinddm_step_coefs k, long long n,
-                                                           const float* __restrict__ ew, const float* __restrict__ ec,
-                                                           int chw, int hw, const float* __restrict__ km,
-                                                           const float* __restrict__ kx, float ka, float kb) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float w = 1.0f, c = 0.0f;
-        const int q = (EDIT || KEEP) ? (int)(i % chw) : 0;
-        if (EDIT) {
-            w = ew[q % hw];
-            c = ec[q];
-        }
-        const float xb = k.mode != 0 ? xtil[i] : 0.0f;
-        const float mean = reverse_step_mean(k, xt[i], eps[i], xb, w, c, EDIT);
-        const float o = mean + k.sigma * z[i];                                    // models.py:459
-        out[i] = KEEP ? keep_blend(k, o, z[i], xb, km[q % hw], kx[q], ka, kb) : o;
-    }
-}
-
-// ---- the same step with the Gaussian noise of models.py:455 drawn INSIDE the kernel (counter-based Philox4x32-10 +
-// Box-Muller): no randn launch, no noise tensor (12 B/px less traffic).  Stream = (seed, step id, element index); the
-// reference never seeds its generator, so there is no bit-level noise contract -- parity tests keep injecting noise
-// through sinddm_reverse_step.
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned long long step, unsigned long long idx4,
-                                               float (&z)[4]) {
-    unsigned c[4] = {(unsigned)idx4, (unsigned)(idx4 >> 32), (unsigned)step, (unsigned)(step >> 32)};
-    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
-    // uniforms in (0, 1]: (x + 1) * 2^-32 evaluated so that 0 is never produced
-    const float u0 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f), u1 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2] >> 8) + 1.0f) * (1.0f / 16777216.0f), u3 = (float)(c[3] >> 8) * (1.0f / 16777216.0f);
-    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-    float s0, c0, s1, c1;
-    sincospif(2.0f * u1, &s0, &c0);
-    sincospif(2.0f * u3, &s1, &c1);
-    z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
-}
-
-// The three tails of a sampler-run step share three compile-time options (sinddm_sample_chain_ex / _keep); the plain
-// instantiations <false, false, false> are the kernels the chain always ran:
-//   EDIT   the ROI edit of reverse_step_kernel<true, *>: w = ew[p], c = ec[ch * HW + p], shared by all samples
-//   NOISE  z is READ from `nz` (this step's B_total*3*HW recorded draws) at the element's flat index inside the whole batch
-//          instead of drawn from Philox; steps with sigma == 0 (and, under KEEP, kb == 0) read nothing
-//   KEEP   the known-region replacement of keep_blend on the step's output: m = km[p], k0 = kx[ch * HW + p], shared by all
-//          samples and read like the edit maps; z is drawn (or read) when sigma != 0 OR kb != 0
-// Per-sample seeds (sinddm_sample_chain_seeds) are NOT a template flag: `sseeds` (device, one 64-bit seed per sample of THIS
-// launch, or NULL) is selected once per block.  With it the Philox key of sample b is sseeds[b] and the counter is the quad
-// index INSIDE the sample's own (3,H,W) tensor -- element e of the sample gets element e of sinddm_normal_fill(3HW, sseeds[b],
-// step) -- instead of (seed, quad index inside the whole batch).  NULL leaves every number as it was.  The two fused tails
-// own one sample per block (blockIdx.y), so the select is a scalar load and a scalar move; the unfused tail, which strides
-// over the flat batch, has a per-sample sibling (reverse_step_rng_samples_kernel) because a sample's quads then no longer
-// coincide with the flat quads.
-template <bool EDIT, bool NOISE, bool KEEP>
-__global__ __launch_bounds__(256) void reverse_step_rng_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
-                                                               const float* __restrict__ xtil, float* __restrict__ out,
-                                                               sinddm_step_coefs k, long long n, unsigned long long seed,
-                                                               unsigned long long step, const float* __restrict__ ew,
-                                                               const float* __restrict__ ec, const float* __restrict__ nz,
-                                                               int chw, int hw, const float* __restrict__ km,
-                                                               const float* __restrict__ kx, float ka, float kb) {
-    const long long n4 = (n + 3) >> 2;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        const long long i0 = q << 2;
-        if (k.sigma != 0.0f || (KEEP && kb != 0.0f)) {
-            if (NOISE) {                        // (a step's slice starts at a multiple of n floats: not 16-byte aligned in general)
-                for (int j = 0; j < 4 && i0 + j < n; ++j) z[j] = nz[i0 + j];
-            } else {
-                philox_normal4(seed, step, (unsigned long long)q, z);
-            }
-        }
-        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT) {
-            int r = (int)(i0 % chw);            // index inside the sample; the quad may run over a plane's or a sample's end
-            for (int j = 0; j < 4 && i0 + j < n; ++j) {
-                w[j] = ew[r % hw];
-                c[j] = ec[r];
-                r = r + 1 == chw ? 0 : r + 1;
-            }
-        }
-        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) {
-            int r = (int)(i0 % chw);
-            for (int j = 0; j < 4 && i0 + j < n; ++j) {
-                m[j] = km[r % hw];
-                k0[j] = kx[r];
-                r = r + 1 == chw ? 0 : r + 1;
-            }
-        }
-        if (i0 + 3 < n) {
-            const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
-            const f32x4 e = *reinterpret_cast<const f32x4*>(eps + i0);
-            f32x4 xb{0.f, 0.f, 0.f, 0.f};
-            if (k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
-            f32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                o[j] = reverse_step_mean(k, x[j], e[j], xb[j], w[j], c[j], EDIT) + k.sigma * z[j];
-                if (KEEP) o[j] = keep_blend(k, o[j], z[j], xb[j], m[j], k0[j], ka, kb);
-            }
-            *reinterpret_cast<f32x4*>(out + i0) = o;
-        } else {
-            for (int j = 0; i0 + j < n; ++j) {
-                const float xb = k.mode != 0 ? xtil[i0 + j] : 0.f;
-                const float o = reverse_step_mean(k, xt[i0 + j], eps[i0 + j], xb, w[j], c[j], EDIT) + k.sigma * z[j];
-                out[i0 + j] = KEEP ? keep_blend(k, o, z[j], xb, m[j], k0[j], ka, kb) : o;
-            }
-        }
-    }
-}
-
-// final 1x1 conv (-> eps) + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
-// four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
-// path): eps never goes to memory.  EDIT / NOISE: a thread's four pixels are contiguous and 16-byte aligned in the maps and
-// in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller), so both are read as f32x4; so are
-// the KEEP mask and known image.
-template <bool EDIT, bool NOISE, bool KEEP>
-__global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const float* __restrict__ a, const float* __restrict__ w,
-                                                                      const float* __restrict__ bias,
-                                                                      const float* __restrict__ xt,
-                                                                      const float* __restrict__ xtil, float* __restrict__ out,
-                                                                      sinddm_step_coefs k, int C, int HW,
-                                                                      unsigned long long seed, unsigned long long step, int b0,
-                                                                      const float* __restrict__ ew,
-                                                                      const float* __restrict__ ec,
-                                                                      const float* __restrict__ nz,
-                                                                      const float* __restrict__ km,
-                                                                      const float* __restrict__ kx, float ka, float kb,
-                                                                      const unsigned long long* __restrict__ sseeds) {
-    const int b = blockIdx.y;
-    const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (p >= HW) return;
-    // the noise key: (seed, index inside the whole batch), or with per-sample seeds (sseeds[b], index inside the sample)
-    const unsigned long long key = sseeds ? sseeds[b] : seed;
-    const long long kofs = sseeds ? -(long long)b * 3 * HW : (long long)b0 * 3 * HW;
-    const float* src = a + (size_t)b * C * HW + p;
-    f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * HW);
-        e[0] += w[c] * v;
-        e[1] += w[C + c] * v;
-        e[2] += w[2 * C + c] * v;
-    }
-    f32x4 mw{1.f, 1.f, 1.f, 1.f};
-    if (EDIT) mw = *reinterpret_cast<const f32x4*>(ew + p);
-    f32x4 mk{0.f, 0.f, 0.f, 0.f};
-    if (KEEP) mk = *reinterpret_cast<const f32x4*>(km + p);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const long long i0 = ((long long)b * 3 + c) * HW + p;
-        const long long ig = i0 + (long long)b0 * 3 * HW;           // flat index inside the whole batch (recorded draws)
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k.sigma != 0.0f || (KEEP && kb != 0.0f)) {
-            if (NOISE) {
-                const f32x4 zv = *reinterpret_cast<const f32x4*>(nz + ig);
-                z[0] = zv[0]; z[1] = zv[1]; z[2] = zv[2]; z[3] = zv[3];
-            } else {
-                philox_normal4(key, step, (unsigned long long)((i0 + kofs) >> 2), z);
-            }
-        }
-        const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
-        f32x4 xb{0.f, 0.f, 0.f, 0.f};
-        if (k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
-        f32x4 mc{0.f, 0.f, 0.f, 0.f};
-        if (EDIT) mc = *reinterpret_cast<const f32x4*>(ec + (size_t)c * HW + p);
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = reverse_step_mean(k, x[j], e[c][j], xb[j], mw[j], mc[j], EDIT) + k.sigma * z[j];
-        if (KEEP) {
-            const f32x4 k0 = *reinterpret_cast<const f32x4*>(kx + (size_t)c * HW + p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = keep_blend(k, o[j], z[j], xb[j], mk[j], k0[j], ka, kb);
-        }
-        *reinterpret_cast<f32x4*>(out + i0) = o;
-    }
-}
-
-// standalone N(0,1) fill from the same generator (tests; initial / re-noise draws of the sampler)
-// the same for padded workspace rows (pitch Wp, true width W): a thread owns a padded quad of a row; the boundary tensors
-// (x_t, x-tilde, x_{t-1}) are plain, so its up to four pixels sit at an unaligned flat index and their N(0,1) draws -- keyed
-// on the FLAT quad index like everywhere else -- come from up to two Philox calls.  EDIT / NOISE: the maps and the recorded
-// draws are plain tensors as well: scalar reads at the unaligned flat index, like x_t; the KEEP maps likewise.
-template <bool EDIT, bool NOISE, bool KEEP>
-__global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
-    const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ xt,
-    const float* __restrict__ xtil, float* __restrict__ out, sinddm_step_coefs k, int C, int H, int W, int Wp,
-    unsigned long long seed, unsigned long long step, int b0, const float* __restrict__ ew, const float* __restrict__ ec,
-    const float* __restrict__ nz, const float* __restrict__ km, const float* __restrict__ kx, float ka, float kb,
-    const unsigned long long* __restrict__ sseeds) {
-    const int b = blockIdx.y;
-    const int qpr = Wp >> 2;
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= H * qpr) return;
-    const int y = q / qpr, x = (q - y * qpr) * 4;
-    const size_t HWp = (size_t)H * Wp;
-    const long long HW = (long long)H * W;
-    // the noise key (as in final_conv_reverse_step_kernel): (seed, index inside the whole batch), or with per-sample seeds
-    // (sseeds[b], index inside the sample)
-    const unsigned long long key = sseeds ? sseeds[b] : seed;
-    const long long kofs = sseeds ? -(long long)b * 3 * HW : (long long)b0 * 3 * HW;
-    const float* src = a + (size_t)b * C * HWp + (size_t)y * Wp + x;
-    f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * HWp);
-        e[0] += w[c] * v;
-        e[1] += w[C + c] * v;
-        e[2] += w[2 * C + c] * v;
-    }
-    const int nv = W - x;                                   // valid pixels of the quad (>= 1)
-    const bool draw = k.sigma != 0.0f || (KEEP && kb != 0.0f);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const long long i0 = ((long long)b * 3 + c) * HW + (long long)y * W + x;
-        const long long ig = i0 + (long long)b0 * 3 * HW;          // flat index inside the whole batch (recorded draws)
-        const long long ik = i0 + kofs;                             // the noise key's index
-        const int r0 = (int)(ik & 3);
-        float za[4] = {0.f, 0.f, 0.f, 0.f}, zb[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!NOISE && draw) {
-            philox_normal4(key, step, (unsigned long long)(ik >> 2), za);
-            if (r0 != 0) philox_normal4(key, step, (unsigned long long)(ik >> 2) + 1ull, zb);
-        }
-        const float z8[8] = {za[0], za[1], za[2], za[3], zb[0], zb[1], zb[2], zb[3]};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (j < nv) {
-                float z = z8[j];                                                   // z8[r0 + j], r0 in 0..3
-                z = r0 == 1 ? z8[j + 1] : z;
-                z = r0 == 2 ? z8[j + 2] : z;
-                z = r0 == 3 ? z8[j + 3] : z;
-                if (NOISE) z = draw ? nz[ig + j] : 0.f;
-                float mw = 1.f, mc = 0.f;
-                const int pp = y * W + x + j;
-                if (EDIT) {
-                    mw = ew[pp];
-                    mc = ec[(size_t)c * HW + pp];
-                }
-                const float xb = k.mode != 0 ? xtil[i0 + j] : 0.f;
-                const float o = reverse_step_mean(k, xt[i0 + j], e[c][j], xb, mw, mc, EDIT) + k.sigma * z;
-                out[i0 + j] = KEEP ? keep_blend(k, o, z, xb, km[pp], kx[(size_t)c * HW + pp], ka, kb) : o;
-            }
-        }
-    }
-}
-__global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ out, long long n, unsigned long long seed,
-                                                            unsigned long long step) {
-    const long long n4 = (n + 3) >> 2;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
-        float z[4];
-        philox_normal4(seed, step, (unsigned long long)q, z);
-        for (int j = 0; j < 4 && (q << 2) + j < n; ++j) out[(q << 2) + j] = z[j];
-    }
-}
-// B slices of n floats (sinddm_normal_fill_samples): slice b (blockIdx.y) is philox_normal_kernel(n, seeds[b], step).  The
-// quad index restarts at every slice; a slice starts at b*n floats -- unaligned when n % 4 != 0 -- so the stores are scalar
-// and the last quad of a slice is cut at the slice's end.
-__global__ __launch_bounds__(256) void philox_normal_samples_kernel(float* __restrict__ out, long long n,
-                                                                    const unsigned long long* __restrict__ seeds,
-                                                                    unsigned long long step) {
-    const unsigned long long key = seeds[blockIdx.y];
-    float* __restrict__ o = out + (long long)blockIdx.y * n;
-    const long long n4 = (n + 3) >> 2;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
-        float z[4];
-        philox_normal4(key, step, (unsigned long long)q, z);
-        for (int j = 0; j < 4 && (q << 2) + j < n; ++j) o[(q << 2) + j] = z[j];
-    }
-}
-
-// reverse_step_rng_kernel with per-sample seeds (the unfused tail of sinddm_sample_chain_seeds; recorded noise wins over
-// seeds, so there is no NOISE variant).  That kernel strides over the quads of the FLAT batch; here a block row (blockIdx.y)
-// owns one sample and walks the quads of the sample's own (3,H,W) tensor: quad q of sample b holds elements 4q .. 4q+3 of
-// the sample and the draws philox_normal4(sseeds[b], step, q).  When chw % 4 != 0 a sample starts at an address that is
-// not 16-byte aligned (scalar loads and stores), and its last quad is partial: the elements past chw belong to the next
-// sample, which draws them from its own key, so they are neither computed nor written here.
-template <bool EDIT, bool KEEP>
-__global__ __launch_bounds__(256) void reverse_step_rng_samples_kernel(
-    const float* __restrict__ xt, const float* __restrict__ eps, const float* __restrict__ xtil, float* __restrict__ out,
-    sinddm_step_coefs k, unsigned long long step, const unsigned long long* __restrict__ sseeds, const float* __restrict__ ew,
-    const float* __restrict__ ec, int chw, int hw, const float* __restrict__ km, const float* __restrict__ kx, float ka,
-    float kb) {
-    const unsigned long long key = sseeds[blockIdx.y];
-    const long long base = (long long)blockIdx.y * chw;
-    const int n4 = (int)(((long long)chw + 3) >> 2);
-    const bool vec = (chw & 3) == 0;                      // every sample then starts on a 16-byte boundary, like the batch
-    for (int q = blockIdx.x * 256 + threadIdx.x; q < n4; q += gridDim.x * 256) {
-        const int r0 = q << 2;                              // index inside the sample
-        const int nv = chw - r0 < 4 ? chw - r0 : 4;         // elements of this quad that belong to the sample (>= 1)
-        const long long i0 = base + r0;
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k.sigma != 0.0f || (KEEP && kb != 0.0f)) philox_normal4(key, step, (unsigned long long)q, z);
-        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT || KEEP) {
-            for (int j = 0; j < nv; ++j) {
-                const int r = r0 + j;
-                if (EDIT) {
-                    w[j] = ew[r % hw];
-                    c[j] = ec[r];
-                }
-                if (KEEP) {
-                    m[j] = km[r % hw];
-                    k0[j] = kx[r];
-                }
-            }
-        }
-        // ONE evaluation for both layouts -- the unrolled four-element form of reverse_step_rng_kernel's 16-byte path, so that the
-        // seeded run rounds like the run that is fed the same numbers as a buffer; only the loads and stores differ
-        f32x4 x{0.f, 0.f, 0.f, 0.f}, e{0.f, 0.f, 0.f, 0.f}, xb{0.f, 0.f, 0.f, 0.f};
-        if (vec) {
-            x = *reinterpret_cast<const f32x4*>(xt + i0);
-            e = *reinterpret_cast<const f32x4*>(eps + i0);
-            if (k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (j < nv) {
-                    x[j] = xt[i0 + j];
-                    e[j] = eps[i0 + j];
-                    if (k.mode != 0) xb[j] = xtil[i0 + j];
-                }
-            }
-        }
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            o[j] = reverse_step_mean(k, x[j], e[j], xb[j], w[j], c[j], EDIT) + k.sigma * z[j];
-            if (KEEP) o[j] = keep_blend(k, o[j], z[j], xb[j], m[j], k0[j], ka, kb);
-        }
-        if (vec) {
-            *reinterpret_cast<f32x4*>(out + i0) = o;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (j < nv) out[i0 + j] = o[j];
-        }
-    }
-}
+// (the reverse-step kernels and the Philox generator: step_tail.h)
 
 // one axis of the bilinear source lookup: taps i0 / i1 and the weight of i1
 //   !WRAP  ATen area_pixel_compute_source_index(align_corners=False): max(scale*(dst+0.5)-0.5, 0), fp32
@@ -1282,34 +902,16 @@ struct ChainStep {
     const float* cond_row;
     const float* x_tilde;
     float* x_next;
-    sinddm_step_coefs coefs;
-    unsigned long long seed, stream_id;
-    int b0;            // index of this call's first sample inside the whole batch (the noise is keyed on the whole batch's flat index)
-    const float* edit_w;   // ROI edit maps (HW / 3*HW floats, shared by the batch) or both NULL
-    const float* edit_c;
-    const float* noise;    // this step's recorded draws for the WHOLE batch (B_total*3*HW floats) or NULL -> Philox
-    const float* keep_m;   // known-region mask / known image (HW / 3*HW floats, shared by the batch) or both NULL
-    const float* keep_x0;
-    float keep_a, keep_b;  // this step's forward scalars of the known image (sinddm_keep_opts::ab)
-    const unsigned long long* sseeds;   // per-sample seeds of THIS call's samples (device) or NULL -> (seed, b0)
+    TailArgs tail;     // the step's scalars and options (step_tail.h)
 };
 
-// one of the eight instantiations of a tail kernel: bit 0 = EDIT, bit 1 = NOISE, bit 2 = KEEP
-#define SINDDM_TAIL_LAUNCH(KERNEL, variant, grid, st, ...)                                                             \
-    do {                                                                                                              \
-        switch (variant) {                                                                                            \
-            case 0: hipLaunchKernelGGL((KERNEL<false, false, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-            case 1: hipLaunchKernelGGL((KERNEL<true, false, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;     \
-            case 2: hipLaunchKernelGGL((KERNEL<false, true, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;     \
-            case 3: hipLaunchKernelGGL((KERNEL<true, true, false>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-            case 4: hipLaunchKernelGGL((KERNEL<false, false, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;     \
-            case 5: hipLaunchKernelGGL((KERNEL<true, false, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-            case 6: hipLaunchKernelGGL((KERNEL<false, true, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-            default: hipLaunchKernelGGL((KERNEL<true, true, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-        }                                                                                                             \
-    } while (0)
-static int tail_variant(const float* edit_w, const float* noise, const float* keep_m) {
-    return (edit_w ? 1 : 0) | (noise ? 2 : 0) | (keep_m ? 4 : 0);
+// The options of a tail launch as compile-time constants: calls f(EDIT, NOISE, KEEP) with std::true_type / std::false_type
+// according to which of the launch's pointers are set; f launches its kernel's <decltype(EDIT)::value, ...> instantiation.
+template <class F>
+static void tail_dispatch(const TailArgs& t, F&& f) {
+    auto keep = [&](auto e, auto n) { t.km ? f(e, n, std::true_type{}) : f(e, n, std::false_type{}); };
+    auto noise = [&](auto e) { t.nz ? keep(e, std::true_type{}) : keep(e, std::false_type{}); };
+    t.ew ? noise(std::true_type{}) : noise(std::false_type{});
 }
 
 int conv3x3_path(int cout, int cin, int coblks, int B, int H, int W) {
@@ -1473,15 +1075,9 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     int cond_stride = P.cond_stride;
     if (cs) { fb.cond = const_cast<float*>(cs->cond_row); cond_stride = 0; }
 
-    CondArgs ca{};
-    ca.params = params; ca.t_dev = reinterpret_cast<const long long*>(t_dev); ca.t_host = t_host; ca.scale = scale;
-    ca.out = fb.cond; ca.cond_stride = P.cond_stride;
-    ca.tm0_w = P.tm0_w; ca.tm0_b = P.tm0_b; ca.tm2_w = P.tm2_w; ca.tm2_b = P.tm2_b;
-    for (int l = 0; l < 4; ++l) {
-        ca.mlp_w[l] = P.blk[l].mlp_w; ca.mlp_b[l] = P.blk[l].mlp_b;
-        ca.tr_w[l] = P.blk[l].tr_w; ca.tr_b[l] = P.blk[l].tr_b;
-        ca.cin[l] = P.blk[l].cin; ca.coff[l] = P.blk[l].cond_off;
-    }
+    CondArgs ca = cond_args(P, params);
+    ca.t_dev = reinterpret_cast<const long long*>(t_dev); ca.t_host = t_host; ca.scale = scale;
+    ca.out = fb.cond;
     ca.cond_vec = tb ? tb->cvec : nullptr; ca.hidden = tb ? tb->hpre : nullptr;
     ca.emb_out = tb ? tb->emb : nullptr; ca.mvec_out = tb ? tb->mvec : nullptr;
     if (!cs) {
@@ -1530,10 +1126,11 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     if (padded) {
         const unsigned gx = (unsigned)((H * (Wp / 4) + 255) / 256);
         if (cs && cs->x_next)
-            SINDDM_TAIL_LAUNCH(final_conv_reverse_step_pitch_kernel, tail_variant(cs->edit_w, cs->noise, cs->keep_m), dim3(gx, B),
-                               st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next, cs->coefs, P.half, H, W,
-                               Wp, cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise, cs->keep_m, cs->keep_x0,
-                               cs->keep_a, cs->keep_b, cs->sseeds);
+            tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
+                hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                                   dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde,
+                                   cs->x_next, P.half, H, W, Wp, cs->tail);
+            });
         else
             hipLaunchKernelGGL(final_conv1x1_pitch_kernel, dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w,
                                params + P.fin_b, out, P.half, H, W, Wp);
@@ -1541,10 +1138,11 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         return 0;
     }
     if (cs && cs->x_next && HW % 4 == 0) {
-        SINDDM_TAIL_LAUNCH(final_conv_reverse_step_kernel, tail_variant(cs->edit_w, cs->noise, cs->keep_m),
-                           dim3((HW / 4 + 255) / 256, B), st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde, cs->x_next,
-                           cs->coefs, P.half, HW, cs->seed, cs->stream_id, cs->b0, cs->edit_w, cs->edit_c, cs->noise, cs->keep_m,
-                           cs->keep_x0, cs->keep_a, cs->keep_b, cs->sseeds);
+        tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
+            hipLaunchKernelGGL((final_conv_reverse_step_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                               dim3((HW / 4 + 255) / 256, B), dim3(256), 0, st, cur, params + P.fin_w, params + P.fin_b, x,
+                               cs->x_tilde, cs->x_next, P.half, HW, cs->tail);
+        });
         SINDDM_LAUNCH_CHECK();
         return 0;
     }
@@ -1602,15 +1200,9 @@ int sinddm_cond_embed(const float* params, const int64_t* t_dev, int t_host, flo
     if (!params || !block_bias_out || B <= 0) return SINDDM_E_BADARG;
     NetPlan P = make_plan(dim);
     if (!P.ok) return SINDDM_E_BADSHAPE;
-    CondArgs ca{};
-    ca.params = params; ca.t_dev = reinterpret_cast<const long long*>(t_dev); ca.t_host = t_host; ca.scale = scale;
-    ca.out = block_bias_out; ca.cond_stride = P.cond_stride;
-    ca.tm0_w = P.tm0_w; ca.tm0_b = P.tm0_b; ca.tm2_w = P.tm2_w; ca.tm2_b = P.tm2_b;
-    for (int l = 0; l < 4; ++l) {
-        ca.mlp_w[l] = P.blk[l].mlp_w; ca.mlp_b[l] = P.blk[l].mlp_b;
-        ca.tr_w[l] = P.blk[l].tr_w; ca.tr_b[l] = P.blk[l].tr_b;
-        ca.cin[l] = P.blk[l].cin; ca.coff[l] = P.blk[l].cond_off;
-    }
+    CondArgs ca = cond_args(P, params);
+    ca.t_dev = reinterpret_cast<const long long*>(t_dev); ca.t_host = t_host; ca.scale = scale;
+    ca.out = block_bias_out;
     ca.cond_vec = cond_vec_out; ca.emb_out = emb_out;
     hipLaunchKernelGGL(cond_kernel, dim3(B), dim3(128), 0, static_cast<hipStream_t>(stream), ca);
     SINDDM_LAUNCH_CHECK();
@@ -1649,38 +1241,50 @@ int sinddm_q_sample(const float* x0, const float* x_orig, const float* noise, fl
     return 0;
 }
 
+// the launch behind sinddm_reverse_step / _edit / _keep (each validates its own arguments): B samples of chw elements,
+// the maps that are set in `t` select the instantiation
+static int reverse_step_launch(const float* x_t, const float* eps, const float* x_tilde, float* out, const TailArgs& t,
+                               long long n, int chw, int hw, void* stream) {
+    long long bx = (n + 255) / 256;
+    if (bx > 8192) bx = 8192;
+    tail_dispatch(t, [&](auto E, auto, auto K) {
+        hipLaunchKernelGGL((reverse_step_kernel<decltype(E)::value, decltype(K)::value>), dim3((unsigned)bx), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), x_t, eps, x_tilde, out, t, n, chw, hw);
+    });
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
 int sinddm_reverse_step(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                         const sinddm_step_coefs* coefs, int64_t n, void* stream) {
     if (!x_t || !eps || !noise || !out || !coefs || n <= 0) return SINDDM_E_BADARG;
     if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
-    long long bx = (n + 255) / 256;
+    TailArgs t{};
+    t.k = *coefs; t.nz = noise;
+    return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)n, 1, 1, stream);
+}
+
+// one row per key: `seed`, or seeds[0 .. rows - 1]
+static int normal_fill_launch(float* out, int rows, int64_t n, uint64_t seed, const uint64_t* seeds, uint64_t stream_id,
+                              void* stream) {
+    long long bx = ((n + 3) / 4 + 255) / 256;
     if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, eps, x_tilde, noise, out, *coefs, (long long)n, nullptr, nullptr, 1, 1, nullptr, nullptr, 1.0f, 0.0f);
+    hipLaunchKernelGGL(philox_normal_rows_kernel, dim3((unsigned)bx, (unsigned)rows), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), out, (long long)n, (unsigned long long)seed,
+                       reinterpret_cast<const unsigned long long*>(seeds), (unsigned long long)stream_id);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }
 
 int sinddm_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
     if (!out || n <= 0) return SINDDM_E_BADARG;
-    long long bx = ((n + 3) / 4 + 255) / 256;
-    if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream), out,
-                       (long long)n, (unsigned long long)seed, (unsigned long long)stream_id);
-    SINDDM_LAUNCH_CHECK();
-    return 0;
+    return normal_fill_launch(out, 1, n, seed, nullptr, stream_id, stream);
 }
 
 int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, void* stream) {
     if (!out || !seeds || B <= 0 || n <= 0 || (reinterpret_cast<uintptr_t>(seeds) & 7) != 0) return SINDDM_E_BADARG;
     if (B > 65535) return SINDDM_E_BADSHAPE;                                   // (one grid row per slice)
-    long long bx = ((n + 3) / 4 + 255) / 256;
-    if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL(philox_normal_samples_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), out, (long long)n, reinterpret_cast<const unsigned long long*>(seeds),
-                       (unsigned long long)stream_id);
-    SINDDM_LAUNCH_CHECK();
-    return 0;
+    return normal_fill_launch(out, B, n, 0, seeds, stream_id, stream);
 }
 
 // sampler runs whose dim -> dim conv launches carry between LO and HI (8x32 tile, 80-channel block) items per CU AND leave
@@ -1694,8 +1298,8 @@ int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* see
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
-// The body of sinddm_sample_chain_ex (halo_y = halo_x = 0), of sinddm_sample_chain_tile (keep = NULL), of
-// sinddm_sample_chain_keep (sample_seeds = NULL) and of sinddm_sample_chain_seeds.  Hc x Wc is the CENTRE size; the
+// The body of every sinddm_sample_chain* entry point: each passes 0 / NULL for the options its signature does not have
+// (sinddm_sample_chain_seeds has them all).  Hc x Wc is the CENTRE size; the
 // steps run on the extended shape H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo,
 // the halo of every step's output is refreshed from its centre (wrap_halo_launch, per half-batch on its own stream), and
 // that of `x` once on entry: the zero padding of the convolutions then never reaches the centre (SINDDM_TILE_HALO).
@@ -1704,6 +1308,8 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                              uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
+    if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
+    if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
     if ((reinterpret_cast<uintptr_t>(sample_seeds) & 7) != 0) return SINDDM_E_BADARG;
     if (!params || !packed || !x || !x_alt || !eps || !coefs || !t_list || !ws || n_steps < 0 || B <= 0 || Hc <= 0 || Wc <= 0)
         return SINDDM_E_BADARG;
@@ -1730,8 +1336,6 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipStream_t sx = static_cast<hipStream_t>(aux_stream);
     const long long n = (long long)B * CHANNELS * H * W;
-    long long bx = ((n + 3) / 4 + 255) / 256;
-    if (bx > 8192) bx = 8192;
     if (ws_bytes < fwd_workspace_bytes(p, B, H, W)) return SINDDM_E_WORKSPACE;
     float* cond_tab = static_cast<float*>(ws);                 // the conditioning region: one row per step of a run
     const bool fuse_tail = (H * W) % 4 == 0 || fwd_pitch(p, W) != W;     // (padded rows: their own fused tail kernel)
@@ -1780,15 +1384,9 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
             len = 2;
             while (i0 + len < n_steps && len < CHAIN_COND_ROWS && t_list[i0 + len] - t_list[i0 + len - 1] == dt) ++len;
         }
-        CondArgs ca{};
-        ca.params = params; ca.t_dev = nullptr; ca.t_host = t_list[i0]; ca.t_step = dt; ca.scale = scale;
-        ca.out = cond_tab; ca.cond_stride = p.cond_stride;
-        ca.tm0_w = p.tm0_w; ca.tm0_b = p.tm0_b; ca.tm2_w = p.tm2_w; ca.tm2_b = p.tm2_b;
-        for (int l = 0; l < 4; ++l) {
-            ca.mlp_w[l] = p.blk[l].mlp_w; ca.mlp_b[l] = p.blk[l].mlp_b;
-            ca.tr_w[l] = p.blk[l].tr_w; ca.tr_b[l] = p.blk[l].tr_b;
-            ca.cin[l] = p.blk[l].cin; ca.coff[l] = p.blk[l].cond_off;
-        }
+        CondArgs ca = cond_args(p, params);
+        ca.t_host = t_list[i0]; ca.t_step = dt; ca.scale = scale;
+        ca.out = cond_tab;
         hipLaunchKernelGGL(cond_kernel, dim3(len), dim3(128), 0, st, ca);
         if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }      // (no early return: the events below are ours)
         if (split) {                                           // the second stream starts behind the table (and behind
@@ -1797,45 +1395,38 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
         }
         for (int i = i0; i < i0 + len && rc == 0; ++i) {
             if (coefs[i].mode != 0 && !x_tilde) { rc = SINDDM_E_BADARG; break; }
+            TailArgs t{};                                      // the step's tail, fused or not (b0 / sseeds: of the whole batch)
+            t.k = coefs[i];
+            t.seed = (unsigned long long)seed; t.step = (unsigned long long)(stream_id0 + (uint64_t)i);
+            t.sseeds = sseeds;
+            t.ew = edit_w; t.ec = edit_c; t.nz = noise ? noise + (size_t)i * (size_t)n : nullptr;
+            t.km = keep_m; t.kx = keep_x0;
+            t.ka = keep_m ? keep_ab[2 * i] : 1.0f; t.kb = keep_m ? keep_ab[2 * i + 1] : 0.0f;
             for (int h = 0; h < (split ? 2 : 1) && rc == 0; ++h) {
                 const size_t o = h ? hoff : 0;
                 ChainStep cs{};
                 cs.cond_row = cond_tab + (size_t)(i - i0) * p.cond_stride;
-                cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail ? nxt + o : nullptr; cs.coefs = coefs[i];
-                cs.seed = (unsigned long long)seed; cs.stream_id = (unsigned long long)(stream_id0 + (uint64_t)i);
-                cs.b0 = h ? Bh[0] : 0;
-                cs.edit_w = edit_w; cs.edit_c = edit_c; cs.noise = noise ? noise + (size_t)i * (size_t)n : nullptr;
-                cs.keep_m = keep_m; cs.keep_x0 = keep_x0;
-                if (keep_m) { cs.keep_a = keep_ab[2 * i]; cs.keep_b = keep_ab[2 * i + 1]; }
-                cs.sseeds = sseeds ? sseeds + (h ? Bh[0] : 0) : nullptr;
+                cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail ? nxt + o : nullptr;
+                cs.tail = t;
+                cs.tail.b0 = h ? Bh[0] : 0;
+                if (sseeds) cs.tail.sseeds = sseeds + cs.tail.b0;
                 rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
                                       h ? sx : st, nullptr, &cs);
                 if (tiled && fuse_tail && rc == 0)
                     rc = wrap_halo_launch(nxt + o, nullptr, Bh[h] * CHANNELS, Hc, Wc, halo_y, halo_x, h ? sx : st);
             }
             if (rc) break;
-            if (!fuse_tail && sseeds) {
+            if (!fuse_tail) {
+                // one row for the flat batch, or with per-sample seeds one row per sample (reverse_step_rows_kernel)
                 const int chw = CHANNELS * H * W;
-                unsigned gx = (unsigned)(((chw + 3) / 4 + 255) / 256);
+                const long long span = sseeds ? chw : n;
+                long long gx = ((span + 3) / 4 + 255) / 256;
                 if (gx > 8192) gx = 8192;
-                const unsigned long long sid = (unsigned long long)(stream_id0 + (uint64_t)i);
-                const float ka = keep_m ? keep_ab[2 * i] : 1.0f, kb = keep_m ? keep_ab[2 * i + 1] : 0.0f;
-#define SINDDM_SEEDED_TAIL(E, K)                                                                                          \
-    hipLaunchKernelGGL((reverse_step_rng_samples_kernel<E, K>), dim3(gx, (unsigned)B), dim3(256), 0, st, cur, eps, x_tilde, nxt,  \
-                       coefs[i], sid, sseeds, edit_w, edit_c, chw, H * W, keep_m, keep_x0, ka, kb)
-                if (edit_w && keep_m) SINDDM_SEEDED_TAIL(true, true);
-                else if (edit_w) SINDDM_SEEDED_TAIL(true, false);
-                else if (keep_m) SINDDM_SEEDED_TAIL(false, true);
-                else SINDDM_SEEDED_TAIL(false, false);
-#undef SINDDM_SEEDED_TAIL
-                if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
-                if (tiled && (rc = wrap_halo_launch(nxt, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st)) != 0) break;
-            } else if (!fuse_tail) {
-                SINDDM_TAIL_LAUNCH(reverse_step_rng_kernel, tail_variant(edit_w, noise, keep_m), dim3((unsigned)bx), st, cur, eps,
-                                   x_tilde, nxt, coefs[i], n, (unsigned long long)seed,
-                                   (unsigned long long)(stream_id0 + (uint64_t)i), edit_w, edit_c,
-                                   noise ? noise + (size_t)i * (size_t)n : nullptr, CHANNELS * H * W, H * W, keep_m, keep_x0,
-                                   keep_m ? keep_ab[2 * i] : 1.0f, keep_m ? keep_ab[2 * i + 1] : 0.0f);
+                tail_dispatch(t, [&](auto E, auto N, auto K) {
+                    hipLaunchKernelGGL((reverse_step_rows_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                                       dim3((unsigned)gx, sseeds ? (unsigned)B : 1u), dim3(256), 0, st, cur, eps, x_tilde, nxt, t,
+                                       span, chw, H * W);
+                });
                 if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
                 if (tiled && (rc = wrap_halo_launch(nxt, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st)) != 0) break;
             }
@@ -1872,8 +1463,8 @@ int sinddm_sample_chain_tile(const float* params, const float* packed, float* x,
                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
-    return sinddm_sample_chain_keep(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
-                                    H, W, ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr);
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_keep(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1881,8 +1472,8 @@ int sinddm_sample_chain_keep(const float* params, const float* packed, float* x,
                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep) {
-    return sinddm_sample_chain_seeds(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
-                                     H, W, ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr);
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr);
 }
 
 int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1890,8 +1481,6 @@ int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x
                               uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                               void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                               const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
-    if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
-    if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
                              ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds);
 }
@@ -1900,16 +1489,16 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
                          const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                          uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                          void* aux_stream, int* result_in_alt) {
-    return sinddm_sample_chain_ex(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
-                                  H, W, ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr);
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr);
 }
 
 int sinddm_sample_chain(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
                         const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                         int* result_in_alt) {
-    return sinddm_sample_chain_ex(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B,
-                                  H, W, ws, ws_bytes, stream, nullptr, result_in_alt, nullptr);
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr);
 }
 
 int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
@@ -1919,13 +1508,9 @@ int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_
         return SINDDM_E_BADARG;
     if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
     if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
-    const long long n = (long long)B * C * HW;
-    long long bx = (n + 255) / 256;
-    if (bx > 8192) bx = 8192;
-    hipLaunchKernelGGL((reverse_step_kernel<true, false>), dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, eps, x_tilde, noise, out, *coefs, n, edit_w, edit_c, C * HW, HW, nullptr, nullptr, 1.0f, 0.0f);
-    SINDDM_LAUNCH_CHECK();
-    return 0;
+    TailArgs t{};
+    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
+    return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)B * C * HW, C * HW, HW, stream);
 }
 
 int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
@@ -1935,18 +1520,10 @@ int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_
     if ((edit_w == nullptr) != (edit_c == nullptr)) return SINDDM_E_BADARG;
     if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
     if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
-    const long long n = (long long)B * C * HW;
-    long long bx = (n + 255) / 256;
-    if (bx > 8192) bx = 8192;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (edit_w)
-        hipLaunchKernelGGL((reverse_step_kernel<true, true>), dim3((unsigned)bx), dim3(256), 0, st, x_t, eps, x_tilde, noise, out,
-                           *coefs, n, edit_w, edit_c, C * HW, HW, keep_m, keep_x0, keep_a, keep_b);
-    else
-        hipLaunchKernelGGL((reverse_step_kernel<false, true>), dim3((unsigned)bx), dim3(256), 0, st, x_t, eps, x_tilde, noise, out,
-                           *coefs, n, nullptr, nullptr, C * HW, HW, keep_m, keep_x0, keep_a, keep_b);
-    SINDDM_LAUNCH_CHECK();
-    return 0;
+    TailArgs t{};
+    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
+    t.km = keep_m; t.kx = keep_x0; t.ka = keep_a; t.kb = keep_b;
+    return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)B * C * HW, C * HW, HW, stream);
 }
 
 #ifdef W2_PHASE

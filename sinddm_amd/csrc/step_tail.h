@@ -1,0 +1,358 @@
+// The reverse-step tail of the sampler (device code of sinddm_fwd.hip): the step's evaluation, written once, the Philox
+// generator, and the kernels that end a step -- stand-alone, unfused behind the network, or fused into its final 1x1 conv.
+#pragma once
+#include "common.h"
+
+namespace sinddm {
+
+// What every tail kernel takes besides its tensors: the step's scalars and its three options.  Maps and draws are shared
+// by all samples of the batch; a NULL pointer is read by no instantiation that could see it (the host picks EDIT / NOISE /
+// KEEP from the pointers).
+struct TailArgs {
+    sinddm_step_coefs k;
+    int b0;                             // index of this launch's first sample inside the whole batch (seed / nz are keyed on the whole batch)
+    unsigned long long seed, step;      // Philox key and stream of this step's draws
+    const unsigned long long* sseeds;   // per-sample seeds of THIS launch's samples (device) or NULL -> (seed, b0)
+    const float* ew;                    // EDIT   ROI edit maps, HW / 3*HW floats
+    const float* ec;
+    const float* nz;                    // NOISE  this step's recorded draws for the WHOLE batch (B_total*3*HW floats)
+    const float* km;                    // KEEP   known-region mask / known image, HW / 3*HW floats
+    const float* kx;
+    float ka, kb;                       // KEEP   this step's forward scalars of the known image (sinddm_keep_opts::ab)
+};
+
+// x_{t-1} mean of one element: predict_start_from_noise + p_mean_variance (normal branch) + q_posterior
+// (reference SinDDM/models.py:306-352,433-447); `w`, `c` = ROI edit map (1, 0 without ROI guidance).
+// EDIT: the predicted clean image is replaced by  w(p) * x_recon + c(ch, p)  before the re-blur mix / clamps --
+// the ROI-guided sampling of the reference (models.py:291-298,430-431) written as a per-pixel affine map
+// (sequential `eta*patch + (1-eta)*x` blends over possibly overlapping boxes compose into one such map).
+__device__ __forceinline__ float reverse_step_mean(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c,
+                                                   bool edit) {
+    float x0 = k.sqrt_recip_ac_t * x - k.sqrt_recipm1_ac_t * e;                   // models.py:308-309
+    if (k.mode == 0) {
+        if (edit) x0 = w * x0 + c;              // x_recon and x_t_mix are the same tensor here (models.py:311-312)
+        const float x0c = k.clip ? fminf(fmaxf(x0, -1.0f), 1.0f) : x0;
+        return k.coef1_t * x0c + k.coef2_t * x;                                   // models.py:324-327
+    }
+    float xp = (x0 - k.gamma_t * xb) / (1.0f - k.gamma_t);                        // models.py:315-316
+    if (edit) xp = w * xp + c;
+    if (k.mode == 1) {
+        float mix = k.gamma_tm1 * xb + (1.0f - k.gamma_tm1) * xp;                 // models.py:435-436
+        float x0c = x0;
+        if (k.clip) {
+            mix = fminf(fmaxf(mix, -1.0f), 1.0f);
+            x0c = fminf(fmaxf(x0, -1.0f), 1.0f);
+        }
+        return k.sqrt_ac_tm1 * mix + k.sqrt_1m_ac_tm1_mvar * (x - k.sqrt_ac_t * x0c) / k.sqrt_1m_ac_t;  // :342-345
+    }
+    return k.clip ? fminf(fmaxf(xp, -1.0f), 1.0f) : xp;                           // models.py:347-348
+}
+
+// KEEP: known-region conditioning (inpainting / outpainting; RePaint-style replacement, no reference line).  Where the mask
+// m(p) is 1 the step's output is replaced by a sample of q(x_{t-1} | known image k0) -- SinDDM's blurred forward process
+// at t-1 -- built from the SAME draw z the step uses (one Gaussian per pixel in either branch); in between the two are
+// blended.  `plain` is what the step writes without the option, `xb` x-tilde (0 in mode 0), ka / kb the forward scalars
+// sqrt(ac[t-1]) / sqrt(1 - ac[t-1]) ((1, 0) at t == 0).  Written so that m == 0 gives `plain` and m == 1 gives `kept`
+// exactly; the keep target is not clamped.
+__device__ __forceinline__ float keep_blend(const sinddm_step_coefs& k, float plain, float z, float xb, float m, float k0,
+                                            float ka, float kb) {
+    const float target = k.mode == 1 ? k.gamma_tm1 * xb + (1.0f - k.gamma_tm1) * k0 : k0;
+    const float kept = ka * target + kb * z;
+    return m * kept + (1.0f - m) * plain;
+}
+
+// THE step of one element, the only place it is written: every kernel below calls it per lane, so all of them round alike.
+// (w, c) is read only under EDIT, (m, k0) only under KEEP; EDIT and KEEP may be on together: the edit acts on x_recon,
+// the keep on the output.
+template <bool EDIT, bool KEEP>
+__device__ __forceinline__ float tail_eval(const TailArgs& a, float x, float e, float xb, float z, float w, float c, float m,
+                                           float k0) {
+    const float o = reverse_step_mean(a.k, x, e, xb, w, c, EDIT) + a.k.sigma * z;          // models.py:459
+    return KEEP ? keep_blend(a.k, o, z, xb, m, k0, a.ka, a.kb) : o;
+}
+// z is drawn (or read) when sigma != 0 or, under KEEP, kb != 0; otherwise it is 0 and nothing is read
+template <bool KEEP>
+__device__ __forceinline__ bool tail_draws(const TailArgs& a) { return a.k.sigma != 0.0f || (KEEP && a.kb != 0.0f); }
+
+// ---- counter-based Philox4x32-10 + Box-Muller: the Gaussian noise of models.py:455 drawn INSIDE the step kernels (no
+// randn launch, no noise tensor: 12 B/px less traffic).  Stream = (seed, step id, element index); the reference never
+// seeds its generator, so there is no bit-level noise contract -- parity tests keep injecting noise through
+// sinddm_reverse_step.
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned long long step, unsigned long long idx4,
+                                               float (&z)[4]) {
+    unsigned c[4] = {(unsigned)idx4, (unsigned)(idx4 >> 32), (unsigned)step, (unsigned)(step >> 32)};
+    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    // uniforms in (0, 1]: (x + 1) * 2^-32 evaluated so that 0 is never produced
+    const float u0 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f), u1 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(c[2] >> 8) + 1.0f) * (1.0f / 16777216.0f), u3 = (float)(c[3] >> 8) * (1.0f / 16777216.0f);
+    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+    float s0, c0, s1, c1;
+    sincospif(2.0f * u1, &s0, &c0);
+    sincospif(2.0f * u3, &s1, &c1);
+    z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
+}
+
+// the draws of one quad: NOISE reads them at `nzq` (one 16-byte load when `vec`, else its nv valid lanes), otherwise they
+// are Philox quad `q` of (key, step)
+template <bool NOISE>
+__device__ __forceinline__ void quad_draw(const float* __restrict__ nzq, bool vec, int nv, unsigned long long key,
+                                          unsigned long long step, unsigned long long q, float (&z)[4]) {
+    if (NOISE) {
+        if (vec) {
+            const f32x4 zv = *reinterpret_cast<const f32x4*>(nzq);
+            z[0] = zv[0]; z[1] = zv[1]; z[2] = zv[2]; z[3] = zv[3];
+        } else {
+            for (int j = 0; j < nv; ++j) z[j] = nzq[j];
+        }
+    } else {
+        philox_normal4(key, step, q, z);
+    }
+}
+
+// one pair of maps for the nv valid lanes of a quad at an arbitrary flat index: `plane` has hw floats, `full` chw, r = the
+// index of the quad's first element inside its sample; the quad may run over a plane's or a sample's end
+__device__ __forceinline__ void quad_maps(const float* __restrict__ plane, const float* __restrict__ full, int r, int nv, int chw,
+                                          int hw, float (&p)[4], float (&f)[4]) {
+    for (int j = 0; j < nv; ++j) {
+        p[j] = plane[r % hw];
+        f[j] = full[r];
+        r = r + 1 == chw ? 0 : r + 1;
+    }
+}
+
+// the noise key of sample b of a fused tail's launch: (seed, index inside the whole batch), or with per-sample seeds
+// (sseeds[b], index inside the sample: element e of the sample gets element e of sinddm_normal_fill(3HW, sseeds[b], step)).
+// `ofs` turns the launch's flat index into the key's index.  One scalar load and a scalar move per block.
+struct NoiseKey {
+    unsigned long long key;
+    long long ofs;
+};
+__device__ __forceinline__ NoiseKey noise_key(const TailArgs& a, int b, long long chw) {
+    return a.sseeds ? NoiseKey{a.sseeds[b], -(long long)b * chw} : NoiseKey{a.seed, (long long)a.b0 * chw};
+}
+
+// ---- the step on its own (sinddm_reverse_step / _edit / _keep): z = a.nz, one draw per element; the maps have period chw
+template <bool EDIT, bool KEEP>
+__global__ __launch_bounds__(256) void reverse_step_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
+                                                           const float* __restrict__ xtil, float* __restrict__ out, TailArgs a,
+                                                           long long n, int chw, int hw) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int q = (EDIT || KEEP) ? (int)(i % chw) : 0;
+        const float xb = a.k.mode != 0 ? xtil[i] : 0.0f;
+        out[i] = tail_eval<EDIT, KEEP>(a, xt[i], eps[i], xb, a.nz[i], EDIT ? a.ew[q % hw] : 1.0f, EDIT ? a.ec[q] : 0.0f,
+                                       KEEP ? a.km[q % hw] : 0.0f, KEEP ? a.kx[q] : 0.0f);
+    }
+}
+
+// ---- the unfused tail of a sampler run (shapes with neither H*W % 4 == 0 nor padded rows), over ROWS: row blockIdx.y is
+// `span` elements from row * span, its quads are counted from the row's start and drawn from the row's key.  The flat
+// launch is one row (span = n, key = seed); with per-sample seeds a row is a sample (span = chw, key = sseeds[row]), so
+// that a sample's quads are those of its own (3,H,W) tensor and the elements past its end -- the next sample's, drawn from
+// that sample's key -- are neither computed nor written.  A full quad of a 16-byte aligned row moves as f32x4, any other
+// quad lane by lane; the evaluation is the same unrolled four lanes either way (idle lanes compute on zeros) -- with ONE
+// exception: the flat launch's partial last quad (no per-sample seeds, n % 4 != 0) is evaluated element by element, the form
+// that quad always had; with the keep maps on, the compiler contracts the unrolled form into other fused multiply-adds
+// (profiles/NOTES_r12.md).  The exception costs every instantiation 7 - 10 VGPRs (its loop lives beside the four lanes).
+// The three compile-time options are those of every tail of a run; <false, false, false> is the kernel the chain always ran:
+//   EDIT   the ROI edit: w = ew[p], c = ec[ch * HW + p]
+//   NOISE  z is READ from `nz` at the element's flat index inside the whole batch instead of drawn from Philox (a step's
+//          slice starts at a multiple of n floats: not 16-byte aligned in general, so lane by lane).  Recorded draws win
+//          over per-sample seeds on the host: no launch has both.
+//   KEEP   the known-region replacement of keep_blend: m = km[p], k0 = kx[ch * HW + p]
+template <bool EDIT, bool NOISE, bool KEEP>
+__global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
+                                                                const float* __restrict__ xtil, float* __restrict__ out,
+                                                                TailArgs a, long long span, int chw, int hw) {
+    const long long base = (long long)blockIdx.y * span;
+    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
+    const bool aligned = (base & 3) == 0;
+    const bool draw = tail_draws<KEEP>(a);
+    const long long n4 = (span + 3) >> 2;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
+        const int nv = span - (q << 2) < 4 ? (int)(span - (q << 2)) : 4;      // lanes of this quad inside the row (>= 1)
+        const long long i0 = base + (q << 2);
+        const bool vec = aligned && nv == 4;
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (draw) quad_draw<NOISE>(a.nz + i0, false, nv, key, a.step, (unsigned long long)q, z);
+        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
+        if (EDIT) quad_maps(a.ew, a.ec, (int)(i0 % chw), nv, chw, hw, w, c);
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
+        if (KEEP) quad_maps(a.km, a.kx, (int)(i0 % chw), nv, chw, hw, m, k0);
+        if (!a.sseeds && nv < 4) {       // the exception above
+            for (int j = 0; j < nv; ++j) {
+                const float xb = a.k.mode != 0 ? xtil[i0 + j] : 0.f;
+                out[i0 + j] = tail_eval<EDIT, KEEP>(a, xt[i0 + j], eps[i0 + j], xb, z[j], w[j], c[j], m[j], k0[j]);
+            }
+            continue;
+        }
+        f32x4 x{0.f, 0.f, 0.f, 0.f}, e{0.f, 0.f, 0.f, 0.f}, xb{0.f, 0.f, 0.f, 0.f};
+        if (vec) {
+            x = *reinterpret_cast<const f32x4*>(xt + i0);
+            e = *reinterpret_cast<const f32x4*>(eps + i0);
+            if (a.k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j < nv) {
+                    x[j] = xt[i0 + j];
+                    e[j] = eps[i0 + j];
+                    if (a.k.mode != 0) xb[j] = xtil[i0 + j];
+                }
+            }
+        }
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = tail_eval<EDIT, KEEP>(a, x[j], e[j], xb[j], z[j], w[j], c[j], m[j], k0[j]);
+        if (vec) {
+            *reinterpret_cast<f32x4*>(out + i0) = o;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < nv) out[i0 + j] = o[j];
+        }
+    }
+}
+
+// ---- final 1x1 conv (-> eps) + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
+// four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
+// path): eps never goes to memory.  A block row owns one sample.  EDIT / NOISE / KEEP: a thread's four pixels are contiguous
+// and 16-byte aligned in the maps and in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller),
+// so all of them are read as f32x4.
+template <bool EDIT, bool NOISE, bool KEEP>
+__global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const float* __restrict__ a, const float* __restrict__ w,
+                                                                      const float* __restrict__ bias,
+                                                                      const float* __restrict__ xt,
+                                                                      const float* __restrict__ xtil, float* __restrict__ out,
+                                                                      int C, int HW, TailArgs t) {
+    const int b = blockIdx.y;
+    const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p >= HW) return;
+    const NoiseKey nk = noise_key(t, b, (long long)3 * HW);
+    const float* src = a + (size_t)b * C * HW + p;
+    f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
+#pragma unroll 8
+    for (int c = 0; c < C; ++c) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * HW);
+        e[0] += w[c] * v;
+        e[1] += w[C + c] * v;
+        e[2] += w[2 * C + c] * v;
+    }
+    f32x4 mw{1.f, 1.f, 1.f, 1.f};
+    if (EDIT) mw = *reinterpret_cast<const f32x4*>(t.ew + p);
+    f32x4 mk{0.f, 0.f, 0.f, 0.f};
+    if (KEEP) mk = *reinterpret_cast<const f32x4*>(t.km + p);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const long long i0 = ((long long)b * 3 + c) * HW + p;
+        const long long ig = i0 + (long long)t.b0 * 3 * HW;         // flat index inside the whole batch (recorded draws)
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (tail_draws<KEEP>(t)) quad_draw<NOISE>(t.nz + ig, true, 4, nk.key, t.step, (unsigned long long)((i0 + nk.ofs) >> 2), z);
+        const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
+        f32x4 xb{0.f, 0.f, 0.f, 0.f};
+        if (t.k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
+        f32x4 mc{0.f, 0.f, 0.f, 0.f};
+        if (EDIT) mc = *reinterpret_cast<const f32x4*>(t.ec + (size_t)c * HW + p);
+        // (two passes, not tail_eval<EDIT, KEEP>: in one pass the compiler contracts the blend into other fused multiply-adds
+        // than this kernel always had -- profiles/NOTES_r12.md)
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = tail_eval<EDIT, false>(t, x[j], e[c][j], xb[j], z[j], mw[j], mc[j], 0.f, 0.f);
+        if (KEEP) {
+            const f32x4 k0 = *reinterpret_cast<const f32x4*>(t.kx + (size_t)c * HW + p);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = keep_blend(t.k, o[j], z[j], xb[j], mk[j], k0[j], t.ka, t.kb);
+        }
+        *reinterpret_cast<f32x4*>(out + i0) = o;
+    }
+}
+
+// ---- the same for padded workspace rows (pitch Wp, true width W): a thread owns a padded quad of a row; the boundary
+// tensors (x_t, x-tilde, x_{t-1}) are plain, so its up to four pixels sit at an unaligned flat index and their N(0,1)
+// draws -- keyed on the FLAT quad index like everywhere else -- come from up to two Philox calls.  EDIT / NOISE / KEEP: the
+// maps and the recorded draws are plain tensors as well: scalar reads at the unaligned flat index, like x_t.
+template <bool EDIT, bool NOISE, bool KEEP>
+__global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
+    const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ xt,
+    const float* __restrict__ xtil, float* __restrict__ out, int C, int H, int W, int Wp, TailArgs t) {
+    const int b = blockIdx.y;
+    const int qpr = Wp >> 2;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= H * qpr) return;
+    const int y = q / qpr, x = (q - y * qpr) * 4;
+    const size_t HWp = (size_t)H * Wp;
+    const long long HW = (long long)H * W;
+    const NoiseKey nk = noise_key(t, b, 3 * HW);
+    const float* src = a + (size_t)b * C * HWp + (size_t)y * Wp + x;
+    f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
+#pragma unroll 8
+    for (int c = 0; c < C; ++c) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * HWp);
+        e[0] += w[c] * v;
+        e[1] += w[C + c] * v;
+        e[2] += w[2 * C + c] * v;
+    }
+    const int nv = W - x;                                   // valid pixels of the quad (>= 1)
+    const bool draw = tail_draws<KEEP>(t);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const long long i0 = ((long long)b * 3 + c) * HW + (long long)y * W + x;
+        const long long ig = i0 + (long long)t.b0 * 3 * HW;        // flat index inside the whole batch (recorded draws)
+        const long long ik = i0 + nk.ofs;                           // the noise key's index
+        const int r0 = (int)(ik & 3);
+        float za[4] = {0.f, 0.f, 0.f, 0.f}, zb[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!NOISE && draw) {
+            philox_normal4(nk.key, t.step, (unsigned long long)(ik >> 2), za);
+            if (r0 != 0) philox_normal4(nk.key, t.step, (unsigned long long)(ik >> 2) + 1ull, zb);
+        }
+        const float z8[8] = {za[0], za[1], za[2], za[3], zb[0], zb[1], zb[2], zb[3]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < nv) {
+                float z = z8[j];                                                   // z8[r0 + j], r0 in 0..3
+                z = r0 == 1 ? z8[j + 1] : z;
+                z = r0 == 2 ? z8[j + 2] : z;
+                z = r0 == 3 ? z8[j + 3] : z;
+                if (NOISE) z = draw ? t.nz[ig + j] : 0.f;
+                const int pp = y * W + x + j;
+                const float xb = t.k.mode != 0 ? xtil[i0 + j] : 0.f;
+                float mw = 1.f, mc = 0.f;
+                if (EDIT) {
+                    mw = t.ew[pp];
+                    mc = t.ec[(size_t)c * HW + pp];
+                }
+                // (the blend after the step, its maps read in place, as this kernel always had it: see the plain-row kernel)
+                const float o = tail_eval<EDIT, false>(t, xt[i0 + j], e[c][j], xb, z, mw, mc, 0.f, 0.f);
+                out[i0 + j] = KEEP ? keep_blend(t.k, o, z, xb, t.km[pp], t.kx[(size_t)c * HW + pp], t.ka, t.kb) : o;
+            }
+        }
+    }
+}
+
+// ---- stand-alone N(0,1) fill from the same generator (tests; initial / re-noise draws of the sampler), over rows like
+// reverse_step_rows_kernel: row blockIdx.y is `span` floats from row * span, filled with quads 0, 1, ... of its key --
+// `seed` (sinddm_normal_fill: one row) or seeds[row] (sinddm_normal_fill_samples).  A row starts at an unaligned address
+// when span % 4 != 0, so the stores are scalar, and its last quad is cut at its end.
+__global__ __launch_bounds__(256) void philox_normal_rows_kernel(float* __restrict__ out, long long span, unsigned long long seed,
+                                                                 const unsigned long long* __restrict__ seeds,
+                                                                 unsigned long long step) {
+    const unsigned long long key = seeds ? seeds[blockIdx.y] : seed;
+    float* __restrict__ o = out + (long long)blockIdx.y * span;
+    const long long n4 = (span + 3) >> 2;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
+        float z[4];
+        philox_normal4(key, step, (unsigned long long)q, z);
+        for (int j = 0; j < 4 && (q << 2) + j < span; ++j) o[(q << 2) + j] = z[j];
+    }
+}
+
+}  // namespace sinddm

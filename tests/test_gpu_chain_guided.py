@@ -131,7 +131,7 @@ def test_roi_chain_replayed_through_oracle(roi_run, golden):
 # (cfg, dim, s, B, two streams, steps).  Which tail a shape takes (sinddm_fwd.hip: fuse_tail / plan_pads_rows / fwd_pitch):
 #   H*W % 4 == 0                      -> final_conv_reverse_step_kernel                   (dim 160, 48x64)
 #   W % 4 != 0 and the plan pads rows -> final_conv_reverse_step_pitch_kernel            (dim 160: 67x90, 133x177)
-#   H*W % 4 != 0, plain rows          -> final_conv1x1 + reverse_step_rng_kernel: the plan pads rows only when every
+#   H*W % 4 != 0, plain rows          -> final_conv1x1 + reverse_step_rows_kernel: the plan pads rows only when every
 #                                        block's channel count is a multiple of 4; dim 20 has dim/2 = 10 -> plain rows
 SHAPES = [("C2", 160, 0, 16, False, [700, 2, 0]),
           ("C2", 160, 1, 16, True, [400, 1, 0]),
@@ -211,7 +211,7 @@ def test_fused_edit_equals_stepwise_edit(cfg, dim, s, B, aux, ts):
     padded = _rows_padded(lib, dim, B, H, W)
     assert padded == (dim == 160 and W % 4 != 0)
     if dim == 20:
-        assert (H * W) % 4 != 0 and not padded             # -> final_conv1x1 + reverse_step_rng_kernel
+        assert (H * W) % 4 != 0 and not padded             # -> final_conv1x1 + reverse_step_rows_kernel
     seed = 515151 + s
     d.roi_guided_sampling = True
     x = x0.clone()
@@ -242,8 +242,10 @@ def test_fused_edit_equals_stepwise_edit(cfg, dim, s, B, aux, ts):
     assert torch.equal(y_api, y2)
 
 
+# B = 1: 3*133*177 % 4 == 3 -- the flat unfused kernel's last quad is partial, with recorded noise too
 @pytest.mark.parametrize("with_edit", [False, True], ids=["plain", "edit"])
-@pytest.mark.parametrize("cfg,dim,s,B,aux,ts", SHAPES, ids=IDS)
+@pytest.mark.parametrize("cfg,dim,s,B,aux,ts", SHAPES + [("C2", 20, 3, 1, False, [311, 2, 0])],
+                         ids=IDS + ["unfused_dim20_133x177_B1_partial_quad"])
 def test_noise_buffer_equals_philox(cfg, dim, s, B, aux, ts, with_edit):
     """`noise` = what sinddm_normal_fill gives for (seed, stream_id0 + i) reproduces the call without it, bit for bit."""
     net, d, H, W, x0, xt, ew, ec = _setup(cfg, dim, s, B)
