@@ -42,6 +42,20 @@ int sinddm_debug_conv_path(int dim, int B, int H, int W);
  * else the value sinddm_debug_conv_path gives for the padded shape.  `dim` may carry SINDDM_DIM_FP32_CONVS (never 8 then). */
 int sinddm_debug_infer_path(int dim, int B, int H, int W);
 
+/* The collapsed inference head: block 4's conv2, its residual projection and final_conv are ONE linear map of block 4's g
+ * (GELU of conv1) and input, eps = conv3x3(g; W_c) + conv1x1(x_in; W_r) + b_c with weights composed when the packed image is
+ * built.  sinddm_debug_head_path: 1 where sinddm_net_forward / sinddm_sample_chain* of this shape evaluate the head that way
+ * (activation rows 16-byte aligned: W % 4 == 0, or a plan that pads its rows), 0 where they keep conv2 + projection +
+ * final_conv; negative = SINDDM_E_*.  `dim` may carry SINDDM_DIM_FP32_CONVS (same answer). */
+int sinddm_debug_head_path(int dim, int B, int H, int W);
+/* Offsets (floats) of the composed weights inside the packed image, behind every older region: out[0] = W_c as
+ * [ci][o][tap] (dim/2 x 3 x 9), out[1] = W_r as [ci][o] (dim x 3), out[2] = b_c (3).  Host-only. */
+int sinddm_debug_head_offsets(int dim, int64_t out[3]);
+/* The head's eps kernel on caller-supplied tensors: g (B, dim/2, H, Wp), x_in (B, dim, H, Wp) with row pitch Wp (% 4 == 0,
+ * W <= Wp < W + 4, pad columns zero), packed = the image of sinddm_pack_weights; writes eps_out (B, 3, H, W), plain. */
+int sinddm_debug_head(const float* packed, const float* g, const float* x_in, float* eps_out, int dim, int B, int H, int W,
+                      int Wp, void* stream);
+
 /* ... and for TRAINING launches (sinddm_net_forward_train / sinddm_net_backward: plain rows, no padding): 8 = the forward
  * 3x3 convs and both data-gradient convs of the dim -> dim blocks take conv_wh (same rule as inference; needs W % 4 == 0),
  * else the value of sinddm_debug_conv_path.  With 8 the 3x3 weight gradients of those convs run on the binary16 pipe too

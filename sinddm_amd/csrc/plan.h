@@ -42,7 +42,10 @@ struct NetPlan {
     BlockPlan blk[4];
     int64_t tm0_w, tm0_b, tm2_w, tm2_b, fin_w, fin_b;
     int64_t nparams, npacked;
-    int64_t pk_zero;   // 64 zero floats at the end of the packed image (LDS-DMA zero-fill source)
+    int64_t pk_zero;   // 64 zero floats behind the blocks' images (LDS-DMA zero-fill source)
+    // the collapsed inference head (head.h), behind every older region: final_conv composed with block 4's conv2 and
+    // residual projection.  pk_hc: W_c as [ci][o][tap] (half x 27 floats), pk_hr: W_r as [ci][o] (dim x 3), pk_hb: b_c (3)
+    int64_t pk_hc, pk_hr, pk_hb;
     int ntensors;
     int64_t tensor_off[64];
     int cond_stride;   // floats per sample of the cond-bias vector (sum of cin, padded to 4)
@@ -130,6 +133,9 @@ inline NetPlan make_plan(int dim_arg) {
     p.nparams = o;
     p.pk_zero = q;
     q += 64;
+    p.pk_hc = q; q += (int64_t)p.half * CHANNELS * 9;
+    p.pk_hr = q; q += (int64_t)dim * CHANNELS;
+    p.pk_hb = q; q += CHANNELS;
     p.npacked = q;
     p.ntensors = nt;
     p.cond_stride = (coff + 3) / 4 * 4;

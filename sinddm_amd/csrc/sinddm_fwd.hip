@@ -229,7 +229,8 @@ static int pack_forward(const NetPlan& P, const float* params, float* packed, hi
             if (rc) return rc;
         }
     }
-    return 0;
+    // the composed weights of the collapsed inference head (head.h)
+    return head_pack_launch(P, params, packed, st);
 }
 
 // =====================================================================================
@@ -914,6 +915,18 @@ static void tail_dispatch(const TailArgs& t, F&& f) {
     t.ew ? noise(std::true_type{}) : noise(std::false_type{});
 }
 
+// Where inference takes the collapsed head (head.h) instead of block 4's conv2 + residual projection + final_conv: the
+// activation rows are 16-byte aligned (Wp = the workspace pitch: W % 4 == 0, or the plan pads its rows), which is also
+// where a sampler run fuses its tail ((H W) % 4 == 0 or padded rows: sample_chain_impl); a plane stays below the buffer
+// loads' out-of-range offset.  Every other shape keeps its launches, kernel for kernel; training (`tb`) needs block 4's
+// output for backward.
+static bool head_applies(const TrainBufs* tb, int H, int Wp) {
+    return SINDDM_HEAD_COLLAPSE && !tb && Wp % 4 == 0 && (long long)H * Wp < (1LL << 28);
+}
+static HeadEps head_eps(const NetPlan& P, const float* packed, const float* g, const float* xin, int H, int Wp) {
+    return HeadEps{g, xin, packed + P.pk_hc, packed + P.pk_hr, packed + P.pk_hb, P.half, P.dim, H, Wp};
+}
+
 int conv3x3_path(int cout, int cin, int coblks, int B, int H, int W) {
     if (!wino_enabled() || cout % 4 != 0) return 0;
     const bool f24 = mt_for(cout) == 5 && cout % 80 == 0 && cin >= 16 && cin % 16 == 0;
@@ -927,14 +940,16 @@ int conv3x3_path(int cout, int cin, int coblks, int B, int H, int W) {
 // GELU -> gbuf (pre-activation -> upre when the training forward saves it), 3x3 conv + residual (1x1 projection or
 // identity of `cur`) -> obuf.  `cond` = the block's per-sample bias rows ([B][cond_stride]; stride 0: one row for the batch).
 // Wt > 0: padded workspace rows -- every tensor here (cur included) has row pitch W (a multiple of 4) and true width Wt.
+// skip2: the block stops behind conv1 (block 4 in front of the collapsed head, which reads gbuf and cur itself): no conv2, no
+// residual projection, and conv1 does not publish the running max that conv2 would read.
 int block_forward(const NetPlan& P, int l, const float* params, const float* packed, const float* cur, const float* cond,
                   int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, int B, int H, int W, hipStream_t st,
-                  int Wt, float* amax) {
+                  int Wt, float* amax, bool skip2) {
     const BlockPlan& b = P.blk[l];
     // the Winograd F(2x4) kernel with binary16 hi/lo frequency GEMMs (conv_wh.h) where its rule takes the launch; `amax` = this
     // block's two running-max scalars (input of conv1, input of conv2), maintained by the kernels that produce those tensors
     const bool wha = amax && b.pk_q1 >= 0 && conv_wh_applies(P.fp32_convs, B, H, W, b.cin, b.cout);
-    const bool whb = amax && b.pk_q2 >= 0 && conv_wh_applies(P.fp32_convs, B, H, W, b.cout, b.cout);
+    const bool whb = !skip2 && amax && b.pk_q2 >= 0 && conv_wh_applies(P.fp32_convs, B, H, W, b.cout, b.cout);
     int rc = Wt > 0 ? dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
                                     Wt, st, W, W, wha ? amax : nullptr)
                     : dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
@@ -976,7 +991,7 @@ int block_forward(const NetPlan& P, int l, const float* params, const float* pac
         c1.w3 = packed + b.pk_c1; c1.nch3 = b.nch1;
         rc = conv_launch(c1, b.mt, st);
     }
-    if (rc) return rc;
+    if (rc || skip2) return rc;
     // conv2 on the binary16 kernel reads the running max of g (slot amax + 1): conv_wh / the C_in = 3 kernel publish it
     // from their epilogues, the fp32 kernels do not (dim = 80 / 240: block 1 has C_in = dim / 2, not a multiple of 16, so conv1
     // stays on an fp32 kernel while conv2 qualifies) -- one pass over g then
@@ -1085,6 +1100,7 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         SINDDM_LAUNCH_CHECK();
     }
 
+    const bool head = head_applies(tb, H, Wp);
     if (amax) {
         // the running-max scalars exist for the binary16 kernels: a launch shape none of them takes (coarse pyramid scales)
         // neither maintains nor zeroes them
@@ -1092,7 +1108,7 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         for (int l = 0; l < 4; ++l) {
             const BlockPlan& b = P.blk[l];
             any = any || (b.pk_q1 >= 0 && conv_wh_applies(P.fp32_convs, B, H, Wp, b.cin, b.cout)) ||
-                  (b.pk_q2 >= 0 && conv_wh_applies(P.fp32_convs, B, H, Wp, b.cout, b.cout));
+                  (!(head && l == 3) && b.pk_q2 >= 0 && conv_wh_applies(P.fp32_convs, B, H, Wp, b.cout, b.cout));
         }
         if (!any) amax = nullptr;
         else if (hipMemsetAsync(amax, 0, (size_t)B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
@@ -1107,6 +1123,7 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     }
     int freeb[4] = {0, 1, 2, 3};
     int curb = -1;
+    const float* head_g = nullptr;
     for (int l = 0; l < 4; ++l) {
         const BlockPlan& b = P.blk[l];
         // pick three scratch buffers different from the one holding `cur`
@@ -1116,20 +1133,42 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         float* hbuf = tb ? tb->h[l] : fb.buf[sel[0]];
         float* gbuf = tb ? tb->g[l] : fb.buf[sel[1]];
         float* obuf = tb ? tb->o[l] : fb.buf[sel[2]];
+        const bool skip2 = head && l == 3;
         const int rc = block_forward(P, l, params, packed, cur, fb.cond + b.cond_off, cond_stride, hbuf, gbuf, obuf,
-                                     tb ? tb->u[l] : nullptr, B, H, Wp, st, padded ? W : 0, amax ? amax + 2 * l : nullptr);
+                                     tb ? tb->u[l] : nullptr, B, H, Wp, st, padded ? W : 0, amax ? amax + 2 * l : nullptr,
+                                     skip2);
         if (rc) return rc;
+        if (skip2) { head_g = gbuf; break; }                 // (cur stays block 4's input)
         cur = obuf;
         curb = sel[2];
     }
     const int HW = H * W;
+    if (head) {
+        // the collapsed head: eps from block 4's g and input, under the step's tail in a sampler run
+        const HeadEps he = head_eps(P, packed, head_g, cur, H, Wp);
+        const dim3 grid((unsigned)((H * (Wp / 4) + 255) / 256), B);
+        if (cs && cs->x_next && padded)
+            tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
+                hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, HeadEps>),
+                                   grid, dim3(256), 0, st, he, x, cs->x_tilde, cs->x_next, H, W, Wp, cs->tail);
+            });
+        else if (cs && cs->x_next)
+            tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
+                hipLaunchKernelGGL((final_conv_reverse_step_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, HeadEps>),
+                                   grid, dim3(256), 0, st, he, x, cs->x_tilde, cs->x_next, HW, cs->tail);
+            });
+        else
+            hipLaunchKernelGGL(head_eps_kernel, grid, dim3(256), 0, st, he, out, W);
+        SINDDM_LAUNCH_CHECK();
+        return 0;
+    }
+    const FinalConvEps fe{cur, params + P.fin_w, params + P.fin_b, P.half, (size_t)H * Wp};
     if (padded) {
         const unsigned gx = (unsigned)((H * (Wp / 4) + 255) / 256);
         if (cs && cs->x_next)
             tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
-                hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                                   dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w, params + P.fin_b, x, cs->x_tilde,
-                                   cs->x_next, P.half, H, W, Wp, cs->tail);
+                hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, FinalConvEps>),
+                                   dim3(gx, B), dim3(256), 0, st, fe, x, cs->x_tilde, cs->x_next, H, W, Wp, cs->tail);
             });
         else
             hipLaunchKernelGGL(final_conv1x1_pitch_kernel, dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w,
@@ -1139,9 +1178,8 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     }
     if (cs && cs->x_next && HW % 4 == 0) {
         tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
-            hipLaunchKernelGGL((final_conv_reverse_step_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                               dim3((HW / 4 + 255) / 256, B), dim3(256), 0, st, cur, params + P.fin_w, params + P.fin_b, x,
-                               cs->x_tilde, cs->x_next, P.half, HW, cs->tail);
+            hipLaunchKernelGGL((final_conv_reverse_step_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, FinalConvEps>),
+                               dim3((HW / 4 + 255) / 256, B), dim3(256), 0, st, fe, x, cs->x_tilde, cs->x_next, HW, cs->tail);
         });
         SINDDM_LAUNCH_CHECK();
         return 0;
@@ -1585,6 +1623,31 @@ int sinddm_debug_infer_path(int dim, int B, int H, int W) {
     const int Wp = fwd_pitch(p, W);
     if (b.pk_q2 >= 0 && conv_wh_applies(p.fp32_convs, B, H, Wp, b.cout, b.cout)) return 8;
     return conv3x3_path(b.cout, b.cout, b.coblks, B, H, Wp);
+}
+
+int sinddm_debug_head_path(int dim, int B, int H, int W) {
+    NetPlan p = make_plan(dim);
+    if (!p.ok || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    return head_applies(nullptr, H, fwd_pitch(p, W)) ? 1 : 0;
+}
+
+int sinddm_debug_head_offsets(int dim, int64_t out[3]) {
+    NetPlan p = make_plan(dim);
+    if (!p.ok || !out) return SINDDM_E_BADARG;
+    out[0] = p.pk_hc; out[1] = p.pk_hr; out[2] = p.pk_hb;
+    return 0;
+}
+
+int sinddm_debug_head(const float* packed, const float* g, const float* x_in, float* eps_out, int dim, int B, int H, int W,
+                      int Wp, void* stream) {
+    if (!packed || !g || !x_in || !eps_out || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    NetPlan p = make_plan(dim);
+    if (!p.ok) return SINDDM_E_BADSHAPE;
+    if (Wp % 4 != 0 || W > Wp || W <= Wp - 4 || (long long)H * Wp >= (1LL << 28) || B > 65535) return SINDDM_E_BADSHAPE;
+    hipLaunchKernelGGL(head_eps_kernel, dim3((unsigned)((H * (Wp / 4) + 255) / 256), B), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), head_eps(p, packed, g, x_in, H, Wp), eps_out, W);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
 }
 
 int sinddm_prof_end3(int kind, double* ms_total, int64_t* launches, double* flops_total, double* exec_flops_total,

@@ -2,6 +2,7 @@
 // generator, and the kernels that end a step -- stand-alone, unfused behind the network, or fused into its final 1x1 conv.
 #pragma once
 #include "common.h"
+#include "head.h"
 
 namespace sinddm {
 
@@ -223,30 +224,23 @@ __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __r
     }
 }
 
-// ---- final 1x1 conv (-> eps) + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
+// ---- eps stage + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
 // four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
-// path): eps never goes to memory.  A block row owns one sample.  EDIT / NOISE / KEEP: a thread's four pixels are contiguous
+// path): eps never goes to memory.  EPS (head.h) fills the thread's e[3]: HeadEps, the collapsed head on block 4's g and
+// input, or FinalConvEps, the final 1x1 conv on block 4's output (shapes the head does not take).  Everything below the
+// call is the tail, whichever stage ran.  A block row owns one sample.  EDIT / NOISE / KEEP: a thread's four pixels are contiguous
 // and 16-byte aligned in the maps and in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller),
 // so all of them are read as f32x4.
-template <bool EDIT, bool NOISE, bool KEEP>
-__global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const float* __restrict__ a, const float* __restrict__ w,
-                                                                      const float* __restrict__ bias,
-                                                                      const float* __restrict__ xt,
+template <bool EDIT, bool NOISE, bool KEEP, class EPS>
+__global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, const float* __restrict__ xt,
                                                                       const float* __restrict__ xtil, float* __restrict__ out,
-                                                                      int C, int HW, TailArgs t) {
+                                                                      int HW, TailArgs t) {
     const int b = blockIdx.y;
     const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (p >= HW) return;
     const NoiseKey nk = noise_key(t, b, (long long)3 * HW);
-    const float* src = a + (size_t)b * C * HW + p;
-    f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * HW);
-        e[0] += w[c] * v;
-        e[1] += w[C + c] * v;
-        e[2] += w[2 * C + c] * v;
-    }
+    f32x4 e[3];
+    eps(b, p >> 2, e);
     f32x4 mw{1.f, 1.f, 1.f, 1.f};
     if (EDIT) mw = *reinterpret_cast<const f32x4*>(t.ew + p);
     f32x4 mk{0.f, 0.f, 0.f, 0.f};
@@ -280,27 +274,20 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(const floa
 // tensors (x_t, x-tilde, x_{t-1}) are plain, so its up to four pixels sit at an unaligned flat index and their N(0,1)
 // draws -- keyed on the FLAT quad index like everywhere else -- come from up to two Philox calls.  EDIT / NOISE / KEEP: the
 // maps and the recorded draws are plain tensors as well: scalar reads at the unaligned flat index, like x_t.
-template <bool EDIT, bool NOISE, bool KEEP>
-__global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(
-    const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ xt,
-    const float* __restrict__ xtil, float* __restrict__ out, int C, int H, int W, int Wp, TailArgs t) {
+template <bool EDIT, bool NOISE, bool KEEP, class EPS>
+__global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS eps, const float* __restrict__ xt,
+                                                                            const float* __restrict__ xtil,
+                                                                            float* __restrict__ out, int H, int W, int Wp,
+                                                                            TailArgs t) {
     const int b = blockIdx.y;
     const int qpr = Wp >> 2;
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= H * qpr) return;
     const int y = q / qpr, x = (q - y * qpr) * 4;
-    const size_t HWp = (size_t)H * Wp;
     const long long HW = (long long)H * W;
     const NoiseKey nk = noise_key(t, b, 3 * HW);
-    const float* src = a + (size_t)b * C * HWp + (size_t)y * Wp + x;
-    f32x4 e[3] = {{bias[0], bias[0], bias[0], bias[0]}, {bias[1], bias[1], bias[1], bias[1]}, {bias[2], bias[2], bias[2], bias[2]}};
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * HWp);
-        e[0] += w[c] * v;
-        e[1] += w[C + c] * v;
-        e[2] += w[2 * C + c] * v;
-    }
+    f32x4 e[3];
+    eps(b, q, e);
     const int nv = W - x;                                   // valid pixels of the quad (>= 1)
     const bool draw = tail_draws<KEEP>(t);
 #pragma unroll
