@@ -1,11 +1,29 @@
 """Deterministic, RNG-free synthetic weights and inputs.
 
-Published SinDDM checkpoints are not available offline, so parity fixtures, the
-smoke test and the benchmark all use the same closed-form weight fill: every
-tensor k of the state dict gets  w.flat[i] = a_k * sin(0.37*i + k)  with a_k
-~ 1/sqrt(fan_in), so activations stay O(1) through the four conv blocks.
-The same function fills the reference model (tests/golden/make_golden.py) and
-the HIP-backed model, so fixtures hold inputs/outputs only.
+Published SinDDM checkpoints are not available offline, so the weights are made
+up here, by two fills.  The same functions fill the reference model
+(tests/golden/make_golden.py) and the HIP-backed model, so fixtures hold
+inputs/outputs only.
+
+closed_form_state_dict: every tensor k of the state dict gets
+w.flat[i] = a_k * sin(0.37*i + k)  with a_k ~ 1/sqrt(fan_in).  Since
+sin(A_co + B_j) = sin A_co cos B_j + cos A_co sin B_j, every conv weight
+reshaped to (C_out, C_in*k*k) has RANK 2: each 3x3 / 1x1 convolution projects its
+input onto two directions.  At dim 32 the network still varies over the image
+(spatial std 1.14 at an rms of 1.21); at dim 160 the sinusoids cancel over a
+fan-in of 720-1440 and eps is almost constant (rms 0.27, spatial std 0.001):
+another noise image moves it by 6e-3, transposing the taps of a 160 -> 160
+convolution by 8e-5, swapping two channels by 3e-5 .. 7e-5 (measured in
+tests/test_weight_fill_host.py).  Every weight channel also has the same
+maximum.  A whole-tensor tolerance of 1e-5 on this network is therefore close
+to blind to a kernel that is wrong in one tile column, one channel chunk or one
+border band.  Use it for the fixtures recorded from the reference, the smoke
+test and the benchmark, where only "the same numbers as before" is asked.
+
+he_state_dict: He-normal weights from the hash generator, full rank (smallest
+singular value > 0.3 of the largest), output rms ~70 with a spatial std of ~37:
+the same mutations move eps by 1e-2 .. 0.5.  Use it for anything that JUDGES a
+kernel: parity against the float64 oracle, precision gates, edge regions.
 """
 from __future__ import annotations
 
@@ -60,6 +78,32 @@ def closed_form_state_dict(dim: int = 160, channels: int = 3, gain: float = 1.0)
         w = amp * np.sin(0.37 * i + k)
         sd[name] = torch.tensor(w.reshape(shape), dtype=torch.float32)
     return sd
+
+
+def he_state_dict(dim: int = 160, key: int = 1000, eps_gain: float = 1.0) -> Dict[str, torch.Tensor]:
+    """He-normal weights (std sqrt(2 / fan_in)), biases 0.05 N(0,1), tensor k from hash_randn(shape, key + k): an untrained
+    network of full-rank weights whose output depends on its input everywhere (module docstring).  A fresh dict of fresh
+    tensors on every call.
+
+    `eps_gain` multiplies final_conv.0.weight and final_conv.0.bias only, so it scales the network's output and nothing
+    inside it.  The He network's eps has an rms of ~70 on unit-variance input: fed into a reverse step with clip_denoised,
+    x_recon saturates at +-1 everywhere and the step no longer depends on eps.  A test of a step or a chain passes
+    HE_EPS_GAIN[dim], which brings eps to an rms of ~1."""
+    sd: Dict[str, torch.Tensor] = OrderedDict()
+    for k, (name, shape) in enumerate(net_param_shapes(dim).items()):
+        amp = 0.05 if name.endswith("bias") else float(np.sqrt(2.0 / int(np.prod(shape[1:]))))
+        sd[name] = hash_randn(shape, key + k) * amp
+    if eps_gain != 1.0:
+        for name in ("final_conv.0.weight", "final_conv.0.bias"):
+            sd[name] = sd[name] * float(eps_gain)
+    return sd
+
+
+# eps_gain that brings the rms of the CPU oracle's eps to ~1 (key = 1000), one constant per width.  Measured with
+# O.net_forward on the input of the chain tests of tests/test_gpu_fullrank.py (tests/fullrank_util.py: chain_inputs),
+# x = 0.5 * hash_randn((2, 3, 24, 40), 61), scale 1, config C2: at eps_gain = 1 the rms of eps is 34.5 at t = 200, 42.2 at
+# t = 100 and 64.2 at t = 0 along the chain; with the constant 0.76, 0.93 and 1.41.
+HE_EPS_GAIN = {160: 0.022}
 
 
 def closed_form_tensor(shape, phase: float = 0.0, amp: float = 1.0, freq: float = 0.618) -> torch.Tensor:

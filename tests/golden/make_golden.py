@@ -15,6 +15,8 @@ Fixtures (G-numbers follow SURVEY.md 8(c)):
   g4_block.npz       SinDDMConvBlock fwd + input grad + weight grads (4 block shapes, dim=32)
   g5_losses.npz      p_losses value + all 52 grads at s=0 and s=2 (dim=32)
   g17_loss_types.npz p_losses with loss_type 'l2' / 'l1_pred_img' (models.py:595-607): values + three gradient tensors
+  g22_he_net.npz     SinDDMNet.forward and p_losses (value + three gradient tensors) with the FULL-RANK weights of
+                     he_state_dict (the closed-form fill is rank 2: sinddm_amd/synth.py), hash-noise inputs (`... g22`)
   g6_psample.npz     p_sample single steps (s=0/s>0, t=17/t=0) with recorded noise
   g7_qsample.npz     q_sample
   g8_bilinear.npz    F.interpolate(mode='bilinear') at the pyramid ratios
@@ -53,7 +55,7 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
 sys.path.insert(0, REPO)
 
-from sinddm_amd.synth import closed_form_state_dict, closed_form_tensor, hash_randn, noise_key  # noqa: E402
+from sinddm_amd.synth import closed_form_state_dict, closed_form_tensor, hash_randn, he_state_dict, noise_key  # noqa: E402
 
 
 # ---------------------------------------------------------------------------
@@ -324,6 +326,40 @@ def g17(meta=None):
                 for pn in ("final_conv.0.weight", "l2.net.0.weight", "l1.ds_conv.weight"):
                     out[f"{lt}_s{s}{tag}_g_{pn}"] = dict(net.named_parameters())[pn].grad.clone()
     save("g17_loss_types.npz", **out)
+
+
+def g22(meta=None):
+    """The reference on full-rank weights (he_state_dict): SinDDMNet.forward at dim 160 (2x3x37x41 and 2x3x24x50, s = 0
+    and 2) and dim 32 (2x3x67x90, s = 2) on hash noise, t = [17, 503]; p_losses ('l1' at s = 2, 'l2' at s = 2 and s = 0, t = [37, 5]) at
+    dim 32: value + the three gradient tensors of G17.  Inputs are regenerated by the tests (keys below): only outputs are stored."""
+    if meta is None:
+        meta = json.load(open(os.path.join(HERE, "g11_img_scales.json")))
+    out = {}
+    t = torch.tensor([17, 503], dtype=torch.long)
+    for dim, (H, W), scales in ((160, (37, 41), (0, 2)), (160, (24, 50), (0, 2)), (32, (67, 90), (2,))):
+        net = rm.SinDDMNet(dim=dim, multiscale=True, device=DEV)
+        net.load_state_dict(he_state_dict(dim))
+        x = hash_randn((2, 3, H, W), 2200 + W)
+        for s in scales:
+            with torch.no_grad():
+                out[f"d{dim}_{H}x{W}_s{s}"] = net(x, t, scale=s)
+    net, d = _small_diffusion(32, meta)
+    net.load_state_dict(he_state_dict(32))
+    pyr = np.load(os.path.join(HERE, "c1_pyramid.npz"))
+    B = 2
+    for lt, s in (("l1", 2), ("l2", 2), ("l2", 0)):
+        d.loss_type = lt
+        orig = _pyr_tensor(pyr[f"scale_{s}"])[None].repeat(B, 1, 1, 1)
+        recon = _pyr_tensor(pyr[f"scale_{s}_recon"])[None].repeat(B, 1, 1, 1) if s > 0 else orig
+        noise = hash_randn(tuple(orig.shape), noise_key("train", s, 22))
+        tt = torch.tensor([37, 5], dtype=torch.long)
+        net.zero_grad()
+        loss = d.p_losses(recon, tt, s, noise=noise, x_orig=orig) if s > 0 else d.p_losses(orig, tt, s, noise=noise)
+        loss.backward()
+        out[f"{lt}_s{s}_loss"] = loss.detach()
+        for pn in ("final_conv.0.weight", "l2.net.0.weight", "l1.ds_conv.weight"):
+            out[f"{lt}_s{s}_g_{pn}"] = dict(net.named_parameters())[pn].grad.clone()
+    save("g22_he_net.npz", **out)
 
 
 def g6_g7(meta):
@@ -787,6 +823,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "g17":
         g17()
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "g22":
+        g22()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "g14":
         g14()
         return
@@ -823,6 +862,7 @@ def main():
         g16(workdir)
         g14()
         g17(meta)
+        g22(meta)
         g_chain("C3", "g18_chain_c3.npz")
         g_chain("C5", "g19_chain_c5_mul24.npz", scale_mul=(2, 4))
         g_chain("C4", "g21_chain_c4.npz")

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from fullrank_util import net_forward_f64 as _net_forward_f64
 from oracle import sinddm_oracle as O
 from sinddm_amd.synth import closed_form_state_dict, hash_randn
 
@@ -33,16 +34,6 @@ def _net(dim=160, sd=None):
     net = SinDDMNet(dim=dim, multiscale=True, device=DEV).to(DEV)
     net.load_state_dict(sd if sd is not None else closed_form_state_dict(dim))
     return net
-
-
-def _net_forward_f64(sd, x, t, scale):
-    """The oracle's network in float64 (the conditioning vector comes from the fp32 oracle: it is not what is tested)."""
-    cond = O.cond_vector(sd, t, scale).double()
-    sd64 = {k: v.double() for k, v in sd.items()}
-    h = x.double()
-    for name in ("l1", "l2", "l3", "l4"):
-        h = O.conv_block(sd64, name, h, cond)
-    return torch.nn.functional.conv2d(h, sd64["final_conv.0.weight"], sd64["final_conv.0.bias"])
 
 
 @pytest.fixture

@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import max_abs, rel_l2
+from fullrank_util import net_forward_f64 as _net_forward_f64
 from oracle import sinddm_oracle as O
 from sinddm_amd.synth import closed_form_state_dict, hash_randn
 from test_head_host import compose_head
@@ -48,15 +49,20 @@ def _net(dim):
 # ---- H1 ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dim", [32, 160])
 def test_composed_weights_in_the_packed_image(dim):
+    _check_composed_weights(dim, _net(dim), closed_form_state_dict(dim))
+
+
+def _check_composed_weights(dim, net, sd):
+    """H1 on the network `net` loaded with the state dict `sd` (tests/test_gpu_fullrank.py runs it on He weights)."""
     L, lib = _lib()
     half = dim // 2
-    packed = _net(dim).packed_weights()
+    packed = net.packed_weights()
     torch.cuda.synchronize()
     off = (C.c_int64 * 3)()
     assert lib.sinddm_debug_head_offsets(dim, off) == 0
     assert off[2] + 3 == packed.numel() == lib.sinddm_packed_count(dim)
     img = packed.cpu().numpy()
-    wc, wr, bc = compose_head(closed_form_state_dict(dim))
+    wc, wr, bc = compose_head(sd)
     want = [wc.permute(1, 0, 2, 3).reshape(-1),                              # [ci][o][tap]
             wr[:, :, 0, 0].t().reshape(-1),                                  # [ci][o]
             bc]
@@ -78,9 +84,13 @@ HEAD_SHAPES = [(1, 4, 4), (5, 8, 8), (9, 12, 12), (13, 17, 20), (33, 36, 36)]
 @pytest.mark.parametrize("H,W,Wp", HEAD_SHAPES, ids=[f"{h}x{w}_pitch{p}" for h, w, p in HEAD_SHAPES])
 @pytest.mark.parametrize("dim", [160, 32])
 def test_head_alone_is_not_wider_than_the_uncollapsed_head_in_fp32(dim, H, W, Wp):
+    _check_head_alone(dim, H, W, Wp, _net(dim), closed_form_state_dict(dim))
+
+
+def _check_head_alone(dim, H, W, Wp, net, sd):
+    """H2 on the network `net` loaded with the state dict `sd` (tests/test_gpu_fullrank.py runs it on He weights)."""
     L, lib = _lib()
     B, half = 3, dim // 2
-    sd = closed_form_state_dict(dim)
     g = hash_randn((B, half, H, W), 900 + H)
     x_in = hash_randn((B, dim, H, W), 901 + W)
 
@@ -95,7 +105,7 @@ def test_head_alone_is_not_wider_than_the_uncollapsed_head_in_fp32(dim, H, W, Wp
     gp[..., :W], xp[..., :W] = g, x_in
     gp, xp = gp.to(DEV), xp.to(DEV)
     got = torch.full((B, 3, H, W), float("nan"), device=DEV)
-    L.check(lib.sinddm_debug_head(L.ptr(_net(dim).packed_weights()), L.ptr(gp), L.ptr(xp), L.ptr(got), dim, B, H, W, Wp,
+    L.check(lib.sinddm_debug_head(L.ptr(net.packed_weights()), L.ptr(gp), L.ptr(xp), L.ptr(got), dim, B, H, W, Wp,
                                   L.stream_ptr(DEV)), "sinddm_debug_head")
     torch.cuda.synchronize()
     got = got.cpu()
@@ -127,16 +137,6 @@ def test_head_arguments():
 
 
 # ---- H3 ----------------------------------------------------------------------------------------------------------------------
-def _net_forward_f64(sd, x, t, scale):
-    """The oracle's network in float64 (the conditioning vector comes from the fp32 oracle, as in tests/test_gpu_h2.py)."""
-    cond = O.cond_vector(sd, t, scale).double()
-    sd64 = {k: v.double() for k, v in sd.items()}
-    h = x.double()
-    for name in ("l1", "l2", "l3", "l4"):
-        h = O.conv_block(sd64, name, h, cond)
-    return F.conv2d(h, sd64["final_conv.0.weight"], sd64["final_conv.0.bias"])
-
-
 FWD = [(160, 2, 13, 17, 1), (160, 2, 33, 36, 1), (160, 1, 8, 16, 1), (32, 2, 9, 12, 1), (20, 2, 9, 12, 1), (20, 2, 9, 13, 0)]
 _REFS = {}
 

@@ -26,7 +26,7 @@ from PIL import Image
 from conftest import max_abs, rel_l2
 from oracle import sinddm_oracle as O
 from sinddm_amd.configs import CONFIGS, build_diffusion
-from sinddm_amd.synth import closed_form_state_dict, closed_form_tensor, hash_randn, noise_key
+from sinddm_amd.synth import closed_form_state_dict, closed_form_tensor, hash_randn, he_state_dict, noise_key
 from tile_util import HALO, centre, circular_oracle, wrap_pad
 
 pytestmark = pytest.mark.gpu
@@ -36,19 +36,14 @@ SENTINEL = -777.0
 _DIFF = {}
 
 
-def _he_state_dict(dim, key=1000):
-    """He-normal weights (std sqrt(2 / fan_in)), biases 0.05 N(0,1), from the hash generator: an untrained network whose
-    output depends on its input everywhere.  (At dim 160 the closed-form fill gives an output that is almost constant over
-    the image -- rms 0.27, spatial std 0.001: the sinusoidal weights cancel over a fan-in of 720-1440 -- so whatever its
-    borders do vanishes in a whole-tensor norm: on the CPU oracle one zero-padded evaluation is 1.9e-3 from
-    shift-equivariant and a plain 4-step chain 1.5e-5 from the circular one, below the chain budget.  With He weights the
-    oracle's plain chain is 0.21 from equivariant, one evaluation 0.36: the chain tests can tell the paddings apart.)"""
+def _he_state_dict(dim):
+    """sinddm_amd.synth.he_state_dict(dim), built once per module.  (At dim 160 the closed-form fill gives an output that is
+    almost constant over the image -- rms 0.27, spatial std 0.001 --, so whatever its borders do vanishes in a whole-tensor
+    norm: on the CPU oracle one zero-padded evaluation is 1.9e-3 from shift-equivariant and a plain 4-step chain 1.5e-5 from
+    the circular one, below the chain budget.  With He weights the oracle's plain chain is 0.21 from equivariant, one
+    evaluation 0.36: the chain tests can tell the paddings apart.)"""
     if dim not in _HE:
-        from sinddm_amd.synth import net_param_shapes
-        _HE[dim] = {}
-        for k, (name, shape) in enumerate(net_param_shapes(dim).items()):
-            amp = 0.05 if name.endswith("bias") else float(np.sqrt(2.0 / int(np.prod(shape[1:]))))
-            _HE[dim][name] = hash_randn(shape, key + k) * amp
+        _HE[dim] = he_state_dict(dim)
     return _HE[dim]
 
 

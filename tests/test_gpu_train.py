@@ -8,6 +8,7 @@ import torch
 from PIL import Image
 
 from conftest import max_abs, rel_l2
+from fullrank_util import klass
 from oracle import sinddm_oracle as O
 from sinddm_amd.synth import closed_form_state_dict, hash_randn, noise_key
 
@@ -286,10 +287,6 @@ def test_net_backward_full_size_vs_oracle_autograd():
     # per class of tensors (the condition path's and the biases' gradients are plain sums over all pixels, accumulated
     # with atomics on the GPU: their rounding noise varies from run to run): HIP error of every tensor < 3x the WORST
     # float32-CPU error in its class
-    def klass(name):
-        if ".mlp." in name or "time_mlp" in name or "time_reshape" in name or name.endswith("ds_conv.bias"):
-            return "cond_path"
-        return "weight" if name.endswith("weight") else "bias"
     errs = {}
     for name, p in net.named_parameters():
         errs[name] = (rel_l2(p.grad.cpu().double(), g64[name]), rel_l2(g32[name].double(), g64[name]))
@@ -354,10 +351,6 @@ def test_net_backward_binary16_convs_vs_float64():
     assert e_gx[0] < 2e-5 and e_gx[0] < 1.5 * e_gx[1] + 1e-7, e_gx
     assert rel_l2(gx_h, gx_f) > 0                      # (the two paths are different kernels)
 
-    def klass(name):
-        if ".mlp." in name or "time_mlp" in name or "time_reshape" in name or name.endswith("ds_conv.bias"):
-            return "cond_path"
-        return "weight" if name.endswith("weight") else "bias"
     errs = {n: (rel_l2(g_h[n], g64[n]), rel_l2(g_f[n], g64[n])) for n in g_h}
     worst_f = {}
     for n, (eh, ef) in errs.items():

@@ -6,7 +6,7 @@ import torch
 
 from conftest import rel_l2, max_abs
 from oracle import sinddm_oracle as O
-from sinddm_amd.synth import closed_form_state_dict, closed_form_tensor, hash_randn, noise_key
+from sinddm_amd.synth import closed_form_state_dict, closed_form_tensor, hash_randn, he_state_dict, noise_key
 
 
 def _sched(meta, name, T=None):
@@ -103,6 +103,41 @@ def test_g17_loss_types(golden):
                 assert abs(float(loss) - float(g[key + "_loss"])) < 2e-6 * max(1.0, abs(float(g[key + "_loss"]))), key
                 for pn in ("final_conv.0.weight", "l2.net.0.weight", "l1.ds_conv.weight"):
                     assert rel_l2(sd[pn].grad, g[f"{key}_g_{pn}"]) < 5e-5, (key, pn)
+
+
+def test_g22_he_net_forward_and_losses(golden):
+    """The oracle against the reference on FULL-RANK weights (he_state_dict; G3 .. G6 and G17 pin it on the closed-form fill,
+    whose rank-2 weights attenuate a structural difference: tests/test_weight_fill_host.py).  The fixture is the reference's
+    fp32 evaluation, so the yardstick is its own distance from the float64 oracle: the fp32 oracle may be twice as far from
+    the fixture, rel_l2(fp32 oracle, golden) <= 2 x rel_l2(golden, float64 oracle), for every forward and every gradient."""
+    from fullrank_util import (G22_FORWARD, G22_GRADS, G22_LOSSES, g22_forward_inputs, g22_loss_inputs, net_forward_f64,
+                               oracle_p_losses_autograd)
+    g = golden("g22_he_net.npz")
+    for dim, H, W, scales in G22_FORWARD:
+        sd = he_state_dict(dim)
+        x, t = g22_forward_inputs(H, W)
+        for s in scales:
+            ref = g[f"d{dim}_{H}x{W}_s{s}"]
+            with torch.no_grad():
+                e32, e64 = rel_l2(O.net_forward(sd, x, t, s), ref), rel_l2(ref, net_forward_f64(sd, x, t, s))
+            print(f"G22 dim {dim} {H}x{W} s={s}: fp32 oracle vs reference {e32:.2e}; reference vs float64 oracle {e64:.2e}")
+            assert float(np.sqrt((ref.astype(np.float64) ** 2).mean())) > 10          # (the He network: eps rms ~ 70)
+            assert e64 < 1e-5 and e32 <= 2 * e64, (dim, H, W, s, e32, e64)
+    sched = _sched(golden("g11_img_scales.json"), "C1")
+    pyr = golden("c1_pyramid.npz")
+    sd = he_state_dict(32)
+    for lt, s in G22_LOSSES:
+        x_start, x_orig, t, noise = g22_loss_inputs(pyr, s)
+        l32, g32 = oracle_p_losses_autograd(sched, sd, x_start, x_orig, t, s, noise, lt, torch.float32)
+        l64, g64 = oracle_p_losses_autograd(sched, sd, x_start, x_orig, t, s, noise, lt, torch.float64)
+        ref = float(g[f"{lt}_s{s}_loss"])
+        print(f"G22 p_losses {lt} s={s}: loss reference {ref:.6g} fp32 oracle {l32:.6g} float64 oracle {l64:.6g}")
+        assert abs(l32 - ref) <= 2 * abs(ref - l64) + 2e-6 * abs(ref), (lt, s, l32, ref, l64)
+        for pn in G22_GRADS:
+            gr = g[f"{lt}_s{s}_g_{pn}"]
+            e32, e64 = rel_l2(g32[pn], gr), rel_l2(gr, g64[pn])
+            print(f"    grad {pn}: fp32 oracle vs reference {e32:.2e}; reference vs float64 oracle {e64:.2e}")
+            assert e64 < 1e-4 and e32 <= 2 * e64, (lt, s, pn, e32, e64)
 
 
 def test_g6_p_sample(golden):
