@@ -32,6 +32,16 @@ int sinddm_prof_end2(double* conv_ms_total, int64_t* conv_launches, double* conv
 int sinddm_prof_end3(int kind, double* ms_total, int64_t* launches, double* flops_total,
                      double* exec_flops_total, int reset);
 
+/* The kernel of EVERY 3x3 convolution of one network evaluation of this shape on the current device, computed by the
+ * very calls the evaluation makes (256 compute units are assumed where no device answers).  Values: 0 = direct implicit
+ * GEMM, 1 = the C_in = 3 kernel, 2 = conv_wino2 (F(2x2,3x3)), 3 = conv_wino3, 4 = conv_wino4 (F(2x4,3x3)), 8 = conv_wh
+ * (F(2x4), binary16 hi/lo frequency GEMMs), -1 = no such launch.  out[2 l + i] = conv i + 1 of block l in the forward:
+ * train = 0 of sinddm_net_forward / sinddm_sample_chain* (rows padded to 4 floats inside the workspace; block 4's conv2
+ * is -1 under the collapsed head), train != 0 of sinddm_net_forward_train, and then out[8 + 2 l + i] = the data gradient
+ * of conv2 (i = 0) and of conv1 (i = 1) of block l in sinddm_net_backward (-1 without train).  `dim_arg` may carry
+ * SINDDM_DIM_FP32_CONVS.  Returns 0 or a negative SINDDM_E_*.  Host-only.  The three hooks below are its entry 5. */
+int sinddm_debug_routes(int dim_arg, int train, int B, int H, int W, int out[16]);
+
 /* Which kernel generation the dim -> dim 3x3 convolutions of a launch of this shape take on the current device:
  * 4 = conv_wino4 (F(2x4,3x3), one wave per SIMD), 3 = conv_wino3 (F(2x4,3x3)), 2 = F(2x2,3x3) kernels, 0 = direct
  * implicit GEMM; negative = SINDDM_E_*.  Lets a test assert that it exercises the kernel it means to. */

@@ -25,7 +25,7 @@ ABI_SYMBOLS = (
     "sinddm_cond_embed", "sinddm_cond_stride", "sinddm_sample_chain", "sinddm_sample_chain2", "sinddm_sample_chain_ex",
     "sinddm_normal_fill", "sinddm_wrap_halo", "sinddm_upsample_bilinear_wrap", "sinddm_sample_chain_tile",
     "sinddm_sample_chain_keep", "sinddm_reverse_step_keep", "sinddm_normal_fill_samples", "sinddm_sample_chain_seeds",
-    "sinddm_debug_head_path", "sinddm_debug_head_offsets", "sinddm_debug_head",
+    "sinddm_debug_head_path", "sinddm_debug_head_offsets", "sinddm_debug_head", "sinddm_debug_routes",
 )
 
 
@@ -118,6 +118,7 @@ def load() -> C.CDLL:
         "sinddm_debug_infer_path": (i, [i, i, i, i]),
         "sinddm_debug_train_path": (i, [i, i, i, i]),
         "sinddm_debug_head_path": (i, [i, i, i, i]),
+        "sinddm_debug_routes": (i, [i, i, i, i, i, C.POINTER(C.c_int)]),
         "sinddm_debug_head_offsets": (i, [i, C.POINTER(C.c_int64)]),
         "sinddm_debug_head": (i, [p, p, p, p, i, i, i, i, i, p]),
         "sinddm_debug_block_train": (i, [p, p, p, i, i, p, p, p, p, p, p, p, i, i, i, p, sz, p]),

@@ -52,6 +52,23 @@ namespace sinddm {
 #define SINDDM_WGRAD_ABL 0
 #endif
 
+inline bool wino_enabled() { return SINDDM_CONV_WINO != 0; }
+
+// CU count of the CURRENT device (kernel selection thresholds and persistent grid sizes).  Cached per device id: the
+// only mutable state of the library besides the debug profiler -- idempotent, and a race on it writes the same value.
+// (256, the MI355X's count, where no device answers: the host-only debug hooks)
+inline int cu_count() {
+    static int cache[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int v = cache[dev];
+    if (v <= 0) {
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
+        cache[dev] = v;
+    }
+    return v;
+}
+
 // Barrier that also publishes this wave's LDS-DMA (buffer_load ... lds).  __syncthreads() is a WORKGROUP-scope fence, for
 // which the gfx950 memory model waits on lgkmcnt only: an LDS-DMA counts on vmcnt and may still be in flight when the
 // other waves pass the barrier and read its destination.  (The compiler does wait before the issuing wave's OWN ds_reads

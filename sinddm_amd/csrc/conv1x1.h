@@ -11,7 +11,7 @@
 // ONE ds_read_b128 and a lane owns 4 consecutive pixels per (channel) in the epilogue: 16-byte stores / residual
 // loads instead of four 4-byte ones (the epilogue is store-issue bound).
 #pragma once
-#include "conv_mfma.h"
+#include "conv_args.h"
 
 namespace sinddm {
 
@@ -367,15 +367,7 @@ inline void conv1x1_all_launch(const ConvArgs& a, int tpi, int ntiles, hipStream
 
 inline int conv1x1_launch(const ConvArgs& a, int mt, hipStream_t st) {
     ConvProfiler& prof = conv_profiler();
-    const bool rec = prof.on && prof.used < ConvProfiler::MAXREC;
-    if (rec) {
-        while (prof.created <= prof.used) {
-            (void)hipEventCreate(&prof.ev[2 * prof.created]);
-            (void)hipEventCreate(&prof.ev[2 * prof.created + 1]);
-            ++prof.created;
-        }
-        (void)hipEventRecord(prof.ev[2 * prof.used], st);
-    }
+    const bool rec = prof.begin(st);
     const int HW = a.H * a.W;
     const int tpi = (HW + C1_PIX - 1) / C1_PIX;
     const dim3 grid((unsigned)(a.B * tpi), (unsigned)a.coblks);
@@ -399,9 +391,8 @@ inline int conv1x1_launch(const ConvArgs& a, int mt, hipStream_t st) {
         default: return SINDDM_E_BADSHAPE;
     }
     if (rec) {
-        (void)hipEventRecord(prof.ev[2 * prof.used + 1], st);
         const double fl = 2.0 * a.B * a.H * a.W * (double)a.Cout * (double)a.Cin2;
-        prof.note(2, fl, fl);
+        prof.end(st, 2, fl, fl);
     }
     SINDDM_LAUNCH_CHECK();
     return 0;

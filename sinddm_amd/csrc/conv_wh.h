@@ -663,7 +663,7 @@ inline bool conv_wh_applies(bool fp32_convs, int B, int H, int W, int cin, int c
     if ((long long)cin * H * W * 4 >= 0x40000000LL) return false;      // (one sample's input is addressed as a 32-bit buffer)
     if ((long long)H * W < SINDDM_WH_MIN_PIXELS) return false;
     return (long long)B * ((W + WH_TW - 1) / WH_TW) * ((H + WH_TH - 1) / WH_TH) * (cout / WH_COB) >=
-           (long long)SINDDM_WH_MIN_ITEMS_PER_CU * wino2_cu_count();
+           (long long)SINDDM_WH_MIN_ITEMS_PER_CU * cu_count();
 }
 
 inline int conv_wh_launch(const ConvArgs& a_in, hipStream_t st) {
@@ -671,15 +671,7 @@ inline int conv_wh_launch(const ConvArgs& a_in, hipStream_t st) {
     if (!wh_shape_ok(a.Cin, a.Cout) || a.W % 4 != 0 || !a.wsinv || (long long)a.Cin * a.H * a.W * 4 >= 0x40000000LL)
         return SINDDM_E_BADSHAPE;
     ConvProfiler& prof = conv_profiler();
-    const bool rec = prof.on && prof.used < ConvProfiler::MAXREC;
-    if (rec) {
-        while (prof.created <= prof.used) {
-            (void)hipEventCreate(&prof.ev[2 * prof.created]);
-            (void)hipEventCreate(&prof.ev[2 * prof.created + 1]);
-            ++prof.created;
-        }
-        (void)hipEventRecord(prof.ev[2 * prof.used], st);
-    }
+    const bool rec = prof.begin(st);
     a.nch3 = a.Cin / 16;
     a.coblks = a.Cout / WH_COB;
     a.tilesX = (a.W + WH_TW - 1) / WH_TW;
@@ -687,7 +679,7 @@ inline int conv_wh_launch(const ConvArgs& a_in, hipStream_t st) {
     a.ntiles = a.B * a.tilesX * a.tilesY;
     a.tiles_per_xcd = (a.ntiles + 7) / 8;
     const int ipx = a.tiles_per_xcd * a.coblks;
-    int wpx = wino2_cu_count() / 8;
+    int wpx = cu_count() / 8;
     if (wpx < 1) wpx = 1;
     if (wpx > ipx) wpx = ipx;
     static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wh_kernel),
@@ -699,10 +691,9 @@ inline int conv_wh_launch(const ConvArgs& a_in, hipStream_t st) {
 #endif
     hipLaunchKernelGGL(conv_wh_kernel, dim3(wpx * 8), dim3(512), WH_LDS, st, a, ipx, wpx);
     if (rec) {
-        (void)hipEventRecord(prof.ev[2 * prof.used + 1], st);
         const double fl = 2.0 * a.B * a.H * (a.Wt > 0 ? a.Wt : a.W) * (double)a.Cout * 9.0 * a.Cin;   // algorithmic (direct-conv) FLOPs
         // executed: four binary16 MFMA terms x 24 frequencies per 8 outputs, on whole 8x32 items
-        prof.note(1, fl, 2.0 * a.ntiles * 32.0 * 24.0 * 4.0 * (double)a.Cout * a.Cin, 8);
+        prof.end(st, 1, fl, 2.0 * a.ntiles * 32.0 * 24.0 * 4.0 * (double)a.Cout * a.Cin, 8);
     }
     SINDDM_LAUNCH_CHECK();
     return 0;

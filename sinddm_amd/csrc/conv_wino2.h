@@ -5,7 +5,8 @@
 // 16 "frequency" GEMMs  M_ij[co][tile] = sum_ci U_ij[co][ci] * V_ij[ci][tile]  replace the 9-tap implicit GEMM
 // (16 multiplies per 4 outputs instead of 36), all in fp32 on v_mfma_f32_16x16x4_f32.
 //
-// What changed against conv_wino.h (one 16-wave workgroup per CU, wave = one frequency), and why:
+// What changed against the first-generation kernel (one 16-wave workgroup per CU, wave = one frequency; archived as
+// tools/variants/conv_wino_gen1.h), and why:
 //   * TWO independent 4-wave workgroups per CU (256 registers per wave).  The first-generation kernel kept all 16
 //     waves of a CU in the same phase, so the matrix pipe idled through every output-transform epilogue (15 % of the
 //     launch), every chunk-barrier ramp (7 %) and every item prologue.  Two workgroups drift against each other:
@@ -648,32 +649,10 @@ inline void conv_wino2_launch_t(const ConvArgs& a, unsigned grid, int ipx, int w
     else conv_wino2_launch_e<MT, MTP, 2>(a, grid, ipx, wpx, st);                         // + 4-byte stores of the last odd column
 }
 
-// CU count of the CURRENT device (kernel selection thresholds and persistent grid sizes).  Cached per device id: the
-// only mutable state of the library besides the debug profiler -- idempotent, and a race on it writes the same value.
-inline int wino2_cu_count() {
-    static int cache[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int v = cache[dev];
-    if (v <= 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-        cache[dev] = v;
-    }
-    return v;
-}
-
 inline int conv_wino2_launch(const ConvArgs& a_in, int mt, hipStream_t st) {
     ConvArgs a = a_in;
     ConvProfiler& prof = conv_profiler();
-    const bool rec = prof.on && prof.used < ConvProfiler::MAXREC;
-    if (rec) {
-        while (prof.created <= prof.used) {
-            (void)hipEventCreate(&prof.ev[2 * prof.created]);
-            (void)hipEventCreate(&prof.ev[2 * prof.created + 1]);
-            ++prof.created;
-        }
-        (void)hipEventRecord(prof.ev[2 * prof.used], st);
-    }
+    const bool rec = prof.begin(st);
     a.tilesX = (a.W + W2_TW - 1) / W2_TW;
     a.tilesY = (a.H + W2_TH - 1) / W2_TH;
     a.ntiles = a.B * a.tilesX * a.tilesY;
@@ -682,16 +661,16 @@ inline int conv_wino2_launch(const ConvArgs& a_in, int mt, hipStream_t st) {
     // than CUs and every item walks the full reduction alone -- one m-tile per item gives 5x the items at a fifth of
     // the latency each (the packed weight image is addressed by global m-tile, so it serves both).
     a.mtp = mt;
-    if (mt > 1 && a.ntiles * a.coblks < wino2_cu_count()) {
+    if (mt > 1 && a.ntiles * a.coblks < cu_count()) {
         a.coblks *= mt;
         mt = 1;
     }
     // persistent launch: two 4-wave workgroups per CU, each walking its share of the XCD's work items
     const int ipx = a.tiles_per_xcd * a.coblks;                  // work items per XCD
 #ifdef W2_ONE_WG
-    int wpx = wino2_cu_count() / 8;
+    int wpx = cu_count() / 8;
 #else
-    int wpx = wino2_cu_count() / 8 * 2;                          // workgroups per XCD
+    int wpx = cu_count() / 8 * 2;                          // workgroups per XCD
 #endif
     if (wpx < 1) wpx = 1;
     if (wpx > ipx) wpx = ipx;
@@ -705,9 +684,8 @@ inline int conv_wino2_launch(const ConvArgs& a_in, int mt, hipStream_t st) {
         default: return SINDDM_E_BADSHAPE;
     }
     if (rec) {
-        (void)hipEventRecord(prof.ev[2 * prof.used + 1], st);
         const double fl = 2.0 * a.B * a.H * (a.Wt > 0 ? a.Wt : a.W) * (double)a.Cout * 9.0 * a.Cin;   // algorithmic (direct-conv) FLOPs
-        prof.note(1, fl, fl * (16.0 / 36.0), 2);
+        prof.end(st, 1, fl, fl * (16.0 / 36.0), 2);
     }
     SINDDM_LAUNCH_CHECK();
     return 0;

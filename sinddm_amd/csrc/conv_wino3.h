@@ -411,22 +411,14 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino3_kernel(ConvArgs p, i
 inline int conv_wino3_launch(const ConvArgs& a_in, hipStream_t st) {
     ConvArgs a = a_in;
     ConvProfiler& prof = conv_profiler();
-    const bool rec = prof.on && prof.used < ConvProfiler::MAXREC;
-    if (rec) {
-        while (prof.created <= prof.used) {
-            (void)hipEventCreate(&prof.ev[2 * prof.created]);
-            (void)hipEventCreate(&prof.ev[2 * prof.created + 1]);
-            ++prof.created;
-        }
-        (void)hipEventRecord(prof.ev[2 * prof.used], st);
-    }
+    const bool rec = prof.begin(st);
     a.tilesX = (a.W + W2_TW - 1) / W2_TW;
     a.tilesY = (a.H + W2_TH - 1) / W2_TH;
     a.ntiles = a.B * a.tilesX * a.tilesY;
     a.tiles_per_xcd = (a.ntiles + 7) / 8;
     a.mtp = W3_MT;
     const int ipx = a.tiles_per_xcd * a.coblks;
-    int wpx = wino2_cu_count() / 8 * 2;
+    int wpx = cu_count() / 8 * 2;
     if (wpx < 1) wpx = 1;
     if (wpx > ipx) wpx = ipx;
     const unsigned grid = (unsigned)(wpx * 8);
@@ -446,9 +438,8 @@ inline int conv_wino3_launch(const ConvArgs& a_in, hipStream_t st) {
     }
 #undef W3_GO
     if (rec) {
-        (void)hipEventRecord(prof.ev[2 * prof.used + 1], st);
         const double fl = 2.0 * a.B * a.H * (a.Wt > 0 ? a.Wt : a.W) * (double)a.Cout * 9.0 * a.Cin;   // algorithmic (direct-conv) FLOPs
-        prof.note(1, fl, fl * (24.0 / 72.0), 3);                                      // F(2x4): 24 multiplies per 8 outputs
+        prof.end(st, 1, fl, fl * (24.0 / 72.0), 3);                                      // F(2x4): 24 multiplies per 8 outputs
     }
     SINDDM_LAUNCH_CHECK();
     return 0;

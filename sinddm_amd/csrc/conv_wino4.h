@@ -664,21 +664,13 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
 
 inline bool conv_wino4_applies(int B, int H, int W, int coblks) {
     return (long long)B * ((W + W4_TW - 1) / W4_TW) * ((H + W4_TH - 1) / W4_TH) * coblks >=
-           (long long)SINDDM_V4_MIN_ITEMS_PER_CU * wino2_cu_count();
+           (long long)SINDDM_V4_MIN_ITEMS_PER_CU * cu_count();
 }
 
 inline int conv_wino4_launch(const ConvArgs& a_in, hipStream_t st) {
     ConvArgs a = a_in;
     ConvProfiler& prof = conv_profiler();
-    const bool rec = prof.on && prof.used < ConvProfiler::MAXREC;
-    if (rec) {
-        while (prof.created <= prof.used) {
-            (void)hipEventCreate(&prof.ev[2 * prof.created]);
-            (void)hipEventCreate(&prof.ev[2 * prof.created + 1]);
-            ++prof.created;
-        }
-        (void)hipEventRecord(prof.ev[2 * prof.used], st);
-    }
+    const bool rec = prof.begin(st);
     a.tilesX = (a.W + W4_TW - 1) / W4_TW;
     a.tilesY = (a.H + W4_TH - 1) / W4_TH;
     a.ntiles = a.B * a.tilesX * a.tilesY;
@@ -689,7 +681,7 @@ inline int conv_wino4_launch(const ConvArgs& a_in, hipStream_t st) {
     a.mtp = w4_launch_no++ % 8;                  // (the kernel does not read mtp: stamp row of this launch)
 #endif
     const int ipx = a.tiles_per_xcd * a.coblks;
-    int wpx = wino2_cu_count() / 8;              // one workgroup per CU
+    int wpx = cu_count() / 8;              // one workgroup per CU
     if (wpx < 1) wpx = 1;
     if (wpx > ipx) wpx = ipx;
     const unsigned grid = (unsigned)(wpx * 8);
@@ -716,9 +708,8 @@ inline int conv_wino4_launch(const ConvArgs& a_in, hipStream_t st) {
     }
 #undef W4_GO
     if (rec) {
-        (void)hipEventRecord(prof.ev[2 * prof.used + 1], st);
         const double fl = 2.0 * a.B * a.H * (a.Wt > 0 ? a.Wt : a.W) * (double)a.Cout * 9.0 * a.Cin;   // algorithmic (direct-conv) FLOPs
-        prof.note(1, fl, fl * (24.0 / 72.0), 4);                                      // F(2x4): 24 multiplies per 8 outputs
+        prof.end(st, 1, fl, fl * (24.0 / 72.0), 4);                                      // F(2x4): 24 multiplies per 8 outputs
     }
     SINDDM_LAUNCH_CHECK();
     return 0;

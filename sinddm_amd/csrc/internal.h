@@ -9,7 +9,7 @@ struct PackSeg {
     long long count;   // elements in this segment
     long long w;       // source weight offset (conv: [cout][cin][taps]), or bias offset
     long long w2;      // second bias offset to add (-1 none)
-    int kind;          // 0: conv chunks, 1: bias, 2: zero page, 3: Winograd F(2x2) 3x3 weights, 4: Winograd F(2x4) 3x3 weights, 5: Winograd F(4x4) 3x3 weights
+    int kind;          // 0: conv chunks, 1: bias, 2: zero page, 3: Winograd F(2x2) 3x3 weights, 4: Winograd F(2x4) 3x3 weights
     int cin, cout, taps, nch, mt, co_lds;
     int transpose;     // 1: data-gradient image (M = cin of the forward conv, taps flipped)
 };
@@ -19,6 +19,35 @@ struct PackArgs {
     long long total;
 };
 int pack_launch(const float* params, float* packed, const PackArgs& a, hipStream_t st);
+
+// appends one direct-kernel image (kind 0) of the conv whose weights are at `w` ([cout][cin][taps], forward orientation)
+inline void pack_add_direct(PackArgs& a, long long dst, long long w, int cin, int cout, int taps, int mt, int coblks, int transpose) {
+    PackSeg s{};
+    s.kind = 0; s.transpose = transpose; s.w2 = -1;
+    s.dst = dst; s.w = w; s.cin = cin; s.cout = cout; s.taps = taps; s.mt = mt; s.co_lds = co_lds_for(mt);
+    s.nch = ((transpose ? cout : cin) + KC - 1) / KC;
+    s.count = (long long)coblks * s.nch * taps * KC * s.co_lds;
+    a.seg[a.nseg++] = s;
+    a.total += s.count;
+}
+// appends the image of format `kind` (0 direct, 3 F(2x2), 4 F(2x4)) of a 3x3 conv, if it has one; `w` = offset of the
+// FORWARD conv's weights, transpose = 1: `c` describes its data gradient
+inline void pack_add_conv3x3(PackArgs& a, const Conv3x3Images& c, int kind, long long w, int transpose) {
+    const int cin = transpose ? c.M : c.K, cout = transpose ? c.K : c.M;       // of the forward conv
+    if (kind == 0) {
+        pack_add_direct(a, c.direct, w, cin, cout, 9, c.mt, c.coblks, transpose);
+        return;
+    }
+    const long long dst = kind == 3 ? c.wino2 : c.wino24;
+    if (dst < 0) return;
+    PackSeg s{};
+    s.kind = kind; s.transpose = transpose; s.w2 = -1; s.taps = 9;
+    s.dst = dst; s.w = w; s.cin = cin; s.cout = cout; s.mt = c.mt;
+    s.nch = conv3x3_nchw(c);
+    s.count = kind == 3 ? wino2_floats(c) : wino24_floats(c);
+    a.seg[a.nseg++] = s;
+    a.total += s.count;
+}
 
 // Saved activations (training forward) + backward scratch, carved from the caller's workspace.
 struct TrainBufs {
@@ -47,18 +76,28 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
 // one SinDDMConvBlock forward (sinddm_fwd.hip); `cond` = the block's per-sample bias rows, stride in floats
 int block_forward(const NetPlan& P, int l, const float* params, const float* packed, const float* cur, const float* cond,
                   int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, int B, int H, int W, hipStream_t st,
-                  int Wt = 0, float* amax = nullptr, bool skip2 = false);
-// which kernel generation a dim -> dim 3x3 conv launch of this shape takes: 4 / 3 = F(2x4) conv_wino4 / conv_wino3,
-// 2 = F(2x2) conv_wino2 / conv_wino, 0 = direct implicit GEMM
-int conv3x3_path(int cout, int cin, int coblks, int B, int H, int W);
+                  const int route[2], int Wt = 0, float* amax = nullptr);
+// Which kernel a 3x3 conv launch takes -- THE routing rule (sinddm_fwd.hip), asked by the forward, the backward's data
+// gradients, the sampler's "stay whole" check and the debug hooks alike.  The values are the ones the hooks report and
+// ConvProfiler::gen records.  have_amax: the running-max scalars conv_wh needs exist for this launch (forward: the
+// evaluation has them; backward: conv1's data gradient only when conv2's took conv_wh); first_conv: a block's conv1
+// (only it may take the C_in = 3 kernel).
+enum ConvKernel { CONV_DIRECT = 0, CONV_C3 = 1, CONV_WINO2 = 2, CONV_WINO3 = 3, CONV_WINO4 = 4, CONV_WH = 8 };
+ConvKernel conv3x3_route(const NetPlan& P, const Conv3x3Images& c, int B, int H, int W, bool have_amax, bool first_conv);
+// One launch of the routed kernel (every route but CONV_C3, which block_forward launches itself): fills w3, nch3, wsinv,
+// coblks and the m-tile count from the images at `packed`; the caller has set the tensors, act / aux / resid / bias, the
+// fused 1x1 fields of the direct kernel and the amax pointers.
+struct ConvArgs;
+int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st);
+// the routes of one network evaluation: out[2 l + i] = conv i + 1 of block l (-1: not launched -- block 4's conv2 under
+// the collapsed head).  Wp = the row pitch the evaluation runs at; returns whether any route is CONV_WH.
+bool forward_routes(const NetPlan& P, bool train, int B, int H, int Wp, bool have_amax, int out[8]);
+int forward_pitch(const NetPlan& P, int W);        // row pitch of an INFERENCE evaluation's activations
 
 // conv_wh.h (the Winograd F(2x4) kernel with binary16 hi/lo frequency GEMMs) lives in sinddm_fwd.hip; the backward TU
-// reaches it through these: the dispatch rule, one launch, the weight image of a conv (transpose = 1: of its data gradient)
-struct ConvArgs;
-bool wh_applies(const NetPlan& P, int B, int H, int W, int cin, int cout);   // (false for every launch of a plan with fp32_convs)
+// packs a conv's images (transpose = 1: of its data gradient) and asks whether the kernel is compiled in through these
 bool wh_enabled();       // compiled in
-int wh_conv(const ConvArgs& c, hipStream_t st);
-int wh_pack(const float* w, float* wsinv, void* img, int cin, int cout, int transpose, hipStream_t st);
+int wh_pack(const Conv3x3Images& c, const float* w, float* packed, int transpose, hipStream_t st);
 // max |x| of every sample of x[B][per_sample] (per_sample % 4 == 0) into amax[b * AMAX_STRIDE] (zeroed by the caller)
 int amax_tensor_launch(const float* x, float* amax, int B, long long per_sample, hipStream_t st);
 

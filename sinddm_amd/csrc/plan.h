@@ -3,6 +3,7 @@
 // SinDDM/models.py:54-67,100-132) and in the MFMA-ready packed weight image.
 #pragma once
 #include <stdint.h>
+#include <initializer_list>
 
 namespace sinddm {
 
@@ -14,26 +15,60 @@ constexpr int CHANNELS = 3;
 inline bool wh_plan_ok(int cin, int cout) { return cin >= 32 && cin % 16 == 0 && cout % 80 == 0; }
 inline long long wh_plan_halfs(int cin, int cout) { return (long long)(cout / 80) * (cin / 16) * 24 * 5 * 512; }
 
+inline int mt_for(int cout) { return (cout % 80 == 0) ? 5 : ((cout % 32 == 0) ? 2 : 1); }
+inline int co_lds_for(int mt) { int m = mt * 16; return (m % 32 == 16) ? m : m + 16; }
+
+// The weight images of ONE 3x3 conv, forward or data gradient: the single owner of every format's size and of the rule
+// that says whether the conv has it.  make_plan / make_bwd_pack only decide WHERE each image goes (their allocation
+// orders differ and are frozen); the pack functions, conv3x3_route and conv3x3_launch (internal.h) read this.
+struct Conv3x3Images {
+    int M, K;          // output / reduction channels of THIS conv (a data gradient: M = forward cin, K = forward cout)
+    int mt;            // 16-row M tiles per workgroup (5, 2 or 1)
+    int coblks;        // workgroups along M = ceil(M / (16 mt))
+    // offsets (floats) into the packed buffer, -1 = the conv has no such image
+    int64_t direct;    // conv_mfma.h   [coblk][chunk of KC k][tap][kc][co_lds]
+    int64_t wino2;     // conv_wino2.h  F(2x2,3x3), register layout [coblk][chunk of 16 k][i][ks][mt][lane][j]
+    int64_t wino24;    // conv_wino3/4.h F(2x4,3x3), [coblk][chunk][i][ks][q 0..7][lane][4]
+    int64_t wh;        // conv_wh.h     binary16 hi/lo F(2x4)
+    int64_t wh_sinv;   // ... and its per-output-channel 2^-e array
+};
+// cin / cout: of the FORWARD conv; transpose: describe its data gradient
+inline Conv3x3Images conv3x3_images(int cin, int cout, bool transpose) {
+    Conv3x3Images c{};
+    c.M = transpose ? cin : cout;
+    c.K = transpose ? cout : cin;
+    c.mt = mt_for(c.M);
+    c.coblks = (c.M + c.mt * 16 - 1) / (c.mt * 16);
+    c.direct = c.wino2 = c.wino24 = c.wh = c.wh_sinv = -1;
+    return c;
+}
+inline int conv3x3_nch(const Conv3x3Images& c) { return (c.K + KC - 1) / KC; }       // chunks of the direct image
+inline int conv3x3_nchw(const Conv3x3Images& c) { return (c.K + 15) / 16; }          // chunks of the Winograd images
+inline int64_t direct_floats(const Conv3x3Images& c) { return (int64_t)c.coblks * conv3x3_nch(c) * 9 * KC * co_lds_for(c.mt); }
+inline int64_t wino2_floats(const Conv3x3Images& c) { return (int64_t)c.coblks * conv3x3_nchw(c) * 16 * 4 * c.mt * 64; }
+// (32768 floats per (co-block, chunk): 4 waves x 4 k-steps x 8 groups x 64 lanes x 4)
+inline int64_t wino24_floats(const Conv3x3Images& c) { return (int64_t)c.coblks * conv3x3_nchw(c) * 32768; }
+inline int64_t wh_floats(const Conv3x3Images& c) { return wh_plan_halfs(c.K, c.M) / 2; }
+inline int64_t wh_sinv_floats(const Conv3x3Images& c) { return (c.M + 63) / 64 * 64; }
+// every conv has the direct image.  F(2x2): every conv2 and its data gradient; a conv1 (and its data gradient) only when
+// the FORWARD conv has C_in >= 8 (the C_in = 3 conv has its own kernel) -- `fwd_cin`, not K: the layouts are frozen
+inline bool wino2_image_ok(bool first_conv, int fwd_cin) { return !first_conv || fwd_cin >= 8; }
+// F(2x4): 80-row blocks and whole 16-channel chunks
+inline bool wino24_image_ok(const Conv3x3Images& c) { return c.mt == 5 && c.M % 80 == 0 && c.K >= 16 && c.K % 16 == 0; }
+inline bool wh_image_ok(const Conv3x3Images& c) { return wh_plan_ok(c.K, c.M); }
+
 struct BlockPlan {
     int cin, cout;
     // flat parameter offsets (floats)
     int64_t mlp_w, mlp_b, tr_w, tr_b, dw_w, dw_b, c1_w, c1_b, c2_w, c2_b, res_w, res_b;  // res_* = -1 if Identity
-    // MFMA tiling of the C_out dimension
+    // MFMA tiling of the C_out dimension (the 1x1 residual image and the bias rows; == c1.mt / c1.coblks)
     int mt;        // 16-row M tiles per workgroup (5, 2 or 1)
     int coblks;    // workgroups along C_out = ceil(cout / (16*mt))
     int co_lds;    // LDS/packed stride of the co axis (== 16 mod 32 -> conflict-free A reads)
-    int nch1;      // conv1 3x3 chunks  = ceil(cin / KC)
-    int nch2;      // conv2 3x3 chunks  = ceil(cout / KC)
     int nchr;      // residual 1x1 chunks = ceil(cin / KC) or 0
-    // packed image offsets (floats)
-    int64_t pk_c1, pk_c2, pk_res, pk_b1, pk_b2;
-    // Winograd F(2x2,3x3) images (register layout [coblk][chunk of 16 ci][xi][ks][mt][lane])
-    int nchw1, nchw2;          // 16-channel chunks of conv1 / conv2
-    int64_t pk_wc1, pk_wc2;    // pk_wc1 = -1 when conv1 stays on the direct kernel (C_in < 8)
-    // Winograd F(2x4,3x3) images of conv_wino3.h ([coblk][chunk][i][ks][q 0..7][lane][4]); -1 = shape not supported
-    int64_t pk_w1f, pk_w2f;
-    // conv_wh.h images and their per-output-channel 2^-e arrays; -1 = shape not supported
-    int64_t pk_q1, pk_q2, pk_qs1, pk_qs2;
+    Conv3x3Images c1, c2;   // conv1 (cin -> cout), conv2 (cout -> cout)
+    // packed image offsets (floats) of the 1x1 residual projection and the two bias rows
+    int64_t pk_res, pk_b1, pk_b2;
     int cond_off;  // offset of this block's per-sample bias inside the cond vector
 };
 
@@ -52,9 +87,6 @@ struct NetPlan {
     bool fp32_convs;   // per-call option SINDDM_DIM_FP32_CONVS: no launch takes the binary16 hi/lo kernels
     bool ok;
 };
-
-inline int mt_for(int cout) { return (cout % 80 == 0) ? 5 : ((cout % 32 == 0) ? 2 : 1); }
-inline int co_lds_for(int mt) { int m = mt * 16; return (m % 32 == 16) ? m : m + 16; }
 
 // dim_arg: the `dim` argument of the C ABI = SinDDMNet's width in the low 16 bits + option bits above (sinddm_hip.h);
 // the layouts (parameters, packed images, workspaces) do not depend on the options
@@ -100,31 +132,24 @@ inline NetPlan make_plan(int dim_arg) {
         b.mt = mt_for(b.cout);
         b.coblks = (b.cout + b.mt * 16 - 1) / (b.mt * 16);
         b.co_lds = co_lds_for(b.mt);
-        b.nch1 = (b.cin + KC - 1) / KC;
-        b.nch2 = (b.cout + KC - 1) / KC;
         b.nchr = (b.res_w >= 0) ? (b.cin + KC - 1) / KC : 0;
-        b.pk_c1 = q; q += (int64_t)b.coblks * b.nch1 * 9 * KC * b.co_lds;
-        b.pk_c2 = q; q += (int64_t)b.coblks * b.nch2 * 9 * KC * b.co_lds;
+        b.c1 = conv3x3_images(b.cin, b.cout, false);
+        b.c2 = conv3x3_images(b.cout, b.cout, false);
+        b.c1.direct = q; q += direct_floats(b.c1);
+        b.c2.direct = q; q += direct_floats(b.c2);
         b.pk_res = q; q += (int64_t)b.coblks * b.nchr * KC * b.co_lds;
         b.pk_b1 = q; q += (int64_t)b.coblks * b.mt * 16;
         b.pk_b2 = q; q += (int64_t)b.coblks * b.mt * 16;
-        b.nchw1 = (b.cin + 15) / 16;
-        b.nchw2 = (b.cout + 15) / 16;
-        if (b.cin >= 8) { b.pk_wc1 = q; q += (int64_t)b.coblks * b.nchw1 * 16 * 4 * b.mt * 64; } else b.pk_wc1 = -1;
-        b.pk_wc2 = q; q += (int64_t)b.coblks * b.nchw2 * 16 * 4 * b.mt * 64;
-        // (32768 floats per (co-block, chunk): 4 waves x 4 k-steps x 8 groups x 64 lanes x 4)
-        const bool f24 = b.mt == 5 && b.cout % 80 == 0;
-        if (f24 && b.cin >= 16 && b.cin % 16 == 0) { b.pk_w1f = q; q += (int64_t)b.coblks * b.nchw1 * 32768; } else b.pk_w1f = -1;
-        if (f24 && b.cout % 16 == 0) { b.pk_w2f = q; q += (int64_t)b.coblks * b.nchw2 * 32768; } else b.pk_w2f = -1;
+        if (wino2_image_ok(true, b.cin)) { b.c1.wino2 = q; q += wino2_floats(b.c1); }
+        if (wino2_image_ok(false, b.cout)) { b.c2.wino2 = q; q += wino2_floats(b.c2); }
+        if (wino24_image_ok(b.c1)) { b.c1.wino24 = q; q += wino24_floats(b.c1); }
+        if (wino24_image_ok(b.c2)) { b.c2.wino24 = q; q += wino24_floats(b.c2); }
         q = (q + 63) / 64 * 64;
-        if (wh_plan_ok(b.cin, b.cout)) {
-            b.pk_q1 = q; q += wh_plan_halfs(b.cin, b.cout) / 2;
-            b.pk_qs1 = q; q += (b.cout + 63) / 64 * 64;
-        } else b.pk_q1 = b.pk_qs1 = -1;
-        if (wh_plan_ok(b.cout, b.cout)) {
-            b.pk_q2 = q; q += wh_plan_halfs(b.cout, b.cout) / 2;
-            b.pk_qs2 = q; q += (b.cout + 63) / 64 * 64;
-        } else b.pk_q2 = b.pk_qs2 = -1;
+        for (Conv3x3Images* c : {&b.c1, &b.c2})
+            if (wh_image_ok(*c)) {
+                c->wh = q; q += wh_floats(*c);
+                c->wh_sinv = q; q += wh_sinv_floats(*c);
+            }
         b.cond_off = coff;
         coff += b.cin;
     }

@@ -4,9 +4,8 @@
 // Replaces autograd through SinDDMNet + torch.optim.Adam + EMA of the reference
 // (SinDDM/models.py:578-611, trainer.py:134,194-214, models.py:18-31).
 #include <utility>
-#include "conv_mfma.h"
-#include "conv_wino.h"
-#include "conv_wino4.h"
+#include "conv_args.h"
+#include "conv1x1.h"
 #include "internal.h"
 #include "wgrad_wino.h"
 #include "wgrad_wh.h"
@@ -529,7 +528,7 @@ static int wgrad_launch(const float* zero, const float* dout, const float* in, f
         w.tilesX = (W + WW_TW - 1) / WW_TW;
         w.tilesY = (H + WW_TH - 1) / WW_TH;
         w.ntiles = B * w.tilesX * w.tilesY;
-        nwg = ww_build_map(w, device_cu_count());      // 0: more slabs than the launch table holds -> the direct kernels below
+        nwg = ww_build_map(w, cu_count());      // 0: more slabs than the launch table holds -> the direct kernels below
     }
     if (nwg > 0) {
         // Winograd-domain weight gradient (2.25x fewer MFMAs); always through the [co][tap][ci] staging slab
@@ -552,25 +551,16 @@ static int wgrad_launch(const float* zero, const float* dout, const float* in, f
         if ((wide ? attr_wide : attr_dword) != hipSuccess) return (int)(wide ? attr_wide : attr_dword);
         if (h16 && attr_h16 != hipSuccess) return (int)attr_h16;
         ConvProfiler& prof = conv_profiler();
-        const bool rec = prof.on && prof.used < ConvProfiler::MAXREC;
-        if (rec) {
-            while (prof.created <= prof.used) {
-                (void)hipEventCreate(&prof.ev[2 * prof.created]);
-                (void)hipEventCreate(&prof.ev[2 * prof.created + 1]);
-                ++prof.created;
-            }
-            (void)hipEventRecord(prof.ev[2 * prof.used], st);
-        }
+        const bool rec = prof.begin(st);
         if (h16) hipLaunchKernelGGL(wgrad_wh_kernel, dim3((unsigned)nwg), dim3(WW_THREADS), lds, st, w);
         else if (wide) hipLaunchKernelGGL(wgrad_wino_wide_kernel, dim3((unsigned)nwg), dim3(WW_THREADS), lds, st, w);
         else hipLaunchKernelGGL(wgrad_wino_kernel, dim3((unsigned)nwg), dim3(WW_THREADS), lds, st, w);
         SINDDM_LAUNCH_CHECK();
         if (rec) {
-            (void)hipEventRecord(prof.ev[2 * prof.used + 1], st);
             const double fl = 2.0 * B * H * W * (double)Cout * Cin * 9.0;
             // kind 4 = Winograd-domain weight gradient, F(2x2): 16/36 executed; generation 8 = binary16 pieces, four terms
-            if (h16) prof.note(4, fl, fl * 16.0 / 36.0 * 4.0, 8);
-            else prof.note(4, fl, fl * 16.0 / 36.0);
+            if (h16) prof.end(st, 4, fl, fl * 16.0 / 36.0 * 4.0, 8);
+            else prof.end(st, 4, fl, fl * 16.0 / 36.0);
         }
         hipLaunchKernelGGL(wgrad_unstage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scr, gw, Cin, n);
         SINDDM_LAUNCH_CHECK();
@@ -585,7 +575,7 @@ static int wgrad_launch(const float* zero, const float* dout, const float* in, f
         a.tilesY = 1;
         a.ntiles = B * a.tilesX;
         const int pairs = a.coblks * a.ciblks;
-        int S = (device_cu_count() / pairs) / 8 * 8;
+        int S = (cu_count() / pairs) / 8 * 8;
         if (S < 8) S = 8;
         const int cap = (a.ntiles + 7) / 8 * 8;
         if (S > cap) S = cap;
@@ -601,7 +591,7 @@ static int wgrad_launch(const float* zero, const float* dout, const float* in, f
         a.coblks = Cout / W3_C;
         a.ciblks = (Cin + W3_C - 1) / W3_C;
         const int pairs = a.coblks * a.ciblks;
-        int S = (device_cu_count() / pairs) / 8 * 8;
+        int S = (cu_count() / pairs) / 8 * 8;
         if (S < 8) S = 8;
         const int cap = (a.ntiles + 7) / 8 * 8;
         if (S > cap) S = cap;
@@ -983,58 +973,41 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
 // =====================================================================================
 struct BwdPack {
     // per block: dgrad of conv2 (cout->cout), dgrad of conv1 (cout->cin), dgrad of res 1x1 (cout->cin)
-    long long dg2[4], dg1[4], dres[4], dfin, zero;
-    long long wdg2[4], wdg1[4];     // Winograd images of the 3x3 data-gradient convs (wdg1 = -1: stays direct)
-    long long wdg2f[4], wdg1f[4];   // their F(2x4) images (conv_wino3.h), -1 = shape not supported
-    long long qdg2[4], qdg1[4];     // their binary16 hi/lo F(2x4) images (conv_wh.h), -1 = shape not supported
-    long long qs2[4], qs1[4];       // ... and the per-output-channel scales of those
+    Conv3x3Images dg2[4], dg1[4];
+    long long dres[4], dfin, zero;
     long long total;
-    int mt2[4], mt1[4], cb2[4], cb1[4];
     int mtf, cbf;
 };
 
+// (allocation order: format by format -- the direct images with the 1x1 ones, F(2x2), F(2x4), binary16)
 static BwdPack make_bwd_pack(const NetPlan& P) {
     BwdPack k{};
     long long q = 0;
     for (int l = 0; l < 4; ++l) {
         const BlockPlan& b = P.blk[l];
-        k.mt2[l] = mt_for(b.cout); k.cb2[l] = (b.cout + k.mt2[l] * 16 - 1) / (k.mt2[l] * 16);
-        k.mt1[l] = mt_for(b.cin);  k.cb1[l] = (b.cin + k.mt1[l] * 16 - 1) / (k.mt1[l] * 16);
-        const int nchK = (b.cout + KC - 1) / KC;      // K channels of every dgrad = forward cout
-        k.dg2[l] = q; q += (long long)k.cb2[l] * nchK * 9 * KC * co_lds_for(k.mt2[l]);
-        k.dg1[l] = q; q += (long long)k.cb1[l] * nchK * 9 * KC * co_lds_for(k.mt1[l]);
-        if (b.res_w >= 0) { k.dres[l] = q; q += (long long)k.cb1[l] * nchK * KC * co_lds_for(k.mt1[l]); }
+        k.dg2[l] = conv3x3_images(b.cout, b.cout, true);
+        k.dg1[l] = conv3x3_images(b.cin, b.cout, true);
+        k.dg2[l].direct = q; q += direct_floats(k.dg2[l]);
+        k.dg1[l].direct = q; q += direct_floats(k.dg1[l]);
+        if (b.res_w >= 0) { k.dres[l] = q; q += (long long)k.dg1[l].coblks * conv3x3_nch(k.dg1[l]) * KC * co_lds_for(k.dg1[l].mt); }
         else k.dres[l] = -1;
     }
     k.mtf = mt_for(P.half); k.cbf = (P.half + k.mtf * 16 - 1) / (k.mtf * 16);
     k.dfin = q; q += (long long)k.cbf * 1 * KC * co_lds_for(k.mtf);     // K = 3 channels -> one chunk
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        const int nchW = (b.cout + 15) / 16;
-        k.wdg2[l] = q; q += (long long)k.cb2[l] * nchW * 16 * 4 * k.mt2[l] * 64;
-        if (b.cin >= 8) { k.wdg1[l] = q; q += (long long)k.cb1[l] * nchW * 16 * 4 * k.mt1[l] * 64; }
-        else k.wdg1[l] = -1;
+        if (wino2_image_ok(false, P.blk[l].cout)) { k.dg2[l].wino2 = q; q += wino2_floats(k.dg2[l]); }
+        if (wino2_image_ok(true, P.blk[l].cin)) { k.dg1[l].wino2 = q; q += wino2_floats(k.dg1[l]); }
     }
-    // F(2x4) Winograd images of the data-gradient convs (conv_wino3.h): 80-channel row blocks, K = forward cout % 16 == 0
+    for (int l = 0; l < 4; ++l)
+        for (Conv3x3Images* c : {&k.dg2[l], &k.dg1[l]})
+            if (wino24_image_ok(*c)) { c->wino24 = q; q += wino24_floats(*c); }
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        const int nchW = (b.cout + 15) / 16;
-        const bool kok = b.cout % 16 == 0;
-        if (kok && k.mt2[l] == 5 && b.cout % 80 == 0) { k.wdg2f[l] = q; q += (long long)k.cb2[l] * nchW * 32768; } else k.wdg2f[l] = -1;
-        if (kok && k.mt1[l] == 5 && b.cin % 80 == 0) { k.wdg1f[l] = q; q += (long long)k.cb1[l] * nchW * 32768; } else k.wdg1f[l] = -1;
-    }
-    // binary16 hi/lo images of the same convs (conv_wh.h): K = forward cout in 16-channel chunks, 80-channel row blocks
-    for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
         q = (q + 63) / 64 * 64;
-        if (wh_plan_ok(b.cout, b.cout)) {
-            k.qdg2[l] = q; q += wh_plan_halfs(b.cout, b.cout) / 2;
-            k.qs2[l] = q; q += (b.cout + 63) / 64 * 64;
-        } else k.qdg2[l] = k.qs2[l] = -1;
-        if (wh_plan_ok(b.cout, b.cin)) {
-            k.qdg1[l] = q; q += wh_plan_halfs(b.cout, b.cin) / 2;
-            k.qs1[l] = q; q += (b.cin + 63) / 64 * 64;
-        } else k.qdg1[l] = k.qs1[l] = -1;
+        for (Conv3x3Images* c : {&k.dg2[l], &k.dg1[l]})
+            if (wh_image_ok(*c)) {
+                c->wh = q; q += wh_floats(*c);
+                c->wh_sinv = q; q += wh_sinv_floats(*c);
+            }
     }
     k.zero = q; q += 64;
     k.total = q;
@@ -1044,81 +1017,38 @@ static BwdPack make_bwd_pack(const NetPlan& P) {
 static int pack_backward(const NetPlan& P, const float* params, float* packed, hipStream_t st) {
     const BwdPack k = make_bwd_pack(P);
     PackArgs a{};
-    int n = 0;
-    long long total = 0;
-    auto add = [&](long long dst, long long w, int fcin, int fcout, int taps, int mt, int coblks) {
-        PackSeg s{};
-        s.kind = 0; s.transpose = 1; s.w2 = -1;
-        s.dst = dst; s.w = w; s.cin = fcin; s.cout = fcout; s.taps = taps; s.mt = mt; s.co_lds = co_lds_for(mt);
-        s.nch = (fcout + KC - 1) / KC;
-        s.count = (long long)coblks * s.nch * taps * KC * s.co_lds;
-        a.seg[n++] = s;
-        total += s.count;
-    };
     for (int l = 0; l < 4; ++l) {
         const BlockPlan& b = P.blk[l];
-        add(k.dg2[l], b.c2_w, b.cout, b.cout, 9, k.mt2[l], k.cb2[l]);
-        add(k.dg1[l], b.c1_w, b.cin, b.cout, 9, k.mt1[l], k.cb1[l]);
-        if (b.res_w >= 0) add(k.dres[l], b.res_w, b.cin, b.cout, 1, k.mt1[l], k.cb1[l]);
+        pack_add_conv3x3(a, k.dg2[l], 0, b.c2_w, 1);
+        pack_add_conv3x3(a, k.dg1[l], 0, b.c1_w, 1);
+        if (b.res_w >= 0) pack_add_direct(a, k.dres[l], b.res_w, b.cin, b.cout, 1, k.dg1[l].mt, k.dg1[l].coblks, 1);
     }
-    add(k.dfin, P.fin_w, P.half, CHANNELS, 1, k.mtf, k.cbf);
-    auto addw = [&](long long dst, long long w, int fcin, int fcout, int mt, int coblks) {
-        PackSeg s{};
-        s.kind = 3; s.transpose = 1; s.w2 = -1; s.taps = 9;
-        s.dst = dst; s.w = w; s.cin = fcin; s.cout = fcout; s.mt = mt;
-        s.nch = (fcout + 15) / 16;
-        s.count = (long long)coblks * s.nch * 16 * 4 * mt * 64;
-        a.seg[n++] = s;
-        total += s.count;
-    };
+    pack_add_direct(a, k.dfin, P.fin_w, P.half, CHANNELS, 1, k.mtf, k.cbf, 1);
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        addw(k.wdg2[l], b.c2_w, b.cout, b.cout, k.mt2[l], k.cb2[l]);
-        if (k.wdg1[l] >= 0) addw(k.wdg1[l], b.c1_w, b.cin, b.cout, k.mt1[l], k.cb1[l]);
+        pack_add_conv3x3(a, k.dg2[l], 3, P.blk[l].c2_w, 1);
+        pack_add_conv3x3(a, k.dg1[l], 3, P.blk[l].c1_w, 1);
     }
     {
         PackSeg z{};
         z.kind = 2; z.dst = k.zero; z.count = 64;
-        a.seg[n++] = z;
-        total += z.count;
+        a.seg[a.nseg++] = z;
+        a.total += z.count;
     }
-    a.nseg = n;
-    a.total = total;
     int rc = pack_launch(params, packed, a, st);
     if (rc) return rc;
     PackArgs f{};
-    n = 0;
-    total = 0;
-    auto addf = [&](long long dst, long long w, int fcin, int fcout, int coblks) {
-        PackSeg s{};
-        s.kind = 4; s.transpose = 1; s.w2 = -1; s.taps = 9; s.mt = 5;
-        s.dst = dst; s.w = w; s.cin = fcin; s.cout = fcout;
-        s.nch = (fcout + 15) / 16;
-        s.count = (long long)coblks * s.nch * 32768;
-        f.seg[n++] = s;
-        total += s.count;
-    };
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        if (k.wdg2f[l] >= 0) addf(k.wdg2f[l], b.c2_w, b.cout, b.cout, k.cb2[l]);
-        if (k.wdg1f[l] >= 0) addf(k.wdg1f[l], b.c1_w, b.cin, b.cout, k.cb1[l]);
+        pack_add_conv3x3(f, k.dg2[l], 4, P.blk[l].c2_w, 1);
+        pack_add_conv3x3(f, k.dg1[l], 4, P.blk[l].c1_w, 1);
     }
-    if (n > 0) {
-        f.nseg = n;
-        f.total = total;
+    if (f.nseg > 0) {
         rc = pack_launch(params, packed, f, st);
         if (rc) return rc;
     }
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        if (k.qdg2[l] >= 0) {
-            rc = wh_pack(params + b.c2_w, packed + k.qs2[l], packed + k.qdg2[l], b.cout, b.cout, 1, st);
-            if (rc) return rc;
-        }
-        if (k.qdg1[l] >= 0) {
-            rc = wh_pack(params + b.c1_w, packed + k.qs1[l], packed + k.qdg1[l], b.cin, b.cout, 1, st);
-            if (rc) return rc;
-        }
+        rc = wh_pack(k.dg2[l], params + P.blk[l].c2_w, packed, 1, st);
+        if (!rc) rc = wh_pack(k.dg1[l], params + P.blk[l].c1_w, packed, 1, st);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -1157,34 +1087,22 @@ static size_t carve_train(const NetPlan& P, int B, int H, int W, char* base, Tra
     return off;
 }
 
-static int conv1x1_or_3x3(const float* zero, const float* in3, int cin3, const float* w3, int nch3, const float* in1,
-                          int cin1, const float* w1, int nch1, const float* aux, int act, float* out, int Cout, int mt,
-                          int coblks, int B, int H, int W, hipStream_t st) {
+// a pure channel-mixing (1x1) data gradient on the HBM-bound 1x1 kernel
+static int conv1x1_dgrad(const float* zero, const float* in1, int cin1, const float* w1, int nch1, float* out, int Cout, int mt,
+                         int coblks, int B, int H, int W, hipStream_t st) {
     ConvArgs c{};
     c.zero = zero;
-    c.in = in3; c.Cin = cin3; c.w3 = w3; c.nch3 = nch3;
     c.in2 = in1; c.Cin2 = cin1; c.w1 = w1; c.nch1 = nch1;
-    c.aux = aux; c.act = act; c.out = out; c.Cout = Cout; c.coblks = coblks;
+    c.out = out; c.Cout = Cout; c.coblks = coblks;
     c.B = B; c.H = H; c.W = W;
-    if (nch3 == 0) return conv1x1_launch(c, mt, st);       // pure channel mixing: the HBM-bound 1x1 kernel
-    return conv_launch(c, mt, st);
+    return conv1x1_launch(c, mt, st);
 }
 
-// `wf`: the F(2x4) image of the same conv (or nullptr): big launches take conv_wino3.h
-static int conv3x3_wino(const float* zero, const float* in3, int cin3, const float* ww, const float* wf, const float* aux,
-                        int act, float* out, int Cout, int mt, int coblks, int B, int H, int W, hipStream_t st) {
-    ConvArgs c{};
-    c.zero = zero;
-    c.in = in3; c.Cin = cin3; c.w3 = ww; c.nch3 = (cin3 + 15) / 16; c.nch1 = 0;
-    c.aux = aux; c.act = act; c.out = out; c.Cout = Cout; c.coblks = coblks;
-    c.B = B; c.H = H; c.W = W;
-    if (SINDDM_WINO_V3 && wf && mt == 5 &&
-        (long long)B * ((W + 31) / 32) * ((H + 3) / 4) * coblks >= SINDDM_V3_MIN_ITEMS_PER_CU * wino2_cu_count()) {
-        c.w3 = wf;
-        if (SINDDM_WINO_V4 && conv_wino4_applies(B, H, W, coblks)) return conv_wino4_launch(c, st);
-        return conv_wino3_launch(c, st);
-    }
-    return conv_wino_launch(c, mt, st);
+// the routes of block l's two 3x3 data gradients: out[0] = conv2's, out[1] = conv1's (which may take conv_wh only behind a
+// conv2 gradient that did: its epilogue publishes the running max of dU)
+static void backward_routes(const NetPlan& P, const BwdPack& k, int l, int B, int H, int W, bool have_amax, int out[2]) {
+    out[0] = conv3x3_route(P, k.dg2[l], B, H, W, have_amax, false);
+    out[1] = conv3x3_route(P, k.dg1[l], B, H, W, out[0] == CONV_WH, false);
 }
 
 // Backward of ONE SinDDMConvBlock (autograd of reference SinDDM/models.py:69-80): dO = gradient of the block output (scratch,
@@ -1196,19 +1114,19 @@ static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float
     const BlockPlan& b = P.blk[l];
     const float* zp = packed_bwd + k.zero;
     int rc;
-    const int nchK = (b.cout + KC - 1) / KC;
     // the two 3x3 data-gradient convs on the binary16 hi/lo Winograd kernel (conv_wh.h) where its rule takes the launch;
     // `amax_b` = the backward half of tb.amax (zeroed by the caller): slot 2l = max |dO| per sample (maintained by the kernel
     // that wrote dO when `dO_published`), slot 2l + 1 = max |dU| (by the first conv's epilogue)
-    const bool wh2 = amax_b && wino_enabled() && k.qdg2[l] >= 0 && wh_applies(P, B, H, W, b.cout, b.cout);
-    const bool wh1 = wh2 && k.qdg1[l] >= 0 && wh_applies(P, B, H, W, b.cout, b.cin);
+    int route[2];
+    backward_routes(P, k, l, B, H, W, amax_b != nullptr, route);
+    const bool wh2 = route[0] == CONV_WH, wh1 = route[1] == CONV_WH;
     if (wh2 && !dO_published) {
         rc = amax_tensor_launch(dO, amax_b + 2 * l, B, (long long)b.cout * H * W, st);
         if (rc) return rc;
     }
     // conv2 + residual projection weight grads
     // (the running maxima of g = conv2's forward input and of h = conv1's are the forward half of tb.amax, slots 2l + 1 / 2l)
-    const bool wha = wh1 && wh_plan_ok(b.cin, b.cout) && wh_applies(P, B, H, W, b.cin, b.cout);
+    const bool wha = wh1 && conv3x3_route(P, b.c1, B, H, W, true, true) == CONV_WH;
     rc = wgrad_launch(zp, dO, tb.g[l], grads + b.c2_w, grads + b.c2_b, B, H, W, b.cout, b.cout, 9, st, tb.wscr,
                       wh2 ? amax_b + 2 * l : nullptr, wh2 ? tb.amax + 2 * l + 1 : nullptr);
     if (rc) return rc;
@@ -1217,35 +1135,25 @@ static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float
         if (rc) return rc;
     }
     // dU = dgrad_conv2(dO) * GELU'(u)
-    if (wh2) {
+    {
         ConvArgs c{};
-        c.zero = zp; c.in = dO; c.Cin = b.cout; c.w3 = packed_bwd + k.qdg2[l]; c.wsinv = packed_bwd + k.qs2[l];
-        c.amax_in = amax_b + 2 * l; c.amax_out = wh1 ? amax_b + 2 * l + 1 : nullptr;
-        c.aux = tb.u[l]; c.act = 2; c.out = dU; c.Cout = b.cout; c.B = B; c.H = H; c.W = W;
-        rc = wh_conv(c, st);
-    } else if (wino_enabled() && b.cout % 4 == 0)        // (K of both data-gradient convs = cout; % 4: see conv_wino_launch)
-        rc = conv3x3_wino(zp, dO, b.cout, packed_bwd + k.wdg2[l], k.wdg2f[l] >= 0 ? packed_bwd + k.wdg2f[l] : nullptr, tb.u[l], 2,
-                          dU, b.cout, k.mt2[l], k.cb2[l], B, H, W, st);
-    else
-        rc = conv1x1_or_3x3(zp, dO, b.cout, packed_bwd + k.dg2[l], nchK, nullptr, 0, nullptr, 0, tb.u[l], 2, dU,
-                            b.cout, k.mt2[l], k.cb2[l], B, H, W, st);
+        c.zero = zp; c.in = dO; c.Cin = b.cout; c.aux = tb.u[l]; c.act = 2; c.out = dU; c.Cout = b.cout;
+        c.B = B; c.H = H; c.W = W;
+        if (wh2) { c.amax_in = amax_b + 2 * l; c.amax_out = wh1 ? amax_b + 2 * l + 1 : nullptr; }
+        rc = conv3x3_launch((ConvKernel)route[0], k.dg2[l], packed_bwd, c, st);
+    }
     if (rc) return rc;
     // conv1 weight grads, dH = dgrad_conv1(dU)
     rc = wgrad_launch(zp, dU, tb.h[l], grads + b.c1_w, grads + b.c1_b, B, H, W, b.cin, b.cout, 9, st, tb.wscr,
                       wha ? amax_b + 2 * l + 1 : nullptr, wha ? tb.amax + 2 * l : nullptr);
     if (rc) return rc;
-    if (wh1) {
+    {
         ConvArgs c{};
-        c.zero = zp; c.in = dU; c.Cin = b.cout; c.w3 = packed_bwd + k.qdg1[l]; c.wsinv = packed_bwd + k.qs1[l];
-        c.amax_in = amax_b + 2 * l + 1;
-        c.act = 0; c.out = dH; c.Cout = b.cin; c.B = B; c.H = H; c.W = W;
-        rc = wh_conv(c, st);
-    } else if (wino_enabled() && k.wdg1[l] >= 0 && b.cout % 4 == 0)
-        rc = conv3x3_wino(zp, dU, b.cout, packed_bwd + k.wdg1[l], k.wdg1f[l] >= 0 ? packed_bwd + k.wdg1f[l] : nullptr, nullptr, 0,
-                          dH, b.cin, k.mt1[l], k.cb1[l], B, H, W, st);
-    else
-        rc = conv1x1_or_3x3(zp, dU, b.cout, packed_bwd + k.dg1[l], nchK, nullptr, 0, nullptr, 0, nullptr, 0, dH,
-                            b.cin, k.mt1[l], k.cb1[l], B, H, W, st);
+        c.zero = zp; c.in = dU; c.Cin = b.cout; c.act = 0; c.out = dH; c.Cout = b.cin;
+        c.B = B; c.H = H; c.W = W;
+        if (wh1) c.amax_in = amax_b + 2 * l + 1;
+        rc = conv3x3_launch((ConvKernel)route[1], k.dg1[l], packed_bwd, c, st);
+    }
     if (rc) return rc;
     // depthwise weight/bias grads and the per-sample condition grads
     if (SINDDM_DWG_ROWS && W % 4 == 0 && W >= 192)
@@ -1259,14 +1167,14 @@ static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float
     if (dst) {
         const float* radd = dO;                      // identity residual
         if (b.res_w >= 0) {
-            rc = conv1x1_or_3x3(zp, nullptr, 0, nullptr, 0, dO, b.cout, packed_bwd + k.dres[l], nchK, nullptr, 0, dU,
-                                b.cin, k.mt1[l], k.cb1[l], B, H, W, st);     // dU is free again
+            rc = conv1x1_dgrad(zp, dO, b.cout, packed_bwd + k.dres[l], conv3x3_nch(k.dg1[l]), dU, b.cin, k.dg1[l].mt,
+                               k.dg1[l].coblks, B, H, W, st);     // dU is free again
             if (rc) return rc;
             radd = dU;
         }
         // (dst is the next block's dO: its running max comes out of this launch when that block's convs will want it)
         float* pub = nullptr;
-        if (amax_b && l > 0 && wino_enabled() && k.qdg2[l - 1] >= 0 && wh_applies(P, B, H, W, b.cin, b.cin)) pub = amax_b + 2 * (l - 1);
+        if (l > 0 && conv3x3_route(P, k.dg2[l - 1], B, H, W, amax_b != nullptr, false) == CONV_WH) pub = amax_b + 2 * (l - 1);
         rc = dwconv_launch(dH, params + b.dw_w, nullptr, nullptr, 0, radd, 1, dst, B, b.cin, H, W, st, 0, 0, pub);
         if (rc) return rc;
     }
@@ -1285,8 +1193,7 @@ static int net_backward_impl(const NetPlan& P, const float* params, const float*
     int di = 0;   // index of the scratch buffer holding dOut of the current block
     float* amax_b = tb.amax + (size_t)B * AMAX_STRIDE;
     if (hipMemsetAsync(amax_b, 0, (size_t)B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
-    rc = conv1x1_or_3x3(zp, nullptr, 0, nullptr, 0, grad_out, CHANNELS, packed_bwd + k.dfin, 1, nullptr, 0, tb.s[di],
-                        P.half, k.mtf, k.cbf, B, H, W, st);
+    rc = conv1x1_dgrad(zp, grad_out, CHANNELS, packed_bwd + k.dfin, 1, tb.s[di], P.half, k.mtf, k.cbf, B, H, W, st);
     if (rc) return rc;
     for (int l = 3; l >= 0; --l) {
         const float* xin = (l == 0) ? x : tb.o[l - 1];
@@ -1395,19 +1302,30 @@ int sinddm_adam_ema_step(float* p, const float* g, float* m, float* v, float* em
     return 0;
 }
 
+int sinddm_debug_routes(int dim_arg, int train, int B, int H, int W, int out[16]) {
+    NetPlan p = make_plan(dim_arg);
+    if (!p.ok || !out || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    for (int i = 0; i < 16; ++i) out[i] = -1;
+    // (both evaluations have the running-max scalars: the workspace carves them)
+    forward_routes(p, train != 0, B, H, train ? W : forward_pitch(p, W), true, out);
+    if (train) {
+        const BwdPack k = make_bwd_pack(p);
+        for (int l = 0; l < 4; ++l) backward_routes(p, k, l, B, H, W, true, out + 8 + 2 * l);
+    }
+    return 0;
+}
+
+// the three one-number hooks: conv2 of the dim -> dim block (block 3)
 int sinddm_debug_conv_path(int dim, int B, int H, int W) {
-    NetPlan p = make_plan(dim);
-    if (!p.ok || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
-    const BlockPlan& b = p.blk[2];                      // the dim -> dim block
-    return conv3x3_path(b.cout, b.cout, b.coblks, B, H, W);
+    int r[16];
+    const int rc = sinddm_debug_routes(dim | SINDDM_DIM_FP32_CONVS, 1, B, H, W, r);
+    return rc ? rc : r[5];
 }
 
 int sinddm_debug_train_path(int dim, int B, int H, int W) {
-    NetPlan p = make_plan(dim);
-    if (!p.ok || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
-    const BlockPlan& b = p.blk[2];
-    if (wino_enabled() && b.pk_q2 >= 0 && wh_applies(p, B, H, W, b.cout, b.cout)) return 8;
-    return conv3x3_path(b.cout, b.cout, b.coblks, B, H, W);
+    int r[16];
+    const int rc = sinddm_debug_routes(dim, 1, B, H, W, r);
+    return rc ? rc : r[5];
 }
 
 int sinddm_debug_block_train(const float* params, const float* packed, const float* packed_bwd, int dim, int l,
@@ -1425,7 +1343,8 @@ int sinddm_debug_block_train(const float* params, const float* packed, const flo
     const BlockPlan& b = p.blk[l];
     const size_t HW = (size_t)H * W;
     if (hipMemsetAsync(tb.amax, 0, (size_t)2 * B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
-    int rc = block_forward(p, l, params, packed, x, cond_bias, b.cin, tb.h[l], tb.g[l], tb.o[l], tb.u[l], B, H, W, st, 0,
+    const int route[2] = {conv3x3_route(p, b.c1, B, H, W, true, true), conv3x3_route(p, b.c2, B, H, W, true, false)};
+    int rc = block_forward(p, l, params, packed, x, cond_bias, b.cin, tb.h[l], tb.g[l], tb.o[l], tb.u[l], B, H, W, st, route, 0,
                            tb.amax + 2 * l);
     if (rc) return rc;
     if (hipMemcpyAsync(y, tb.o[l], B * b.cout * HW * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)

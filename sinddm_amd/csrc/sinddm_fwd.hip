@@ -1,7 +1,6 @@
 // Forward path of the SinDDM hot path for gfx950: weight packing, conditioning MLP, depthwise
 // 5x5, MFMA 3x3 convs, final 1x1, and the HBM-bound diffusion elementwise kernels.
 #include "conv_mfma.h"
-#include "conv_wino.h"
 #include "conv_wino4.h"
 #include "conv_wh.h"
 #include "internal.h"
@@ -48,7 +47,6 @@ __global__ void pack_kernel(const float* __restrict__ params, float* __restrict_
     } else if (g.kind == 3) {
         // Winograd F(2x2,3x3): U_xi = G g G^T in the MFMA A-operand register image
         // [coblk][chunk of 16 ci][xi][ks][mt][lane]; lane -> (co = lane&15, ci = lane>>4)
-#if SINDDM_WINO_V2
         // second-generation kernel (conv_wino2.h): [coblk][chunk][i][ks][mt][lane][j] -- a lane's four frequencies
         // (i, 0..3) are one 16-byte load; frequency row 2 is stored negated (the kernel evaluates d1 - d2 for it)
         long long r = j;
@@ -60,15 +58,6 @@ __global__ void pack_kernel(const float* __restrict__ params, float* __restrict_
         const int xi = fi_ * 4 + fj_;
         const int ch = (int)(r % g.nch); r /= g.nch;
         const int cb = (int)r;
-#else
-        const int lane = (int)(j % 64);
-        long long r = j / 64;
-        const int mt = (int)(r % g.mt); r /= g.mt;
-        const int ks = (int)(r % 4); r /= 4;
-        const int xi = (int)(r % 16); r /= 16;
-        const int ch = (int)(r % g.nch); r /= g.nch;
-        const int cb = (int)r;
-#endif
         const int m = cb * g.mt * 16 + mt * 16 + (lane & 15);
         const int k = ch * 16 + ks * 4 + (lane >> 4);
         const int M = g.transpose ? g.cin : g.cout;      // rows of THIS conv
@@ -93,7 +82,7 @@ __global__ void pack_kernel(const float* __restrict__ params, float* __restrict_
                 for (int b2 = 0; b2 < 3; ++b2) rowv += G[fj][b2] * gt[a][b2];
                 acc += G[fi][a] * rowv;
             }
-            v = (SINDDM_WINO_V2 && fi == 2) ? -acc : acc;
+            v = fi == 2 ? -acc : acc;
         }
     } else if (g.kind == 4) {
         // Winograd F(2x4,3x3) of conv_wino3.h: U = G2 g G4^T, register image [coblk][chunk][i][ks][q][lane][slot];
@@ -147,36 +136,14 @@ int pack_launch(const float* params, float* packed, const PackArgs& a, hipStream
 
 static int pack_forward(const NetPlan& P, const float* params, float* packed, hipStream_t st) {
     PackArgs a{};
-    int n = 0;
-    long long total = 0;
-    auto add = [&](PackSeg s) { a.seg[n++] = s; total += s.count; };
+    auto add = [&](PackSeg s) { a.seg[a.nseg++] = s; a.total += s.count; };
     for (int l = 0; l < 4; ++l) {
         const BlockPlan& b = P.blk[l];
-        PackSeg s{};
-        s.kind = 0; s.mt = b.mt; s.co_lds = b.co_lds; s.transpose = 0; s.w2 = -1;
-        // conv1: cin -> cout, 3x3
-        s.dst = b.pk_c1; s.count = (long long)b.coblks * b.nch1 * 9 * KC * b.co_lds;
-        s.w = b.c1_w; s.cin = b.cin; s.cout = b.cout; s.taps = 9; s.nch = b.nch1;
-        add(s);
-        // conv2: cout -> cout, 3x3
-        s.dst = b.pk_c2; s.count = (long long)b.coblks * b.nch2 * 9 * KC * b.co_lds;
-        s.w = b.c2_w; s.cin = b.cout; s.cout = b.cout; s.taps = 9; s.nch = b.nch2;
-        add(s);
-        if (b.nchr > 0) {
-            s.dst = b.pk_res; s.count = (long long)b.coblks * b.nchr * KC * b.co_lds;
-            s.w = b.res_w; s.cin = b.cin; s.cout = b.cout; s.taps = 1; s.nch = b.nchr;
-            add(s);
-        }
-        PackSeg wz{};
-        wz.kind = 3; wz.mt = b.mt; wz.transpose = 0; wz.w2 = -1; wz.taps = 9;
-        if (b.pk_wc1 >= 0) {
-            wz.dst = b.pk_wc1; wz.nch = b.nchw1; wz.count = (long long)b.coblks * b.nchw1 * 16 * 4 * b.mt * 64;
-            wz.w = b.c1_w; wz.cin = b.cin; wz.cout = b.cout;
-            add(wz);
-        }
-        wz.dst = b.pk_wc2; wz.nch = b.nchw2; wz.count = (long long)b.coblks * b.nchw2 * 16 * 4 * b.mt * 64;
-        wz.w = b.c2_w; wz.cin = b.cout; wz.cout = b.cout;
-        add(wz);
+        pack_add_conv3x3(a, b.c1, 0, b.c1_w, 0);
+        pack_add_conv3x3(a, b.c2, 0, b.c2_w, 0);
+        if (b.nchr > 0) pack_add_direct(a, b.pk_res, b.res_w, b.cin, b.cout, 1, b.mt, b.coblks, 0);
+        pack_add_conv3x3(a, b.c1, 3, b.c1_w, 0);
+        pack_add_conv3x3(a, b.c2, 3, b.c2_w, 0);
         PackSeg t{};
         t.kind = 1; t.cout = b.cout; t.count = (long long)b.coblks * b.mt * 16;
         t.dst = b.pk_b1; t.w = b.c1_b; t.w2 = -1;
@@ -187,47 +154,23 @@ static int pack_forward(const NetPlan& P, const float* params, float* packed, hi
     PackSeg z{};
     z.kind = 2; z.dst = P.pk_zero; z.count = 64;
     add(z);
-    a.nseg = n;
-    a.total = total;
     int rc = pack_launch(params, packed, a, st);
     if (rc) return rc;
     // second launch: the F(2x4) Winograd images of conv_wino3.h
     PackArgs f{};
-    n = 0;
-    total = 0;
-    auto addf = [&](PackSeg sg) { f.seg[n++] = sg; total += sg.count; };
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        PackSeg wz{};
-        wz.kind = 4; wz.mt = b.mt; wz.transpose = 0; wz.w2 = -1; wz.taps = 9;
-        if (b.pk_w1f >= 0) {
-            wz.dst = b.pk_w1f; wz.nch = b.nchw1; wz.count = (long long)b.coblks * b.nchw1 * 32768;
-            wz.w = b.c1_w; wz.cin = b.cin; wz.cout = b.cout;
-            addf(wz);
-        }
-        if (b.pk_w2f >= 0) {
-            wz.dst = b.pk_w2f; wz.nch = b.nchw2; wz.count = (long long)b.coblks * b.nchw2 * 32768;
-            wz.w = b.c2_w; wz.cin = b.cout; wz.cout = b.cout;
-            addf(wz);
-        }
+        pack_add_conv3x3(f, P.blk[l].c1, 4, P.blk[l].c1_w, 0);
+        pack_add_conv3x3(f, P.blk[l].c2, 4, P.blk[l].c2_w, 0);
     }
-    if (n > 0) {
-        f.nseg = n;
-        f.total = total;
+    if (f.nseg > 0) {
         rc = pack_launch(params, packed, f, st);
         if (rc) return rc;
     }
     // the binary16 hi/lo images of conv_wh.h and their per-channel scales
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        if (b.pk_q1 >= 0) {
-            rc = wh_pack_launch(params + b.c1_w, packed + b.pk_qs1, packed + b.pk_q1, b.cin, b.cout, 0, st);
-            if (rc) return rc;
-        }
-        if (b.pk_q2 >= 0) {
-            rc = wh_pack_launch(params + b.c2_w, packed + b.pk_qs2, packed + b.pk_q2, b.cout, b.cout, 0, st);
-            if (rc) return rc;
-        }
+        rc = wh_pack(P.blk[l].c1, params + P.blk[l].c1_w, packed, 0, st);
+        if (!rc) rc = wh_pack(P.blk[l].c2, params + P.blk[l].c2_w, packed, 0, st);
+        if (rc) return rc;
     }
     // the composed weights of the collapsed inference head (head.h)
     return head_pack_launch(P, params, packed, st);
@@ -869,16 +812,15 @@ static size_t cond_region_bytes(const NetPlan& P, int B) {
 #endif
 // row pitch of the library's own activation buffers in inference: W rounded up to 4 floats
 // Padded rows need every producer to write the pad columns as zeros (ConvArgs::Wt): the depthwise kernels, the C_in = 3
-// conv, the Winograd kernels of conv_wino2/3/4.h and conv_wh do; the direct implicit-GEMM kernel (conv_mfma.h) and the
-// first-generation Winograd kernel do not.  So the pitch is a property of the PLAN: rows are padded only when
+// conv, the Winograd kernels of conv_wino2/3/4.h and conv_wh do; the direct implicit-GEMM kernel (conv_mfma.h) does not.  So the pitch is a property of the PLAN: rows are padded only when
 // block_forward routes every 3x3 conv of the network to a Wt-aware kernel (all channel counts multiples of 4, C_in = 3 or
 // >= 8) -- other widths (--dim 10, 20, 28 ...) keep plain rows and the kernels' edge variants.
 static bool plan_pads_rows(const NetPlan& P) {
-    if (!SINDDM_PITCH || !wino_enabled() || !SINDDM_WINO_V2 || !SINDDM_CONV_C3) return false;
+    if (!SINDDM_PITCH || !wino_enabled() || !SINDDM_CONV_C3) return false;
     for (int l = 0; l < 4; ++l) {
         const BlockPlan& b = P.blk[l];
         if (b.cout % 4 != 0) return false;
-        if (b.cin != 3 && !(b.pk_wc1 >= 0 && b.cin % 4 == 0)) return false;
+        if (b.cin != 3 && !(b.c1.wino2 >= 0 && b.cin % 4 == 0)) return false;
     }
     return true;
 }
@@ -920,127 +862,133 @@ static void tail_dispatch(const TailArgs& t, F&& f) {
 // where a sampler run fuses its tail ((H W) % 4 == 0 or padded rows: sample_chain_impl); a plane stays below the buffer
 // loads' out-of-range offset.  Every other shape keeps its launches, kernel for kernel; training (`tb`) needs block 4's
 // output for backward.
-static bool head_applies(const TrainBufs* tb, int H, int Wp) {
-    return SINDDM_HEAD_COLLAPSE && !tb && Wp % 4 == 0 && (long long)H * Wp < (1LL << 28);
+static bool head_applies(bool train, int H, int Wp) {
+    return SINDDM_HEAD_COLLAPSE && !train && Wp % 4 == 0 && (long long)H * Wp < (1LL << 28);
 }
 static HeadEps head_eps(const NetPlan& P, const float* packed, const float* g, const float* xin, int H, int Wp) {
     return HeadEps{g, xin, packed + P.pk_hc, packed + P.pk_hr, packed + P.pk_hb, P.half, P.dim, H, Wp};
 }
 
-int conv3x3_path(int cout, int cin, int coblks, int B, int H, int W) {
-    if (!wino_enabled() || cout % 4 != 0) return 0;
-    const bool f24 = mt_for(cout) == 5 && cout % 80 == 0 && cin >= 16 && cin % 16 == 0;
-    const bool v3 = SINDDM_WINO_V3 && f24 &&
-                    (long long)B * ((W + 31) / 32) * ((H + 3) / 4) * coblks >= SINDDM_V3_MIN_ITEMS_PER_CU * wino2_cu_count();
-    if (v3 && SINDDM_WINO_V4 && conv_wino4_applies(B, H, W, coblks)) return 4;
-    return v3 ? 3 : 2;
+// THE routing rule of the 3x3 convs (internal.h): conv_wh where the running maxima exist and its own rule takes the launch;
+// launches with enough work for every workgroup slot the F(2x4) kernels (25 % fewer MFMAs), the ones with several 8x32
+// items per CU conv_wino4's one-wave-per-SIMD form; then F(2x2) (its kernel stages a wave's four channel planes of a chunk
+// through one descriptor: K % 4 == 0 -- dim = 10, 20, 28 ... stay direct); the C_in = 3 kernel; the direct implicit GEMM.
+ConvKernel conv3x3_route(const NetPlan& P, const Conv3x3Images& c, int B, int H, int W, bool have_amax, bool first_conv) {
+    if (wino_enabled() && c.K % 4 == 0) {
+        if (have_amax && c.wh >= 0 && conv_wh_applies(P.fp32_convs, B, H, W, c.K, c.M)) return CONV_WH;
+        if (SINDDM_WINO_V3 && c.wino24 >= 0 &&
+            (long long)B * ((W + 31) / 32) * ((H + 3) / 4) * c.coblks >= SINDDM_V3_MIN_ITEMS_PER_CU * cu_count())
+            return SINDDM_WINO_V4 && conv_wino4_applies(B, H, W, c.coblks) ? CONV_WINO4 : CONV_WINO3;
+        if (c.wino2 >= 0) return CONV_WINO2;
+    }
+    return first_conv && c.K == 3 && SINDDM_CONV_C3 ? CONV_C3 : CONV_DIRECT;
 }
+
+int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st) {
+    a.coblks = c.coblks;
+    switch (k) {
+        case CONV_WH:
+            a.w3 = packed + c.wh; a.wsinv = packed + c.wh_sinv;
+            return conv_wh_launch(a, st);
+        case CONV_WINO4:
+        case CONV_WINO3:
+            a.w3 = packed + c.wino24; a.nch3 = conv3x3_nchw(c);
+            return k == CONV_WINO4 ? conv_wino4_launch(a, st) : conv_wino3_launch(a, st);
+        case CONV_WINO2:
+            if (a.Cin % 4 != 0) return SINDDM_E_BADSHAPE;       // (see conv3x3_route)
+            a.w3 = packed + c.wino2; a.nch3 = conv3x3_nchw(c);
+            return conv_wino2_launch(a, c.mt, st);
+        case CONV_DIRECT:
+            a.w3 = packed + c.direct; a.nch3 = conv3x3_nch(c);
+            return conv_launch(a, c.mt, st);
+        default: return SINDDM_E_BADARG;
+    }
+}
+
+bool forward_routes(const NetPlan& P, bool train, int B, int H, int Wp, bool have_amax, int out[8]) {
+    const bool head = head_applies(train, H, Wp);
+    bool any = false;
+    for (int l = 0; l < 4; ++l) {
+        out[2 * l] = conv3x3_route(P, P.blk[l].c1, B, H, Wp, have_amax, true);
+        out[2 * l + 1] = head && l == 3 ? -1 : conv3x3_route(P, P.blk[l].c2, B, H, Wp, have_amax, false);
+        any = any || out[2 * l] == CONV_WH || out[2 * l + 1] == CONV_WH;
+    }
+    return any;
+}
+int forward_pitch(const NetPlan& P, int W) { return fwd_pitch(P, W); }
 
 // One SinDDMConvBlock forward (reference SinDDM/models.py:69-80): depthwise 5x5 + per-sample condition -> hbuf, 3x3 conv +
 // GELU -> gbuf (pre-activation -> upre when the training forward saves it), 3x3 conv + residual (1x1 projection or
 // identity of `cur`) -> obuf.  `cond` = the block's per-sample bias rows ([B][cond_stride]; stride 0: one row for the batch).
+// route: the ConvKernel of conv1 and conv2 (forward_routes).  route[1] < 0: the block stops behind conv1 (block 4 in front of
+// the collapsed head, which reads gbuf and cur itself): no conv2, no residual projection, and conv1 does not publish the
+// running max that conv2 would read.
 // Wt > 0: padded workspace rows -- every tensor here (cur included) has row pitch W (a multiple of 4) and true width Wt.
-// skip2: the block stops behind conv1 (block 4 in front of the collapsed head, which reads gbuf and cur itself): no conv2, no
-// residual projection, and conv1 does not publish the running max that conv2 would read.
+// amax = this block's two running-max scalars (input of conv1, input of conv2), maintained by the kernels that produce
+// those tensors for the convs that conv_wh takes.
 int block_forward(const NetPlan& P, int l, const float* params, const float* packed, const float* cur, const float* cond,
                   int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, int B, int H, int W, hipStream_t st,
-                  int Wt, float* amax, bool skip2) {
+                  const int route[2], int Wt, float* amax) {
     const BlockPlan& b = P.blk[l];
-    // the Winograd F(2x4) kernel with binary16 hi/lo frequency GEMMs (conv_wh.h) where its rule takes the launch; `amax` = this
-    // block's two running-max scalars (input of conv1, input of conv2), maintained by the kernels that produce those tensors
-    const bool wha = amax && b.pk_q1 >= 0 && conv_wh_applies(P.fp32_convs, B, H, W, b.cin, b.cout);
-    const bool whb = !skip2 && amax && b.pk_q2 >= 0 && conv_wh_applies(P.fp32_convs, B, H, W, b.cout, b.cout);
+    const bool wha = route[0] == CONV_WH, whb = route[1] == CONV_WH;
+    if ((wha || whb) && !amax) return SINDDM_E_BADARG;
     int rc = Wt > 0 ? dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
                                     Wt, st, W, W, wha ? amax : nullptr)
                     : dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
                                     W, st, 0, 0, wha ? amax : nullptr);
     if (rc) return rc;
-    const bool wino = wino_enabled();
-    ConvArgs c1{};
-    c1.in = hbuf; c1.bias = packed + b.pk_b1; c1.out = gbuf;
-    c1.B = B; c1.H = H; c1.W = W; c1.Cin = b.cin; c1.Cout = b.cout; c1.nch1 = 0;
-    c1.coblks = b.coblks; c1.act = 1; c1.zero = packed + P.pk_zero; c1.Wt = Wt;
-    c1.out_pre = upre;
-    constexpr int c3 = SINDDM_CONV_C3;
-    // launches with enough work for every workgroup slot take the F(2x4) kernel (25 % fewer MFMAs)
-    const bool v3 = SINDDM_WINO_V3 && wino &&
-                    (long long)B * ((W + 31) / 32) * ((H + 3) / 4) * b.coblks >= SINDDM_V3_MIN_ITEMS_PER_CU * wino2_cu_count();
-    // ... and the ones with several 8x32 items per CU its one-wave-per-SIMD form (weights shared by two n-tiles)
-    const bool v4 = SINDDM_WINO_V4 && v3 && conv_wino4_applies(B, H, W, b.coblks);
-    if (wha) {
-        c1.w3 = packed + b.pk_q1; c1.wsinv = packed + b.pk_qs1; c1.amax_in = amax; c1.amax_out = whb ? amax + 1 : nullptr;
-        c1.bias = params + b.c1_b;
-        rc = conv_wh_launch(c1, st);
-    } else if (v3 && b.pk_w1f >= 0) {
-        c1.w3 = packed + b.pk_w1f; c1.nch3 = b.nchw1;
-        rc = v4 ? conv_wino4_launch(c1, st) : conv_wino3_launch(c1, st);
-    } else if (wino && b.pk_wc1 >= 0 && b.cin % 4 == 0) {
-        c1.w3 = packed + b.pk_wc1; c1.nch3 = b.nchw1;
-        rc = conv_wino_launch(c1, b.mt, st);
-    } else if (b.cin == 3 && c3) {
+    if (route[0] == CONV_C3) {
         // C_in = 3: dedicated VALU kernel straight from the PyTorch-layout weights
         const int nwg = ((H * W + 255) / 256) * B;
         int split = 1;                                       // channel groups: aim at >= ~2048 workgroups
         while (split < 8 && nwg * split < 2048 && b.cout % (split * 2) == 0) split *= 2;
         hipLaunchKernelGGL(conv3x3_c3_gelu_kernel, dim3((H * W + 255) / 256, B, split), dim3(256), 0, st, hbuf,
-                           params + b.c1_w, params + b.c1_b, gbuf, c1.out_pre, H, W, b.cout, b.cout / split, Wt > 0 ? Wt : W,
+                           params + b.c1_w, params + b.c1_b, gbuf, upre, H, W, b.cout, b.cout / split, Wt > 0 ? Wt : W,
                            whb ? amax + 1 : nullptr);
         SINDDM_LAUNCH_CHECK();
-        rc = 0;
     } else {
-        c1.w3 = packed + b.pk_c1; c1.nch3 = b.nch1;
-        rc = conv_launch(c1, b.mt, st);
+        ConvArgs c1{};
+        c1.in = hbuf; c1.out = gbuf; c1.out_pre = upre;
+        c1.B = B; c1.H = H; c1.W = W; c1.Cin = b.cin; c1.Cout = b.cout;
+        c1.act = 1; c1.zero = packed + P.pk_zero; c1.Wt = Wt;
+        c1.bias = wha ? params + b.c1_b : packed + b.pk_b1;      // (conv_wh reads the plain bias row)
+        if (wha) { c1.amax_in = amax; c1.amax_out = whb ? amax + 1 : nullptr; }
+        rc = conv3x3_launch((ConvKernel)route[0], b.c1, packed, c1, st);
     }
-    if (rc || skip2) return rc;
+    if (rc || route[1] < 0) return rc;
     // conv2 on the binary16 kernel reads the running max of g (slot amax + 1): conv_wh / the C_in = 3 kernel publish it
     // from their epilogues, the fp32 kernels do not (dim = 80 / 240: block 1 has C_in = dim / 2, not a multiple of 16, so conv1
     // stays on an fp32 kernel while conv2 qualifies) -- one pass over g then
-    if (whb && !(wha || (b.cin == 3 && c3 && !(v3 && b.pk_w1f >= 0) && !(wino && b.pk_wc1 >= 0 && b.cin % 4 == 0)))) {
+    if (whb && !wha && route[0] != CONV_C3) {
         rc = amax_tensor_launch(gbuf, amax + 1, B, (long long)b.cout * H * W, st);
         if (rc) return rc;
     }
     ConvArgs c2{};
     c2.in = gbuf; c2.out = obuf;
     c2.B = B; c2.H = H; c2.W = W; c2.Cin = b.cout; c2.Cout = b.cout;
-    c2.coblks = b.coblks; c2.act = 0; c2.zero = packed + P.pk_zero; c2.Wt = Wt;
-    if (wino && b.cout % 4 == 0) {       // (C_in of conv2 = cout; % 4: see conv_wino_launch)
-        // Winograd 3x3; a 1x1 residual projection runs first on the direct kernel and is added as `resid`
-        if (b.nchr > 0) {
-            ConvArgs r1{};
-            r1.in2 = cur; r1.Cin2 = b.cin; r1.w1 = packed + b.pk_res; r1.nch1 = b.nchr; r1.nch3 = 0;
-            r1.bias = packed + b.pk_b2; r1.out = obuf; r1.Cout = b.cout; r1.coblks = b.coblks;
-            r1.B = B; r1.H = H; r1.W = W; r1.zero = packed + P.pk_zero;
-            rc = conv1x1_launch(r1, b.mt, st);
-            if (rc) return rc;
-            c2.resid = obuf; c2.bias = nullptr;          // in place: each thread reads resid[o] before writing out[o]
-        } else {
-            c2.resid = cur; c2.bias = packed + b.pk_b2;
-        }
-        c2.nch1 = 0;
-        if (whb) {
-            c2.w3 = packed + b.pk_q2; c2.wsinv = packed + b.pk_qs2; c2.amax_in = amax + 1;
-            rc = conv_wh_launch(c2, st);
-        } else if (v3 && b.pk_w2f >= 0) {
-            c2.w3 = packed + b.pk_w2f; c2.nch3 = b.nchw2;
-            rc = v4 ? conv_wino4_launch(c2, st) : conv_wino3_launch(c2, st);
-        } else {
-            c2.w3 = packed + b.pk_wc2; c2.nch3 = b.nchw2;
-            rc = conv_wino_launch(c2, b.mt, st);
-        }
+    c2.act = 0; c2.zero = packed + P.pk_zero; c2.Wt = Wt;
+    c2.bias = packed + b.pk_b2;
+    if (b.nchr == 0) c2.resid = cur;
+    else if (route[1] == CONV_DIRECT) {          // the direct kernel fuses the 1x1 residual projection
+        c2.in2 = cur; c2.Cin2 = b.cin; c2.w1 = packed + b.pk_res; c2.nch1 = b.nchr;
     } else {
-        c2.w3 = packed + b.pk_c2; c2.bias = packed + b.pk_b2; c2.nch3 = b.nch2;
-        if (b.nchr > 0) { c2.in2 = cur; c2.Cin2 = b.cin; c2.w1 = packed + b.pk_res; c2.nch1 = b.nchr; }
-        else { c2.resid = cur; c2.nch1 = 0; }
-        rc = conv_launch(c2, b.mt, st);
+        // the Winograd kernels do not: it runs first on the 1x1 kernel and is added as `resid`
+        ConvArgs r1{};
+        r1.in2 = cur; r1.Cin2 = b.cin; r1.w1 = packed + b.pk_res; r1.nch1 = b.nchr; r1.nch3 = 0;
+        r1.bias = packed + b.pk_b2; r1.out = obuf; r1.Cout = b.cout; r1.coblks = b.coblks;
+        r1.B = B; r1.H = H; r1.W = W; r1.zero = packed + P.pk_zero;
+        rc = conv1x1_launch(r1, b.mt, st);
+        if (rc) return rc;
+        c2.resid = obuf; c2.bias = nullptr;          // in place: each thread reads resid[o] before writing out[o]
     }
-    return rc;
+    if (whb) c2.amax_in = amax + 1;
+    return conv3x3_launch((ConvKernel)route[1], b.c2, packed, c2, st);
 }
 
-bool wh_applies(const NetPlan& P, int B, int H, int W, int cin, int cout) { return conv_wh_applies(P.fp32_convs, B, H, W, cin, cout); }
 bool wh_enabled() { return SINDDM_CONV_WH != 0; }
-int wh_conv(const ConvArgs& c, hipStream_t st) { return conv_wh_launch(c, st); }
-int wh_pack(const float* w, float* wsinv, void* img, int cin, int cout, int transpose, hipStream_t st) {
-    return wh_pack_launch(w, wsinv, img, cin, cout, transpose, st);
+int wh_pack(const Conv3x3Images& c, const float* w, float* packed, int transpose, hipStream_t st) {
+    if (c.wh < 0) return 0;
+    return wh_pack_launch(w, packed + c.wh_sinv, packed + c.wh, transpose ? c.M : c.K, transpose ? c.K : c.M, transpose, st);
 }
 
 __global__ __launch_bounds__(256) void amax_tensor_kernel(const float* __restrict__ x, float* __restrict__ amax, long long n4) {
@@ -1057,7 +1005,7 @@ int amax_tensor_launch(const float* x, float* amax, int B, long long per_sample,
     if (per_sample % 4 != 0) return SINDDM_E_BADSHAPE;
     const long long n4 = per_sample / 4;
     long long bx = (n4 + 2047) / 2048;                    // eight 16-byte loads per lane
-    const long long cap = (8LL * wino2_cu_count() + B - 1) / B;
+    const long long cap = (8LL * cu_count() + B - 1) / B;
     if (bx > cap) bx = cap;
     if (bx < 1) bx = 1;
     hipLaunchKernelGGL(amax_tensor_kernel, dim3((unsigned)bx, B), dim3(256), 0, st, x, amax, n4);
@@ -1100,19 +1048,12 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         SINDDM_LAUNCH_CHECK();
     }
 
-    const bool head = head_applies(tb, H, Wp);
-    if (amax) {
-        // the running-max scalars exist for the binary16 kernels: a launch shape none of them takes (coarse pyramid scales)
-        // neither maintains nor zeroes them
-        bool any = false;
-        for (int l = 0; l < 4; ++l) {
-            const BlockPlan& b = P.blk[l];
-            any = any || (b.pk_q1 >= 0 && conv_wh_applies(P.fp32_convs, B, H, Wp, b.cin, b.cout)) ||
-                  (!(head && l == 3) && b.pk_q2 >= 0 && conv_wh_applies(P.fp32_convs, B, H, Wp, b.cout, b.cout));
-        }
-        if (!any) amax = nullptr;
-        else if (hipMemsetAsync(amax, 0, (size_t)B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
-    }
+    // the routes of this evaluation's eight 3x3 convs.  The running-max scalars exist for the binary16 kernels: a launch
+    // shape none of them takes (coarse pyramid scales) neither maintains nor zeroes them
+    int route[8];
+    if (!forward_routes(P, tb != nullptr, B, H, Wp, amax != nullptr, route)) amax = nullptr;
+    else if (hipMemsetAsync(amax, 0, (size_t)B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
+    const bool head = route[7] < 0;
     const float* cur = x;
     if (padded) {
         const long long nrows = (long long)B * CHANNELS * H;
@@ -1133,12 +1074,11 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         float* hbuf = tb ? tb->h[l] : fb.buf[sel[0]];
         float* gbuf = tb ? tb->g[l] : fb.buf[sel[1]];
         float* obuf = tb ? tb->o[l] : fb.buf[sel[2]];
-        const bool skip2 = head && l == 3;
         const int rc = block_forward(P, l, params, packed, cur, fb.cond + b.cond_off, cond_stride, hbuf, gbuf, obuf,
-                                     tb ? tb->u[l] : nullptr, B, H, Wp, st, padded ? W : 0, amax ? amax + 2 * l : nullptr,
-                                     skip2);
+                                     tb ? tb->u[l] : nullptr, B, H, Wp, st, route + 2 * l, padded ? W : 0,
+                                     amax ? amax + 2 * l : nullptr);
         if (rc) return rc;
-        if (skip2) { head_g = gbuf; break; }                 // (cur stays block 4's input)
+        if (route[2 * l + 1] < 0) { head_g = gbuf; break; }  // (the collapsed head: cur stays block 4's input)
         cur = obuf;
         curb = sel[2];
     }
@@ -1383,13 +1323,13 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     // overlap: the tail round of one fills with the other's items.  Same numbers either way (the noise is keyed on the
     // whole batch's flat index: ChainStep::b0; with per-sample seeds the second half gets its own part of the array).
     const long long items = (long long)B * ((fwd_pitch(p, W) + 31) / 32) * ((H + 7) / 8) * 2;
-    const long long ncu = wino2_cu_count();
+    const long long ncu = cu_count();
     const long long rounds = (items + ncu - 1) / ncu;
     bool split = sx != nullptr && sx != st && B >= 2 && fuse_tail && n_steps > 0 && items < SINDDM_SPLIT_ITEMS_HI * ncu &&
                  items >= SINDDM_SPLIT_ITEMS_LO * ncu && (rounds * ncu - items) * 25 >= rounds * ncu;
     // (a batch whose 3x3 convs take the binary16 kernels stays whole: its halves could fall below their items-per-CU
     // threshold and run on the fp32 kernels -- the same chain would then round differently with and without a second stream)
-    if (split && conv_wh_applies(p.fp32_convs, B, H, fwd_pitch(p, W), p.dim, p.dim))
+    if (split && conv3x3_route(p, p.blk[2].c2, B, H, fwd_pitch(p, W), true, false) == CONV_WH)       // (the dim -> dim conv)
         split = false;
     // (the two halves carve their own cores behind the shared conditioning table: only if that really fits -- ADVICE r4)
     if (split && cond_region_bytes(p, B) + fwd_workspace_core(p, (B + 1) / 2, H, W) + fwd_workspace_core(p, B - (B + 1) / 2, H, W) > ws_bytes)
@@ -1617,18 +1557,15 @@ int sinddm_prof_end2(double* conv_ms_total, int64_t* conv_launches, double* conv
 }
 
 int sinddm_debug_infer_path(int dim, int B, int H, int W) {
-    NetPlan p = make_plan(dim);
-    if (!p.ok || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
-    const BlockPlan& b = p.blk[2];                      // the dim -> dim block
-    const int Wp = fwd_pitch(p, W);
-    if (b.pk_q2 >= 0 && conv_wh_applies(p.fp32_convs, B, H, Wp, b.cout, b.cout)) return 8;
-    return conv3x3_path(b.cout, b.cout, b.coblks, B, H, Wp);
+    int r[16];
+    const int rc = sinddm_debug_routes(dim, 0, B, H, W, r);
+    return rc ? rc : r[5];                              // conv2 of the dim -> dim block
 }
 
 int sinddm_debug_head_path(int dim, int B, int H, int W) {
     NetPlan p = make_plan(dim);
     if (!p.ok || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
-    return head_applies(nullptr, H, fwd_pitch(p, W)) ? 1 : 0;
+    return head_applies(false, H, fwd_pitch(p, W)) ? 1 : 0;
 }
 
 int sinddm_debug_head_offsets(int dim, int64_t out[3]) {
