@@ -225,7 +225,8 @@ int sinddm_sample_chain_tile(const float* params, const float* packed, float* x,
  *     out    = m[p] * kept + (1 - m[p]) * plain               exact at m == 0 (`plain`) and at m == 1 (`kept`)
  * keep_a / keep_b = sqrt_alphas_cumprod[t-1] / sqrt_one_minus_alphas_cumprod[t-1] for t > 0 and (1, 0) for t == 0.  The keep
  * target is not clamped.  z is drawn when sigma != 0 OR keep_b != 0.  An ROI edit may be on as well: it acts on x_recon,
- * the keep on the output.  RePaint's resampling jumps (stepping back up in t and down again) are NOT part of this. */
+ * the keep on the output.  RePaint's resampling jumps (stepping back up in t and down again) are a separate option of the
+ * run: sinddm_sample_chain_resample (below). */
 typedef struct sinddm_keep_opts {
     const float* mask;   /* device, HW floats, 16-byte aligned        */
     const float* x0;     /* device, 3*HW floats, 16-byte aligned      */
@@ -281,6 +282,67 @@ int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x
  * samples); edit_w / edit_c: both or neither. */
 int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                              const sinddm_step_coefs* coefs /*host*/, const float* edit_w, const float* edit_c /*both or neither, may be NULL*/,
+                             const float* keep_m, const float* keep_x0, float keep_a, float keep_b,
+                             int B, int C, int HW, void* stream);
+
+/* ---- resampling jumps: the other half of RePaint, inside the chain call -------------------------------------------- */
+/* Replacing the known pixels after every step (sinddm_keep_opts) lets the network see them only through the next step's
+ * input.  Resampling steps back UP in t by a few levels and comes down again, several times, so that the generated region is
+ * reshaped with the known one in view.  The upward move is that of SinDDM's blurred forward process, not the textbook
+ * sqrt(alpha) x + sqrt(1 - alpha) z (no reference line; derivation in DESIGN.md 3).  With sa / sb = sqrt_alphas_cumprod /
+ * sqrt_one_minus_alphas_cumprod and gamma the clamped sampling gamma of the scale (0 in mode 0), the marginal at level l is
+ * sa[l] * (gamma[l] * x_tilde + (1 - gamma[l]) * x0) + sb[l] * eps.  The reverse step t = l + 1 writes y at level l (keep
+ * applied when on); a jump from l to l' = l + J then writes, in the same kernel,
+ *     out = r * y + s * z2 + d * (x_tilde - x0h)
+ *     r = sa[l'] / sa[l]     s = sqrt(1 - r^2)     d = sa[l'] * (gamma[l'] - gamma[l])       (host, float64; d = 0 in mode 0)
+ * z2 is a fresh N(0,1) draw, independent of the step's own z.  x0h is the step's estimate of the clean image: x_recon of the
+ * step after the ROI edit, clamped to [-1, 1] when coefs.clip; with keep maps  m[p] * k0[ch][p] + (1 - m[p]) * x_recon.  In
+ * mode 0 the d term is absent and x_tilde is not read.  Exact: if y has the level-l marginal and x0h = x0, `out` has the
+ * level-l' marginal.  A step that is followed by a jump runs unfused (the network writes eps, then ONE elementwise kernel
+ * does step + jump); every other step of the call keeps its launches.  There is no jump after a mode-2 step (t == 0). */
+typedef struct sinddm_jump_coefs {
+    int on;              /* 0: the step is not followed by a jump (r, s, d are ignored) */
+    float r, s, d;
+} sinddm_jump_coefs;
+
+/* In-kernel z2 draws come from the step's key and quad at stream id  stream_id0 + i + SINDDM_JUMP_STREAM: the noise contract
+ * above extends word for word.  Unseeded, z2 of flat element e is element e of sinddm_normal_fill(B*3*H*W, seed,
+ * stream_id0 + i + SINDDM_JUMP_STREAM); with sample_seeds, z2 of element e of sample b is element e of
+ * sinddm_normal_fill(3*H*W, sample_seeds[b], stream_id0 + i + SINDDM_JUMP_STREAM).  The sampler's layout: k = 2^31 + 2 + i. */
+#define SINDDM_JUMP_STREAM 0x80000000ull
+
+/* Options of a resampled run.
+ *   jumps  one entry per step of the call.
+ *   noise  the z2 draws of the call's jumps in order of occurrence, one B*3*H*W slot per jump (the extended size under a
+ *          halo).  Read when opts->noise is set; ignored otherwise. */
+typedef struct sinddm_resample_opts {
+    const sinddm_jump_coefs* jumps;   /* HOST, n_steps entries                      */
+    const float* noise;               /* device, 16-byte aligned, or NULL           */
+} sinddm_resample_opts;
+
+/* sinddm_sample_chain_seeds with resampling jumps.  rs = NULL, rs->jumps = NULL or no entry `on` is sinddm_sample_chain_seeds
+ * itself (that entry is a thin wrapper over this one): the same launches, the same numbers.  t_list holds the EXPANDED walk
+ * (a jump to level l' is followed by the step t = l'); the call does not check that the levels match: r, s, d say what the
+ * jump does.  Halo, keep, edit, seeds and the two-stream split work as before: the jump kernel runs once per half-batch on
+ * that half-batch's stream, and results with / without aux_stream are identical.
+ * SINDDM_E_BADARG (before any device work): a jump on a step with coefs[i].mode == 2, r outside (0, 1], s < 0, d != 0 in mode
+ * 0, rs->noise not 16-byte aligned, opts->noise without rs->noise on a run that has jumps. */
+int sinddm_sample_chain_resample(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                                 const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                                 int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                                 void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                                 const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                                 const sinddm_keep_opts* keep /*host, may be NULL*/,
+                                 const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/,
+                                 const sinddm_resample_opts* rs /*host, may be NULL*/);
+
+/* One reverse step followed by a jump, noise supplied by the caller (`noise` the step's z, `jump_noise` z2, both B*C*HW
+ * floats): the step-by-step route and the cross-check of the chain call; mirrors sinddm_reverse_step_keep.  edit_w / edit_c
+ * and keep_m / keep_x0 are each both-or-neither and may be NULL (keep_a / keep_b are then ignored).  `jump->on` is not read.
+ * SINDDM_E_BADARG: coefs->mode == 2, r outside (0, 1], s < 0, d != 0 in mode 0, a missing pointer. */
+int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_tilde, const float* noise,
+                             const float* jump_noise, float* out, const sinddm_step_coefs* coefs /*host*/,
+                             const sinddm_jump_coefs* jump /*host*/, const float* edit_w, const float* edit_c,
                              const float* keep_m, const float* keep_x0, float keep_a, float keep_b,
                              int B, int C, int HW, void* stream);
 

@@ -19,7 +19,9 @@ cylindrical panoramas (`--tile x --scale_mul 1 4`).  All five modes honour it.
 `inpaint` and `outpaint` (no reference modes) keep some pixels exactly and generate the rest to fit, by replacing the
 known region after every reverse step inside the step kernels: `--mode inpaint --mask_path FILE [--soft_mask]` fills the
 black part of the mask (white = keep the training image's pixel; the file is brought to the finest scale's size);
-`--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.
+`--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.  `--resample R --jump_length J`
+(both modes; defaults 1 1 = no jumps) add RePaint's resampling: at every noise level that is a multiple of J the run jumps
+back up by J levels and comes down again, R times in all, so that the generated region is shaped with the known one in view.
 `--seeds S [S ...]` (one per sample of the batch) or `--seed_base N` (seeds N ... N + batch - 1) give every sample its own
 noise seed (no reference flag: the reference never seeds its generator): the image of a seed is the same at any batch size,
 position in the batch and number of GPUs.  `--vary_from_scale S` keeps the given seeds below scale S and derives fresh
@@ -78,6 +80,9 @@ def build_parser():
     g.add_argument("--seeds", type=int, nargs="+", default=None)
     g.add_argument("--seed_base", type=int, default=None)
     p.add_argument("--vary_from_scale", type=int, default=None)
+    # no reference flags: RePaint's resampling jumps of `inpaint` / `outpaint` (MultiScaleGaussianDiffusion.resample)
+    p.add_argument("--resample", type=int, default=1)
+    p.add_argument("--jump_length", type=int, default=1)
     return p
 
 
@@ -97,6 +102,8 @@ def parse_args(argv=None):
         p.error("--vary_from_scale needs --seeds or --seed_base")
     if args.vary_from_scale is not None and args.vary_from_scale < 0:
         p.error("--vary_from_scale must be >= 0")
+    if args.resample < 1 or args.jump_length < 1:
+        p.error("--resample and --jump_length must be >= 1")
     return args
 
 
@@ -192,10 +199,12 @@ def main():
         h, w = ms_diffusion.image_sizes[n_scales - 1]
         known = np.asarray(Image.open(args.mask_path).convert("L").resize((w, h), Image.NEAREST)) > 127
         trainer.inpaint(torch.from_numpy(known.astype(np.float32)), batch_size=args.sample_batch_size,
-                        hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
+                        hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True,
+                        resample=args.resample, jump_length=args.jump_length, **seed_kw)
     elif args.mode == 'outpaint':
         trainer.outpaint(scale_mul, anchor=tuple(args.anchor), batch_size=args.sample_batch_size,
-                         custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
+                         custom_t_list=sample_t_list, save_unbatched=True, resample=args.resample,
+                         jump_length=args.jump_length, **seed_kw)
     else:
         raise NotImplementedError(
             f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint and outpaint are built for MI355X; "

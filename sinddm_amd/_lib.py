@@ -26,11 +26,13 @@ ABI_SYMBOLS = (
     "sinddm_normal_fill", "sinddm_wrap_halo", "sinddm_upsample_bilinear_wrap", "sinddm_sample_chain_tile",
     "sinddm_sample_chain_keep", "sinddm_reverse_step_keep", "sinddm_normal_fill_samples", "sinddm_sample_chain_seeds",
     "sinddm_debug_head_path", "sinddm_debug_head_offsets", "sinddm_debug_head", "sinddm_debug_routes",
+    "sinddm_sample_chain_resample", "sinddm_reverse_step_jump",
 )
 
 
 ABI_VERSION = 3               # SINDDM_ABI_VERSION of include/sinddm_hip.h this binding was written against
 DIM_FP32_CONVS = 0x10000     # SINDDM_DIM_FP32_CONVS of include/sinddm_hip.h: option bit of every `dim` argument
+JUMP_STREAM = 1 << 31        # SINDDM_JUMP_STREAM of include/sinddm_hip.h: a jump's z2 draw is the step's stream id plus this
 TILE_HALO = 16               # SINDDM_TILE_HALO of include/sinddm_hip.h: the network's receptive radius = halo of a wrapped axis
 
 
@@ -53,6 +55,17 @@ class KeepOpts(C.Structure):
     """Mirror of `sinddm_keep_opts` (include/sinddm_hip.h): `mask` / `x0` device pointers, `ab` a HOST array of
     (keep_a, keep_b) per step of the call."""
     _fields_ = [("mask", C.c_void_p), ("x0", C.c_void_p), ("ab", C.POINTER(C.c_float))]
+
+
+class JumpCoefs(C.Structure):
+    """Mirror of `sinddm_jump_coefs` (include/sinddm_hip.h): the jump that follows a step, or on = 0."""
+    _fields_ = [("on", C.c_int), ("r", C.c_float), ("s", C.c_float), ("d", C.c_float)]
+
+
+class ResampleOpts(C.Structure):
+    """Mirror of `sinddm_resample_opts` (include/sinddm_hip.h): `jumps` a HOST array of one entry per step, `noise` a device
+    pointer (the z2 draws of the call's jumps, one slot per jump) or None."""
+    _fields_ = [("jumps", C.POINTER(JumpCoefs)), ("noise", C.c_void_p)]
 
 
 class SinddmError(RuntimeError):
@@ -101,6 +114,10 @@ def load() -> C.CDLL:
         "sinddm_sample_chain_tile": (i, chain + [C.POINTER(ChainOpts), i, i]),
         "sinddm_sample_chain_keep": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts)]),
         "sinddm_sample_chain_seeds": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p]),
+        "sinddm_sample_chain_resample": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
+                                                     C.POINTER(ResampleOpts)]),
+        "sinddm_reverse_step_jump": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(JumpCoefs), p, p, p, p, f, f, i, i, i,
+                                         p]),
         "sinddm_normal_fill_samples": (i, [p, i, i64, p, C.c_uint64, p]),
         "sinddm_reverse_step_keep": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, p, p, f, f, i, i, i, p]),
         "sinddm_wrap_halo": (i, [p, p, i, i, i, i, i, p]),

@@ -1276,6 +1276,26 @@ int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* see
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
+// a jump description the kernels can take: r in (0, 1], s >= 0, d only where x-tilde exists; never after a mode-2 step
+static bool jump_valid(const sinddm_jump_coefs& j, const sinddm_step_coefs& k) {
+    return k.mode != 2 && j.r > 0.0f && j.r <= 1.0f && j.s >= 0.0f && (k.mode != 0 || j.d == 0.0f);
+}
+
+// reverse step + jump (reverse_step_jump_kernel) over `Bn` samples of chw elements: one row per sample with per-sample
+// seeds, else one row of the whole launch; t.b0 / t.sseeds / t.nz / jp.nz as the kernel documents them
+static int jump_launch(const float* x_t, const float* eps, const float* x_tilde, float* out, const TailArgs& t, const JumpArgs& jp,
+                       int Bn, int chw, int hw, hipStream_t st) {
+    const long long span = t.sseeds ? chw : (long long)Bn * chw;
+    long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
+    if (gx > 8192) gx = 8192;
+    tail_dispatch(t, [&](auto E, auto N, auto K) {
+        hipLaunchKernelGGL((reverse_step_jump_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                           dim3((unsigned)gx, t.sseeds ? (unsigned)Bn : 1u), dim3(256), 0, st, x_t, eps, x_tilde, out, t, jp, span,
+                           chw, hw);
+    });
+    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+}
+
 // The body of every sinddm_sample_chain* entry point: each passes 0 / NULL for the options its signature does not have
 // (sinddm_sample_chain_seeds has them all).  Hc x Wc is the CENTRE size; the
 // steps run on the extended shape H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo,
@@ -1285,7 +1305,7 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                              uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                             const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
+                             const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs) {
     if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
     if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
     if ((reinterpret_cast<uintptr_t>(sample_seeds) & 7) != 0) return SINDDM_E_BADARG;
@@ -1309,6 +1329,16 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     if (((reinterpret_cast<uintptr_t>(edit_w) | reinterpret_cast<uintptr_t>(edit_c) | reinterpret_cast<uintptr_t>(noise) |
           reinterpret_cast<uintptr_t>(keep_m) | reinterpret_cast<uintptr_t>(keep_x0)) & 15) != 0)
         return SINDDM_E_BADARG;
+    // resampling jumps: a step with jumps[i].on runs unfused and ends in reverse_step_jump_kernel; none on: `jumps` stays NULL
+    // and nothing below differs from the call without `rs`
+    const sinddm_jump_coefs* jumps = nullptr;
+    for (int i = 0; rs && rs->jumps && i < n_steps; ++i) {
+        if (!rs->jumps[i].on) continue;
+        if (!jump_valid(rs->jumps[i], coefs[i])) return SINDDM_E_BADARG;
+        jumps = rs->jumps;
+    }
+    const float* jump_noise = jumps ? rs->noise : nullptr;   // one slot per jump, in order of occurrence
+    if ((reinterpret_cast<uintptr_t>(jump_noise) & 15) != 0 || (jumps && noise && !jump_noise)) return SINDDM_E_BADARG;
     NetPlan p = make_plan(dim);
     if (!p.ok) return SINDDM_E_BADSHAPE;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1353,6 +1383,7 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     float* cur = x;
     float* nxt = x_alt;
     int rc = 0;
+    int n_jumped = 0;                                          // jumps so far: the slot of rs->noise
     if (tiled) rc = wrap_halo_launch(x, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st);     // (ordered before both halves: ev_go)
     for (int i0 = 0; i0 < n_steps && rc == 0;) {
         // a run: up to CHAIN_COND_ROWS steps whose t is an arithmetic progression (the sampler's always is)
@@ -1380,16 +1411,25 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
             t.ew = edit_w; t.ec = edit_c; t.nz = noise ? noise + (size_t)i * (size_t)n : nullptr;
             t.km = keep_m; t.kx = keep_x0;
             t.ka = keep_m ? keep_ab[2 * i] : 1.0f; t.kb = keep_m ? keep_ab[2 * i + 1] : 0.0f;
+            const bool jump = jumps && jumps[i].on;            // the step writes eps; step + jump are one kernel behind it
+            JumpArgs jp{};
+            if (jump) {
+                jp.r = jumps[i].r; jp.s = jumps[i].s; jp.d = jumps[i].d;
+                if (noise) jp.nz = jump_noise + (size_t)n_jumped * (size_t)n;
+                ++n_jumped;
+            }
             for (int h = 0; h < (split ? 2 : 1) && rc == 0; ++h) {
                 const size_t o = h ? hoff : 0;
                 ChainStep cs{};
                 cs.cond_row = cond_tab + (size_t)(i - i0) * p.cond_stride;
-                cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail ? nxt + o : nullptr;
+                cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail && !jump ? nxt + o : nullptr;
                 cs.tail = t;
                 cs.tail.b0 = h ? Bh[0] : 0;
                 if (sseeds) cs.tail.sseeds = sseeds + cs.tail.b0;
                 rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
                                       h ? sx : st, nullptr, &cs);
+                if (jump && fuse_tail && rc == 0)
+                    rc = jump_launch(cur + o, eps + o, cs.x_tilde, nxt + o, cs.tail, jp, Bh[h], CHANNELS * H * W, H * W, h ? sx : st);
                 if (tiled && fuse_tail && rc == 0)
                     rc = wrap_halo_launch(nxt + o, nullptr, Bh[h] * CHANNELS, Hc, Wc, halo_y, halo_x, h ? sx : st);
             }
@@ -1400,12 +1440,16 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                 const long long span = sseeds ? chw : n;
                 long long gx = ((span + 3) / 4 + 255) / 256;
                 if (gx > 8192) gx = 8192;
-                tail_dispatch(t, [&](auto E, auto N, auto K) {
-                    hipLaunchKernelGGL((reverse_step_rows_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                                       dim3((unsigned)gx, sseeds ? (unsigned)B : 1u), dim3(256), 0, st, cur, eps, x_tilde, nxt, t,
-                                       span, chw, H * W);
-                });
-                if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
+                if (jump) {
+                    if ((rc = jump_launch(cur, eps, x_tilde, nxt, t, jp, B, chw, H * W, st)) != 0) break;
+                } else {
+                    tail_dispatch(t, [&](auto E, auto N, auto K) {
+                        hipLaunchKernelGGL((reverse_step_rows_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                                           dim3((unsigned)gx, sseeds ? (unsigned)B : 1u), dim3(256), 0, st, cur, eps, x_tilde, nxt, t,
+                                           span, chw, H * W);
+                    });
+                    if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
+                }
                 if (tiled && (rc = wrap_halo_launch(nxt, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st)) != 0) break;
             }
             float* t_ = cur; cur = nxt; nxt = t_;
@@ -1434,7 +1478,7 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
                            uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                            void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1442,7 +1486,7 @@ int sinddm_sample_chain_tile(const float* params, const float* packed, float* x,
                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_keep(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1451,7 +1495,7 @@ int sinddm_sample_chain_keep(const float* params, const float* packed, float* x,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1460,7 +1504,16 @@ int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x
                               void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                               const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, nullptr);
+}
+
+int sinddm_sample_chain_resample(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                                 const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                                 uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                                 void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
+                                 const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs) {
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs);
 }
 
 int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1468,7 +1521,7 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
                          uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                          void* aux_stream, int* result_in_alt) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1476,7 +1529,7 @@ int sinddm_sample_chain(const float* params, const float* packed, float* x, floa
                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                         int* result_in_alt) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr);
+                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr);
 }
 
 int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
@@ -1502,6 +1555,23 @@ int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_
     t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
     t.km = keep_m; t.kx = keep_x0; t.ka = keep_a; t.kb = keep_b;
     return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)B * C * HW, C * HW, HW, stream);
+}
+
+int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_tilde, const float* noise, const float* jump_noise,
+                             float* out, const sinddm_step_coefs* coefs, const sinddm_jump_coefs* jump, const float* edit_w,
+                             const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B, int C,
+                             int HW, void* stream) {
+    if (!x_t || !eps || !noise || !jump_noise || !out || !coefs || !jump || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
+    if ((edit_w == nullptr) != (edit_c == nullptr) || (keep_m == nullptr) != (keep_x0 == nullptr)) return SINDDM_E_BADARG;
+    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
+    if (!jump_valid(*jump, *coefs)) return SINDDM_E_BADARG;
+    if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
+    TailArgs t{};
+    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
+    t.km = keep_m; t.kx = keep_x0; t.ka = keep_m ? keep_a : 1.0f; t.kb = keep_m ? keep_b : 0.0f;
+    JumpArgs jp{};
+    jp.r = jump->r; jp.s = jump->s; jp.d = jump->d; jp.nz = jump_noise;
+    return jump_launch(x_t, eps, x_tilde, out, t, jp, B, C * HW, HW, static_cast<hipStream_t>(stream));
 }
 
 #ifdef W2_PHASE

@@ -224,6 +224,105 @@ __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __r
     }
 }
 
+// ---- reverse step + RESAMPLING JUMP in one pass (RePaint's upward move on SinDDM's blurred forward process; no reference
+// line; derivation in DESIGN.md 3).  The step t = l + 1 writes y at level l; the jump takes it back up to level l' = l + J:
+//     out = r * y + s * z2 + d * (x-tilde - x0h)
+// with r = sa[l'] / sa[l], s = sqrt(1 - r^2), d = sa[l'] * (gamma[l'] - gamma[l]) (host, float64; d = 0 in mode 0, where
+// x-tilde is not read), z2 a second N(0,1) draw and x0h the step's own estimate of the clean image (step_x0 below; under
+// KEEP  m * k0 + (1 - m) * x0h).  If y has the level-l marginal and x0h is the clean image, `out` has the level-l' marginal.
+struct JumpArgs {
+    float r, s, d;                      // sinddm_jump_coefs
+    const float* nz;                    // NOISE  the jump's recorded z2 draws for the WHOLE batch (B_total*3*HW floats)
+};
+
+// the clean-image estimate of a step, `xp` of reverse_step_mean (x0 itself in mode 0): after the ROI edit, clamped when
+// k.clip as mode 2 clamps it.  A helper of its own: the tails keep reverse_step_mean's contraction pattern and its numbers.
+__device__ __forceinline__ float step_x0(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c, bool edit) {
+    const float x0 = k.sqrt_recip_ac_t * x - k.sqrt_recipm1_ac_t * e;
+    float xp = k.mode == 0 ? x0 : (x0 - k.gamma_t * xb) / (1.0f - k.gamma_t);
+    if (edit) xp = w * xp + c;
+    return k.clip ? fminf(fmaxf(xp, -1.0f), 1.0f) : xp;
+}
+
+// step + jump of one element: the step's value is tail_eval's, as in every tail
+template <bool EDIT, bool KEEP>
+__device__ __forceinline__ float jump_eval(const TailArgs& a, const JumpArgs& jp, float x, float e, float xb, float z, float z2,
+                                           float w, float c, float m, float k0) {
+    const float y = tail_eval<EDIT, KEEP>(a, x, e, xb, z, w, c, m, k0);
+    float o = jp.r * y + jp.s * z2;
+    if (a.k.mode != 0) {
+        const float xp = step_x0(a.k, x, e, xb, w, c, EDIT);
+        const float x0h = KEEP ? m * k0 + (1.0f - m) * xp : xp;
+        o += jp.d * (xb - x0h);
+    }
+    return o;
+}
+
+// lanes [jlo, jhi) of the quad at p: one 16-byte access when the quad is full and p is 16-byte aligned, else lane by lane
+__device__ __forceinline__ void quad_load(const float* __restrict__ p, int jlo, int jhi, float (&v)[4]) {
+    if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j >= jlo && j < jhi) v[j] = p[j];
+    }
+}
+
+// Over ROWS, like reverse_step_rows_kernel: row blockIdx.y is `span` elements from row * span of the launch's tensors.  With
+// per-sample seeds a row is a sample (span = chw, key = sseeds[row], quads counted from the sample's start); otherwise the
+// launch is one row of a.seed's stream that starts at element b0 * chw of the WHOLE batch -- a half-batch of a two-stream
+// run, whose start is inside a quad of the stream when b0 * chw % 4 != 0.  So a thread owns a quad OF THE KEY'S STREAM
+// and lanes [jlo, jhi) of it lie inside the row: the first and the last quad of a row may be partial.  Two draws per
+// element: z from stream a.step (the step's own, as in every tail), z2 from a.step + SINDDM_JUMP_STREAM, same key, same
+// quad.  NOISE reads both at the element's flat index inside the whole batch (a.nz, jp.nz) instead.
+template <bool EDIT, bool NOISE, bool KEEP>
+__global__ __launch_bounds__(256) void reverse_step_jump_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
+                                                                const float* __restrict__ xtil, float* __restrict__ out,
+                                                                TailArgs a, JumpArgs jp, long long span, int chw, int hw) {
+    const long long base = (long long)blockIdx.y * span;
+    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
+    const long long gofs = (long long)a.b0 * chw;           // the launch's first element inside the whole batch
+    const long long kofs = a.sseeds ? 0 : gofs;             // the row's first element inside the key's stream
+    const bool draw = tail_draws<KEEP>(a), draw2 = jp.s != 0.0f;
+    const long long q1 = (kofs + span + 3) >> 2;
+    for (long long q = (kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x; q < q1; q += (long long)gridDim.x * 256) {
+        const long long e0 = (q << 2) - kofs;               // lane 0's index inside the row: -3 .. span - 1
+        const int jlo = e0 < 0 ? (int)-e0 : 0;
+        const int jhi = span - e0 < 4 ? (int)(span - e0) : 4;
+        const long long i0 = base + e0;                     // ... inside the launch's tensors (lanes below jlo are not touched)
+        float z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f};
+        if (NOISE) {
+            if (draw) quad_load(a.nz + gofs + i0, jlo, jhi, z);
+            if (draw2) quad_load(jp.nz + gofs + i0, jlo, jhi, z2);
+        } else {
+            if (draw) philox_normal4(key, a.step, (unsigned long long)q, z);
+            if (draw2) philox_normal4(key, a.step + SINDDM_JUMP_STREAM, (unsigned long long)q, z2);
+        }
+        // (the maps have period chw: lanes below jlo read the wrapped index, a valid one, and are not used)
+        const int r0 = (int)(((i0 % chw) + chw) % chw);
+        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
+        if (EDIT) quad_maps(a.ew, a.ec, r0, jhi, chw, hw, w, c);
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
+        if (KEEP) quad_maps(a.km, a.kx, r0, jhi, chw, hw, m, k0);
+        float x[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f};
+        quad_load(xt + i0, jlo, jhi, x);
+        quad_load(eps + i0, jlo, jhi, e);
+        if (a.k.mode != 0) quad_load(xtil + i0, jlo, jhi, xb);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = jump_eval<EDIT, KEEP>(a, jp, x[j], e[j], xb[j], z[j], z2[j], w[j], c[j], m[j], k0[j]);
+        if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(out + i0) & 15) == 0) {
+            *reinterpret_cast<f32x4*>(out + i0) = o;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j >= jlo && j < jhi) out[i0 + j] = o[j];
+        }
+    }
+}
+
 // ---- eps stage + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
 // four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
 // path): eps never goes to memory.  EPS (head.h) fills the thread's e[3]: HeadEps, the collapsed head on block 4's g and

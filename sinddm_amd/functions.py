@@ -178,6 +178,39 @@ def outpaint_offset(canvas, image, anchor=(0.5, 0.5)) -> Tuple[int, int]:
     return int(float(anchor[0]) * (int(canvas[0]) - int(image[0]))), int(float(anchor[1]) * (int(canvas[1]) - int(image[1])))
 
 
+def resample_schedule(t_seq: Sequence[int], resample: int = 1, jump: int = 1):
+    """The walk of a resampled run (RePaint's resampling on this sampler's level convention), its ONE owner.  `t_seq` is the
+    descending run of reverse steps `_run_steps` gets (step t takes a state at noise level t and writes one at level t - 1);
+    L = t_seq[0] is its input level.  Walk down; after a step that reaches level l a jump back up to l + J follows when
+    l >= 0, l % J == 0, l + J <= L and that anchor has been jumped from fewer than R - 1 times; the walk goes on with step
+    t = l + J.  Anchors do not nest (the levels l + J - 1 .. l + 1 are no multiples of J), so the number of steps is
+    len(t_seq) + (R - 1) * J * |anchors|.  t_seq = 9..0, J = 3, R = 2:  9 8 7 ^9 9 8 7 6 5 4 ^6 6 5 4 3 2 1 ^3 3 2 1 0.
+    Returns (steps, jump_to): the expanded step list and, per step, the level to jump to afterwards or None.  R = 1 returns
+    t_seq with no jumps."""
+    steps = [int(t) for t in t_seq]
+    R, J = int(resample), int(jump)
+    if R < 1 or J < 1:
+        raise ValueError(f"resample_schedule: resample {resample} / jump {jump} must be >= 1")
+    if R == 1 or not steps:
+        return steps, [None] * len(steps)
+    if steps[-1] < 0 or any(a - b != 1 for a, b in zip(steps, steps[1:])):
+        raise ValueError("resample_schedule: t_seq must descend in steps of 1 and stay >= 0")
+    L, t_min = steps[0], steps[-1]
+    out, jump_to, used = [], [], {}
+    t = L
+    while t >= t_min:
+        lvl = t - 1
+        out.append(t)
+        if lvl >= 0 and lvl % J == 0 and lvl + J <= L and used.get(lvl, 0) < R - 1:
+            used[lvl] = used.get(lvl, 0) + 1
+            jump_to.append(lvl + J)
+            t = lvl + J
+        else:
+            jump_to.append(None)
+            t = lvl
+    return out, jump_to
+
+
 def _disk(radius: int) -> np.ndarray:
     """skimage.morphology.disk: (2r+1)^2 footprint of the pixels within Euclidean distance r."""
     yy, xx = np.mgrid[-radius:radius + 1, -radius:radius + 1]

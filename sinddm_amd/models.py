@@ -94,19 +94,21 @@ CHAIN_NOISE_BYTES = 1 << 30
 
 # ---- per-sample noise seeds (include/sinddm_hip.h "the noise contract") -------------------------------------
 SEED_LIMIT = 1 << 63          # a sample seed is a Python int in [0, 2^63): 8 bytes on the device
-_STREAM_KINDS = {"init": 0, "renoise": 1, "step": 2}
+_STREAM_KINDS = {"init": 0, "renoise": 1, "step": 2, "jump": _lib.JUMP_STREAM + 2}
 
 
 def noise_stream_id(s: int, kind: str, i: int = 0) -> int:
     """Stream id of one draw of a seeded sample: (s << 32) | k with k = 0 the initial draw of p_sample_loop at scale s,
     k = 1 the re-noise draw of p_sample_via_scale_loop, k = 2 + i the reverse step at position i of the scale's run (counted
-    from the run's first step).  The ONE owner of this layout: the fused route hands noise_stream_id(s, "step", 0) to the
-    library as stream_id0, the step-by-step route asks for every position."""
+    from the run's first step), k = 2^31 + 2 + i the second draw (z2) of the resampling jump that follows the step at position
+    i of the EXPANDED walk (i < 2^31 - 2, which a run with jumps also keeps its steps below: the library adds
+    SINDDM_JUMP_STREAM to the step's id).  The ONE owner of this layout: the fused route hands noise_stream_id(s, "step", 0)
+    to the library as stream_id0, the step-by-step route asks for every position."""
     k = _STREAM_KINDS[kind]
     s, i = int(s), int(i)
-    if kind != "step" and i != 0:
+    if kind not in ("step", "jump") and i != 0:
         raise ValueError(f"the {kind!r} draw of a scale has no position")
-    if not (0 <= s < (1 << 31)) or not (0 <= i < (1 << 32) - 2):
+    if not (0 <= s < (1 << 31)) or not (0 <= i < ((1 << 31) if kind == "jump" else (1 << 32)) - 2):
         raise ValueError(f"noise_stream_id: scale {s} / position {i} out of range")
     return (s << 32) | (k + i)
 
@@ -515,6 +517,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # (seed of b, noise_stream_id, element index inside the sample) alone: the sample does not depend on its batch, its
         # position in it, the two-stream split or the rank that runs it.  Not together with `noise_fn`.
         self.sample_seeds = None
+        # RePaint's resampling for known-region sampling: None or (R, J), both >= 1.  At anchor levels (multiples of J) the run
+        # jumps back up by J levels and comes down again, until the stretch has been walked R times (the schedule:
+        # functions.resample_schedule; the upward move: sinddm_sample_chain_resample).  R = 1 is None.  A sampling option,
+        # like `keep_maps` (which it is meant for, and does not require); not available with CLIP guidance.
+        self.resample = None
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -562,12 +569,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
         return z
 
     def _draw(self, kind: str, shape, s: int, t: int, device, pos: int = 0) -> torch.Tensor:
-        """One N(0,1) draw of the sampler: `kind` 'init' / 'renoise' / 'step' (`pos` = the step's position in its run)."""
+        """One N(0,1) draw of the sampler: `kind` 'init' / 'renoise' / 'step' / 'jump' (`pos` = the step's position in its
+        run; 'jump' is the second draw of the jump that follows that step)."""
         seeds = self._seeds_for(s, shape[0])
         if seeds is not None:
             sid = noise_stream_id(s, kind, pos)
             hy, hx = self._tile_halo()
-            if kind == "step" and (hy or hx):
+            if kind in ("step", "jump") and (hy or hx):
                 # the tiled chain draws over the EXTENDED sample and discards the halo's draws: take the centre
                 H, W = int(shape[-2]), int(shape[-1])
                 z = self._seeded_normal(seeds, tuple(shape[:-2]) + (H + 2 * hy, W + 2 * hx), sid, device)
@@ -776,6 +784,43 @@ class MultiScaleGaussianDiffusion(nn.Module):
             self._keep_ab_cache = cache
         return cache[1]
 
+    def _jump_levels(self, s: int):
+        """float64 (sa, sb, gamma) per noise level of scale s, as the jumps see the process: sa / sb = sqrt(ac) / sqrt(1 - ac)
+        of the host copy of `alphas_cumprod` (so that sa^2 + sb^2 = 1 to float64 rounding), gamma the clamped sampling gamma
+        (the row `gamma_t` / `gamma_tm1` of `step_coefs` come from; zeros in mode 0)."""
+        h = self._host()
+        ac = h['alphas_cumprod'].astype(np.float64)
+        if (not self.reblurring) or int(s) == 0:
+            g = np.zeros_like(ac)
+        else:
+            g = h['gammas_clamped'][int(s) - 1].astype(np.float64)
+        return np.sqrt(ac), np.sqrt(1.0 - ac), g
+
+    def _jump_table(self, s: int):
+        """jt(l, l2) -> (r, s, d) in float64 of the jump from level l up to level l2 >= l at scale s (sinddm_jump_coefs):
+        r = sa[l2] / sa[l], s = sqrt(1 - r^2), d = sa[l2] * (gamma[l2] - gamma[l])."""
+        sa, _, g = self._jump_levels(s)
+
+        def jt(l: int, l2: int):
+            l, l2 = int(l), int(l2)
+            if not 0 <= l <= l2 < self.num_timesteps:
+                raise ValueError(f"jump {l} -> {l2} outside the schedule's levels")
+            r = float(sa[l2] / sa[l])
+            return r, float(np.sqrt(max(0.0, 1.0 - r * r))), float(sa[l2] * (g[l2] - g[l]))
+        return jt
+
+    def _resample_cfg(self):
+        """(R, J) of `resample` (validated) when it asks for jumps, else None."""
+        if self.resample is None:
+            return None
+        R, J = (int(v) for v in self.resample)
+        if R < 1 or J < 1:
+            raise ValueError(f"resample = {self.resample!r}: R and J must be >= 1")
+        if self.clip_guided_sampling:
+            raise NotImplementedError("resample with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has "
+                                      "no resampling jump")
+        return (R, J) if R > 1 else None
+
     def _keep_entry(self, s: int, img: torch.Tensor):
         """The (mask, x0) pair of `keep_maps` for scale s, checked against the running sample (the library takes raw
         pointers: a mismatching map would be read out of bounds), or None."""
@@ -831,9 +876,19 @@ class MultiScaleGaussianDiffusion(nn.Module):
         the step-by-step route replaces through sinddm_reverse_step_keep.
         With `sample_seeds` set the call is sinddm_sample_chain_seeds: sample b's step at position i of the run draws
         sinddm_normal_fill(3 H W, seed_b, noise_stream_id(s, 'step', i)) inside the step kernel, and no seed is taken from
-        torch's generator; the step-by-step route fills the same numbers through sinddm_normal_fill_samples."""
+        torch's generator; the step-by-step route fills the same numbers through sinddm_normal_fill_samples.
+        With `resample` = (R, J), R > 1, `t_seq` is expanded by functions.resample_schedule and the run is ONE
+        sinddm_sample_chain_resample call on every route above (in-kernel noise, `chain_noise` buffers with a 'jump' draw per
+        jump, seeds, tiled): a step that is followed by a jump ends in the step + jump kernel instead of its fused tail.  The
+        step-by-step route goes through sinddm_reverse_step_jump.  `draw_log` gets ("chain_resample", s, seed or seeds,
+        expanded t list, jump targets)."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
+        rs_cfg = self._resample_cfg()
+        jump_to = None                                         # per step of the EXPANDED walk: the level to jump to, or None
+        if rs_cfg is not None:
+            from .functions import resample_schedule
+            t_seq, jump_to = resample_schedule(t_seq, *rs_cfg)
         sseeds = self._seeds_for(s, img.shape[0])
         keep = self._keep_entry(s, img)
         roi = bool(self.roi_guided_sampling and s < self.n_scales - 1)     # models.py:430-431
@@ -843,7 +898,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 and img.shape[1] == self.channels == 3)
         if not fast:
             for pos, i in enumerate(t_seq):
-                img = self._p_sample_host_t(img, i, s, step_pos=pos)
+                img = self._p_sample_host_t(img, i, s, step_pos=pos, jump_to=jump_to[pos] if jump_to else None)
                 self._dump_interm(img, s, f'output_t-{i:03}_s-{s}.png')
             return img
         lib = _lib.load()
@@ -884,10 +939,16 @@ class MultiScaleGaussianDiffusion(nn.Module):
             ab = (C.c_float * (2 * n))(*[float(v) for t in t_seq for v in ab_tab[t]])
             kopts = _lib.KeepOpts()
             kopts.mask, kopts.x0 = _lib.ptr(km), _lib.ptr(kx)
+        ropts = None
+        if jump_to is not None:
+            jt = self._jump_table(s)
+            jumps = (_lib.JumpCoefs * n)(*[_lib.JumpCoefs(0, 0.0, 0.0, 0.0) if l2 is None else _lib.JumpCoefs(1, *jt(t - 1, l2))
+                                           for t, l2 in zip(t_seq, jump_to)])
+            ropts = _lib.ResampleOpts()
         aux = _aux_stream(x.device) if self.two_streams else None
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
 
-        def chain(i0, k, seed, noise, sid0=0, seeds_dev=None):
+        def chain(i0, k, seed, noise, sid0=0, seeds_dev=None, jump_noise=None):
             nonlocal x, x_alt
             opts.noise = _lib.ptr(noise)
             in_alt = C.c_int(0)
@@ -897,7 +958,12 @@ class MultiScaleGaussianDiffusion(nn.Module):
                     B, Hc, Wc, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts))
             if kopts is not None:
                 kopts.ab = C.cast(C.addressof(ab) + 2 * i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
-            if seeds_dev is not None:
+            if ropts is not None:
+                ropts.jumps = C.cast(C.addressof(jumps) + i0 * C.sizeof(_lib.JumpCoefs), C.POINTER(_lib.JumpCoefs))
+                ropts.noise = _lib.ptr(jump_noise)
+                _lib.check(lib.sinddm_sample_chain_resample(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
+                                                            _lib.ptr(seeds_dev), C.byref(ropts)), "sinddm_sample_chain_resample")
+            elif seeds_dev is not None:
                 _lib.check(lib.sinddm_sample_chain_seeds(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
                                                          _lib.ptr(seeds_dev)), "sinddm_sample_chain_seeds")
             elif kopts is not None:
@@ -919,15 +985,24 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 # (tiled: the draws have the sample's own size and fill the centre of their slot; the halo of a slot is
                 # never used -- the halo of a step's output is overwritten with its wrapped centre)
                 noise = (torch.zeros if tiled else torch.empty)((k,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+                jn = None                                      # the piece's jumps, one slot each in order of occurrence
+                if jump_to is not None:
+                    nj = max(1, sum(1 for l2 in jump_to[i0:i0 + k] if l2 is not None))
+                    jn = (torch.zeros if tiled else torch.empty)((nj,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+                nj = 0
                 for j in range(k):
                     noise[j][:, :, hy:hy + Hc, hx:hx + Wc].copy_(self._draw("step", img.shape, s, t_seq[i0 + j], x.device))
-                chain(i0, k, 0, noise)
+                    if jump_to is not None and jump_to[i0 + j] is not None:
+                        jn[nj][:, :, hy:hy + Hc, hx:hx + Wc].copy_(self._draw("jump", img.shape, s, t_seq[i0 + j], x.device))
+                        nj += 1
+                chain(i0, k, 0, noise, jump_noise=jn)
             return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
         if sseeds is not None:
             if self.draw_log is not None:
                 # (draw i of sample b is sinddm_normal_fill(3 H W, seeds[b], noise_stream_id(s, 'step', i)), over the
                 # extended size when tiled)
-                self.draw_log.append(("chain_seeds", s, list(sseeds), list(t_seq)))
+                self.draw_log.append(("chain_resample", s, list(sseeds), list(t_seq), list(jump_to)) if jump_to is not None
+                                     else ("chain_seeds", s, list(sseeds), list(t_seq)))
             chain(0, n, 0, None, noise_stream_id(s, "step", 0), torch.tensor(sseeds, dtype=torch.int64, device=x.device))
             return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
         # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
@@ -935,7 +1010,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
         if self.draw_log is not None:
             # (tiled: draw i of the run is sinddm_normal_fill(seed, i) over the EXTENDED (B,3,H+2hy,W+2hx) tensor)
-            self.draw_log.append(("chain_tile", s, seed, list(t_seq), (hy, hx)) if tiled else ("chain", s, seed, list(t_seq)))
+            if jump_to is not None:
+                # (the jump after step i draws sinddm_normal_fill(seed, i + 2^31) on top, over the same tensor)
+                self.draw_log.append(("chain_resample", s, seed, list(t_seq), list(jump_to)))
+            else:
+                self.draw_log.append(("chain_tile", s, seed, list(t_seq), (hy, hx)) if tiled else ("chain", s, seed, list(t_seq)))
         chain(0, n, seed, None)
         return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
 
@@ -956,10 +1035,14 @@ class MultiScaleGaussianDiffusion(nn.Module):
         return self.denoise_fn(x, t_dev, scale=s)                           # plug point, models.py:356
 
     def _p_sample_host_t(self, x: torch.Tensor, t: int, s: int, clip_denoised: bool = True,
-                         repeat_noise: bool = False, step_pos: int = 0) -> torch.Tensor:
+                         repeat_noise: bool = False, step_pos: int = 0, jump_to: Optional[int] = None) -> torch.Tensor:
         """One reverse step with the timestep known on the host: net forward + ONE fused kernel.  `step_pos`: the step's
-        position in its run -- with `sample_seeds` it selects the draw (noise_stream_id(s, 'step', step_pos))."""
+        position in its run -- with `sample_seeds` it selects the draw (noise_stream_id(s, 'step', step_pos)).  `jump_to`:
+        the level a resampling jump takes the step's output back up to (sinddm_reverse_step_jump: step + jump in one kernel,
+        a second draw of kind 'jump'), or None."""
         keep = self._keep_entry(s, x)                                       # (raises under CLIP guidance)
+        if jump_to is not None and self.clip_guided_sampling:
+            raise NotImplementedError("a resampling jump on a CLIP-guided step")
         if self.clip_guided_sampling:
             if self.clip_model is None or self.guidance_sub_iters is None or self.stop_guidance is None:
                 raise RuntimeError("clip_guided_sampling is set but clip_model / guidance_sub_iters / stop_guidance are not: "
@@ -984,6 +1067,20 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
             xt = xt.contiguous()
         out = torch.empty_like(x)
+        if jump_to is not None:
+            B_, C_, H_, W_ = x.shape
+            z2 = self._draw("jump", x.shape, s, t, x.device, step_pos)
+            ew = ec = None
+            if self.roi_guided_sampling and s < self.n_scales - 1:
+                ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
+            ka, kb = (float(v) for v in self._keep_ab_table()[int(t)]) if keep is not None else (1.0, 0.0)
+            jc = _lib.JumpCoefs(1, *self._jump_table(s)(int(t) - 1, int(jump_to)))
+            _lib.check(lib.sinddm_reverse_step_jump(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(z2),
+                                                    _lib.ptr(out), C.byref(k), C.byref(jc), _lib.ptr(ew), _lib.ptr(ec),
+                                                    _lib.ptr(keep[0]) if keep is not None else None,
+                                                    _lib.ptr(keep[1]) if keep is not None else None, ka, kb, B_, C_, H_ * W_,
+                                                    _lib.stream_ptr(x.device)), "sinddm_reverse_step_jump")
+            return out
         if keep is not None:
             B_, C_, H_, W_ = x.shape
             ew = ec = None

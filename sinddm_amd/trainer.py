@@ -471,24 +471,33 @@ class MultiscaleTrainer(object):
             em.roi_guided_sampling = False
 
     # ---- known-region sampling: some pixels are given, the rest is generated to fit (no reference counterpart) ----
-    def _sample_kept(self, keep_maps, tag, **kw):
+    def _sample_kept(self, keep_maps, tag, resample=1, jump_length=1, **kw):
         em = self.ema_model
+        R, J = int(resample), int(jump_length)
+        if R < 1 or J < 1:
+            raise ValueError(f'{tag}: resample {resample} / jump_length {jump_length} must be >= 1')
         em.keep_maps = keep_maps
+        em.resample = (R, J) if R > 1 else None
         try:
             return self.sample_scales(custom_sample=False, image_name='', start_noise=True,
                                       desc=f'{tag}_{str(datetime.datetime.now()).replace(":", "_")}', **kw)
         finally:
             em.keep_maps = None
+            em.resample = None
 
     @torch.no_grad()
     def inpaint(self, mask, batch_size=16, hard=True, custom_t_list=None, save_unbatched=False, save_images=True,
-                seeds=None, vary_from_scale=None):
+                seeds=None, vary_from_scale=None, resample=1, jump_length=1):
         """Fill a hole in the training image: `mask` is (H, W) at the finest scale's size, 1 = keep the training image's
         pixel, 0 = generate.  At every scale the known image is that scale's training image and the mask comes from
         `functions.keep_mask_pyramid` (`hard`: a coarse pixel is kept only if its whole footprint is known); after every
         reverse step the known pixels are overwritten with the forward-diffused training image of that noise level, inside
-        the step kernels (`ema_model.keep_maps` -> sinddm_sample_chain_keep: one library call per scale).  RePaint's
-        resampling jumps are not built.  Returns the per-scale batches and writes PNGs like `sample_scales`."""
+        the step kernels (`ema_model.keep_maps` -> sinddm_sample_chain_keep: one library call per scale).  `resample` = R > 1
+        adds RePaint's resampling: at every level that is a multiple of `jump_length` = J the run jumps back up by J levels
+        and comes down again, until the stretch has been walked R times (`ema_model.resample` -> functions.resample_schedule
+        and sinddm_sample_chain_resample: still one library call per scale, R times the network evaluations on the
+        resampled stretches).  The defaults (1, 1) are the run without jumps, bit for bit.  No image-quality claim is made.
+        Returns the per-scale batches and writes PNGs like `sample_scales`."""
         from .functions import keep_mask_pyramid
         em = self.ema_model
         m = torch.as_tensor(mask)
@@ -497,16 +506,17 @@ class MultiscaleTrainer(object):
         masks = keep_mask_pyramid(m, [em.image_sizes[s] for s in range(self.n_scales)], hard=hard)
         maps = {s: (masks[s].to(self.device).contiguous(), self.data_list[s][0][0].contiguous())
                 for s in range(self.n_scales)}
-        return self._sample_kept(maps, 'inpaint', batch_size=batch_size, custom_t_list=custom_t_list,
-                                 save_unbatched=save_unbatched, save_images=save_images, seeds=seeds,
-                                 vary_from_scale=vary_from_scale)
+        return self._sample_kept(maps, 'inpaint', resample=resample, jump_length=jump_length, batch_size=batch_size,
+                                 custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
+                                 seeds=seeds, vary_from_scale=vary_from_scale)
 
     @torch.no_grad()
     def outpaint(self, scale_mul, anchor=(0.5, 0.5), batch_size=16, custom_t_list=None, save_unbatched=False,
-                 save_images=True, seeds=None, vary_from_scale=None):
+                 save_images=True, seeds=None, vary_from_scale=None, resample=1, jump_length=1):
         """Grow the canvas around the training image: at every scale the sample has `target_size(s, scale_mul)`, the
         scale's own training image sits unresampled at int(anchor * (canvas - image)) and is kept (mask 1 on that
-        rectangle), the rest is generated.  `scale_mul` < 1 on an axis is a ValueError."""
+        rectangle), the rest is generated.  `scale_mul` < 1 on an axis is a ValueError.  `resample` / `jump_length`: as for
+        `inpaint`."""
         from .functions import outpaint_offset
         em = self.ema_model
         if min(float(scale_mul[0]), float(scale_mul[1])) < 1:
@@ -522,7 +532,8 @@ class MultiscaleTrainer(object):
             k0[:, y0:y0 + h, x0:x0 + w] = img
             m[y0:y0 + h, x0:x0 + w] = 1.0
             maps[s] = (m, k0)
-        return self._sample_kept(maps, 'outpaint', scale_mul=tuple(scale_mul), batch_size=batch_size,
+        return self._sample_kept(maps, 'outpaint', resample=resample, jump_length=jump_length, scale_mul=tuple(scale_mul),
+                                 batch_size=batch_size,
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
                                  seeds=seeds, vary_from_scale=vary_from_scale)
 
