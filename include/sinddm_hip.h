@@ -346,6 +346,73 @@ int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_
                              const float* keep_m, const float* keep_x0, float keep_a, float keep_b,
                              int B, int C, int HW, void* stream);
 
+/* ---- layout conditioning: paint-to-image inside the chain call ------------------------------------------------------- */
+/* At every conditioned reverse step the LOW spatial frequencies of the predicted clean image are pulled to those of a layout
+ * picture L; the high frequencies stay the model's own (ILVR-style conditioning on SinDDM's x_recon; no reference line;
+ * derivation in DESIGN.md 3).  One scale: the image (the centre) is Hc x Wc, the buffers H x W = (Hc + 2 halo_y) x
+ * (Wc + 2 halo_x).  Block size N = `down`, 1 <= N <= 64, any integer; h = ceil(Hc / N), w = ceil(Wc / N).
+ *   clean estimate  xp[b] is what the step computes before its clamp, after the ROI edit when one is on:
+ *                     mode 0       xp = ew * x0 + ec
+ *                     modes 1, 2   xp = ew * ((x0 - gamma_t * x_tilde) / (1 - gamma_t)) + ec
+ *                   with x0 = sqrt_recip_ac_t * x - sqrt_recipm1_ac_t * eps.
+ *   block delta     D[b][ch][Y][X] = mean of  L[ch] - xp[b][ch]  over the centre pixels of block (Y, X): rows
+ *                   Y * N ... min((Y + 1) * N, Hc) - 1, columns likewise; a partial edge block divides by its own pixel
+ *                   count.  Under a halo the block grid starts at (halo_y, halo_x) and covers the centre only: halo pixels
+ *                   are never read (their eps has seen the zero padding, it is not the wrapped centre's).
+ *   upsampled delta U(D)[b][ch][y][x] = bilinear interpolation between block centres: centre coordinate yc = y - halo_y
+ *                   (modulo Hc on a wrapped axis), source coordinate fy = (yc + 0.5) / N - 0.5.  Plain axis: fy clamped to
+ *                   [0, h - 1], y0 = floor(fy), y1 = min(y0 + 1, h - 1).  Wrapped axis: no clamp, y0 = floor(fy) mod h,
+ *                   y1 = (y0 + 1) mod h (the convention of sinddm_upsample_bilinear_wrap).  x alike.  N = 1: the identity.
+ *   the step        the ordinary step with the edit constant replaced per sample by  c_eff = ec + g_i * U(D)[b]  (ec = 0
+ *                   without an ROI edit): the pull acts on x_recon before the re-blur mix and the clamps, exactly where the
+ *                   ROI edit acts; keep maps act on the output as before.  g_i = 0 is the ordinary step;  N = 1, g = 1
+ *                   replaces x_recon by L.
+ * D is reduced in fp32 without atomics, in an order that depends on N and the block's extent alone: the D of a sample does
+ * not depend on its batch, its position in it or the two-stream split, bit for bit. */
+typedef struct sinddm_layout_opts {
+    const float* layout;   /* device, 3*H*W floats, 16-byte aligned; arrives wrapped under a halo; shared by all samples */
+    int down;              /* the block size N                                                                            */
+    const float* g;        /* HOST, n_steps floats in [0, 1]: the strength per step                                       */
+    float* delta;          /* device scratch, B*3*h*w floats                                                              */
+} sinddm_layout_opts;
+
+/* sinddm_sample_chain_resample with layout conditioning (that entry is a thin wrapper over this one).  lo = NULL,
+ * lo->layout = NULL or every g_i == 0: the same launches, the same numbers as sinddm_sample_chain_resample.  A step with
+ * g_i > 0 runs unfused, as a jump step does: the network writes eps, then the delta kernel, then the layout tail -- each per
+ * half-batch on that half's stream, the second half with its own slice of `delta`; every other step keeps its fused tail.
+ * Results with / without aux_stream are identical; seeds, recorded draws, halo, keep and edit work as before.
+ * SINDDM_E_BADARG (before any device work): with lo->layout set, `g` missing or a g_i outside [0, 1]; and on a run with some
+ * g_i > 0 (the rest of the block is read by no other run): `down` outside 1 ... 64, `delta` missing, `layout` not 16-byte
+ * aligned, a step with both g_i > 0 and jumps[i].on (layout pull inside a resampling jump is not built). */
+int sinddm_sample_chain_layout(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                               const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                               int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                               void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                               const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                               const sinddm_keep_opts* keep /*host, may be NULL*/,
+                               const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/,
+                               const sinddm_resample_opts* rs /*host, may be NULL*/,
+                               const sinddm_layout_opts* lo /*host, may be NULL*/);
+
+/* The block delta on its own: delta[B][3][h][w] from the step's inputs.  H x W is the CENTRE size (as in the chain calls);
+ * x_t, eps, x_tilde are B*3*(H + 2 halo_y)*(W + 2 halo_x) floats, layout / edit_c one sample of that, edit_w one plane.
+ * edit_w / edit_c both-or-neither.  x_tilde is read in modes 1 and 2 only.
+ * SINDDM_E_BADARG: a missing pointer, `down` outside 1 ... 64, a negative halo; SINDDM_E_BADSHAPE: B * 3 > 65535. */
+int sinddm_layout_delta(const float* x_t, const float* eps, const float* x_tilde, const float* layout, float* delta,
+                        const sinddm_step_coefs* coefs /*host*/, const float* edit_w, const float* edit_c, int down,
+                        int B, int H, int W, int halo_y, int halo_x, void* stream);
+
+/* One conditioned reverse step, noise supplied by the caller, `delta` given (sinddm_layout_delta's, or any B*3*h*w floats):
+ * the step-by-step route and the cross-check of the chain call; mirrors sinddm_reverse_step_keep.  edit_w / edit_c and
+ * keep_m / keep_x0 are each both-or-neither and may be NULL (keep_a / keep_b are then ignored).  H x W is the CENTRE size; an
+ * axis wraps when its halo is set or its wrap flag is (the step-by-step route of a tiled run steps the centre: halo 0, flag
+ * set).  SINDDM_E_BADARG: a missing pointer, `down` outside 1 ... 64, g outside [0, 1], a negative halo. */
+int sinddm_reverse_step_layout(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                               const sinddm_step_coefs* coefs /*host*/, const float* delta, float g, int down,
+                               const float* edit_w, const float* edit_c, const float* keep_m, const float* keep_x0,
+                               float keep_a, float keep_b, int B, int H, int W, int halo_y, int halo_x, int wrap_y,
+                               int wrap_x, void* stream);
+
 /* ---- training ------------------------------------------------------------------------------ */
 /* Scratch for one training forward+backward of a (B,3,H,W) batch: saved activations (about
  * 1843 floats per pixel per sample at dim=160) + backward scratch. */

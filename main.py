@@ -22,6 +22,11 @@ black part of the mask (white = keep the training image's pixel; the file is bro
 `--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.  `--resample R --jump_length J`
 (both modes; defaults 1 1 = no jumps) add RePaint's resampling: at every noise level that is a multiple of J the run jumps
 back up by J levels and comes down again, R times in all, so that the generated region is shaped with the known one in view.
+`paint2image` (no reference mode) redraws a rough picture -- a scribble, a colour sketch, a blurred photo -- in the training
+image's texture while its layout stays put: `--mode paint2image --input_image FILE [--layout_down N] [--layout_strength G]
+[--layout_t_min T] [--layout_scales A B]` pulls the low spatial frequencies (the band below N pixels of the finest scale) of
+every step's predicted clean image towards the picture's, with strength G in [0, 1], at the steps with t >= T of the scales
+A ... B (default: all).  FILE (a path, or a name inside the dataset folder) is brought to the finest target size.
 `--seeds S [S ...]` (one per sample of the batch) or `--seed_base N` (seeds N ... N + batch - 1) give every sample its own
 noise seed (no reference flag: the reference never seeds its generator): the image of a seed is the same at any batch size,
 position in the batch and number of GPUs.  `--vary_from_scale S` keeps the given seeds below scale S and derives fresh
@@ -83,6 +88,11 @@ def build_parser():
     # no reference flags: RePaint's resampling jumps of `inpaint` / `outpaint` (MultiScaleGaussianDiffusion.resample)
     p.add_argument("--resample", type=int, default=1)
     p.add_argument("--jump_length", type=int, default=1)
+    # no reference flags: layout conditioning of `paint2image` (MultiscaleTrainer.paint2image)
+    p.add_argument("--layout_down", type=int, default=8)
+    p.add_argument("--layout_strength", type=float, default=1.0)
+    p.add_argument("--layout_t_min", type=int, default=0)
+    p.add_argument("--layout_scales", type=int, nargs=2, default=None)
     return p
 
 
@@ -104,6 +114,14 @@ def parse_args(argv=None):
         p.error("--vary_from_scale must be >= 0")
     if args.resample < 1 or args.jump_length < 1:
         p.error("--resample and --jump_length must be >= 1")
+    if not 1 <= args.layout_down <= 64:
+        p.error("--layout_down must be in 1 ... 64")
+    if not 0.0 <= args.layout_strength <= 1.0:
+        p.error("--layout_strength must be in [0, 1]")
+    if args.layout_t_min < 0:
+        p.error("--layout_t_min must be >= 0")
+    if args.layout_scales is not None and not 0 <= args.layout_scales[0] <= args.layout_scales[1]:
+        p.error("--layout_scales A B needs 0 <= A <= B")
     return args
 
 
@@ -205,9 +223,19 @@ def main():
         trainer.outpaint(scale_mul, anchor=tuple(args.anchor), batch_size=args.sample_batch_size,
                          custom_t_list=sample_t_list, save_unbatched=True, resample=args.resample,
                          jump_length=args.jump_length, **seed_kw)
+    elif args.mode == 'paint2image':
+        import numpy as np
+        from PIL import Image
+        path = args.input_image if os.path.exists(args.input_image) else os.path.join(args.dataset_folder, args.input_image)
+        h, w = ms_diffusion.target_size(n_scales - 1, scale_mul)
+        pic = np.asarray(Image.open(path).convert("RGB").resize((w, h), Image.LANCZOS), dtype=np.float32)
+        layout = torch.from_numpy(pic.transpose(2, 0, 1).copy()).div(255).mul(2).sub(1)
+        trainer.paint2image(layout, batch_size=args.sample_batch_size, down=args.layout_down, strength=args.layout_strength,
+                            t_min=args.layout_t_min, scales=args.layout_scales, scale_mul=scale_mul,
+                            custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
     else:
         raise NotImplementedError(
-            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint and outpaint are built for MI355X; "
+            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint and paint2image are built for MI355X; "
             "the CLIP-guided modes of the reference need CLIP autograd and are out of scope (SURVEY.md section 8)")
     if world > 1:
         td.destroy_process_group()

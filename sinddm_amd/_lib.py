@@ -27,6 +27,7 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_keep", "sinddm_reverse_step_keep", "sinddm_normal_fill_samples", "sinddm_sample_chain_seeds",
     "sinddm_debug_head_path", "sinddm_debug_head_offsets", "sinddm_debug_head", "sinddm_debug_routes",
     "sinddm_sample_chain_resample", "sinddm_reverse_step_jump",
+    "sinddm_sample_chain_layout", "sinddm_layout_delta", "sinddm_reverse_step_layout",
 )
 
 
@@ -66,6 +67,12 @@ class ResampleOpts(C.Structure):
     """Mirror of `sinddm_resample_opts` (include/sinddm_hip.h): `jumps` a HOST array of one entry per step, `noise` a device
     pointer (the z2 draws of the call's jumps, one slot per jump) or None."""
     _fields_ = [("jumps", C.POINTER(JumpCoefs)), ("noise", C.c_void_p)]
+
+
+class LayoutOpts(C.Structure):
+    """Mirror of `sinddm_layout_opts` (include/sinddm_hip.h): `layout` / `delta` device pointers, `down` the block size N, `g`
+    a HOST array of one strength per step of the call."""
+    _fields_ = [("layout", C.c_void_p), ("down", C.c_int), ("g", C.POINTER(C.c_float)), ("delta", C.c_void_p)]
 
 
 class SinddmError(RuntimeError):
@@ -116,6 +123,11 @@ def load() -> C.CDLL:
         "sinddm_sample_chain_seeds": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p]),
         "sinddm_sample_chain_resample": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
                                                      C.POINTER(ResampleOpts)]),
+        "sinddm_sample_chain_layout": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
+                                                   C.POINTER(ResampleOpts), C.POINTER(LayoutOpts)]),
+        "sinddm_layout_delta": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, i, i, i, p]),
+        "sinddm_reverse_step_layout": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, f, i, p, p, p, p, f, f, i, i, i, i, i, i, i,
+                                           p]),
         "sinddm_reverse_step_jump": (i, [p, p, p, p, p, p, C.POINTER(StepCoefs), C.POINTER(JumpCoefs), p, p, p, p, f, f, i, i, i,
                                          p]),
         "sinddm_normal_fill_samples": (i, [p, i, i64, p, C.c_uint64, p]),

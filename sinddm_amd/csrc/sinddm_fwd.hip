@@ -1296,6 +1296,43 @@ static int jump_launch(const float* x_t, const float* eps, const float* x_tilde,
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
 
+// the geometry of a layout-conditioned scale (LayoutArgs without D and g): centre Hc x Wc, block size N
+static LayoutArgs layout_geom(int Hc, int Wc, int halo_y, int halo_x, int N, bool wrap_y, bool wrap_x) {
+    LayoutArgs g{};
+    g.N = N; g.Hc = Hc; g.Wc = Wc; g.hy = halo_y; g.hx = halo_x;
+    g.H = Hc + 2 * halo_y; g.W = Wc + 2 * halo_x;
+    g.h = (Hc + N - 1) / N; g.w = (Wc + N - 1) / N;
+    g.wrap_y = wrap_y || halo_y != 0; g.wrap_x = wrap_x || halo_x != 0;
+    return g;
+}
+
+// block deltas of `Bn` samples (layout_delta_kernel): g.D is written
+static int layout_delta_launch(const float* x_t, const float* eps, const float* x_tilde, const float* layout, const float* edit_w,
+                               const float* edit_c, const sinddm_step_coefs& k, const LayoutArgs& g, int Bn, hipStream_t st) {
+    const int cols = (256 / g.N) * g.N, bpw = cols / g.N;
+    const dim3 grid((unsigned)((g.w + bpw - 1) / bpw), (unsigned)g.h, (unsigned)(Bn * CHANNELS));
+    float* D = const_cast<float*>(g.D);
+    if (edit_w)
+        hipLaunchKernelGGL(layout_delta_kernel<true>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, D, k, g, cols);
+    else
+        hipLaunchKernelGGL(layout_delta_kernel<false>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, D, k, g, cols);
+    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+}
+
+// the conditioned step (reverse_step_layout_kernel) over `Bn` samples: rows as in jump_launch
+static int layout_step_launch(const float* x_t, const float* eps, const float* x_tilde, float* out, const TailArgs& t,
+                              const LayoutArgs& g, int Bn, int chw, int hw, hipStream_t st) {
+    const long long span = t.sseeds ? chw : (long long)Bn * chw;
+    long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
+    if (gx > 8192) gx = 8192;
+    tail_dispatch(t, [&](auto E, auto N, auto K) {
+        hipLaunchKernelGGL((reverse_step_layout_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                           dim3((unsigned)gx, t.sseeds ? (unsigned)Bn : 1u), dim3(256), 0, st, x_t, eps, x_tilde, out, t, g, span,
+                           chw, hw);
+    });
+    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+}
+
 // The body of every sinddm_sample_chain* entry point: each passes 0 / NULL for the options its signature does not have
 // (sinddm_sample_chain_seeds has them all).  Hc x Wc is the CENTRE size; the
 // steps run on the extended shape H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo,
@@ -1305,7 +1342,8 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
                              uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                             const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs) {
+                             const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
+                             const sinddm_layout_opts* lo) {
     if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
     if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
     if ((reinterpret_cast<uintptr_t>(sample_seeds) & 7) != 0) return SINDDM_E_BADARG;
@@ -1339,6 +1377,28 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     }
     const float* jump_noise = jumps ? rs->noise : nullptr;   // one slot per jump, in order of occurrence
     if ((reinterpret_cast<uintptr_t>(jump_noise) & 15) != 0 || (jumps && noise && !jump_noise)) return SINDDM_E_BADARG;
+    // layout conditioning: a step with g[i] > 0 runs unfused and ends in layout_delta_kernel + reverse_step_layout_kernel; no
+    // such step: `lay_g` stays NULL and nothing below differs from the call without `lo`
+    const float* lay_g = nullptr;
+    LayoutArgs lay{};
+    if (lo && lo->layout) {
+        if (!lo->g) return SINDDM_E_BADARG;
+        for (int i = 0; i < n_steps; ++i) {
+            if (!(lo->g[i] >= 0.0f && lo->g[i] <= 1.0f)) return SINDDM_E_BADARG;
+            if (lo->g[i] > 0.0f) {
+                if (jumps && jumps[i].on) return SINDDM_E_BADARG;
+                lay_g = lo->g;
+            }
+        }
+        if (lay_g) {                                           // (the rest of the block is read only by a run that pulls)
+            if (lo->down < 1 || lo->down > 64 || !lo->delta || (reinterpret_cast<uintptr_t>(lo->layout) & 15) != 0)
+                return SINDDM_E_BADARG;
+            if ((long long)CHANNELS * H * W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;    // (an element's index inside its sample is an int)
+            if ((long long)B * CHANNELS > 65535) return SINDDM_E_BADSHAPE;               // (one grid plane per (sample, channel))
+            lay = layout_geom(Hc, Wc, halo_y, halo_x, lo->down, false, false);
+            if (lay.h > 65535) return SINDDM_E_BADSHAPE;                                  // (one grid row per block row)
+        }
+    }
     NetPlan p = make_plan(dim);
     if (!p.ok) return SINDDM_E_BADSHAPE;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1418,11 +1478,13 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                 if (noise) jp.nz = jump_noise + (size_t)n_jumped * (size_t)n;
                 ++n_jumped;
             }
+            const bool pull = lay_g && lay_g[i] > 0.0f;        // the step writes eps; delta kernel + layout tail behind it
+            if (pull) lay.g = lay_g[i];
             for (int h = 0; h < (split ? 2 : 1) && rc == 0; ++h) {
                 const size_t o = h ? hoff : 0;
                 ChainStep cs{};
                 cs.cond_row = cond_tab + (size_t)(i - i0) * p.cond_stride;
-                cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail && !jump ? nxt + o : nullptr;
+                cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail && !jump && !pull ? nxt + o : nullptr;
                 cs.tail = t;
                 cs.tail.b0 = h ? Bh[0] : 0;
                 if (sseeds) cs.tail.sseeds = sseeds + cs.tail.b0;
@@ -1430,6 +1492,14 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                                       h ? sx : st, nullptr, &cs);
                 if (jump && fuse_tail && rc == 0)
                     rc = jump_launch(cur + o, eps + o, cs.x_tilde, nxt + o, cs.tail, jp, Bh[h], CHANNELS * H * W, H * W, h ? sx : st);
+                if (pull && fuse_tail && rc == 0) {
+                    LayoutArgs lh = lay;                       // (the half's own slice of the scratch)
+                    lh.D = lo->delta + (size_t)cs.tail.b0 * CHANNELS * lay.h * lay.w;
+                    rc = layout_delta_launch(cur + o, eps + o, cs.x_tilde, lo->layout, edit_w, edit_c, t.k, lh, Bh[h], h ? sx : st);
+                    if (rc == 0)
+                        rc = layout_step_launch(cur + o, eps + o, cs.x_tilde, nxt + o, cs.tail, lh, Bh[h], CHANNELS * H * W, H * W,
+                                                h ? sx : st);
+                }
                 if (tiled && fuse_tail && rc == 0)
                     rc = wrap_halo_launch(nxt + o, nullptr, Bh[h] * CHANNELS, Hc, Wc, halo_y, halo_x, h ? sx : st);
             }
@@ -1442,6 +1512,10 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                 if (gx > 8192) gx = 8192;
                 if (jump) {
                     if ((rc = jump_launch(cur, eps, x_tilde, nxt, t, jp, B, chw, H * W, st)) != 0) break;
+                } else if (pull) {
+                    lay.D = lo->delta;
+                    if ((rc = layout_delta_launch(cur, eps, x_tilde, lo->layout, edit_w, edit_c, t.k, lay, B, st)) != 0) break;
+                    if ((rc = layout_step_launch(cur, eps, x_tilde, nxt, t, lay, B, chw, H * W, st)) != 0) break;
                 } else {
                     tail_dispatch(t, [&](auto E, auto N, auto K) {
                         hipLaunchKernelGGL((reverse_step_rows_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
@@ -1478,7 +1552,7 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
                            uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                            void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1486,7 +1560,7 @@ int sinddm_sample_chain_tile(const float* params, const float* packed, float* x,
                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_keep(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1495,7 +1569,7 @@ int sinddm_sample_chain_keep(const float* params, const float* packed, float* x,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1504,7 +1578,7 @@ int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x
                               void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                               const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_resample(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1513,7 +1587,17 @@ int sinddm_sample_chain_resample(const float* params, const float* packed, float
                                  void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                                  const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, nullptr);
+}
+
+int sinddm_sample_chain_layout(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                               const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                               uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                               void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
+                               const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
+                               const sinddm_layout_opts* lo) {
+    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, lo);
 }
 
 int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1521,7 +1605,7 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
                          uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                          void* aux_stream, int* result_in_alt) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1529,7 +1613,7 @@ int sinddm_sample_chain(const float* params, const float* packed, float* x, floa
                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                         int* result_in_alt) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
@@ -1572,6 +1656,36 @@ int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_
     JumpArgs jp{};
     jp.r = jump->r; jp.s = jump->s; jp.d = jump->d; jp.nz = jump_noise;
     return jump_launch(x_t, eps, x_tilde, out, t, jp, B, C * HW, HW, static_cast<hipStream_t>(stream));
+}
+
+int sinddm_layout_delta(const float* x_t, const float* eps, const float* x_tilde, const float* layout, float* delta,
+                        const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, int down, int B, int H, int W,
+                        int halo_y, int halo_x, void* stream) {
+    if (!x_t || !eps || !layout || !delta || !coefs || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    if (down < 1 || down > 64 || halo_y < 0 || halo_x < 0 || halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;
+    if ((edit_w == nullptr) != (edit_c == nullptr) || (coefs->mode != 0 && !x_tilde)) return SINDDM_E_BADARG;
+    if ((long long)B * CHANNELS > 65535 || (H + down - 1) / down > 65535) return SINDDM_E_BADSHAPE;
+    LayoutArgs g = layout_geom(H, W, halo_y, halo_x, down, false, false);
+    g.D = delta;
+    return layout_delta_launch(x_t, eps, x_tilde, layout, edit_w, edit_c, *coefs, g, B, static_cast<hipStream_t>(stream));
+}
+
+int sinddm_reverse_step_layout(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                               const sinddm_step_coefs* coefs, const float* delta, float g, int down, const float* edit_w,
+                               const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B,
+                               int H, int W, int halo_y, int halo_x, int wrap_y, int wrap_x, void* stream) {
+    if (!x_t || !eps || !noise || !out || !coefs || !delta || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    if (down < 1 || down > 64 || !(g >= 0.0f && g <= 1.0f)) return SINDDM_E_BADARG;
+    if (halo_y < 0 || halo_x < 0 || halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;
+    if ((edit_w == nullptr) != (edit_c == nullptr) || (keep_m == nullptr) != (keep_x0 == nullptr)) return SINDDM_E_BADARG;
+    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
+    LayoutArgs la = layout_geom(H, W, halo_y, halo_x, down, wrap_y != 0, wrap_x != 0);
+    if ((long long)CHANNELS * la.H * la.W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
+    la.D = delta; la.g = g;
+    TailArgs t{};
+    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
+    t.km = keep_m; t.kx = keep_x0; t.ka = keep_m ? keep_a : 1.0f; t.kb = keep_m ? keep_b : 0.0f;
+    return layout_step_launch(x_t, eps, x_tilde, out, t, la, B, CHANNELS * la.H * la.W, la.H * la.W, static_cast<hipStream_t>(stream));
 }
 
 #ifdef W2_PHASE

@@ -323,6 +323,156 @@ __global__ __launch_bounds__(256) void reverse_step_jump_kernel(const float* __r
     }
 }
 
+// ---- LAYOUT conditioning (paint-to-image; ILVR-style low-band pull on x_recon, no reference line; contract in
+// include/sinddm_hip.h, derivation in DESIGN.md 3).  The centre Hc x Wc of a sample is cut into N x N blocks (h x w of them,
+// the last row / column partial).  D[b][ch][Y][X] is the mean over block (Y, X) of  L[ch] - xp[b][ch],  xp the step's clean
+// estimate before its clamp (step_xp); U(D) is D interpolated bilinearly between block centres, and the conditioned step is
+// the ordinary one with the edit constant  c_eff = ec + g * U(D)[b].  Two kernels behind the network's eps: the reduction
+// (a neighbourhood: the one thing a pointwise tail cannot do), then a tail that reads four taps of D per element.
+struct LayoutArgs {
+    const float* D;                     // block deltas of THIS launch's samples: [Bn][3][h][w]
+    float g;                            // the step's strength
+    int N;                              // block size, 1 .. 64
+    int H, W;                           // the buffers' size: (Hc + 2 hy) x (Wc + 2 hx)
+    int Hc, Wc, hy, hx;                 // the centre and the halo
+    int h, w;                           // ceil(Hc / N), ceil(Wc / N)
+    int wrap_y, wrap_x;                 // the axis wraps (always with a halo on it)
+};
+
+// `xp` of reverse_step_mean after the ROI edit, NOT clamped (x0 itself in mode 0): what the pull acts on
+__device__ __forceinline__ float step_xp(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c, bool edit) {
+    const float x0 = k.sqrt_recip_ac_t * x - k.sqrt_recipm1_ac_t * e;
+    const float xp = k.mode == 0 ? x0 : (x0 - k.gamma_t * xb) / (1.0f - k.gamma_t);
+    return edit ? w * xp + c : xp;
+}
+
+// One workgroup owns block row Y of one (sample, channel) plane over `cols` = (256 / N) * N centre columns, i.e. whole
+// blocks.  A thread owns a column: it adds its up to N rows top to bottom in a register (a wave reads 64 consecutive floats
+// of a row), the column sums meet in LDS, and one thread per block adds its N columns left to right.  No atomics, and the
+// order of a cell's additions depends on N and the block's own extent alone -- not on the batch, the sample's position or
+// the grid.  Columns past Wc hold an exact 0.  Halo pixels are never read.
+template <bool EDIT>
+__global__ __launch_bounds__(256) void layout_delta_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
+                                                           const float* __restrict__ xtil, const float* __restrict__ lay,
+                                                           const float* __restrict__ ew, const float* __restrict__ ec,
+                                                           float* __restrict__ D, sinddm_step_coefs k, LayoutArgs g, int cols) {
+    __shared__ float col[256];
+    const int bc = blockIdx.z, ch = bc % 3, Y = blockIdx.y;
+    const int xc = blockIdx.x * cols + threadIdx.x;
+    const int y0 = Y * g.N, y1 = min(y0 + g.N, g.Hc);
+    const size_t plane = (size_t)g.H * g.W;
+    float s = 0.0f;
+    if ((int)threadIdx.x < cols && xc < g.Wc) {
+        for (int y = y0; y < y1; ++y) {
+            const size_t p = (size_t)(y + g.hy) * g.W + g.hx + xc;
+            const size_t i = (size_t)bc * plane + p;
+            const float xb = k.mode != 0 ? xtil[i] : 0.0f;
+            s += lay[(size_t)ch * plane + p] - step_xp(k, xt[i], eps[i], xb, EDIT ? ew[p] : 1.0f, EDIT ? ec[(size_t)ch * plane + p] : 0.0f, EDIT);
+        }
+    }
+    col[threadIdx.x] = s;
+    __syncthreads();
+    const int bpw = cols / g.N, X = blockIdx.x * bpw + threadIdx.x;
+    if ((int)threadIdx.x < bpw && X < g.w) {
+        float t = 0.0f;
+        for (int j = 0; j < g.N; ++j) t += col[threadIdx.x * g.N + j];
+        const int nx = min((X + 1) * g.N, g.Wc) - X * g.N;
+        D[((size_t)bc * g.h + Y) * g.w + X] = t / (float)((y1 - y0) * nx);
+    }
+}
+
+// one axis of U: buffer coordinate v (halo included) -> the two block indices and the weight of the second.  Source
+// coordinate (vc + 0.5) / N - 0.5 of the centre coordinate vc; clamped to [0, n - 1] on a plain axis, taken modulo n on a
+// wrapped one (the convention of sinddm_upsample_bilinear_wrap).  N = 1: i0 = vc, weight 0.
+__device__ __forceinline__ void layout_axis(int v, int halo, int size, int N, int n, bool wrap, int& i0, int& i1, float& l) {
+    int vc = v - halo;
+    if (wrap) {
+        vc %= size;
+        if (vc < 0) vc += size;
+    }
+    float f = ((float)vc + 0.5f) / (float)N - 0.5f;
+    if (wrap) {
+        const float fl = floorf(f);
+        l = f - fl;
+        i0 = (int)fl % n;
+        if (i0 < 0) i0 += n;
+        i1 = i0 + 1 == n ? 0 : i0 + 1;
+    } else {
+        f = fminf(fmaxf(f, 0.0f), (float)(n - 1));
+        i0 = (int)f;
+        l = f - (float)i0;
+        i1 = min(i0 + 1, n - 1);
+    }
+}
+
+// g * U(D) at element r (index inside its sample) of launch-local sample b
+__device__ __forceinline__ float layout_pull(const LayoutArgs& g, int b, int r) {
+    const int hw = g.H * g.W;
+    const int ch = r / hw, p = r - ch * hw, y = p / g.W, x = p - y * g.W;
+    int iy0, iy1, ix0, ix1;
+    float ly, lx;
+    layout_axis(y, g.hy, g.Hc, g.N, g.h, g.wrap_y != 0, iy0, iy1, ly);
+    layout_axis(x, g.hx, g.Wc, g.N, g.w, g.wrap_x != 0, ix0, ix1, lx);
+    const float* __restrict__ d = g.D + ((size_t)b * 3 + ch) * g.h * g.w;
+    const float tl = d[iy0 * g.w + ix0], tr = d[iy0 * g.w + ix1], bl = d[iy1 * g.w + ix0], br = d[iy1 * g.w + ix1];
+    return g.g * ((1.0f - ly) * ((1.0f - lx) * tl + lx * tr) + ly * ((1.0f - lx) * bl + lx * br));
+}
+
+// The conditioned step, over ROWS exactly like reverse_step_jump_kernel (rows of a key's stream, partial first / last quads
+// of a half-batch, per-sample seeds, recorded draws): tail_eval with the edit always on and c_eff in place of ec (w = 1
+// without ROI maps).  An element's sample is its index inside the launch divided by chw: D is this launch's slice.
+template <bool EDIT, bool NOISE, bool KEEP>
+__global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
+                                                                  const float* __restrict__ xtil, float* __restrict__ out,
+                                                                  TailArgs a, LayoutArgs g, long long span, int chw, int hw) {
+    const long long base = (long long)blockIdx.y * span;
+    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
+    const long long gofs = (long long)a.b0 * chw;           // the launch's first element inside the whole batch
+    const long long kofs = a.sseeds ? 0 : gofs;             // the row's first element inside the key's stream
+    const bool draw = tail_draws<KEEP>(a);
+    const long long q1 = (kofs + span + 3) >> 2;
+    for (long long q = (kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x; q < q1; q += (long long)gridDim.x * 256) {
+        const long long e0 = (q << 2) - kofs;               // lane 0's index inside the row: -3 .. span - 1
+        const int jlo = e0 < 0 ? (int)-e0 : 0;
+        const int jhi = span - e0 < 4 ? (int)(span - e0) : 4;
+        const long long i0 = base + e0;                     // ... inside the launch's tensors (lanes below jlo are not touched)
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (draw) {
+            if (NOISE) quad_load(a.nz + gofs + i0, jlo, jhi, z);
+            else philox_normal4(key, a.step, (unsigned long long)q, z);
+        }
+        const int r0 = (int)(((i0 % chw) + chw) % chw);
+        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
+        if (EDIT) quad_maps(a.ew, a.ec, r0, jhi, chw, hw, w, c);
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
+        if (KEEP) quad_maps(a.km, a.kx, r0, jhi, chw, hw, m, k0);
+        // the first valid lane's sample and index inside it; the lanes behind it may run over the sample's end
+        const long long iv = i0 + jlo;
+        int b = (int)(iv / chw), r = (int)(iv - (long long)b * chw);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= jlo && j < jhi) {
+                c[j] += layout_pull(g, b, r);
+                if (++r == chw) { r = 0; ++b; }
+            }
+        }
+        float x[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f};
+        quad_load(xt + i0, jlo, jhi, x);
+        quad_load(eps + i0, jlo, jhi, e);
+        if (a.k.mode != 0) quad_load(xtil + i0, jlo, jhi, xb);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = tail_eval<true, KEEP>(a, x[j], e[j], xb[j], z[j], w[j], c[j], m[j], k0[j]);
+        if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(out + i0) & 15) == 0) {
+            *reinterpret_cast<f32x4*>(out + i0) = o;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j >= jlo && j < jhi) out[i0 + j] = o[j];
+        }
+    }
+}
+
 // ---- eps stage + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
 // four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
 // path): eps never goes to memory.  EPS (head.h) fills the thread's e[3]: HeadEps, the collapsed head on block 4's g and

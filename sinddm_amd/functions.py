@@ -211,6 +211,48 @@ def resample_schedule(t_seq: Sequence[int], resample: int = 1, jump: int = 1):
     return out, jump_to
 
 
+# ---- helpers of layout conditioning (MultiscaleTrainer.paint2image; no reference counterpart) ------------------------
+def layout_strengths(t_seq: Sequence[int], strength: float = 1.0, t_min: int = 0) -> List[float]:
+    """The per-step strengths g_i of a layout-conditioned run: `strength` at the steps with t >= t_min, 0 below (those steps
+    keep their fused tail: the last, least noisy steps are left to the model).  `strength` must lie in [0, 1]."""
+    g = float(strength)
+    if not 0.0 <= g <= 1.0:
+        raise ValueError(f"layout_strengths: strength {strength} outside [0, 1]")
+    if int(t_min) < 0:
+        raise ValueError(f"layout_strengths: t_min {t_min} must be >= 0")
+    return [g if int(t) >= int(t_min) else 0.0 for t in t_seq]
+
+
+def layout_blocks(n_finest: int, scale_factor: float, n_scales: int) -> List[int]:
+    """Block size per scale for a block of `n_finest` pixels at the finest one: N_s = max(1, round(N / f^(n_scales-1-s))),
+    the same physical band at every scale.  1 <= n_finest <= 64 (the kernels' range)."""
+    n = int(n_finest)
+    if not 1 <= n <= 64:
+        raise ValueError(f"layout_blocks: block size {n_finest} outside 1 ... 64")
+    if int(n_scales) < 1 or not float(scale_factor) > 1.0:
+        raise ValueError(f"layout_blocks: n_scales {n_scales} / scale_factor {scale_factor}")
+    return [max(1, int(round(n / float(scale_factor) ** (int(n_scales) - 1 - s)))) for s in range(int(n_scales))]
+
+
+def _layout_pyramid(layout, sizes) -> List[torch.Tensor]:
+    """A (3, H, W) layout picture brought to every (h, w) of `sizes` by area averaging (`_area_weights`: every output
+    pixel is a convex combination, so a constant image stays constant and the range is kept): fp32 tensors on the layout's
+    device."""
+    lay = torch.as_tensor(layout)
+    if lay.dim() != 3 or lay.shape[0] != 3:
+        raise ValueError(f"_layout_pyramid: layout must be (3, H, W), got {tuple(lay.shape)}")
+    device = lay.device
+    full = lay.detach().to("cpu", torch.float64).numpy()
+    out = []
+    for h, w in sizes:
+        h, w = int(h), int(w)
+        if h > full.shape[1] or w > full.shape[2] or h < 1 or w < 1:
+            raise ValueError(f"_layout_pyramid: scale {(h, w)} does not fit the layout {full.shape[1:]}")
+        avg = np.einsum("ij,cjk,lk->cil", _area_weights(h, full.shape[1]), full, _area_weights(w, full.shape[2]))
+        out.append(torch.from_numpy(avg.astype(np.float32)).to(device))
+    return out
+
+
 def _disk(radius: int) -> np.ndarray:
     """skimage.morphology.disk: (2r+1)^2 footprint of the pixels within Euclidean distance r."""
     yy, xx = np.mgrid[-radius:radius + 1, -radius:radius + 1]

@@ -522,6 +522,16 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # functions.resample_schedule; the upward move: sinddm_sample_chain_resample).  R = 1 is None.  A sampling option,
         # like `keep_maps` (which it is meant for, and does not require); not available with CLIP guidance.
         self.resample = None
+        # layout conditioning (paint-to-image): None or {s: (3, H_s, W_s) fp32 tensor on the sample's device}.  At a scale with
+        # an entry, every reverse step with t >= layout_t_min pulls the low spatial frequencies of the predicted clean image
+        # towards the layout's, with strength layout_strength in [0, 1]; "low" is the band below the block size
+        # layout_down[s] (1 ... 64; functions.layout_blocks gives one physical band for all scales).  Strength and t_min are
+        # one number or a dict per scale.  The contract: include/sinddm_hip.h (sinddm_layout_opts).  A sampling option like
+        # `keep_maps`; not available with CLIP guidance or together with `resample`.
+        self.layout_maps = None
+        self.layout_down = {}
+        self.layout_strength = 1.0
+        self.layout_t_min = 0
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -840,6 +850,35 @@ class MultiScaleGaussianDiffusion(nn.Module):
                                        f"running sample {tuple(img.shape)} {img.dtype} {img.device} (expected {shape} float32)")
         return m.contiguous(), k0.contiguous()
 
+    def _layout_entry(self, s: int, img: torch.Tensor):
+        """(layout, N, strength, t_min) of `layout_maps` for scale s, checked against the running sample as `_keep_entry`
+        checks its maps, or None (no entry, or strength 0)."""
+        if self.layout_maps is None:
+            return None
+        if self.clip_guided_sampling:
+            raise NotImplementedError("layout_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and "
+                                      "has no layout pull")
+        lay = self.layout_maps.get(int(s))
+        if lay is None:
+            return None
+        shape = (int(img.shape[1]), int(img.shape[-2]), int(img.shape[-1]))
+        if shape[0] != 3 or tuple(lay.shape) != shape or lay.dtype != torch.float32 or lay.device != img.device:
+            raise _lib.SinddmError(f"layout_maps[{int(s)}] {tuple(lay.shape)} {lay.dtype} {lay.device} does not match the "
+                                   f"running sample {tuple(img.shape)} {img.dtype} {img.device} (expected {shape} float32)")
+        per = lambda v: v.get(int(s), 0) if isinstance(v, dict) else v
+        if int(s) not in self.layout_down:
+            raise ValueError(f"layout_down has no block size for scale {int(s)}")
+        N, g, t_min = int(self.layout_down[int(s)]), float(per(self.layout_strength)), int(per(self.layout_t_min))
+        if not 1 <= N <= 64:
+            raise ValueError(f"layout_down[{int(s)}] = {N} outside 1 ... 64")
+        if not 0.0 <= g <= 1.0 or t_min < 0:
+            raise ValueError(f"layout_strength {g} outside [0, 1] or layout_t_min {t_min} < 0 at scale {int(s)}")
+        if g == 0.0:
+            return None                                        # (the run without the option, resampled or not)
+        if self._resample_cfg() is not None:
+            raise NotImplementedError("layout_maps with resample: the layout pull inside a resampling jump is not built")
+        return lay.contiguous(), N, g, t_min
+
     def _tile_halo(self) -> Tuple[int, int]:
         """(halo_y, halo_x) in pixels of the `tile` setting: _lib.TILE_HALO on a wrapped axis, 0 elsewhere."""
         wy, wx = self.tile
@@ -881,9 +920,20 @@ class MultiScaleGaussianDiffusion(nn.Module):
         sinddm_sample_chain_resample call on every route above (in-kernel noise, `chain_noise` buffers with a 'jump' draw per
         jump, seeds, tiled): a step that is followed by a jump ends in the step + jump kernel instead of its fused tail.  The
         step-by-step route goes through sinddm_reverse_step_jump.  `draw_log` gets ("chain_resample", s, seed or seeds,
-        expanded t list, jump targets)."""
+        expanded t list, jump targets).
+        With `layout_maps` set at this scale the run is ONE sinddm_sample_chain_layout call on every route above: the steps
+        with t >= layout_t_min run unfused (network, block-delta kernel, layout tail), the others keep their fused tail; the
+        draws and `draw_log` entries are those of the run without it.  The step-by-step route goes through
+        sinddm_layout_delta + sinddm_reverse_step_layout."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
+        lay = self._layout_entry(s, img)                       # (raises with `resample` / CLIP guidance)
+        lay_g = None                                           # per step: the strength of the pull
+        if lay is not None:
+            from .functions import layout_strengths
+            lay_g = layout_strengths(t_seq, lay[2], lay[3])
+            if not any(v > 0.0 for v in lay_g):
+                lay = lay_g = None
         rs_cfg = self._resample_cfg()
         jump_to = None                                         # per step of the EXPANDED walk: the level to jump to, or None
         if rs_cfg is not None:
@@ -945,6 +995,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
             jumps = (_lib.JumpCoefs * n)(*[_lib.JumpCoefs(0, 0.0, 0.0, 0.0) if l2 is None else _lib.JumpCoefs(1, *jt(t - 1, l2))
                                            for t, l2 in zip(t_seq, jump_to)])
             ropts = _lib.ResampleOpts()
+        lopts = None
+        if lay is not None:
+            lay_map = self._wrap_pad(lay[0], hy, hx) if tiled else lay[0]  # (locals of this frame: alive for the call)
+            lay_delta = torch.empty(B * 3 * (-(-Hc // lay[1])) * (-(-Wc // lay[1])), dtype=x.dtype, device=x.device)
+            garr = (C.c_float * n)(*lay_g)
+            lopts = _lib.LayoutOpts()
+            lopts.layout, lopts.down, lopts.delta = _lib.ptr(lay_map), lay[1], _lib.ptr(lay_delta)
         aux = _aux_stream(x.device) if self.two_streams else None
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
 
@@ -958,7 +1015,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
                     B, Hc, Wc, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts))
             if kopts is not None:
                 kopts.ab = C.cast(C.addressof(ab) + 2 * i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
-            if ropts is not None:
+            if lopts is not None:
+                lopts.g = C.cast(C.addressof(garr) + i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
+                _lib.check(lib.sinddm_sample_chain_layout(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
+                                                          _lib.ptr(seeds_dev), None, C.byref(lopts)), "sinddm_sample_chain_layout")
+            elif ropts is not None:
                 ropts.jumps = C.cast(C.addressof(jumps) + i0 * C.sizeof(_lib.JumpCoefs), C.POINTER(_lib.JumpCoefs))
                 ropts.noise = _lib.ptr(jump_noise)
                 _lib.check(lib.sinddm_sample_chain_resample(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
@@ -1041,6 +1102,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
         the level a resampling jump takes the step's output back up to (sinddm_reverse_step_jump: step + jump in one kernel,
         a second draw of kind 'jump'), or None."""
         keep = self._keep_entry(s, x)                                       # (raises under CLIP guidance)
+        lay = self._layout_entry(s, x)                                      # (so does this)
         if jump_to is not None and self.clip_guided_sampling:
             raise NotImplementedError("a resampling jump on a CLIP-guided step")
         if self.clip_guided_sampling:
@@ -1067,6 +1129,28 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
             xt = xt.contiguous()
         out = torch.empty_like(x)
+        if lay is not None and int(t) >= lay[3]:
+            # the conditioned step: block deltas of (layout - x_recon), then the step with c_eff = ec + g * U(D)
+            if jump_to is not None:
+                raise NotImplementedError("a layout pull on a step that is followed by a resampling jump")
+            B_, C_, H_, W_ = x.shape
+            ew = ec = None
+            if self.roi_guided_sampling and s < self.n_scales - 1:
+                ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
+            ka, kb = (float(v) for v in self._keep_ab_table()[int(t)]) if keep is not None else (1.0, 0.0)
+            N = lay[1]
+            delta = torch.empty(B_ * 3 * (-(-H_ // N)) * (-(-W_ // N)), dtype=x.dtype, device=x.device)
+            st = _lib.stream_ptr(x.device)
+            _lib.check(lib.sinddm_layout_delta(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(lay[0]), _lib.ptr(delta),
+                                               C.byref(k), _lib.ptr(ew), _lib.ptr(ec), N, B_, H_, W_, 0, 0, st),
+                       "sinddm_layout_delta")
+            _lib.check(lib.sinddm_reverse_step_layout(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
+                                                      C.byref(k), _lib.ptr(delta), lay[2], N, _lib.ptr(ew), _lib.ptr(ec),
+                                                      _lib.ptr(keep[0]) if keep is not None else None,
+                                                      _lib.ptr(keep[1]) if keep is not None else None, ka, kb, B_, H_, W_, 0, 0,
+                                                      int(bool(self.tile[0])), int(bool(self.tile[1])), st),
+                       "sinddm_reverse_step_layout")
+            return out
         if jump_to is not None:
             B_, C_, H_, W_ = x.shape
             z2 = self._draw("jump", x.shape, s, t, x.device, step_pos)

@@ -537,6 +537,44 @@ class MultiscaleTrainer(object):
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
                                  seeds=seeds, vary_from_scale=vary_from_scale)
 
+    # ---- layout conditioning: redraw a rough picture in the training image's texture (no reference counterpart) ----
+    @torch.no_grad()
+    def paint2image(self, layout, batch_size=16, down=8, strength=1.0, t_min=0, scales=None, scale_mul=(1, 1), seeds=None,
+                    vary_from_scale=None, custom_t_list=None, save_unbatched=False, save_images=True):
+        """Paint-to-image: `layout` is a (3, H, W) picture in [-1, 1] at the finest target size
+        (`ema_model.target_size(n_scales - 1, scale_mul)`) -- a scribble, a colour sketch, a blurred photo, another sample.
+        At every reverse step with t >= `t_min` the low spatial frequencies of the predicted clean image are pulled towards
+        the layout's with `strength` in [0, 1]; the high frequencies stay the model's own.  "Low" is the band below `down`
+        pixels at the finest scale, the same physical band at every scale (`functions.layout_blocks`); the layout reaches
+        each scale by area averaging (`functions._layout_pyramid`).  `scales` = (first, last) limits the conditioned scales
+        (inclusive; default all).  Runs `sample_scales` with `ema_model.layout_maps` / `layout_down` / `layout_strength` /
+        `layout_t_min` set (sinddm_sample_chain_layout: still one library call per scale) and clears them afterwards.
+        strength = 0 is `sample_scales` itself, bit for bit.  No image-quality claim is made."""
+        from .functions import layout_blocks, _layout_pyramid
+        em = self.ema_model
+        lay = torch.as_tensor(layout)
+        sizes = [tuple(em.target_size(s, scale_mul)) for s in range(self.n_scales)]
+        if lay.dim() != 3 or tuple(lay.shape) != (3,) + sizes[-1]:
+            raise ValueError(f'paint2image: layout {tuple(lay.shape)} must be (3, {sizes[-1][0]}, {sizes[-1][1]}), the finest '
+                             f'target size')
+        if not (0.0 <= float(strength) <= 1.0) or int(t_min) < 0:
+            raise ValueError(f'paint2image: strength {strength} outside [0, 1] or t_min {t_min} < 0')
+        first, last = (0, self.n_scales - 1) if scales is None else (int(scales[0]), int(scales[1]))
+        if not 0 <= first <= last < self.n_scales:
+            raise ValueError(f'paint2image: scales {scales} outside 0 ... {self.n_scales - 1}')
+        blocks = layout_blocks(down, self.scale_factor, self.n_scales)
+        pyr = _layout_pyramid(lay.to(torch.float32), sizes)
+        em.layout_maps = {s: pyr[s].to(self.device).contiguous() for s in range(first, last + 1)}
+        em.layout_down = {s: blocks[s] for s in range(first, last + 1)}
+        em.layout_strength, em.layout_t_min = float(strength), int(t_min)
+        try:
+            return self.sample_scales(scale_mul=tuple(scale_mul), custom_sample=False, image_name='', start_noise=True,
+                                      desc=f'paint2image_{str(datetime.datetime.now()).replace(":", "_")}',
+                                      batch_size=batch_size, custom_t_list=custom_t_list, save_unbatched=save_unbatched,
+                                      save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale)
+        finally:
+            em.layout_maps, em.layout_down, em.layout_strength, em.layout_t_min = None, {}, 1.0, 0
+
     # ---- CLIP-driven modes of the reference.  CLIP itself (clip/, text2live_util/) is not part of this build; the
     # driver takes any `clip_model` with the interface the reference uses: get_text_embedding(text, template=...),
     # zero_grad(), calculate_clip_loss(image in [0,1], embedding) (differentiable), cfg["n_aug"] ----
