@@ -146,7 +146,7 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
  *                    element e of the (B,3,H,W) state instead of drawing from Philox (`seed` / `stream_id0` are then
  *                    ignored).  Steps whose sigma is 0 (t == 0) read nothing, but keep their slot. */
 typedef struct sinddm_chain_opts {
-    const float* edit_w;   /* HW floats or NULL            (both or neither)                    */
+    const float* edit_w;   /* HW floats or NULL            (both or neither; per sample: sinddm_batch_opts) */
     const float* edit_c;   /* 3*HW floats or NULL                                               */
     const float* noise;    /* n_steps * B*3*H*W floats, step-major, or NULL -> in-kernel Philox */
 } sinddm_chain_opts;
@@ -228,7 +228,7 @@ int sinddm_sample_chain_tile(const float* params, const float* packed, float* x,
  * the keep on the output.  RePaint's resampling jumps (stepping back up in t and down again) are a separate option of the
  * run: sinddm_sample_chain_resample (below). */
 typedef struct sinddm_keep_opts {
-    const float* mask;   /* device, HW floats, 16-byte aligned        */
+    const float* mask;   /* device, HW floats, 16-byte aligned (per sample: sinddm_batch_opts) */
     const float* x0;     /* device, 3*HW floats, 16-byte aligned      */
     const float* ab;     /* HOST, 2*n_steps floats: (keep_a, keep_b) per step */
 } sinddm_keep_opts;
@@ -370,13 +370,15 @@ int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_
  * D is reduced in fp32 without atomics, in an order that depends on N and the block's extent alone: the D of a sample does
  * not depend on its batch, its position in it or the two-stream split, bit for bit. */
 typedef struct sinddm_layout_opts {
-    const float* layout;   /* device, 3*H*W floats, 16-byte aligned; arrives wrapped under a halo; shared by all samples */
+    const float* layout;   /* device, 3*H*W floats, 16-byte aligned; arrives wrapped under a halo; shared by all samples
+                              (one per sample: sinddm_batch_opts) */
     int down;              /* the block size N                                                                            */
     const float* g;        /* HOST, n_steps floats in [0, 1]: the strength per step                                       */
     float* delta;          /* device scratch, B*3*h*w floats                                                              */
 } sinddm_layout_opts;
 
-/* sinddm_sample_chain_resample with layout conditioning (that entry is a thin wrapper over this one).  lo = NULL,
+/* sinddm_sample_chain_resample with layout conditioning (that entry is a thin wrapper over this one; this one over
+ * sinddm_sample_chain_batch).  lo = NULL,
  * lo->layout = NULL or every g_i == 0: the same launches, the same numbers as sinddm_sample_chain_resample.  A step with
  * g_i > 0 runs unfused, as a jump step does: the network writes eps, then the delta kernel, then the layout tail -- each per
  * half-batch on that half's stream, the second half with its own slice of `delta`; every other step keeps its fused tail.
@@ -393,6 +395,41 @@ int sinddm_sample_chain_layout(const float* params, const float* packed, float* 
                                const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/,
                                const sinddm_resample_opts* rs /*host, may be NULL*/,
                                const sinddm_layout_opts* lo /*host, may be NULL*/);
+
+/* ---- per-sample conditioning maps: a batch of independent edit jobs per call ------------------------------------------ */
+/* Each map family of a chain call is shared by the batch (the default, as in every entry above) or PER SAMPLE: the pointer
+ * then holds B slices back to back and sample b of the batch reads slice b -- whatever the two-stream split does with the
+ * batch.  H and W below are the extended size under a halo, and per-sample maps arrive wrapped like shared ones.  The
+ * mask and the known image of `keep` are independent of each other; the two edit maps go together, like the pair itself.
+ * `layout_gain[b]` scales the layout strength of sample b: its step i pulls with the fp32 product g_i * layout_gain[b]
+ * (gain 0: no pull for that sample, though the step still runs unfused).  What stays shared per call: the t schedule,
+ * `rs`, the halo, `down` and `g`. */
+typedef struct sinddm_batch_opts {
+    int edit_per_sample;        /* opts->edit_w is B*H*W floats, opts->edit_c B*3*H*W */
+    int keep_mask_per_sample;   /* keep->mask is B*H*W floats                         */
+    int keep_x0_per_sample;     /* keep->x0 is B*3*H*W floats                         */
+    int layout_per_sample;      /* lo->layout is B*3*H*W floats                       */
+    const float* layout_gain;   /* device, B floats in [0, 1], or NULL                */
+} sinddm_batch_opts;
+
+/* sinddm_sample_chain_layout with per-sample maps (that entry is a thin wrapper over this one).  bo = NULL or all members
+ * zero: the same launches, the same numbers as sinddm_sample_chain_layout.  With shared maps every kernel computes what it
+ * did; a per-sample map only moves the address a sample reads.  Sample b's result is, bit for bit, sample b of the
+ * shared-map call that gets its slices (same batch, seed and start), wherever the network itself is independent of the
+ * other samples.
+ * SINDDM_E_BADARG (before any device work): a flag set whose pointer is NULL; `layout_gain` without lo->layout;
+ * `layout_gain` not 4-byte aligned; a per-sample map whose slices would not all start on a 16-byte boundary on a run that
+ * ends in the plain fused tail (H*W % 4 == 0 keeps every slice aligned when the map is). */
+int sinddm_sample_chain_batch(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                              const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                              int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                              void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                              const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                              const sinddm_keep_opts* keep /*host, may be NULL*/,
+                              const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/,
+                              const sinddm_resample_opts* rs /*host, may be NULL*/,
+                              const sinddm_layout_opts* lo /*host, may be NULL*/,
+                              const sinddm_batch_opts* bo /*host, may be NULL*/);
 
 /* The block delta on its own: delta[B][3][h][w] from the step's inputs.  H x W is the CENTRE size (as in the chain calls);
  * x_t, eps, x_tilde are B*3*(H + 2 halo_y)*(W + 2 halo_x) floats, layout / edit_c one sample of that, edit_w one plane.

@@ -31,6 +31,10 @@ A ... B (default: all).  FILE (a path, or a name inside the dataset folder) is b
 noise seed (no reference flag: the reference never seeds its generator): the image of a seed is the same at any batch size,
 position in the batch and number of GPUs.  `--vary_from_scale S` keeps the given seeds below scale S and derives fresh
 ones per sample from S on: `--seeds 17 17 17 17 --vary_from_scale 3` makes four variations of one coarse layout.
+A batch of independent jobs: `--mask_path`, `--input_image` and `--layout_strength` take one or more values and `--anchor` one
+or more pairs.  With N > 1 values the batch size must be a multiple of N and sample b gets value b % N (so `--seeds` sweeps
+line up: `--sample_batch_size 8 --mask_path a.png b.png --seed_base 0` fills each hole four times); every sample is then
+conditioned on its own maps inside the one chain call per scale.  One value is the command line as it was.
 The CLIP-guided modes (clip_content, clip_style_*, clip_roi; main.py:153-255) are not wired to the command line: CLIP
 itself is outside this build.  Their drivers exist (`MultiscaleTrainer.clip_sampling` / `clip_roi_sampling`, the guidance
 branch of `p_mean_variance`) and take any scorer with the reference's ClipExtractor interface.
@@ -68,12 +72,46 @@ _FLAGS = [
 ]
 
 
+class Jobs(list):
+    """Several values of a per-job flag, one job each (a single value stays the scalar it always was)."""
+
+
+class _OneOrMore(argparse.Action):
+    """nargs='+': one value is stored as itself, several as `Jobs`."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values[0] if len(values) == 1 else Jobs(values))
+
+
+class _Pairs(argparse.Action):
+    """--anchor y x [y x ...]: one pair is stored as the flat [y, x], several as `Jobs` of pairs."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if len(values) % 2:
+            parser.error(f"{option_string}: y x pairs expected, got {len(values)} values")
+        pairs = [list(values[i:i + 2]) for i in range(0, len(values), 2)]
+        setattr(namespace, self.dest, pairs[0] if len(pairs) == 1 else Jobs(pairs))
+
+
+_PER_JOB = ("mask_path", "input_image", "layout_strength", "anchor")     # the flags that take one value per job
+
+
+def job_values(value, batch_size):
+    """A per-job flag for a batch: `Jobs` of N values -> the list of `batch_size` values, sample b gets value b % N; one
+    value is returned as it is."""
+    if not isinstance(value, Jobs):
+        return value
+    return [value[b % len(value)] for b in range(int(batch_size))]
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     for name, dflt, typ, nargs in _FLAGS:
         kw = dict(default=dflt, type=typ)
         if nargs:
             kw["nargs"] = nargs
+        if name in _PER_JOB:
+            kw.update(nargs="+", action=_Pairs if name == "anchor" else _OneOrMore)
         p.add_argument("--" + name, **kw)
     p.add_argument("--sample_limited_t", action="store_true")
     # no reference flag (there: padding_mode='circular' on the nn.Conv2d's): borders that wrap around on the x axis (360-degree
@@ -90,7 +128,7 @@ def build_parser():
     p.add_argument("--jump_length", type=int, default=1)
     # no reference flags: layout conditioning of `paint2image` (MultiscaleTrainer.paint2image)
     p.add_argument("--layout_down", type=int, default=8)
-    p.add_argument("--layout_strength", type=float, default=1.0)
+    p.add_argument("--layout_strength", type=float, default=1.0, nargs="+", action=_OneOrMore)
     p.add_argument("--layout_t_min", type=int, default=0)
     p.add_argument("--layout_scales", type=int, nargs=2, default=None)
     return p
@@ -116,8 +154,14 @@ def parse_args(argv=None):
         p.error("--resample and --jump_length must be >= 1")
     if not 1 <= args.layout_down <= 64:
         p.error("--layout_down must be in 1 ... 64")
-    if not 0.0 <= args.layout_strength <= 1.0:
-        p.error("--layout_strength must be in [0, 1]")
+    for g in (args.layout_strength if isinstance(args.layout_strength, Jobs) else [args.layout_strength]):
+        if not 0.0 <= g <= 1.0:
+            p.error("--layout_strength must be in [0, 1]")
+    for name in _PER_JOB:
+        v = getattr(args, name)
+        if isinstance(v, Jobs) and args.sample_batch_size % len(v):
+            p.error(f"--{name}: {len(v)} values need --sample_batch_size to be a multiple of {len(v)}, got "
+                    f"{args.sample_batch_size}")
     if args.layout_t_min < 0:
         p.error("--layout_t_min must be >= 0")
     if args.layout_scales is not None and not 0 <= args.layout_scales[0] <= args.layout_scales[1]:
@@ -215,22 +259,41 @@ def main():
         import numpy as np
         from PIL import Image
         h, w = ms_diffusion.image_sizes[n_scales - 1]
-        known = np.asarray(Image.open(args.mask_path).convert("L").resize((w, h), Image.NEAREST)) > 127
-        trainer.inpaint(torch.from_numpy(known.astype(np.float32)), batch_size=args.sample_batch_size,
+        load = lambda f: torch.from_numpy((np.asarray(Image.open(f).convert("L").resize((w, h), Image.NEAREST)) > 127)
+                                          .astype(np.float32))
+        paths = job_values(args.mask_path, args.sample_batch_size)
+        if isinstance(paths, list):                                        # one mask per sample
+            files = {f: load(f) for f in args.mask_path}
+            known = torch.stack([files[f] for f in paths])
+        else:
+            known = load(paths)
+        trainer.inpaint(known, batch_size=args.sample_batch_size,
                         hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True,
                         resample=args.resample, jump_length=args.jump_length, **seed_kw)
     elif args.mode == 'outpaint':
-        trainer.outpaint(scale_mul, anchor=tuple(args.anchor), batch_size=args.sample_batch_size,
+        anchor = job_values(args.anchor, args.sample_batch_size)
+        anchor = [tuple(a) for a in anchor] if isinstance(args.anchor, Jobs) else tuple(anchor)
+        trainer.outpaint(scale_mul, anchor=anchor, batch_size=args.sample_batch_size,
                          custom_t_list=sample_t_list, save_unbatched=True, resample=args.resample,
                          jump_length=args.jump_length, **seed_kw)
     elif args.mode == 'paint2image':
         import numpy as np
         from PIL import Image
-        path = args.input_image if os.path.exists(args.input_image) else os.path.join(args.dataset_folder, args.input_image)
         h, w = ms_diffusion.target_size(n_scales - 1, scale_mul)
-        pic = np.asarray(Image.open(path).convert("RGB").resize((w, h), Image.LANCZOS), dtype=np.float32)
-        layout = torch.from_numpy(pic.transpose(2, 0, 1).copy()).div(255).mul(2).sub(1)
-        trainer.paint2image(layout, batch_size=args.sample_batch_size, down=args.layout_down, strength=args.layout_strength,
+
+        def load(name):
+            path = name if os.path.exists(name) else os.path.join(args.dataset_folder, name)
+            pic = np.asarray(Image.open(path).convert("RGB").resize((w, h), Image.LANCZOS), dtype=np.float32)
+            return torch.from_numpy(pic.transpose(2, 0, 1).copy()).div(255).mul(2).sub(1)
+
+        names = job_values(args.input_image, args.sample_batch_size)
+        if isinstance(names, list):                                        # one picture per sample
+            files = {f: load(f) for f in args.input_image}
+            layout = torch.stack([files[f] for f in names])
+        else:
+            layout = load(names)
+        trainer.paint2image(layout, batch_size=args.sample_batch_size, down=args.layout_down,
+                            strength=job_values(args.layout_strength, args.sample_batch_size),
                             t_min=args.layout_t_min, scales=args.layout_scales, scale_mul=scale_mul,
                             custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
     else:

@@ -28,6 +28,7 @@ ABI_SYMBOLS = (
     "sinddm_debug_head_path", "sinddm_debug_head_offsets", "sinddm_debug_head", "sinddm_debug_routes",
     "sinddm_sample_chain_resample", "sinddm_reverse_step_jump",
     "sinddm_sample_chain_layout", "sinddm_layout_delta", "sinddm_reverse_step_layout",
+    "sinddm_sample_chain_batch",
 )
 
 
@@ -73,6 +74,13 @@ class LayoutOpts(C.Structure):
     """Mirror of `sinddm_layout_opts` (include/sinddm_hip.h): `layout` / `delta` device pointers, `down` the block size N, `g`
     a HOST array of one strength per step of the call."""
     _fields_ = [("layout", C.c_void_p), ("down", C.c_int), ("g", C.POINTER(C.c_float)), ("delta", C.c_void_p)]
+
+
+class BatchOpts(C.Structure):
+    """Mirror of `sinddm_batch_opts` (include/sinddm_hip.h): which map families hold one slice per sample, and the device
+    pointer of the per-sample layout gains or None."""
+    _fields_ = [("edit_per_sample", C.c_int), ("keep_mask_per_sample", C.c_int), ("keep_x0_per_sample", C.c_int),
+                ("layout_per_sample", C.c_int), ("layout_gain", C.c_void_p)]
 
 
 class SinddmError(RuntimeError):
@@ -125,6 +133,8 @@ def load() -> C.CDLL:
                                                      C.POINTER(ResampleOpts)]),
         "sinddm_sample_chain_layout": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
                                                    C.POINTER(ResampleOpts), C.POINTER(LayoutOpts)]),
+        "sinddm_sample_chain_batch": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
+                                                  C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts)]),
         "sinddm_layout_delta": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, i, i, i, p]),
         "sinddm_reverse_step_layout": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, f, i, p, p, p, p, f, f, i, i, i, i, i, i, i,
                                            p]),

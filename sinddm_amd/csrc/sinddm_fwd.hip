@@ -5,6 +5,7 @@
 #include "conv_wh.h"
 #include "internal.h"
 #include "step_tail.h"
+#include "batch_check.h"
 #include <type_traits>
 namespace sinddm {
 
@@ -1306,16 +1307,22 @@ static LayoutArgs layout_geom(int Hc, int Wc, int halo_y, int halo_x, int N, boo
     return g;
 }
 
-// block deltas of `Bn` samples (layout_delta_kernel): g.D is written
-static int layout_delta_launch(const float* x_t, const float* eps, const float* x_tilde, const float* layout, const float* edit_w,
-                               const float* edit_c, const sinddm_step_coefs& k, const LayoutArgs& g, int Bn, hipStream_t st) {
+// block deltas of `Bn` samples (layout_delta_kernel): g.D is written; `t` carries the step's scalars, the edit maps and
+// their strides, as for the tail behind it
+static int layout_delta_launch(const float* x_t, const float* eps, const float* x_tilde, const float* layout, const TailArgs& t,
+                               const LayoutArgs& g, int Bn, hipStream_t st) {
+    const float* edit_w = t.ew;
+    const float* edit_c = t.ec;
+    const sinddm_step_coefs& k = t.k;
     const int cols = (256 / g.N) * g.N, bpw = cols / g.N;
     const dim3 grid((unsigned)((g.w + bpw - 1) / bpw), (unsigned)g.h, (unsigned)(Bn * CHANNELS));
     float* D = const_cast<float*>(g.D);
     if (edit_w)
-        hipLaunchKernelGGL(layout_delta_kernel<true>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, D, k, g, cols);
+        hipLaunchKernelGGL(layout_delta_kernel<true>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, t.sew, t.sec, D, k, g,
+                           cols);
     else
-        hipLaunchKernelGGL(layout_delta_kernel<false>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, D, k, g, cols);
+        hipLaunchKernelGGL(layout_delta_kernel<false>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, t.sew, t.sec, D, k, g,
+                           cols);
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
 
@@ -1343,7 +1350,7 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                              uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
-                             const sinddm_layout_opts* lo) {
+                             const sinddm_layout_opts* lo, const sinddm_batch_opts* bo) {
     if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
     if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
     if ((reinterpret_cast<uintptr_t>(sample_seeds) & 7) != 0) return SINDDM_E_BADARG;
@@ -1401,6 +1408,13 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
     }
     NetPlan p = make_plan(dim);
     if (!p.ok) return SINDDM_E_BADSHAPE;
+    // per-sample maps (batch_check.h): the strides of step_tail.h; all 0 without `bo`, and nothing below differs then
+    BatchStrides bs{};
+    if (const int rcb = batch_strides(bo, edit_w, edit_c, keep_m, keep_x0, lo ? lo->layout : nullptr, H, W,
+                                      (H * W) % 4 == 0 && fwd_pitch(p, W) == W, &bs))
+        return rcb;
+    const float* lay_gain = bo && lay_g ? bo->layout_gain : nullptr;     // (read only by a run that pulls, like the rest of `lo`)
+    lay.sl = lay_g ? bs.sl : 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipStream_t sx = static_cast<hipStream_t>(aux_stream);
     const long long n = (long long)B * CHANNELS * H * W;
@@ -1470,6 +1484,7 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
             t.sseeds = sseeds;
             t.ew = edit_w; t.ec = edit_c; t.nz = noise ? noise + (size_t)i * (size_t)n : nullptr;
             t.km = keep_m; t.kx = keep_x0;
+            t.sew = bs.sew; t.sec = bs.sec; t.skm = bs.skm; t.skx = bs.skx;
             t.ka = keep_m ? keep_ab[2 * i] : 1.0f; t.kb = keep_m ? keep_ab[2 * i + 1] : 0.0f;
             const bool jump = jumps && jumps[i].on;            // the step writes eps; step + jump are one kernel behind it
             JumpArgs jp{};
@@ -1488,6 +1503,9 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                 cs.tail = t;
                 cs.tail.b0 = h ? Bh[0] : 0;
                 if (sseeds) cs.tail.sseeds = sseeds + cs.tail.b0;
+                // (per-sample maps: the half's own slices, like its seeds -- the kernels index them with the launch's sample)
+                cs.tail.ew = batch_slice(t.ew, cs.tail.b0, t.sew); cs.tail.ec = batch_slice(t.ec, cs.tail.b0, t.sec);
+                cs.tail.km = batch_slice(t.km, cs.tail.b0, t.skm); cs.tail.kx = batch_slice(t.kx, cs.tail.b0, t.skx);
                 rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
                                       h ? sx : st, nullptr, &cs);
                 if (jump && fuse_tail && rc == 0)
@@ -1495,7 +1513,9 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                 if (pull && fuse_tail && rc == 0) {
                     LayoutArgs lh = lay;                       // (the half's own slice of the scratch)
                     lh.D = lo->delta + (size_t)cs.tail.b0 * CHANNELS * lay.h * lay.w;
-                    rc = layout_delta_launch(cur + o, eps + o, cs.x_tilde, lo->layout, edit_w, edit_c, t.k, lh, Bh[h], h ? sx : st);
+                    lh.gain = lay_gain ? lay_gain + cs.tail.b0 : nullptr;
+                    rc = layout_delta_launch(cur + o, eps + o, cs.x_tilde, batch_slice(lo->layout, cs.tail.b0, lay.sl), cs.tail, lh,
+                                             Bh[h], h ? sx : st);
                     if (rc == 0)
                         rc = layout_step_launch(cur + o, eps + o, cs.x_tilde, nxt + o, cs.tail, lh, Bh[h], CHANNELS * H * W, H * W,
                                                 h ? sx : st);
@@ -1514,7 +1534,8 @@ static int sample_chain_impl(const float* params, const float* packed, float* x,
                     if ((rc = jump_launch(cur, eps, x_tilde, nxt, t, jp, B, chw, H * W, st)) != 0) break;
                 } else if (pull) {
                     lay.D = lo->delta;
-                    if ((rc = layout_delta_launch(cur, eps, x_tilde, lo->layout, edit_w, edit_c, t.k, lay, B, st)) != 0) break;
+                    lay.gain = lay_gain;
+                    if ((rc = layout_delta_launch(cur, eps, x_tilde, lo->layout, t, lay, B, st)) != 0) break;
                     if ((rc = layout_step_launch(cur, eps, x_tilde, nxt, t, lay, B, chw, H * W, st)) != 0) break;
                 } else {
                     tail_dispatch(t, [&](auto E, auto N, auto K) {
@@ -1552,7 +1573,7 @@ int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, f
                            uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                            void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1560,7 +1581,7 @@ int sinddm_sample_chain_tile(const float* params, const float* packed, float* x,
                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_keep(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1569,7 +1590,7 @@ int sinddm_sample_chain_keep(const float* params, const float* packed, float* x,
                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                              const sinddm_keep_opts* keep) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1578,7 +1599,7 @@ int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x
                               void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                               const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_resample(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1587,7 +1608,7 @@ int sinddm_sample_chain_resample(const float* params, const float* packed, float
                                  void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                                  const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, nullptr, nullptr);
 }
 
 int sinddm_sample_chain_layout(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1596,8 +1617,19 @@ int sinddm_sample_chain_layout(const float* params, const float* packed, float* 
                                void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
                                const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
                                const sinddm_layout_opts* lo) {
+    return sinddm_sample_chain_batch(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H,
+                                     W, ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs,
+                                     lo, nullptr);
+}
+
+int sinddm_sample_chain_batch(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
+                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
+                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
+                              const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
+                              const sinddm_layout_opts* lo, const sinddm_batch_opts* bo) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, lo);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, lo, bo);
 }
 
 int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1605,7 +1637,7 @@ int sinddm_sample_chain2(const float* params, const float* packed, float* x, flo
                          uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                          void* aux_stream, int* result_in_alt) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_sample_chain(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
@@ -1613,7 +1645,7 @@ int sinddm_sample_chain(const float* params, const float* packed, float* x, floa
                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
                         int* result_in_alt) {
     return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
+                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
@@ -1667,7 +1699,9 @@ int sinddm_layout_delta(const float* x_t, const float* eps, const float* x_tilde
     if ((long long)B * CHANNELS > 65535 || (H + down - 1) / down > 65535) return SINDDM_E_BADSHAPE;
     LayoutArgs g = layout_geom(H, W, halo_y, halo_x, down, false, false);
     g.D = delta;
-    return layout_delta_launch(x_t, eps, x_tilde, layout, edit_w, edit_c, *coefs, g, B, static_cast<hipStream_t>(stream));
+    TailArgs t{};
+    t.k = *coefs; t.ew = edit_w; t.ec = edit_c;
+    return layout_delta_launch(x_t, eps, x_tilde, layout, t, g, B, static_cast<hipStream_t>(stream));
 }
 
 int sinddm_reverse_step_layout(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,

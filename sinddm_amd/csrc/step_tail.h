@@ -6,21 +6,29 @@
 
 namespace sinddm {
 
-// What every tail kernel takes besides its tensors: the step's scalars and its three options.  Maps and draws are shared
-// by all samples of the batch; a NULL pointer is read by no instantiation that could see it (the host picks EDIT / NOISE /
-// KEEP from the pointers).
+// What every tail kernel takes besides its tensors: the step's scalars and its three options.  A NULL pointer is read by no
+// instantiation that could see it (the host picks EDIT / NOISE / KEEP from the pointers).  Each map family is shared by all
+// samples of the batch (its stride 0) or PER SAMPLE: sample b of THIS launch reads its slice at  ptr + b * stride  (stride in
+// floats: the family's size).  Like `sseeds`, the pointers are those of the launch's first sample: the host offsets them
+// for the second half-batch, and no kernel adds b0 to a map index.  The stride is address arithmetic only: the shared
+// call computes what it always did.
 struct TailArgs {
     sinddm_step_coefs k;
     int b0;                             // index of this launch's first sample inside the whole batch (seed / nz are keyed on the whole batch)
     unsigned long long seed, step;      // Philox key and stream of this step's draws
     const unsigned long long* sseeds;   // per-sample seeds of THIS launch's samples (device) or NULL -> (seed, b0)
-    const float* ew;                    // EDIT   ROI edit maps, HW / 3*HW floats
+    const float* ew;                    // EDIT   ROI edit maps, HW / 3*HW floats per slice
     const float* ec;
     const float* nz;                    // NOISE  this step's recorded draws for the WHOLE batch (B_total*3*HW floats)
-    const float* km;                    // KEEP   known-region mask / known image, HW / 3*HW floats
+    const float* km;                    // KEEP   known-region mask / known image, HW / 3*HW floats per slice
     const float* kx;
     float ka, kb;                       // KEEP   this step's forward scalars of the known image (sinddm_keep_opts::ab)
+    int sew, sec, skm, skx;             // per-sample strides of ew / ec / km / kx: 0 (shared) or HW / 3*HW / HW / 3*HW
 };
+// sample b's slice of a map (b is launch-local; the offset is 64-bit, the index inside the slice stays an int)
+__device__ __forceinline__ const float* map_slice(const float* __restrict__ p, long long b, int stride) {
+    return p + (size_t)(b * (long long)stride);
+}
 
 // x_{t-1} mean of one element: predict_start_from_noise + p_mean_variance (normal branch) + q_posterior
 // (reference SinDDM/models.py:306-352,433-447); `w`, `c` = ROI edit map (1, 0 without ROI guidance).
@@ -120,14 +128,23 @@ __device__ __forceinline__ void quad_draw(const float* __restrict__ nzq, bool ve
     }
 }
 
-// one pair of maps for the nv valid lanes of a quad at an arbitrary flat index: `plane` has hw floats, `full` chw, r = the
-// index of the quad's first element inside its sample; the quad may run over a plane's or a sample's end
-__device__ __forceinline__ void quad_maps(const float* __restrict__ plane, const float* __restrict__ full, int r, int nv, int chw,
-                                          int hw, float (&p)[4], float (&f)[4]) {
-    for (int j = 0; j < nv; ++j) {
+// one pair of maps for lanes [jlo, jhi) of a quad at an arbitrary flat index: a slice of `plane` has hw floats, one of `full`
+// chw; `iv` = the launch-local flat index of lane jlo, whose sample is iv / chw.  The quad may run over a plane's or a
+// sample's end: where the index wraps, the slices move on to the next sample's (strides sp / sf; 0: the shared maps again).
+__device__ __forceinline__ void quad_maps(const float* __restrict__ plane, const float* __restrict__ full, int sp, int sf,
+                                          long long iv, int jlo, int jhi, int chw, int hw, float (&p)[4], float (&f)[4]) {
+    const long long b = iv / chw;
+    int r = (int)(iv - b * chw);
+    plane = map_slice(plane, b, sp);
+    full = map_slice(full, b, sf);
+    for (int j = jlo; j < jhi; ++j) {
         p[j] = plane[r % hw];
         f[j] = full[r];
-        r = r + 1 == chw ? 0 : r + 1;
+        if (++r == chw) {
+            r = 0;
+            plane += sp;
+            full += sf;
+        }
     }
 }
 
@@ -148,10 +165,12 @@ __global__ __launch_bounds__(256) void reverse_step_kernel(const float* __restri
                                                            const float* __restrict__ xtil, float* __restrict__ out, TailArgs a,
                                                            long long n, int chw, int hw) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int q = (EDIT || KEEP) ? (int)(i % chw) : 0;
+        const long long b = (EDIT || KEEP) ? i / chw : 0;
+        const int q = (EDIT || KEEP) ? (int)(i - b * chw) : 0;
         const float xb = a.k.mode != 0 ? xtil[i] : 0.0f;
-        out[i] = tail_eval<EDIT, KEEP>(a, xt[i], eps[i], xb, a.nz[i], EDIT ? a.ew[q % hw] : 1.0f, EDIT ? a.ec[q] : 0.0f,
-                                       KEEP ? a.km[q % hw] : 0.0f, KEEP ? a.kx[q] : 0.0f);
+        out[i] = tail_eval<EDIT, KEEP>(a, xt[i], eps[i], xb, a.nz[i], EDIT ? map_slice(a.ew, b, a.sew)[q % hw] : 1.0f,
+                                       EDIT ? map_slice(a.ec, b, a.sec)[q] : 0.0f, KEEP ? map_slice(a.km, b, a.skm)[q % hw] : 0.0f,
+                                       KEEP ? map_slice(a.kx, b, a.skx)[q] : 0.0f);
     }
 }
 
@@ -186,9 +205,9 @@ __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __r
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         if (draw) quad_draw<NOISE>(a.nz + i0, false, nv, key, a.step, (unsigned long long)q, z);
         float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT) quad_maps(a.ew, a.ec, (int)(i0 % chw), nv, chw, hw, w, c);
+        if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, i0, 0, nv, chw, hw, w, c);
         float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) quad_maps(a.km, a.kx, (int)(i0 % chw), nv, chw, hw, m, k0);
+        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, i0, 0, nv, chw, hw, m, k0);
         if (!a.sseeds && nv < 4) {       // the exception above
             for (int j = 0; j < nv; ++j) {
                 const float xb = a.k.mode != 0 ? xtil[i0 + j] : 0.f;
@@ -300,12 +319,12 @@ __global__ __launch_bounds__(256) void reverse_step_jump_kernel(const float* __r
             if (draw) philox_normal4(key, a.step, (unsigned long long)q, z);
             if (draw2) philox_normal4(key, a.step + SINDDM_JUMP_STREAM, (unsigned long long)q, z2);
         }
-        // (the maps have period chw: lanes below jlo read the wrapped index, a valid one, and are not used)
-        const int r0 = (int)(((i0 % chw) + chw) % chw);
+        // (lanes below jlo keep the neutral maps and are not used)
+        const long long iv = i0 + jlo;                      // the first valid lane: >= 0, its sample is iv / chw
         float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT) quad_maps(a.ew, a.ec, r0, jhi, chw, hw, w, c);
+        if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, iv, jlo, jhi, chw, hw, w, c);
         float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) quad_maps(a.km, a.kx, r0, jhi, chw, hw, m, k0);
+        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, jlo, jhi, chw, hw, m, k0);
         float x[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f};
         quad_load(xt + i0, jlo, jhi, x);
         quad_load(eps + i0, jlo, jhi, e);
@@ -337,6 +356,8 @@ struct LayoutArgs {
     int Hc, Wc, hy, hx;                 // the centre and the halo
     int h, w;                           // ceil(Hc / N), ceil(Wc / N)
     int wrap_y, wrap_x;                 // the axis wraps (always with a halo on it)
+    int sl;                             // per-sample stride of the layout picture: 0 (shared) or 3 * H * W
+    const float* gain;                  // per-sample factor on g of THIS launch's samples (device) or NULL
 };
 
 // `xp` of reverse_step_mean after the ROI edit, NOT clamped (x0 itself in mode 0): what the pull acts on
@@ -346,6 +367,7 @@ __device__ __forceinline__ float step_xp(const sinddm_step_coefs& k, float x, fl
     return edit ? w * xp + c : xp;
 }
 
+// `lay` is one picture for the batch or one per sample (g.sl), the edit maps likewise (sew / sec).
 // One workgroup owns block row Y of one (sample, channel) plane over `cols` = (256 / N) * N centre columns, i.e. whole
 // blocks.  A thread owns a column: it adds its up to N rows top to bottom in a register (a wave reads 64 consecutive floats
 // of a row), the column sums meet in LDS, and one thread per block adds its N columns left to right.  No atomics, and the
@@ -355,12 +377,19 @@ template <bool EDIT>
 __global__ __launch_bounds__(256) void layout_delta_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                            const float* __restrict__ xtil, const float* __restrict__ lay,
                                                            const float* __restrict__ ew, const float* __restrict__ ec,
-                                                           float* __restrict__ D, sinddm_step_coefs k, LayoutArgs g, int cols) {
+                                                           int sew, int sec, float* __restrict__ D, sinddm_step_coefs k,
+                                                           LayoutArgs g, int cols) {
     __shared__ float col[256];
     const int bc = blockIdx.z, ch = bc % 3, Y = blockIdx.y;
     const int xc = blockIdx.x * cols + threadIdx.x;
     const int y0 = Y * g.N, y1 = min(y0 + g.N, g.Hc);
     const size_t plane = (size_t)g.H * g.W;
+    const int bs = bc / 3;                                  // the sample: its own layout / edit slices when they are per sample
+    lay = map_slice(lay, bs, g.sl);
+    if (EDIT) {
+        ew = map_slice(ew, bs, sew);
+        ec = map_slice(ec, bs, sec);
+    }
     float s = 0.0f;
     if ((int)threadIdx.x < cols && xc < g.Wc) {
         for (int y = y0; y < y1; ++y) {
@@ -405,7 +434,8 @@ __device__ __forceinline__ void layout_axis(int v, int halo, int size, int N, in
     }
 }
 
-// g * U(D) at element r (index inside its sample) of launch-local sample b
+// g * U(D) at element r (index inside its sample) of launch-local sample b; with a per-sample gain the strength is the fp32
+// product g * gain[b], formed once, in place of g
 __device__ __forceinline__ float layout_pull(const LayoutArgs& g, int b, int r) {
     const int hw = g.H * g.W;
     const int ch = r / hw, p = r - ch * hw, y = p / g.W, x = p - y * g.W;
@@ -415,7 +445,8 @@ __device__ __forceinline__ float layout_pull(const LayoutArgs& g, int b, int r) 
     layout_axis(x, g.hx, g.Wc, g.N, g.w, g.wrap_x != 0, ix0, ix1, lx);
     const float* __restrict__ d = g.D + ((size_t)b * 3 + ch) * g.h * g.w;
     const float tl = d[iy0 * g.w + ix0], tr = d[iy0 * g.w + ix1], bl = d[iy1 * g.w + ix0], br = d[iy1 * g.w + ix1];
-    return g.g * ((1.0f - ly) * ((1.0f - lx) * tl + lx * tr) + ly * ((1.0f - lx) * bl + lx * br));
+    const float gb = g.gain ? g.g * g.gain[b] : g.g;
+    return gb * ((1.0f - ly) * ((1.0f - lx) * tl + lx * tr) + ly * ((1.0f - lx) * bl + lx * br));
 }
 
 // The conditioned step, over ROWS exactly like reverse_step_jump_kernel (rows of a key's stream, partial first / last quads
@@ -441,13 +472,12 @@ __global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* _
             if (NOISE) quad_load(a.nz + gofs + i0, jlo, jhi, z);
             else philox_normal4(key, a.step, (unsigned long long)q, z);
         }
-        const int r0 = (int)(((i0 % chw) + chw) % chw);
+        const long long iv = i0 + jlo;                      // the first valid lane: >= 0, its sample is iv / chw
         float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT) quad_maps(a.ew, a.ec, r0, jhi, chw, hw, w, c);
+        if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, iv, jlo, jhi, chw, hw, w, c);
         float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) quad_maps(a.km, a.kx, r0, jhi, chw, hw, m, k0);
+        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, jlo, jhi, chw, hw, m, k0);
         // the first valid lane's sample and index inside it; the lanes behind it may run over the sample's end
-        const long long iv = i0 + jlo;
         int b = (int)(iv / chw), r = (int)(iv - (long long)b * chw);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -479,7 +509,7 @@ __global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* _
 // input, or FinalConvEps, the final 1x1 conv on block 4's output (shapes the head does not take).  Everything below the
 // call is the tail, whichever stage ran.  A block row owns one sample.  EDIT / NOISE / KEEP: a thread's four pixels are contiguous
 // and 16-byte aligned in the maps and in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller),
-// so all of them are read as f32x4.
+// so all of them are read as f32x4 -- a per-sample slice starts a multiple of HW floats behind its pointer, aligned as well.
 template <bool EDIT, bool NOISE, bool KEEP, class EPS>
 __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, const float* __restrict__ xt,
                                                                       const float* __restrict__ xtil, float* __restrict__ out,
@@ -491,9 +521,9 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, c
     f32x4 e[3];
     eps(b, p >> 2, e);
     f32x4 mw{1.f, 1.f, 1.f, 1.f};
-    if (EDIT) mw = *reinterpret_cast<const f32x4*>(t.ew + p);
+    if (EDIT) mw = *reinterpret_cast<const f32x4*>(map_slice(t.ew, b, t.sew) + p);
     f32x4 mk{0.f, 0.f, 0.f, 0.f};
-    if (KEEP) mk = *reinterpret_cast<const f32x4*>(t.km + p);
+    if (KEEP) mk = *reinterpret_cast<const f32x4*>(map_slice(t.km, b, t.skm) + p);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + p;
@@ -504,14 +534,14 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, c
         f32x4 xb{0.f, 0.f, 0.f, 0.f};
         if (t.k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
         f32x4 mc{0.f, 0.f, 0.f, 0.f};
-        if (EDIT) mc = *reinterpret_cast<const f32x4*>(t.ec + (size_t)c * HW + p);
+        if (EDIT) mc = *reinterpret_cast<const f32x4*>(map_slice(t.ec, b, t.sec) + (size_t)c * HW + p);
         // (two passes, not tail_eval<EDIT, KEEP>: in one pass the compiler contracts the blend into other fused multiply-adds
         // than this kernel always had -- profiles/NOTES_r12.md)
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = tail_eval<EDIT, false>(t, x[j], e[c][j], xb[j], z[j], mw[j], mc[j], 0.f, 0.f);
         if (KEEP) {
-            const f32x4 k0 = *reinterpret_cast<const f32x4*>(t.kx + (size_t)c * HW + p);
+            const f32x4 k0 = *reinterpret_cast<const f32x4*>(map_slice(t.kx, b, t.skx) + (size_t)c * HW + p);
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = keep_blend(t.k, o[j], z[j], xb[j], mk[j], k0[j], t.ka, t.kb);
         }
@@ -539,6 +569,10 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS 
     eps(b, q, e);
     const int nv = W - x;                                   // valid pixels of the quad (>= 1)
     const bool draw = tail_draws<KEEP>(t);
+    const float* __restrict__ ew = EDIT ? map_slice(t.ew, b, t.sew) : nullptr;     // sample b's maps (block-uniform)
+    const float* __restrict__ ec = EDIT ? map_slice(t.ec, b, t.sec) : nullptr;
+    const float* __restrict__ km = KEEP ? map_slice(t.km, b, t.skm) : nullptr;
+    const float* __restrict__ kx = KEEP ? map_slice(t.kx, b, t.skx) : nullptr;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + (long long)y * W + x;
@@ -563,12 +597,12 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS 
                 const float xb = t.k.mode != 0 ? xtil[i0 + j] : 0.f;
                 float mw = 1.f, mc = 0.f;
                 if (EDIT) {
-                    mw = t.ew[pp];
-                    mc = t.ec[(size_t)c * HW + pp];
+                    mw = ew[pp];
+                    mc = ec[(size_t)c * HW + pp];
                 }
                 // (the blend after the step, its maps read in place, as this kernel always had it: see the plain-row kernel)
                 const float o = tail_eval<EDIT, false>(t, xt[i0 + j], e[c][j], xb, z, mw, mc, 0.f, 0.f);
-                out[i0 + j] = KEEP ? keep_blend(t.k, o, z, xb, t.km[pp], t.kx[(size_t)c * HW + pp], t.ka, t.kb) : o;
+                out[i0 + j] = KEEP ? keep_blend(t.k, o, z, xb, km[pp], kx[(size_t)c * HW + pp], t.ka, t.kb) : o;
             }
         }
     }

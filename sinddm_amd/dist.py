@@ -86,6 +86,14 @@ def shard_seeds(seeds):
     return seeds[o:o + local_batch(len(seeds))]
 
 
+def shard_rows(t):
+    """This rank's samples of a per-sample `(B_global, ...)` tensor or length-B_global sequence (maps, gains, box lists): rows
+    shard_offset : shard_offset + local_batch, the boundaries of `shard_seeds`.  The whole of it on a single process."""
+    n = int(t.shape[0]) if isinstance(t, torch.Tensor) else len(t)
+    o = shard_offset(n)
+    return t[o:o + local_batch(n)]
+
+
 def allreduce_sum_(t: torch.Tensor, force: bool = False) -> torch.Tensor:
     """In-place SUM all-reduce (identity on a single process).  With the gloo backend device tensors are
     staged through the host, so the 2-process tests can share one GPU; nccl (RCCL) reduces in place."""

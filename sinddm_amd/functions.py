@@ -145,12 +145,19 @@ def _area_weights(n_out: int, n_in: int) -> np.ndarray:
     return np.maximum(overlap, 0).astype(np.float64) / float(n_in)
 
 
-def keep_mask_pyramid(mask, sizes, hard: bool = True) -> List[torch.Tensor]:
+def keep_mask_pyramid(mask, sizes, hard: bool = True, batch: bool = False) -> List[torch.Tensor]:
     """A full-resolution {0,1} mask (H, W), 1 = known, brought to every scale by area averaging: one fp32 (h, w) tensor
     per entry of `sizes` ((h, w) pairs), on the mask's device.  `hard` keeps a pixel only if its whole footprint is known
     (average >= 1 - 1e-6; the smallest share of a footprint pixel is 1 / H): a coarse pixel that mixes known and unknown
-    content is generated, never pinned.  hard=False returns the averages (the step kernels blend with them)."""
+    content is generated, never pinned.  hard=False returns the averages (the step kernels blend with them).
+    `batch`: the mask is a (B, H, W) stack, one job per sample, and the tensors are (B, h, w): row b is what the call returns
+    for mask b alone.  It has to be asked for: a 3-d mask handed over by mistake (an RGB picture) stays an error."""
     m = torch.as_tensor(mask)
+    if batch:
+        if m.dim() != 3 or m.shape[0] < 1:
+            raise ValueError(f"keep_mask_pyramid: a batch of masks must be (B, H, W), got {tuple(m.shape)}")
+        rows = [keep_mask_pyramid(m[b], sizes, hard) for b in range(m.shape[0])]
+        return [torch.stack([r[i] for r in rows]) for i in range(len(rows[0]))]
     if m.dim() != 2:
         raise ValueError(f"keep_mask_pyramid: mask must be (H, W), got {tuple(m.shape)}")
     device = m.device
@@ -223,6 +230,22 @@ def layout_strengths(t_seq: Sequence[int], strength: float = 1.0, t_min: int = 0
     return [g if int(t) >= int(t_min) else 0.0 for t in t_seq]
 
 
+def split_strength(strength, batch_size: int):
+    """`strength` of paint2image -> (shared per-step strength, per-sample gains or None).  One number: (it, None).  A
+    sequence of `batch_size` values in [0, 1]: their maximum in fp32 and value / maximum per sample (fp32; all ones when the
+    maximum is 0), so that the step's strength for sample b, the fp32 product, is the sample's own value to one rounding."""
+    if np.ndim(strength) == 0:
+        return float(strength), None
+    v = np.asarray(strength, dtype=np.float32).reshape(-1)
+    if v.shape[0] != int(batch_size):
+        raise ValueError(f"paint2image: {v.shape[0]} strengths for batch_size={int(batch_size)}")
+    if not bool(np.all((v >= 0.0) & (v <= 1.0))):
+        raise ValueError(f"paint2image: strength {v.tolist()} outside [0, 1]")
+    top = np.float32(v.max())
+    gain = v / top if top > 0 else np.ones_like(v)
+    return float(top), [float(x) for x in gain]
+
+
 def layout_blocks(n_finest: int, scale_factor: float, n_scales: int) -> List[int]:
     """Block size per scale for a block of `n_finest` pixels at the finest one: N_s = max(1, round(N / f^(n_scales-1-s))),
     the same physical band at every scale.  1 <= n_finest <= 64 (the kernels' range)."""
@@ -237,10 +260,13 @@ def layout_blocks(n_finest: int, scale_factor: float, n_scales: int) -> List[int
 def _layout_pyramid(layout, sizes) -> List[torch.Tensor]:
     """A (3, H, W) layout picture brought to every (h, w) of `sizes` by area averaging (`_area_weights`: every output
     pixel is a convex combination, so a constant image stays constant and the range is kept): fp32 tensors on the layout's
-    device."""
+    device.  A (B, 3, H, W) stack of pictures gives (B, 3, h, w) tensors: row b is what the call returns for picture b alone."""
     lay = torch.as_tensor(layout)
+    if lay.dim() == 4 and lay.shape[0] > 0 and lay.shape[1] == 3:
+        rows = [_layout_pyramid(lay[b], sizes) for b in range(lay.shape[0])]
+        return [torch.stack([r[i] for r in rows]) for i in range(len(rows[0]))]
     if lay.dim() != 3 or lay.shape[0] != 3:
-        raise ValueError(f"_layout_pyramid: layout must be (3, H, W), got {tuple(lay.shape)}")
+        raise ValueError(f"_layout_pyramid: layout must be (3, H, W) or (B, 3, H, W), got {tuple(lay.shape)}")
     device = lay.device
     full = lay.detach().to("cpu", torch.float64).numpy()
     out = []

@@ -532,6 +532,17 @@ class MultiScaleGaussianDiffusion(nn.Module):
         self.layout_down = {}
         self.layout_strength = 1.0
         self.layout_t_min = 0
+        # per-sample conditioning: a batch of B independent edit jobs per run.  Every map above may carry a leading batch
+        # dimension -- keep_maps[s] = (mask (H,W) or (B,H,W), x0 (3,H,W) or (B,3,H,W)), the two independent of each other;
+        # layout_maps[s] (3,H,W) or (B,3,H,W) -- and sample b is then conditioned on row b alone, whatever its position in
+        # the batch, the two-stream split or the rank that runs it (sinddm_sample_chain_batch).  `layout_gain`: None or B
+        # floats in [0, 1], sample b's factor on the layout strength.  `roi_bbs_batch` / `roi_target_patch_batch`: None or
+        # B box lists / B patch lists (each what `roi_bbs` / `roi_target_patch` is for the whole batch; without the
+        # second, every sample takes `roi_target_patch`).  The t schedule, `resample`, `tile`, `layout_down` and
+        # `layout_t_min` stay one per run.
+        self.layout_gain = None
+        self.roi_bbs_batch = None
+        self.roi_target_patch_batch = None
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -671,6 +682,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
 
     def roi_patch_modification(self, x_recon, scale=0, eta=0.8):            # models.py:291-298 (in place, like it)
         w, c = self.roi_edit_maps(scale, x_recon.shape[-2], x_recon.shape[-1], x_recon.device, eta)
+        if w.dim() == 3:                                                    # per-sample maps (roi_bbs_batch)
+            if w.shape[0] != x_recon.shape[0]:
+                raise ValueError(f"roi_bbs_batch has {w.shape[0]} box lists, the batch {x_recon.shape[0]} samples")
+            x_recon.mul_(w[:, None]).add_(c)
+            return x_recon
         x_recon.mul_(w[None, None]).add_(c[None])
         return x_recon
 
@@ -678,21 +694,41 @@ class MultiScaleGaussianDiffusion(nn.Module):
         """The reference's sequential ROI blends `x[box] = eta * patch + (1 - eta) * x[box]` over all boxes
         (models.py:291-298) composed into ONE per-pixel affine map x -> w * x + c (w: (H,W), c: (3,H,W)); this is
         what the step kernels apply (`sinddm_sample_chain_ex` with edit maps; `sinddm_reverse_step_edit` on the
-        step-by-step route).  Cached per (scale, size, boxes)."""
-        key = (int(scale), int(H), int(W), float(eta), tuple(tuple(int(v) for v in bb) for bb in self.roi_bbs),
-               id(self.roi_target_patch[scale]))
+        step-by-step route).  Cached per (scale, size, boxes).  With `roi_bbs_batch` set the maps are per sample,
+        (B,H,W) and (B,3,H,W): row b is built from roi_bbs_batch[b] (and roi_target_patch_batch[b]) exactly as the shared
+        pair is built from `roi_bbs`."""
+        boxes = lambda bbs: tuple(tuple(int(v) for v in bb) for bb in bbs)
+        if self.roi_bbs_batch is not None:
+            pb = self.roi_target_patch_batch
+            if pb is not None and len(pb) != len(self.roi_bbs_batch):
+                raise ValueError(f"roi_target_patch_batch has {len(pb)} entries, roi_bbs_batch {len(self.roi_bbs_batch)}")
+            patches = [(pb[b] if pb is not None else self.roi_target_patch)[scale] for b in range(len(self.roi_bbs_batch))]
+            key = (int(scale), int(H), int(W), float(eta), tuple(boxes(bbs) for bbs in self.roi_bbs_batch),
+                   tuple(id(pt) for pt in patches))
+            if self._roi_cache.get("key") == key:
+                return self._roi_cache["w"], self._roi_cache["c"]
+            rows = [self._roi_maps_one(scale, H, W, device, eta, bbs, pt) for bbs, pt in zip(self.roi_bbs_batch, patches)]
+            self._roi_cache = {"key": key, "w": torch.stack([r[0] for r in rows]).contiguous(),
+                               "c": torch.stack([r[1] for r in rows]).contiguous()}
+            return self._roi_cache["w"], self._roi_cache["c"]
+        key = (int(scale), int(H), int(W), float(eta), boxes(self.roi_bbs), id(self.roi_target_patch[scale]))
         if self._roi_cache.get("key") == key:
             return self._roi_cache["w"], self._roi_cache["c"]
-        w = torch.ones((H, W), device=device, dtype=torch.float32)
-        c = torch.zeros((self.channels, H, W), device=device, dtype=torch.float32)
-        for bb in self.roi_bbs:                                             # bounding box is [y, x, h, w]
-            bb = [int(bb_i / np.power(self.scale_factor, self.n_scales - scale - 1)) for bb_i in bb]
-            y, x, h, ww = bb
-            patch = F.interpolate(self.roi_target_patch[scale].to(device=device, dtype=torch.float32), size=(h, ww))[0]
-            c[:, y:y + h, x:x + ww] = eta * patch + (1 - eta) * c[:, y:y + h, x:x + ww]
-            w[y:y + h, x:x + ww] *= (1 - eta)
+        w, c = self._roi_maps_one(scale, H, W, device, eta, self.roi_bbs, self.roi_target_patch[scale])
         self._roi_cache = {"key": key, "w": w.contiguous(), "c": c.contiguous()}
         return self._roi_cache["w"], self._roi_cache["c"]
+
+    def _roi_maps_one(self, scale: int, H: int, W: int, device, eta: float, bbs, target_patch):
+        """(w, c) of one box list and the scale's target patch: one job's maps."""
+        w = torch.ones((H, W), device=device, dtype=torch.float32)
+        c = torch.zeros((self.channels, H, W), device=device, dtype=torch.float32)
+        for bb in bbs:                                                      # bounding box is [y, x, h, w]
+            bb = [int(bb_i / np.power(self.scale_factor, self.n_scales - scale - 1)) for bb_i in bb]
+            y, x, h, ww = bb
+            patch = F.interpolate(target_patch.to(device=device, dtype=torch.float32), size=(h, ww))[0]
+            c[:, y:y + h, x:x + ww] = eta * patch + (1 - eta) * c[:, y:y + h, x:x + ww]
+            w[y:y + h, x:x + ww] *= (1 - eta)
+        return w, c
 
     def _clip_guidance(self, x_recon, t0: int, s: int, clip_denoised: bool):
         """The CLIP-guidance block of p_mean_variance (models.py:367-421): the score's gradient is taken with respect to
@@ -833,7 +869,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
 
     def _keep_entry(self, s: int, img: torch.Tensor):
         """The (mask, x0) pair of `keep_maps` for scale s, checked against the running sample (the library takes raw
-        pointers: a mismatching map would be read out of bounds), or None."""
+        pointers: a mismatching map would be read out of bounds), or None.  Either may carry a leading batch dimension,
+        which must be the running batch."""
         if self.keep_maps is None:
             return None
         if self.clip_guided_sampling:
@@ -843,11 +880,12 @@ class MultiScaleGaussianDiffusion(nn.Module):
         if entry is None:
             return None
         m, k0 = entry
-        H, W = int(img.shape[-2]), int(img.shape[-1])
+        H, W, B = int(img.shape[-2]), int(img.shape[-1]), int(img.shape[0])
         for name, t, shape in (("mask", m, (H, W)), ("x0", k0, (int(img.shape[1]), H, W))):
-            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != img.device:
+            if tuple(t.shape) not in (shape, (B,) + shape) or t.dtype != torch.float32 or t.device != img.device:
                 raise _lib.SinddmError(f"keep_maps[{int(s)}] {name} {tuple(t.shape)} {t.dtype} {t.device} does not match the "
-                                       f"running sample {tuple(img.shape)} {img.dtype} {img.device} (expected {shape} float32)")
+                                       f"running sample {tuple(img.shape)} {img.dtype} {img.device} (expected {shape} or "
+                                       f"{(B,) + shape} float32)")
         return m.contiguous(), k0.contiguous()
 
     def _layout_entry(self, s: int, img: torch.Tensor):
@@ -862,9 +900,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
         if lay is None:
             return None
         shape = (int(img.shape[1]), int(img.shape[-2]), int(img.shape[-1]))
-        if shape[0] != 3 or tuple(lay.shape) != shape or lay.dtype != torch.float32 or lay.device != img.device:
+        bshape = (int(img.shape[0]),) + shape                  # (one picture per sample)
+        if shape[0] != 3 or tuple(lay.shape) not in (shape, bshape) or lay.dtype != torch.float32 or lay.device != img.device:
             raise _lib.SinddmError(f"layout_maps[{int(s)}] {tuple(lay.shape)} {lay.dtype} {lay.device} does not match the "
-                                   f"running sample {tuple(img.shape)} {img.dtype} {img.device} (expected {shape} float32)")
+                                   f"running sample {tuple(img.shape)} {img.dtype} {img.device} (expected {shape} or {bshape} "
+                                   f"float32)")
         per = lambda v: v.get(int(s), 0) if isinstance(v, dict) else v
         if int(s) not in self.layout_down:
             raise ValueError(f"layout_down has no block size for scale {int(s)}")
@@ -878,6 +918,18 @@ class MultiScaleGaussianDiffusion(nn.Module):
         if self._resample_cfg() is not None:
             raise NotImplementedError("layout_maps with resample: the layout pull inside a resampling jump is not built")
         return lay.contiguous(), N, g, t_min
+
+    def _layout_gain_for(self, B: int, device) -> Optional[torch.Tensor]:
+        """`layout_gain` as B fp32 values on `device`, validated against the running batch, or None."""
+        if self.layout_gain is None:
+            return None
+        g = np.asarray(self.layout_gain.detach().cpu() if isinstance(self.layout_gain, torch.Tensor) else self.layout_gain,
+                       dtype=np.float32).reshape(-1)
+        if g.shape[0] != int(B):
+            raise ValueError(f"layout_gain has {g.shape[0]} values, the batch {int(B)} samples")
+        if not bool(np.all((g >= 0.0) & (g <= 1.0))):
+            raise ValueError(f"layout_gain {g.tolist()} outside [0, 1]")
+        return torch.from_numpy(g.copy()).to(device)
 
     def _tile_halo(self) -> Tuple[int, int]:
         """(halo_y, halo_x) in pixels of the `tile` setting: _lib.TILE_HALO on a wrapped axis, 0 elsewhere."""
@@ -924,7 +976,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
         With `layout_maps` set at this scale the run is ONE sinddm_sample_chain_layout call on every route above: the steps
         with t >= layout_t_min run unfused (network, block-delta kernel, layout tail), the others keep their fused tail; the
         draws and `draw_log` entries are those of the run without it.  The step-by-step route goes through
-        sinddm_layout_delta + sinddm_reverse_step_layout."""
+        sinddm_layout_delta + sinddm_reverse_step_layout.
+        With a per-sample map or `layout_gain` (a leading batch dimension on a keep / layout map, `roi_bbs_batch`) the run is
+        ONE sinddm_sample_chain_batch call: the maps are wrapped like shared ones when tiled, the draws and `draw_log` entries
+        are unchanged.  Every other run keeps the entry it takes above.  The step-by-step route makes B = 1 calls of the
+        single-step entries on each sample's slices."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
         lay = self._layout_entry(s, img)                       # (raises with `resample` / CLIP guidance)
@@ -979,6 +1035,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         opts = _lib.ChainOpts()
         if roi:
             ew, ec = self.roi_edit_maps(s, Hc, Wc, x.device)               # (cached on self: alive for the call)
+            if ew.dim() == 3 and ew.shape[0] != B:                         # (raw pointers: B slices are read)
+                raise ValueError(f"roi_bbs_batch has {ew.shape[0]} box lists, the batch {B} samples")
             if tiled:                                                      # (locals of this frame: alive for the call)
                 ew, ec = self._wrap_pad(ew, hy, hx), self._wrap_pad(ec, hy, hx)
             opts.edit_w, opts.edit_c = _lib.ptr(ew), _lib.ptr(ec)
@@ -996,6 +1054,12 @@ class MultiScaleGaussianDiffusion(nn.Module):
                                            for t, l2 in zip(t_seq, jump_to)])
             ropts = _lib.ResampleOpts()
         lopts = None
+        bopts = None
+        gain = self._layout_gain_for(B, x.device) if lay is not None else None
+        per = (int(roi and ew.dim() == 3), int(keep is not None and km.dim() == 3), int(keep is not None and kx.dim() == 4),
+               int(lay is not None and lay[0].dim() == 4))
+        if any(per) or gain is not None:
+            bopts = _lib.BatchOpts(*per, _lib.ptr(gain))               # (`gain`: a local of this frame, alive for the call)
         if lay is not None:
             lay_map = self._wrap_pad(lay[0], hy, hx) if tiled else lay[0]  # (locals of this frame: alive for the call)
             lay_delta = torch.empty(B * 3 * (-(-Hc // lay[1])) * (-(-Wc // lay[1])), dtype=x.dtype, device=x.device)
@@ -1015,7 +1079,16 @@ class MultiScaleGaussianDiffusion(nn.Module):
                     B, Hc, Wc, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts))
             if kopts is not None:
                 kopts.ab = C.cast(C.addressof(ab) + 2 * i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
-            if lopts is not None:
+            if bopts is not None:
+                if lopts is not None:
+                    lopts.g = C.cast(C.addressof(garr) + i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
+                if ropts is not None:
+                    ropts.jumps = C.cast(C.addressof(jumps) + i0 * C.sizeof(_lib.JumpCoefs), C.POINTER(_lib.JumpCoefs))
+                    ropts.noise = _lib.ptr(jump_noise)
+                ref = lambda o: C.byref(o) if o is not None else None
+                _lib.check(lib.sinddm_sample_chain_batch(*args, hy, hx, ref(kopts), _lib.ptr(seeds_dev), ref(ropts), ref(lopts),
+                                                         C.byref(bopts)), "sinddm_sample_chain_batch")
+            elif lopts is not None:
                 lopts.g = C.cast(C.addressof(garr) + i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
                 _lib.check(lib.sinddm_sample_chain_layout(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
                                                           _lib.ptr(seeds_dev), None, C.byref(lopts)), "sinddm_sample_chain_layout")
@@ -1129,63 +1202,70 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
             xt = xt.contiguous()
         out = torch.empty_like(x)
-        if lay is not None and int(t) >= lay[3]:
+        B_, C_, H_, W_ = x.shape
+        pull = lay is not None and int(t) >= lay[3]
+        if pull and jump_to is not None:
+            raise NotImplementedError("a layout pull on a step that is followed by a resampling jump")
+        z2 = self._draw("jump", x.shape, s, t, x.device, step_pos) if jump_to is not None else None
+        ew = ec = None
+        if self.roi_guided_sampling and s < self.n_scales - 1:             # models.py:430-431
+            ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
+        gain = self._layout_gain_for(B_, x.device) if pull else None
+        g = lay[2] if pull else 0.0
+        if ((ew is not None and ew.dim() == 3) or (keep is not None and (keep[0].dim() == 3 or keep[1].dim() == 4))
+                or (pull and lay[0].dim() == 4) or gain is not None):
+            # per-sample maps: the single-step entries with B = 1 on each sample's slices (a cross-check route)
+            if ew is not None and ew.dim() == 3 and ew.shape[0] != B_:
+                raise ValueError(f"roi_bbs_batch has {ew.shape[0]} box lists, the batch {B_} samples")
+            row = lambda v, nd, b: v if v is None or v.dim() == nd else v[b]
+            gains = gain.cpu().numpy() if gain is not None else None
+            for b in range(B_):
+                keep_b = None if keep is None else (row(keep[0], 2, b), row(keep[1], 3, b))
+                lay_b = row(lay[0], 3, b) if pull else None
+                # (the strength the chain's kernel forms: the fp32 product g * gain[b])
+                g_b = float(np.float32(g) * gains[b]) if gains is not None else g
+                sl = lambda v: None if v is None else v[b:b + 1]
+                self._step_tail(sl(x), sl(eps), sl(xt), sl(z), sl(z2), sl(out), k, t, s, keep_b, lay_b, lay[1] if pull else 0, g_b,
+                                row(ew, 2, b), row(ec, 3, b), jump_to)
+            return out
+        self._step_tail(x, eps, xt, z, z2, out, k, t, s, keep, lay[0] if pull else None, lay[1] if pull else 0, g, ew, ec, jump_to)
+        return out
+
+    def _step_tail(self, x, eps, xt, z, z2, out, k, t, s, keep, lay, N, g, ew, ec, jump_to):
+        """The single-step entry that ends a step of `_p_sample_host_t`: `out` is written.  `keep` = (mask, x0) or None, `lay`
+        the layout picture of a conditioned step (block size N, strength g) or None, (ew, ec) the ROI maps or None, `jump_to`
+        the level of a resampling jump (second draw z2) or None -- all shared by the B samples of this call."""
+        lib = _lib.load()
+        B_, C_, H_, W_ = x.shape
+        st = _lib.stream_ptr(x.device)
+        ka, kb = (float(v) for v in self._keep_ab_table()[int(t)]) if keep is not None else (1.0, 0.0)
+        km, kx = (_lib.ptr(keep[0]), _lib.ptr(keep[1])) if keep is not None else (None, None)
+        if lay is not None:
             # the conditioned step: block deltas of (layout - x_recon), then the step with c_eff = ec + g * U(D)
-            if jump_to is not None:
-                raise NotImplementedError("a layout pull on a step that is followed by a resampling jump")
-            B_, C_, H_, W_ = x.shape
-            ew = ec = None
-            if self.roi_guided_sampling and s < self.n_scales - 1:
-                ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
-            ka, kb = (float(v) for v in self._keep_ab_table()[int(t)]) if keep is not None else (1.0, 0.0)
-            N = lay[1]
             delta = torch.empty(B_ * 3 * (-(-H_ // N)) * (-(-W_ // N)), dtype=x.dtype, device=x.device)
-            st = _lib.stream_ptr(x.device)
-            _lib.check(lib.sinddm_layout_delta(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(lay[0]), _lib.ptr(delta),
+            _lib.check(lib.sinddm_layout_delta(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(lay), _lib.ptr(delta),
                                                C.byref(k), _lib.ptr(ew), _lib.ptr(ec), N, B_, H_, W_, 0, 0, st),
                        "sinddm_layout_delta")
             _lib.check(lib.sinddm_reverse_step_layout(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
-                                                      C.byref(k), _lib.ptr(delta), lay[2], N, _lib.ptr(ew), _lib.ptr(ec),
-                                                      _lib.ptr(keep[0]) if keep is not None else None,
-                                                      _lib.ptr(keep[1]) if keep is not None else None, ka, kb, B_, H_, W_, 0, 0,
-                                                      int(bool(self.tile[0])), int(bool(self.tile[1])), st),
+                                                      C.byref(k), _lib.ptr(delta), g, N, _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb,
+                                                      B_, H_, W_, 0, 0, int(bool(self.tile[0])), int(bool(self.tile[1])), st),
                        "sinddm_reverse_step_layout")
-            return out
-        if jump_to is not None:
-            B_, C_, H_, W_ = x.shape
-            z2 = self._draw("jump", x.shape, s, t, x.device, step_pos)
-            ew = ec = None
-            if self.roi_guided_sampling and s < self.n_scales - 1:
-                ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
-            ka, kb = (float(v) for v in self._keep_ab_table()[int(t)]) if keep is not None else (1.0, 0.0)
+        elif jump_to is not None:
             jc = _lib.JumpCoefs(1, *self._jump_table(s)(int(t) - 1, int(jump_to)))
             _lib.check(lib.sinddm_reverse_step_jump(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(z2),
-                                                    _lib.ptr(out), C.byref(k), C.byref(jc), _lib.ptr(ew), _lib.ptr(ec),
-                                                    _lib.ptr(keep[0]) if keep is not None else None,
-                                                    _lib.ptr(keep[1]) if keep is not None else None, ka, kb, B_, C_, H_ * W_,
-                                                    _lib.stream_ptr(x.device)), "sinddm_reverse_step_jump")
-            return out
-        if keep is not None:
-            B_, C_, H_, W_ = x.shape
-            ew = ec = None
-            if self.roi_guided_sampling and s < self.n_scales - 1:
-                ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
-            ka, kb = (float(v) for v in self._keep_ab_table()[int(t)])
+                                                    _lib.ptr(out), C.byref(k), C.byref(jc), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb,
+                                                    B_, C_, H_ * W_, st), "sinddm_reverse_step_jump")
+        elif keep is not None:
             _lib.check(lib.sinddm_reverse_step_keep(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
-                                                    C.byref(k), _lib.ptr(ew), _lib.ptr(ec), _lib.ptr(keep[0]),
-                                                    _lib.ptr(keep[1]), ka, kb, B_, C_, H_ * W_,
-                                                    _lib.stream_ptr(x.device)), "sinddm_reverse_step_keep")
-            return out
-        if self.roi_guided_sampling and s < self.n_scales - 1:             # models.py:430-431
-            B_, C_, H_, W_ = x.shape
-            ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
+                                                    C.byref(k), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb, B_, C_, H_ * W_, st),
+                       "sinddm_reverse_step_keep")
+        elif ew is not None:
             _lib.check(lib.sinddm_reverse_step_edit(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z),
                                                     _lib.ptr(out), C.byref(k), _lib.ptr(ew), _lib.ptr(ec), B_, C_,
-                                                    H_ * W_, _lib.stream_ptr(x.device)), "sinddm_reverse_step_edit")
-            return out
-        _lib.check(lib.sinddm_reverse_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
-                                           C.byref(k), x.numel(), _lib.stream_ptr(x.device)), "sinddm_reverse_step")
-        return out
+                                                    H_ * W_, st), "sinddm_reverse_step_edit")
+        else:
+            _lib.check(lib.sinddm_reverse_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
+                                               C.byref(k), x.numel(), st), "sinddm_reverse_step")
 
     @torch.no_grad()
     def p_sample(self, x, t, s, clip_denoised=True, repeat_noise=False):   # models.py:449-459

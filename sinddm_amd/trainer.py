@@ -297,9 +297,12 @@ class MultiscaleTrainer(object):
         on MI355X); returns the list of per-scale (global) sample batches.
         `seeds`: the GLOBAL list of `batch_size` per-sample noise seeds (`ema_model.sample_seeds` for the duration of the
         call; a rank takes the seeds of its own shard, so the gathered batch holds the images a single process makes, in
-        the same order).  `vary_from_scale` = S: scales >= S use seeds derived per sample (`models.vary_seeds`)."""
+        the same order).  `vary_from_scale` = S: scales >= S use seeds derived per sample (`models.vary_seeds`).
+        Per-sample conditioning on `ema_model` (maps with a leading batch dimension, `layout_gain`, `roi_bbs_batch`) is GLOBAL
+        too: `batch_size` rows, of which a rank takes its own shard's for the duration of the call (`dist.shard_rows`)."""
         em = self.ema_model
         local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=True)
+        local_maps = self._local_batch_maps(batch_size)
         # --- what to run: one (scale, size index, start timestep) triple per stage ---
         scales = list(range(self.n_scales)) if custom_scales is None else list(custom_scales)
         size_idx = list(range(self.n_scales)) if custom_image_size_idxs is None else list(custom_image_size_idxs)
@@ -325,8 +328,11 @@ class MultiscaleTrainer(object):
         mine = sdist.local_batch(batch_size)
         per_scale, cur, shown = [], None, None
         prev_seeds = em.sample_seeds
+        prev_maps = {k: getattr(em, k) for k in local_maps}
         if local_seeds is not None:
             em.sample_seeds = local_seeds
+        for k, v in local_maps.items():
+            setattr(em, k, v)
         try:
             for stage, s in enumerate(scales):
                 if stage > 0:
@@ -344,12 +350,38 @@ class MultiscaleTrainer(object):
                     save_image(shown, str(out_dir / t_tag) + f'_out_s{stage}_{tag}_sm_{stretch[0]}_{stretch[1]}.png', nrow=4)
         finally:
             em.sample_seeds = prev_seeds
+            for k, v in prev_maps.items():
+                setattr(em, k, v)
         if writer and save_unbatched and shown is not None:
             single_dir = Path(str(self.results_folder / f'final_samples_unbatched_{tag}'))
             single_dir.mkdir(parents=True, exist_ok=True)
             for b, one in enumerate(shown):
                 save_image(one, str(single_dir / t_tag) + f'_out_b{b}.png')
         return per_scale
+
+    def _local_batch_maps(self, batch_size) -> dict:
+        """This rank's rows of the per-sample conditioning on `ema_model`, as {attribute: value to set for the call}: every
+        keep / layout map with a leading batch dimension, `layout_gain`, `roi_bbs_batch` and `roi_target_patch_batch` must have
+        `batch_size` (global) rows and is cut with `dist.shard_rows`.  Empty when nothing is per sample."""
+        em, B, out = self.ema_model, int(batch_size), {}
+
+        def rows(v, what):
+            n = int(v.shape[0]) if isinstance(v, torch.Tensor) else len(v)
+            if n != B:
+                raise ValueError(f'{what} has {n} rows for batch_size={B}')
+            return sdist.shard_rows(v)
+
+        if em.keep_maps is not None and any(m.dim() == 3 or k0.dim() == 4 for m, k0 in em.keep_maps.values()):
+            out['keep_maps'] = {s: (rows(m, f'keep_maps[{s}] mask').contiguous() if m.dim() == 3 else m,
+                                    rows(k0, f'keep_maps[{s}] x0').contiguous() if k0.dim() == 4 else k0)
+                                for s, (m, k0) in em.keep_maps.items()}
+        if em.layout_maps is not None and any(v.dim() == 4 for v in em.layout_maps.values()):
+            out['layout_maps'] = {s: rows(v, f'layout_maps[{s}]').contiguous() if v.dim() == 4 else v
+                                  for s, v in em.layout_maps.items()}
+        for name in ('layout_gain', 'roi_bbs_batch', 'roi_target_patch_batch'):
+            if getattr(em, name) is not None:
+                out[name] = rows(getattr(em, name), name)
+        return out
 
     def _local_seeds(self, seeds, vary_from_scale, batch_size, sharded):
         """`ema_model.sample_seeds` of a driver call: None without `seeds`; else the global list (checked against
@@ -447,16 +479,21 @@ class MultiscaleTrainer(object):
 
     @torch.no_grad()
     def roi_guided_sampling(self, custom_t_list=None, target_roi=None, roi_bb_list=None, save_unbatched=False,
-                            batch_size=4, scale_mul=(1, 1), save_images=True, seeds=None, vary_from_scale=None):
+                            batch_size=4, scale_mul=(1, 1), save_images=True, seeds=None, vary_from_scale=None,
+                            per_sample=False):
         """ROI guided generation (trainer.py:436-454): at every scale but the finest the predicted clean image is
         pulled (eta = 0.8) towards a patch of the training image inside the given boxes; the blend runs inside the
         step kernels of the sampler's chain call (`sinddm_sample_chain_ex` with edit maps: one library call per scale,
         step noise from the in-kernel Philox stream).  With a `noise_fn`, or with `ema_model.chain_guided = False`,
-        the run goes step by step through `sinddm_reverse_step_edit`."""
+        the run goes step by step through `sinddm_reverse_step_edit`.  `per_sample`: `roi_bb_list` holds `batch_size` box
+        lists, one job per sample (`ema_model.roi_bbs_batch` -> sinddm_sample_chain_batch); the target patch stays shared."""
         from .functions import extract_patch
         em = self.ema_model
+        if per_sample and len(roi_bb_list) != int(batch_size):
+            raise ValueError(f'roi_guided_sampling: {len(roi_bb_list)} box lists for batch_size={int(batch_size)}')
         em.roi_guided_sampling = True
-        em.roi_bbs = roi_bb_list
+        em.roi_bbs = [] if per_sample else roi_bb_list
+        em.roi_bbs_batch = [list(bbs) for bbs in roi_bb_list] if per_sample else None
         em.roi_target_patch = []       # (the reference appends on every call; a fresh list per call is what it means)
         for scale in range(self.n_scales):
             bb = [int(bb_i / np.power(self.scale_factor, self.n_scales - scale - 1)) for bb_i in target_roi]
@@ -469,6 +506,7 @@ class MultiscaleTrainer(object):
                                       seeds=seeds, vary_from_scale=vary_from_scale)
         finally:
             em.roi_guided_sampling = False
+            em.roi_bbs_batch = None
 
     # ---- known-region sampling: some pixels are given, the rest is generated to fit (no reference counterpart) ----
     def _sample_kept(self, keep_maps, tag, resample=1, jump_length=1, **kw):
@@ -497,13 +535,15 @@ class MultiscaleTrainer(object):
         and comes down again, until the stretch has been walked R times (`ema_model.resample` -> functions.resample_schedule
         and sinddm_sample_chain_resample: still one library call per scale, R times the network evaluations on the
         resampled stretches).  The defaults (1, 1) are the run without jumps, bit for bit.  No image-quality claim is made.
-        Returns the per-scale batches and writes PNGs like `sample_scales`."""
+        A (batch_size, H, W) stack of masks gives every sample its own hole: one job per sample, still one library call per
+        scale (sinddm_sample_chain_batch).  Returns the per-scale batches and writes PNGs like `sample_scales`."""
         from .functions import keep_mask_pyramid
         em = self.ema_model
         m = torch.as_tensor(mask)
-        if tuple(m.shape) != tuple(em.image_sizes[self.n_scales - 1]):
-            raise ValueError(f'inpaint: mask {tuple(m.shape)} is not the finest scale {tuple(em.image_sizes[self.n_scales - 1])}')
-        masks = keep_mask_pyramid(m, [em.image_sizes[s] for s in range(self.n_scales)], hard=hard)
+        fine = tuple(em.image_sizes[self.n_scales - 1])
+        if tuple(m.shape) not in (fine, (int(batch_size),) + fine):
+            raise ValueError(f'inpaint: mask {tuple(m.shape)} is not the finest scale {fine} (or {int(batch_size)} of them)')
+        masks = keep_mask_pyramid(m, [em.image_sizes[s] for s in range(self.n_scales)], hard=hard, batch=m.dim() == 3)
         maps = {s: (masks[s].to(self.device).contiguous(), self.data_list[s][0][0].contiguous())
                 for s in range(self.n_scales)}
         return self._sample_kept(maps, 'inpaint', resample=resample, jump_length=jump_length, batch_size=batch_size,
@@ -516,22 +556,30 @@ class MultiscaleTrainer(object):
         """Grow the canvas around the training image: at every scale the sample has `target_size(s, scale_mul)`, the
         scale's own training image sits unresampled at int(anchor * (canvas - image)) and is kept (mask 1 on that
         rectangle), the rest is generated.  `scale_mul` < 1 on an axis is a ValueError.  `resample` / `jump_length`: as for
-        `inpaint`."""
+        `inpaint`.  `anchor` may be a list of `batch_size` (y, x) pairs: every sample gets its own mask and known image."""
         from .functions import outpaint_offset
         em = self.ema_model
         if min(float(scale_mul[0]), float(scale_mul[1])) < 1:
             raise ValueError(f'outpaint: scale_mul {tuple(scale_mul)} < 1 would crop the known image')
+        anchors = None
+        if len(anchor) > 0 and isinstance(anchor[0], (tuple, list)):
+            anchors = [tuple(a) for a in anchor]
+            if len(anchors) != int(batch_size):
+                raise ValueError(f'outpaint: {len(anchors)} anchors for batch_size={int(batch_size)}')
         maps = {}
         for s in range(self.n_scales):
             img = self.data_list[s][0][0]
             h, w = int(img.shape[1]), int(img.shape[2])
             Hc, Wc = em.target_size(s, scale_mul)
-            y0, x0 = outpaint_offset((Hc, Wc), (h, w), anchor)
-            k0 = torch.zeros((img.shape[0], Hc, Wc), dtype=torch.float32, device=img.device)
-            m = torch.zeros((Hc, Wc), dtype=torch.float32, device=img.device)
-            k0[:, y0:y0 + h, x0:x0 + w] = img
-            m[y0:y0 + h, x0:x0 + w] = 1.0
-            maps[s] = (m, k0)
+            pairs = []
+            for a in (anchors if anchors is not None else [anchor]):
+                y0, x0 = outpaint_offset((Hc, Wc), (h, w), a)
+                k0 = torch.zeros((img.shape[0], Hc, Wc), dtype=torch.float32, device=img.device)
+                m = torch.zeros((Hc, Wc), dtype=torch.float32, device=img.device)
+                k0[:, y0:y0 + h, x0:x0 + w] = img
+                m[y0:y0 + h, x0:x0 + w] = 1.0
+                pairs.append((m, k0))
+            maps[s] = pairs[0] if anchors is None else (torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs]))
         return self._sample_kept(maps, 'outpaint', resample=resample, jump_length=jump_length, scale_mul=tuple(scale_mul),
                                  batch_size=batch_size,
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
@@ -549,14 +597,18 @@ class MultiscaleTrainer(object):
         each scale by area averaging (`functions._layout_pyramid`).  `scales` = (first, last) limits the conditioned scales
         (inclusive; default all).  Runs `sample_scales` with `ema_model.layout_maps` / `layout_down` / `layout_strength` /
         `layout_t_min` set (sinddm_sample_chain_layout: still one library call per scale) and clears them afterwards.
-        strength = 0 is `sample_scales` itself, bit for bit.  No image-quality claim is made."""
-        from .functions import layout_blocks, _layout_pyramid
+        strength = 0 is `sample_scales` itself, bit for bit.  No image-quality claim is made.
+        `layout` may be (batch_size, 3, H, W), one picture per sample, and `strength` a list of `batch_size` values: their
+        maximum becomes the shared per-step strength and value / maximum the sample's `layout_gain`
+        (`split_strength`; sinddm_sample_chain_batch)."""
+        from .functions import layout_blocks, _layout_pyramid, split_strength
         em = self.ema_model
         lay = torch.as_tensor(layout)
         sizes = [tuple(em.target_size(s, scale_mul)) for s in range(self.n_scales)]
-        if lay.dim() != 3 or tuple(lay.shape) != (3,) + sizes[-1]:
+        if tuple(lay.shape) not in ((3,) + sizes[-1], (int(batch_size), 3) + sizes[-1]):
             raise ValueError(f'paint2image: layout {tuple(lay.shape)} must be (3, {sizes[-1][0]}, {sizes[-1][1]}), the finest '
-                             f'target size')
+                             f'target size, or {int(batch_size)} of them')
+        strength, gain = split_strength(strength, batch_size)
         if not (0.0 <= float(strength) <= 1.0) or int(t_min) < 0:
             raise ValueError(f'paint2image: strength {strength} outside [0, 1] or t_min {t_min} < 0')
         first, last = (0, self.n_scales - 1) if scales is None else (int(scales[0]), int(scales[1]))
@@ -567,6 +619,7 @@ class MultiscaleTrainer(object):
         em.layout_maps = {s: pyr[s].to(self.device).contiguous() for s in range(first, last + 1)}
         em.layout_down = {s: blocks[s] for s in range(first, last + 1)}
         em.layout_strength, em.layout_t_min = float(strength), int(t_min)
+        em.layout_gain = gain
         try:
             return self.sample_scales(scale_mul=tuple(scale_mul), custom_sample=False, image_name='', start_noise=True,
                                       desc=f'paint2image_{str(datetime.datetime.now()).replace(":", "_")}',
@@ -574,6 +627,7 @@ class MultiscaleTrainer(object):
                                       save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale)
         finally:
             em.layout_maps, em.layout_down, em.layout_strength, em.layout_t_min = None, {}, 1.0, 0
+            em.layout_gain = None
 
     # ---- CLIP-driven modes of the reference.  CLIP itself (clip/, text2live_util/) is not part of this build; the
     # driver takes any `clip_model` with the interface the reference uses: get_text_embedding(text, template=...),
