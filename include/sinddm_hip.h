@@ -152,7 +152,8 @@ typedef struct sinddm_chain_opts {
 } sinddm_chain_opts;
 
 /* sinddm_sample_chain2 with options; opts = NULL (or all members NULL) is sinddm_sample_chain2 itself, bit for bit.
- * sinddm_sample_chain and sinddm_sample_chain2 are thin wrappers over this entry.  The two-stream split, the workspace
+ * Every sinddm_sample_chain* entry fills one internal description of the run and calls one body: the entries differ only in
+ * which options their signatures can express, and an absent option is the call without it.  The two-stream split, the workspace
  * layout and the results do not depend on the options: a split run reads each half-batch's own part of `noise`.
  * SINDDM_E_BADARG: edit_w without edit_c (or the reverse), a pointer that is not 16-byte aligned. */
 int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, float* x_alt, float* eps,
@@ -263,8 +264,8 @@ int sinddm_sample_chain_keep(const float* params, const float* packed, float* x,
 int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* seeds /*device, B*/,
                                uint64_t stream_id, void* stream);
 
-/* sinddm_sample_chain_keep with per-sample seeds.  sample_seeds = NULL is sinddm_sample_chain_keep itself (that entry is a
- * thin wrapper over this one): the same launches, the same numbers.  With seeds, step i of the call adds to element e of
+/* sinddm_sample_chain_keep with per-sample seeds.  sample_seeds = NULL is sinddm_sample_chain_keep itself (every chain entry
+ * fills one internal description; they differ only in the options they can express): the same launches, the same numbers.  With seeds, step i of the call adds to element e of
  * sample b  sigma_i * (element e of sinddm_normal_fill(3*H*W, sample_seeds[b], stream_id0 + i))  -- H, W the extended size
  * under a halo -- and `seed` is ignored.  opts->noise still wins over both.  ROI maps, halo, keep and the two-stream split
  * work as before (the second half-batch reads its own part of sample_seeds); results with / without aux_stream are
@@ -321,7 +322,8 @@ typedef struct sinddm_resample_opts {
 } sinddm_resample_opts;
 
 /* sinddm_sample_chain_seeds with resampling jumps.  rs = NULL, rs->jumps = NULL or no entry `on` is sinddm_sample_chain_seeds
- * itself (that entry is a thin wrapper over this one): the same launches, the same numbers.  t_list holds the EXPANDED walk
+ * itself (every chain entry fills one internal description; they differ only in the options they can express): the same
+ * launches, the same numbers.  t_list holds the EXPANDED walk
  * (a jump to level l' is followed by the step t = l'); the call does not check that the levels match: r, s, d say what the
  * jump does.  Halo, keep, edit, seeds and the two-stream split work as before: the jump kernel runs once per half-batch on
  * that half-batch's stream, and results with / without aux_stream are identical.
@@ -377,8 +379,8 @@ typedef struct sinddm_layout_opts {
     float* delta;          /* device scratch, B*3*h*w floats                                                              */
 } sinddm_layout_opts;
 
-/* sinddm_sample_chain_resample with layout conditioning (that entry is a thin wrapper over this one; this one over
- * sinddm_sample_chain_batch).  lo = NULL,
+/* sinddm_sample_chain_resample with layout conditioning (every chain entry fills one internal description; they differ only
+ * in the options they can express).  lo = NULL,
  * lo->layout = NULL or every g_i == 0: the same launches, the same numbers as sinddm_sample_chain_resample.  A step with
  * g_i > 0 runs unfused, as a jump step does: the network writes eps, then the delta kernel, then the layout tail -- each per
  * half-batch on that half's stream, the second half with its own slice of `delta`; every other step keeps its fused tail.
@@ -412,7 +414,8 @@ typedef struct sinddm_batch_opts {
     const float* layout_gain;   /* device, B floats in [0, 1], or NULL                */
 } sinddm_batch_opts;
 
-/* sinddm_sample_chain_layout with per-sample maps (that entry is a thin wrapper over this one).  bo = NULL or all members
+/* sinddm_sample_chain_layout with per-sample maps (every chain entry fills one internal description; they differ only in the
+ * options they can express).  bo = NULL or all members
  * zero: the same launches, the same numbers as sinddm_sample_chain_layout.  With shared maps every kernel computes what it
  * did; a per-sample map only moves the address a sample reads.  Sample b's result is, bit for bit, sample b of the
  * shared-map call that gets its slices (same batch, seed and start), wherever the network itself is independent of the

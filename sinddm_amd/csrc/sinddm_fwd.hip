@@ -5,7 +5,7 @@
 #include "conv_wh.h"
 #include "internal.h"
 #include "step_tail.h"
-#include "batch_check.h"
+#include "chain_run.h"
 #include <type_traits>
 namespace sinddm {
 
@@ -1234,12 +1234,30 @@ static int reverse_step_launch(const float* x_t, const float* eps, const float* 
     return 0;
 }
 
+// the TailArgs of a single step: caller-supplied noise, maps shared by the batch (coefs = NULL: step_args_ok refuses the call)
+static TailArgs step_tail_args(const sinddm_step_coefs* coefs, const float* noise, const float* edit_w = nullptr,
+                               const float* edit_c = nullptr, const float* keep_m = nullptr, const float* keep_x0 = nullptr,
+                               float keep_a = 0.0f, float keep_b = 0.0f) {
+    TailArgs t{};
+    if (coefs) t.k = *coefs;
+    t.nz = noise; t.ew = edit_w; t.ec = edit_c;
+    t.km = keep_m; t.kx = keep_x0; t.ka = keep_a; t.kb = keep_b;
+    return t;
+}
+
+// what the single-step entries check alike: the tensors are there, x-tilde where the mode reads it, a pair of maps is both
+// or neither.  Each entry adds the requirements and the shape bounds that are its own.
+static bool step_args_ok(const float* x_t, const float* eps, const float* x_tilde, const float* out, const sinddm_step_coefs* coefs,
+                         const TailArgs& t) {
+    if (!x_t || !eps || !t.nz || !out || !coefs) return false;
+    if ((t.ew == nullptr) != (t.ec == nullptr) || (t.km == nullptr) != (t.kx == nullptr)) return false;
+    return coefs->mode == 0 || x_tilde;
+}
+
 int sinddm_reverse_step(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                         const sinddm_step_coefs* coefs, int64_t n, void* stream) {
-    if (!x_t || !eps || !noise || !out || !coefs || n <= 0) return SINDDM_E_BADARG;
-    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
-    TailArgs t{};
-    t.k = *coefs; t.nz = noise;
+    const TailArgs t = step_tail_args(coefs, noise);
+    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || n <= 0) return SINDDM_E_BADARG;
     return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)n, 1, 1, stream);
 }
 
@@ -1277,22 +1295,41 @@ int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* see
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
-// a jump description the kernels can take: r in (0, 1], s >= 0, d only where x-tilde exists; never after a mode-2 step
-static bool jump_valid(const sinddm_jump_coefs& j, const sinddm_step_coefs& k) {
-    return k.mode != 2 && j.r > 0.0f && j.r <= 1.0f && j.s >= 0.0f && (k.mode != 0 || j.d == 0.0f);
+// the tensors and the extent of one unfused tail launch: Bn samples of chw elements (hw per channel) on stream st
+struct TailIO {
+    const float* x_t;
+    const float* eps;
+    const float* x_tilde;
+    float* out;
+    int Bn, chw, hw;
+    hipStream_t st;
+};
+
+// the rows of a tail launch: one per sample with per-sample seeds, else one row of the whole launch
+static long long tail_span(const TailIO& io, const TailArgs& t) { return t.sseeds ? io.chw : (long long)io.Bn * io.chw; }
+
+// the plain step of a shape without a fused tail (reverse_step_rows_kernel); t.b0 / t.sseeds / t.nz as the kernel documents them
+static int rows_launch(const TailIO& io, const TailArgs& t) {
+    const long long span = tail_span(io, t);
+    long long gx = ((span + 3) / 4 + 255) / 256;               // (no + 1: a row of this kernel starts on a quad of its stream)
+    if (gx > 8192) gx = 8192;
+    tail_dispatch(t, [&](auto E, auto N, auto K) {
+        hipLaunchKernelGGL((reverse_step_rows_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
+                           span, io.chw, io.hw);
+    });
+    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
 
-// reverse step + jump (reverse_step_jump_kernel) over `Bn` samples of chw elements: one row per sample with per-sample
-// seeds, else one row of the whole launch; t.b0 / t.sseeds / t.nz / jp.nz as the kernel documents them
-static int jump_launch(const float* x_t, const float* eps, const float* x_tilde, float* out, const TailArgs& t, const JumpArgs& jp,
-                       int Bn, int chw, int hw, hipStream_t st) {
-    const long long span = t.sseeds ? chw : (long long)Bn * chw;
+// reverse step + jump (reverse_step_jump_kernel); jp.nz as the kernel documents it
+static int jump_launch(const TailIO& io, const TailArgs& t, const JumpArgs& jp) {
+    const long long span = tail_span(io, t);
     long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
     if (gx > 8192) gx = 8192;
     tail_dispatch(t, [&](auto E, auto N, auto K) {
         hipLaunchKernelGGL((reverse_step_jump_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                           dim3((unsigned)gx, t.sseeds ? (unsigned)Bn : 1u), dim3(256), 0, st, x_t, eps, x_tilde, out, t, jp, span,
-                           chw, hw);
+                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
+                           jp, span, io.chw, io.hw);
     });
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
@@ -1307,369 +1344,343 @@ static LayoutArgs layout_geom(int Hc, int Wc, int halo_y, int halo_x, int N, boo
     return g;
 }
 
-// block deltas of `Bn` samples (layout_delta_kernel): g.D is written; `t` carries the step's scalars, the edit maps and
-// their strides, as for the tail behind it
-static int layout_delta_launch(const float* x_t, const float* eps, const float* x_tilde, const float* layout, const TailArgs& t,
-                               const LayoutArgs& g, int Bn, hipStream_t st) {
-    const float* edit_w = t.ew;
-    const float* edit_c = t.ec;
-    const sinddm_step_coefs& k = t.k;
+// block deltas of io.Bn samples (layout_delta_kernel): g.D is written, io.out is not; `t` carries the step's scalars, the
+// edit maps and their strides, as for the tail behind it
+static int layout_delta_launch(const TailIO& io, const float* layout, const TailArgs& t, const LayoutArgs& g) {
     const int cols = (256 / g.N) * g.N, bpw = cols / g.N;
-    const dim3 grid((unsigned)((g.w + bpw - 1) / bpw), (unsigned)g.h, (unsigned)(Bn * CHANNELS));
+    const dim3 grid((unsigned)((g.w + bpw - 1) / bpw), (unsigned)g.h, (unsigned)(io.Bn * CHANNELS));
     float* D = const_cast<float*>(g.D);
-    if (edit_w)
-        hipLaunchKernelGGL(layout_delta_kernel<true>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, t.sew, t.sec, D, k, g,
-                           cols);
+    if (t.ew)
+        hipLaunchKernelGGL(layout_delta_kernel<true>, grid, dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, layout, t.ew, t.ec, t.sew,
+                           t.sec, D, t.k, g, cols);
     else
-        hipLaunchKernelGGL(layout_delta_kernel<false>, grid, dim3(256), 0, st, x_t, eps, x_tilde, layout, edit_w, edit_c, t.sew, t.sec, D, k, g,
-                           cols);
+        hipLaunchKernelGGL(layout_delta_kernel<false>, grid, dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, layout, t.ew, t.ec, t.sew,
+                           t.sec, D, t.k, g, cols);
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
 
-// the conditioned step (reverse_step_layout_kernel) over `Bn` samples: rows as in jump_launch
-static int layout_step_launch(const float* x_t, const float* eps, const float* x_tilde, float* out, const TailArgs& t,
-                              const LayoutArgs& g, int Bn, int chw, int hw, hipStream_t st) {
-    const long long span = t.sseeds ? chw : (long long)Bn * chw;
+// the conditioned step (reverse_step_layout_kernel): rows as in jump_launch
+static int layout_step_launch(const TailIO& io, const TailArgs& t, const LayoutArgs& g) {
+    const long long span = tail_span(io, t);
     long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
     if (gx > 8192) gx = 8192;
     tail_dispatch(t, [&](auto E, auto N, auto K) {
         hipLaunchKernelGGL((reverse_step_layout_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                           dim3((unsigned)gx, t.sseeds ? (unsigned)Bn : 1u), dim3(256), 0, st, x_t, eps, x_tilde, out, t, g, span,
-                           chw, hw);
+                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
+                           g, span, io.chw, io.hw);
     });
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
 
-// The body of every sinddm_sample_chain* entry point: each passes 0 / NULL for the options its signature does not have
-// (sinddm_sample_chain_seeds has them all).  Hc x Wc is the CENTRE size; the
-// steps run on the extended shape H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo,
-// the halo of every step's output is refreshed from its centre (wrap_halo_launch, per half-batch on its own stream), and
-// that of `x` once on entry: the zero padding of the convolutions then never reaches the centre (SINDDM_TILE_HALO).
-static int sample_chain_impl(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                             const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                             uint64_t stream_id0, int dim, int B, int Hc, int Wc, void* ws, size_t ws_bytes, void* stream,
-                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                             const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
-                             const sinddm_layout_opts* lo, const sinddm_batch_opts* bo) {
-    if ((halo_y != 0 && halo_y < SINDDM_TILE_HALO) || (halo_x != 0 && halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
-    if (halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;                // (H + 2 halo stays an int)
-    if ((reinterpret_cast<uintptr_t>(sample_seeds) & 7) != 0) return SINDDM_E_BADARG;
-    if (!params || !packed || !x || !x_alt || !eps || !coefs || !t_list || !ws || n_steps < 0 || B <= 0 || Hc <= 0 || Wc <= 0)
-        return SINDDM_E_BADARG;
-    const bool tiled = halo_y != 0 || halo_x != 0;
-    const int H = Hc + 2 * halo_y, W = Wc + 2 * halo_x;
-    const float* edit_w = opts ? opts->edit_w : nullptr;
-    const float* edit_c = opts ? opts->edit_c : nullptr;
-    const float* noise = opts ? opts->noise : nullptr;
-    const float* keep_m = keep ? keep->mask : nullptr;
-    const float* keep_x0 = keep ? keep->x0 : nullptr;
-    const float* keep_ab = keep_m ? keep->ab : nullptr;        // HOST: (keep_a, keep_b) per step
-    if ((edit_w == nullptr) != (edit_c == nullptr) || (keep_m == nullptr) != (keep_x0 == nullptr)) return SINDDM_E_BADARG;
-    if (keep_m && !keep_ab) return SINDDM_E_BADARG;
-    if ((edit_w || keep_m) && (long long)CHANNELS * H * W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;      // (the maps are indexed with ints)
-    // per-sample seeds: recorded draws win over them, as they win over `seed`; the kernels then never see the array
-    const unsigned long long* sseeds = noise ? nullptr : reinterpret_cast<const unsigned long long*>(sample_seeds);
-    if (sseeds && ((long long)CHANNELS * H * W > 0x7fffffffLL || B > 65535)) return SINDDM_E_BADSHAPE;  // (per-sample quads are ints)
-    // (the plain fused tail reads the maps and the draws as 16-byte vectors)
-    if (((reinterpret_cast<uintptr_t>(edit_w) | reinterpret_cast<uintptr_t>(edit_c) | reinterpret_cast<uintptr_t>(noise) |
-          reinterpret_cast<uintptr_t>(keep_m) | reinterpret_cast<uintptr_t>(keep_x0)) & 15) != 0)
-        return SINDDM_E_BADARG;
-    // resampling jumps: a step with jumps[i].on runs unfused and ends in reverse_step_jump_kernel; none on: `jumps` stays NULL
-    // and nothing below differs from the call without `rs`
-    const sinddm_jump_coefs* jumps = nullptr;
-    for (int i = 0; rs && rs->jumps && i < n_steps; ++i) {
-        if (!rs->jumps[i].on) continue;
-        if (!jump_valid(rs->jumps[i], coefs[i])) return SINDDM_E_BADARG;
-        jumps = rs->jumps;
-    }
-    const float* jump_noise = jumps ? rs->noise : nullptr;   // one slot per jump, in order of occurrence
-    if ((reinterpret_cast<uintptr_t>(jump_noise) & 15) != 0 || (jumps && noise && !jump_noise)) return SINDDM_E_BADARG;
-    // layout conditioning: a step with g[i] > 0 runs unfused and ends in layout_delta_kernel + reverse_step_layout_kernel; no
-    // such step: `lay_g` stays NULL and nothing below differs from the call without `lo`
-    const float* lay_g = nullptr;
-    LayoutArgs lay{};
-    if (lo && lo->layout) {
-        if (!lo->g) return SINDDM_E_BADARG;
-        for (int i = 0; i < n_steps; ++i) {
-            if (!(lo->g[i] >= 0.0f && lo->g[i] <= 1.0f)) return SINDDM_E_BADARG;
-            if (lo->g[i] > 0.0f) {
-                if (jumps && jumps[i].on) return SINDDM_E_BADARG;
-                lay_g = lo->g;
-            }
-        }
-        if (lay_g) {                                           // (the rest of the block is read only by a run that pulls)
-            if (lo->down < 1 || lo->down > 64 || !lo->delta || (reinterpret_cast<uintptr_t>(lo->layout) & 15) != 0)
-                return SINDDM_E_BADARG;
-            if ((long long)CHANNELS * H * W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;    // (an element's index inside its sample is an int)
-            if ((long long)B * CHANNELS > 65535) return SINDDM_E_BADSHAPE;               // (one grid plane per (sample, channel))
-            lay = layout_geom(Hc, Wc, halo_y, halo_x, lo->down, false, false);
-            if (lay.h > 65535) return SINDDM_E_BADSHAPE;                                  // (one grid row per block row)
-        }
-    }
-    NetPlan p = make_plan(dim);
-    if (!p.ok) return SINDDM_E_BADSHAPE;
-    // per-sample maps (batch_check.h): the strides of step_tail.h; all 0 without `bo`, and nothing below differs then
-    BatchStrides bs{};
-    if (const int rcb = batch_strides(bo, edit_w, edit_c, keep_m, keep_x0, lo ? lo->layout : nullptr, H, W,
-                                      (H * W) % 4 == 0 && fwd_pitch(p, W) == W, &bs))
-        return rcb;
-    const float* lay_gain = bo && lay_g ? bo->layout_gain : nullptr;     // (read only by a run that pulls, like the rest of `lo`)
-    lay.sl = lay_g ? bs.sl : 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipStream_t sx = static_cast<hipStream_t>(aux_stream);
-    const long long n = (long long)B * CHANNELS * H * W;
-    if (ws_bytes < fwd_workspace_bytes(p, B, H, W)) return SINDDM_E_WORKSPACE;
-    float* cond_tab = static_cast<float*>(ws);                 // the conditioning region: one row per step of a run
-    const bool fuse_tail = (H * W) % 4 == 0 || fwd_pitch(p, W) != W;     // (padded rows: their own fused tail kernel)
-    // Coarse pyramid scales: a launch carries a handful of work items per CU (C2 48x64 at batch 16: 1.5), every kernel ends
-    // in a partly filled round and pays its fixed ramp / drain, and each step is a chain of 16 dependent launches.  The
-    // chains of the batch are independent, so with a second stream the batch runs as TWO half-batches whose launches
-    // overlap: the tail round of one fills with the other's items.  Same numbers either way (the noise is keyed on the
-    // whole batch's flat index: ChainStep::b0; with per-sample seeds the second half gets its own part of the array).
+// ---- the sampler chain: one ChainRun (chain_run.h) from every entry, checked there, enqueued here ------------------------
+// The batch of a run as one launch sequence, or as two half-batches on two streams.
+// Coarse pyramid scales: a launch carries a handful of work items per CU (C2 48x64 at batch 16: 1.5), every kernel ends
+// in a partly filled round and pays its fixed ramp / drain, and each step is a chain of 16 dependent launches.  The
+// chains of the batch are independent, so with a second stream the batch runs as TWO half-batches whose launches
+// overlap: the tail round of one fills with the other's items.  Same numbers either way (the noise is keyed on the
+// whole batch's flat index: TailArgs::b0; with per-sample seeds the second half gets its own part of the array).
+struct ChainSplit {
+    bool on;
+    int Bh[2];                           // samples per half (one half: {B, 0})
+    char* wsh[2];                        // each half's workspace ...
+    size_t wsz[2];                       // ... and its size
+    size_t hoff;                         // the second half's offset into x / x_alt / eps / x_tilde
+    hipEvent_t ev_go, ev_done;           // ours while `on`: chain_split creates them, sample_chain_impl destroys them
+};
+
+// what the steps of one chain call share
+struct ChainCtx {
+    const ChainRun& r;
+    ChainChecked c;
+    NetPlan p;
+    BatchStrides bs;
+    LayoutArgs lay;                      // the geometry of a run that pulls (D, g, gain: per launch)
+    const float* lay_gain;
+    bool fuse_tail;                      // the network's last kernel ends in the plain step: (H W) % 4 == 0, or padded rows
+    hipStream_t st, sx;
+    float* cond_tab;                     // the conditioning region: one row per step of a run
+    ChainSplit sp;
+};
+
+// one step of the run, for both halves (b0 / sseeds of `t`: of the whole batch)
+struct ChainStepPlan {
+    int i;
+    const float* cond_row;
+    float* cur;
+    float* nxt;
+    TailArgs t;
+    bool jump, pull;                     // the step writes eps; its tail is launched behind the network
+    JumpArgs jp;
+    float g;                             // pull: the step's strength
+};
+
+// the split rule and the carving of the workspace; 0, or SINDDM_E_BADARG when an event cannot be created
+static int chain_split(ChainCtx& k) {
+    const ChainRun& r = k.r;
+    const NetPlan& p = k.p;
+    const int B = r.B, H = k.c.H, W = k.c.W;
+    ChainSplit& s = k.sp;
     const long long items = (long long)B * ((fwd_pitch(p, W) + 31) / 32) * ((H + 7) / 8) * 2;
     const long long ncu = cu_count();
     const long long rounds = (items + ncu - 1) / ncu;
-    bool split = sx != nullptr && sx != st && B >= 2 && fuse_tail && n_steps > 0 && items < SINDDM_SPLIT_ITEMS_HI * ncu &&
+    bool split = k.sx != nullptr && k.sx != k.st && B >= 2 && k.fuse_tail && r.n_steps > 0 && items < SINDDM_SPLIT_ITEMS_HI * ncu &&
                  items >= SINDDM_SPLIT_ITEMS_LO * ncu && (rounds * ncu - items) * 25 >= rounds * ncu;
     // (a batch whose 3x3 convs take the binary16 kernels stays whole: its halves could fall below their items-per-CU
     // threshold and run on the fp32 kernels -- the same chain would then round differently with and without a second stream)
     if (split && conv3x3_route(p, p.blk[2].c2, B, H, fwd_pitch(p, W), true, false) == CONV_WH)       // (the dim -> dim conv)
         split = false;
     // (the two halves carve their own cores behind the shared conditioning table: only if that really fits -- ADVICE r4)
-    if (split && cond_region_bytes(p, B) + fwd_workspace_core(p, (B + 1) / 2, H, W) + fwd_workspace_core(p, B - (B + 1) / 2, H, W) > ws_bytes)
+    if (split && cond_region_bytes(p, B) + fwd_workspace_core(p, (B + 1) / 2, H, W) + fwd_workspace_core(p, B - (B + 1) / 2, H, W) > r.ws_bytes)
         split = false;
-    const int Bh[2] = {split ? (B + 1) / 2 : B, split ? B - (B + 1) / 2 : 0};
-    char* wsh[2] = {static_cast<char*>(ws), nullptr};
-    size_t wsz[2] = {ws_bytes, 0};
-    hipEvent_t ev_go = nullptr, ev_done = nullptr;
+    s = ChainSplit{};
+    s.on = split;
+    s.Bh[0] = split ? (B + 1) / 2 : B; s.Bh[1] = split ? B - (B + 1) / 2 : 0;
+    s.wsh[0] = static_cast<char*>(r.ws); s.wsz[0] = r.ws_bytes;
     if (split) {
-        wsh[0] = static_cast<char*>(ws) + cond_region_bytes(p, B);
-        wsz[0] = fwd_workspace_core(p, Bh[0], H, W);
-        wsh[1] = wsh[0] + wsz[0];
-        wsz[1] = fwd_workspace_core(p, Bh[1], H, W);
-        if (hipEventCreateWithFlags(&ev_go, hipEventDisableTiming) != hipSuccess) return SINDDM_E_BADARG;
-        if (hipEventCreateWithFlags(&ev_done, hipEventDisableTiming) != hipSuccess) {
-            (void)hipEventDestroy(ev_go);
+        s.wsh[0] = static_cast<char*>(r.ws) + cond_region_bytes(p, B);
+        s.wsz[0] = fwd_workspace_core(p, s.Bh[0], H, W);
+        s.wsh[1] = s.wsh[0] + s.wsz[0];
+        s.wsz[1] = fwd_workspace_core(p, s.Bh[1], H, W);
+        if (hipEventCreateWithFlags(&s.ev_go, hipEventDisableTiming) != hipSuccess) return SINDDM_E_BADARG;
+        if (hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) != hipSuccess) {
+            (void)hipEventDestroy(s.ev_go);
             return SINDDM_E_BADARG;
         }
     }
-    const size_t hoff = (size_t)Bh[0] * CHANNELS * H * W;      // the second half's offset into x / x_alt / eps / x_tilde
-    float* cur = x;
-    float* nxt = x_alt;
+    s.hoff = (size_t)s.Bh[0] * CHANNELS * H * W;
+    return 0;
+}
+
+// Half h of one step, on its own stream: the network, then the tail the step ends in -- step + jump, or block delta +
+// conditioned step, or the plain rows kernel where the shape has no fused tail, or nothing (the network's last kernel was
+// the tail) -- then the halo of the step's output when tiled.  A run that is not split has the one half h = 0.
+static int chain_half_step(const ChainCtx& k, const ChainStepPlan& s, int h) {
+    const ChainRun& r = k.r;
+    const int H = k.c.H, W = k.c.W, Bn = k.sp.Bh[h];
+    const size_t o = h ? k.sp.hoff : 0;
+    hipStream_t st = h ? k.sx : k.st;
+    ChainStep cs{};
+    cs.cond_row = s.cond_row;
+    cs.x_tilde = r.x_tilde ? r.x_tilde + o : nullptr; cs.x_next = k.fuse_tail && !s.jump && !s.pull ? s.nxt + o : nullptr;
+    cs.tail = s.t;
+    const int b0 = cs.tail.b0 = h ? k.sp.Bh[0] : 0;
+    if (k.c.sseeds) cs.tail.sseeds = k.c.sseeds + b0;
+    // (per-sample maps: the half's own slices, like its seeds -- the kernels index them with the launch's sample)
+    cs.tail.ew = batch_slice(s.t.ew, b0, s.t.sew); cs.tail.ec = batch_slice(s.t.ec, b0, s.t.sec);
+    cs.tail.km = batch_slice(s.t.km, b0, s.t.skm); cs.tail.kx = batch_slice(s.t.kx, b0, s.t.skx);
+    int rc = net_forward_impl(k.p, r.params, r.packed, s.cur + o, nullptr, r.t_list[s.i], r.scale, r.eps + o, Bn, H, W, k.sp.wsh[h],
+                              k.sp.wsz[h], st, nullptr, &cs);
+    if (rc) return rc;
+    const TailIO io{s.cur + o, r.eps + o, cs.x_tilde, s.nxt + o, Bn, CHANNELS * H * W, H * W, st};
+    if (s.jump) {
+        rc = jump_launch(io, cs.tail, s.jp);
+    } else if (s.pull) {
+        LayoutArgs lh = k.lay;                                 // (the half's own slice of the scratch)
+        lh.g = s.g;
+        lh.D = r.layout_delta + (size_t)b0 * CHANNELS * lh.h * lh.w;
+        lh.gain = k.lay_gain ? k.lay_gain + b0 : nullptr;
+        rc = layout_delta_launch(io, batch_slice(r.layout, b0, lh.sl), cs.tail, lh);
+        if (rc == 0) rc = layout_step_launch(io, cs.tail, lh);
+    } else if (!k.fuse_tail) {
+        rc = rows_launch(io, cs.tail);
+    }
+    if (rc == 0 && k.c.tiled) rc = wrap_halo_launch(io.out, nullptr, Bn * CHANNELS, r.Hc, r.Wc, r.halo_y, r.halo_x, st);
+    return rc;
+}
+
+// Every step of the call, run by run: a run is up to CHAIN_COND_ROWS steps whose t is an arithmetic progression (the
+// sampler's always is), embedded by one cond_kernel launch.  `*result` ends on the buffer the last step wrote.
+static int chain_enqueue(const ChainCtx& k, float** result) {
+    const ChainRun& r = k.r;
+    const ChainSplit& sp = k.sp;
+    const long long n = (long long)r.B * CHANNELS * k.c.H * k.c.W;
+    float* cur = r.x;
+    float* nxt = r.x_alt;
     int rc = 0;
-    int n_jumped = 0;                                          // jumps so far: the slot of rs->noise
-    if (tiled) rc = wrap_halo_launch(x, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st);     // (ordered before both halves: ev_go)
-    for (int i0 = 0; i0 < n_steps && rc == 0;) {
-        // a run: up to CHAIN_COND_ROWS steps whose t is an arithmetic progression (the sampler's always is)
+    int n_jumped = 0;                                          // jumps so far: the slot of the jumps' noise
+    if (k.c.tiled) rc = wrap_halo_launch(r.x, nullptr, r.B * CHANNELS, r.Hc, r.Wc, r.halo_y, r.halo_x, k.st);      // (ordered before both halves: ev_go)
+    for (int i0 = 0; i0 < r.n_steps && rc == 0;) {
         int len = 1, dt = 0;
-        if (i0 + 1 < n_steps) {
-            dt = t_list[i0 + 1] - t_list[i0];
+        if (i0 + 1 < r.n_steps) {
+            dt = r.t_list[i0 + 1] - r.t_list[i0];
             len = 2;
-            while (i0 + len < n_steps && len < CHAIN_COND_ROWS && t_list[i0 + len] - t_list[i0 + len - 1] == dt) ++len;
+            while (i0 + len < r.n_steps && len < CHAIN_COND_ROWS && r.t_list[i0 + len] - r.t_list[i0 + len - 1] == dt) ++len;
         }
-        CondArgs ca = cond_args(p, params);
-        ca.t_host = t_list[i0]; ca.t_step = dt; ca.scale = scale;
-        ca.out = cond_tab;
-        hipLaunchKernelGGL(cond_kernel, dim3(len), dim3(128), 0, st, ca);
-        if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }      // (no early return: the events below are ours)
-        if (split) {                                           // the second stream starts behind the table (and behind
+        CondArgs ca = cond_args(k.p, r.params);
+        ca.t_host = r.t_list[i0]; ca.t_step = dt; ca.scale = r.scale;
+        ca.out = k.cond_tab;
+        hipLaunchKernelGGL(cond_kernel, dim3(len), dim3(128), 0, k.st, ca);
+        if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }      // (no early return: the events are the caller's to destroy)
+        if (sp.on) {                                           // the second stream starts behind the table (and behind
             // everything the caller enqueued before this call); a failed dependency must not become a silent race
-            if (hipEventRecord(ev_go, st) != hipSuccess || hipStreamWaitEvent(sx, ev_go, 0) != hipSuccess) { rc = SINDDM_E_BADARG; break; }
+            if (hipEventRecord(sp.ev_go, k.st) != hipSuccess || hipStreamWaitEvent(k.sx, sp.ev_go, 0) != hipSuccess) { rc = SINDDM_E_BADARG; break; }
         }
         for (int i = i0; i < i0 + len && rc == 0; ++i) {
-            if (coefs[i].mode != 0 && !x_tilde) { rc = SINDDM_E_BADARG; break; }
-            TailArgs t{};                                      // the step's tail, fused or not (b0 / sseeds: of the whole batch)
-            t.k = coefs[i];
-            t.seed = (unsigned long long)seed; t.step = (unsigned long long)(stream_id0 + (uint64_t)i);
-            t.sseeds = sseeds;
-            t.ew = edit_w; t.ec = edit_c; t.nz = noise ? noise + (size_t)i * (size_t)n : nullptr;
-            t.km = keep_m; t.kx = keep_x0;
-            t.sew = bs.sew; t.sec = bs.sec; t.skm = bs.skm; t.skx = bs.skx;
-            t.ka = keep_m ? keep_ab[2 * i] : 1.0f; t.kb = keep_m ? keep_ab[2 * i + 1] : 0.0f;
-            const bool jump = jumps && jumps[i].on;            // the step writes eps; step + jump are one kernel behind it
-            JumpArgs jp{};
-            if (jump) {
-                jp.r = jumps[i].r; jp.s = jumps[i].s; jp.d = jumps[i].d;
-                if (noise) jp.nz = jump_noise + (size_t)n_jumped * (size_t)n;
+            if (r.coefs[i].mode != 0 && !r.x_tilde) { rc = SINDDM_E_BADARG; break; }
+            ChainStepPlan s{};
+            s.i = i; s.cond_row = k.cond_tab + (size_t)(i - i0) * k.p.cond_stride; s.cur = cur; s.nxt = nxt;
+            TailArgs& t = s.t;
+            t.k = r.coefs[i];
+            t.seed = (unsigned long long)r.seed; t.step = (unsigned long long)(r.stream_id0 + (uint64_t)i);
+            t.sseeds = k.c.sseeds;
+            t.ew = r.edit_w; t.ec = r.edit_c; t.nz = r.noise ? r.noise + (size_t)i * (size_t)n : nullptr;
+            t.km = r.keep_m; t.kx = r.keep_x0;
+            t.sew = k.bs.sew; t.sec = k.bs.sec; t.skm = k.bs.skm; t.skx = k.bs.skx;
+            t.ka = r.keep_m ? r.keep_ab[2 * i] : 1.0f; t.kb = r.keep_m ? r.keep_ab[2 * i + 1] : 0.0f;
+            s.jump = k.c.jumps && k.c.jumps[i].on;
+            if (s.jump) {
+                s.jp.r = k.c.jumps[i].r; s.jp.s = k.c.jumps[i].s; s.jp.d = k.c.jumps[i].d;
+                if (r.noise) s.jp.nz = k.c.jump_noise + (size_t)n_jumped * (size_t)n;
                 ++n_jumped;
             }
-            const bool pull = lay_g && lay_g[i] > 0.0f;        // the step writes eps; delta kernel + layout tail behind it
-            if (pull) lay.g = lay_g[i];
-            for (int h = 0; h < (split ? 2 : 1) && rc == 0; ++h) {
-                const size_t o = h ? hoff : 0;
-                ChainStep cs{};
-                cs.cond_row = cond_tab + (size_t)(i - i0) * p.cond_stride;
-                cs.x_tilde = x_tilde ? x_tilde + o : nullptr; cs.x_next = fuse_tail && !jump && !pull ? nxt + o : nullptr;
-                cs.tail = t;
-                cs.tail.b0 = h ? Bh[0] : 0;
-                if (sseeds) cs.tail.sseeds = sseeds + cs.tail.b0;
-                // (per-sample maps: the half's own slices, like its seeds -- the kernels index them with the launch's sample)
-                cs.tail.ew = batch_slice(t.ew, cs.tail.b0, t.sew); cs.tail.ec = batch_slice(t.ec, cs.tail.b0, t.sec);
-                cs.tail.km = batch_slice(t.km, cs.tail.b0, t.skm); cs.tail.kx = batch_slice(t.kx, cs.tail.b0, t.skx);
-                rc = net_forward_impl(p, params, packed, cur + o, nullptr, t_list[i], scale, eps + o, Bh[h], H, W, wsh[h], wsz[h],
-                                      h ? sx : st, nullptr, &cs);
-                if (jump && fuse_tail && rc == 0)
-                    rc = jump_launch(cur + o, eps + o, cs.x_tilde, nxt + o, cs.tail, jp, Bh[h], CHANNELS * H * W, H * W, h ? sx : st);
-                if (pull && fuse_tail && rc == 0) {
-                    LayoutArgs lh = lay;                       // (the half's own slice of the scratch)
-                    lh.D = lo->delta + (size_t)cs.tail.b0 * CHANNELS * lay.h * lay.w;
-                    lh.gain = lay_gain ? lay_gain + cs.tail.b0 : nullptr;
-                    rc = layout_delta_launch(cur + o, eps + o, cs.x_tilde, batch_slice(lo->layout, cs.tail.b0, lay.sl), cs.tail, lh,
-                                             Bh[h], h ? sx : st);
-                    if (rc == 0)
-                        rc = layout_step_launch(cur + o, eps + o, cs.x_tilde, nxt + o, cs.tail, lh, Bh[h], CHANNELS * H * W, H * W,
-                                                h ? sx : st);
-                }
-                if (tiled && fuse_tail && rc == 0)
-                    rc = wrap_halo_launch(nxt + o, nullptr, Bh[h] * CHANNELS, Hc, Wc, halo_y, halo_x, h ? sx : st);
-            }
+            s.pull = k.c.lay_g && k.c.lay_g[i] > 0.0f;
+            if (s.pull) s.g = k.c.lay_g[i];
+            for (int h = 0; h < (sp.on ? 2 : 1) && rc == 0; ++h) rc = chain_half_step(k, s, h);
             if (rc) break;
-            if (!fuse_tail) {
-                // one row for the flat batch, or with per-sample seeds one row per sample (reverse_step_rows_kernel)
-                const int chw = CHANNELS * H * W;
-                const long long span = sseeds ? chw : n;
-                long long gx = ((span + 3) / 4 + 255) / 256;
-                if (gx > 8192) gx = 8192;
-                if (jump) {
-                    if ((rc = jump_launch(cur, eps, x_tilde, nxt, t, jp, B, chw, H * W, st)) != 0) break;
-                } else if (pull) {
-                    lay.D = lo->delta;
-                    lay.gain = lay_gain;
-                    if ((rc = layout_delta_launch(cur, eps, x_tilde, lo->layout, t, lay, B, st)) != 0) break;
-                    if ((rc = layout_step_launch(cur, eps, x_tilde, nxt, t, lay, B, chw, H * W, st)) != 0) break;
-                } else {
-                    tail_dispatch(t, [&](auto E, auto N, auto K) {
-                        hipLaunchKernelGGL((reverse_step_rows_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                                           dim3((unsigned)gx, sseeds ? (unsigned)B : 1u), dim3(256), 0, st, cur, eps, x_tilde, nxt, t,
-                                           span, chw, H * W);
-                    });
-                    if (hipGetLastError() != hipSuccess) { rc = SINDDM_E_BADARG; break; }
-                }
-                if (tiled && (rc = wrap_halo_launch(nxt, nullptr, B * CHANNELS, Hc, Wc, halo_y, halo_x, st)) != 0) break;
-            }
             float* t_ = cur; cur = nxt; nxt = t_;
         }
-        if (split) {                                           // the caller's stream continues behind both halves (and the
+        if (sp.on) {                                           // the caller's stream continues behind both halves (and the
             // next run's table is not written under the second half) -- ALSO when a launch failed mid-run: the caller
             // frees x / x_alt / eps on the error path, the work already queued on the second stream must be behind `st`
-            if (hipEventRecord(ev_done, sx) != hipSuccess || hipStreamWaitEvent(st, ev_done, 0) != hipSuccess) {
-                (void)hipStreamSynchronize(sx);
+            if (hipEventRecord(sp.ev_done, k.sx) != hipSuccess || hipStreamWaitEvent(k.st, sp.ev_done, 0) != hipSuccess) {
+                (void)hipStreamSynchronize(k.sx);
                 if (!rc) rc = SINDDM_E_BADARG;
             }
         }
         i0 += len;
     }
-    if (split) {
-        (void)hipEventDestroy(ev_go);                          // (destruction is deferred until the recorded work is done)
-        (void)hipEventDestroy(ev_done);
+    *result = cur;
+    return rc;
+}
+
+// The body of every sinddm_sample_chain* entry point.  r.Hc x r.Wc is the CENTRE size; the steps run on the extended shape
+// H x W = (Hc + 2 halo_y) x (Wc + 2 halo_x), which is what every buffer has.  With a halo, the halo of every step's output
+// is refreshed from its centre (wrap_halo_launch, per half-batch on its own stream), and that of `x` once on entry: the
+// zero padding of the convolutions then never reaches the centre (SINDDM_TILE_HALO).  The error code of a defective call
+// is decided in this order: chain_check, the plan, batch_strides, the workspace.
+static int sample_chain_impl(const ChainRun& r) {
+    ChainCtx k{r};
+    if (const int rc = chain_check(r, &k.c)) return rc;
+    const int H = k.c.H, W = k.c.W;
+    k.p = make_plan(r.dim);
+    if (!k.p.ok) return SINDDM_E_BADSHAPE;
+    // per-sample maps (batch_check.h): the strides of step_tail.h; all 0 without the block, and nothing below differs then
+    if (const int rc = batch_strides(&r.batch, r.edit_w, r.edit_c, r.keep_m, r.keep_x0, r.layout, H, W,
+                                     (H * W) % 4 == 0 && fwd_pitch(k.p, W) == W, &k.bs))
+        return rc;
+    if (k.c.lay_g) {                                           // (the layout block is read only by a run that pulls)
+        k.lay = layout_geom(r.Hc, r.Wc, r.halo_y, r.halo_x, r.layout_down, false, false);
+        k.lay.sl = k.bs.sl;
+        k.lay_gain = r.batch.layout_gain;
+    }
+    if (r.ws_bytes < fwd_workspace_bytes(k.p, r.B, H, W)) return SINDDM_E_WORKSPACE;
+    k.st = static_cast<hipStream_t>(r.stream);
+    k.sx = static_cast<hipStream_t>(r.aux_stream);
+    k.cond_tab = static_cast<float*>(r.ws);
+    k.fuse_tail = (H * W) % 4 == 0 || fwd_pitch(k.p, W) != W;           // (padded rows: their own fused tail kernel)
+    if (const int rc = chain_split(k)) return rc;
+    float* result = r.x;
+    const int rc = chain_enqueue(k, &result);
+    if (k.sp.on) {
+        (void)hipEventDestroy(k.sp.ev_go);                     // (destruction is deferred until the recorded work is done)
+        (void)hipEventDestroy(k.sp.ev_done);
     }
     if (rc) return rc;
-    if (result_in_alt) *result_in_alt = (cur == x_alt) ? 1 : 0;
+    if (r.result_in_alt) *r.result_in_alt = (result == r.x_alt) ? 1 : 0;
     return 0;
 }
 
-int sinddm_sample_chain_ex(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                           const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                           uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                           void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+// Every entry: the 21 arguments they share (CHAIN_SHARED), then the options its signature can express.
+#define CHAIN_SHARED_PARAMS                                                                                                       \
+    const float *params, const float *packed, float *x, float *x_alt, float *eps, const float *x_tilde,                          \
+        const sinddm_step_coefs *coefs, const int *t_list, int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, \
+        int B, int H, int W, void *ws, size_t ws_bytes, void *stream
+#define CHAIN_SHARED(aux)                                                                                                          \
+    chain_run_fill(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W, ws,     \
+                   ws_bytes, stream, aux, result_in_alt)
+
+int sinddm_sample_chain(CHAIN_SHARED_PARAMS, int* result_in_alt) {
+    return sample_chain_impl(CHAIN_SHARED(nullptr));
 }
 
-int sinddm_sample_chain_tile(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                             const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                             uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, nullptr, nullptr, nullptr, nullptr, nullptr);
+int sinddm_sample_chain2(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt) {
+    return sample_chain_impl(CHAIN_SHARED(aux_stream));
 }
 
-int sinddm_sample_chain_keep(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                             const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                             uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                             void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                             const sinddm_keep_opts* keep) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, nullptr, nullptr, nullptr, nullptr);
+int sinddm_sample_chain_ex(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts);
+    return sample_chain_impl(r);
 }
 
-int sinddm_sample_chain_seeds(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                              const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, nullptr, nullptr, nullptr);
+int sinddm_sample_chain_tile(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                             int halo_x) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts);
+    r.halo_y = halo_y; r.halo_x = halo_x;
+    return sample_chain_impl(r);
 }
 
-int sinddm_sample_chain_resample(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                                 const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                                 uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                                 void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                                 const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, nullptr, nullptr);
+int sinddm_sample_chain_keep(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                             int halo_x, const sinddm_keep_opts* keep) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep);
+    r.halo_y = halo_y; r.halo_x = halo_x;
+    return sample_chain_impl(r);
 }
 
-int sinddm_sample_chain_layout(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                               const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                               uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                               void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                               const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
-                               const sinddm_layout_opts* lo) {
-    return sinddm_sample_chain_batch(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H,
-                                     W, ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs,
-                                     lo, nullptr);
+int sinddm_sample_chain_seeds(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                              int halo_x, const sinddm_keep_opts* keep, const uint64_t* sample_seeds) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep);
+    r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
+    return sample_chain_impl(r);
 }
 
-int sinddm_sample_chain_batch(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                              const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                              uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                              void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y, int halo_x,
-                              const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
-                              const sinddm_layout_opts* lo, const sinddm_batch_opts* bo) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, opts, halo_y, halo_x, keep, sample_seeds, rs, lo, bo);
+int sinddm_sample_chain_resample(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts,
+                                 int halo_y, int halo_x, const sinddm_keep_opts* keep, const uint64_t* sample_seeds,
+                                 const sinddm_resample_opts* rs) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep); chain_run_set(r, rs);
+    r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
+    return sample_chain_impl(r);
 }
 
-int sinddm_sample_chain2(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                         const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                         uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                         void* aux_stream, int* result_in_alt) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, aux_stream, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+int sinddm_sample_chain_layout(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                               int halo_x, const sinddm_keep_opts* keep, const uint64_t* sample_seeds,
+                               const sinddm_resample_opts* rs, const sinddm_layout_opts* lo) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep); chain_run_set(r, rs); chain_run_set(r, lo);
+    r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
+    return sample_chain_impl(r);
 }
 
-int sinddm_sample_chain(const float* params, const float* packed, float* x, float* x_alt, float* eps, const float* x_tilde,
-                        const sinddm_step_coefs* coefs, const int* t_list, int n_steps, float scale, uint64_t seed,
-                        uint64_t stream_id0, int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
-                        int* result_in_alt) {
-    return sample_chain_impl(params, packed, x, x_alt, eps, x_tilde, coefs, t_list, n_steps, scale, seed, stream_id0, dim, B, H, W,
-                             ws, ws_bytes, stream, nullptr, result_in_alt, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+int sinddm_sample_chain_batch(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                              int halo_x, const sinddm_keep_opts* keep, const uint64_t* sample_seeds,
+                              const sinddm_resample_opts* rs, const sinddm_layout_opts* lo, const sinddm_batch_opts* bo) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep); chain_run_set(r, rs); chain_run_set(r, lo); chain_run_set(r, bo);
+    r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
+    return sample_chain_impl(r);
 }
+#undef CHAIN_SHARED
+#undef CHAIN_SHARED_PARAMS
 
 int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                              const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, int B, int C,
                              int HW, void* stream) {
-    if (!x_t || !eps || !noise || !out || !coefs || !edit_w || !edit_c || B <= 0 || C <= 0 || HW <= 0)
-        return SINDDM_E_BADARG;
-    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
+    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c);
+    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !edit_w || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
     if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
-    TailArgs t{};
-    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
     return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)B * C * HW, C * HW, HW, stream);
 }
 
 int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                              const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, const float* keep_m,
                              const float* keep_x0, float keep_a, float keep_b, int B, int C, int HW, void* stream) {
-    if (!x_t || !eps || !noise || !out || !coefs || !keep_m || !keep_x0 || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
-    if ((edit_w == nullptr) != (edit_c == nullptr)) return SINDDM_E_BADARG;
-    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
+    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b);
+    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !keep_m || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
     if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
-    TailArgs t{};
-    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
-    t.km = keep_m; t.kx = keep_x0; t.ka = keep_a; t.kb = keep_b;
     return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)B * C * HW, C * HW, HW, stream);
 }
 
@@ -1677,17 +1688,14 @@ int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_
                              float* out, const sinddm_step_coefs* coefs, const sinddm_jump_coefs* jump, const float* edit_w,
                              const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B, int C,
                              int HW, void* stream) {
-    if (!x_t || !eps || !noise || !jump_noise || !out || !coefs || !jump || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
-    if ((edit_w == nullptr) != (edit_c == nullptr) || (keep_m == nullptr) != (keep_x0 == nullptr)) return SINDDM_E_BADARG;
-    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
+    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_m ? keep_a : 1.0f, keep_m ? keep_b : 0.0f);
+    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !jump_noise || !jump || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
     if (!jump_valid(*jump, *coefs)) return SINDDM_E_BADARG;
     if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
-    TailArgs t{};
-    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
-    t.km = keep_m; t.kx = keep_x0; t.ka = keep_m ? keep_a : 1.0f; t.kb = keep_m ? keep_b : 0.0f;
     JumpArgs jp{};
     jp.r = jump->r; jp.s = jump->s; jp.d = jump->d; jp.nz = jump_noise;
-    return jump_launch(x_t, eps, x_tilde, out, t, jp, B, C * HW, HW, static_cast<hipStream_t>(stream));
+    const TailIO io{x_t, eps, x_tilde, out, B, C * HW, HW, static_cast<hipStream_t>(stream)};
+    return jump_launch(io, t, jp);
 }
 
 int sinddm_layout_delta(const float* x_t, const float* eps, const float* x_tilde, const float* layout, float* delta,
@@ -1699,27 +1707,24 @@ int sinddm_layout_delta(const float* x_t, const float* eps, const float* x_tilde
     if ((long long)B * CHANNELS > 65535 || (H + down - 1) / down > 65535) return SINDDM_E_BADSHAPE;
     LayoutArgs g = layout_geom(H, W, halo_y, halo_x, down, false, false);
     g.D = delta;
-    TailArgs t{};
-    t.k = *coefs; t.ew = edit_w; t.ec = edit_c;
-    return layout_delta_launch(x_t, eps, x_tilde, layout, t, g, B, static_cast<hipStream_t>(stream));
+    const TailArgs t = step_tail_args(coefs, nullptr, edit_w, edit_c);
+    const TailIO io{x_t, eps, x_tilde, nullptr, B, 0, 0, static_cast<hipStream_t>(stream)};      // (the delta launch reads no extent)
+    return layout_delta_launch(io, layout, t, g);
 }
 
 int sinddm_reverse_step_layout(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                                const sinddm_step_coefs* coefs, const float* delta, float g, int down, const float* edit_w,
                                const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B,
                                int H, int W, int halo_y, int halo_x, int wrap_y, int wrap_x, void* stream) {
-    if (!x_t || !eps || !noise || !out || !coefs || !delta || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_m ? keep_a : 1.0f, keep_m ? keep_b : 0.0f);
+    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !delta || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
     if (down < 1 || down > 64 || !(g >= 0.0f && g <= 1.0f)) return SINDDM_E_BADARG;
     if (halo_y < 0 || halo_x < 0 || halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;
-    if ((edit_w == nullptr) != (edit_c == nullptr) || (keep_m == nullptr) != (keep_x0 == nullptr)) return SINDDM_E_BADARG;
-    if (coefs->mode != 0 && !x_tilde) return SINDDM_E_BADARG;
     LayoutArgs la = layout_geom(H, W, halo_y, halo_x, down, wrap_y != 0, wrap_x != 0);
     if ((long long)CHANNELS * la.H * la.W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
     la.D = delta; la.g = g;
-    TailArgs t{};
-    t.k = *coefs; t.nz = noise; t.ew = edit_w; t.ec = edit_c;
-    t.km = keep_m; t.kx = keep_x0; t.ka = keep_m ? keep_a : 1.0f; t.kb = keep_m ? keep_b : 0.0f;
-    return layout_step_launch(x_t, eps, x_tilde, out, t, la, B, CHANNELS * la.H * la.W, la.H * la.W, static_cast<hipStream_t>(stream));
+    const TailIO io{x_t, eps, x_tilde, out, B, CHANNELS * la.H * la.W, la.H * la.W, static_cast<hipStream_t>(stream)};
+    return layout_step_launch(io, t, la);
 }
 
 #ifdef W2_PHASE

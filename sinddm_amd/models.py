@@ -397,6 +397,107 @@ class SinDDMNet(nn.Module):
 # --------------------------------------------------------------------------------------------
 # diffusion process
 # --------------------------------------------------------------------------------------------
+def _at(arr, i0: int, ctype, per: int = 1):
+    """&arr[per * i0] of a ctypes array of `ctype`, as the pointer a call takes (None stays NULL)."""
+    return None if arr is None else C.cast(C.addressof(arr) + per * i0 * C.sizeof(ctype), C.POINTER(ctype))
+
+
+class _ChainCall:
+    """The buffers and option blocks of one chain run of `MultiScaleGaussianDiffusion._run_steps`: the steps `t_seq` (already
+    expanded by `jump_to`) of scale s on `img`, through sinddm_sample_chain_batch -- the entry that can express every option;
+    one that is off goes in as NULL, which is the call without it, launch for launch.  Every tensor and ctypes array the
+    library reads through a raw pointer is an attribute here, so it lives as long as the object."""
+
+    def __init__(self, d, img, s, t_seq, jump_to, *, roi, keep, lay, lay_g):
+        self.lib, self.net, self.s = _lib.load(), d.denoise_fn, s
+        hy, hx = self.halo = d._tile_halo()
+        tiled = self.tiled = bool(hy or hx)
+        wrap = (lambda t: d._wrap_pad(t, hy, hx)) if tiled else (lambda t: t)
+        self.Hc, self.Wc = int(img.shape[2]), int(img.shape[3])    # the sample's own size; H, W below: the buffers' size
+        x = self.x = d._wrap_pad(img, hy, hx) if tiled else img.contiguous().clone()
+        self.x_alt, self.eps = torch.empty_like(x), torch.empty_like(x)
+        B, _, H, W = x.shape
+        tab = d._coef_table(s)
+        n = len(t_seq)
+        self.coefs = (_lib.StepCoefs * n)(*[tab[t] for t in t_seq])
+        self.tl = (C.c_int * n)(*t_seq)
+        self.xt = None
+        if self.coefs[0].mode != 0 or self.coefs[n - 1].mode != 0:
+            xt = d.img_prev_upsample
+            if xt is None:
+                raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
+            if xt.shape != img.shape or xt.dtype != x.dtype or xt.device != x.device:
+                # (the library takes raw pointers: a mismatching x-tilde would be read out of bounds)
+                raise _lib.SinddmError(f"img_prev_upsample {tuple(xt.shape)} {xt.dtype} {xt.device} does not match the "
+                                       f"running sample {tuple(img.shape)} {x.dtype} {x.device}")
+            self.xt = d._wrap_pad(xt, hy, hx) if tiled else xt.contiguous()
+        self.packed = self.net.packed_weights()
+        self.ws = _workspace(x.device, self.lib.sinddm_workspace_bytes(self.net.dim, B, H, W))
+        self.opts = _lib.ChainOpts()
+        if roi:
+            ew, ec = d.roi_edit_maps(s, self.Hc, self.Wc, x.device)
+            if ew.dim() == 3 and ew.shape[0] != B:                         # (raw pointers: B slices are read)
+                raise ValueError(f"roi_bbs_batch has {ew.shape[0]} box lists, the batch {B} samples")
+            self.edit = ew, ec = wrap(ew), wrap(ec)
+            self.opts.edit_w, self.opts.edit_c = _lib.ptr(ew), _lib.ptr(ec)
+        self.kopts = self.ab = None
+        if keep is not None:
+            self.keep = km, kx = wrap(keep[0]), wrap(keep[1])
+            ab_tab = d._keep_ab_table()
+            self.ab = (C.c_float * (2 * n))(*[float(v) for t in t_seq for v in ab_tab[t]])
+            self.kopts = _lib.KeepOpts()
+            self.kopts.mask, self.kopts.x0 = _lib.ptr(km), _lib.ptr(kx)
+        self.ropts = self.jumps = None
+        if jump_to is not None:
+            jt = d._jump_table(s)
+            self.jumps = (_lib.JumpCoefs * n)(*[_lib.JumpCoefs(0, 0.0, 0.0, 0.0) if l2 is None
+                                                else _lib.JumpCoefs(1, *jt(t - 1, l2)) for t, l2 in zip(t_seq, jump_to)])
+            self.ropts = _lib.ResampleOpts()
+        self.lopts = self.garr = self.bopts = None
+        self.gain = d._layout_gain_for(B, x.device) if lay is not None else None
+        per = (int(roi and ew.dim() == 3), int(keep is not None and km.dim() == 3), int(keep is not None and kx.dim() == 4),
+               int(lay is not None and lay[0].dim() == 4))
+        if any(per) or self.gain is not None:
+            self.bopts = _lib.BatchOpts(*per, _lib.ptr(self.gain))
+        if lay is not None:
+            self.lay_map = wrap(lay[0])
+            self.lay_delta = torch.empty(B * 3 * (-(-self.Hc // lay[1])) * (-(-self.Wc // lay[1])), dtype=x.dtype, device=x.device)
+            self.garr = (C.c_float * n)(*lay_g)
+            self.lopts = _lib.LayoutOpts()
+            self.lopts.layout, self.lopts.down, self.lopts.delta = _lib.ptr(self.lay_map), lay[1], _lib.ptr(self.lay_delta)
+        # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
+        self.aux = _aux_stream(x.device) if d.two_streams else None
+
+    def call(self, i0, k, seed, noise=None, sid0=0, seeds_dev=None, jump_noise=None):
+        """Steps [i0, i0 + k) of the run: `noise` / `jump_noise` recorded draws of exactly these steps, or the in-kernel draws
+        of `seeds_dev` (one seed per sample) or `seed`, at stream ids sid0 + 0 ... k - 1."""
+        x, net, ref = self.x, self.net, (lambda o: C.byref(o) if o is not None else None)
+        self.opts.noise = _lib.ptr(noise)
+        if self.kopts is not None:
+            self.kopts.ab = _at(self.ab, i0, C.c_float, 2)
+        if self.ropts is not None:
+            self.ropts.jumps, self.ropts.noise = _at(self.jumps, i0, _lib.JumpCoefs), _lib.ptr(jump_noise)
+        if self.lopts is not None:
+            self.lopts.g = _at(self.garr, i0, C.c_float)
+        in_alt = C.c_int(0)
+        _lib.check(self.lib.sinddm_sample_chain_batch(
+            _lib.ptr(net.flat_params), _lib.ptr(self.packed), _lib.ptr(x), _lib.ptr(self.x_alt), _lib.ptr(self.eps),
+            _lib.ptr(self.xt), _at(self.coefs, i0, _lib.StepCoefs), _at(self.tl, i0, C.c_int), k, float(self.s), seed, sid0,
+            net.dim_arg, x.shape[0], self.Hc, self.Wc, self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr(x.device), self.aux,
+            C.byref(in_alt), C.byref(self.opts), *self.halo, ref(self.kopts), _lib.ptr(seeds_dev), ref(self.ropts),
+            ref(self.lopts), ref(self.bopts)), "sinddm_sample_chain_batch")
+        if in_alt.value:
+            self.x, self.x_alt = self.x_alt, self.x
+
+    def centre(self, t: torch.Tensor) -> torch.Tensor:
+        """The sample's own pixels of a (B, 3, H, W) buffer of the run's extended size (a view)."""
+        hy, hx = self.halo
+        return t[:, :, hy:hy + self.Hc, hx:hx + self.Wc]
+
+    def result(self) -> torch.Tensor:
+        return self.centre(self.x).contiguous() if self.tiled else self.x
+
+
 class MultiScaleGaussianDiffusion(nn.Module):
     """Multi-scale DDPM with SinDDM's re-blurring (reference SinDDM/models.py:155-631)."""
 
@@ -950,37 +1051,35 @@ class MultiScaleGaussianDiffusion(nn.Module):
         return ext
 
     def _run_steps(self, img: torch.Tensor, s: int, t_seq) -> torch.Tensor:
-        """The reverse steps `t_seq` of scale s (the loop bodies of models.py:477-485,536-546).  Production path: ONE
-        library call for the whole run (sinddm_sample_chain_ex) -- the per-step scalars come from a prebuilt table, the
-        states ping-pong between two buffers, the N(0,1) draws of models.py:455 are generated inside the step kernel,
-        and Python is not entered between steps.  ROI guidance (every scale but the finest) rides the same call: its
-        edit maps go to the fused step kernels (`chain_guided = False` sends it down the step-by-step route).  Injected
-        noise (`noise_fn`) takes the step-by-step path, which the parity fixtures pin, unless `chain_noise` is set: then
-        the same draws, fetched in the same order, are handed to the chain call as buffers of at most
-        CHAIN_NOISE_BYTES.  CLIP guidance, intermediate dumps, foreign denoisers and CPU tensors are step by step.
-        With `tile` set the run works on the sample extended by the wrapped halo (sinddm_sample_chain_tile: the state,
-        x-tilde, the edit maps and the noise buffers all have the extended size) and returns the centre; the in-kernel
-        draws are keyed on the extended index, so a tiled and a plain run of one seed are unrelated.  The step-by-step
-        route extends each network input instead (`_eps`) and steps the centre: it is the cross-check of the tiled chain.
-        With `keep_maps` set the scale's mask and known image (wrapped like the edit maps when tiled) and the per-step
-        forward scalars go to sinddm_sample_chain_keep: still one call, with ROI maps, `chain_noise` and two streams alike;
-        the step-by-step route replaces through sinddm_reverse_step_keep.
-        With `sample_seeds` set the call is sinddm_sample_chain_seeds: sample b's step at position i of the run draws
-        sinddm_normal_fill(3 H W, seed_b, noise_stream_id(s, 'step', i)) inside the step kernel, and no seed is taken from
-        torch's generator; the step-by-step route fills the same numbers through sinddm_normal_fill_samples.
-        With `resample` = (R, J), R > 1, `t_seq` is expanded by functions.resample_schedule and the run is ONE
-        sinddm_sample_chain_resample call on every route above (in-kernel noise, `chain_noise` buffers with a 'jump' draw per
-        jump, seeds, tiled): a step that is followed by a jump ends in the step + jump kernel instead of its fused tail.  The
-        step-by-step route goes through sinddm_reverse_step_jump.  `draw_log` gets ("chain_resample", s, seed or seeds,
-        expanded t list, jump targets).
-        With `layout_maps` set at this scale the run is ONE sinddm_sample_chain_layout call on every route above: the steps
-        with t >= layout_t_min run unfused (network, block-delta kernel, layout tail), the others keep their fused tail; the
-        draws and `draw_log` entries are those of the run without it.  The step-by-step route goes through
-        sinddm_layout_delta + sinddm_reverse_step_layout.
-        With a per-sample map or `layout_gain` (a leading batch dimension on a keep / layout map, `roi_bbs_batch`) the run is
-        ONE sinddm_sample_chain_batch call: the maps are wrapped like shared ones when tiled, the draws and `draw_log` entries
-        are unchanged.  Every other run keeps the entry it takes above.  The step-by-step route makes B = 1 calls of the
-        single-step entries on each sample's slices."""
+        """The reverse steps `t_seq` of scale s (the loop bodies of models.py:477-485,536-546).  Production path: library
+        calls that each run many steps (`_ChainCall`) -- the per-step scalars come from a prebuilt table, the states ping-pong
+        between two buffers, the N(0,1) draws of models.py:455 are generated inside the step kernel, and Python is not entered
+        between steps.  CLIP guidance, intermediate dumps, foreign denoisers, CPU tensors, ROI guidance with
+        `chain_guided = False` and `noise_fn` without `chain_noise` go step by step instead (`_p_sample_host_t`, the route
+        the parity fixtures pin), which honours every option below through the single-step entries.
+
+        The options of a run, carried by the same call and free to combine except where noted:
+          ROI guidance   (every scale but the finest) the edit maps act in the step kernels.
+          `tile`         the run works on the sample extended by the wrapped halo -- state, x-tilde, every map and the noise
+                         buffers have the extended size -- and returns the centre.  In-kernel draws are keyed on the extended
+                         index: a tiled and a plain run of one seed are unrelated.  The step-by-step route extends each
+                         network input instead (`_eps`) and steps the centre: the cross-check of the tiled chain.
+          `keep_maps`    the scale's mask and known image and the per-step forward scalars: known pixels are replaced inside
+                         every step.
+          `resample`     (R, J), R > 1: `t_seq` is expanded by functions.resample_schedule; a step that is followed by a jump
+                         ends in the step + jump kernel instead of its fused tail.
+          `layout_maps`  the steps with t >= layout_t_min run unfused (network, block-delta kernel, layout tail), the others
+                         keep their fused tail.  Not with `resample`.
+          per sample     a leading batch dimension on a keep / layout map, `roi_bbs_batch`, `layout_gain`: sample b reads
+                         slice b.  Neither this nor a layout changes the draws or the `draw_log` entries.
+        The noise is one of three:
+          `noise_fn` + `chain_noise`   the draws the step-by-step loop would fetch, in its order ('step' per step, 'jump' per
+                         jump), handed over as buffers of at most CHAIN_NOISE_BYTES: one call per piece.
+          `sample_seeds` sample b's step at position i of the run draws sinddm_normal_fill(3 H W, seed_b,
+                         noise_stream_id(s, 'step', i)) in the step kernel; torch's generator is not touched.  `draw_log`:
+                         ("chain_seeds", s, seeds, t list), or ("chain_resample", s, seeds, expanded t list, jump targets).
+          otherwise      one 62-bit seed from torch's CPU generator keys the in-kernel draws.  `draw_log`: ("chain", s, seed,
+                         t list), tiled ("chain_tile", ..., (hy, hx)), resampled ("chain_resample", s, seed, ..., jump targets)."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
         lay = self._layout_entry(s, img)                       # (raises with `resample` / CLIP guidance)
@@ -1007,108 +1106,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 img = self._p_sample_host_t(img, i, s, step_pos=pos, jump_to=jump_to[pos] if jump_to else None)
                 self._dump_interm(img, s, f'output_t-{i:03}_s-{s}.png')
             return img
-        lib = _lib.load()
-        net = self.denoise_fn
-        hy, hx = self._tile_halo()
-        tiled = bool(hy or hx)
-        Hc, Wc = int(img.shape[2]), int(img.shape[3])              # the sample's own size; H, W below: the buffers' size
-        x = self._wrap_pad(img, hy, hx) if tiled else img.contiguous().clone()
-        x_alt = torch.empty_like(x)
-        eps = torch.empty_like(x)
-        B, Cc, H, W = x.shape
-        tab = self._coef_table(s)
-        n = len(t_seq)
-        coefs = (_lib.StepCoefs * n)(*[tab[t] for t in t_seq])
-        tl = (C.c_int * n)(*t_seq)
-        xt = None
-        if coefs[0].mode != 0 or coefs[n - 1].mode != 0:
-            xt = self.img_prev_upsample
-            if xt is None:
-                raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
-            if xt.shape != img.shape or xt.dtype != x.dtype or xt.device != x.device:
-                # (the library takes raw pointers: a mismatching x-tilde would be read out of bounds)
-                raise _lib.SinddmError(f"img_prev_upsample {tuple(xt.shape)} {xt.dtype} {xt.device} does not match the "
-                                       f"running sample {tuple(img.shape)} {x.dtype} {x.device}")
-            xt = self._wrap_pad(xt, hy, hx) if tiled else xt.contiguous()
-        packed = net.packed_weights()
-        ws = _workspace(x.device, lib.sinddm_workspace_bytes(net.dim, B, H, W))
-        opts = _lib.ChainOpts()
-        if roi:
-            ew, ec = self.roi_edit_maps(s, Hc, Wc, x.device)               # (cached on self: alive for the call)
-            if ew.dim() == 3 and ew.shape[0] != B:                         # (raw pointers: B slices are read)
-                raise ValueError(f"roi_bbs_batch has {ew.shape[0]} box lists, the batch {B} samples")
-            if tiled:                                                      # (locals of this frame: alive for the call)
-                ew, ec = self._wrap_pad(ew, hy, hx), self._wrap_pad(ec, hy, hx)
-            opts.edit_w, opts.edit_c = _lib.ptr(ew), _lib.ptr(ec)
-        kopts = None
-        if keep is not None:
-            km, kx = (self._wrap_pad(keep[0], hy, hx), self._wrap_pad(keep[1], hy, hx)) if tiled else keep
-            ab_tab = self._keep_ab_table()
-            ab = (C.c_float * (2 * n))(*[float(v) for t in t_seq for v in ab_tab[t]])
-            kopts = _lib.KeepOpts()
-            kopts.mask, kopts.x0 = _lib.ptr(km), _lib.ptr(kx)
-        ropts = None
-        if jump_to is not None:
-            jt = self._jump_table(s)
-            jumps = (_lib.JumpCoefs * n)(*[_lib.JumpCoefs(0, 0.0, 0.0, 0.0) if l2 is None else _lib.JumpCoefs(1, *jt(t - 1, l2))
-                                           for t, l2 in zip(t_seq, jump_to)])
-            ropts = _lib.ResampleOpts()
-        lopts = None
-        bopts = None
-        gain = self._layout_gain_for(B, x.device) if lay is not None else None
-        per = (int(roi and ew.dim() == 3), int(keep is not None and km.dim() == 3), int(keep is not None and kx.dim() == 4),
-               int(lay is not None and lay[0].dim() == 4))
-        if any(per) or gain is not None:
-            bopts = _lib.BatchOpts(*per, _lib.ptr(gain))               # (`gain`: a local of this frame, alive for the call)
-        if lay is not None:
-            lay_map = self._wrap_pad(lay[0], hy, hx) if tiled else lay[0]  # (locals of this frame: alive for the call)
-            lay_delta = torch.empty(B * 3 * (-(-Hc // lay[1])) * (-(-Wc // lay[1])), dtype=x.dtype, device=x.device)
-            garr = (C.c_float * n)(*lay_g)
-            lopts = _lib.LayoutOpts()
-            lopts.layout, lopts.down, lopts.delta = _lib.ptr(lay_map), lay[1], _lib.ptr(lay_delta)
-        aux = _aux_stream(x.device) if self.two_streams else None
-        # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
-
-        def chain(i0, k, seed, noise, sid0=0, seeds_dev=None, jump_noise=None):
-            nonlocal x, x_alt
-            opts.noise = _lib.ptr(noise)
-            in_alt = C.c_int(0)
-            args = (_lib.ptr(net.flat_params), _lib.ptr(packed), _lib.ptr(x), _lib.ptr(x_alt), _lib.ptr(eps), _lib.ptr(xt),
-                    C.cast(C.addressof(coefs) + i0 * C.sizeof(_lib.StepCoefs), C.POINTER(_lib.StepCoefs)),
-                    C.cast(C.addressof(tl) + i0 * C.sizeof(C.c_int), C.POINTER(C.c_int)), k, float(s), seed, sid0, net.dim_arg,
-                    B, Hc, Wc, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device), aux, C.byref(in_alt), C.byref(opts))
-            if kopts is not None:
-                kopts.ab = C.cast(C.addressof(ab) + 2 * i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
-            if bopts is not None:
-                if lopts is not None:
-                    lopts.g = C.cast(C.addressof(garr) + i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
-                if ropts is not None:
-                    ropts.jumps = C.cast(C.addressof(jumps) + i0 * C.sizeof(_lib.JumpCoefs), C.POINTER(_lib.JumpCoefs))
-                    ropts.noise = _lib.ptr(jump_noise)
-                ref = lambda o: C.byref(o) if o is not None else None
-                _lib.check(lib.sinddm_sample_chain_batch(*args, hy, hx, ref(kopts), _lib.ptr(seeds_dev), ref(ropts), ref(lopts),
-                                                         C.byref(bopts)), "sinddm_sample_chain_batch")
-            elif lopts is not None:
-                lopts.g = C.cast(C.addressof(garr) + i0 * C.sizeof(C.c_float), C.POINTER(C.c_float))
-                _lib.check(lib.sinddm_sample_chain_layout(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
-                                                          _lib.ptr(seeds_dev), None, C.byref(lopts)), "sinddm_sample_chain_layout")
-            elif ropts is not None:
-                ropts.jumps = C.cast(C.addressof(jumps) + i0 * C.sizeof(_lib.JumpCoefs), C.POINTER(_lib.JumpCoefs))
-                ropts.noise = _lib.ptr(jump_noise)
-                _lib.check(lib.sinddm_sample_chain_resample(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
-                                                            _lib.ptr(seeds_dev), C.byref(ropts)), "sinddm_sample_chain_resample")
-            elif seeds_dev is not None:
-                _lib.check(lib.sinddm_sample_chain_seeds(*args, hy, hx, C.byref(kopts) if kopts is not None else None,
-                                                         _lib.ptr(seeds_dev)), "sinddm_sample_chain_seeds")
-            elif kopts is not None:
-                _lib.check(lib.sinddm_sample_chain_keep(*args, hy, hx, C.byref(kopts)), "sinddm_sample_chain_keep")
-            elif tiled:
-                _lib.check(lib.sinddm_sample_chain_tile(*args, hy, hx), "sinddm_sample_chain_tile")
-            else:
-                _lib.check(lib.sinddm_sample_chain_ex(*args), "sinddm_sample_chain_ex")
-            if in_alt.value:
-                x, x_alt = x_alt, x
-
+        run = _ChainCall(self, img, s, t_seq, jump_to, roi=roi, keep=keep, lay=lay, lay_g=lay_g)
+        n, x, tiled = len(t_seq), run.x, run.tiled
         if self.noise_fn is not None:
             # recorded noise: pieces of as many steps as fit the byte budget; each piece's draws are fetched exactly as the
             # step-by-step loop fetches them (one `_draw("step", ...)` per step, t = 0 included, in step order) and the
@@ -1125,20 +1124,21 @@ class MultiScaleGaussianDiffusion(nn.Module):
                     jn = (torch.zeros if tiled else torch.empty)((nj,) + tuple(x.shape), dtype=x.dtype, device=x.device)
                 nj = 0
                 for j in range(k):
-                    noise[j][:, :, hy:hy + Hc, hx:hx + Wc].copy_(self._draw("step", img.shape, s, t_seq[i0 + j], x.device))
+                    run.centre(noise[j]).copy_(self._draw("step", img.shape, s, t_seq[i0 + j], x.device))
                     if jump_to is not None and jump_to[i0 + j] is not None:
-                        jn[nj][:, :, hy:hy + Hc, hx:hx + Wc].copy_(self._draw("jump", img.shape, s, t_seq[i0 + j], x.device))
+                        run.centre(jn[nj]).copy_(self._draw("jump", img.shape, s, t_seq[i0 + j], x.device))
                         nj += 1
-                chain(i0, k, 0, noise, jump_noise=jn)
-            return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
+                run.call(i0, k, 0, noise=noise, jump_noise=jn)
+            return run.result()
         if sseeds is not None:
             if self.draw_log is not None:
                 # (draw i of sample b is sinddm_normal_fill(3 H W, seeds[b], noise_stream_id(s, 'step', i)), over the
                 # extended size when tiled)
                 self.draw_log.append(("chain_resample", s, list(sseeds), list(t_seq), list(jump_to)) if jump_to is not None
                                      else ("chain_seeds", s, list(sseeds), list(t_seq)))
-            chain(0, n, 0, None, noise_stream_id(s, "step", 0), torch.tensor(sseeds, dtype=torch.int64, device=x.device))
-            return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
+            run.call(0, n, 0, sid0=noise_stream_id(s, "step", 0),
+                     seeds_dev=torch.tensor(sseeds, dtype=torch.int64, device=x.device))
+            return run.result()
         # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
         # sample, seeding only the CUDA generator (torch.cuda.manual_seed) does not
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
@@ -1148,9 +1148,9 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 # (the jump after step i draws sinddm_normal_fill(seed, i + 2^31) on top, over the same tensor)
                 self.draw_log.append(("chain_resample", s, seed, list(t_seq), list(jump_to)))
             else:
-                self.draw_log.append(("chain_tile", s, seed, list(t_seq), (hy, hx)) if tiled else ("chain", s, seed, list(t_seq)))
-        chain(0, n, seed, None)
-        return x[:, :, hy:hy + Hc, hx:hx + Wc].contiguous() if tiled else x
+                self.draw_log.append(("chain_tile", s, seed, list(t_seq), run.halo) if tiled else ("chain", s, seed, list(t_seq)))
+        run.call(0, n, seed)
+        return run.result()
 
     def _eps(self, x, t_dev, t_host, s):
         hy, hx = self._tile_halo()

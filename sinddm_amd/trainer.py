@@ -483,10 +483,11 @@ class MultiscaleTrainer(object):
                             per_sample=False):
         """ROI guided generation (trainer.py:436-454): at every scale but the finest the predicted clean image is
         pulled (eta = 0.8) towards a patch of the training image inside the given boxes; the blend runs inside the
-        step kernels of the sampler's chain call (`sinddm_sample_chain_ex` with edit maps: one library call per scale,
+        step kernels of the sampler's chain call (the edit maps of `sinddm_chain_opts`: one library call per scale,
         step noise from the in-kernel Philox stream).  With a `noise_fn`, or with `ema_model.chain_guided = False`,
         the run goes step by step through `sinddm_reverse_step_edit`.  `per_sample`: `roi_bb_list` holds `batch_size` box
-        lists, one job per sample (`ema_model.roi_bbs_batch` -> sinddm_sample_chain_batch); the target patch stays shared."""
+        lists, one job per sample (`ema_model.roi_bbs_batch` -> the per-sample flags of `sinddm_batch_opts`); the target
+        patch stays shared."""
         from .functions import extract_patch
         em = self.ema_model
         if per_sample and len(roi_bb_list) != int(batch_size):
@@ -530,13 +531,14 @@ class MultiscaleTrainer(object):
         pixel, 0 = generate.  At every scale the known image is that scale's training image and the mask comes from
         `functions.keep_mask_pyramid` (`hard`: a coarse pixel is kept only if its whole footprint is known); after every
         reverse step the known pixels are overwritten with the forward-diffused training image of that noise level, inside
-        the step kernels (`ema_model.keep_maps` -> sinddm_sample_chain_keep: one library call per scale).  `resample` = R > 1
-        adds RePaint's resampling: at every level that is a multiple of `jump_length` = J the run jumps back up by J levels
-        and comes down again, until the stretch has been walked R times (`ema_model.resample` -> functions.resample_schedule
-        and sinddm_sample_chain_resample: still one library call per scale, R times the network evaluations on the
-        resampled stretches).  The defaults (1, 1) are the run without jumps, bit for bit.  No image-quality claim is made.
+        the step kernels (`ema_model.keep_maps` -> `sinddm_keep_opts` of the chain call: one library call per scale).
+        `resample` = R > 1 adds RePaint's resampling: at every level that is a multiple of `jump_length` = J the run jumps
+        back up by J levels and comes down again, until the stretch has been walked R times (`ema_model.resample` ->
+        functions.resample_schedule and `sinddm_resample_opts`: still one library call per scale, R times the network
+        evaluations on the resampled stretches).  The defaults (1, 1) are the run without jumps, bit for bit.  No
+        image-quality claim is made.
         A (batch_size, H, W) stack of masks gives every sample its own hole: one job per sample, still one library call per
-        scale (sinddm_sample_chain_batch).  Returns the per-scale batches and writes PNGs like `sample_scales`."""
+        scale (`sinddm_batch_opts`).  Returns the per-scale batches and writes PNGs like `sample_scales`."""
         from .functions import keep_mask_pyramid
         em = self.ema_model
         m = torch.as_tensor(mask)
@@ -596,11 +598,11 @@ class MultiscaleTrainer(object):
         pixels at the finest scale, the same physical band at every scale (`functions.layout_blocks`); the layout reaches
         each scale by area averaging (`functions._layout_pyramid`).  `scales` = (first, last) limits the conditioned scales
         (inclusive; default all).  Runs `sample_scales` with `ema_model.layout_maps` / `layout_down` / `layout_strength` /
-        `layout_t_min` set (sinddm_sample_chain_layout: still one library call per scale) and clears them afterwards.
+        `layout_t_min` set (`sinddm_layout_opts` of the chain call: still one library call per scale) and clears them afterwards.
         strength = 0 is `sample_scales` itself, bit for bit.  No image-quality claim is made.
         `layout` may be (batch_size, 3, H, W), one picture per sample, and `strength` a list of `batch_size` values: their
         maximum becomes the shared per-step strength and value / maximum the sample's `layout_gain`
-        (`split_strength`; sinddm_sample_chain_batch)."""
+        (`split_strength`; `sinddm_batch_opts::layout_gain`)."""
         from .functions import layout_blocks, _layout_pyramid, split_strength
         em = self.ema_model
         lay = torch.as_tensor(layout)

@@ -288,7 +288,7 @@ WHOLE_SCALE = [("C2", 1, 16, 521, 2 * 0.0),
 @pytest.mark.parametrize("cfg,s,B,n_steps,bound", WHOLE_SCALE, ids=["C2_s1_B16_521", "C3_s5_B4_118"])
 def test_chain_noise_equals_stepwise_over_a_whole_scale(cfg, s, B, n_steps, bound, monkeypatch):
     """The full default run of a scale (p_sample_via_scale_loop, custom_t = None) with a hash-keyed `noise_fn`, dim 160:
-    `chain_noise = True` (the draws handed to sinddm_sample_chain_ex in >= 3 pieces) against the step-by-step route the
+    `chain_noise = True` (the draws handed to sinddm_sample_chain_batch in >= 3 pieces) against the step-by-step route the
     fixtures pin.  This ties the fused tail kernels to the pinned path over a whole scale, not over three steps.
 
     The bound is measured, not chosen: on commit 331afdd (the parent of this feature), MI355X with 256 CUs, the plain
@@ -321,8 +321,8 @@ def test_chain_noise_equals_stepwise_over_a_whole_scale(cfg, s, B, n_steps, boun
     per = (n_steps + 2) // 3                                    # steps per piece: three pieces
     monkeypatch.setattr(models, "CHAIN_NOISE_BYTES", per * B * 3 * H * W * 4)
     pieces = []
-    real = lib.sinddm_sample_chain_ex
-    monkeypatch.setattr(lib, "sinddm_sample_chain_ex", lambda *a: (pieces.append(a[8]), real(*a))[1])
+    real = lib.sinddm_sample_chain_batch
+    monkeypatch.setattr(lib, "sinddm_sample_chain_batch", lambda *a: (pieces.append(a[8]), real(*a))[1])
     d.chain_noise = True
     got = d.p_sample_via_scale_loop(B, img, s)
     torch.cuda.synchronize()
