@@ -96,6 +96,18 @@ int sinddm_q_sample(const float* x0, const float* x_orig, const float* noise, fl
                     const float* tab_sqrt_ac, const float* tab_sqrt_1m_ac, const float* gamma_row,
                     const int64_t* t_dev, int t_host, int B, int64_t n, void* stream);
 
+/* sinddm_q_sample with the wrapped halo of tileable TRAINING fused behind it (below: "tileable sampling"):
+ * x0, x_orig, noise are the centre-size (B,C,H,W) tensors of sinddm_q_sample, out_ext is the EXTENDED
+ * (B,C,H + 2 halo_y,W + 2 halo_x) x_noisy, halo included: every element takes the value sinddm_q_sample gives the centre
+ * pixel it wraps to (a true modulo: a halo may be wider than the image) -- sinddm_q_sample followed by sinddm_wrap_halo
+ * with src, bit for bit, in one pass.  A zero halo on an axis leaves that axis alone; (0, 0) is sinddm_q_sample's result.
+ * x_orig / gamma_row / t_dev / t_host as for sinddm_q_sample.
+ * SINDDM_E_BADARG: a null x0 / noise / out_ext / table, x_orig without gamma_row, non-positive sizes, a negative halo. */
+int sinddm_q_sample_wrap(const float* x0, const float* x_orig, const float* noise, float* out_ext,
+                         const float* tab_sqrt_ac, const float* tab_sqrt_1m_ac, const float* gamma_row,
+                         const int64_t* t_dev, int t_host, int B, int C, int H, int W, int halo_y, int halo_x,
+                         void* stream);
+
 /* Per-step scalars of one reverse diffusion step (all samples share t, models.py:481,541). */
 typedef struct sinddm_step_coefs {
     int mode;            /* 0: s==0 or !reblurring (DDPM posterior, models.py:322-330)
@@ -481,6 +493,15 @@ int sinddm_net_backward(const float* params, const float* packed, const float* p
  * grad_out = -sign(noise - eps)/n * grad_scale.           reference SinDDM/models.py:594 */
 int sinddm_l1_loss_fwd_bwd(const float* noise, const float* eps, float* loss_out, float* grad_out,
                            int64_t n, float grad_scale, void* stream);
+
+/* sinddm_l1_loss_fwd_bwd between a centre-size noise (BC,H,W) and the CENTRE of an extended eps_ext
+ * (BC,H + 2 halo_y,W + 2 halo_x) -- tileable training, where the network ran on the image extended by its wrapped halo:
+ * loss_out[0] += mean over the BC*H*W centre elements of |noise - eps| (caller zeroes loss_out); if grad_out_ext != NULL
+ * it has the EXTENDED shape and is written everywhere: -sign(noise - eps)/(BC*H*W) * grad_scale on the centre (the values
+ * sinddm_l1_loss_fwd_bwd gives for the contiguous crop, bit for bit), exactly 0 on the halo -- the buffer need not be
+ * cleared.  SINDDM_E_BADARG: a null noise / eps_ext / loss_out, non-positive sizes, a negative halo. */
+int sinddm_l1_loss_crop_fwd_bwd(const float* noise, const float* eps_ext, float* loss_out, float* grad_out_ext,
+                                int BC, int H, int W, int halo_y, int halo_x, float grad_scale, void* stream);
 
 /* Fused optimizer / EMA over flat buffers of n floats.  mode bits: 1 = Adam update of p from g
  * (torch.optim.Adam defaults, reference trainer.py:134,208; step_size = lr/(1-beta1^k),

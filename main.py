@@ -16,6 +16,9 @@ ranks as independent chains and all-gathered (RCCL over xGMI):
 `--roi_target y x h w` and `--roi_bbs y x h w [y x h w ...]` (finest-scale pixel coordinates).
 `--tile {none,x,y,xy}` (no reference flag) samples with borders that wrap around on the named axes: tileable textures,
 cylindrical panoramas (`--tile x --scale_mul 1 4`).  All five modes honour it.
+`--train_tile {none,x,y,xy}` (no reference flag) TRAINS with borders that wrap around on the named axes, so the weights have seen
+the seam `--tile` later asks them for; the intended pairing is `--mode train --tile xy --train_tile xy`.  It changes the
+training step only (`--tile` alone keeps sampling from zero-padding-trained weights), and is not stored in checkpoints.
 `inpaint` and `outpaint` (no reference modes) keep some pixels exactly and generate the rest to fit, by replacing the
 known region after every reverse step inside the step kernels: `--mode inpaint --mask_path FILE [--soft_mask]` fills the
 black part of the mask (white = keep the training image's pixel; the file is brought to the finest scale's size);
@@ -118,6 +121,8 @@ def build_parser():
     # panoramas), the y axis or both (seamlessly tileable textures) -- MultiScaleGaussianDiffusion.tile
     p.add_argument("--soft_mask", action="store_true")    # inpaint: blend with the area-averaged mask at coarse scales
     p.add_argument("--tile", choices=("none", "x", "y", "xy"), default="none")
+    # the training half of --tile (MultiScaleGaussianDiffusion.train_tile): p_losses wraps the named axes around
+    p.add_argument("--train_tile", choices=("none", "x", "y", "xy"), default="none")
     # no reference flags: per-sample noise seeds (MultiScaleGaussianDiffusion.sample_seeds) of every sampling mode
     g = p.add_mutually_exclusive_group()
     g.add_argument("--seeds", type=int, nargs="+", default=None)
@@ -221,9 +226,10 @@ def main():
         train_batch_size=args.train_batch_size, train_lr=args.train_lr, train_num_steps=args.train_num_steps,
         gradient_accumulate_every=args.grad_accumulate, ema_decay=0.995, fp16=False,
         save_and_sample_every=args.save_and_sample_every, avg_window=args.avg_window,
-        sched_milestones=sched_milestones, results_folder=results_folder, device=device)
+        sched_milestones=sched_milestones, results_folder=results_folder, device=device,
+        train_tile=("y" in args.train_tile, "x" in args.train_tile))
 
-    # a sampling option (training is unchanged): every mode below samples with the EMA model
+    # a sampling option (training is governed by --train_tile): every mode below samples with the EMA model
     trainer.ema_model.tile = ("y" in args.tile, "x" in args.tile)
     if args.load_milestone > 0:
         trainer.load(milestone=args.load_milestone)

@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_resample", "sinddm_reverse_step_jump",
     "sinddm_sample_chain_layout", "sinddm_layout_delta", "sinddm_reverse_step_layout",
     "sinddm_sample_chain_batch",
+    "sinddm_q_sample_wrap", "sinddm_l1_loss_crop_fwd_bwd",
 )
 
 
@@ -121,6 +122,7 @@ def load() -> C.CDLL:
         "sinddm_cond_embed": (i, [p, p, i, f, i, i, p, p, p, p]),
         "sinddm_cond_stride": (i, [i]),
         "sinddm_q_sample": (i, [p, p, p, p, p, p, p, p, i, i, i64, p]),
+        "sinddm_q_sample_wrap": (i, [p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, p]),
         "sinddm_reverse_step": (i, [p, p, p, p, p, C.POINTER(StepCoefs), i64, p]),
         "sinddm_reverse_step_edit": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, p]),
         "sinddm_sample_chain": (i, chain[:-2] + [C.POINTER(C.c_int)]),                      # (no aux_stream)
@@ -167,6 +169,7 @@ def load() -> C.CDLL:
         "sinddm_net_forward_train": (i, [p, p, p, p, i, f, p, i, i, i, i, p, sz, p]),
         "sinddm_net_backward": (i, [p, p, p, p, p, p, p, i, i, i, i, p, sz, p]),
         "sinddm_l1_loss_fwd_bwd": (i, [p, p, p, p, i64, f, p]),
+        "sinddm_l1_loss_crop_fwd_bwd": (i, [p, p, p, p, i, i, i, i, i, f, p]),
         "sinddm_adam_ema_step": (i, [p, p, p, p, p, f, f, f, f, f, f, f, i, i64, p]),
     }
     for name, (res, args) in sig.items():

@@ -93,3 +93,34 @@ class _L1Fn(torch.autograd.Function):
 def l1_loss(noise, eps):
     """mean(|noise - eps|)  (reference models.py:594)."""
     return _L1Fn.apply(noise, eps)
+
+
+class _L1CropFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, noise, eps_ext, halo):
+        lib = _lib.load()
+        noise = noise.contiguous()
+        eps_ext = eps_ext.contiguous()
+        hy, hx = int(halo[0]), int(halo[1])
+        H, W = int(noise.shape[-2]), int(noise.shape[-1])
+        if tuple(eps_ext.shape) != (*noise.shape[:-2], H + 2 * hy, W + 2 * hx):
+            raise _lib.SinddmError(f"l1_loss_crop: eps {tuple(eps_ext.shape)} is not noise {tuple(noise.shape)} extended by "
+                                   f"the halo {(hy, hx)}")
+        loss = torch.zeros((), dtype=torch.float32, device=eps_ext.device)
+        g = torch.empty_like(eps_ext)                  # the kernel writes the halo's zeros itself
+        _lib.check(lib.sinddm_l1_loss_crop_fwd_bwd(_lib.ptr(noise), _lib.ptr(eps_ext), _lib.ptr(loss), _lib.ptr(g),
+                                                   noise.numel() // (H * W), H, W, hy, hx, 1.0,
+                                                   _lib.stream_ptr(eps_ext.device)), "sinddm_l1_loss_crop_fwd_bwd")
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (g,) = ctx.saved_tensors
+        return None, g * grad_loss, None
+
+
+def l1_loss_crop(noise, eps_ext, halo):
+    """mean(|noise - centre(eps_ext)|) of tileable training: `eps_ext` is the network's output on the image extended by the
+    wrapped halo `halo` = (halo_y, halo_x); its gradient has the extended shape and is 0 on the halo."""
+    return _L1CropFn.apply(noise, eps_ext, halo)

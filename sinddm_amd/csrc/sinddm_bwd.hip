@@ -927,6 +927,12 @@ __global__ __launch_bounds__(256) void cond_backward_kernel(CondBwdArgs a) {
 // =====================================================================================
 // L1 loss forward+backward, fused Adam / EMA
 // =====================================================================================
+// d|noise-eps|/d eps = -sign(noise-eps), sign(0) = 0   (reference SinDDM/models.py:594), times the mean's 1/n and the
+// caller's scale: the gradient element of l1_loss_kernel and l1_loss_crop_kernel
+__device__ __forceinline__ float l1_grad_elem(float d, float inv_n, float gscale) {
+    return (d > 0.f ? -1.f : (d < 0.f ? 1.f : 0.f)) * inv_n * gscale;
+}
+
 __global__ __launch_bounds__(256) void l1_loss_kernel(const float* __restrict__ noise, const float* __restrict__ eps,
                                                       float* __restrict__ loss, float* __restrict__ grad, long long n,
                                                       float inv_n, float gscale) {
@@ -935,8 +941,38 @@ __global__ __launch_bounds__(256) void l1_loss_kernel(const float* __restrict__ 
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float d = noise[i] - eps[i];
         s += fabsf(d);
-        // d|noise-eps|/d eps = -sign(noise-eps), sign(0) = 0   (reference SinDDM/models.py:594)
-        if (grad) grad[i] = (d > 0.f ? -1.f : (d < 0.f ? 1.f : 0.f)) * inv_n * gscale;
+        if (grad) grad[i] = l1_grad_elem(d, inv_n, gscale);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss, ((red[0] + red[1]) + (red[2] + red[3])) * inv_n);
+}
+
+// The same loss between a centre-size noise [BC][H][W] and the CENTRE of an extended eps [BC][H + 2 hy][W + 2 hx] (tileable
+// training: the network ran on the image extended by its wrapped halo).  A thread walks the EXTENDED index space, so the
+// gradient -- extended too -- is written everywhere: l1_grad_elem on the centre, 0 on the halo (the buffer need not be
+// cleared).  n_ext = BC * He * We; inv_n = 1 / (BC * H * W).  Same reduction as l1_loss_kernel.
+__global__ __launch_bounds__(256) void l1_loss_crop_kernel(const float* __restrict__ noise, const float* __restrict__ eps,
+                                                           float* __restrict__ loss, float* __restrict__ grad,
+                                                           long long n_ext, int H, int W, int hy, int hx, float inv_n,
+                                                           float gscale) {
+    __shared__ float red[4];
+    const int He = H + 2 * hy, We = W + 2 * hx;
+    float s = 0.f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_ext; i += (long long)gridDim.x * 256) {
+        const long long row = i / We;
+        const int x = (int)(i - row * We) - hx;
+        const long long bc = row / He;
+        const int y = (int)(row - bc * He) - hy;
+        float gv = 0.f;
+        if (y >= 0 && y < H && x >= 0 && x < W) {
+            const float d = noise[((size_t)bc * H + y) * W + x] - eps[i];
+            s += fabsf(d);
+            gv = l1_grad_elem(d, inv_n, gscale);
+        }
+        if (grad) grad[i] = gv;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -1283,6 +1319,21 @@ int sinddm_l1_loss_fwd_bwd(const float* noise, const float* eps, float* loss_out
     if (bx > 1024) bx = 1024;
     hipLaunchKernelGGL(l1_loss_kernel, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream), noise, eps,
                        loss_out, grad_out, (long long)n, 1.0f / (float)n, grad_scale);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sinddm_l1_loss_crop_fwd_bwd(const float* noise, const float* eps_ext, float* loss_out, float* grad_out_ext, int BC, int H,
+                                int W, int halo_y, int halo_x, float grad_scale, void* stream) {
+    if (!noise || !eps_ext || !loss_out || BC <= 0 || H <= 0 || W <= 0 || halo_y < 0 || halo_x < 0 || halo_y > (1 << 20) ||
+        halo_x > (1 << 20))
+        return SINDDM_E_BADARG;
+    const long long n = (long long)BC * H * W;
+    const long long n_ext = (long long)BC * (H + 2 * halo_y) * (W + 2 * halo_x);
+    long long bx = (n_ext + 255) / 256;
+    if (bx > 1024) bx = 1024;
+    hipLaunchKernelGGL(l1_loss_crop_kernel, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream), noise, eps_ext,
+                       loss_out, grad_out_ext, n_ext, H, W, halo_y, halo_x, 1.0f / (float)n, grad_scale);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }

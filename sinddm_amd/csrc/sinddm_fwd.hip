@@ -660,6 +660,26 @@ __global__ __launch_bounds__(256) void final_conv1x1_kernel(const float* __restr
 // =====================================================================================
 // diffusion elementwise kernels (HBM-bound)
 // =====================================================================================
+// One element (T = float) or quad (T = f32x4) of q_sample: the arithmetic of q_sample_kernel and q_sample_wrap_kernel, in
+// one place so that the two agree bit for bit.  `o` is read only where `mix` is set.  Each a*b + c*d has ONE fused product,
+// and which one is written out here.  Left to the compiler's contraction, the same source line came out with three roundings
+// in the three instantiations of q_sample_kernel (Q_ROUND_* below), and a fourth kernel would have been free to differ from
+// all of them.  `r` keeps every instantiation's results what they were, and lets q_sample_wrap_kernel reproduce whichever
+// instantiation sinddm_q_sample launches for the same tensors (q_sample_route).
+enum { Q_FUSE_GX = 1,       // the mix: set fma(g, x0, (1-g)*x_orig), clear fma(1-g, x_orig, g*x0)
+       Q_FUSE_CAX = 2 };    // the sample: set fma(ca, x, cb*noise), clear fma(cb, noise, ca*x)
+enum { Q_ROUND_QUAD = 0, Q_ROUND_QUAD_UN4 = Q_FUSE_GX, Q_ROUND_FLOAT = Q_FUSE_GX | Q_FUSE_CAX };   // <4,1>, <4,4>, <1,1>
+
+__device__ __forceinline__ float q_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ f32x4 q_fma(float a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(f32x4{a, a, a, a}, b, c); }
+
+template <typename T>
+__device__ __forceinline__ T q_sample_elem(const T& x, const T& o, const T& z, bool mix, float g, float ca, float cb, int r) {
+    T v = x;
+    if (mix) v = (r & Q_FUSE_GX) ? q_fma(g, v, (1.0f - g) * o) : q_fma(1.0f - g, o, g * v);      // models.py:584-585
+    return (r & Q_FUSE_CAX) ? q_fma(ca, v, cb * z) : q_fma(cb, z, ca * v);                       // models.py:574-575
+}
+
 // VEC = 4: 16-byte accesses (n % 4 == 0 keeps every sample's base 16-byte aligned), UN quads per thread requested before
 // the first one is used (4 for big tensors, 1 when that would leave CUs without workgroups); VEC = 1: any n.  The per-sample coefficients are three scalar loads per workgroup.
 template <int VEC, int UN>
@@ -693,16 +713,14 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
             for (int u = 0; u < UN; ++u) {
                 const long long q = q0 + u * 256;
                 if (q >= nq) continue;
-                f32x4 w = v[u];
-                if (o4) w = g * w + (1.0f - g) * o[u];       // models.py:584-585
-                y4[q] = ca * w + cb * z[u];                   // models.py:574-575
+                y4[q] = q_sample_elem(v[u], o[u], z[u], o4 != nullptr, g, ca, cb, UN == 4 ? Q_ROUND_QUAD_UN4 : Q_ROUND_QUAD);
             }
         }
     } else {
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-            float v = x0[base + i];
-            if (xo) v = g * v + (1.0f - g) * xo[base + i];   // models.py:584-585
-            out[base + i] = ca * v + cb * nz[base + i];      // models.py:574-575
+            float o;
+            if (xo) o = xo[base + i];
+            out[base + i] = q_sample_elem(x0[base + i], o, nz[base + i], xo != nullptr, g, ca, cb, Q_ROUND_FLOAT);
         }
     }
 }
@@ -786,6 +804,46 @@ int wrap_halo_launch(float* ext, const float* src, int BC, int H, int W, int hy,
     else hipLaunchKernelGGL(wrap_halo_kernel<1>, dim3((unsigned)bx), dim3(256), 0, st, ext, src, nq, H, W, hy, hx);
     SINDDM_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- tileable training: q_sample written straight into the extended image (sinddm_q_sample_wrap) -------------------------
+// = q_sample_kernel followed by wrap_halo_kernel with src, in one pass: a thread owns VEC consecutive floats of an extended
+// row of sample blockIdx.y, finds the centre pixels they wrap to (true modulo), reads x0 / x_orig / noise THERE and writes
+// q_sample_elem of them.  ext: [B][C][H + 2 hy][W + 2 hx]; the inputs [B][C][H][W].  VEC = 4 under wrap_halo_kernel<4>'s
+// conditions (W % 4 == 0, hx % 4 == 0, 16-byte aligned bases: a quad's source quad is contiguous, aligned and inside one row).
+// nq: quads (VEC = 4) or elements (VEC = 1) of ONE extended sample.  round: the Q_ROUND_* of the kernel sinddm_q_sample would
+// launch for the same tensors (not a function of VEC, which also depends on the halo); uniform, and the kernel is HBM-bound.
+template <int VEC>
+__global__ __launch_bounds__(256) void q_sample_wrap_kernel(const float* __restrict__ x0, const float* __restrict__ xo,
+                                                            const float* __restrict__ nz, float* __restrict__ ext,
+                                                            const float* __restrict__ tabA, const float* __restrict__ tabB,
+                                                            const float* __restrict__ gam, const long long* __restrict__ t_dev,
+                                                            int t_host, long long nq, int C, int H, int W, int hy, int hx,
+                                                            int round) {
+    const int b = blockIdx.y;
+    const long long t = t_dev ? t_dev[b] : (long long)t_host;
+    const float ca = tabA[t], cb = tabB[t];
+    const float g = (xo != nullptr) ? gam[t] : 0.0f;
+    const int He = H + 2 * hy, We = W + 2 * hx, qpr = We / VEC;
+    const size_t sbase = (size_t)b * C * H * W, dbase = (size_t)b * C * He * We;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+        const long long row = q / qpr;
+        const int x = (int)(q - row * qpr) * VEC;
+        const int c = (int)(row / He);
+        const int y = (int)(row - (long long)c * He);
+        int cy = (y - hy) % H, cx = (x - hx) % W;                                   // true modulo: a halo may be wider than the image
+        if (cy < 0) cy += H;
+        if (cx < 0) cx += W;
+        const size_t si = sbase + ((size_t)c * H + cy) * W + cx;
+        float* d = ext + dbase + ((size_t)c * He + y) * We + x;
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<f32x4*>(d) = q_sample_elem(*reinterpret_cast<const f32x4*>(x0 + si),
+                                                         *reinterpret_cast<const f32x4*>((xo ? xo : x0) + si),
+                                                         *reinterpret_cast<const f32x4*>(nz + si), xo != nullptr, g, ca, cb, round);
+        } else {
+            *d = q_sample_elem(x0[si], (xo ? xo : x0)[si], nz[si], xo != nullptr, g, ca, cb, round);
+        }
+    }
 }
 
 // =====================================================================================
@@ -1190,6 +1248,12 @@ int sinddm_cond_embed(const float* params, const int64_t* t_dev, int t_host, flo
 
 int sinddm_cond_stride(int dim) { NetPlan p = make_plan(dim); return p.ok ? p.cond_stride : -1; }
 
+// which instantiation of q_sample_kernel runs B samples of n elements (`al`: every tensor 16-byte aligned), named by its rounding
+static int q_sample_route(int B, long long n, bool al) {
+    if (n % 4 != 0 || !al) return Q_ROUND_FLOAT;
+    return (long long)B * (n / 4) >= 4LL * 1024 * 2048 ? Q_ROUND_QUAD_UN4 : Q_ROUND_QUAD;   // >= 8 workgroups of 1024 quads per CU
+}
+
 int sinddm_q_sample(const float* x0, const float* x_orig, const float* noise, float* out, const float* tab_sqrt_ac,
                     const float* tab_sqrt_1m_ac, const float* gamma_row, const int64_t* t_dev, int t_host, int B,
                     int64_t n, void* stream) {
@@ -1197,8 +1261,9 @@ int sinddm_q_sample(const float* x0, const float* x_orig, const float* noise, fl
     if (x_orig && !gamma_row) return SINDDM_E_BADARG;
     const bool al = ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(out) |
                       reinterpret_cast<uintptr_t>(x_orig)) & 15) == 0;
-    if (n % 4 == 0 && al) {
-        const bool big = (long long)B * (n / 4) >= 4LL * 1024 * 2048;       // >= 8 workgroups of 1024 quads per CU
+    const int route = q_sample_route(B, n, al);
+    if (route != Q_ROUND_FLOAT) {
+        const bool big = route == Q_ROUND_QUAD_UN4;
         long long bx = big ? (n / 4 + 1023) / 1024 : (n / 4 + 255) / 256;
         if (bx > 4096) bx = 4096;
         if (big)
@@ -1216,6 +1281,31 @@ int sinddm_q_sample(const float* x0, const float* x_orig, const float* noise, fl
                            x_orig, noise, out, tab_sqrt_ac, tab_sqrt_1m_ac, gamma_row,
                            reinterpret_cast<const long long*>(t_dev), t_host, (long long)n);
     }
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sinddm_q_sample_wrap(const float* x0, const float* x_orig, const float* noise, float* out_ext, const float* tab_sqrt_ac,
+                         const float* tab_sqrt_1m_ac, const float* gamma_row, const int64_t* t_dev, int t_host, int B, int C,
+                         int H, int W, int halo_y, int halo_x, void* stream) {
+    if (!x0 || !noise || !out_ext || !tab_sqrt_ac || !tab_sqrt_1m_ac || B <= 0 || C <= 0 || H <= 0 || W <= 0 || halo_y < 0 ||
+        halo_x < 0 || halo_y > (1 << 20) || halo_x > (1 << 20))
+        return SINDDM_E_BADARG;
+    if (x_orig && !gamma_row) return SINDDM_E_BADARG;
+    const bool al_in = ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(x_orig)) & 15) == 0;
+    const int round = q_sample_route(B, (long long)C * H * W, al_in);    // sinddm_q_sample on these tensors (into an aligned `out`)
+    const bool vec = W % 4 == 0 && halo_x % 4 == 0 && al_in && (reinterpret_cast<uintptr_t>(out_ext) & 15) == 0;
+    const long long nq = (long long)C * (H + 2 * halo_y) * ((W + 2 * halo_x) / (vec ? 4 : 1));
+    long long bx = (nq + 255) / 256;
+    if (bx > 4096) bx = 4096;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long* td = reinterpret_cast<const long long*>(t_dev);
+    if (vec)
+        hipLaunchKernelGGL(q_sample_wrap_kernel<4>, dim3((unsigned)bx, B), dim3(256), 0, st, x0, x_orig, noise, out_ext, tab_sqrt_ac,
+                           tab_sqrt_1m_ac, gamma_row, td, t_host, nq, C, H, W, halo_y, halo_x, round);
+    else
+        hipLaunchKernelGGL(q_sample_wrap_kernel<1>, dim3((unsigned)bx, B), dim3(256), 0, st, x0, x_orig, noise, out_ext, tab_sqrt_ac,
+                           tab_sqrt_1m_ac, gamma_row, td, t_host, nq, C, H, W, halo_y, halo_x, round);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }

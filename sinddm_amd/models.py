@@ -607,6 +607,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # _lib.TILE_HALO pixels (the network's receptive radius) and the centre is kept.  A sampling option: training is
         # unchanged.
         self.tile = (False, False)
+        # tileable TRAINING: (wrap_y, wrap_x) -- p_losses trains the network with circular padding on the wrapped axes, by
+        # the same construction (x_noisy extended by its wrapped halo, the loss on the centre: every parameter gradient is
+        # then the circularly padded network's).  Separate from `tile`, which p_losses does not read; not
+        # stored in checkpoints.
+        self.train_tile = (False, False)
         # known-region conditioning (inpainting / outpainting): None or {s: (mask (H,W), x0 (3,H,W))}, fp32, on the sample's
         # device.  At a scale with an entry every reverse step overwrites the pixels whose mask is 1 with the
         # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
@@ -1382,6 +1387,22 @@ class MultiScaleGaussianDiffusion(nn.Module):
                                        _lib.stream_ptr(x0.device)), "sinddm_q_sample")
         return out
 
+    def _q_sample_wrap_impl(self, x0, t_dev, noise, halo, x_orig=None, gamma_row=None):
+        """x_noisy of p_losses extended by its wrapped halo (sinddm_q_sample_wrap): (B,C,H + 2 hy,W + 2 hx)."""
+        lib = _lib.load()
+        x0 = x0.contiguous()
+        noise = noise.contiguous()
+        B, Cc, H, W = x0.shape
+        hy, hx = halo
+        out = torch.empty((B, Cc, H + 2 * hy, W + 2 * hx), dtype=x0.dtype, device=x0.device)
+        t_dev = t_dev.to(device=x0.device, dtype=torch.int64).contiguous()
+        _lib.check(lib.sinddm_q_sample_wrap(_lib.ptr(x0), _lib.ptr(x_orig.contiguous()) if x_orig is not None else None,
+                                            _lib.ptr(noise), _lib.ptr(out), _lib.ptr(self.sqrt_alphas_cumprod),
+                                            _lib.ptr(self.sqrt_one_minus_alphas_cumprod),
+                                            _lib.ptr(gamma_row) if gamma_row is not None else None, _lib.ptr(t_dev), 0,
+                                            B, Cc, H, W, hy, hx, _lib.stream_ptr(x0.device)), "sinddm_q_sample_wrap")
+        return out
+
     def q_sample(self, x_start, t, noise=None):                            # models.py:570-576
         noise = default(noise, lambda: torch.randn_like(x_start))
         return self._q_sample_impl(x_start, t, 0, noise)
@@ -1390,6 +1411,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         noise = default(noise, lambda: torch.randn_like(x_start))
         if self.loss_type not in ('l1', 'l2', 'l1_pred_img'):
             raise NotImplementedError()
+        if any(self.train_tile):
+            return self._p_losses_tiled(x_start, t, s, noise, x_orig)
         if int(s) > 0:
             gamma_row = self.gammas[int(s) - 1].reshape(-1).contiguous()    # NOT clamped to 0.55 in training
             x_noisy = self._q_sample_impl(x_start, t, 0, noise, x_orig=x_orig, gamma_row=gamma_row)
@@ -1405,6 +1428,35 @@ class MultiScaleGaussianDiffusion(nn.Module):
             return F.mse_loss(noise, x_recon)
         if int(s) > 0:
             if int(t[0]) > 0:                                               # (the reference's host sync, models.py:599)
+                g = extract(self.gammas[int(s) - 1].reshape(-1), t - 1, x_start.shape)
+                x_mix_prev = g * x_start + (1 - g) * x_orig
+            else:
+                x_mix_prev = x_orig
+        else:
+            x_mix_prev = x_start
+        return (x_mix_prev - x_recon).abs().mean()
+
+    def _p_losses_tiled(self, x_start, t, s, noise, x_orig):
+        """p_losses with wrap-around borders on the axes of `train_tile` (no reference line: padding_mode='circular' on the
+        reference's nn.Conv2d's while it trains).  x_noisy is written extended by its wrapped halo, the zero-padded training
+        forward runs on the extended image and the loss is taken on the centre: the gradient handed back is 0 on the halo,
+        and every parameter gradient equals the circularly padded network's."""
+        hy, hx = halo = (_lib.TILE_HALO if self.train_tile[0] else 0, _lib.TILE_HALO if self.train_tile[1] else 0)
+        H, W = int(x_start.shape[2]), int(x_start.shape[3])
+        if int(s) > 0:
+            gamma_row = self.gammas[int(s) - 1].reshape(-1).contiguous()    # NOT clamped to 0.55 in training
+            x_noisy = self._q_sample_wrap_impl(x_start, t, noise, halo, x_orig=x_orig, gamma_row=gamma_row)
+        else:
+            x_noisy = self._q_sample_wrap_impl(x_start, t, noise, halo)
+        x_recon = self.denoise_fn(x_noisy, t, int(s))                       # extended
+        if self.loss_type == 'l1':
+            from .autograd import l1_loss_crop
+            return l1_loss_crop(noise, x_recon, halo)
+        x_recon = x_recon[:, :, hy:hy + H, hx:hx + W]                       # (its backward zero-fills the halo)
+        if self.loss_type == 'l2':
+            return F.mse_loss(noise, x_recon)
+        if int(s) > 0:
+            if int(t[0]) > 0:
                 g = extract(self.gammas[int(s) - 1].reshape(-1), t - 1, x_start.shape)
                 x_mix_prev = g * x_start + (1 - g) * x_orig
             else:

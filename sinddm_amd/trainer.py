@@ -90,7 +90,7 @@ class MultiscaleTrainer(object):
                  image_sizes=None, train_batch_size=32, train_lr=2e-5, train_num_steps=100000,
                  gradient_accumulate_every=2, fp16=False, step_start_ema=2000, update_ema_every=10,
                  save_and_sample_every=25000, avg_window=100, sched_milestones=None, results_folder='./results',
-                 device=None):
+                 device=None, train_tile=(False, False)):
         super().__init__()
         self.device = device
         self.sched_milestones = [10000, 30000, 60000, 80000, 90000] if sched_milestones is None else sched_milestones
@@ -100,6 +100,9 @@ class MultiscaleTrainer(object):
         self.ema = EMA(ema_decay)
         self.ema_decay = ema_decay
         self.ema_model = copy.deepcopy(self.model)
+        # tileable training (wrap_y, wrap_x): the model that trains wraps its borders in p_losses.  The EMA copy never
+        # trains; how it SAMPLES is its own `tile` setting.
+        self.model.train_tile = (bool(train_tile[0]), bool(train_tile[1]))
         self.update_ema_every = update_ema_every
         self.step_start_ema = step_start_ema
         self.save_and_sample_every = save_and_sample_every
