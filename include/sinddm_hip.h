@@ -446,6 +446,63 @@ int sinddm_sample_chain_batch(const float* params, const float* packed, float* x
                               const sinddm_layout_opts* lo /*host, may be NULL*/,
                               const sinddm_batch_opts* bo /*host, may be NULL*/);
 
+/* ---- few-step sampling: strided schedules and a second-order multistep step ------------------------------------------ */
+/* A step may land on any lower level u < t, not only t - 1: the strided step is the ordinary step with coefs filled for
+ * the pair (t, u) on the host (mode 0: the DDIM form  coef2 = sqrt(sb_u^2 - sigma^2) / sb_t,  coef1 = sa_u - coef2 * sa_t;
+ * mode 1: the `tm1` fields take level u; landing on the clean image from a scale > 0: mode 2), and keep_ab = (sa_u, sb_u).
+ * Every chain entry takes such coefs as it takes any other; t_list holds the levels the network is evaluated at.
+ *
+ * The multistep step makes few steps accurate (DPM-Solver++(2M) written for SinDDM's blurred process; no reference line;
+ * derivation in DESIGN.md 3).  With the marginal  sa[l] * (gamma[l] * x_tilde + (1 - gamma[l]) * x0) + sb[l] * eps  and
+ * kappa[l] = sa[l] * (1 - gamma[l]) / sb[l],  y = (x - sa * gamma * x_tilde) / sb  obeys  dy = x0_hat d(kappa); the rule
+ * extrapolates the clean estimate D in log kappa from the two last evaluations tau_{i-1} > tau_i, landing on u_i:
+ *     D~_i = D_i + rho_i * (D_i - D_{i-1})      rho_i = ln(kappa[u_i] / kappa[tau_i]) / (2 ln(kappa[tau_i] / kappa[tau_{i-1}]))
+ * and rho = 0 on the first step of a run and on a step that lands on the clean image.  Per element the step is
+ *     xp   = the step's clean estimate before the ROI edit and the clamp (sinddm_layout_opts: "clean estimate", ew = 1, ec = 0)
+ *     eps' = eps - q * (xp - hist)               hist is read only when q != 0
+ *     hist = xp
+ *     out  = the ordinary step (edit, clamps, keep, noise) on eps'
+ *     q_i  = rho_i * (1 - gamma[tau_i]) / sqrt_recipm1_ac[tau_i]         (host, float64)
+ * which turns the step's x_recon into xp + rho * (xp - hist); the ROI edit is affine and the same at every step, so it
+ * commutes with the extrapolation.  q = 0 is the ordinary step, exactly. */
+typedef struct sinddm_solver_opts {
+    const float* q;     /* HOST, n_steps entries, >= 0 and finite; 0 = first-order step */
+    float* hist;        /* DEVICE, (B,3,H,W) of the run's extended size, 16-byte aligned */
+} sinddm_solver_opts;
+
+/* sinddm_sample_chain_batch with the multistep solver (every chain entry fills one internal description; they differ only
+ * in the options they can express).  so = NULL or so->q = NULL: the same launches, the same numbers as
+ * sinddm_sample_chain_batch.  With the block EVERY step of the call runs unfused -- the network writes eps, then one
+ * elementwise kernel does the step above -- per half-batch on that half's stream, the second half with its own part of
+ * `hist` (the offset of its part of x).  Every step writes `hist`; a step reads it only when q[i] != 0, so the first call of
+ * a run needs no initialisation and a run cut into several calls continues where it stopped.  Under a halo `hist` has the
+ * extended size; its halo holds what the halo elements computed and never reaches the centre.  Seeds, recorded draws, halo,
+ * keep, edit and per-sample maps work as before; results with / without aux_stream are identical.
+ * SINDDM_E_BADARG (before any device work): q without hist, hist not 16-byte aligned, a q[i] that is negative or not
+ * finite, q[i] != 0 on a step with coefs[i].mode == 2, a step with jumps[i].on or a layout pull g_i > 0 in the same call. */
+int sinddm_sample_chain_solver(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                               const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                               int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                               void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                               const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                               const sinddm_keep_opts* keep /*host, may be NULL*/,
+                               const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/,
+                               const sinddm_resample_opts* rs /*host, may be NULL*/,
+                               const sinddm_layout_opts* lo /*host, may be NULL*/,
+                               const sinddm_batch_opts* bo /*host, may be NULL*/,
+                               const sinddm_solver_opts* so /*host, may be NULL*/);
+
+/* One multistep step, noise supplied by the caller: the step-by-step route and the cross-check of the chain call; mirrors
+ * sinddm_reverse_step_keep.  `hist` (B*C*HW floats) is written, and read when q != 0.  edit_w / edit_c and keep_m / keep_x0
+ * are each both-or-neither and may be NULL (keep_a / keep_b are then ignored).  With q = 0, `out` is what
+ * sinddm_reverse_step / _edit / _keep write, bit for bit (the entry runs their kernel, then writes `hist` in a pass of its
+ * own; inside a chain call a q[i] = 0 step is the same step to fp32 rounding).
+ * SINDDM_E_BADARG: a missing pointer, q negative or not finite, q != 0 with coefs->mode == 2. */
+int sinddm_reverse_step_ms(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                           const sinddm_step_coefs* coefs /*host*/, float q, float* hist, const float* edit_w,
+                           const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b,
+                           int B, int C, int HW, void* stream);
+
 /* The block delta on its own: delta[B][3][h][w] from the step's inputs.  H x W is the CENTRE size (as in the chain calls);
  * x_t, eps, x_tilde are B*3*(H + 2 halo_y)*(W + 2 halo_x) floats, layout / edit_c one sample of that, edit_w one plane.
  * edit_w / edit_c both-or-neither.  x_tilde is read in modes 1 and 2 only.

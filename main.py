@@ -25,6 +25,10 @@ black part of the mask (white = keep the training image's pixel; the file is bro
 `--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.  `--resample R --jump_length J`
 (both modes; defaults 1 1 = no jumps) add RePaint's resampling: at every noise level that is a multiple of J the run jumps
 back up by J levels and comes down again, R times in all, so that the generated region is shaped with the known one in view.
+`--sample_steps N [N ...]` (no reference flag; one value, or one per scale) evaluates the network at no more than N levels per
+scale instead of all of them, `--sample_spacing {t,logsnr}` chooses which, `--solver_order 2` takes the second-order multistep
+step that makes few steps accurate, `--eta F` scales the noise of a scale-0 step (1 = the reference's, 0 = deterministic).  Every
+sampling mode honours them, except together with `--resample` and, for `--solver_order 2`, `paint2image`.
 `paint2image` (no reference mode) redraws a rough picture -- a scribble, a colour sketch, a blurred photo -- in the training
 image's texture while its layout stays put: `--mode paint2image --input_image FILE [--layout_down N] [--layout_strength G]
 [--layout_t_min T] [--layout_scales A B]` pulls the low spatial frequencies (the band below N pixels of the finest scale) of
@@ -131,6 +135,11 @@ def build_parser():
     # no reference flags: RePaint's resampling jumps of `inpaint` / `outpaint` (MultiScaleGaussianDiffusion.resample)
     p.add_argument("--resample", type=int, default=1)
     p.add_argument("--jump_length", type=int, default=1)
+    # no reference flags: few-step sampling (MultiScaleGaussianDiffusion.sample_steps / sample_spacing / solver_order / eta)
+    p.add_argument("--sample_steps", type=int, nargs="+", default=None)
+    p.add_argument("--sample_spacing", choices=("t", "logsnr"), default="t")
+    p.add_argument("--solver_order", type=int, choices=(1, 2), default=1)
+    p.add_argument("--eta", type=float, default=1.0)
     # no reference flags: layout conditioning of `paint2image` (MultiscaleTrainer.paint2image)
     p.add_argument("--layout_down", type=int, default=8)
     p.add_argument("--layout_strength", type=float, default=1.0, nargs="+", action=_OneOrMore)
@@ -157,6 +166,10 @@ def parse_args(argv=None):
         p.error("--vary_from_scale must be >= 0")
     if args.resample < 1 or args.jump_length < 1:
         p.error("--resample and --jump_length must be >= 1")
+    if args.sample_steps is not None and min(args.sample_steps) < 1:
+        p.error("--sample_steps must be >= 1")
+    if args.eta < 0.0:
+        p.error("--eta must be >= 0")
     if not 1 <= args.layout_down <= 64:
         p.error("--layout_down must be in 1 ... 64")
     for g in (args.layout_strength if isinstance(args.layout_strength, Jobs) else [args.layout_strength]):
@@ -231,6 +244,12 @@ def main():
 
     # a sampling option (training is governed by --train_tile): every mode below samples with the EMA model
     trainer.ema_model.tile = ("y" in args.tile, "x" in args.tile)
+    if args.sample_steps is not None:
+        if len(args.sample_steps) not in (1, n_scales):
+            raise SystemExit(f"--sample_steps: {len(args.sample_steps)} values for {n_scales} scales (give one, or one per scale)")
+        trainer.ema_model.sample_steps = args.sample_steps[0] if len(args.sample_steps) == 1 else list(args.sample_steps)
+    trainer.ema_model.sample_spacing, trainer.ema_model.solver_order, trainer.ema_model.eta = (
+        args.sample_spacing, args.solver_order, args.eta)
     if args.load_milestone > 0:
         trainer.load(milestone=args.load_milestone)
     if args.mode == 'train':

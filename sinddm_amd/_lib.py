@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_resample", "sinddm_reverse_step_jump",
     "sinddm_sample_chain_layout", "sinddm_layout_delta", "sinddm_reverse_step_layout",
     "sinddm_sample_chain_batch",
+    "sinddm_sample_chain_solver", "sinddm_reverse_step_ms",
     "sinddm_q_sample_wrap", "sinddm_l1_loss_crop_fwd_bwd",
 )
 
@@ -84,6 +85,12 @@ class BatchOpts(C.Structure):
                 ("layout_per_sample", C.c_int), ("layout_gain", C.c_void_p)]
 
 
+class SolverOpts(C.Structure):
+    """Mirror of `sinddm_solver_opts` (include/sinddm_hip.h): `q` a HOST array of one extrapolation factor per step of the
+    call (0: a first-order step), `hist` the device buffer that carries the previous step's clean estimate."""
+    _fields_ = [("q", C.POINTER(C.c_float)), ("hist", C.c_void_p)]
+
+
 class SinddmError(RuntimeError):
     pass
 
@@ -137,6 +144,10 @@ def load() -> C.CDLL:
                                                    C.POINTER(ResampleOpts), C.POINTER(LayoutOpts)]),
         "sinddm_sample_chain_batch": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
                                                   C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts)]),
+        "sinddm_sample_chain_solver": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
+                                                   C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts),
+                                                   C.POINTER(SolverOpts)]),
+        "sinddm_reverse_step_ms": (i, [p, p, p, p, p, C.POINTER(StepCoefs), f, p, p, p, p, p, f, f, i, i, i, p]),
         "sinddm_layout_delta": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, i, i, i, p]),
         "sinddm_reverse_step_layout": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, f, i, p, p, p, p, f, f, i, i, i, i, i, i, i,
                                            p]),

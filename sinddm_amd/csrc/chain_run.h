@@ -45,6 +45,9 @@ struct ChainRun {
     const float* layout_g;               // HOST, one per step
     float* layout_delta;
     int layout_down;
+    // sinddm_solver_opts
+    const float* solver_q;               // HOST, one per step; NULL: the call without the block
+    float* solver_hist;
     sinddm_batch_opts batch;             // (all 0 is the call without the block: batch_strides)
 };
 
@@ -76,6 +79,9 @@ inline void chain_run_set(ChainRun& r, const sinddm_layout_opts* lo) {
 inline void chain_run_set(ChainRun& r, const sinddm_batch_opts* bo) {
     if (bo) r.batch = *bo;
 }
+inline void chain_run_set(ChainRun& r, const sinddm_solver_opts* so) {
+    if (so) { r.solver_q = so->q; r.solver_hist = so->hist; }
+}
 
 // a jump description the kernels can take: r in (0, 1], s >= 0, d only where x-tilde exists; never after a mode-2 step
 inline bool jump_valid(const sinddm_jump_coefs& j, const sinddm_step_coefs& k) {
@@ -90,10 +96,11 @@ struct ChainChecked {
     const sinddm_jump_coefs* jumps;      // NULL: no step of the run jumps, and nothing differs from the call without them
     const float* jump_noise;             // one slot per jump, in order of occurrence
     const float* lay_g;                  // NULL: no step of the run pulls, and nothing differs from the call without a layout
+    const float* ms_q;                   // NULL: no solver block, and nothing differs from the call without it
 };
 
 // Every check of a chain call that comes before the plan, in the order that decides which of two defects is reported.
-// 0, or the SINDDM_E_* to return; nothing is dereferenced but the HOST arrays coefs / jumps / layout_g.
+// 0, or the SINDDM_E_* to return; nothing is dereferenced but the HOST arrays coefs / jumps / layout_g / solver_q.
 inline int chain_check(const ChainRun& r, ChainChecked* out) {
     const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
     *out = ChainChecked{};
@@ -139,6 +146,16 @@ inline int chain_check(const ChainRun& r, ChainChecked* out) {
             if (3LL * r.B > 65535) return SINDDM_E_BADSHAPE;                             // (one grid plane per (sample, channel))
             if ((r.Hc + r.layout_down - 1) / r.layout_down > 65535) return SINDDM_E_BADSHAPE;      // (one grid row per block row)
         }
+    }
+    // multistep solver: with the block EVERY step runs unfused and ends in reverse_step_ms_kernel (q[i] == 0: first order)
+    if (r.solver_q) {
+        if (!r.solver_hist || (bits(r.solver_hist) & 15) != 0) return SINDDM_E_BADARG;
+        for (int i = 0; i < r.n_steps; ++i) {
+            if (!(r.solver_q[i] >= 0.0f && r.solver_q[i] <= 3.0e38f)) return SINDDM_E_BADARG;            // (negative, inf, NaN)
+            if (r.solver_q[i] != 0.0f && r.coefs[i].mode == 2) return SINDDM_E_BADARG;
+        }
+        if (c.jumps || c.lay_g) return SINDDM_E_BADARG;        // (multistep through a jump or a pull is not built)
+        c.ms_q = r.solver_q;
     }
     *out = c;
     return 0;

@@ -1424,6 +1424,19 @@ static int jump_launch(const TailIO& io, const TailArgs& t, const JumpArgs& jp) 
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
 
+// the multistep step (reverse_step_ms_kernel): rows as in jump_launch; `hist` has the launch's extent
+static int ms_launch(const TailIO& io, const TailArgs& t, float q, float* hist) {
+    const long long span = tail_span(io, t);
+    long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
+    if (gx > 8192) gx = 8192;
+    tail_dispatch(t, [&](auto E, auto N, auto K) {
+        hipLaunchKernelGGL((reverse_step_ms_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
+                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
+                           q, hist, span, io.chw, io.hw);
+    });
+    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+}
+
 // the geometry of a layout-conditioned scale (LayoutArgs without D and g): centre Hc x Wc, block size N
 static LayoutArgs layout_geom(int Hc, int Wc, int halo_y, int halo_x, int N, bool wrap_y, bool wrap_x) {
     LayoutArgs g{};
@@ -1499,9 +1512,10 @@ struct ChainStepPlan {
     float* cur;
     float* nxt;
     TailArgs t;
-    bool jump, pull;                     // the step writes eps; its tail is launched behind the network
+    bool jump, pull, ms;                 // the step writes eps; its tail is launched behind the network
     JumpArgs jp;
     float g;                             // pull: the step's strength
+    float q;                             // ms: the step's extrapolation factor (0: first order)
 };
 
 // the split rule and the carving of the workspace; 0, or SINDDM_E_BADARG when an event cannot be created
@@ -1542,7 +1556,7 @@ static int chain_split(ChainCtx& k) {
 }
 
 // Half h of one step, on its own stream: the network, then the tail the step ends in -- step + jump, or block delta +
-// conditioned step, or the plain rows kernel where the shape has no fused tail, or nothing (the network's last kernel was
+// conditioned step, or the multistep step, or the plain rows kernel where the shape has no fused tail, or nothing (the network's last kernel was
 // the tail) -- then the halo of the step's output when tiled.  A run that is not split has the one half h = 0.
 static int chain_half_step(const ChainCtx& k, const ChainStepPlan& s, int h) {
     const ChainRun& r = k.r;
@@ -1551,7 +1565,7 @@ static int chain_half_step(const ChainCtx& k, const ChainStepPlan& s, int h) {
     hipStream_t st = h ? k.sx : k.st;
     ChainStep cs{};
     cs.cond_row = s.cond_row;
-    cs.x_tilde = r.x_tilde ? r.x_tilde + o : nullptr; cs.x_next = k.fuse_tail && !s.jump && !s.pull ? s.nxt + o : nullptr;
+    cs.x_tilde = r.x_tilde ? r.x_tilde + o : nullptr; cs.x_next = k.fuse_tail && !s.jump && !s.pull && !s.ms ? s.nxt + o : nullptr;
     cs.tail = s.t;
     const int b0 = cs.tail.b0 = h ? k.sp.Bh[0] : 0;
     if (k.c.sseeds) cs.tail.sseeds = k.c.sseeds + b0;
@@ -1571,6 +1585,8 @@ static int chain_half_step(const ChainCtx& k, const ChainStepPlan& s, int h) {
         lh.gain = k.lay_gain ? k.lay_gain + b0 : nullptr;
         rc = layout_delta_launch(io, batch_slice(r.layout, b0, lh.sl), cs.tail, lh);
         if (rc == 0) rc = layout_step_launch(io, cs.tail, lh);
+    } else if (s.ms) {
+        rc = ms_launch(io, cs.tail, s.q, r.solver_hist + o);   // (the half's own part of the history)
     } else if (!k.fuse_tail) {
         rc = rows_launch(io, cs.tail);
     }
@@ -1625,6 +1641,8 @@ static int chain_enqueue(const ChainCtx& k, float** result) {
             }
             s.pull = k.c.lay_g && k.c.lay_g[i] > 0.0f;
             if (s.pull) s.g = k.c.lay_g[i];
+            s.ms = k.c.ms_q != nullptr;
+            if (s.ms) s.q = k.c.ms_q[i];
             for (int h = 0; h < (sp.on ? 2 : 1) && rc == 0; ++h) rc = chain_half_step(k, s, h);
             if (rc) break;
             float* t_ = cur; cur = nxt; nxt = t_;
@@ -1753,6 +1771,17 @@ int sinddm_sample_chain_batch(CHAIN_SHARED_PARAMS, void* aux_stream, int* result
     r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
     return sample_chain_impl(r);
 }
+
+int sinddm_sample_chain_solver(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                               int halo_x, const sinddm_keep_opts* keep, const uint64_t* sample_seeds,
+                               const sinddm_resample_opts* rs, const sinddm_layout_opts* lo, const sinddm_batch_opts* bo,
+                               const sinddm_solver_opts* so) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep); chain_run_set(r, rs); chain_run_set(r, lo); chain_run_set(r, bo);
+    chain_run_set(r, so);
+    r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
+    return sample_chain_impl(r);
+}
 #undef CHAIN_SHARED
 #undef CHAIN_SHARED_PARAMS
 
@@ -1786,6 +1815,28 @@ int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_
     jp.r = jump->r; jp.s = jump->s; jp.d = jump->d; jp.nz = jump_noise;
     const TailIO io{x_t, eps, x_tilde, out, B, C * HW, HW, static_cast<hipStream_t>(stream)};
     return jump_launch(io, t, jp);
+}
+
+int sinddm_reverse_step_ms(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                           const sinddm_step_coefs* coefs, float q, float* hist, const float* edit_w, const float* edit_c,
+                           const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B, int C, int HW, void* stream) {
+    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_m ? keep_a : 1.0f, keep_m ? keep_b : 0.0f);
+    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !hist || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
+    if (!(q >= 0.0f && q <= 3.0e38f) || (q != 0.0f && coefs->mode == 2)) return SINDDM_E_BADARG;
+    if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
+    if (q == 0.0f) {
+        // the plain step, bit for bit: the kernel of sinddm_reverse_step / _edit / _keep itself, then the history on its own
+        const long long n = (long long)B * C * HW;
+        if (const int rc = reverse_step_launch(x_t, eps, x_tilde, out, t, n, C * HW, HW, stream)) return rc;
+        long long bx = (n + 255) / 256;
+        if (bx > 8192) bx = 8192;
+        hipLaunchKernelGGL(step_xp_kernel, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream), x_t, eps, x_tilde, hist,
+                           *coefs, n);
+        SINDDM_LAUNCH_CHECK();
+        return 0;
+    }
+    const TailIO io{x_t, eps, x_tilde, out, B, C * HW, HW, static_cast<hipStream_t>(stream)};
+    return ms_launch(io, t, q, hist);
 }
 
 int sinddm_layout_delta(const float* x_t, const float* eps, const float* x_tilde, const float* layout, float* delta,

@@ -503,6 +503,94 @@ __global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* _
     }
 }
 
+// ---- SECOND-ORDER MULTISTEP step (few-step sampling; DPM-Solver++(2M) written for SinDDM's blurred process; no reference
+// line; contract in include/sinddm_hip.h, derivation in DESIGN.md 3).  The ordinary step on an extrapolated noise estimate:
+//     xp   = step_xp(k, x, e, xb, 1, 0, false)        this step's clean estimate, unedited and unclamped
+//     e'   = e - q * (xp - P)                          P = hist: the previous step's xp; read only when q != 0
+//     hist = xp
+//     out  = tail_eval<EDIT, KEEP>(a, x, e', xb, z, w, c, m, k0)
+// q = rho * (1 - gamma_t) / sqrt_recipm1_ac_t (host, float64) makes the step's xp  xp + rho * (xp - P).  q == 0 hands `e`
+// through untouched: the plain step -- to rounding: with the history's estimate beside it the compiler contracts the four
+// unrolled lanes into other fused multiply-adds than reverse_step_kernel's element loop (1.2e-7 apart on the MI355X,
+// profiles/NOTES_r21.md), so the single-step entry, whose q == 0 form is pinned bit for bit, runs that kernel itself then.
+// `hist` is read and written in place by the thread that owns the element, so it is the one pointer here without
+// __restrict__.
+
+// lanes [jlo, jhi) of the quad at p: one 16-byte store when the quad is full and p is 16-byte aligned, else lane by lane
+__device__ __forceinline__ void quad_store(float* p, int jlo, int jhi, const f32x4& v) {
+    if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(p) = v;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j >= jlo && j < jhi) p[j] = v[j];
+    }
+}
+
+// Over ROWS exactly like reverse_step_jump_kernel (rows of a key's stream, partial first / last quads of a half-batch,
+// per-sample seeds, recorded draws, per-sample map strides); `hist` has the launch's extent, like `out`.
+template <bool EDIT, bool NOISE, bool KEEP>
+__global__ __launch_bounds__(256) void reverse_step_ms_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
+                                                              const float* __restrict__ xtil, float* __restrict__ out,
+                                                              TailArgs a, float q, float* hist, long long span, int chw,
+                                                              int hw) {
+    const long long base = (long long)blockIdx.y * span;
+    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
+    const long long gofs = (long long)a.b0 * chw;           // the launch's first element inside the whole batch
+    const long long kofs = a.sseeds ? 0 : gofs;             // the row's first element inside the key's stream
+    const bool draw = tail_draws<KEEP>(a);
+    const long long q1 = (kofs + span + 3) >> 2;
+    for (long long qd = (kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x; qd < q1; qd += (long long)gridDim.x * 256) {
+        const long long e0 = (qd << 2) - kofs;              // lane 0's index inside the row: -3 .. span - 1
+        const int jlo = e0 < 0 ? (int)-e0 : 0;
+        const int jhi = span - e0 < 4 ? (int)(span - e0) : 4;
+        const long long i0 = base + e0;                     // ... inside the launch's tensors (lanes below jlo are not touched)
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (draw) {
+            if (NOISE) quad_load(a.nz + gofs + i0, jlo, jhi, z);
+            else philox_normal4(key, a.step, (unsigned long long)qd, z);
+        }
+        const long long iv = i0 + jlo;                      // the first valid lane: >= 0, its sample is iv / chw
+        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
+        if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, iv, jlo, jhi, chw, hw, w, c);
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
+        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, jlo, jhi, chw, hw, m, k0);
+        float x[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f};
+        quad_load(xt + i0, jlo, jhi, x);
+        quad_load(eps + i0, jlo, jhi, e);
+        if (a.k.mode != 0) quad_load(xtil + i0, jlo, jhi, xb);
+        float p[4] = {0.f, 0.f, 0.f, 0.f};
+        if (q != 0.0f) {                                    // (the previous step's estimate; not `quad_load`: no __restrict__)
+            float* hp = hist + i0;
+            if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(hp) & 15) == 0) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(hp);
+                p[0] = t[0]; p[1] = t[1]; p[2] = t[2]; p[3] = t[3];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j >= jlo && j < jhi) p[j] = hp[j];
+            }
+        }
+        f32x4 o, h;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            h[j] = step_xp(a.k, x[j], e[j], xb[j], 1.0f, 0.0f, false);
+            const float e2 = q != 0.0f ? e[j] - q * (h[j] - p[j]) : e[j];
+            o[j] = tail_eval<EDIT, KEEP>(a, x[j], e2, xb[j], z[j], w[j], c[j], m[j], k0[j]);
+        }
+        quad_store(hist + i0, jlo, jhi, h);
+        quad_store(out + i0, jlo, jhi, o);
+    }
+}
+
+// the history alone: hist = step_xp of every element (the single-step entry at q == 0, beside the plain step's own kernel)
+__global__ __launch_bounds__(256) void step_xp_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
+                                                      const float* __restrict__ xtil, float* __restrict__ hist,
+                                                      sinddm_step_coefs k, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        hist[i] = step_xp(k, xt[i], eps[i], k.mode != 0 ? xtil[i] : 0.0f, 1.0f, 0.0f, false);
+}
+
 // ---- eps stage + reverse step + in-kernel noise in one pass (sampler runs; H*W % 4 == 0 so that a thread's
 // four pixels are one quad of the flat [B][3][H][W] index the generator is keyed on -- same numbers as the two-kernel
 // path): eps never goes to memory.  EPS (head.h) fills the thread's e[3]: HeadEps, the collapsed head on block 4's g and

@@ -218,6 +218,47 @@ def resample_schedule(t_seq: Sequence[int], resample: int = 1, jump: int = 1):
     return out, jump_to
 
 
+# ---- few-step sampling (no reference counterpart: the reference evaluates the network at every level) ----------------
+def stride_schedule(t_seq: Sequence[int], n: int, spacing: str = "t", kappa=None):
+    """The levels of a few-step run, its ONE owner.  `t_seq` is the descending run [a, a-1, ..., b] `_run_steps` gets; at most
+    `n` of its levels are kept.  Returns (taus, lands): the network is evaluated at taus[i] and that step lands on level
+    lands[i] = taus[i + 1]; the last step lands on b - 1 (-1: the clean image).  taus[0] = a, and taus[-1] = b when more than
+    one level is kept.
+      spacing 't'       rint(linspace(a, b, min(n, len(t_seq))))
+      spacing 'logsnr'  for each of n equally spaced values of log kappa between levels a and b, the level of the run nearest
+                        in log kappa; `kappa[l]` (float64, indexed by level) must rise strictly as l falls over the run
+    Both drop duplicates, so fewer than n levels may remain.  n >= len(t_seq) returns t_seq itself with lands = t - 1."""
+    steps = [int(t) for t in t_seq]
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"stride_schedule: n = {n} must be >= 1")
+    if spacing not in ("t", "logsnr"):
+        raise ValueError(f"stride_schedule: spacing {spacing!r} is neither 't' nor 'logsnr'")
+    if not steps:
+        return [], []
+    if steps[-1] < 0 or any(a - b != 1 for a, b in zip(steps, steps[1:])):
+        raise ValueError("stride_schedule: t_seq must descend in steps of 1 and stay >= 0")
+    a, b = steps[0], steps[-1]
+    if spacing == "logsnr":
+        if kappa is None:
+            raise ValueError("stride_schedule: spacing 'logsnr' needs kappa")
+        kap = np.asarray(kappa, dtype=np.float64)[b:a + 1]                  # kap[j]: level b + j
+        if kap.shape[0] != len(steps) or not bool(np.all(np.isfinite(kap)) and np.all(kap > 0.0) and np.all(np.diff(kap) < 0.0)):
+            raise ValueError("stride_schedule: kappa must be finite, positive and rise strictly as the level falls over the run")
+    if n >= len(steps):
+        return steps, [t - 1 for t in steps]
+    if spacing == "t":
+        taus = [int(v) for v in np.rint(np.linspace(a, b, n))]
+    else:
+        lam = np.log(kap)
+        taus = [b + int(np.argmin(np.abs(lam - v))) for v in np.linspace(lam[-1], lam[0], n)]
+        taus[0] = a
+        if n > 1:
+            taus[-1] = b
+    taus = sorted(set(taus), reverse=True)
+    return taus, taus[1:] + [b - 1]
+
+
 # ---- helpers of layout conditioning (MultiscaleTrainer.paint2image; no reference counterpart) ------------------------
 def layout_strengths(t_seq: Sequence[int], strength: float = 1.0, t_min: int = 0) -> List[float]:
     """The per-step strengths g_i of a layout-conditioned run: `strength` at the steps with t >= t_min, 0 below (those steps

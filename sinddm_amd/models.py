@@ -14,6 +14,9 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
                                 (no reference line: padding_mode='circular' on its nn.Conv2d's)
   per-sample noise seeds     -> sinddm_sample_chain_seeds / sinddm_normal_fill_samples   (`sample_seeds`; no reference
                                 line: the reference never seeds its generator)
+  few-step sampling          -> strided step scalars (`step_coefs_to`) through every chain entry; `solver_order = 2`:
+                                sinddm_sample_chain_solver / sinddm_reverse_step_ms   (no reference line: the reference
+                                evaluates the network at every level)
 
 There is no CPU / eager-PyTorch fallback: tensors must live on a ROCm device and the shared
 library must be built, otherwise calls raise.
@@ -408,7 +411,9 @@ class _ChainCall:
     one that is off goes in as NULL, which is the call without it, launch for launch.  Every tensor and ctypes array the
     library reads through a raw pointer is an attribute here, so it lives as long as the object."""
 
-    def __init__(self, d, img, s, t_seq, jump_to, *, roi, keep, lay, lay_g):
+    def __init__(self, d, img, s, t_seq, jump_to, *, roi, keep, lay, lay_g, lands=None, q=None):
+        # `lands`: the level each step lands on (a strided run; None: t - 1 everywhere, the prebuilt table); `q`: the
+        # multistep factors of a second-order run -- the run then goes through sinddm_sample_chain_solver with a history buffer
         self.lib, self.net, self.s = _lib.load(), d.denoise_fn, s
         hy, hx = self.halo = d._tile_halo()
         tiled = self.tiled = bool(hy or hx)
@@ -419,7 +424,10 @@ class _ChainCall:
         B, _, H, W = x.shape
         tab = d._coef_table(s)
         n = len(t_seq)
-        self.coefs = (_lib.StepCoefs * n)(*[tab[t] for t in t_seq])
+        if lands is None:
+            self.coefs = (_lib.StepCoefs * n)(*[tab[t] for t in t_seq])
+        else:
+            self.coefs = (_lib.StepCoefs * n)(*[d.step_coefs_to(t, u, s, eta=d.eta) for t, u in zip(t_seq, lands)])
         self.tl = (C.c_int * n)(*t_seq)
         self.xt = None
         if self.coefs[0].mode != 0 or self.coefs[n - 1].mode != 0:
@@ -444,7 +452,9 @@ class _ChainCall:
         if keep is not None:
             self.keep = km, kx = wrap(keep[0]), wrap(keep[1])
             ab_tab = d._keep_ab_table()
-            self.ab = (C.c_float * (2 * n))(*[float(v) for t in t_seq for v in ab_tab[t]])
+            # (row l + 1 holds the forward scalars of level l, row 0 those of the clean image)
+            self.ab = (C.c_float * (2 * n))(*[float(v) for l in (lands if lands is not None else [t - 1 for t in t_seq])
+                                              for v in ab_tab[l + 1]])
             self.kopts = _lib.KeepOpts()
             self.kopts.mask, self.kopts.x0 = _lib.ptr(km), _lib.ptr(kx)
         self.ropts = self.jumps = None
@@ -465,6 +475,12 @@ class _ChainCall:
             self.garr = (C.c_float * n)(*lay_g)
             self.lopts = _lib.LayoutOpts()
             self.lopts.layout, self.lopts.down, self.lopts.delta = _lib.ptr(self.lay_map), lay[1], _lib.ptr(self.lay_delta)
+        self.sopts = self.q = self.hist = None
+        if q is not None:
+            self.q = (C.c_float * n)(*q)
+            self.hist = torch.empty_like(x)                    # (written by every step before any step reads it: q[0] = 0)
+            self.sopts = _lib.SolverOpts()
+            self.sopts.hist = _lib.ptr(self.hist)
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
         self.aux = _aux_stream(x.device) if d.two_streams else None
 
@@ -480,12 +496,16 @@ class _ChainCall:
         if self.lopts is not None:
             self.lopts.g = _at(self.garr, i0, C.c_float)
         in_alt = C.c_int(0)
-        _lib.check(self.lib.sinddm_sample_chain_batch(
-            _lib.ptr(net.flat_params), _lib.ptr(self.packed), _lib.ptr(x), _lib.ptr(self.x_alt), _lib.ptr(self.eps),
-            _lib.ptr(self.xt), _at(self.coefs, i0, _lib.StepCoefs), _at(self.tl, i0, C.c_int), k, float(self.s), seed, sid0,
-            net.dim_arg, x.shape[0], self.Hc, self.Wc, self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr(x.device), self.aux,
-            C.byref(in_alt), C.byref(self.opts), *self.halo, ref(self.kopts), _lib.ptr(seeds_dev), ref(self.ropts),
-            ref(self.lopts), ref(self.bopts)), "sinddm_sample_chain_batch")
+        args = [_lib.ptr(net.flat_params), _lib.ptr(self.packed), _lib.ptr(x), _lib.ptr(self.x_alt), _lib.ptr(self.eps),
+                _lib.ptr(self.xt), _at(self.coefs, i0, _lib.StepCoefs), _at(self.tl, i0, C.c_int), k, float(self.s), seed, sid0,
+                net.dim_arg, x.shape[0], self.Hc, self.Wc, self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr(x.device), self.aux,
+                C.byref(in_alt), C.byref(self.opts), *self.halo, ref(self.kopts), _lib.ptr(seeds_dev), ref(self.ropts),
+                ref(self.lopts), ref(self.bopts)]
+        if self.sopts is not None:                             # (the multistep run: the one entry that can say it)
+            self.sopts.q = _at(self.q, i0, C.c_float)
+            _lib.check(self.lib.sinddm_sample_chain_solver(*args, C.byref(self.sopts)), "sinddm_sample_chain_solver")
+        else:
+            _lib.check(self.lib.sinddm_sample_chain_batch(*args), "sinddm_sample_chain_batch")
         if in_alt.value:
             self.x, self.x_alt = self.x_alt, self.x
 
@@ -649,6 +669,18 @@ class MultiScaleGaussianDiffusion(nn.Module):
         self.layout_gain = None
         self.roi_bbs_batch = None
         self.roi_target_patch_batch = None
+        # few-step sampling.  `sample_steps`: None (the network is evaluated at every level of every scale, as in the
+        # reference), an int (at most that many evaluations per scale) or one value per scale (None: every level).
+        # `sample_spacing`: which levels are kept -- 't' equally spaced in t, 'logsnr' equally spaced in log kappa
+        # (functions.stride_schedule).  `solver_order`: 1 the step as it is (at a scale > 0 the DDIM form with SinDDM's
+        # re-blur mix, at scale 0 the DDIM form with `eta`), 2 the second-order multistep step on top of it
+        # (sinddm_sample_chain_solver).  `eta`: the noise of a scale-0 step as a share of the posterior's, 1.0 the
+        # reference's DDPM step, 0 deterministic; `omega` stays the knob of the finer scales.  Sampling options like `tile`;
+        # not stored in checkpoints; not with CLIP guidance or `resample`; order 2 not with `layout_maps`.
+        self.sample_steps = None
+        self.sample_spacing = 't'
+        self.solver_order = 1
+        self.eta = 1.0
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
@@ -751,6 +783,102 @@ class MultiScaleGaussianDiffusion(nn.Module):
             k.mode = 2
             k.sigma = 0.0
         return k
+
+    def step_coefs_to(self, t: int, u: int, s: int, clip_denoised: bool = True, eta: float = 1.0) -> _lib.StepCoefs:
+        """Host scalars of the reverse step from level t that lands on level u < t (u = -1: the clean image), in the fields of
+        `step_coefs`, so that every step kernel takes the strided step unchanged.  u == t - 1 with eta == 1 IS
+        `step_coefs(t, s)`.  Mode 0 (float64 on the tables of `_jump_levels`): the DDIM step with
+        sigma = eta * sqrt((1 - ac_u) / (1 - ac_t)) * sqrt(1 - ac_t / ac_u), coef2 = sqrt(sb_u^2 - sigma^2) / sb_t,
+        coef1 = sa_u - coef2 * sa_t; landing clean coef1 = 1, coef2 = sigma = 0.  Mode 1: the `tm1` fields take level u
+        (var = omega * (1 - ac_u)); landing clean at a scale > 0 is mode 2 with t's own scalars.  `eta` acts in mode 0 only."""
+        t, u, s = int(t), int(u), int(s)
+        if not (0 <= t < self.num_timesteps and -1 <= u < t):
+            raise ValueError(f"step_coefs_to: no step from level {t} to level {u}")
+        if u == t - 1 and float(eta) == 1.0:
+            return self.step_coefs(t, s, clip_denoised)
+        h = self._host()
+        k = _lib.StepCoefs()
+        k.clip = 1 if clip_denoised else 0
+        k.sqrt_recip_ac_t = float(h['sqrt_recip_alphas_cumprod'][t])
+        k.sqrt_recipm1_ac_t = float(h['sqrt_recipm1_alphas_cumprod'][t])
+        one = np.float32(1)
+        if (not self.reblurring) or s == 0:
+            k.mode = 0
+            if u < 0:
+                k.coef1_t, k.coef2_t, k.sigma = 1.0, 0.0, 0.0
+                return k
+            sa, sb, _ = self._jump_levels(s)
+            ac = h['alphas_cumprod'].astype(np.float64)
+            sigma = float(eta) * np.sqrt((1.0 - ac[u]) / (1.0 - ac[t])) * np.sqrt(max(0.0, 1.0 - ac[t] / ac[u]))
+            coef2 = np.sqrt(max(0.0, sb[u] * sb[u] - sigma * sigma)) / sb[t]
+            k.coef1_t, k.coef2_t, k.sigma = float(sa[u] - coef2 * sa[t]), float(coef2), float(sigma)
+            return k
+        g = h['gammas_clamped'][s - 1]
+        k.gamma_t = float(g[t])
+        if u < 0:
+            k.mode = 2
+            k.sigma = 0.0
+            return k
+        k.mode = 1
+        k.gamma_tm1 = float(g[u])
+        ac_u = h['alphas_cumprod'][u]
+        var = np.float32(np.float32(self.omega) * (one - ac_u))
+        logvar = np.log(np.maximum(var, np.float32(1e-20)))
+        k.sqrt_ac_tm1 = float(h['sqrt_alphas_cumprod'][u])
+        k.sqrt_ac_t = float(h['sqrt_alphas_cumprod'][t])
+        k.sqrt_1m_ac_t = float(h['sqrt_one_minus_alphas_cumprod'][t])
+        k.sqrt_1m_ac_tm1_mvar = float(np.sqrt(np.float32(one - ac_u - var)))
+        k.sigma = float(np.exp(np.float32(0.5) * np.float32(logvar)))
+        return k
+
+    def _kappa(self, s: int) -> np.ndarray:
+        """float64 kappa[l] = sa[l] * (1 - gamma[l]) / sb[l] per level of scale s (the tables of `_jump_levels`): the variable
+        the probability flow of SinDDM's blurred process is linear in; it rises as the level falls."""
+        sa, sb, g = self._jump_levels(s)
+        return sa * (1.0 - g) / sb
+
+    def _solver_q(self, s: int, taus, lands):
+        """The multistep factors q_i = rho_i * kappa[tau_i] of a run (float64; sinddm_solver_opts): rho_i =
+        ln(kappa[u_i] / kappa[tau_i]) / (2 ln(kappa[tau_i] / kappa[tau_{i-1}])), 0 on the first step and on a step that lands on
+        the clean image.  kappa[tau] = (1 - gamma[tau]) / sqrt_recipm1_ac[tau]."""
+        kap = self._kappa(s)
+        q = []
+        for i, (t, u) in enumerate(zip(taus, lands)):
+            if i == 0 or u < 0:
+                q.append(0.0)
+                continue
+            rho = np.log(kap[u] / kap[t]) / (2.0 * np.log(kap[t] / kap[taus[i - 1]]))
+            q.append(float(rho * kap[t]))
+        return q
+
+    def _few_step_cfg(self, s: int):
+        """(n or None, spacing, order) of the few-step options for scale s, validated; None when every one is at its default."""
+        order, spacing, eta = int(self.solver_order), self.sample_spacing, float(self.eta)
+        if order not in (1, 2):
+            raise ValueError(f"solver_order = {self.solver_order!r}: 1 or 2")
+        if spacing not in ('t', 'logsnr'):
+            raise ValueError(f"sample_spacing = {spacing!r}: 't' or 'logsnr'")
+        if not 0.0 <= eta:
+            raise ValueError(f"eta = {self.eta!r} must be >= 0")
+        n = self.sample_steps
+        if n is not None and not isinstance(n, (int, np.integer)):
+            n = list(n)
+            if len(n) != self.n_scales:
+                raise ValueError(f"sample_steps has {len(n)} entries for {self.n_scales} scales")
+            n = n[min(int(s), self.n_scales - 1)]              # (custom sizes past the pyramid take the finest scale's entry)
+        if n is not None:
+            n = int(n)
+            if n < 1:
+                raise ValueError(f"sample_steps = {self.sample_steps!r}: at least one evaluation per scale")
+        if self.sample_steps is None and order == 1 and eta == 1.0:
+            return None
+        if self.clip_guided_sampling:
+            raise NotImplementedError("sample_steps / solver_order / eta with clip_guided_sampling: the CLIP-guided step runs in "
+                                      "eager torch ops on the reference's own schedule")
+        if self._resample_cfg() is not None:
+            raise NotImplementedError("sample_steps / solver_order / eta with resample: a resampling jump inside a strided or "
+                                      "multistep run is not built")
+        return n, spacing, order
 
     # ---- reference API: fine-grained pieces (off the hot path; kept for callers / app modes) ----
     def q_mean_variance(self, x_start, t):                                  # models.py:300-304
@@ -1077,6 +1205,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
                          keep their fused tail.  Not with `resample`.
           per sample     a leading batch dimension on a keep / layout map, `roi_bbs_batch`, `layout_gain`: sample b reads
                          slice b.  Neither this nor a layout changes the draws or the `draw_log` entries.
+          few steps      `sample_steps` / `sample_spacing`: `t_seq` is thinned by functions.stride_schedule to the levels the
+                         network is evaluated at, each step lands on the next of them (`step_coefs_to`); `draw_log` entries
+                         keep their shape with those levels as the t list.  `solver_order` = 2: every step runs unfused and
+                         ends in the multistep kernel (sinddm_sample_chain_solver).  Not with `resample`; order 2 not with
+                         `layout_maps`.
         The noise is one of three:
           `noise_fn` + `chain_noise`   the draws the step-by-step loop would fetch, in its order ('step' per step, 'jump' per
                          jump), handed over as buffers of at most CHAIN_NOISE_BYTES: one call per piece.
@@ -1087,6 +1220,14 @@ class MultiScaleGaussianDiffusion(nn.Module):
                          t list), tiled ("chain_tile", ..., (hy, hx)), resampled ("chain_resample", s, seed, ..., jump targets)."""
         t_seq = [int(t) for t in t_seq]
         s = int(s)
+        few = self._few_step_cfg(s)                            # (raises with `resample` / CLIP guidance)
+        lands = q = None                                       # per step: the level it lands on, its multistep factor
+        if few is not None and t_seq:
+            from .functions import stride_schedule
+            t_seq, lands = stride_schedule(t_seq, few[0] if few[0] is not None else len(t_seq), few[1],
+                                           self._kappa(s) if few[1] == 'logsnr' else None)
+            if few[2] == 2:
+                q = self._solver_q(s, t_seq, lands)
         lay = self._layout_entry(s, img)                       # (raises with `resample` / CLIP guidance)
         lay_g = None                                           # per step: the strength of the pull
         if lay is not None:
@@ -1094,6 +1235,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
             lay_g = layout_strengths(t_seq, lay[2], lay[3])
             if not any(v > 0.0 for v in lay_g):
                 lay = lay_g = None
+        if lay is not None and q is not None:
+            raise NotImplementedError("solver_order = 2 with layout_maps: the multistep step through a layout pull is not built")
         rs_cfg = self._resample_cfg()
         jump_to = None                                         # per step of the EXPANDED walk: the level to jump to, or None
         if rs_cfg is not None:
@@ -1107,11 +1250,14 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 and len(t_seq) > 0 and img.is_cuda and img.dtype == torch.float32 and img.dim() == 4
                 and img.shape[1] == self.channels == 3)
         if not fast:
+            hist = torch.empty_like(img) if q is not None else None
             for pos, i in enumerate(t_seq):
-                img = self._p_sample_host_t(img, i, s, step_pos=pos, jump_to=jump_to[pos] if jump_to else None)
+                img = self._p_sample_host_t(img, i, s, step_pos=pos, jump_to=jump_to[pos] if jump_to else None,
+                                            land=lands[pos] if lands is not None else None,
+                                            q=q[pos] if q is not None else None, hist=hist)
                 self._dump_interm(img, s, f'output_t-{i:03}_s-{s}.png')
             return img
-        run = _ChainCall(self, img, s, t_seq, jump_to, roi=roi, keep=keep, lay=lay, lay_g=lay_g)
+        run = _ChainCall(self, img, s, t_seq, jump_to, roi=roi, keep=keep, lay=lay, lay_g=lay_g, lands=lands, q=q)
         n, x, tiled = len(t_seq), run.x, run.tiled
         if self.noise_fn is not None:
             # recorded noise: pieces of as many steps as fit the byte budget; each piece's draws are fetched exactly as the
@@ -1174,11 +1320,19 @@ class MultiScaleGaussianDiffusion(nn.Module):
         return self.denoise_fn(x, t_dev, scale=s)                           # plug point, models.py:356
 
     def _p_sample_host_t(self, x: torch.Tensor, t: int, s: int, clip_denoised: bool = True,
-                         repeat_noise: bool = False, step_pos: int = 0, jump_to: Optional[int] = None) -> torch.Tensor:
+                         repeat_noise: bool = False, step_pos: int = 0, jump_to: Optional[int] = None,
+                         land: Optional[int] = None, q: Optional[float] = None,
+                         hist: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One reverse step with the timestep known on the host: net forward + ONE fused kernel.  `step_pos`: the step's
         position in its run -- with `sample_seeds` it selects the draw (noise_stream_id(s, 'step', step_pos)).  `jump_to`:
         the level a resampling jump takes the step's output back up to (sinddm_reverse_step_jump: step + jump in one kernel,
-        a second draw of kind 'jump'), or None."""
+        a second draw of kind 'jump'), or None.  `land`: the level the step lands on (None: t - 1; `step_coefs_to`).  `q` /
+        `hist`: the multistep factor of the step and the buffer that carries the previous step's clean estimate
+        (sinddm_reverse_step_ms: `hist` is written, and read when q != 0), or None."""
+        if (land is not None or q is not None) and (self.clip_guided_sampling or jump_to is not None):
+            raise NotImplementedError("a strided or multistep step under CLIP guidance or before a resampling jump")
+        if (q is None) != (hist is None):
+            raise ValueError("a multistep step takes q and hist together")
         keep = self._keep_entry(s, x)                                       # (raises under CLIP guidance)
         lay = self._layout_entry(s, x)                                      # (so does this)
         if jump_to is not None and self.clip_guided_sampling:
@@ -1199,7 +1353,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
             z = noise_like(x.shape, x.device, True).contiguous()
         else:
             z = self._draw("step", x.shape, s, t, x.device, step_pos)
-        k = self.step_coefs(t, s, clip_denoised)
+        k = self.step_coefs(t, s, clip_denoised) if land is None else self.step_coefs_to(t, land, s, clip_denoised, self.eta)
         xt = None
         if k.mode != 0:
             xt = self.img_prev_upsample
@@ -1209,6 +1363,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         out = torch.empty_like(x)
         B_, C_, H_, W_ = x.shape
         pull = lay is not None and int(t) >= lay[3]
+        if pull and q is not None:
+            raise NotImplementedError("a layout pull on a multistep step")
         if pull and jump_to is not None:
             raise NotImplementedError("a layout pull on a step that is followed by a resampling jump")
         z2 = self._draw("jump", x.shape, s, t, x.device, step_pos) if jump_to is not None else None
@@ -1231,19 +1387,22 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 g_b = float(np.float32(g) * gains[b]) if gains is not None else g
                 sl = lambda v: None if v is None else v[b:b + 1]
                 self._step_tail(sl(x), sl(eps), sl(xt), sl(z), sl(z2), sl(out), k, t, s, keep_b, lay_b, lay[1] if pull else 0, g_b,
-                                row(ew, 2, b), row(ec, 3, b), jump_to)
+                                row(ew, 2, b), row(ec, 3, b), jump_to, land, q, sl(hist))
             return out
-        self._step_tail(x, eps, xt, z, z2, out, k, t, s, keep, lay[0] if pull else None, lay[1] if pull else 0, g, ew, ec, jump_to)
+        self._step_tail(x, eps, xt, z, z2, out, k, t, s, keep, lay[0] if pull else None, lay[1] if pull else 0, g, ew, ec, jump_to,
+                        land, q, hist)
         return out
 
-    def _step_tail(self, x, eps, xt, z, z2, out, k, t, s, keep, lay, N, g, ew, ec, jump_to):
+    def _step_tail(self, x, eps, xt, z, z2, out, k, t, s, keep, lay, N, g, ew, ec, jump_to, land=None, q=None, hist=None):
         """The single-step entry that ends a step of `_p_sample_host_t`: `out` is written.  `keep` = (mask, x0) or None, `lay`
         the layout picture of a conditioned step (block size N, strength g) or None, (ew, ec) the ROI maps or None, `jump_to`
-        the level of a resampling jump (second draw z2) or None -- all shared by the B samples of this call."""
+        the level of a resampling jump (second draw z2) or None -- all shared by the B samples of this call.  `land`: the level
+        the step lands on (None: t - 1), whose forward scalars the keep uses; (q, hist): a multistep step."""
         lib = _lib.load()
         B_, C_, H_, W_ = x.shape
         st = _lib.stream_ptr(x.device)
-        ka, kb = (float(v) for v in self._keep_ab_table()[int(t)]) if keep is not None else (1.0, 0.0)
+        row_ab = int(t) if land is None else int(land) + 1      # (row l + 1: the forward scalars of level l)
+        ka, kb = (float(v) for v in self._keep_ab_table()[row_ab]) if keep is not None else (1.0, 0.0)
         km, kx = (_lib.ptr(keep[0]), _lib.ptr(keep[1])) if keep is not None else (None, None)
         if lay is not None:
             # the conditioned step: block deltas of (layout - x_recon), then the step with c_eff = ec + g * U(D)
@@ -1260,6 +1419,10 @@ class MultiScaleGaussianDiffusion(nn.Module):
             _lib.check(lib.sinddm_reverse_step_jump(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(z2),
                                                     _lib.ptr(out), C.byref(k), C.byref(jc), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb,
                                                     B_, C_, H_ * W_, st), "sinddm_reverse_step_jump")
+        elif hist is not None:
+            _lib.check(lib.sinddm_reverse_step_ms(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out), C.byref(k),
+                                                  float(q), _lib.ptr(hist), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb, B_, C_,
+                                                  H_ * W_, st), "sinddm_reverse_step_ms")
         elif keep is not None:
             _lib.check(lib.sinddm_reverse_step_keep(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
                                                     C.byref(k), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb, B_, C_, H_ * W_, st),
