@@ -390,14 +390,25 @@ __global__ __launch_bounds__(256) void dwconv5_kernel(const float* __restrict__ 
 }
 
 // Register-window variant for rows that are a multiple of 4 pixels (16-byte aligned): no LDS, no barrier.  A lane owns 4
-// consecutive output columns of DWR_ROWS output rows and slides over the DWR_ROWS + 4 input rows: per input row three
-// aligned 16-byte loads (columns x-4 .. x+7, eight of them used) feed the five output rows it touches (100 FMAs); the 25
-// taps are wave-uniform (scalar registers).  Every load of a lane is independent of its FMAs, so many rows are in flight
-// per wave and the only dependence on other lanes is the L1 (the halo columns of the neighbours).
+// consecutive output columns of DWR_ROWS output rows and slides over the DWR_ROWS + 4 input rows: per input row ONE
+// aligned 16-byte load of its own quad; the two columns either side of it are the neighbour lanes' registers (two DPP wave
+// shifts each way), and only lane 0 / lane 63 fetch the pair beyond the wave's 256 columns (one 8-byte load, every other lane
+// out of range).  The eight columns feed the five output rows the input row touches (100 FMAs, each output's 25 in the order
+// input row, then tap column); the 25 taps are wave-uniform (scalar registers).  Every load of a lane is independent of its
+// FMAs, so many rows are in flight per wave.  (Side quads from memory instead, profiles/NOTES_r22.md: +4 % time, three
+// times the L1 requests.)
 #ifndef DWR_ROWS_
-#define DWR_ROWS_ 12
+#define DWR_ROWS_ 16     // (16 rows re-read 4 halo rows: 170 VGPRs, two waves per SIMD, and still faster than 12 or 8 rows at three or four)
 #endif
 constexpr int DWR_ROWS = DWR_ROWS_;
+
+// lane i takes `src` of lane i - 1 (wave_shr:1) / lane i + 1 (wave_shl:1); the lane without such a neighbour keeps `old`
+__device__ __forceinline__ float dpp_wave_shr1(float old, float src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float dpp_wave_shl1(float old, float src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src), 0x130, 0xf, 0xf, false));
+}
 
 __global__ __launch_bounds__(256) void dwconv5_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, const float* __restrict__ cond,
@@ -407,7 +418,7 @@ __global__ __launch_bounds__(256) void dwconv5_rows_kernel(const float* __restri
     // Wt: true width when the rows are padded to W (input pads hold zeros, output pads are written as zeros); else = W
     const int c = blockIdx.y, b = blockIdx.z;
     const int by = blockIdx.x / bandsX, bx = blockIdx.x - by * bandsX;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (rows and their offsets: scalar)
     const int x4 = (bx * 64 + lane) * 4;                     // first output column of this lane
     const int y0 = (by * 4 + wv) * DWR_ROWS;                 // first output row of this wave
     const size_t plane = ((size_t)b * C + c) * H * W;
@@ -417,22 +428,28 @@ __global__ __launch_bounds__(256) void dwconv5_rows_kernel(const float* __restri
     const float add = (bias ? bias[c] : 0.0f) + (cond ? cond[(size_t)b * cond_stride + c] : 0.0f);
     if (y0 >= H) return;
     const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + plane), 0, H * W * 4, 0x00020000);
-    constexpr int OOBI = 0x40000000;
     const bool colok = x4 < W;
-    // quads left / right of the lane's own: outside the row -> zero (W % 4 == 0: a quad is entirely in or out)
+    // Per-lane column byte offsets, fixed for the whole wave; a row adds its own (wave-uniform) byte offset.  A column outside
+    // the row starts at OOBV, and a row outside the plane makes the sum negative or >= H W 4: as an unsigned offset each is
+    // beyond num_records (<= 2^30), so the buffer load returns zeros without a compare per row.
+    // (W % 4 == 0: a quad is entirely in the row or entirely out)
+    constexpr unsigned OOBV = 0x50000000u;
     const bool lok = colok && x4 >= 4, rok = colok && x4 + 4 < W;
+    const unsigned cm = colok ? (unsigned)x4 * 4u : OOBV;
+    // the pair a lane cannot get from a neighbour lane: left of lane 0, right of lane 63
+    const unsigned ce = lane == 0 ? (lok ? (unsigned)x4 * 4u - 8u : OOBV) : ((lane == 63 && rok) ? (unsigned)x4 * 4u + 16u : OOBV);
     f32x4 acc[DWR_ROWS];
 #pragma unroll
     for (int r = 0; r < DWR_ROWS; ++r) acc[r] = f32x4{add, add, add, add};
 #pragma unroll
     for (int ir = 0; ir < DWR_ROWS + 4; ++ir) {
-        const int gy = y0 + ir - 2;
-        const bool rowok = gy >= 0 && gy < H;
-        const int base = (gy * W + x4) * 4;
-        const f32x4 ql = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, (rowok && lok) ? base - 16 : OOBI, 0, 0));
-        const f32x4 qm = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, (rowok && colok) ? base : OOBI, 0, 0));
-        const f32x4 qr = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, (rowok && rok) ? base + 16 : OOBI, 0, 0));
-        const float in[8] = {ql[2], ql[3], qm[0], qm[1], qm[2], qm[3], qr[0], qr[1]};     // columns x4-2 .. x4+5
+        const unsigned ro = (unsigned)((y0 + ir - 2) * W) * 4u;          // (wave-uniform)
+        const f32x4 qm = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, (int)(cm + ro), 0, 0));
+        const f32x2 qe = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsx, (int)(ce + ro), 0, 0));
+        // columns x4-2 .. x4+5: the outer pairs are lane -1's last two and lane +1's first two (a lane right of the row holds
+        // zeros); lane 0 / lane 63 have no such neighbour and keep the pair they loaded
+        const float in[8] = {dpp_wave_shr1(qe[0], qm[2]), dpp_wave_shr1(qe[1], qm[3]), qm[0], qm[1], qm[2], qm[3],
+                             dpp_wave_shl1(qe[0], qm[0]), dpp_wave_shl1(qe[1], qm[1])};
 #pragma unroll
         for (int r = 0; r < DWR_ROWS; ++r) {
             const int ky = ir - r;                               // input row ir contributes tap row ky to output row r
@@ -445,6 +462,7 @@ __global__ __launch_bounds__(256) void dwconv5_rows_kernel(const float* __restri
             }
         }
     }
+    const bool pads = bx * 256 + 256 > Wt;                                // (block-uniform) this band holds output pad columns
     float mx = 0.f;
 #pragma unroll
     for (int r = 0; r < DWR_ROWS; ++r) {
@@ -453,11 +471,12 @@ __global__ __launch_bounds__(256) void dwconv5_rows_kernel(const float* __restri
             const size_t o = plane + (size_t)gy * W + x4;
             f32x4 v = acc[r];
             if (addt) v += *reinterpret_cast<const f32x4*>(addt + o);
-            if (x4 + 4 > Wt) {
+            if (pads) {
 #pragma unroll
                 for (int cc = 0; cc < 4; ++cc) v[cc] = x4 + cc < Wt ? v[cc] : 0.0f;
             }
-            mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+            mx = fmaxf(fmaxf(mx, fabsf(v[0])), fabsf(v[1]));
+            mx = fmaxf(fmaxf(mx, fabsf(v[2])), fabsf(v[3]));
             *reinterpret_cast<f32x4*>(out + o) = v;
         }
     }
