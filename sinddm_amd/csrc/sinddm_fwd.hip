@@ -935,6 +935,36 @@ static void tail_dispatch(const TailArgs& t, F&& f) {
     t.ew ? noise(std::true_type{}) : noise(std::false_type{});
 }
 
+// the tensors and the extent of one unfused tail launch: Bn samples of chw elements (hw per channel) on stream st
+struct TailIO {
+    const float* x_t;
+    const float* eps;
+    const float* x_tilde;
+    float* out;
+    int Bn, chw, hw;
+    hipStream_t st;
+};
+
+// the rows of a tail launch: one per sample with per-sample seeds, else one row of the whole launch
+static long long tail_span(const TailIO& io, const TailArgs& t) { return t.sseeds ? io.chw : (long long)io.Bn * io.chw; }
+
+// One launch of a tail kernel over rows: `kernel(E, N, K)` names the instantiation (TAIL_KERNEL), `extra` is what the kernel
+// takes between the TailArgs and the extent (it documents them).  `mid_quad`: a kernel on the stream-row walk (step_tail.h).
+template <class Pick, class... Extra>
+static int tail_rows_launch(const TailIO& io, const TailArgs& t, bool mid_quad, Pick kernel, const Extra&... extra) {
+    const long long span = tail_span(io, t);
+    long long gx = mid_quad ? ((span + 3) / 4 + 1 + 255) / 256     // (+ 1: a row that starts inside a quad of its stream)
+                            : ((span + 3) / 4 + 255) / 256;        // (no + 1: a row of this kernel starts on a quad of its stream)
+    if (gx > 8192) gx = 8192;
+    tail_dispatch(t, [&](auto E, auto N, auto K) {
+        hipLaunchKernelGGL(kernel(E, N, K), dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps,
+                           io.x_tilde, io.out, t, extra..., span, io.chw, io.hw);
+    });
+    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+}
+#define TAIL_KERNEL(name) \
+    [](auto E, auto N, auto K) { return &name<decltype(E)::value, decltype(N)::value, decltype(K)::value>; }
+
 // Where inference takes the collapsed head (head.h) instead of block 4's conv2 + residual projection + final_conv: the
 // activation rows are 16-byte aligned (Wp = the workspace pitch: W % 4 == 0, or the plan pads its rows), which is also
 // where a sampler run fuses its tail ((H W) % 4 == 0 or padded rows: sample_chain_impl); a plane stays below the buffer
@@ -1404,56 +1434,18 @@ int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* see
 #define SINDDM_SPLIT_ITEMS_LO 3
 #endif
 
-// the tensors and the extent of one unfused tail launch: Bn samples of chw elements (hw per channel) on stream st
-struct TailIO {
-    const float* x_t;
-    const float* eps;
-    const float* x_tilde;
-    float* out;
-    int Bn, chw, hw;
-    hipStream_t st;
-};
-
-// the rows of a tail launch: one per sample with per-sample seeds, else one row of the whole launch
-static long long tail_span(const TailIO& io, const TailArgs& t) { return t.sseeds ? io.chw : (long long)io.Bn * io.chw; }
-
-// the plain step of a shape without a fused tail (reverse_step_rows_kernel); t.b0 / t.sseeds / t.nz as the kernel documents them
+// the plain step of a shape without a fused tail; t.b0 / t.sseeds / t.nz as the kernel documents them
 static int rows_launch(const TailIO& io, const TailArgs& t) {
-    const long long span = tail_span(io, t);
-    long long gx = ((span + 3) / 4 + 255) / 256;               // (no + 1: a row of this kernel starts on a quad of its stream)
-    if (gx > 8192) gx = 8192;
-    tail_dispatch(t, [&](auto E, auto N, auto K) {
-        hipLaunchKernelGGL((reverse_step_rows_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
-                           span, io.chw, io.hw);
-    });
-    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+    return tail_rows_launch(io, t, false, TAIL_KERNEL(reverse_step_rows_kernel));
 }
 
-// reverse step + jump (reverse_step_jump_kernel); jp.nz as the kernel documents it
+// reverse step + jump
 static int jump_launch(const TailIO& io, const TailArgs& t, const JumpArgs& jp) {
-    const long long span = tail_span(io, t);
-    long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
-    if (gx > 8192) gx = 8192;
-    tail_dispatch(t, [&](auto E, auto N, auto K) {
-        hipLaunchKernelGGL((reverse_step_jump_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
-                           jp, span, io.chw, io.hw);
-    });
-    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+    return tail_rows_launch(io, t, true, TAIL_KERNEL(reverse_step_jump_kernel), jp);
 }
-
-// the multistep step (reverse_step_ms_kernel): rows as in jump_launch; `hist` has the launch's extent
+// the multistep step: `hist` has the launch's extent
 static int ms_launch(const TailIO& io, const TailArgs& t, float q, float* hist) {
-    const long long span = tail_span(io, t);
-    long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
-    if (gx > 8192) gx = 8192;
-    tail_dispatch(t, [&](auto E, auto N, auto K) {
-        hipLaunchKernelGGL((reverse_step_ms_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
-                           q, hist, span, io.chw, io.hw);
-    });
-    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+    return tail_rows_launch(io, t, true, TAIL_KERNEL(reverse_step_ms_kernel), q, hist);
 }
 
 // the geometry of a layout-conditioned scale (LayoutArgs without D and g): centre Hc x Wc, block size N
@@ -1481,17 +1473,9 @@ static int layout_delta_launch(const TailIO& io, const float* layout, const Tail
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
 }
 
-// the conditioned step (reverse_step_layout_kernel): rows as in jump_launch
+// the conditioned step
 static int layout_step_launch(const TailIO& io, const TailArgs& t, const LayoutArgs& g) {
-    const long long span = tail_span(io, t);
-    long long gx = ((span + 3) / 4 + 1 + 255) / 256;           // (+ 1: a row that starts inside a quad of its stream)
-    if (gx > 8192) gx = 8192;
-    tail_dispatch(t, [&](auto E, auto N, auto K) {
-        hipLaunchKernelGGL((reverse_step_layout_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value>),
-                           dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps, io.x_tilde, io.out, t,
-                           g, span, io.chw, io.hw);
-    });
-    return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+    return tail_rows_launch(io, t, true, TAIL_KERNEL(reverse_step_layout_kernel), g);
 }
 
 // ---- the sampler chain: one ChainRun (chain_run.h) from every entry, checked there, enqueued here ------------------------
@@ -1804,58 +1788,78 @@ int sinddm_sample_chain_solver(CHAIN_SHARED_PARAMS, void* aux_stream, int* resul
 #undef CHAIN_SHARED
 #undef CHAIN_SHARED_PARAMS
 
+// What the single-step entries over a batch shape (B samples of C planes of hw elements) share: the step's TailArgs (the
+// keep scalars count only beside the keep maps: (1, 0) without them), its TailIO, and the checks in the order every entry
+// keeps -- SINDDM_E_BADARG for a missing tensor, a half pair of maps, `own_ok` false (the entry's own requirements) or an
+// empty shape, then SINDDM_E_BADSHAPE for a sample beyond an int's range.  rc == 0: ready to launch.
+struct StepCall {
+    int rc;
+    TailArgs t;
+    TailIO io;
+};
+static StepCall step_call(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                          const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, const float* keep_m,
+                          const float* keep_x0, float keep_a, float keep_b, bool own_ok, int B, int C, long long hw, void* stream) {
+    StepCall sc{};
+    sc.t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_m ? keep_a : 1.0f, keep_m ? keep_b : 0.0f);
+    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, sc.t) || !own_ok || B <= 0 || C <= 0 || hw <= 0) sc.rc = SINDDM_E_BADARG;
+    else if (hw > 0x7fffffffLL / C) sc.rc = SINDDM_E_BADSHAPE;
+    else sc.io = TailIO{x_t, eps, x_tilde, out, B, (int)(C * hw), (int)hw, static_cast<hipStream_t>(stream)};
+    return sc;
+}
+// the plain step's own kernel on a checked call
+static int plain_step_launch(const StepCall& sc) {
+    return reverse_step_launch(sc.io.x_t, sc.io.eps, sc.io.x_tilde, sc.io.out, sc.t, (long long)sc.io.Bn * sc.io.chw, sc.io.chw, sc.io.hw,
+                               sc.io.st);
+}
+
 int sinddm_reverse_step_edit(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                              const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, int B, int C,
                              int HW, void* stream) {
-    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c);
-    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !edit_w || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
-    if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
-    return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)B * C * HW, C * HW, HW, stream);
+    const StepCall sc = step_call(x_t, eps, x_tilde, noise, out, coefs, edit_w, edit_c, nullptr, nullptr, 0.0f, 0.0f, edit_w != nullptr, B, C,
+                                  HW, stream);
+    return sc.rc ? sc.rc : plain_step_launch(sc);
 }
 
 int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                              const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, const float* keep_m,
                              const float* keep_x0, float keep_a, float keep_b, int B, int C, int HW, void* stream) {
-    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b);
-    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !keep_m || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
-    if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
-    return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)B * C * HW, C * HW, HW, stream);
+    const StepCall sc = step_call(x_t, eps, x_tilde, noise, out, coefs, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b, keep_m != nullptr,
+                                  B, C, HW, stream);
+    return sc.rc ? sc.rc : plain_step_launch(sc);
 }
 
 int sinddm_reverse_step_jump(const float* x_t, const float* eps, const float* x_tilde, const float* noise, const float* jump_noise,
                              float* out, const sinddm_step_coefs* coefs, const sinddm_jump_coefs* jump, const float* edit_w,
                              const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B, int C,
                              int HW, void* stream) {
-    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_m ? keep_a : 1.0f, keep_m ? keep_b : 0.0f);
-    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !jump_noise || !jump || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
-    if (!jump_valid(*jump, *coefs)) return SINDDM_E_BADARG;
-    if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
+    const bool own_ok = jump_noise && jump && coefs && jump_valid(*jump, *coefs);
+    const StepCall sc = step_call(x_t, eps, x_tilde, noise, out, coefs, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b, own_ok, B, C, HW,
+                                  stream);
+    if (sc.rc) return sc.rc;
     JumpArgs jp{};
     jp.r = jump->r; jp.s = jump->s; jp.d = jump->d; jp.nz = jump_noise;
-    const TailIO io{x_t, eps, x_tilde, out, B, C * HW, HW, static_cast<hipStream_t>(stream)};
-    return jump_launch(io, t, jp);
+    return jump_launch(sc.io, sc.t, jp);
 }
 
 int sinddm_reverse_step_ms(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
                            const sinddm_step_coefs* coefs, float q, float* hist, const float* edit_w, const float* edit_c,
                            const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B, int C, int HW, void* stream) {
-    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_m ? keep_a : 1.0f, keep_m ? keep_b : 0.0f);
-    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !hist || B <= 0 || C <= 0 || HW <= 0) return SINDDM_E_BADARG;
-    if (!(q >= 0.0f && q <= 3.0e38f) || (q != 0.0f && coefs->mode == 2)) return SINDDM_E_BADARG;
-    if ((long long)C * HW > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
+    const bool own_ok = hist && coefs && q >= 0.0f && q <= 3.0e38f && !(q != 0.0f && coefs->mode == 2);
+    const StepCall sc = step_call(x_t, eps, x_tilde, noise, out, coefs, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b, own_ok, B, C, HW,
+                                  stream);
+    if (sc.rc) return sc.rc;
     if (q == 0.0f) {
         // the plain step, bit for bit: the kernel of sinddm_reverse_step / _edit / _keep itself, then the history on its own
         const long long n = (long long)B * C * HW;
-        if (const int rc = reverse_step_launch(x_t, eps, x_tilde, out, t, n, C * HW, HW, stream)) return rc;
+        if (const int rc = plain_step_launch(sc)) return rc;
         long long bx = (n + 255) / 256;
         if (bx > 8192) bx = 8192;
-        hipLaunchKernelGGL(step_xp_kernel, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream), x_t, eps, x_tilde, hist,
-                           *coefs, n);
+        hipLaunchKernelGGL(step_xp_kernel, dim3((unsigned)bx), dim3(256), 0, sc.io.st, x_t, eps, x_tilde, hist, *coefs, n);
         SINDDM_LAUNCH_CHECK();
         return 0;
     }
-    const TailIO io{x_t, eps, x_tilde, out, B, C * HW, HW, static_cast<hipStream_t>(stream)};
-    return ms_launch(io, t, q, hist);
+    return ms_launch(sc.io, sc.t, q, hist);
 }
 
 int sinddm_layout_delta(const float* x_t, const float* eps, const float* x_tilde, const float* layout, float* delta,
@@ -1876,15 +1880,14 @@ int sinddm_reverse_step_layout(const float* x_t, const float* eps, const float* 
                                const sinddm_step_coefs* coefs, const float* delta, float g, int down, const float* edit_w,
                                const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b, int B,
                                int H, int W, int halo_y, int halo_x, int wrap_y, int wrap_x, void* stream) {
-    const TailArgs t = step_tail_args(coefs, noise, edit_w, edit_c, keep_m, keep_x0, keep_m ? keep_a : 1.0f, keep_m ? keep_b : 0.0f);
-    if (!step_args_ok(x_t, eps, x_tilde, out, coefs, t) || !delta || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
-    if (down < 1 || down > 64 || !(g >= 0.0f && g <= 1.0f)) return SINDDM_E_BADARG;
-    if (halo_y < 0 || halo_x < 0 || halo_y > (1 << 20) || halo_x > (1 << 20)) return SINDDM_E_BADARG;
-    LayoutArgs la = layout_geom(H, W, halo_y, halo_x, down, wrap_y != 0, wrap_x != 0);
-    if ((long long)CHANNELS * la.H * la.W > 0x7fffffffLL) return SINDDM_E_BADSHAPE;
+    const bool own_ok = delta && H > 0 && W > 0 && down >= 1 && down <= 64 && g >= 0.0f && g <= 1.0f && halo_y >= 0 && halo_x >= 0 &&
+                        halo_y <= (1 << 20) && halo_x <= (1 << 20);
+    LayoutArgs la{};
+    if (own_ok) la = layout_geom(H, W, halo_y, halo_x, down, wrap_y != 0, wrap_x != 0);
     la.D = delta; la.g = g;
-    const TailIO io{x_t, eps, x_tilde, out, B, CHANNELS * la.H * la.W, la.H * la.W, static_cast<hipStream_t>(stream)};
-    return layout_step_launch(io, t, la);
+    const StepCall sc = step_call(x_t, eps, x_tilde, noise, out, coefs, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b, own_ok, B, CHANNELS,
+                                  (long long)la.H * la.W, stream);
+    return sc.rc ? sc.rc : layout_step_launch(sc.io, sc.t, la);
 }
 
 #ifdef W2_PHASE

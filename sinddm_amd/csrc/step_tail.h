@@ -243,6 +243,106 @@ __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __r
     }
 }
 
+// ---- the STREAM-ROW WALK of the tails launched behind the network's eps (jump, layout, multistep): what they share, written
+// once.  Over ROWS, like reverse_step_rows_kernel: row blockIdx.y is `span` elements from row * span of the launch's tensors.
+// With per-sample seeds a row is a sample (span = chw, key = sseeds[row], quads counted from the sample's start); otherwise
+// the launch is one row of a.seed's stream that starts at element b0 * chw of the WHOLE batch -- a half-batch of a
+// two-stream run, whose start is inside a quad of the stream when b0 * chw % 4 != 0.  So a thread owns a quad OF THE KEY'S
+// STREAM and lanes [jlo, jhi) of it lie inside the row: the first and the last quad of a row may be partial.
+// reverse_step_rows_kernel is not on this walk: its rows start on a quad of their own stream, and its element-by-element
+// exception would make the walk branch on its caller.
+
+// lanes [jlo, jhi) of the quad at p: one 16-byte access when the quad is full and p is 16-byte aligned, else lane by lane.
+// Plain pointers: the multistep history goes through both, read and written in place by the thread that owns the element.
+__device__ __forceinline__ void quad_load(const float* p, int jlo, int jhi, float (&v)[4]) {
+    if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j >= jlo && j < jhi) v[j] = p[j];
+    }
+}
+__device__ __forceinline__ void quad_store(float* p, int jlo, int jhi, const f32x4& v) {
+    if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(p) = v;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j >= jlo && j < jhi) p[j] = v[j];
+    }
+}
+
+// a thread's row: once per thread.  Its quads are q0, q0 + gridDim.x * 256, ... below q1.
+struct StreamRow {
+    unsigned long long key;             // the row's Philox key
+    long long base;                     // the row's first element inside the launch's tensors
+    long long gofs;                     // the launch's first element inside the whole batch (where recorded draws are read)
+    long long kofs;                     // the row's first element inside the key's stream
+    long long span, q0, q1;
+    int chw, hw;
+    bool draw;                          // tail_draws
+};
+template <bool KEEP>
+__device__ __forceinline__ StreamRow stream_row(const TailArgs& a, long long span, int chw, int hw) {
+    StreamRow r;
+    r.key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
+    r.base = (long long)blockIdx.y * span;
+    r.gofs = (long long)a.b0 * chw;
+    r.kofs = a.sseeds ? 0 : r.gofs;
+    r.span = span; r.chw = chw; r.hw = hw;
+    r.q0 = (r.kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x;
+    r.q1 = (r.kofs + span + 3) >> 2;
+    r.draw = tail_draws<KEEP>(a);
+    return r;
+}
+
+// one quad of the walk: all that a form's arithmetic reads.  Lanes outside [jlo, jhi) hold zeros and the neutral maps; the
+// four lanes are evaluated unrolled either way, and quad_store writes the valid ones at i0.
+struct StreamQuad {
+    long long i0;                       // lane 0's index inside the launch's tensors (lanes below jlo are not touched)
+    int jlo, jhi;
+    int b, r;                           // the first valid lane's sample (launch-local) and its index inside the sample
+    float z[4];                         // the step's draws: Philox quad q of (key, a.step); NOISE: a.nz at gofs + i0; 0 when nothing draws
+    float w[4], c[4], m[4], k0[4];      // the edit maps (1, 0 without EDIT) and the keep maps (0, 0 without KEEP)
+    float x[4], e[4], xb[4];            // x_t, eps, x-tilde (0 in mode 0)
+};
+template <bool EDIT, bool NOISE, bool KEEP>
+__device__ __forceinline__ StreamQuad stream_quad(const TailArgs& a, const StreamRow& row, long long q) {
+    StreamQuad s{};
+    const long long e0 = (q << 2) - row.kofs;               // lane 0's index inside the row: -3 .. span - 1
+    s.jlo = e0 < 0 ? (int)-e0 : 0;
+    s.jhi = row.span - e0 < 4 ? (int)(row.span - e0) : 4;
+    s.i0 = row.base + e0;
+    if (row.draw) {
+        if (NOISE) quad_load(a.nz + row.gofs + s.i0, s.jlo, s.jhi, s.z);
+        else philox_normal4(row.key, a.step, (unsigned long long)q, s.z);
+    }
+    const long long iv = s.i0 + s.jlo;                      // the first valid lane: >= 0, its sample is iv / chw
+    s.b = (int)(iv / row.chw);
+    s.r = (int)(iv - (long long)s.b * row.chw);
+    // (quad_maps indexes its arrays with a loop counter: arrays of their own, so that the struct stays in registers)
+    float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
+    if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, iv, s.jlo, s.jhi, row.chw, row.hw, w, c);
+    float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
+    if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, s.jlo, s.jhi, row.chw, row.hw, m, k0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s.w[j] = w[j]; s.c[j] = c[j]; s.m[j] = m[j]; s.k0[j] = k0[j];
+    }
+    return s;
+}
+// ... and its tensors, a call of their own: a form reads them behind what it adds to the draws or the maps (the jump's second
+// draw, the layout pull with its own loads), or x, e and xb would sit in registers across that: the layout form with both
+// maps then needs 75 VGPRs for 63, one wave less per SIMD
+__device__ __forceinline__ void stream_quad_load(const TailArgs& a, StreamQuad& s, const float* __restrict__ xt,
+                                                 const float* __restrict__ eps, const float* __restrict__ xtil) {
+    quad_load(xt + s.i0, s.jlo, s.jhi, s.x);
+    quad_load(eps + s.i0, s.jlo, s.jhi, s.e);
+    if (a.k.mode != 0) quad_load(xtil + s.i0, s.jlo, s.jhi, s.xb);
+}
+
 // ---- reverse step + RESAMPLING JUMP in one pass (RePaint's upward move on SinDDM's blurred forward process; no reference
 // line; derivation in DESIGN.md 3).  The step t = l + 1 writes y at level l; the jump takes it back up to level l' = l + J:
 //     out = r * y + s * z2 + d * (x-tilde - x0h)
@@ -256,10 +356,14 @@ struct JumpArgs {
 
 // the clean-image estimate of a step, `xp` of reverse_step_mean (x0 itself in mode 0): after the ROI edit, clamped when
 // k.clip as mode 2 clamps it.  A helper of its own: the tails keep reverse_step_mean's contraction pattern and its numbers.
-__device__ __forceinline__ float step_x0(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c, bool edit) {
+// step_xp is the same estimate NOT clamped: what the layout pull and the multistep history act on.
+__device__ __forceinline__ float step_xp(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c, bool edit) {
     const float x0 = k.sqrt_recip_ac_t * x - k.sqrt_recipm1_ac_t * e;
-    float xp = k.mode == 0 ? x0 : (x0 - k.gamma_t * xb) / (1.0f - k.gamma_t);
-    if (edit) xp = w * xp + c;
+    const float xp = k.mode == 0 ? x0 : (x0 - k.gamma_t * xb) / (1.0f - k.gamma_t);
+    return edit ? w * xp + c : xp;
+}
+__device__ __forceinline__ float step_x0(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c, bool edit) {
+    const float xp = step_xp(k, x, e, xb, w, c, edit);
     return k.clip ? fminf(fmaxf(xp, -1.0f), 1.0f) : xp;
 }
 
@@ -277,68 +381,27 @@ __device__ __forceinline__ float jump_eval(const TailArgs& a, const JumpArgs& jp
     return o;
 }
 
-// lanes [jlo, jhi) of the quad at p: one 16-byte access when the quad is full and p is 16-byte aligned, else lane by lane
-__device__ __forceinline__ void quad_load(const float* __restrict__ p, int jlo, int jhi, float (&v)[4]) {
-    if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j >= jlo && j < jhi) v[j] = p[j];
-    }
-}
-
-// Over ROWS, like reverse_step_rows_kernel: row blockIdx.y is `span` elements from row * span of the launch's tensors.  With
-// per-sample seeds a row is a sample (span = chw, key = sseeds[row], quads counted from the sample's start); otherwise the
-// launch is one row of a.seed's stream that starts at element b0 * chw of the WHOLE batch -- a half-batch of a two-stream
-// run, whose start is inside a quad of the stream when b0 * chw % 4 != 0.  So a thread owns a quad OF THE KEY'S STREAM
-// and lanes [jlo, jhi) of it lie inside the row: the first and the last quad of a row may be partial.  Two draws per
-// element: z from stream a.step (the step's own, as in every tail), z2 from a.step + SINDDM_JUMP_STREAM, same key, same
-// quad.  NOISE reads both at the element's flat index inside the whole batch (a.nz, jp.nz) instead.
+// Two draws per element: z from stream a.step (the step's own, as in every tail), z2 from a.step + SINDDM_JUMP_STREAM, same
+// key, same quad.  NOISE reads both at the element's flat index inside the whole batch (a.nz, jp.nz) instead.
 template <bool EDIT, bool NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_jump_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                 const float* __restrict__ xtil, float* __restrict__ out,
                                                                 TailArgs a, JumpArgs jp, long long span, int chw, int hw) {
-    const long long base = (long long)blockIdx.y * span;
-    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
-    const long long gofs = (long long)a.b0 * chw;           // the launch's first element inside the whole batch
-    const long long kofs = a.sseeds ? 0 : gofs;             // the row's first element inside the key's stream
-    const bool draw = tail_draws<KEEP>(a), draw2 = jp.s != 0.0f;
-    const long long q1 = (kofs + span + 3) >> 2;
-    for (long long q = (kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x; q < q1; q += (long long)gridDim.x * 256) {
-        const long long e0 = (q << 2) - kofs;               // lane 0's index inside the row: -3 .. span - 1
-        const int jlo = e0 < 0 ? (int)-e0 : 0;
-        const int jhi = span - e0 < 4 ? (int)(span - e0) : 4;
-        const long long i0 = base + e0;                     // ... inside the launch's tensors (lanes below jlo are not touched)
-        float z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f};
-        if (NOISE) {
-            if (draw) quad_load(a.nz + gofs + i0, jlo, jhi, z);
-            if (draw2) quad_load(jp.nz + gofs + i0, jlo, jhi, z2);
-        } else {
-            if (draw) philox_normal4(key, a.step, (unsigned long long)q, z);
-            if (draw2) philox_normal4(key, a.step + SINDDM_JUMP_STREAM, (unsigned long long)q, z2);
+    const StreamRow row = stream_row<KEEP>(a, span, chw, hw);
+    const bool draw2 = jp.s != 0.0f;
+    for (long long q = row.q0; q < row.q1; q += (long long)gridDim.x * 256) {
+        StreamQuad s = stream_quad<EDIT, NOISE, KEEP>(a, row, q);
+        float z2[4] = {0.f, 0.f, 0.f, 0.f};
+        if (draw2) {
+            if (NOISE) quad_load(jp.nz + row.gofs + s.i0, s.jlo, s.jhi, z2);
+            else philox_normal4(row.key, a.step + SINDDM_JUMP_STREAM, (unsigned long long)q, z2);
         }
-        // (lanes below jlo keep the neutral maps and are not used)
-        const long long iv = i0 + jlo;                      // the first valid lane: >= 0, its sample is iv / chw
-        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, iv, jlo, jhi, chw, hw, w, c);
-        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, jlo, jhi, chw, hw, m, k0);
-        float x[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f};
-        quad_load(xt + i0, jlo, jhi, x);
-        quad_load(eps + i0, jlo, jhi, e);
-        if (a.k.mode != 0) quad_load(xtil + i0, jlo, jhi, xb);
+        stream_quad_load(a, s, xt, eps, xtil);
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = jump_eval<EDIT, KEEP>(a, jp, x[j], e[j], xb[j], z[j], z2[j], w[j], c[j], m[j], k0[j]);
-        if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(out + i0) & 15) == 0) {
-            *reinterpret_cast<f32x4*>(out + i0) = o;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (j >= jlo && j < jhi) out[i0 + j] = o[j];
-        }
+        for (int j = 0; j < 4; ++j)
+            o[j] = jump_eval<EDIT, KEEP>(a, jp, s.x[j], s.e[j], s.xb[j], s.z[j], z2[j], s.w[j], s.c[j], s.m[j], s.k0[j]);
+        quad_store(out + s.i0, s.jlo, s.jhi, o);
     }
 }
 
@@ -359,13 +422,6 @@ struct LayoutArgs {
     int sl;                             // per-sample stride of the layout picture: 0 (shared) or 3 * H * W
     const float* gain;                  // per-sample factor on g of THIS launch's samples (device) or NULL
 };
-
-// `xp` of reverse_step_mean after the ROI edit, NOT clamped (x0 itself in mode 0): what the pull acts on
-__device__ __forceinline__ float step_xp(const sinddm_step_coefs& k, float x, float e, float xb, float w, float c, bool edit) {
-    const float x0 = k.sqrt_recip_ac_t * x - k.sqrt_recipm1_ac_t * e;
-    const float xp = k.mode == 0 ? x0 : (x0 - k.gamma_t * xb) / (1.0f - k.gamma_t);
-    return edit ? w * xp + c : xp;
-}
 
 // `lay` is one picture for the batch or one per sample (g.sl), the edit maps likewise (sew / sec).
 // One workgroup owns block row Y of one (sample, channel) plane over `cols` = (256 / N) * N centre columns, i.e. whole
@@ -449,57 +505,28 @@ __device__ __forceinline__ float layout_pull(const LayoutArgs& g, int b, int r) 
     return gb * ((1.0f - ly) * ((1.0f - lx) * tl + lx * tr) + ly * ((1.0f - lx) * bl + lx * br));
 }
 
-// The conditioned step, over ROWS exactly like reverse_step_jump_kernel (rows of a key's stream, partial first / last quads
-// of a half-batch, per-sample seeds, recorded draws): tail_eval with the edit always on and c_eff in place of ec (w = 1
-// without ROI maps).  An element's sample is its index inside the launch divided by chw: D is this launch's slice.
+// The conditioned step: tail_eval with the edit always on and c_eff in place of ec (w = 1 without ROI maps).  An element's
+// sample is its index inside the launch divided by chw: D is this launch's slice.
 template <bool EDIT, bool NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                   const float* __restrict__ xtil, float* __restrict__ out,
                                                                   TailArgs a, LayoutArgs g, long long span, int chw, int hw) {
-    const long long base = (long long)blockIdx.y * span;
-    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
-    const long long gofs = (long long)a.b0 * chw;           // the launch's first element inside the whole batch
-    const long long kofs = a.sseeds ? 0 : gofs;             // the row's first element inside the key's stream
-    const bool draw = tail_draws<KEEP>(a);
-    const long long q1 = (kofs + span + 3) >> 2;
-    for (long long q = (kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x; q < q1; q += (long long)gridDim.x * 256) {
-        const long long e0 = (q << 2) - kofs;               // lane 0's index inside the row: -3 .. span - 1
-        const int jlo = e0 < 0 ? (int)-e0 : 0;
-        const int jhi = span - e0 < 4 ? (int)(span - e0) : 4;
-        const long long i0 = base + e0;                     // ... inside the launch's tensors (lanes below jlo are not touched)
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (draw) {
-            if (NOISE) quad_load(a.nz + gofs + i0, jlo, jhi, z);
-            else philox_normal4(key, a.step, (unsigned long long)q, z);
-        }
-        const long long iv = i0 + jlo;                      // the first valid lane: >= 0, its sample is iv / chw
-        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, iv, jlo, jhi, chw, hw, w, c);
-        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, jlo, jhi, chw, hw, m, k0);
-        // the first valid lane's sample and index inside it; the lanes behind it may run over the sample's end
-        int b = (int)(iv / chw), r = (int)(iv - (long long)b * chw);
+    const StreamRow row = stream_row<KEEP>(a, span, chw, hw);
+    for (long long q = row.q0; q < row.q1; q += (long long)gridDim.x * 256) {
+        StreamQuad s = stream_quad<EDIT, NOISE, KEEP>(a, row, q);
+        int b = s.b, r = s.r;                               // the lanes behind the first valid one may run over the sample's end
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (j >= jlo && j < jhi) {
-                c[j] += layout_pull(g, b, r);
+            if (j >= s.jlo && j < s.jhi) {
+                s.c[j] += layout_pull(g, b, r);
                 if (++r == chw) { r = 0; ++b; }
             }
         }
-        float x[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f};
-        quad_load(xt + i0, jlo, jhi, x);
-        quad_load(eps + i0, jlo, jhi, e);
-        if (a.k.mode != 0) quad_load(xtil + i0, jlo, jhi, xb);
+        stream_quad_load(a, s, xt, eps, xtil);
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = tail_eval<true, KEEP>(a, x[j], e[j], xb[j], z[j], w[j], c[j], m[j], k0[j]);
-        if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(out + i0) & 15) == 0) {
-            *reinterpret_cast<f32x4*>(out + i0) = o;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (j >= jlo && j < jhi) out[i0 + j] = o[j];
-        }
+        for (int j = 0; j < 4; ++j) o[j] = tail_eval<true, KEEP>(a, s.x[j], s.e[j], s.xb[j], s.z[j], s.w[j], s.c[j], s.m[j], s.k0[j]);
+        quad_store(out + s.i0, s.jlo, s.jhi, o);
     }
 }
 
@@ -513,73 +540,28 @@ __global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* _
 // through untouched: the plain step -- to rounding: with the history's estimate beside it the compiler contracts the four
 // unrolled lanes into other fused multiply-adds than reverse_step_kernel's element loop (1.2e-7 apart on the MI355X,
 // profiles/NOTES_r21.md), so the single-step entry, whose q == 0 form is pinned bit for bit, runs that kernel itself then.
-// `hist` is read and written in place by the thread that owns the element, so it is the one pointer here without
-// __restrict__.
-
-// lanes [jlo, jhi) of the quad at p: one 16-byte store when the quad is full and p is 16-byte aligned, else lane by lane
-__device__ __forceinline__ void quad_store(float* p, int jlo, int jhi, const f32x4& v) {
-    if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-        *reinterpret_cast<f32x4*>(p) = v;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j >= jlo && j < jhi) p[j] = v[j];
-    }
-}
-
-// Over ROWS exactly like reverse_step_jump_kernel (rows of a key's stream, partial first / last quads of a half-batch,
-// per-sample seeds, recorded draws, per-sample map strides); `hist` has the launch's extent, like `out`.
+// `hist` has the launch's extent, like `out`; it is read and written in place by the thread that owns the element, so it
+// is the one pointer here without __restrict__.
 template <bool EDIT, bool NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_ms_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                               const float* __restrict__ xtil, float* __restrict__ out,
                                                               TailArgs a, float q, float* hist, long long span, int chw,
                                                               int hw) {
-    const long long base = (long long)blockIdx.y * span;
-    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
-    const long long gofs = (long long)a.b0 * chw;           // the launch's first element inside the whole batch
-    const long long kofs = a.sseeds ? 0 : gofs;             // the row's first element inside the key's stream
-    const bool draw = tail_draws<KEEP>(a);
-    const long long q1 = (kofs + span + 3) >> 2;
-    for (long long qd = (kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x; qd < q1; qd += (long long)gridDim.x * 256) {
-        const long long e0 = (qd << 2) - kofs;              // lane 0's index inside the row: -3 .. span - 1
-        const int jlo = e0 < 0 ? (int)-e0 : 0;
-        const int jhi = span - e0 < 4 ? (int)(span - e0) : 4;
-        const long long i0 = base + e0;                     // ... inside the launch's tensors (lanes below jlo are not touched)
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (draw) {
-            if (NOISE) quad_load(a.nz + gofs + i0, jlo, jhi, z);
-            else philox_normal4(key, a.step, (unsigned long long)qd, z);
-        }
-        const long long iv = i0 + jlo;                      // the first valid lane: >= 0, its sample is iv / chw
-        float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-        if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, iv, jlo, jhi, chw, hw, w, c);
-        float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, jlo, jhi, chw, hw, m, k0);
-        float x[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f};
-        quad_load(xt + i0, jlo, jhi, x);
-        quad_load(eps + i0, jlo, jhi, e);
-        if (a.k.mode != 0) quad_load(xtil + i0, jlo, jhi, xb);
-        float p[4] = {0.f, 0.f, 0.f, 0.f};
-        if (q != 0.0f) {                                    // (the previous step's estimate; not `quad_load`: no __restrict__)
-            float* hp = hist + i0;
-            if (jlo == 0 && jhi == 4 && (reinterpret_cast<uintptr_t>(hp) & 15) == 0) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(hp);
-                p[0] = t[0]; p[1] = t[1]; p[2] = t[2]; p[3] = t[3];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j >= jlo && j < jhi) p[j] = hp[j];
-            }
-        }
+    const StreamRow row = stream_row<KEEP>(a, span, chw, hw);
+    for (long long qd = row.q0; qd < row.q1; qd += (long long)gridDim.x * 256) {
+        StreamQuad s = stream_quad<EDIT, NOISE, KEEP>(a, row, qd);
+        stream_quad_load(a, s, xt, eps, xtil);
+        float p[4] = {0.f, 0.f, 0.f, 0.f};                  // the previous step's estimate
+        if (q != 0.0f) quad_load(hist + s.i0, s.jlo, s.jhi, p);
         f32x4 o, h;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            h[j] = step_xp(a.k, x[j], e[j], xb[j], 1.0f, 0.0f, false);
-            const float e2 = q != 0.0f ? e[j] - q * (h[j] - p[j]) : e[j];
-            o[j] = tail_eval<EDIT, KEEP>(a, x[j], e2, xb[j], z[j], w[j], c[j], m[j], k0[j]);
+            h[j] = step_xp(a.k, s.x[j], s.e[j], s.xb[j], 1.0f, 0.0f, false);
+            const float e2 = q != 0.0f ? s.e[j] - q * (h[j] - p[j]) : s.e[j];
+            o[j] = tail_eval<EDIT, KEEP>(a, s.x[j], e2, s.xb[j], s.z[j], s.w[j], s.c[j], s.m[j], s.k0[j]);
         }
-        quad_store(hist + i0, jlo, jhi, h);
-        quad_store(out + i0, jlo, jhi, o);
+        quad_store(hist + s.i0, s.jlo, s.jhi, h);
+        quad_store(out + s.i0, s.jlo, s.jhi, o);
     }
 }
 

@@ -8,7 +8,8 @@ project's own step-by-step route, bit-level identities and the order of accuracy
   1. sinddm_reverse_step_ms against the float64 restatement (modes 0 / 1, keep and edit off / on, 5x7 and 8x12: 3 H W % 4
      == 1 and == 0, B = 2 so that a quad crosses a sample's end); `hist`; q = 0 is the plain step bit for bit;
   2. the chain equals the same schedule driven step by step, on the five shapes of test_gpu_keep.CASES (one per tail kernel /
-     row layout, two streams, tiled) and the 18-sample run whose second half starts inside a quad;
+     row layout, two streams, tiled) and the 18-sample run whose second half starts inside a quad; on the same shapes, maps
+     with a slice per sample equal the shared-map run sample by sample, bit for bit;
   3. identities, bit for bit: Philox == buffers (unseeded, seeded), a run repeats, two streams == one, options at their
      defaults == options unset, so = NULL == sinddm_sample_chain_batch;
   4. the seeds contract through a multistep chain;
@@ -61,9 +62,10 @@ def _seeded_draws(c, x0, seeds, n_steps, sid0):
 
 
 def _chain_solver(c, x0, taus, lands, order=2, seed=0, sid0=0, aux=False, edit=None, keep=None, noise=None, seeds=None,
-                  entry="solver", so="block", hist=None, q=None, expect_rc=0):
+                  entry="solver", so="block", hist=None, q=None, expect_rc=0, per_sample=False):
     """sinddm_sample_chain_solver (or _batch) on centre-size arguments of a test_gpu_keep._Ctx, extended here; the extended
-    result.  so: "block" (q of `order`: all zeros for order 1), "null" (so = NULL) or "no_q" (a block whose q is NULL)."""
+    result.  so: "block" (q of `order`: all zeros for order 1), "null" (so = NULL) or "no_q" (a block whose q is NULL).
+    per_sample: the edit and keep maps have a leading batch dimension, one slice per sample (sinddm_batch_opts)."""
     from sinddm_amd import _lib
     from sinddm_amd.models import _aux_stream, _workspace
     lib = _lib.load()
@@ -92,7 +94,8 @@ def _chain_solver(c, x0, taus, lands, order=2, seed=0, sid0=0, aux=False, edit=N
     args = [_lib.ptr(c.net.flat_params), _lib.ptr(c.net.packed_weights()), _lib.ptr(xa), _lib.ptr(xb), _lib.ptr(eps), _lib.ptr(xt),
             coefs, tl, n, float(c.s), seed, sid0, c.dim, B, H, We - 2 * c.hx, ws.data_ptr(), ws.numel(), _lib.stream_ptr(DEV),
             _aux_stream(DEV) if aux else None, C.byref(flag), C.byref(opts), 0, c.hx,
-            C.byref(kopts) if kopts is not None else None, _lib.ptr(sd), None, None, None]
+            C.byref(kopts) if kopts is not None else None, _lib.ptr(sd), None, None,
+            C.byref(_lib.BatchOpts(int(edit is not None), int(keep is not None), int(keep is not None), 0, None)) if per_sample else None]
     if entry == "batch":
         rc = lib.sinddm_sample_chain_batch(*args)
     else:
@@ -211,13 +214,27 @@ def test_reverse_step_ms_against_float64(s, prev, t, u, H, W):
 
 
 # ---- 2: chain equals stepwise ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("variant", ["plain", "maps", "recorded"])
+@pytest.mark.parametrize("variant", ["plain", "maps", "recorded", "per_sample_maps"])
 @pytest.mark.parametrize("cfg,dim,s,B,aux,T,hx", MS_CASES + [MS_UNALIGNED], ids=CASE_IDS + ["pitch_67x90_B18_unaligned_half"])
 def test_multistep_chain_equals_stepwise(cfg, dim, s, B, aux, T, hx, variant):
     c = _ctx(cfg, dim, s, B, hx)
     seed = 818181 + s
     taus, lands = _sched(T)
     assert c.d.step_coefs_to(taus[-1], -1, s).mode == (0 if s == 0 else 2)
+    if variant == "per_sample_maps":
+        # Maps with a slice per sample: where 3 H W % 4 != 0 (67x90, 133x177) a quad of the unseeded launch runs over a sample's
+        # end into the next sample's slices.  The stride is address arithmetic only, so the yardstick is the shared-map run
+        # of the lines below: sample b of the run on row b's maps, bit for bit (first, second and last sample).
+        from test_gpu_batch_maps import _maps
+        mp = _maps(c, B)
+        y = _chain_solver(c, c.x0, taus, lands, seed=seed, aux=aux, edit=(mp["ew"], mp["ec"]), keep=(mp["m"], mp["k0"]), per_sample=True)
+        assert torch.isfinite(y).all()
+        for b in sorted({0, 1, B - 1}):
+            row = {k: v[b].clone() for k, v in mp.items()}                  # (a tensor of its own: the entry wants 16-byte aligned maps)
+            yb = _chain_solver(c, c.x0, taus, lands, seed=seed, aux=aux, edit=(row["ew"], row["ec"]), keep=(row["m"], row["k0"]))
+            assert torch.equal(y[b], yb[b]), b
+            assert not torch.equal(y[(b + 1) % B], yb[(b + 1) % B])         # (the rows differ, and it shows)
+        return
     maps = variant == "maps"
     kw = dict(edit=(c.ew, c.ec), keep=(c.m, c.k0)) if maps else {}
     nz = torch.stack([_draw(c, c.x0, seed, i) for i in range(len(taus))]).contiguous()
