@@ -90,6 +90,24 @@ int sinddm_debug_block_train(const float* params, const float* packed, const flo
 int sinddm_debug_wgrad_map(int Cin, int Cout, int64_t ntiles, int ncu, uint32_t* wg_out, int wg_cap, int32_t* splits_out,
                            int splits_cap);
 
+/* Which kernel a weight-gradient launch takes (enum WgradKernel of the library; the rule is wgrad_plan):
+ * 0 = the generic K-split kernel (wgrad_mfma_kernel, C_out % 80 != 0), 1 = the 80x80-slab 1x1 kernel, 2 = the 80x80-slab
+ * direct 3x3 kernel (C_in < 16, or a launch table that does not fit), 3 = Winograd domain with dword DMA (wgrad_wino_kernel),
+ * 4 = Winograd domain, wide form (W % 4 == 0), 5 = Winograd domain on the binary16 matrix pipe (wgrad_wh_kernel).
+ * The depthwise weight gradient, a separate choice: 6 = tile kernel, 7 = rows kernel (W % 4 == 0, W >= 192). */
+#define SINDDM_DWGRAD_TILES 6
+#define SINDDM_DWGRAD_ROWS 7
+/* Host-only (no device call): ONE weight-gradient launch of taps (9 or 1) x Cin -> Cout over B x H x W on `ncu` compute
+ * units (<= 0: the current device's, 256 where none answers); have_scr: the caller has a staging slab, have_amax: the running
+ * maxima of both operands exist.  out = { kernel, workgroups, S = pixel splits per slab (0 where the Winograd launch table
+ * splits per slab), 1 if the kernel adds into the staging slab }.  Returns 0 or a negative SINDDM_E_*. */
+int sinddm_debug_wgrad_plan(int taps, int Cin, int Cout, int B, int H, int W, int have_scr, int have_amax, int ncu, int out[4]);
+/* Host-only: the same four numbers for the 17 weight-gradient launches of sinddm_net_backward of this shape, in launch
+ * order -- the final 1x1, then for block 3, 2, 1, 0: conv2, the residual 1x1 (all four -1 under an identity residual),
+ * conv1, depthwise (workgroups = C_in * B) -- into out[4 * launch + 0..3]; cap (ints in out) >= 68.  `ncu` sizes the
+ * weight-gradient grids only: the data-gradient routes behind the binary16 choice ask the device as sinddm_debug_routes does. */
+int sinddm_debug_wgrad_routes(int dim_arg, int B, int H, int W, int ncu, int* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,15 +39,6 @@ namespace sinddm {
 #ifndef SINDDM_WGRAD_WIDE     // 1: W % 4 == 0 launches of the Winograd weight gradient on wgrad_wino_wide_kernel (16-byte DMA)
 #define SINDDM_WGRAD_WIDE 1
 #endif
-#ifndef SINDDM_WGRAD_W3       // 1: 80x80-slab direct 3x3 weight gradient where the Winograd one does not apply
-#define SINDDM_WGRAD_W3 1
-#endif
-#ifndef SINDDM_WGRAD_W1       // 1: 80x80-slab 1x1 weight gradient
-#define SINDDM_WGRAD_W1 1
-#endif
-#ifndef SINDDM_WGRAD_STAGE    // 1: coalesced [co][tap][ci] staging slab for the 3x3 weight-gradient atomics
-#define SINDDM_WGRAD_STAGE 1
-#endif
 #ifndef SINDDM_WGRAD_ABL      // timing ablation bits of the weight-gradient kernels (results WRONG when != 0)
 #define SINDDM_WGRAD_ABL 0
 #endif

@@ -7,7 +7,7 @@
 #include "conv_args.h"
 #include "conv1x1.h"
 #include "internal.h"
-#include "wgrad_wino.h"
+#include "wgrad_plan.h"
 #include "wgrad_wh.h"
 
 namespace sinddm {
@@ -18,21 +18,13 @@ namespace sinddm {
 // GEMM view: M = co (16-row tiles), N = ci (one 16-col tile per tap), K = pixels (4 per MFMA).
 // A workgroup owns one (co-block of MT*16, ci-block of 16) slab of the gradient and walks a strided
 // subset of the 2x32 pixel tiles; its 4 waves split the tile's 16 k-steps (K split), each holding all
-// MT x TAPS accumulator tiles (180 registers at MT=5, TAPS=9) across the whole walk.  Both operand
+// MT x TAPS accumulator tiles (MT = 2 or 1: C_out % 80 == 0 takes the slab kernels) across the whole walk.  Both operand
 // tiles are fetched with LDS DMA (global_load_lds: one wave instruction per dout channel row / per
 // input (channel,row); out-of-image and missing-channel rows come from a page of zeros) into a
 // double-buffered LDS image, ONE barrier per tile.  At the end the 4 partial slabs are combined in
 // LDS and added to the global gradient with one atomic per element.
 // LDS strides == 2 (mod 32) make both operand reads (lane -> channel*stride + pixel) conflict-free.
 // =====================================================================================
-constexpr int WG_THREADS = 256;
-constexpr int WG_TH = 2, WG_TW = 32;
-constexpr int WG_CI = 16;
-constexpr int WG_PSO = WG_TH * WG_TW + 2;              // 66
-constexpr int WG_IRS = WG_TW + 2;                      // 34
-constexpr int WG_IHR = WG_TH + 2;                      // 4
-constexpr int WG_PSI = ((WG_IHR * WG_IRS - 2 + 31) / 32) * 32 + 2;   // 162
-
 struct WgradArgs {
     const float* dout;   // [B][Cout][H][W]
     const float* in;     // [B][Cin][H][W]
@@ -193,11 +185,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_mfma_kernel(WgradArgs p) 
 // cross-wave reduction is needed and a 64-pixel tile (73 KB of LDS) feeds 3600 MFMAs: 2.4x fewer L2->LDS bytes
 // per FLOP than the K-split kernel above, whose DMA latency cost 38% of its time (ablation in DESIGN.md).
 // -------------------------------------------------------------------------------------
-constexpr int W3_WAVES = 16;                              // 15 compute waves + 1 that only moves data (4 waves per SIMD)
-constexpr int W3_THREADS = W3_WAVES * 64;
-constexpr int W3_C = 80;                                  // co and ci per workgroup
-constexpr int W3_BUF = W3_C * WG_PSO + W3_C * WG_PSI;     // floats per stage
-
 __global__ __launch_bounds__(W3_THREADS) void wgrad3x3_kernel(WgradArgs p) {
     typedef __attribute__((address_space(3))) void* lds_ptr;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -378,11 +365,6 @@ __global__ __launch_bounds__(W3_THREADS) void wgrad3x3_kernel(WgradArgs p) {
 // tile, wave 15 only moves data and sums dout for the bias.  Pixels are flattened (no halo): a tile is 64 consecutive
 // pixels of one image, one whole-wave DMA instruction per channel.
 // -------------------------------------------------------------------------------------
-constexpr int W1_C = 80;
-constexpr int W1_PIX = 64;
-constexpr int W1_PS = W1_PIX + 2;                          // plane stride == 2 (mod 32)
-constexpr int W1_BUF = 2 * W1_C * W1_PS;                   // dout planes + input planes per stage (10560 floats)
-
 __global__ __launch_bounds__(1024) void wgrad1x1_kernel(WgradArgs p) {
     typedef __attribute__((address_space(3))) void* lds_ptr;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -496,146 +478,38 @@ __global__ void wgrad_unstage_kernel(const float* __restrict__ scr, float* __res
     gw[i] += scr[((size_t)co * 9 + t) * Cin + ci];
 }
 
-template <int MT, int TAPS>
-static void wgrad_launch_t(const WgradArgs& a, unsigned grid, hipStream_t st) {
-    constexpr size_t lds = (size_t)2 * (MT * 16 * WG_PSO + WG_CI * WG_PSI) * sizeof(float);
-    hipLaunchKernelGGL((wgrad_mfma_kernel<MT, TAPS>), dim3(grid), dim3(WG_THREADS), lds, st, a);
-}
-
-// amax_d / amax_i: the per-sample running maxima of dout / in when their producers maintain them (training on the binary16
-// kernels): the Winograd-domain weight gradient then runs on the binary16 matrix pipe too (wgrad_wh.h)
-static int wgrad_launch(const float* zero, const float* dout, const float* in, float* gw, float* gb, int B, int H, int W,
-                        int Cin, int Cout, int taps, hipStream_t st, float* scr = nullptr, const float* amax_d = nullptr,
-                        const float* amax_i = nullptr) {
-    WgradArgs a{};
-    a.zero = zero;
-    a.dout = dout; a.in = in; a.gw = gw; a.gb = gb;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    constexpr int abl = SINDDM_WGRAD_ABL;
-    constexpr int w3 = SINDDM_WGRAD_W3;
-    a.abl = abl;
-    a.tilesX = (W + WG_TW - 1) / WG_TW;
-    a.tilesY = (H + WG_TH - 1) / WG_TH;
-    a.ntiles = B * a.tilesX * a.tilesY;
-    constexpr int ww = SINDDM_WGRAD_WINO;
-    WwArgs w{};
-    int nwg = 0;
-    if (taps == 9 && Cout % WW_CO == 0 && Cin >= 16 && ww && scr) {
-        w.dout = dout; w.in = in; w.gw = scr; w.gb = gb;
-        w.B = B; w.H = H; w.W = W; w.Cin = Cin; w.Cout = Cout;
-        w.coblks = Cout / WW_CO;
-        w.ciblks = (Cin + WW_CI - 1) / WW_CI;
-        w.tilesX = (W + WW_TW - 1) / WW_TW;
-        w.tilesY = (H + WW_TH - 1) / WW_TH;
-        w.ntiles = B * w.tilesX * w.tilesY;
-        nwg = ww_build_map(w, cu_count());      // 0: more slabs than the launch table holds -> the direct kernels below
-    }
-    if (nwg > 0) {
-        // Winograd-domain weight gradient (2.25x fewer MFMAs); always through the [co][tap][ci] staging slab
-        if ((size_t)WW_CO * H * W * 4 >= 0x40000000ull) return SINDDM_E_BADSHAPE;
-        const int n = Cout * Cin * 9;
+// One weight-gradient launch as `p` (wgrad_plan.h) describes it: fills the kernel's arguments and launches, decides nothing.
+// scr: the staging slab the plan was told about; amax_d / amax_i: the per-sample running maxima of dout / in (WGRAD_WH only)
+static int wgrad_launch(const WgradPlan& p, const float* zero, const float* dout, const float* in, float* gw, float* gb,
+                        hipStream_t st, float* scr = nullptr, const float* amax_d = nullptr, const float* amax_i = nullptr) {
+    // the 80-channel kernels: the largest per-sample channel slab must stay below the buffer OOB marker
+    if (p.kernel != WGRAD_GENERIC && (size_t)80 * p.H * p.W * 4 >= 0x40000000ull) return SINDDM_E_BADSHAPE;
+    const int n = p.Cout * p.Cin * 9;
+    if (p.staged) {
         hipError_t e = hipMemsetAsync(scr, 0, (size_t)n * sizeof(float), st);
         if (e != hipSuccess) return (int)e;
-        // rows of 16-byte groups (W % 4 == 0): the variant with 16-byte DMA and ds_read_b64 operands
-        const bool wide = SINDDM_WGRAD_WIDE && W % 4 == 0;
-        const bool h16 = SINDDM_WGRAD_WH && wide && amax_d && amax_i && wh_enabled();
-        w.amax_d = amax_d; w.amax_i = amax_i;
-        const size_t lds = (size_t)WW_STAGES * (wide ? WX_BUF : WW_BUF) * sizeof(float);
-        // (more than 64 KB of dynamic LDS needs the per-function opt-in: once per kernel and process, its result checked)
-        static const hipError_t attr_wide = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_wino_wide_kernel),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)WW_STAGES * WX_BUF * sizeof(float)));
-        static const hipError_t attr_dword = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_wino_kernel),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)WW_STAGES * WW_BUF * sizeof(float)));
-        static const hipError_t attr_h16 = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_wh_kernel),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)WW_STAGES * WX_BUF * sizeof(float)));
-        if ((wide ? attr_wide : attr_dword) != hipSuccess) return (int)(wide ? attr_wide : attr_dword);
-        if (h16 && attr_h16 != hipSuccess) return (int)attr_h16;
-        ConvProfiler& prof = conv_profiler();
-        const bool rec = prof.begin(st);
-        if (h16) hipLaunchKernelGGL(wgrad_wh_kernel, dim3((unsigned)nwg), dim3(WW_THREADS), lds, st, w);
-        else if (wide) hipLaunchKernelGGL(wgrad_wino_wide_kernel, dim3((unsigned)nwg), dim3(WW_THREADS), lds, st, w);
-        else hipLaunchKernelGGL(wgrad_wino_kernel, dim3((unsigned)nwg), dim3(WW_THREADS), lds, st, w);
-        SINDDM_LAUNCH_CHECK();
-        if (rec) {
-            const double fl = 2.0 * B * H * W * (double)Cout * Cin * 9.0;
-            // kind 4 = Winograd-domain weight gradient, F(2x2): 16/36 executed; generation 8 = binary16 pieces, four terms
-            if (h16) prof.end(st, 4, fl, fl * 16.0 / 36.0 * 4.0, 8);
-            else prof.end(st, 4, fl, fl * 16.0 / 36.0);
-        }
-        hipLaunchKernelGGL(wgrad_unstage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scr, gw, Cin, n);
-        SINDDM_LAUNCH_CHECK();
-        return 0;
     }
-    constexpr int w1 = SINDDM_WGRAD_W1;
-    if (taps == 1 && Cout % W1_C == 0 && w1) {
-        if ((size_t)W1_C * H * W * 4 >= 0x40000000ull) return SINDDM_E_BADSHAPE;
-        a.coblks = Cout / W1_C;
-        a.ciblks = (Cin + W1_C - 1) / W1_C;
-        a.tilesX = (H * W + W1_PIX - 1) / W1_PIX;      // flat tiles per image
-        a.tilesY = 1;
-        a.ntiles = B * a.tilesX;
-        const int pairs = a.coblks * a.ciblks;
-        int S = (cu_count() / pairs) / 8 * 8;
-        if (S < 8) S = 8;
-        const int cap = (a.ntiles + 7) / 8 * 8;
-        if (S > cap) S = cap;
-        a.S = S;
-        constexpr size_t lds = (size_t)2 * W1_BUF * sizeof(float);
-        hipLaunchKernelGGL(wgrad1x1_kernel, dim3((unsigned)(pairs * S)), dim3(1024), lds, st, a);
-        SINDDM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (taps == 9 && Cout % W3_C == 0 && w3) {
-        // one workgroup per CU; the largest per-sample channel slab must stay below the buffer OOB marker
-        if ((size_t)W3_C * H * W * 4 >= 0x40000000ull) return SINDDM_E_BADSHAPE;
-        a.coblks = Cout / W3_C;
-        a.ciblks = (Cin + W3_C - 1) / W3_C;
-        const int pairs = a.coblks * a.ciblks;
-        int S = (cu_count() / pairs) / 8 * 8;
-        if (S < 8) S = 8;
-        const int cap = (a.ntiles + 7) / 8 * 8;
-        if (S > cap) S = cap;
-        a.S = S;
-        constexpr size_t lds = (size_t)2 * W3_BUF * sizeof(float);
-        constexpr int stage = SINDDM_WGRAD_STAGE;
-        const int n = Cout * Cin * 9;
-        if (scr && stage) {
-            hipError_t e = hipMemsetAsync(scr, 0, (size_t)n * sizeof(float), st);
-            if (e != hipSuccess) return (int)e;
-            a.gw = scr;
-            a.scr = 1;
-        }
-        hipLaunchKernelGGL(wgrad3x3_kernel, dim3((unsigned)(pairs * S)), dim3(W3_THREADS), lds, st, a);
-        SINDDM_LAUNCH_CHECK();
-        if (a.scr) {
-            hipLaunchKernelGGL(wgrad_unstage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scr, gw, Cin, n);
-            SINDDM_LAUNCH_CHECK();
-        }
-        return 0;
-    }
-    const int mt = mt_for(Cout);
-    a.coblks = (Cout + mt * 16 - 1) / (mt * 16);
-    a.ciblks = (Cin + WG_CI - 1) / WG_CI;
-    a.tilesX = (W + WG_TW - 1) / WG_TW;
-    a.tilesY = (H + WG_TH - 1) / WG_TH;
-    a.ntiles = B * a.tilesX * a.tilesY;
-    const int pairs = a.coblks * a.ciblks;
-    int S = (1024 / pairs) / 8 * 8;
-    if (S < 8) S = 8;
-    const int cap = (a.ntiles + 7) / 8 * 8;
-    if (S > cap) S = cap;
-    a.S = S;
-    const unsigned grid = (unsigned)(pairs * S);
-    if (taps == 9) {
-        if (mt == 5) wgrad_launch_t<5, 9>(a, grid, st);
-        else if (mt == 2) wgrad_launch_t<2, 9>(a, grid, st);
-        else wgrad_launch_t<1, 9>(a, grid, st);
+    if (p.kernel >= WGRAD_WINO) {
+        const int rc = ww_launch(p, dout, in, scr, gb, amax_d, amax_i, st);
+        if (rc) return rc;
     } else {
-        if (mt == 5) wgrad_launch_t<5, 1>(a, grid, st);
-        else if (mt == 2) wgrad_launch_t<2, 1>(a, grid, st);
-        else wgrad_launch_t<1, 1>(a, grid, st);
+        WgradArgs a{};
+        a.zero = zero; a.dout = dout; a.in = in; a.gw = p.staged ? scr : gw; a.gb = gb;
+        a.B = p.B; a.H = p.H; a.W = p.W; a.Cin = p.Cin; a.Cout = p.Cout;
+        a.coblks = p.coblks; a.ciblks = p.ciblks; a.S = p.S;
+        a.tilesX = p.tilesX; a.tilesY = p.tilesY; a.ntiles = p.ntiles;
+        a.abl = SINDDM_WGRAD_ABL; a.scr = p.staged;
+        const bool m2 = mt_for(p.Cout) == 2;
+        void (*const kernel)(WgradArgs) = p.kernel == WGRAD_SLAB1 ? wgrad1x1_kernel : p.kernel == WGRAD_SLAB3 ? wgrad3x3_kernel
+            : p.taps == 9 ? (m2 ? wgrad_mfma_kernel<2, 9> : wgrad_mfma_kernel<1, 9>)
+                          : (m2 ? wgrad_mfma_kernel<2, 1> : wgrad_mfma_kernel<1, 1>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.nwg), dim3(p.kernel == WGRAD_GENERIC ? WG_THREADS : W3_THREADS), p.lds, st, a);
+        SINDDM_LAUNCH_CHECK();
     }
-    SINDDM_LAUNCH_CHECK();
+    if (p.staged) {
+        hipLaunchKernelGGL(wgrad_unstage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scr, gw, p.Cin, n);
+        SINDDM_LAUNCH_CHECK();
+    }
     return 0;
 }
 
@@ -1134,11 +1008,31 @@ static int conv1x1_dgrad(const float* zero, const float* in1, int cin1, const fl
     return conv1x1_launch(c, mt, st);
 }
 
-// the routes of block l's two 3x3 data gradients: out[0] = conv2's, out[1] = conv1's (which may take conv_wh only behind a
-// conv2 gradient that did: its epilogue publishes the running max of dU)
-static void backward_routes(const NetPlan& P, const BwdPack& k, int l, int B, int H, int W, bool have_amax, int out[2]) {
-    out[0] = conv3x3_route(P, k.dg2[l], B, H, W, have_amax, false);
-    out[1] = conv3x3_route(P, k.dg1[l], B, H, W, out[0] == CONV_WH, false);
+// Everything block l's backward decides: block_backward, sinddm_debug_routes and sinddm_debug_wgrad_routes read this.  Running
+// maxima per sample: backward slot 2l = max |dO|, 2l + 1 = max |dU|; forward slot 2l = max |h| (conv1's input), 2l + 1 = max |g|.
+struct BlockBackward {
+    ConvKernel dg2, dg1;   // the 3x3 data gradients of conv2 / conv1
+    bool wh2;              // dg2 on conv_wh: it and conv2's weight gradient read backward slot 2l (+ forward 2l + 1)
+    bool wh1;              // dg1 on conv_wh, only behind a dg2 that is: dg2's epilogue publishes backward slot 2l + 1
+    bool wha;              // ... and the forward conv1 was too (forward slot 2l exists): conv1's weight gradient reads both
+    bool pub;              // the depthwise data gradient publishes backward slot 2(l - 1): block l - 1's dg2 will read it
+    WgradPlan w2, wres, w1;   // weight gradients of conv2, the residual 1x1 (wres.nwg == 0: identity residual) and conv1
+    bool dw_rows;          // depthwise weight gradient on the register-window rows kernel (wide aligned images), else tiles
+};
+static BlockBackward block_backward_plan(const NetPlan& P, const BwdPack& k, int l, int B, int H, int W, bool have_amax, int ncu) {
+    const BlockPlan& b = P.blk[l];
+    BlockBackward d{};
+    d.dg2 = conv3x3_route(P, k.dg2[l], B, H, W, have_amax, false);
+    d.wh2 = d.dg2 == CONV_WH;
+    d.dg1 = conv3x3_route(P, k.dg1[l], B, H, W, d.wh2, false);
+    d.wh1 = d.dg1 == CONV_WH;
+    d.wha = d.wh1 && conv3x3_route(P, b.c1, B, H, W, true, true) == CONV_WH;
+    d.pub = l > 0 && conv3x3_route(P, k.dg2[l - 1], B, H, W, have_amax, false) == CONV_WH;
+    d.w2 = wgrad_plan(9, b.cout, b.cout, B, H, W, true, d.wh2 && wh_enabled(), ncu);
+    if (b.res_w >= 0) d.wres = wgrad_plan(1, b.cin, b.cout, B, H, W, false, false, ncu);
+    d.w1 = wgrad_plan(9, b.cin, b.cout, B, H, W, true, d.wha && wh_enabled(), ncu);
+    d.dw_rows = SINDDM_DWG_ROWS && W % 4 == 0 && W >= 192;
+    return d;
 }
 
 // Backward of ONE SinDDMConvBlock (autograd of reference SinDDM/models.py:69-80): dO = gradient of the block output (scratch,
@@ -1150,24 +1044,19 @@ static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float
     const BlockPlan& b = P.blk[l];
     const float* zp = packed_bwd + k.zero;
     int rc;
-    // the two 3x3 data-gradient convs on the binary16 hi/lo Winograd kernel (conv_wh.h) where its rule takes the launch;
-    // `amax_b` = the backward half of tb.amax (zeroed by the caller): slot 2l = max |dO| per sample (maintained by the kernel
-    // that wrote dO when `dO_published`), slot 2l + 1 = max |dU| (by the first conv's epilogue)
-    int route[2];
-    backward_routes(P, k, l, B, H, W, amax_b != nullptr, route);
-    const bool wh2 = route[0] == CONV_WH, wh1 = route[1] == CONV_WH;
-    if (wh2 && !dO_published) {
+    // `amax_b` = the backward half of tb.amax (zeroed by the caller); slot 2l comes from the kernel that wrote dO when `dO_published`
+    const BlockBackward d = block_backward_plan(P, k, l, B, H, W, amax_b != nullptr, cu_count());
+    if (d.wh2 && !dO_published) {
         rc = amax_tensor_launch(dO, amax_b + 2 * l, B, (long long)b.cout * H * W, st);
         if (rc) return rc;
     }
     // conv2 + residual projection weight grads
     // (the running maxima of g = conv2's forward input and of h = conv1's are the forward half of tb.amax, slots 2l + 1 / 2l)
-    const bool wha = wh1 && conv3x3_route(P, b.c1, B, H, W, true, true) == CONV_WH;
-    rc = wgrad_launch(zp, dO, tb.g[l], grads + b.c2_w, grads + b.c2_b, B, H, W, b.cout, b.cout, 9, st, tb.wscr,
-                      wh2 ? amax_b + 2 * l : nullptr, wh2 ? tb.amax + 2 * l + 1 : nullptr);
+    rc = wgrad_launch(d.w2, zp, dO, tb.g[l], grads + b.c2_w, grads + b.c2_b, st, tb.wscr, d.wh2 ? amax_b + 2 * l : nullptr,
+                      d.wh2 ? tb.amax + 2 * l + 1 : nullptr);
     if (rc) return rc;
-    if (b.res_w >= 0) {
-        rc = wgrad_launch(zp, dO, xin, grads + b.res_w, grads + b.res_b, B, H, W, b.cin, b.cout, 1, st);
+    if (d.wres.nwg > 0) {
+        rc = wgrad_launch(d.wres, zp, dO, xin, grads + b.res_w, grads + b.res_b, st);
         if (rc) return rc;
     }
     // dU = dgrad_conv2(dO) * GELU'(u)
@@ -1175,29 +1064,25 @@ static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float
         ConvArgs c{};
         c.zero = zp; c.in = dO; c.Cin = b.cout; c.aux = tb.u[l]; c.act = 2; c.out = dU; c.Cout = b.cout;
         c.B = B; c.H = H; c.W = W;
-        if (wh2) { c.amax_in = amax_b + 2 * l; c.amax_out = wh1 ? amax_b + 2 * l + 1 : nullptr; }
-        rc = conv3x3_launch((ConvKernel)route[0], k.dg2[l], packed_bwd, c, st);
+        if (d.wh2) { c.amax_in = amax_b + 2 * l; c.amax_out = d.wh1 ? amax_b + 2 * l + 1 : nullptr; }
+        rc = conv3x3_launch(d.dg2, k.dg2[l], packed_bwd, c, st);
     }
     if (rc) return rc;
     // conv1 weight grads, dH = dgrad_conv1(dU)
-    rc = wgrad_launch(zp, dU, tb.h[l], grads + b.c1_w, grads + b.c1_b, B, H, W, b.cin, b.cout, 9, st, tb.wscr,
-                      wha ? amax_b + 2 * l + 1 : nullptr, wha ? tb.amax + 2 * l : nullptr);
+    rc = wgrad_launch(d.w1, zp, dU, tb.h[l], grads + b.c1_w, grads + b.c1_b, st, tb.wscr, d.wha ? amax_b + 2 * l + 1 : nullptr,
+                      d.wha ? tb.amax + 2 * l : nullptr);
     if (rc) return rc;
     {
         ConvArgs c{};
         c.zero = zp; c.in = dU; c.Cin = b.cout; c.act = 0; c.out = dH; c.Cout = b.cin;
         c.B = B; c.H = H; c.W = W;
-        if (wh1) c.amax_in = amax_b + 2 * l + 1;
-        rc = conv3x3_launch((ConvKernel)route[1], k.dg1[l], packed_bwd, c, st);
+        if (d.wh1) c.amax_in = amax_b + 2 * l + 1;
+        rc = conv3x3_launch(d.dg1, k.dg1[l], packed_bwd, c, st);
     }
     if (rc) return rc;
     // depthwise weight/bias grads and the per-sample condition grads
-    if (SINDDM_DWG_ROWS && W % 4 == 0 && W >= 192)
-        hipLaunchKernelGGL(dwconv5_wgrad_rows_kernel, dim3(b.cin, B), dim3(256), 0, st, dH, xin, grads + b.dw_w,
-                           grads + b.dw_b, tb.dcond + b.cond_off, P.cond_stride, b.cin, H, W);
-    else
-        hipLaunchKernelGGL(dwconv5_wgrad_kernel, dim3(b.cin, B), dim3(256), 0, st, dH, xin, grads + b.dw_w,
-                           grads + b.dw_b, tb.dcond + b.cond_off, P.cond_stride, b.cin, H, W);
+    hipLaunchKernelGGL(d.dw_rows ? dwconv5_wgrad_rows_kernel : dwconv5_wgrad_kernel, dim3(b.cin, B), dim3(256), 0, st, dH, xin,
+                       grads + b.dw_w, grads + b.dw_b, tb.dcond + b.cond_off, P.cond_stride, b.cin, H, W);
     SINDDM_LAUNCH_CHECK();
     // data grad w.r.t. the block input: dw^T(dH) + residual path
     if (dst) {
@@ -1209,9 +1094,8 @@ static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float
             radd = dU;
         }
         // (dst is the next block's dO: its running max comes out of this launch when that block's convs will want it)
-        float* pub = nullptr;
-        if (l > 0 && conv3x3_route(P, k.dg2[l - 1], B, H, W, amax_b != nullptr, false) == CONV_WH) pub = amax_b + 2 * (l - 1);
-        rc = dwconv_launch(dH, params + b.dw_w, nullptr, nullptr, 0, radd, 1, dst, B, b.cin, H, W, st, 0, 0, pub);
+        rc = dwconv_launch(dH, params + b.dw_w, nullptr, nullptr, 0, radd, 1, dst, B, b.cin, H, W, st, 0, 0,
+                           d.pub ? amax_b + 2 * (l - 1) : nullptr);
         if (rc) return rc;
     }
     return 0;
@@ -1224,7 +1108,8 @@ static int net_backward_impl(const NetPlan& P, const float* params, const float*
     const float* zp = packed_bwd + k.zero;
     int rc;
     // ---- final 1x1 conv: weight/bias grads, then data grad into s[0] ----
-    rc = wgrad_launch(zp, grad_out, tb.o[3], grads + P.fin_w, grads + P.fin_b, B, H, W, P.half, CHANNELS, 1, st);
+    rc = wgrad_launch(wgrad_plan(1, P.half, CHANNELS, B, H, W, false, false, cu_count()), zp, grad_out, tb.o[3], grads + P.fin_w,
+                      grads + P.fin_b, st);
     if (rc) return rc;
     int di = 0;   // index of the scratch buffer holding dOut of the current block
     float* amax_b = tb.amax + (size_t)B * AMAX_STRIDE;
@@ -1361,7 +1246,10 @@ int sinddm_debug_routes(int dim_arg, int train, int B, int H, int W, int out[16]
     forward_routes(p, train != 0, B, H, train ? W : forward_pitch(p, W), true, out);
     if (train) {
         const BwdPack k = make_bwd_pack(p);
-        for (int l = 0; l < 4; ++l) backward_routes(p, k, l, B, H, W, true, out + 8 + 2 * l);
+        for (int l = 0; l < 4; ++l) {
+            const BlockBackward d = block_backward_plan(p, k, l, B, H, W, true, cu_count());
+            out[8 + 2 * l] = d.dg2; out[8 + 2 * l + 1] = d.dg1;
+        }
     }
     return 0;
 }
@@ -1415,17 +1303,41 @@ int sinddm_debug_block_train(const float* params, const float* packed, const flo
 int sinddm_debug_wgrad_map(int Cin, int Cout, int64_t ntiles, int ncu, uint32_t* wg_out, int wg_cap, int32_t* splits_out,
                            int splits_cap) {
     if (Cin < 1 || Cout < WW_CO || Cout % WW_CO || ntiles < 1 || !wg_out || !splits_out) return SINDDM_E_BADARG;
-    WwArgs w{};
-    w.Cin = Cin; w.Cout = Cout;
-    w.coblks = Cout / WW_CO;
-    w.ciblks = (Cin + WW_CI - 1) / WW_CI;
-    w.ntiles = (int)(ntiles > 0x7fffffff ? 0x7fffffff : ntiles);
-    const int n = ww_build_map(w, ncu);
+    WwMap map{};
+    const int coblks = Cout / WW_CO, ciblks = (Cin + WW_CI - 1) / WW_CI;
+    const int n = ww_build_map(map, Cin, coblks, ciblks, (int)(ntiles > 0x7fffffff ? 0x7fffffff : ntiles), ncu);
     if (n <= 0) return SINDDM_E_BADSHAPE;
-    if (n > wg_cap || w.coblks * w.ciblks > splits_cap) return SINDDM_E_BADARG;     // caller's buffers are too small
-    for (int i = 0; i < n; ++i) wg_out[i] = w.map.wg[i];
-    for (int q = 0; q < w.coblks * w.ciblks; ++q) splits_out[q] = w.map.S[q];
+    if (n > wg_cap || coblks * ciblks > splits_cap) return SINDDM_E_BADARG;     // caller's buffers are too small
+    for (int i = 0; i < n; ++i) wg_out[i] = map.wg[i];
+    for (int q = 0; q < coblks * ciblks; ++q) splits_out[q] = map.S[q];
     return n;
+}
+
+static void wgrad_report(const WgradPlan& p, int out[4]) { out[0] = p.kernel; out[1] = p.nwg; out[2] = p.S; out[3] = p.staged; }
+
+int sinddm_debug_wgrad_plan(int taps, int Cin, int Cout, int B, int H, int W, int have_scr, int have_amax, int ncu, int out[4]) {
+    if ((taps != 1 && taps != 9) || Cin < 1 || Cout < 1 || B <= 0 || H <= 0 || W <= 0 || !out) return SINDDM_E_BADARG;
+    wgrad_report(wgrad_plan(taps, Cin, Cout, B, H, W, have_scr != 0, have_amax != 0, ncu > 0 ? ncu : cu_count()), out);
+    return 0;
+}
+
+int sinddm_debug_wgrad_routes(int dim_arg, int B, int H, int W, int ncu, int* out, int cap) {
+    NetPlan p = make_plan(dim_arg);
+    if (!p.ok || !out || cap < 4 * 17 || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    if (ncu <= 0) ncu = cu_count();
+    for (int i = 0; i < 4 * 17; ++i) out[i] = -1;
+    wgrad_report(wgrad_plan(1, p.half, CHANNELS, B, H, W, false, false, ncu), out);
+    const BwdPack k = make_bwd_pack(p);
+    for (int l = 3; l >= 0; --l) {
+        const BlockBackward d = block_backward_plan(p, k, l, B, H, W, true, ncu);
+        int* o = out + 4 * (1 + 4 * (3 - l));
+        wgrad_report(d.w2, o);
+        if (d.wres.nwg > 0) wgrad_report(d.wres, o + 4);
+        wgrad_report(d.w1, o + 8);
+        o[12] = d.dw_rows ? SINDDM_DWGRAD_ROWS : SINDDM_DWGRAD_TILES;
+        o[13] = p.blk[l].cin * B; o[14] = 0; o[15] = 0;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -21,7 +21,8 @@
 // pixel splits of a slab run with alternating signs of dM (the sign rides on the scale; the epilogue's factor undoes it), so
 // the bias cancels between the splits that are summed into one gradient.
 #pragma once
-#include "wgrad_wino.h"
+#include "conv_args.h"
+#include "wgrad_plan.h"
 
 namespace sinddm {
 
@@ -273,6 +274,43 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wh_kernel(WwArgs p) {
 #pragma unroll
         for (int nt = 0; nt < 3; ++nt) acc[mt][nt] = (acc[mt][nt] * out_a) * out_v;
     ww_epilogue(p, smem, acc, bsum, dobias, xi, lane, cb, ci0);
+}
+
+// more than 64 KB of dynamic LDS needs the per-function opt-in
+inline hipError_t ww_lds_optin(void (*kernel)(WwArgs), int buf) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)((size_t)WW_STAGES * buf * sizeof(float)));
+}
+
+// One launch of the Winograd-domain kernel plan `p` names (WGRAD_WINO, _WIDE or _WH); scr = the zeroed [co][tap][ci] staging
+// slab, amax_d / amax_i = the per-sample running maxima of dout / in (WGRAD_WH reads them)
+inline int ww_launch(const WgradPlan& p, const float* dout, const float* in, float* scr, float* gb, const float* amax_d,
+                     const float* amax_i, hipStream_t st) {
+    WwArgs w{};
+    w.dout = dout; w.in = in; w.gw = scr; w.gb = gb;
+    w.B = p.B; w.H = p.H; w.W = p.W; w.Cin = p.Cin; w.Cout = p.Cout;
+    w.coblks = p.coblks; w.ciblks = p.ciblks;
+    w.tilesX = p.tilesX; w.tilesY = p.tilesY; w.ntiles = p.ntiles;
+    w.amax_d = amax_d; w.amax_i = amax_i;
+    w.map = p.map;
+    const bool h16 = p.kernel == WGRAD_WH, wide = p.kernel != WGRAD_WINO;
+    // (once per kernel and process, its result checked)
+    static const hipError_t optin[3] = {ww_lds_optin(wgrad_wino_kernel, WW_BUF), ww_lds_optin(wgrad_wino_wide_kernel, WX_BUF),
+                                        ww_lds_optin(wgrad_wh_kernel, WX_BUF)};
+    if (optin[wide] != hipSuccess) return (int)optin[wide];
+    if (h16 && optin[2] != hipSuccess) return (int)optin[2];
+    ConvProfiler& prof = conv_profiler();
+    const bool rec = prof.begin(st);
+    hipLaunchKernelGGL(h16 ? wgrad_wh_kernel : wide ? wgrad_wino_wide_kernel : wgrad_wino_kernel, dim3((unsigned)p.nwg),
+                       dim3(WW_THREADS), p.lds, st, w);
+    SINDDM_LAUNCH_CHECK();
+    if (rec) {
+        const double fl = 2.0 * p.B * p.H * p.W * (double)p.Cout * p.Cin * 9.0;
+        // kind 4 = Winograd-domain weight gradient, F(2x2): 16/36 executed; generation 8 = binary16 pieces, four terms
+        if (h16) prof.end(st, 4, fl, fl * 16.0 / 36.0 * 4.0, 8);
+        else prof.end(st, 4, fl, fl * 16.0 / 36.0);
+    }
+    return 0;
 }
 
 }  // namespace sinddm

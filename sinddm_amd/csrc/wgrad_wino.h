@@ -72,18 +72,18 @@ struct WwArgs {
 
 // returns the number of workgroups, or 0 when the table cannot describe the launch (more slabs than it holds: the caller
 // then takes the direct weight-gradient kernels -- a slower path, not an error)
-inline int ww_build_map(WwArgs& w, int ncu) {
-    const int slabs = w.coblks * w.ciblks;
+inline int ww_build_map(WwMap& map, int Cin, int coblks, int ciblks, int ntiles, int ncu) {
+    const int slabs = coblks * ciblks;
     if (slabs > WW_MAXSLAB || ncu < 1) return 0;
     if (ncu > WW_MAXWG) ncu = WW_MAXWG;
     int nt[WW_MAXSLAB], S[WW_MAXSLAB], units = 0;
     for (int q = 0; q < slabs; ++q) {
-        const int cib = q % w.ciblks;
-        const int nci = w.Cin - cib * WW_CI < WW_CI ? w.Cin - cib * WW_CI : WW_CI;
+        const int cib = q % ciblks;
+        const int nci = Cin - cib * WW_CI < WW_CI ? Cin - cib * WW_CI : WW_CI;
         nt[q] = ((nci + 15) >> 4) + WW_SPLIT_C0;     // cost of a tile: n-tiles + fixed part
         units += nt[q];
     }
-    const int cap = w.ntiles < 0xffff ? w.ntiles : 0xffff;
+    const int cap = ntiles < 0xffff ? ntiles : 0xffff;
     int total = 0;
     for (int q = 0; q < slabs; ++q) {
         int v = (int)((long long)ncu * nt[q] / units);
@@ -118,8 +118,8 @@ inline int ww_build_map(WwArgs& w, int ncu) {
     int start[9];
     start[0] = 0;
     for (int x = 0; x < 8; ++x) start[x + 1] = start[x] + (total - x + 7) / 8;
-    for (int id = 0; id < total; ++id) w.map.wg[id] = order[start[id & 7] + (id >> 3)];
-    for (int q = 0; q < slabs; ++q) w.map.S[q] = (unsigned short)S[q];
+    for (int id = 0; id < total; ++id) map.wg[id] = order[start[id & 7] + (id >> 3)];
+    for (int q = 0; q < slabs; ++q) map.S[q] = (unsigned short)S[q];
     return total;
 }
 

@@ -1,6 +1,7 @@
 """SHA-256 digests of what the network's 3x3 conv routes compute and launch, to compare two checkouts bit for bit.
 
-    python tools/net_digest.py [--tree DIR] [--out FILE.txt]
+    python tools/net_digest.py [--tree DIR] [--out FILE.txt] [--grads FILE.pt]
+    python tools/net_digest.py --compare A.pt B.pt
 
 `--tree DIR` imports the package of another checkout (its own library beside its own sources); everything goes through the
 C ABI of version 3 and the three one-number route hooks every such tree has, so one file drives any of them.  Run it on two
@@ -9,12 +10,16 @@ leave every line alone.
 
 Lines, in this order:
   * `routes ...`: sinddm_debug_conv_path / _infer_path / _train_path / _head_path over the grid of tests/test_routes_host.py
-    (one digest per width, and the row count).  Without a device the tool stops here (the hooks then assume 256 CUs).
+    (one digest per width, and the row count), and -- only where the tree has sinddm_debug_wgrad_routes -- the 17
+    weight-gradient launches over the same grid at 256, 64 and 304 CUs.  Without a device the tool stops here (the hooks
+    then assume 256 CUs).
   * both packed buffers (zero-filled before packing, so the alignment gaps do not differ) at dims 160, 80, 32, 20, 10;
   * sinddm_net_forward on closed-form and He weights at one shape per route;
   * y and grad_x of sinddm_net_forward_train + sinddm_net_backward (the parameter gradients go through atomics: the suite
     gates them, a digest cannot);
   * per shape, the launch counts per (kind, generation) of the conv profiler.
+`--grads` saves the flat parameter gradients of the TRAIN shapes; `--compare` prints, per shape, the worst per-tensor rel-L2
+distance between two such files (two runs of one tree give the run-to-run noise of the atomics: the suite's bound is 2e-6).
 """
 import argparse
 import ctypes as C
@@ -56,12 +61,35 @@ def route_rows(lib):
     return table
 
 
+def compare(a_path, b_path, net_param_shapes):
+    a, b = torch.load(a_path), torch.load(b_path)
+    worst_all = 0.0
+    for tag in a:
+        dim, off, worst = int(tag.split()[0][3:]), 0, (0.0, "")
+        for name, shape in net_param_shapes(dim).items():
+            n = 1
+            for v in shape:
+                n *= v
+            x, y = a[tag][off:off + n].double(), b[tag][off:off + n].double()
+            worst = max(worst, (float((x - y).norm() / y.norm().clamp_min(1e-300)), name))
+            off += n
+        assert off == a[tag].numel() == b[tag].numel()
+        worst_all = max(worst_all, worst[0])
+        print(f"flat_grads {tag}: worst per-tensor rel-L2 {worst[0]:.3e} ({worst[1]})")
+    print(f"flat_grads worst {worst_all:.3e}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--grads", default=None)
+    ap.add_argument("--compare", nargs=2, default=None)
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.tree))
+    if args.compare:
+        from sinddm_amd.synth import net_param_shapes
+        return compare(*args.compare, net_param_shapes)
     from sinddm_amd import _lib
     from sinddm_amd.synth import closed_form_state_dict, hash_randn, he_state_dict, net_param_shapes
     lib = _lib.load()
@@ -81,6 +109,17 @@ def main():
         rows += len(tab)
         emit(f"routes dim{da & 0xFFFF} fp32_convs{int(bool(da & FP32))} rows{len(tab)}", sha(repr(tab).encode()))
     emit(f"routes rows compared {rows}", sha(b""))
+    if hasattr(lib, "sinddm_debug_wgrad_routes"):
+        for ncu in (256, 64, 304):
+            tab = []
+            for dim in DIMS:
+                for da in (dim, dim | FP32):
+                    for B in BATCHES:
+                        for H, W in SIZES:
+                            out = (C.c_int * 68)()
+                            _lib.check(lib.sinddm_debug_wgrad_routes(da, B, H, W, ncu, out, 68), "sinddm_debug_wgrad_routes")
+                            tab.append((da, B, H, W, list(out)))
+            emit(f"wgrad routes ncu{ncu} rows{len(tab)}", sha(repr(tab).encode()))
     if not torch.cuda.is_available():
         print("no device: route tables only", flush=True)
         finish()
@@ -144,6 +183,7 @@ def main():
         emit(f"forward {tag} launches {counts}", sha(counts.encode()))
         del ws
 
+    grads = {}
     for dim, fp32, B, H, W in TRAIN:
         da = dim | (FP32 if fp32 else 0)
         p, pk, pkb = net(dim, "he")
@@ -165,7 +205,10 @@ def main():
         emit(f"train {tag} y", sha_t(y))
         emit(f"train {tag} grad_x", sha_t(gx))
         emit(f"train {tag} launches {counts}", sha(counts.encode()))
+        grads[tag] = gp.cpu()
         del ws
+    if args.grads:
+        torch.save(grads, args.grads)
     finish()
 
 
