@@ -503,6 +503,49 @@ int sinddm_reverse_step_ms(const float* x_t, const float* eps, const float* x_ti
                            const float* edit_c, const float* keep_m, const float* keep_x0, float keep_a, float keep_b,
                            int B, int C, int HW, void* stream);
 
+/* ---- seed blending: a sample's draw is a fixed combination of the draws of K seeds ------------------------------------- */
+/* The noise contract of per-sample seeds with one change: for stream id j the N(0,1) draw of element e of sample b is
+ *     z = sum_k weights[b*K + k] * (element e of sinddm_normal_fill(3*H*W, keys[b*K + k], j))
+ * evaluated in fp32 as  z = w0 * n0,  then  z = fma(wk, nk, z)  for k = 1 .. K-1, each operation rounded once (a term whose
+ * weight is 0 is skipped for k >= 1).  The streams of different keys are independent, so z is N(0,1) again when
+ * sum_k w^2 = 1; the library takes any finite weights.  Rows of weights on an arc interpolate between two samples, rows on
+ * a circle make a closed loop.  K = 1 with weight 1 is the per-sample seed keys[b], bit for bit. */
+#define SINDDM_MIX_MAX 4
+typedef struct sinddm_mix_opts {
+    const uint64_t* keys;     /* device, B*K entries, 8-byte aligned */
+    const float*    weights;  /* device, B*K entries, 4-byte aligned */
+    int             K;        /* 1 .. SINDDM_MIX_MAX */
+} sinddm_mix_opts;
+
+/* sinddm_normal_fill_samples of the blend: slice b of `out` (n floats at out + b*n) is the blend above of
+ * sinddm_normal_fill(n, keys[b*K + k], stream_id).  The sampler's initial / re-noise draws and the per-step draws of its
+ * step-by-step route.  SINDDM_E_BADARG: out / keys / weights NULL, keys not 8-byte or weights not 4-byte aligned, B <= 0,
+ * n <= 0, K outside 1 .. SINDDM_MIX_MAX; SINDDM_E_BADSHAPE: B > 65535. */
+int sinddm_normal_fill_mix(float* out, int B, int64_t n, const uint64_t* keys /*device, B*K*/,
+                           const float* weights /*device, B*K*/, int K, uint64_t stream_id, void* stream);
+
+/* sinddm_sample_chain_solver with a blend (every chain entry fills one internal description; they differ only in the options
+ * they can express).  mx = NULL or mx->keys = NULL: the same launches, the same numbers as sinddm_sample_chain_solver.  With
+ * the block, step i of the call adds to element e of sample b  sigma_i * z  with z the blend above at stream id
+ * stream_id0 + i (H, W the extended size under a halo); a jump's second draw is blended likewise at
+ * stream_id0 + i + SINDDM_JUMP_STREAM; `seed` is ignored.  opts->noise still wins over the block.  Halo, keep, ROI,
+ * per-sample maps, jumps, layout pulls, the multistep step and the two-stream split work as before (the second half-batch
+ * reads its own part of the tables); results with / without aux_stream are identical.
+ * SINDDM_E_BADARG (before any device work): K outside 1 .. SINDDM_MIX_MAX, keys without weights, keys not 8-byte or weights
+ * not 4-byte aligned, the block together with sample_seeds; SINDDM_E_BADSHAPE: B > 65535 or 3*H*W >= 2^31 (as for seeds). */
+int sinddm_sample_chain_mix(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                            const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                            int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                            void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                            const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                            const sinddm_keep_opts* keep /*host, may be NULL*/,
+                            const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/,
+                            const sinddm_resample_opts* rs /*host, may be NULL*/,
+                            const sinddm_layout_opts* lo /*host, may be NULL*/,
+                            const sinddm_batch_opts* bo /*host, may be NULL*/,
+                            const sinddm_solver_opts* so /*host, may be NULL*/,
+                            const sinddm_mix_opts* mx /*host, may be NULL*/);
+
 /* The block delta on its own: delta[B][3][h][w] from the step's inputs.  H x W is the CENTRE size (as in the chain calls);
  * x_t, eps, x_tilde are B*3*(H + 2 halo_y)*(W + 2 halo_x) floats, layout / edit_c one sample of that, edit_w one plane.
  * edit_w / edit_c both-or-neither.  x_tilde is read in modes 1 and 2 only.

@@ -38,6 +38,12 @@ A ... B (default: all).  FILE (a path, or a name inside the dataset folder) is b
 noise seed (no reference flag: the reference never seeds its generator): the image of a seed is the same at any batch size,
 position in the batch and number of GPUs.  `--vary_from_scale S` keeps the given seeds below scale S and derives fresh
 ones per sample from S on: `--seeds 17 17 17 17 --vary_from_scale 3` makes four variations of one coarse layout.
+`--interp_seeds A B` and `--loop_seeds BASE A B [--loop_radius R]` (no reference flags; in place of `--seeds`) blend seeds:
+every noise draw of frame b is a fixed unit-norm combination of the draws of the named seeds, so the frames walk from sample A
+to sample B, or around sample BASE on a closed circle of radius R (default 0.5).  `--frames N` is the batch size and frame b
+is sample b; `--blend_from_scale S` lets the scales below S use each frame's first seed alone (a shared coarse layout with
+detail that moves); `--gif MS` also writes the finest scale's frames as one animated GIF, MS milliseconds per frame, a loop
+repeating for ever.  Every sampling mode honours them.
 A batch of independent jobs: `--mask_path`, `--input_image` and `--layout_strength` take one or more values and `--anchor` one
 or more pairs.  With N > 1 values the batch size must be a multiple of N and sample b gets value b % N (so `--seeds` sweeps
 line up: `--sample_batch_size 8 --mask_path a.png b.png --seed_base 0` fills each hole four times); every sample is then
@@ -131,6 +137,14 @@ def build_parser():
     g = p.add_mutually_exclusive_group()
     g.add_argument("--seeds", type=int, nargs="+", default=None)
     g.add_argument("--seed_base", type=int, default=None)
+    # no reference flags: seed blending (MultiScaleGaussianDiffusion.seed_mix) of every sampling mode.  --frames N is the batch
+    # size: frame b is sample b, an interpolation from sample A to sample B or a closed loop around sample BASE.
+    g.add_argument("--interp_seeds", type=int, nargs=2, default=None, metavar=("A", "B"))
+    g.add_argument("--loop_seeds", type=int, nargs=3, default=None, metavar=("BASE", "A", "B"))
+    p.add_argument("--loop_radius", type=float, default=0.5)
+    p.add_argument("--frames", type=int, default=None)
+    p.add_argument("--blend_from_scale", type=int, default=0)
+    p.add_argument("--gif", type=int, default=None, metavar="MS")      # also write the frames as one animated GIF, MS per frame
     p.add_argument("--vary_from_scale", type=int, default=None)
     # no reference flags: RePaint's resampling jumps of `inpaint` / `outpaint` (MultiScaleGaussianDiffusion.resample)
     p.add_argument("--resample", type=int, default=1)
@@ -150,9 +164,27 @@ def build_parser():
 
 def parse_args(argv=None):
     """Parse the command line and resolve the seed flags: `args.seeds` becomes the list of `sample_batch_size` seeds (or
-    stays None)."""
+    stays None), `args.seed_mix` the [frames][K] blend tables of --interp_seeds / --loop_seeds (or None)."""
     p = build_parser()
     args = p.parse_args(argv)
+    args.seed_mix = None
+    if args.interp_seeds is not None or args.loop_seeds is not None:
+        from sinddm_amd.models import interp_seeds, loop_seeds
+        if args.frames is not None:
+            args.sample_batch_size = args.frames
+        try:
+            if args.interp_seeds is not None:
+                args.seed_mix = interp_seeds(*args.interp_seeds, args.sample_batch_size)
+            else:
+                args.seed_mix = loop_seeds(*args.loop_seeds, args.sample_batch_size, args.loop_radius)
+        except ValueError as e:
+            p.error(str(e))
+        if args.blend_from_scale < 0:
+            p.error("--blend_from_scale must be >= 0")
+        if args.gif is not None and args.gif < 1:
+            p.error("--gif MS must be >= 1")
+    elif args.frames is not None or args.gif is not None or args.blend_from_scale != 0:
+        p.error("--frames / --gif / --blend_from_scale need --interp_seeds or --loop_seeds")
     if args.seed_base is not None:
         args.seeds = [args.seed_base + b for b in range(args.sample_batch_size)]
     if args.seeds is not None:
@@ -252,12 +284,19 @@ def main():
         args.sample_spacing, args.solver_order, args.eta)
     if args.load_milestone > 0:
         trainer.load(milestone=args.load_milestone)
+    if args.seed_mix is not None:                                          # (a blend in place of seeds; the old command lines: untouched)
+        from sinddm_amd.models import mix_from_scale
+        if args.blend_from_scale > n_scales:
+            raise SystemExit(f"--blend_from_scale {args.blend_from_scale} is past the {n_scales} scales")
+        seed_kw = dict(seed_mix=mix_from_scale(args.seed_mix, args.blend_from_scale, n_scales) if args.blend_from_scale > 0
+                       else args.seed_mix)
+    frames = None                                                          # the per-scale batches of the sampling modes
     if args.mode == 'train':
         trainer.train()
         trainer.sample_scales(scale_mul=(1, 1), custom_sample=True, image_name=args.image_name,
                               batch_size=args.sample_batch_size, custom_t_list=sample_t_list, **seed_kw)
     elif args.mode == 'sample':
-        trainer.sample_scales(scale_mul=scale_mul, custom_sample=True, image_name=args.image_name,
+        frames = trainer.sample_scales(scale_mul=scale_mul, custom_sample=True, image_name=args.image_name,
                               batch_size=args.sample_batch_size, custom_t_list=sample_t_list, save_unbatched=True,
                               **seed_kw)
     elif args.mode in ('style_transfer', 'harmonization'):                 # reference main.py:296-322
@@ -267,7 +306,7 @@ def main():
         use_hist = args.mode == 'style_transfer'
         custom_t = [0] * (n_scales - 1) + [start_t]
         trainer.ema_model.reblurring = True
-        trainer.image2image(input_folder=i2i_folder, input_file=args.input_image, mask=args.harm_mask,
+        frames = trainer.image2image(input_folder=i2i_folder, input_file=args.input_image, mask=args.harm_mask,
                             hist_ref_path=f'{args.dataset_folder}scale_{start_s}/', batch_size=args.sample_batch_size,
                             image_name=args.image_name, start_s=start_s, custom_t=custom_t, scale_mul=(1, 1),
                             device=device, use_hist=use_hist, save_unbatched=True, auto_scale=50000, mode=args.mode,
@@ -276,7 +315,7 @@ def main():
         if not args.roi_target or len(args.roi_target) != 4 or not args.roi_bbs or len(args.roi_bbs) % 4:
             raise SystemExit("--mode roi needs --roi_target y x h w and --roi_bbs y x h w [y x h w ...]")
         bbs = [list(args.roi_bbs[i:i + 4]) for i in range(0, len(args.roi_bbs), 4)]
-        trainer.roi_guided_sampling(custom_t_list=sample_t_list, target_roi=list(args.roi_target), roi_bb_list=bbs,
+        frames = trainer.roi_guided_sampling(custom_t_list=sample_t_list, target_roi=list(args.roi_target), roi_bb_list=bbs,
                                     save_unbatched=True, batch_size=args.sample_batch_size, scale_mul=scale_mul, **seed_kw)
     elif args.mode == 'inpaint':
         if not args.mask_path:
@@ -292,13 +331,13 @@ def main():
             known = torch.stack([files[f] for f in paths])
         else:
             known = load(paths)
-        trainer.inpaint(known, batch_size=args.sample_batch_size,
+        frames = trainer.inpaint(known, batch_size=args.sample_batch_size,
                         hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True,
                         resample=args.resample, jump_length=args.jump_length, **seed_kw)
     elif args.mode == 'outpaint':
         anchor = job_values(args.anchor, args.sample_batch_size)
         anchor = [tuple(a) for a in anchor] if isinstance(args.anchor, Jobs) else tuple(anchor)
-        trainer.outpaint(scale_mul, anchor=anchor, batch_size=args.sample_batch_size,
+        frames = trainer.outpaint(scale_mul, anchor=anchor, batch_size=args.sample_batch_size,
                          custom_t_list=sample_t_list, save_unbatched=True, resample=args.resample,
                          jump_length=args.jump_length, **seed_kw)
     elif args.mode == 'paint2image':
@@ -317,7 +356,7 @@ def main():
             layout = torch.stack([files[f] for f in names])
         else:
             layout = load(names)
-        trainer.paint2image(layout, batch_size=args.sample_batch_size, down=args.layout_down,
+        frames = trainer.paint2image(layout, batch_size=args.sample_batch_size, down=args.layout_down,
                             strength=job_values(args.layout_strength, args.sample_batch_size),
                             t_min=args.layout_t_min, scales=args.layout_scales, scale_mul=scale_mul,
                             custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
@@ -325,6 +364,12 @@ def main():
         raise NotImplementedError(
             f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint and paint2image are built for MI355X; "
             "the CLIP-guided modes of the reference need CLIP autograd and are out of scope (SURVEY.md section 8)")
+    if args.gif is not None and frames and rank == 0:
+        from sinddm_amd.functions import write_gif
+        path = os.path.join(results_folder, f"{args.mode}_{'loop' if args.loop_seeds is not None else 'interp'}.gif")
+        # (an interpolation plays once; a loop closes on itself: loop=0 repeats it for ever)
+        write_gif(((frames[-1] + 1) * 0.5).clamp(0, 1).cpu(), path, args.gif, loop=0 if args.loop_seeds is not None else None)
+        print("wrote " + path)
     if world > 1:
         td.destroy_process_group()
 

@@ -32,12 +32,14 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_batch",
     "sinddm_sample_chain_solver", "sinddm_reverse_step_ms",
     "sinddm_q_sample_wrap", "sinddm_l1_loss_crop_fwd_bwd",
+    "sinddm_sample_chain_mix", "sinddm_normal_fill_mix",
 )
 
 
 ABI_VERSION = 3               # SINDDM_ABI_VERSION of include/sinddm_hip.h this binding was written against
 DIM_FP32_CONVS = 0x10000     # SINDDM_DIM_FP32_CONVS of include/sinddm_hip.h: option bit of every `dim` argument
 JUMP_STREAM = 1 << 31        # SINDDM_JUMP_STREAM of include/sinddm_hip.h: a jump's z2 draw is the step's stream id plus this
+MIX_MAX = 4                  # SINDDM_MIX_MAX of include/sinddm_hip.h: seeds per blended sample
 TILE_HALO = 16               # SINDDM_TILE_HALO of include/sinddm_hip.h: the network's receptive radius = halo of a wrapped axis
 
 
@@ -90,6 +92,12 @@ class SolverOpts(C.Structure):
     """Mirror of `sinddm_solver_opts` (include/sinddm_hip.h): `q` a HOST array of one extrapolation factor per step of the
     call (0: a first-order step), `hist` the device buffer that carries the previous step's clean estimate."""
     _fields_ = [("q", C.POINTER(C.c_float)), ("hist", C.c_void_p)]
+
+
+class MixOpts(C.Structure):
+    """Mirror of `sinddm_mix_opts` (include/sinddm_hip.h): `keys` (uint64) / `weights` (float32) device tables of K entries
+    per sample, or None."""
+    _fields_ = [("keys", C.c_void_p), ("weights", C.c_void_p), ("K", C.c_int)]
 
 
 class SinddmError(RuntimeError):
@@ -148,6 +156,10 @@ def load() -> C.CDLL:
         "sinddm_sample_chain_solver": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
                                                    C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts),
                                                    C.POINTER(SolverOpts)]),
+        "sinddm_sample_chain_mix": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
+                                                C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts),
+                                                C.POINTER(SolverOpts), C.POINTER(MixOpts)]),
+        "sinddm_normal_fill_mix": (i, [p, i, i64, p, p, i, C.c_uint64, p]),
         "sinddm_reverse_step_ms": (i, [p, p, p, p, p, C.POINTER(StepCoefs), f, p, p, p, p, p, f, f, i, i, i, p]),
         "sinddm_layout_delta": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, i, i, i, p]),
         "sinddm_reverse_step_layout": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, f, i, p, p, p, p, f, f, i, i, i, i, i, i, i,

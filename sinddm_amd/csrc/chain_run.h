@@ -49,6 +49,10 @@ struct ChainRun {
     const float* solver_q;               // HOST, one per step; NULL: the call without the block
     float* solver_hist;
     sinddm_batch_opts batch;             // (all 0 is the call without the block: batch_strides)
+    // sinddm_mix_opts
+    const uint64_t* mix_keys;            // NULL: the call without the block
+    const float* mix_w;
+    int mix_K;
 };
 
 // the 21 arguments every entry shares; the options start out absent
@@ -82,6 +86,9 @@ inline void chain_run_set(ChainRun& r, const sinddm_batch_opts* bo) {
 inline void chain_run_set(ChainRun& r, const sinddm_solver_opts* so) {
     if (so) { r.solver_q = so->q; r.solver_hist = so->hist; }
 }
+inline void chain_run_set(ChainRun& r, const sinddm_mix_opts* mx) {
+    if (mx && mx->keys) { r.mix_keys = mx->keys; r.mix_w = mx->weights; r.mix_K = mx->K; }
+}
 
 // a jump description the kernels can take: r in (0, 1], s >= 0, d only where x-tilde exists; never after a mode-2 step
 inline bool jump_valid(const sinddm_jump_coefs& j, const sinddm_step_coefs& k) {
@@ -93,6 +100,9 @@ struct ChainChecked {
     int H, W;                            // the extended size
     bool tiled;
     const unsigned long long* sseeds;    // per-sample seeds the kernels see: NULL when recorded draws win over them
+    const unsigned long long* mkeys;     // the blend tables the kernels see (K entries per sample): NULL without the block
+    const float* mw;                     // and when recorded draws win over it
+    int mK;
     const sinddm_jump_coefs* jumps;      // NULL: no step of the run jumps, and nothing differs from the call without them
     const float* jump_noise;             // one slot per jump, in order of occurrence
     const float* lay_g;                  // NULL: no step of the run pulls, and nothing differs from the call without a layout
@@ -107,6 +117,12 @@ inline int chain_check(const ChainRun& r, ChainChecked* out) {
     if ((r.halo_y != 0 && r.halo_y < SINDDM_TILE_HALO) || (r.halo_x != 0 && r.halo_x < SINDDM_TILE_HALO)) return SINDDM_E_BADARG;
     if (r.halo_y > (1 << 20) || r.halo_x > (1 << 20)) return SINDDM_E_BADARG;            // (H + 2 halo stays an int)
     if ((bits(r.sample_seeds) & 7) != 0) return SINDDM_E_BADARG;
+    if (r.mix_keys) {                                          // a blend of K per-sample streams: never beside per-sample seeds
+        if (r.mix_K < 1 || r.mix_K > SINDDM_MIX_MAX) return SINDDM_E_BADARG;
+        if (!r.mix_w) return SINDDM_E_BADARG;
+        if ((bits(r.mix_keys) & 7) != 0 || (bits(r.mix_w) & 3) != 0) return SINDDM_E_BADARG;
+        if (r.sample_seeds) return SINDDM_E_BADARG;
+    }
     if (!r.params || !r.packed || !r.x || !r.x_alt || !r.eps || !r.coefs || !r.t_list || !r.ws || r.n_steps < 0 || r.B <= 0 ||
         r.Hc <= 0 || r.Wc <= 0)
         return SINDDM_E_BADARG;
@@ -120,6 +136,11 @@ inline int chain_check(const ChainRun& r, ChainChecked* out) {
     // per-sample seeds: recorded draws win over them, as they win over `seed`; the kernels then never see the array
     c.sseeds = r.noise ? nullptr : reinterpret_cast<const unsigned long long*>(r.sample_seeds);
     if (c.sseeds && (past_int || r.B > 65535)) return SINDDM_E_BADSHAPE;                 // (per-sample quads are ints)
+    // ... and over a blend, whose rows are laid out like seeded ones
+    if (r.mix_keys && !r.noise) {
+        c.mkeys = reinterpret_cast<const unsigned long long*>(r.mix_keys); c.mw = r.mix_w; c.mK = r.mix_K;
+        if (past_int || r.B > 65535) return SINDDM_E_BADSHAPE;
+    }
     // (the plain fused tail reads the maps and the draws as 16-byte vectors)
     if (((bits(r.edit_w) | bits(r.edit_c) | bits(r.noise) | bits(r.keep_m) | bits(r.keep_x0)) & 15) != 0) return SINDDM_E_BADARG;
     // resampling jumps: a step with jumps[i].on runs unfused and ends in reverse_step_jump_kernel

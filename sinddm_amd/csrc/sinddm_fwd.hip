@@ -927,11 +927,14 @@ struct ChainStep {
 };
 
 // The options of a tail launch as compile-time constants: calls f(EDIT, NOISE, KEEP) with std::true_type / std::false_type
-// according to which of the launch's pointers are set; f launches its kernel's <decltype(EDIT)::value, ...> instantiation.
+// (NOISE: an integral_constant of DRAW_PHILOX / DRAW_RECORDED / DRAW_MIX) according to which of the launch's pointers are set; f launches its kernel's <decltype(EDIT)::value, ...> instantiation.
 template <class F>
 static void tail_dispatch(const TailArgs& t, F&& f) {
     auto keep = [&](auto e, auto n) { t.km ? f(e, n, std::true_type{}) : f(e, n, std::false_type{}); };
-    auto noise = [&](auto e) { t.nz ? keep(e, std::true_type{}) : keep(e, std::false_type{}); };
+    auto noise = [&](auto e) {
+        t.nz ? keep(e, std::integral_constant<int, DRAW_RECORDED>{})
+             : t.mkeys ? keep(e, std::integral_constant<int, DRAW_MIX>{}) : keep(e, std::integral_constant<int, DRAW_PHILOX>{});
+    };
     t.ew ? noise(std::true_type{}) : noise(std::false_type{});
 }
 
@@ -945,8 +948,9 @@ struct TailIO {
     hipStream_t st;
 };
 
-// the rows of a tail launch: one per sample with per-sample seeds, else one row of the whole launch
-static long long tail_span(const TailIO& io, const TailArgs& t) { return t.sseeds ? io.chw : (long long)io.Bn * io.chw; }
+// the rows of a tail launch: one per sample with per-sample seeds or a blend, else one row of the whole launch
+static bool tail_per_sample(const TailArgs& t) { return t.sseeds || (t.mkeys && !t.nz); }
+static long long tail_span(const TailIO& io, const TailArgs& t) { return tail_per_sample(t) ? io.chw : (long long)io.Bn * io.chw; }
 
 // One launch of a tail kernel over rows: `kernel(E, N, K)` names the instantiation (TAIL_KERNEL), `extra` is what the kernel
 // takes between the TailArgs and the extent (it documents them).  `mid_quad`: a kernel on the stream-row walk (step_tail.h).
@@ -957,7 +961,7 @@ static int tail_rows_launch(const TailIO& io, const TailArgs& t, bool mid_quad, 
                             : ((span + 3) / 4 + 255) / 256;        // (no + 1: a row of this kernel starts on a quad of its stream)
     if (gx > 8192) gx = 8192;
     tail_dispatch(t, [&](auto E, auto N, auto K) {
-        hipLaunchKernelGGL(kernel(E, N, K), dim3((unsigned)gx, t.sseeds ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps,
+        hipLaunchKernelGGL(kernel(E, N, K), dim3((unsigned)gx, tail_per_sample(t) ? (unsigned)io.Bn : 1u), dim3(256), 0, io.st, io.x_t, io.eps,
                            io.x_tilde, io.out, t, extra..., span, io.chw, io.hw);
     });
     return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
@@ -1400,14 +1404,14 @@ int sinddm_reverse_step(const float* x_t, const float* eps, const float* x_tilde
     return reverse_step_launch(x_t, eps, x_tilde, out, t, (long long)n, 1, 1, stream);
 }
 
-// one row per key: `seed`, or seeds[0 .. rows - 1]
+// one row per key: `seed`, or seeds[0 .. rows - 1]; with mix_w one row per blend of K keys (seeds / mix_w: rows * K entries)
 static int normal_fill_launch(float* out, int rows, int64_t n, uint64_t seed, const uint64_t* seeds, uint64_t stream_id,
-                              void* stream) {
+                              void* stream, const float* mix_w = nullptr, int K = 0) {
     long long bx = ((n + 3) / 4 + 255) / 256;
     if (bx > 8192) bx = 8192;
     hipLaunchKernelGGL(philox_normal_rows_kernel, dim3((unsigned)bx, (unsigned)rows), dim3(256), 0,
                        static_cast<hipStream_t>(stream), out, (long long)n, (unsigned long long)seed,
-                       reinterpret_cast<const unsigned long long*>(seeds), (unsigned long long)stream_id);
+                       reinterpret_cast<const unsigned long long*>(seeds), mix_w, K, (unsigned long long)stream_id);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }
@@ -1421,6 +1425,14 @@ int sinddm_normal_fill_samples(float* out, int B, int64_t n, const uint64_t* see
     if (!out || !seeds || B <= 0 || n <= 0 || (reinterpret_cast<uintptr_t>(seeds) & 7) != 0) return SINDDM_E_BADARG;
     if (B > 65535) return SINDDM_E_BADSHAPE;                                   // (one grid row per slice)
     return normal_fill_launch(out, B, n, 0, seeds, stream_id, stream);
+}
+
+int sinddm_normal_fill_mix(float* out, int B, int64_t n, const uint64_t* keys, const float* weights, int K, uint64_t stream_id,
+                           void* stream) {
+    if (!out || !keys || !weights || B <= 0 || n <= 0 || K < 1 || K > SINDDM_MIX_MAX) return SINDDM_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(keys) & 7) != 0 || (reinterpret_cast<uintptr_t>(weights) & 3) != 0) return SINDDM_E_BADARG;
+    if (B > 65535) return SINDDM_E_BADSHAPE;                                   // (one grid row per slice)
+    return normal_fill_launch(out, B, n, 0, keys, stream_id, stream, weights, K);
 }
 
 // sampler runs whose dim -> dim conv launches carry between LO and HI (8x32 tile, 80-channel block) items per CU AND leave
@@ -1572,6 +1584,10 @@ static int chain_half_step(const ChainCtx& k, const ChainStepPlan& s, int h) {
     cs.tail = s.t;
     const int b0 = cs.tail.b0 = h ? k.sp.Bh[0] : 0;
     if (k.c.sseeds) cs.tail.sseeds = k.c.sseeds + b0;
+    if (k.c.mkeys) {                                           // (the half's own part of the blend tables)
+        cs.tail.mkeys = k.c.mkeys + (size_t)b0 * k.c.mK;
+        cs.tail.mw = k.c.mw + (size_t)b0 * k.c.mK;
+    }
     // (per-sample maps: the half's own slices, like its seeds -- the kernels index them with the launch's sample)
     cs.tail.ew = batch_slice(s.t.ew, b0, s.t.sew); cs.tail.ec = batch_slice(s.t.ec, b0, s.t.sec);
     cs.tail.km = batch_slice(s.t.km, b0, s.t.skm); cs.tail.kx = batch_slice(s.t.kx, b0, s.t.skx);
@@ -1632,6 +1648,7 @@ static int chain_enqueue(const ChainCtx& k, float** result) {
             t.k = r.coefs[i];
             t.seed = (unsigned long long)r.seed; t.step = (unsigned long long)(r.stream_id0 + (uint64_t)i);
             t.sseeds = k.c.sseeds;
+            t.mkeys = k.c.mkeys; t.mw = k.c.mw; t.mK = k.c.mK;
             t.ew = r.edit_w; t.ec = r.edit_c; t.nz = r.noise ? r.noise + (size_t)i * (size_t)n : nullptr;
             t.km = r.keep_m; t.kx = r.keep_x0;
             t.sew = k.bs.sew; t.sec = k.bs.sec; t.skm = k.bs.skm; t.skx = k.bs.skx;
@@ -1782,6 +1799,17 @@ int sinddm_sample_chain_solver(CHAIN_SHARED_PARAMS, void* aux_stream, int* resul
     ChainRun r = CHAIN_SHARED(aux_stream);
     chain_run_set(r, opts); chain_run_set(r, keep); chain_run_set(r, rs); chain_run_set(r, lo); chain_run_set(r, bo);
     chain_run_set(r, so);
+    r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
+    return sample_chain_impl(r);
+}
+
+int sinddm_sample_chain_mix(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                            int halo_x, const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
+                            const sinddm_layout_opts* lo, const sinddm_batch_opts* bo, const sinddm_solver_opts* so,
+                            const sinddm_mix_opts* mx) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep); chain_run_set(r, rs); chain_run_set(r, lo); chain_run_set(r, bo);
+    chain_run_set(r, so); chain_run_set(r, mx);
     r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
     return sample_chain_impl(r);
 }

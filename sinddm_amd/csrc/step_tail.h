@@ -7,7 +7,7 @@
 namespace sinddm {
 
 // What every tail kernel takes besides its tensors: the step's scalars and its three options.  A NULL pointer is read by no
-// instantiation that could see it (the host picks EDIT / NOISE / KEEP from the pointers).  Each map family is shared by all
+// instantiation that could see it (the host picks EDIT / NOISE / KEEP from the pointers: nz -> recorded draws, else mkeys -> a blend).  Each map family is shared by all
 // samples of the batch (its stride 0) or PER SAMPLE: sample b of THIS launch reads its slice at  ptr + b * stride  (stride in
 // floats: the family's size).  Like `sseeds`, the pointers are those of the launch's first sample: the host offsets them
 // for the second half-batch, and no kernel adds b0 to a map index.  The stride is address arithmetic only: the shared
@@ -24,7 +24,14 @@ struct TailArgs {
     const float* kx;
     float ka, kb;                       // KEEP   this step's forward scalars of the known image (sinddm_keep_opts::ab)
     int sew, sec, skm, skx;             // per-sample strides of ew / ec / km / kx: 0 (shared) or HW / 3*HW / HW / 3*HW
+    const unsigned long long* mkeys;    // MIX    the blend tables of THIS launch's samples (device): key[b*K + k], w[b*K + k]
+    const float* mw;
+    int mK;                             // MIX    seeds per sample, 1 .. SINDDM_MIX_MAX
 };
+// Where a tail's N(0,1) draws come from, the NOISE option of every tail kernel: Philox of one key per launch or per sample
+// (the kernels the chain always ran), recorded draws read from `nz`, or a BLEND of K per-sample Philox streams (philox_mix4).
+// Rows under DRAW_MIX are laid out as under per-sample seeds: a row is a sample, its quads are counted from its start.
+enum { DRAW_PHILOX = 0, DRAW_RECORDED = 1, DRAW_MIX = 2 };
 // sample b's slice of a map (b is launch-local; the offset is 64-bit, the index inside the slice stays an int)
 __device__ __forceinline__ const float* map_slice(const float* __restrict__ p, long long b, int stride) {
     return p + (size_t)(b * (long long)stride);
@@ -111,12 +118,41 @@ __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned
     z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
 }
 
+// THE blended draw, the only place it is written: the four normals of quad q of a row whose draw is the fixed combination
+//     z = sum_k w[k] * n(key[k])        (w[k] = 0 for k >= 1 is skipped: that stream is not drawn)
+// of K independent streams -- N(0,1) again when sum w^2 = 1.  Evaluated as  z = w0 * n0,  z = fma(wk, nk, z)  with the
+// explicit rounding intrinsics, so that no call site is contracted differently from another: the tails, the fill and a host
+// that composes recorded draws from the fill all get the same bits.  K = 1, w = 1 is philox_normal4(key, step, q) itself.
+// `key` / `w` are the row's K entries: block-uniform, scalar loads.
+__device__ __forceinline__ void philox_mix4(const unsigned long long* __restrict__ key, const float* __restrict__ w, int K,
+                                            unsigned long long step, unsigned long long q, float (&z)[4]) {
+    float n[4];
+    philox_normal4(key[0], step, q, n);
+    const float w0 = w[0];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = __fmul_rn(w0, n[j]);
+    for (int k = 1; k < K; ++k) {
+        const float wk = w[k];
+        if (wk == 0.0f) continue;
+        philox_normal4(key[k], step, q, n);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[j] = __fmaf_rn(wk, n[j], z[j]);
+    }
+}
+// the draw of quad q of launch-local sample `row`: that sample's blend under DRAW_MIX, else Philox of `key`
+template <int NOISE>
+__device__ __forceinline__ void philox_draw4(const TailArgs& a, int row, unsigned long long key, unsigned long long step,
+                                             unsigned long long q, float (&z)[4]) {
+    if (NOISE == DRAW_MIX) philox_mix4(a.mkeys + (size_t)row * a.mK, a.mw + (size_t)row * a.mK, a.mK, step, q, z);
+    else philox_normal4(key, step, q, z);
+}
+
 // the draws of one quad: NOISE reads them at `nzq` (one 16-byte load when `vec`, else its nv valid lanes), otherwise they
-// are Philox quad `q` of (key, step)
-template <bool NOISE>
-__device__ __forceinline__ void quad_draw(const float* __restrict__ nzq, bool vec, int nv, unsigned long long key,
-                                          unsigned long long step, unsigned long long q, float (&z)[4]) {
-    if (NOISE) {
+// are Philox quad `q` of (key, step) -- of sample `row`'s blend under DRAW_MIX
+template <int NOISE>
+__device__ __forceinline__ void quad_draw(const TailArgs& a, int row, const float* __restrict__ nzq, bool vec, int nv,
+                                          unsigned long long key, unsigned long long step, unsigned long long q, float (&z)[4]) {
+    if (NOISE == DRAW_RECORDED) {
         if (vec) {
             const f32x4 zv = *reinterpret_cast<const f32x4*>(nzq);
             z[0] = zv[0]; z[1] = zv[1]; z[2] = zv[2]; z[3] = zv[3];
@@ -124,7 +160,7 @@ __device__ __forceinline__ void quad_draw(const float* __restrict__ nzq, bool ve
             for (int j = 0; j < nv; ++j) z[j] = nzq[j];
         }
     } else {
-        philox_normal4(key, step, q, z);
+        philox_draw4<NOISE>(a, row, key, step, q, z);
     }
 }
 
@@ -150,12 +186,15 @@ __device__ __forceinline__ void quad_maps(const float* __restrict__ plane, const
 
 // the noise key of sample b of a fused tail's launch: (seed, index inside the whole batch), or with per-sample seeds
 // (sseeds[b], index inside the sample: element e of the sample gets element e of sinddm_normal_fill(3HW, sseeds[b], step)).
-// `ofs` turns the launch's flat index into the key's index.  One scalar load and a scalar move per block.
+// `ofs` turns the launch's flat index into the key's index.  One scalar load and a scalar move per block.  A blended
+// sample (DRAW_MIX) is indexed like a seeded one.
 struct NoiseKey {
     unsigned long long key;
     long long ofs;
 };
+template <int NOISE>
 __device__ __forceinline__ NoiseKey noise_key(const TailArgs& a, int b, long long chw) {
+    if (NOISE == DRAW_MIX) return NoiseKey{0ull, -(long long)b * chw};      // (the keys are read by philox_mix4)
     return a.sseeds ? NoiseKey{a.sseeds[b], -(long long)b * chw} : NoiseKey{a.seed, (long long)a.b0 * chw};
 }
 
@@ -187,14 +226,17 @@ __global__ __launch_bounds__(256) void reverse_step_kernel(const float* __restri
 //   EDIT   the ROI edit: w = ew[p], c = ec[ch * HW + p]
 //   NOISE  z is READ from `nz` at the element's flat index inside the whole batch instead of drawn from Philox (a step's
 //          slice starts at a multiple of n floats: not 16-byte aligned in general, so lane by lane).  Recorded draws win
-//          over per-sample seeds on the host: no launch has both.
+//          over per-sample seeds on the host: no launch has both.  An int since the blend: DRAW_PHILOX (the draw above),
+//          DRAW_RECORDED (this), DRAW_MIX (z is the row's blend of K Philox streams, philox_mix4; rows are samples, as with
+//          per-sample seeds, and the exception below does not apply).
 //   KEEP   the known-region replacement of keep_blend: m = km[p], k0 = kx[ch * HW + p]
-template <bool EDIT, bool NOISE, bool KEEP>
+template <bool EDIT, int NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                 const float* __restrict__ xtil, float* __restrict__ out,
                                                                 TailArgs a, long long span, int chw, int hw) {
     const long long base = (long long)blockIdx.y * span;
-    const unsigned long long key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
+    const bool per_sample = NOISE == DRAW_MIX || a.sseeds;
+    const unsigned long long key = NOISE != DRAW_MIX && a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
     const bool aligned = (base & 3) == 0;
     const bool draw = tail_draws<KEEP>(a);
     const long long n4 = (span + 3) >> 2;
@@ -203,12 +245,12 @@ __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __r
         const long long i0 = base + (q << 2);
         const bool vec = aligned && nv == 4;
         float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (draw) quad_draw<NOISE>(a.nz + i0, false, nv, key, a.step, (unsigned long long)q, z);
+        if (draw) quad_draw<NOISE>(a, blockIdx.y, a.nz + i0, false, nv, key, a.step, (unsigned long long)q, z);
         float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
         if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, i0, 0, nv, chw, hw, w, c);
         float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
         if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, i0, 0, nv, chw, hw, m, k0);
-        if (!a.sseeds && nv < 4) {       // the exception above
+        if (!per_sample && nv < 4) {     // the exception above
             for (int j = 0; j < nv; ++j) {
                 const float xb = a.k.mode != 0 ? xtil[i0 + j] : 0.f;
                 out[i0 + j] = tail_eval<EDIT, KEEP>(a, xt[i0 + j], eps[i0 + j], xb, z[j], w[j], c[j], m[j], k0[j]);
@@ -245,7 +287,7 @@ __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __r
 
 // ---- the STREAM-ROW WALK of the tails launched behind the network's eps (jump, layout, multistep): what they share, written
 // once.  Over ROWS, like reverse_step_rows_kernel: row blockIdx.y is `span` elements from row * span of the launch's tensors.
-// With per-sample seeds a row is a sample (span = chw, key = sseeds[row], quads counted from the sample's start); otherwise
+// With per-sample seeds or a blend a row is a sample (span = chw, key = sseeds[row], quads counted from the sample's start); otherwise
 // the launch is one row of a.seed's stream that starts at element b0 * chw of the WHOLE batch -- a half-batch of a
 // two-stream run, whose start is inside a quad of the stream when b0 * chw % 4 != 0.  So a thread owns a quad OF THE KEY'S
 // STREAM and lanes [jlo, jhi) of it lie inside the row: the first and the last quad of a row may be partial.
@@ -284,13 +326,13 @@ struct StreamRow {
     int chw, hw;
     bool draw;                          // tail_draws
 };
-template <bool KEEP>
+template <int NOISE, bool KEEP>
 __device__ __forceinline__ StreamRow stream_row(const TailArgs& a, long long span, int chw, int hw) {
     StreamRow r;
     r.key = a.sseeds ? a.sseeds[blockIdx.y] : a.seed;
     r.base = (long long)blockIdx.y * span;
     r.gofs = (long long)a.b0 * chw;
-    r.kofs = a.sseeds ? 0 : r.gofs;
+    r.kofs = NOISE == DRAW_MIX || a.sseeds ? 0 : r.gofs;
     r.span = span; r.chw = chw; r.hw = hw;
     r.q0 = (r.kofs >> 2) + (long long)blockIdx.x * 256 + threadIdx.x;
     r.q1 = (r.kofs + span + 3) >> 2;
@@ -308,7 +350,7 @@ struct StreamQuad {
     float w[4], c[4], m[4], k0[4];      // the edit maps (1, 0 without EDIT) and the keep maps (0, 0 without KEEP)
     float x[4], e[4], xb[4];            // x_t, eps, x-tilde (0 in mode 0)
 };
-template <bool EDIT, bool NOISE, bool KEEP>
+template <bool EDIT, int NOISE, bool KEEP>
 __device__ __forceinline__ StreamQuad stream_quad(const TailArgs& a, const StreamRow& row, long long q) {
     StreamQuad s{};
     const long long e0 = (q << 2) - row.kofs;               // lane 0's index inside the row: -3 .. span - 1
@@ -316,8 +358,8 @@ __device__ __forceinline__ StreamQuad stream_quad(const TailArgs& a, const Strea
     s.jhi = row.span - e0 < 4 ? (int)(row.span - e0) : 4;
     s.i0 = row.base + e0;
     if (row.draw) {
-        if (NOISE) quad_load(a.nz + row.gofs + s.i0, s.jlo, s.jhi, s.z);
-        else philox_normal4(row.key, a.step, (unsigned long long)q, s.z);
+        if (NOISE == DRAW_RECORDED) quad_load(a.nz + row.gofs + s.i0, s.jlo, s.jhi, s.z);
+        else philox_draw4<NOISE>(a, blockIdx.y, row.key, a.step, (unsigned long long)q, s.z);
     }
     const long long iv = s.i0 + s.jlo;                      // the first valid lane: >= 0, its sample is iv / chw
     s.b = (int)(iv / row.chw);
@@ -383,18 +425,18 @@ __device__ __forceinline__ float jump_eval(const TailArgs& a, const JumpArgs& jp
 
 // Two draws per element: z from stream a.step (the step's own, as in every tail), z2 from a.step + SINDDM_JUMP_STREAM, same
 // key, same quad.  NOISE reads both at the element's flat index inside the whole batch (a.nz, jp.nz) instead.
-template <bool EDIT, bool NOISE, bool KEEP>
+template <bool EDIT, int NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_jump_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                 const float* __restrict__ xtil, float* __restrict__ out,
                                                                 TailArgs a, JumpArgs jp, long long span, int chw, int hw) {
-    const StreamRow row = stream_row<KEEP>(a, span, chw, hw);
+    const StreamRow row = stream_row<NOISE, KEEP>(a, span, chw, hw);
     const bool draw2 = jp.s != 0.0f;
     for (long long q = row.q0; q < row.q1; q += (long long)gridDim.x * 256) {
         StreamQuad s = stream_quad<EDIT, NOISE, KEEP>(a, row, q);
         float z2[4] = {0.f, 0.f, 0.f, 0.f};
         if (draw2) {
-            if (NOISE) quad_load(jp.nz + row.gofs + s.i0, s.jlo, s.jhi, z2);
-            else philox_normal4(row.key, a.step + SINDDM_JUMP_STREAM, (unsigned long long)q, z2);
+            if (NOISE == DRAW_RECORDED) quad_load(jp.nz + row.gofs + s.i0, s.jlo, s.jhi, z2);
+            else philox_draw4<NOISE>(a, blockIdx.y, row.key, a.step + SINDDM_JUMP_STREAM, (unsigned long long)q, z2);
         }
         stream_quad_load(a, s, xt, eps, xtil);
         f32x4 o;
@@ -507,11 +549,11 @@ __device__ __forceinline__ float layout_pull(const LayoutArgs& g, int b, int r) 
 
 // The conditioned step: tail_eval with the edit always on and c_eff in place of ec (w = 1 without ROI maps).  An element's
 // sample is its index inside the launch divided by chw: D is this launch's slice.
-template <bool EDIT, bool NOISE, bool KEEP>
+template <bool EDIT, int NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                   const float* __restrict__ xtil, float* __restrict__ out,
                                                                   TailArgs a, LayoutArgs g, long long span, int chw, int hw) {
-    const StreamRow row = stream_row<KEEP>(a, span, chw, hw);
+    const StreamRow row = stream_row<NOISE, KEEP>(a, span, chw, hw);
     for (long long q = row.q0; q < row.q1; q += (long long)gridDim.x * 256) {
         StreamQuad s = stream_quad<EDIT, NOISE, KEEP>(a, row, q);
         int b = s.b, r = s.r;                               // the lanes behind the first valid one may run over the sample's end
@@ -542,12 +584,12 @@ __global__ __launch_bounds__(256) void reverse_step_layout_kernel(const float* _
 // profiles/NOTES_r21.md), so the single-step entry, whose q == 0 form is pinned bit for bit, runs that kernel itself then.
 // `hist` has the launch's extent, like `out`; it is read and written in place by the thread that owns the element, so it
 // is the one pointer here without __restrict__.
-template <bool EDIT, bool NOISE, bool KEEP>
+template <bool EDIT, int NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_ms_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                               const float* __restrict__ xtil, float* __restrict__ out,
                                                               TailArgs a, float q, float* hist, long long span, int chw,
                                                               int hw) {
-    const StreamRow row = stream_row<KEEP>(a, span, chw, hw);
+    const StreamRow row = stream_row<NOISE, KEEP>(a, span, chw, hw);
     for (long long qd = row.q0; qd < row.q1; qd += (long long)gridDim.x * 256) {
         StreamQuad s = stream_quad<EDIT, NOISE, KEEP>(a, row, qd);
         stream_quad_load(a, s, xt, eps, xtil);
@@ -580,14 +622,14 @@ __global__ __launch_bounds__(256) void step_xp_kernel(const float* __restrict__ 
 // call is the tail, whichever stage ran.  A block row owns one sample.  EDIT / NOISE / KEEP: a thread's four pixels are contiguous
 // and 16-byte aligned in the maps and in the step's noise slice too (HW % 4 == 0; the pointers are checked by the caller),
 // so all of them are read as f32x4 -- a per-sample slice starts a multiple of HW floats behind its pointer, aligned as well.
-template <bool EDIT, bool NOISE, bool KEEP, class EPS>
+template <bool EDIT, int NOISE, bool KEEP, class EPS>
 __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, const float* __restrict__ xt,
                                                                       const float* __restrict__ xtil, float* __restrict__ out,
                                                                       int HW, TailArgs t) {
     const int b = blockIdx.y;
     const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (p >= HW) return;
-    const NoiseKey nk = noise_key(t, b, (long long)3 * HW);
+    const NoiseKey nk = noise_key<NOISE>(t, b, (long long)3 * HW);
     f32x4 e[3];
     eps(b, p >> 2, e);
     f32x4 mw{1.f, 1.f, 1.f, 1.f};
@@ -599,7 +641,7 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, c
         const long long i0 = ((long long)b * 3 + c) * HW + p;
         const long long ig = i0 + (long long)t.b0 * 3 * HW;         // flat index inside the whole batch (recorded draws)
         float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (tail_draws<KEEP>(t)) quad_draw<NOISE>(t.nz + ig, true, 4, nk.key, t.step, (unsigned long long)((i0 + nk.ofs) >> 2), z);
+        if (tail_draws<KEEP>(t)) quad_draw<NOISE>(t, b, t.nz + ig, true, 4, nk.key, t.step, (unsigned long long)((i0 + nk.ofs) >> 2), z);
         const f32x4 x = *reinterpret_cast<const f32x4*>(xt + i0);
         f32x4 xb{0.f, 0.f, 0.f, 0.f};
         if (t.k.mode != 0) xb = *reinterpret_cast<const f32x4*>(xtil + i0);
@@ -623,7 +665,7 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, c
 // tensors (x_t, x-tilde, x_{t-1}) are plain, so its up to four pixels sit at an unaligned flat index and their N(0,1)
 // draws -- keyed on the FLAT quad index like everywhere else -- come from up to two Philox calls.  EDIT / NOISE / KEEP: the
 // maps and the recorded draws are plain tensors as well: scalar reads at the unaligned flat index, like x_t.
-template <bool EDIT, bool NOISE, bool KEEP, class EPS>
+template <bool EDIT, int NOISE, bool KEEP, class EPS>
 __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS eps, const float* __restrict__ xt,
                                                                             const float* __restrict__ xtil,
                                                                             float* __restrict__ out, int H, int W, int Wp,
@@ -634,7 +676,7 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS 
     if (q >= H * qpr) return;
     const int y = q / qpr, x = (q - y * qpr) * 4;
     const long long HW = (long long)H * W;
-    const NoiseKey nk = noise_key(t, b, 3 * HW);
+    const NoiseKey nk = noise_key<NOISE>(t, b, 3 * HW);
     f32x4 e[3];
     eps(b, q, e);
     const int nv = W - x;                                   // valid pixels of the quad (>= 1)
@@ -650,9 +692,9 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS 
         const long long ik = i0 + nk.ofs;                           // the noise key's index
         const int r0 = (int)(ik & 3);
         float za[4] = {0.f, 0.f, 0.f, 0.f}, zb[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!NOISE && draw) {
-            philox_normal4(nk.key, t.step, (unsigned long long)(ik >> 2), za);
-            if (r0 != 0) philox_normal4(nk.key, t.step, (unsigned long long)(ik >> 2) + 1ull, zb);
+        if (NOISE != DRAW_RECORDED && draw) {
+            philox_draw4<NOISE>(t, b, nk.key, t.step, (unsigned long long)(ik >> 2), za);
+            if (r0 != 0) philox_draw4<NOISE>(t, b, nk.key, t.step, (unsigned long long)(ik >> 2) + 1ull, zb);
         }
         const float z8[8] = {za[0], za[1], za[2], za[3], zb[0], zb[1], zb[2], zb[3]};
 #pragma unroll
@@ -662,7 +704,7 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS 
                 z = r0 == 1 ? z8[j + 1] : z;
                 z = r0 == 2 ? z8[j + 2] : z;
                 z = r0 == 3 ? z8[j + 3] : z;
-                if (NOISE) z = draw ? t.nz[ig + j] : 0.f;
+                if (NOISE == DRAW_RECORDED) z = draw ? t.nz[ig + j] : 0.f;
                 const int pp = y * W + x + j;
                 const float xb = t.k.mode != 0 ? xtil[i0 + j] : 0.f;
                 float mw = 1.f, mc = 0.f;
@@ -682,15 +724,17 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS 
 // reverse_step_rows_kernel: row blockIdx.y is `span` floats from row * span, filled with quads 0, 1, ... of its key --
 // `seed` (sinddm_normal_fill: one row) or seeds[row] (sinddm_normal_fill_samples).  A row starts at an unaligned address
 // when span % 4 != 0, so the stores are scalar, and its last quad is cut at its end.
+// With `mw` the row is a blend (sinddm_normal_fill_mix): seeds / mw hold K entries per row, drawn by philox_mix4.
 __global__ __launch_bounds__(256) void philox_normal_rows_kernel(float* __restrict__ out, long long span, unsigned long long seed,
                                                                  const unsigned long long* __restrict__ seeds,
-                                                                 unsigned long long step) {
-    const unsigned long long key = seeds ? seeds[blockIdx.y] : seed;
+                                                                 const float* __restrict__ mw, int K, unsigned long long step) {
+    const unsigned long long key = seeds && !mw ? seeds[blockIdx.y] : seed;
     float* __restrict__ o = out + (long long)blockIdx.y * span;
     const long long n4 = (span + 3) >> 2;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
         float z[4];
-        philox_normal4(key, step, (unsigned long long)q, z);
+        if (mw) philox_mix4(seeds + (size_t)blockIdx.y * K, mw + (size_t)blockIdx.y * K, K, step, (unsigned long long)q, z);
+        else philox_normal4(key, step, (unsigned long long)q, z);
         for (int j = 0; j < 4 && (q << 2) + j < span; ++j) o[(q << 2) + j] = z[j];
     }
 }

@@ -320,6 +320,20 @@ def _layout_pyramid(layout, sizes) -> List[torch.Tensor]:
     return out
 
 
+def write_gif(frames, path, ms: int, loop=0) -> str:
+    """The (N, 3, H, W) batch `frames` (values in [0, 1]) as one animated GIF at `path`, frame b shown for `ms` milliseconds
+    in batch order.  `loop` = 0 repeats for ever (a closed loop of `loop_seeds`), None plays once."""
+    arr = torch.as_tensor(frames).detach().to("cpu", torch.float32)
+    if arr.dim() != 4 or arr.shape[1] != 3 or arr.shape[0] < 1:
+        raise ValueError(f"write_gif: frames must be (N, 3, H, W), got {tuple(arr.shape)}")
+    if int(ms) < 1:
+        raise ValueError(f"write_gif: {ms} ms per frame")
+    pics = [Image.fromarray((f.clamp(0, 1).mul(255).add(0.5).to(torch.uint8).permute(1, 2, 0).numpy())) for f in arr]
+    kw = {} if loop is None else {"loop": int(loop)}
+    pics[0].save(str(path), format="GIF", save_all=True, append_images=pics[1:], duration=int(ms), disposal=1, **kw)
+    return str(path)
+
+
 def _disk(radius: int) -> np.ndarray:
     """skimage.morphology.disk: (2r+1)^2 footprint of the pixels within Euclidean distance r."""
     yy, xx = np.mgrid[-radius:radius + 1, -radius:radius + 1]

@@ -14,6 +14,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
                                 (no reference line: padding_mode='circular' on its nn.Conv2d's)
   per-sample noise seeds     -> sinddm_sample_chain_seeds / sinddm_normal_fill_samples   (`sample_seeds`; no reference
                                 line: the reference never seeds its generator)
+  seed blending (`seed_mix`) -> sinddm_sample_chain_mix / sinddm_normal_fill_mix   (no reference line: a sample's draw as
+                                a fixed combination of the draws of K seeds -- interpolations and loops between samples)
   few-step sampling          -> strided step scalars (`step_coefs_to`) through every chain entry; `solver_order = 2`:
                                 sinddm_sample_chain_solver / sinddm_reverse_step_ms   (no reference line: the reference
                                 evaluates the network at every level)
@@ -157,6 +159,76 @@ def vary_seeds(seeds, from_scale: int, n_scales: int):
         used.add(z >> 1)
         derived.append(z >> 1)
     return [list(seeds) if s < from_scale else list(derived) for s in range(n_scales)]
+
+
+# ---- seed blending (include/sinddm_hip.h "seed blending") ---------------------------------------------------
+# A mix is a pair (keys, weights) of [B][K] nested sequences: sample b's every N(0,1) draw is sum_k weights[b][k] * (the draw
+# of seed keys[b][k]), which is N(0,1) again when the row's squared weights add up to 1.  The helpers below are host code.
+MIX_TOL = 1e-5                # |sum_k w^2 - 1| a row of `seed_mix` may have
+
+
+def _check_mix(keys, weights, what: str = "seed_mix"):
+    """The validated ([B][K] ints, [B][K] floats) of one mix table."""
+    keys = [list(r.tolist() if isinstance(r, (np.ndarray, torch.Tensor)) else r) for r in keys]
+    weights = [list(r.tolist() if isinstance(r, (np.ndarray, torch.Tensor)) else r) for r in weights]
+    if len(keys) != len(weights) or not keys:
+        raise ValueError(f"{what}: {len(keys)} rows of seeds for {len(weights)} rows of weights")
+    K = len(keys[0])
+    if not 1 <= K <= _lib.MIX_MAX:
+        raise ValueError(f"{what}: {K} seeds per sample, 1 .. {_lib.MIX_MAX} can be blended")
+    out_k, out_w = [], []
+    for kr, wr in zip(keys, weights):
+        if len(kr) != K or len(wr) != K:
+            raise ValueError(f"{what}: every row holds the same number of seeds and weights ({K})")
+        out_k.append(_check_seed_row(kr, what))
+        wr = [float(v) for v in wr]
+        if not all(math.isfinite(v) for v in wr):
+            raise ValueError(f"{what}: a weight is not finite: {wr}")
+        if abs(sum(v * v for v in wr) - 1.0) > MIX_TOL:
+            raise ValueError(f"{what}: the squared weights of a row must add up to 1 (unit variance), got {wr}")
+        out_w.append(wr)
+    return out_k, out_w
+
+
+def interp_seeds(a: int, b: int, frames: int):
+    """The mix that walks from sample `a` (frame 0) to sample `b` (the last frame) on a quarter circle: K = 2, weights
+    (cos th_i, sin th_i), th_i = i / (frames - 1) * pi / 2; the end rows are exactly (1, 0) and (0, 1)."""
+    a, b = _check_seed_row([a, b], "interp_seeds")
+    frames = int(frames)
+    if frames < 2:
+        raise ValueError(f"interp_seeds: {frames} frames, at least 2 are needed")
+    w = []
+    for i in range(frames):
+        th = i / (frames - 1) * (math.pi / 2)
+        w.append([1.0, 0.0] if i == 0 else [0.0, 1.0] if i == frames - 1 else [math.cos(th), math.sin(th)])
+    return [[a, b] for _ in range(frames)], w
+
+
+def loop_seeds(base: int, a: int, b: int, frames: int, radius: float = 0.5):
+    """The mix of a closed loop around sample `base`: K = 3, weights (sqrt(1 - r^2), r cos ph_i, r sin ph_i),
+    ph_i = 2 pi i / frames -- frame `frames` would be frame 0 again."""
+    base, a, b = _check_seed_row([base, a, b], "loop_seeds")
+    frames, r = int(frames), float(radius)
+    if frames < 1:
+        raise ValueError(f"loop_seeds: {frames} frames")
+    if not 0.0 <= r <= 1.0:
+        raise ValueError(f"loop_seeds: radius {radius} is outside [0, 1]")
+    c = math.sqrt(1.0 - r * r)
+    return ([[base, a, b] for _ in range(frames)],
+            [[c, r * math.cos(2 * math.pi * i / frames), r * math.sin(2 * math.pi * i / frames)] for i in range(frames)])
+
+
+def mix_from_scale(mix, from_scale: int, n_scales: int):
+    """The [n_scales][B][K] form of a mix in which the scales below `from_scale` use each row's FIRST seed alone (weight 1,
+    the others 0) and the scales from `from_scale` on the mix itself: a shared coarse layout -- where the rows share their
+    first seed -- with detail that moves."""
+    keys, w = _check_mix(*mix, what="mix_from_scale")
+    from_scale, n_scales = int(from_scale), int(n_scales)
+    if not 0 <= from_scale <= n_scales:
+        raise ValueError(f"mix_from_scale: from_scale {from_scale} is outside [0, {n_scales}]")
+    first = [[1.0] + [0.0] * (len(r) - 1) for r in w]
+    return ([[list(r) for r in keys] for _ in range(n_scales)],
+            [[list(r) for r in (first if s < from_scale else w)] for s in range(n_scales)])
 
 
 _AUX: Dict[int, "torch.cuda.Stream"] = {}
@@ -484,9 +556,10 @@ class _ChainCall:
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
         self.aux = _aux_stream(x.device) if d.two_streams else None
 
-    def call(self, i0, k, seed, noise=None, sid0=0, seeds_dev=None, jump_noise=None):
+    def call(self, i0, k, seed, noise=None, sid0=0, seeds_dev=None, jump_noise=None, mix_dev=None):
         """Steps [i0, i0 + k) of the run: `noise` / `jump_noise` recorded draws of exactly these steps, or the in-kernel draws
-        of `seeds_dev` (one seed per sample) or `seed`, at stream ids sid0 + 0 ... k - 1."""
+        of `seeds_dev` (one seed per sample), of `mix_dev` ((B, K) int64 seeds, (B, K) float32 weights: a blend per sample)
+        or of `seed`, at stream ids sid0 + 0 ... k - 1."""
         x, net, ref = self.x, self.net, (lambda o: C.byref(o) if o is not None else None)
         self.opts.noise = _lib.ptr(noise)
         if self.kopts is not None:
@@ -501,8 +574,12 @@ class _ChainCall:
                 net.dim_arg, x.shape[0], self.Hc, self.Wc, self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr(x.device), self.aux,
                 C.byref(in_alt), C.byref(self.opts), *self.halo, ref(self.kopts), _lib.ptr(seeds_dev), ref(self.ropts),
                 ref(self.lopts), ref(self.bopts)]
-        if self.sopts is not None:                             # (the multistep run: the one entry that can say it)
+        if self.sopts is not None:
             self.sopts.q = _at(self.q, i0, C.c_float)
+        if mix_dev is not None:                                # (the blended run: the one entry that can say it)
+            mopts = _lib.MixOpts(_lib.ptr(mix_dev[0]), _lib.ptr(mix_dev[1]), int(mix_dev[0].shape[1]))
+            _lib.check(self.lib.sinddm_sample_chain_mix(*args, ref(self.sopts), C.byref(mopts)), "sinddm_sample_chain_mix")
+        elif self.sopts is not None:                           # (the multistep run: the one entry that can say it)
             _lib.check(self.lib.sinddm_sample_chain_solver(*args, C.byref(self.sopts)), "sinddm_sample_chain_solver")
         else:
             _lib.check(self.lib.sinddm_sample_chain_batch(*args), "sinddm_sample_chain_batch")
@@ -643,6 +720,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # (seed of b, noise_stream_id, element index inside the sample) alone: the sample does not depend on its batch, its
         # position in it, the two-stream split or the rank that runs it.  Not together with `noise_fn`.
         self.sample_seeds = None
+        # seed blending: None, or (keys, weights) -- two [B][K] nested sequences, or [n_scales][B][K] like `sample_seeds`
+        # (`mix_from_scale`) -- K <= 4 seeds in [0, 2^63) and K finite weights per sample whose squares add up to 1.  Every
+        # N(0,1) draw of sample b is then  sum_k weights[b][k] * (the draw sample_seeds = keys[b][k] would give):  N(0,1)
+        # again, and a function of the row alone, like a seeded sample.  Rows on an arc interpolate between two samples
+        # (`interp_seeds`), rows on a circle make a closed loop (`loop_seeds`).  Not together with `sample_seeds` or
+        # `noise_fn`; not with CLIP guidance.
+        self.seed_mix = None
         # RePaint's resampling for known-region sampling: None or (R, J), both >= 1.  At anchor levels (multiples of J) the run
         # jumps back up by J levels and comes down again, until the stretch has been walked R times (the schedule:
         # functions.resample_schedule; the upward move: sinddm_sample_chain_resample).  R = 1 is None.  A sampling option,
@@ -701,6 +785,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         ss = self.sample_seeds
         if ss is None:
             return None
+        if self.seed_mix is not None:
+            raise ValueError("sample_seeds and seed_mix are both set: two noise sources")
         if self.noise_fn is not None:
             raise ValueError("sample_seeds and noise_fn are both set: two noise sources")
         if isinstance(ss, (torch.Tensor, np.ndarray)):
@@ -717,6 +803,49 @@ class MultiScaleGaussianDiffusion(nn.Module):
             raise ValueError(f"sample_seeds holds {len(row)} seeds for a batch of {int(B)}")
         return _check_seed_row(row)
 
+    def _mix_for(self, s: int, B: int):
+        """The (keys, weights) tables of scale s from `seed_mix` (validated, [B][K] each), or None when unset."""
+        mx = self.seed_mix
+        if mx is None:
+            return None
+        if self.sample_seeds is not None:
+            raise ValueError("seed_mix and sample_seeds are both set: two noise sources")
+        if self.noise_fn is not None:
+            raise ValueError("seed_mix and noise_fn are both set: two noise sources")
+        if self.clip_guided_sampling:
+            raise NotImplementedError("seed_mix with CLIP-guided sampling")
+        if not isinstance(mx, (tuple, list)) or len(mx) != 2:
+            raise ValueError("seed_mix is a pair (keys, weights)")
+        keys, w = (v.tolist() if isinstance(v, (np.ndarray, torch.Tensor)) else list(v) for v in mx)
+
+        def depth(v):
+            return 1 + depth(v[0]) if isinstance(v, (list, tuple, np.ndarray, torch.Tensor)) and len(v) > 0 else 0
+        if depth(keys) != depth(w) or depth(keys) not in (2, 3):
+            raise ValueError("seed_mix: keys and weights are [B][K] or [n_scales][B][K] nested sequences of one shape")
+        if depth(keys) == 3:
+            if len(keys) != self.n_scales or len(w) != self.n_scales:
+                raise ValueError(f"seed_mix has {len(keys)} / {len(w)} tables for {self.n_scales} scales")
+            i = min(int(s), self.n_scales - 1)                # (custom sizes past the pyramid sample with the finest scale's table)
+            keys, w = keys[i], w[i]
+        if len(keys) != int(B) or len(w) != int(B):
+            raise ValueError(f"seed_mix holds {len(keys)} rows for a batch of {int(B)}")
+        return _check_mix(keys, w)
+
+    @staticmethod
+    def _mix_tensors(mix, device):
+        """The device tables of a validated mix: (B, K) int64 seeds, (B, K) float32 weights."""
+        return (torch.tensor(mix[0], dtype=torch.int64, device=device), torch.tensor(mix[1], dtype=torch.float32, device=device))
+
+    def _mixed_normal(self, mix, shape, sid: int, device) -> torch.Tensor:
+        """(B, ...) N(0,1): slice b = the blend of sinddm_normal_fill(numel per sample, keys[b][k], sid)."""
+        lib = _lib.load()
+        shape = tuple(int(v) for v in shape)
+        z = torch.empty(shape, dtype=torch.float32, device=device)
+        kd, wd = self._mix_tensors(mix, device)
+        _lib.check(lib.sinddm_normal_fill_mix(_lib.ptr(z), shape[0], z.numel() // shape[0], _lib.ptr(kd), _lib.ptr(wd),
+                                              int(kd.shape[1]), int(sid), _lib.stream_ptr(z.device)), "sinddm_normal_fill_mix")
+        return z
+
     def _seeded_normal(self, seeds, shape, sid: int, device) -> torch.Tensor:
         """(B, ...) N(0,1): slice b = sinddm_normal_fill(numel per sample, seeds[b], sid)."""
         lib = _lib.load()
@@ -731,16 +860,20 @@ class MultiScaleGaussianDiffusion(nn.Module):
         """One N(0,1) draw of the sampler: `kind` 'init' / 'renoise' / 'step' / 'jump' (`pos` = the step's position in its
         run; 'jump' is the second draw of the jump that follows that step)."""
         seeds = self._seeds_for(s, shape[0])
-        if seeds is not None:
+        mix = self._mix_for(s, shape[0])
+        if seeds is not None or mix is not None:
+            # (a blend is drawn like its seeds would be: same stream ids, same extended size, the blend of the slices)
             sid = noise_stream_id(s, kind, pos)
+            fill = (lambda shp: self._seeded_normal(seeds, shp, sid, device)) if seeds is not None else \
+                   (lambda shp: self._mixed_normal(mix, shp, sid, device))
             hy, hx = self._tile_halo()
             if kind in ("step", "jump") and (hy or hx):
                 # the tiled chain draws over the EXTENDED sample and discards the halo's draws: take the centre
                 H, W = int(shape[-2]), int(shape[-1])
-                z = self._seeded_normal(seeds, tuple(shape[:-2]) + (H + 2 * hy, W + 2 * hx), sid, device)
+                z = fill(tuple(shape[:-2]) + (H + 2 * hy, W + 2 * hx))
                 z = z[..., hy:hy + H, hx:hx + W].contiguous()
             else:
-                z = self._seeded_normal(seeds, shape, sid, device)
+                z = fill(shape)
             if self.draw_log is not None:
                 self.draw_log.append((kind, int(s), int(t), z.clone()))
             return z
@@ -1210,12 +1343,14 @@ class MultiScaleGaussianDiffusion(nn.Module):
                          keep their shape with those levels as the t list.  `solver_order` = 2: every step runs unfused and
                          ends in the multistep kernel (sinddm_sample_chain_solver).  Not with `resample`; order 2 not with
                          `layout_maps`.
-        The noise is one of three:
+        The noise is one of four:
           `noise_fn` + `chain_noise`   the draws the step-by-step loop would fetch, in its order ('step' per step, 'jump' per
                          jump), handed over as buffers of at most CHAIN_NOISE_BYTES: one call per piece.
           `sample_seeds` sample b's step at position i of the run draws sinddm_normal_fill(3 H W, seed_b,
                          noise_stream_id(s, 'step', i)) in the step kernel; torch's generator is not touched.  `draw_log`:
                          ("chain_seeds", s, seeds, t list), or ("chain_resample", s, seeds, expanded t list, jump targets).
+          `seed_mix`     the same with the blend of the row's seeds in place of the one seed's draw
+                         (sinddm_sample_chain_mix).  `draw_log`: ("chain_mix", s, (keys, weights), t list, jump targets or None).
           otherwise      one 62-bit seed from torch's CPU generator keys the in-kernel draws.  `draw_log`: ("chain", s, seed,
                          t list), tiled ("chain_tile", ..., (hy, hx)), resampled ("chain_resample", s, seed, ..., jump targets)."""
         t_seq = [int(t) for t in t_seq]
@@ -1243,6 +1378,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
             from .functions import resample_schedule
             t_seq, jump_to = resample_schedule(t_seq, *rs_cfg)
         sseeds = self._seeds_for(s, img.shape[0])
+        mix = self._mix_for(s, img.shape[0])
         keep = self._keep_entry(s, img)
         roi = bool(self.roi_guided_sampling and s < self.n_scales - 1)     # models.py:430-431
         fast = ((self.noise_fn is None or self.chain_noise) and isinstance(self.denoise_fn, SinDDMNet)
@@ -1289,6 +1425,12 @@ class MultiScaleGaussianDiffusion(nn.Module):
                                      else ("chain_seeds", s, list(sseeds), list(t_seq)))
             run.call(0, n, 0, sid0=noise_stream_id(s, "step", 0),
                      seeds_dev=torch.tensor(sseeds, dtype=torch.int64, device=x.device))
+            return run.result()
+        if mix is not None:
+            if self.draw_log is not None:
+                # (draw i of sample b is the blend of sinddm_normal_fill(3 H W, keys[b][k], noise_stream_id(s, 'step', i)))
+                self.draw_log.append(("chain_mix", s, (mix[0], mix[1]), list(t_seq), list(jump_to) if jump_to is not None else None))
+            run.call(0, n, 0, sid0=noise_stream_id(s, "step", 0), mix_dev=self._mix_tensors(mix, x.device))
             return run.result()
         # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
         # sample, seeding only the CUDA generator (torch.cuda.manual_seed) does not

@@ -294,7 +294,8 @@ class MultiscaleTrainer(object):
     @torch.no_grad()
     def sample_scales(self, scale_mul=None, batch_size=16, custom_sample=False, custom_image_size_idxs=None,
                       custom_scales=None, image_name='', start_noise=True, custom_t_list=None, desc=None,
-                      save_unbatched=True, save_images=True, seeds=None, vary_from_scale=None) -> List[torch.Tensor]:
+                      save_unbatched=True, save_images=True, seeds=None, vary_from_scale=None,
+                      seed_mix=None) -> List[torch.Tensor]:
         """Drive the sampler over all scales (behaviour of reference trainer.py:226-285).  Under torch.distributed the
         batch is sharded over ranks as independent chains and gathered with one all-gather per scale (RCCL over xGMI
         on MI355X); returns the list of per-scale (global) sample batches.
@@ -302,9 +303,13 @@ class MultiscaleTrainer(object):
         call; a rank takes the seeds of its own shard, so the gathered batch holds the images a single process makes, in
         the same order).  `vary_from_scale` = S: scales >= S use seeds derived per sample (`models.vary_seeds`).
         Per-sample conditioning on `ema_model` (maps with a leading batch dimension, `layout_gain`, `roi_bbs_batch`) is GLOBAL
-        too: `batch_size` rows, of which a rank takes its own shard's for the duration of the call (`dist.shard_rows`)."""
+        too: `batch_size` rows, of which a rank takes its own shard's for the duration of the call (`dist.shard_rows`).
+        `seed_mix`: in place of `seeds`, the GLOBAL blend tables (keys, weights), [batch_size][K] or
+        [n_scales][batch_size][K] (`ema_model.seed_mix` for the duration of the call; `models.interp_seeds`, `loop_seeds`,
+        `mix_from_scale`): sample b is frame b, and a rank takes the rows of its own shard like its seeds."""
         em = self.ema_model
         local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=True)
+        local_mix = self._local_mix(seed_mix, seeds, batch_size, sharded=True)
         local_maps = self._local_batch_maps(batch_size)
         # --- what to run: one (scale, size index, start timestep) triple per stage ---
         scales = list(range(self.n_scales)) if custom_scales is None else list(custom_scales)
@@ -330,10 +335,12 @@ class MultiscaleTrainer(object):
                              'without chains (every rank must join the all-gather)')
         mine = sdist.local_batch(batch_size)
         per_scale, cur, shown = [], None, None
-        prev_seeds = em.sample_seeds
+        prev_seeds, prev_mix = em.sample_seeds, em.seed_mix
         prev_maps = {k: getattr(em, k) for k in local_maps}
         if local_seeds is not None:
             em.sample_seeds = local_seeds
+        if local_mix is not None:
+            em.seed_mix = local_mix
         for k, v in local_maps.items():
             setattr(em, k, v)
         try:
@@ -352,7 +359,7 @@ class MultiscaleTrainer(object):
                     shown = (whole + 1) * 0.5
                     save_image(shown, str(out_dir / t_tag) + f'_out_s{stage}_{tag}_sm_{stretch[0]}_{stretch[1]}.png', nrow=4)
         finally:
-            em.sample_seeds = prev_seeds
+            em.sample_seeds, em.seed_mix = prev_seeds, prev_mix
             for k, v in prev_maps.items():
                 setattr(em, k, v)
         if writer and save_unbatched and shown is not None:
@@ -403,6 +410,32 @@ class MultiscaleTrainer(object):
             rows = [sdist.shard_seeds(r) for r in rows]
         return rows[0] if vary_from_scale is None else rows
 
+    def _local_mix(self, seed_mix, seeds, batch_size, sharded):
+        """`ema_model.seed_mix` of a driver call: None without `seed_mix`; else the global tables (checked against
+        `batch_size`, every row validated) and -- for the drivers that shard the batch over ranks -- cut to this rank's rows
+        with `dist.shard_rows`, before anything else reads them."""
+        from .models import _check_mix
+        if seed_mix is None:
+            return None
+        if seeds is not None:
+            raise ValueError('seeds and seed_mix are both given: two noise sources')
+        if not isinstance(seed_mix, (tuple, list)) or len(seed_mix) != 2:
+            raise ValueError('seed_mix is a pair (keys, weights)')
+        keys, w = (v.tolist() if isinstance(v, (np.ndarray, torch.Tensor)) else v for v in seed_mix)
+        per_scale = len(keys) > 0 and len(keys[0]) > 0 and isinstance(keys[0][0], (list, tuple, np.ndarray, torch.Tensor))
+        tabs = list(zip(keys, w)) if per_scale else [(keys, w)]
+        if per_scale and (len(keys) != self.n_scales or len(w) != self.n_scales):
+            raise ValueError(f'seed_mix has {len(keys)} / {len(w)} tables for {self.n_scales} scales')
+        out = []
+        for k, v in tabs:
+            k, v = _check_mix(k, v)
+            if len(k) != int(batch_size):
+                raise ValueError(f'seed_mix holds {len(k)} rows for batch_size={int(batch_size)}')
+            out.append((sdist.shard_rows(k), sdist.shard_rows(v)) if sharded else (k, v))
+        if not per_scale:
+            return out[0]
+        return [k for k, _ in out], [v for _, v in out]
+
     # ---- application drivers of the reference that run entirely on the hot path (SURVEY 8(f) row 4) ----
     def _i2i_source(self, input_folder, input_file, mask, hist_ref_path, image_name, use_hist, auto_scale, mode, device):
         """Host-side preparation of harmonization / style transfer: the (optionally shrunk, optionally histogram
@@ -428,16 +461,17 @@ class MultiscaleTrainer(object):
     @torch.no_grad()
     def image2image(self, input_folder='', input_file='', mask='', hist_ref_path='', image_name='', start_s=1,
                     custom_t=None, batch_size=16, scale_mul=(1, 1), device=None, use_hist=False, save_unbatched=True,
-                    auto_scale=None, mode=None, save_images=True, seeds=None, vary_from_scale=None):
+                    auto_scale=None, mode=None, save_images=True, seeds=None, vary_from_scale=None, seed_mix=None):
         """Harmonization / style transfer (behaviour of reference trainer.py:287-362): the input image is re-noised at
         scale `start_s` to `custom_t[start_s]` and denoised through the remaining scales by the trained model; in
         harmonization mode the result is pasted into the input through the dilated mask.  Returns the per-scale sample
-        batches (the reference only writes PNGs).  `seeds` / `vary_from_scale`: as in `sample_scales` (this driver does
-        not shard the batch: every process runs all `batch_size` chains)."""
+        batches (the reference only writes PNGs).  `seeds` / `vary_from_scale` / `seed_mix`: as in `sample_scales` (this
+        driver does not shard the batch: every process runs all `batch_size` chains)."""
         import os
         device = self.device if device is None else device
         em = self.ema_model
         local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=False)
+        local_mix = self._local_mix(seed_mix, seeds, batch_size, sharded=False)
         t_starts = em.num_timesteps_ideal if custom_t is None else custom_t
         src, keep = self._i2i_source(input_folder, input_file, mask, hist_ref_path, image_name, use_hist, auto_scale,
                                      mode, device)
@@ -453,9 +487,11 @@ class MultiscaleTrainer(object):
             out_dir.mkdir(parents=True, exist_ok=True)
         last = self.n_scales - 1
         outs, shown = [], None
-        prev_seeds = em.sample_seeds
+        prev_seeds, prev_mix = em.sample_seeds, em.seed_mix
         if local_seeds is not None:
             em.sample_seeds = local_seeds
+        if local_mix is not None:
+            em.seed_mix = local_mix
         try:
             for s in range(start_s, self.n_scales):
                 # target size of this scale: the (possibly shrunk) input divided by scale_factor^(scales still to go)
@@ -471,7 +507,7 @@ class MultiscaleTrainer(object):
                     save_image(shown, str(out_dir / f'{stem}_i2i_s_{s}_t_{t_tag}_hist_{"on" if use_hist else "off"}_{stamp}.png'),
                                nrow=4)
         finally:
-            em.sample_seeds = prev_seeds
+            em.sample_seeds, em.seed_mix = prev_seeds, prev_mix
         if save_images and save_unbatched:
             single_dir = Path(str(self.results_folder / f'unbatched_i2i_s{start_s}_t_{t_tag}_{stamp}'))
             single_dir.mkdir(parents=True, exist_ok=True)
@@ -483,7 +519,7 @@ class MultiscaleTrainer(object):
     @torch.no_grad()
     def roi_guided_sampling(self, custom_t_list=None, target_roi=None, roi_bb_list=None, save_unbatched=False,
                             batch_size=4, scale_mul=(1, 1), save_images=True, seeds=None, vary_from_scale=None,
-                            per_sample=False):
+                            per_sample=False, seed_mix=None):
         """ROI guided generation (trainer.py:436-454): at every scale but the finest the predicted clean image is
         pulled (eta = 0.8) towards a patch of the training image inside the given boxes; the blend runs inside the
         step kernels of the sampler's chain call (the edit maps of `sinddm_chain_opts`: one library call per scale,
@@ -507,7 +543,7 @@ class MultiscaleTrainer(object):
                                       custom_t_list=custom_t_list,
                                       desc=f'roi_{str(datetime.datetime.now()).replace(":", "_")}',
                                       save_unbatched=save_unbatched, start_noise=True, save_images=save_images,
-                                      seeds=seeds, vary_from_scale=vary_from_scale)
+                                      seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix)
         finally:
             em.roi_guided_sampling = False
             em.roi_bbs_batch = None
@@ -529,7 +565,7 @@ class MultiscaleTrainer(object):
 
     @torch.no_grad()
     def inpaint(self, mask, batch_size=16, hard=True, custom_t_list=None, save_unbatched=False, save_images=True,
-                seeds=None, vary_from_scale=None, resample=1, jump_length=1):
+                seeds=None, vary_from_scale=None, resample=1, jump_length=1, seed_mix=None):
         """Fill a hole in the training image: `mask` is (H, W) at the finest scale's size, 1 = keep the training image's
         pixel, 0 = generate.  At every scale the known image is that scale's training image and the mask comes from
         `functions.keep_mask_pyramid` (`hard`: a coarse pixel is kept only if its whole footprint is known); after every
@@ -553,11 +589,11 @@ class MultiscaleTrainer(object):
                 for s in range(self.n_scales)}
         return self._sample_kept(maps, 'inpaint', resample=resample, jump_length=jump_length, batch_size=batch_size,
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
-                                 seeds=seeds, vary_from_scale=vary_from_scale)
+                                 seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix)
 
     @torch.no_grad()
     def outpaint(self, scale_mul, anchor=(0.5, 0.5), batch_size=16, custom_t_list=None, save_unbatched=False,
-                 save_images=True, seeds=None, vary_from_scale=None, resample=1, jump_length=1):
+                 save_images=True, seeds=None, vary_from_scale=None, resample=1, jump_length=1, seed_mix=None):
         """Grow the canvas around the training image: at every scale the sample has `target_size(s, scale_mul)`, the
         scale's own training image sits unresampled at int(anchor * (canvas - image)) and is kept (mask 1 on that
         rectangle), the rest is generated.  `scale_mul` < 1 on an axis is a ValueError.  `resample` / `jump_length`: as for
@@ -588,12 +624,12 @@ class MultiscaleTrainer(object):
         return self._sample_kept(maps, 'outpaint', resample=resample, jump_length=jump_length, scale_mul=tuple(scale_mul),
                                  batch_size=batch_size,
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
-                                 seeds=seeds, vary_from_scale=vary_from_scale)
+                                 seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix)
 
     # ---- layout conditioning: redraw a rough picture in the training image's texture (no reference counterpart) ----
     @torch.no_grad()
     def paint2image(self, layout, batch_size=16, down=8, strength=1.0, t_min=0, scales=None, scale_mul=(1, 1), seeds=None,
-                    vary_from_scale=None, custom_t_list=None, save_unbatched=False, save_images=True):
+                    vary_from_scale=None, custom_t_list=None, save_unbatched=False, save_images=True, seed_mix=None):
         """Paint-to-image: `layout` is a (3, H, W) picture in [-1, 1] at the finest target size
         (`ema_model.target_size(n_scales - 1, scale_mul)`) -- a scribble, a colour sketch, a blurred photo, another sample.
         At every reverse step with t >= `t_min` the low spatial frequencies of the predicted clean image are pulled towards
@@ -629,7 +665,8 @@ class MultiscaleTrainer(object):
             return self.sample_scales(scale_mul=tuple(scale_mul), custom_sample=False, image_name='', start_noise=True,
                                       desc=f'paint2image_{str(datetime.datetime.now()).replace(":", "_")}',
                                       batch_size=batch_size, custom_t_list=custom_t_list, save_unbatched=save_unbatched,
-                                      save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale)
+                                      save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale,
+                                      seed_mix=seed_mix)
         finally:
             em.layout_maps, em.layout_down, em.layout_strength, em.layout_t_min = None, {}, 1.0, 0
             em.layout_gain = None
