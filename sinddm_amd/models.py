@@ -38,6 +38,7 @@ from torch import nn
 
 from . import _lib
 from .functions import cosine_beta_schedule, default, exists, extract, noise_like
+from .sampler import RunPlan, pack_steps, refuse
 from .synth import net_param_shapes
 
 
@@ -472,87 +473,48 @@ class SinDDMNet(nn.Module):
 # --------------------------------------------------------------------------------------------
 # diffusion process
 # --------------------------------------------------------------------------------------------
-def _at(arr, i0: int, ctype, per: int = 1):
-    """&arr[per * i0] of a ctypes array of `ctype`, as the pointer a call takes (None stays NULL)."""
-    return None if arr is None else C.cast(C.addressof(arr) + per * i0 * C.sizeof(ctype), C.POINTER(ctype))
-
-
 class _ChainCall:
-    """The buffers and option blocks of one chain run of `MultiScaleGaussianDiffusion._run_steps`: the steps `t_seq` (already
-    expanded by `jump_to`) of scale s on `img`, through sinddm_sample_chain_batch -- the entry that can express every option;
-    one that is off goes in as NULL, which is the call without it, launch for launch.  Every tensor and ctypes array the
-    library reads through a raw pointer is an attribute here, so it lives as long as the object."""
+    """The buffers and option blocks of one chain run of `MultiScaleGaussianDiffusion._run_steps`: the steps of `plan` (a
+    sampler.RunPlan) on `img`, through sinddm_sample_chain_batch -- the entry that can express every option; one that is off
+    goes in as NULL, which is the call without it, launch for launch.  Every tensor and ctypes array the library reads through
+    a raw pointer is an attribute here, so it lives as long as the object."""
 
-    def __init__(self, d, img, s, t_seq, jump_to, *, roi, keep, lay, lay_g, lands=None, q=None):
-        # `lands`: the level each step lands on (a strided run; None: t - 1 everywhere, the prebuilt table); `q`: the
-        # multistep factors of a second-order run -- the run then goes through sinddm_sample_chain_solver with a history buffer
-        self.lib, self.net, self.s = _lib.load(), d.denoise_fn, s
-        hy, hx = self.halo = d._tile_halo()
+    def __init__(self, d, plan, img):
+        self.lib, self.net, self.s, self.plan = _lib.load(), d.denoise_fn, plan.s, plan
+        hy, hx = self.halo = plan.halo
         tiled = self.tiled = bool(hy or hx)
         wrap = (lambda t: d._wrap_pad(t, hy, hx)) if tiled else (lambda t: t)
         self.Hc, self.Wc = int(img.shape[2]), int(img.shape[3])    # the sample's own size; H, W below: the buffers' size
         x = self.x = d._wrap_pad(img, hy, hx) if tiled else img.contiguous().clone()
         self.x_alt, self.eps = torch.empty_like(x), torch.empty_like(x)
         B, _, H, W = x.shape
-        tab = d._coef_table(s)
-        n = len(t_seq)
-        if lands is None:
-            self.coefs = (_lib.StepCoefs * n)(*[tab[t] for t in t_seq])
-        else:
-            self.coefs = (_lib.StepCoefs * n)(*[d.step_coefs_to(t, u, s, eta=d.eta) for t, u in zip(t_seq, lands)])
-        self.tl = (C.c_int * n)(*t_seq)
-        self.xt = None
-        if self.coefs[0].mode != 0 or self.coefs[n - 1].mode != 0:
-            xt = d.img_prev_upsample
-            if xt is None:
-                raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
-            if xt.shape != img.shape or xt.dtype != x.dtype or xt.device != x.device:
-                # (the library takes raw pointers: a mismatching x-tilde would be read out of bounds)
-                raise _lib.SinddmError(f"img_prev_upsample {tuple(xt.shape)} {xt.dtype} {xt.device} does not match the "
-                                       f"running sample {tuple(img.shape)} {x.dtype} {x.device}")
-            self.xt = d._wrap_pad(xt, hy, hx) if tiled else xt.contiguous()
+        xt = plan.xt
+        if xt is not None and (xt.shape != img.shape or xt.dtype != x.dtype or xt.device != x.device):
+            # (the library takes raw pointers: a mismatching x-tilde would be read out of bounds)
+            raise _lib.SinddmError(f"img_prev_upsample {tuple(xt.shape)} {xt.dtype} {xt.device} does not match the "
+                                   f"running sample {tuple(img.shape)} {x.dtype} {x.device}")
+        self.xt = wrap(xt) if xt is not None else None
         self.packed = self.net.packed_weights()
         self.ws = _workspace(x.device, self.lib.sinddm_workspace_bytes(self.net.dim, B, H, W))
-        self.opts = _lib.ChainOpts()
-        if roi:
-            ew, ec = d.roi_edit_maps(s, self.Hc, self.Wc, x.device)
-            if ew.dim() == 3 and ew.shape[0] != B:                         # (raw pointers: B slices are read)
-                raise ValueError(f"roi_bbs_batch has {ew.shape[0]} box lists, the batch {B} samples")
-            self.edit = ew, ec = wrap(ew), wrap(ec)
-            self.opts.edit_w, self.opts.edit_c = _lib.ptr(ew), _lib.ptr(ec)
-        self.kopts = self.ab = None
-        if keep is not None:
-            self.keep = km, kx = wrap(keep[0]), wrap(keep[1])
-            ab_tab = d._keep_ab_table()
-            # (row l + 1 holds the forward scalars of level l, row 0 those of the clean image)
-            self.ab = (C.c_float * (2 * n))(*[float(v) for l in (lands if lands is not None else [t - 1 for t in t_seq])
-                                              for v in ab_tab[l + 1]])
-            self.kopts = _lib.KeepOpts()
-            self.kopts.mask, self.kopts.x0 = _lib.ptr(km), _lib.ptr(kx)
-        self.ropts = self.jumps = None
-        if jump_to is not None:
-            jt = d._jump_table(s)
-            self.jumps = (_lib.JumpCoefs * n)(*[_lib.JumpCoefs(0, 0.0, 0.0, 0.0) if l2 is None
-                                                else _lib.JumpCoefs(1, *jt(t - 1, l2)) for t, l2 in zip(t_seq, jump_to)])
-            self.ropts = _lib.ResampleOpts()
-        self.lopts = self.garr = self.bopts = None
-        self.gain = d._layout_gain_for(B, x.device) if lay is not None else None
-        per = (int(roi and ew.dim() == 3), int(keep is not None and km.dim() == 3), int(keep is not None and kx.dim() == 4),
-               int(lay is not None and lay[0].dim() == 4))
-        if any(per) or self.gain is not None:
-            self.bopts = _lib.BatchOpts(*per, _lib.ptr(self.gain))
-        if lay is not None:
-            self.lay_map = wrap(lay[0])
-            self.lay_delta = torch.empty(B * 3 * (-(-self.Hc // lay[1])) * (-(-self.Wc // lay[1])), dtype=x.dtype, device=x.device)
-            self.garr = (C.c_float * n)(*lay_g)
-            self.lopts = _lib.LayoutOpts()
-            self.lopts.layout, self.lopts.down, self.lopts.delta = _lib.ptr(self.lay_map), lay[1], _lib.ptr(self.lay_delta)
-        self.sopts = self.q = self.hist = None
-        if q is not None:
-            self.q = (C.c_float * n)(*q)
+        # the option blocks: the maps (wrapped under a halo) go in here, the per-step host arrays with each call
+        self.edit = [wrap(m) for m in plan.roi] if plan.roi is not None else (None, None)
+        self.opts = _lib.ChainOpts(_lib.ptr(self.edit[0]), _lib.ptr(self.edit[1]), None)
+        self.kopts = self.lopts = self.bopts = self.sopts = self.hist = None
+        if plan.keep is not None:
+            self.keep = [wrap(m) for m in plan.keep]
+            self.kopts = _lib.KeepOpts(_lib.ptr(self.keep[0]), _lib.ptr(self.keep[1]), None)
+        self.ropts = _lib.ResampleOpts() if plan.jump_to is not None else None
+        self.gain = torch.from_numpy(plan.gain.copy()).to(x.device) if plan.gain is not None else None
+        if any(plan.per) or self.gain is not None:
+            self.bopts = _lib.BatchOpts(*plan.per, _lib.ptr(self.gain))
+        if plan.lay is not None:
+            N = plan.lay[1]
+            self.lay_map = wrap(plan.lay[0])
+            self.lay_delta = torch.empty(B * 3 * (-(-self.Hc // N)) * (-(-self.Wc // N)), dtype=x.dtype, device=x.device)
+            self.lopts = _lib.LayoutOpts(_lib.ptr(self.lay_map), N, None, _lib.ptr(self.lay_delta))
+        if plan.order2:
             self.hist = torch.empty_like(x)                    # (written by every step before any step reads it: q[0] = 0)
-            self.sopts = _lib.SolverOpts()
-            self.sopts.hist = _lib.ptr(self.hist)
+            self.sopts = _lib.SolverOpts(None, _lib.ptr(self.hist))
         # (the second stream lets the library run coarse scales as two overlapping half-batches; same numbers either way)
         self.aux = _aux_stream(x.device) if d.two_streams else None
 
@@ -561,21 +523,17 @@ class _ChainCall:
         of `seeds_dev` (one seed per sample), of `mix_dev` ((B, K) int64 seeds, (B, K) float32 weights: a blend per sample)
         or of `seed`, at stream ids sid0 + 0 ... k - 1."""
         x, net, ref = self.x, self.net, (lambda o: C.byref(o) if o is not None else None)
+        p = self.host = pack_steps(self.plan, i0, k)            # (the per-step host arrays of this piece)
         self.opts.noise = _lib.ptr(noise)
-        if self.kopts is not None:
-            self.kopts.ab = _at(self.ab, i0, C.c_float, 2)
-        if self.ropts is not None:
-            self.ropts.jumps, self.ropts.noise = _at(self.jumps, i0, _lib.JumpCoefs), _lib.ptr(jump_noise)
-        if self.lopts is not None:
-            self.lopts.g = _at(self.garr, i0, C.c_float)
+        for blk, name, v in ((self.kopts, "ab", p.ab), (self.ropts, "jumps", p.jumps), (self.ropts, "noise", _lib.ptr(jump_noise)),
+                             (self.lopts, "g", p.g), (self.sopts, "q", p.q)):
+            if blk is not None:
+                setattr(blk, name, v)
         in_alt = C.c_int(0)
         args = [_lib.ptr(net.flat_params), _lib.ptr(self.packed), _lib.ptr(x), _lib.ptr(self.x_alt), _lib.ptr(self.eps),
-                _lib.ptr(self.xt), _at(self.coefs, i0, _lib.StepCoefs), _at(self.tl, i0, C.c_int), k, float(self.s), seed, sid0,
-                net.dim_arg, x.shape[0], self.Hc, self.Wc, self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr(x.device), self.aux,
-                C.byref(in_alt), C.byref(self.opts), *self.halo, ref(self.kopts), _lib.ptr(seeds_dev), ref(self.ropts),
-                ref(self.lopts), ref(self.bopts)]
-        if self.sopts is not None:
-            self.sopts.q = _at(self.q, i0, C.c_float)
+                _lib.ptr(self.xt), p.coefs, p.tl, k, float(self.s), seed, sid0, net.dim_arg, x.shape[0], self.Hc, self.Wc,
+                self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr(x.device), self.aux, C.byref(in_alt), C.byref(self.opts),
+                *self.halo, ref(self.kopts), _lib.ptr(seeds_dev), ref(self.ropts), ref(self.lopts), ref(self.bopts)]
         if mix_dev is not None:                                # (the blended run: the one entry that can say it)
             mopts = _lib.MixOpts(_lib.ptr(mix_dev[0]), _lib.ptr(mix_dev[1]), int(mix_dev[0].shape[1]))
             _lib.check(self.lib.sinddm_sample_chain_mix(*args, ref(self.sopts), C.byref(mopts)), "sinddm_sample_chain_mix")
@@ -812,8 +770,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
             raise ValueError("seed_mix and sample_seeds are both set: two noise sources")
         if self.noise_fn is not None:
             raise ValueError("seed_mix and noise_fn are both set: two noise sources")
-        if self.clip_guided_sampling:
-            raise NotImplementedError("seed_mix with CLIP-guided sampling")
+        refuse(self, "seed_mix", "clip")
         if not isinstance(mx, (tuple, list)) or len(mx) != 2:
             raise ValueError("seed_mix is a pair (keys, weights)")
         keys, w = (v.tolist() if isinstance(v, (np.ndarray, torch.Tensor)) else list(v) for v in mx)
@@ -836,24 +793,20 @@ class MultiScaleGaussianDiffusion(nn.Module):
         """The device tables of a validated mix: (B, K) int64 seeds, (B, K) float32 weights."""
         return (torch.tensor(mix[0], dtype=torch.int64, device=device), torch.tensor(mix[1], dtype=torch.float32, device=device))
 
-    def _mixed_normal(self, mix, shape, sid: int, device) -> torch.Tensor:
-        """(B, ...) N(0,1): slice b = the blend of sinddm_normal_fill(numel per sample, keys[b][k], sid)."""
+    def _keyed_normal(self, seeds, mix, shape, sid: int, device) -> torch.Tensor:
+        """(B, ...) N(0,1) of a seeded run: slice b = sinddm_normal_fill(numel per sample, seeds[b], sid) -- or, with a `mix`,
+        the blend of those of keys[b][k]."""
         lib = _lib.load()
         shape = tuple(int(v) for v in shape)
         z = torch.empty(shape, dtype=torch.float32, device=device)
-        kd, wd = self._mix_tensors(mix, device)
-        _lib.check(lib.sinddm_normal_fill_mix(_lib.ptr(z), shape[0], z.numel() // shape[0], _lib.ptr(kd), _lib.ptr(wd),
-                                              int(kd.shape[1]), int(sid), _lib.stream_ptr(z.device)), "sinddm_normal_fill_mix")
-        return z
-
-    def _seeded_normal(self, seeds, shape, sid: int, device) -> torch.Tensor:
-        """(B, ...) N(0,1): slice b = sinddm_normal_fill(numel per sample, seeds[b], sid)."""
-        lib = _lib.load()
-        shape = tuple(int(v) for v in shape)
-        z = torch.empty(shape, dtype=torch.float32, device=device)
-        sd = torch.tensor(seeds, dtype=torch.int64, device=device)
-        _lib.check(lib.sinddm_normal_fill_samples(_lib.ptr(z), shape[0], z.numel() // shape[0], _lib.ptr(sd), int(sid),
-                                                  _lib.stream_ptr(z.device)), "sinddm_normal_fill_samples")
+        n, st = z.numel() // shape[0], _lib.stream_ptr(z.device)
+        if mix is not None:
+            kd, wd = self._mix_tensors(mix, device)
+            _lib.check(lib.sinddm_normal_fill_mix(_lib.ptr(z), shape[0], n, _lib.ptr(kd), _lib.ptr(wd), int(kd.shape[1]), int(sid), st),
+                       "sinddm_normal_fill_mix")
+        else:
+            sd = torch.tensor(seeds, dtype=torch.int64, device=device)
+            _lib.check(lib.sinddm_normal_fill_samples(_lib.ptr(z), shape[0], n, _lib.ptr(sd), int(sid), st), "sinddm_normal_fill_samples")
         return z
 
     def _draw(self, kind: str, shape, s: int, t: int, device, pos: int = 0) -> torch.Tensor:
@@ -863,23 +816,16 @@ class MultiScaleGaussianDiffusion(nn.Module):
         mix = self._mix_for(s, shape[0])
         if seeds is not None or mix is not None:
             # (a blend is drawn like its seeds would be: same stream ids, same extended size, the blend of the slices)
-            sid = noise_stream_id(s, kind, pos)
-            fill = (lambda shp: self._seeded_normal(seeds, shp, sid, device)) if seeds is not None else \
-                   (lambda shp: self._mixed_normal(mix, shp, sid, device))
-            hy, hx = self._tile_halo()
-            if kind in ("step", "jump") and (hy or hx):
-                # the tiled chain draws over the EXTENDED sample and discards the halo's draws: take the centre
-                H, W = int(shape[-2]), int(shape[-1])
-                z = fill(tuple(shape[:-2]) + (H + 2 * hy, W + 2 * hx))
+            # the tiled chain draws over the EXTENDED sample and discards the halo's draws: take the centre
+            hy, hx = self._tile_halo() if kind in ("step", "jump") else (0, 0)
+            H, W = int(shape[-2]), int(shape[-1])
+            z = self._keyed_normal(seeds, mix, tuple(shape[:-2]) + (H + 2 * hy, W + 2 * hx), noise_stream_id(s, kind, pos), device)
+            if hy or hx:
                 z = z[..., hy:hy + H, hx:hx + W].contiguous()
-            else:
-                z = fill(shape)
-            if self.draw_log is not None:
-                self.draw_log.append((kind, int(s), int(t), z.clone()))
-            return z
-        if self.noise_fn is not None:
+        elif self.noise_fn is not None:
             return self.noise_fn(kind, tuple(shape), int(s), int(t), device).contiguous()
-        z = torch.randn(tuple(shape), device=device)
+        else:
+            z = torch.randn(tuple(shape), device=device)
         if self.draw_log is not None:
             self.draw_log.append((kind, int(s), int(t), z.clone()))
         return z
@@ -1005,12 +951,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 raise ValueError(f"sample_steps = {self.sample_steps!r}: at least one evaluation per scale")
         if self.sample_steps is None and order == 1 and eta == 1.0:
             return None
-        if self.clip_guided_sampling:
-            raise NotImplementedError("sample_steps / solver_order / eta with clip_guided_sampling: the CLIP-guided step runs in "
-                                      "eager torch ops on the reference's own schedule")
-        if self._resample_cfg() is not None:
-            raise NotImplementedError("sample_steps / solver_order / eta with resample: a resampling jump inside a strided or "
-                                      "multistep run is not built")
+        refuse(self, "few_step", "clip")
+        refuse(self, "few_step", "resample")
         return n, spacing, order
 
     # ---- reference API: fine-grained pieces (off the hot path; kept for callers / app modes) ----
@@ -1229,9 +1171,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
         R, J = (int(v) for v in self.resample)
         if R < 1 or J < 1:
             raise ValueError(f"resample = {self.resample!r}: R and J must be >= 1")
-        if self.clip_guided_sampling:
-            raise NotImplementedError("resample with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has "
-                                      "no resampling jump")
+        refuse(self, "resample", "clip")
         return (R, J) if R > 1 else None
 
     def _keep_entry(self, s: int, img: torch.Tensor):
@@ -1240,9 +1180,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
         which must be the running batch."""
         if self.keep_maps is None:
             return None
-        if self.clip_guided_sampling:
-            raise NotImplementedError("keep_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and "
-                                      "has no known-region replacement")
+        refuse(self, "keep_maps", "clip")
         entry = self.keep_maps.get(int(s))
         if entry is None:
             return None
@@ -1260,9 +1198,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
         checks its maps, or None (no entry, or strength 0)."""
         if self.layout_maps is None:
             return None
-        if self.clip_guided_sampling:
-            raise NotImplementedError("layout_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and "
-                                      "has no layout pull")
+        refuse(self, "layout_maps", "clip")
         lay = self.layout_maps.get(int(s))
         if lay is None:
             return None
@@ -1282,8 +1218,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
             raise ValueError(f"layout_strength {g} outside [0, 1] or layout_t_min {t_min} < 0 at scale {int(s)}")
         if g == 0.0:
             return None                                        # (the run without the option, resampled or not)
-        if self._resample_cfg() is not None:
-            raise NotImplementedError("layout_maps with resample: the layout pull inside a resampling jump is not built")
+        refuse(self, "layout_maps", "resample")
         return lay.contiguous(), N, g, t_min
 
     def _layout_gain_for(self, B: int, device) -> Optional[torch.Tensor]:
@@ -1353,96 +1288,50 @@ class MultiScaleGaussianDiffusion(nn.Module):
                          (sinddm_sample_chain_mix).  `draw_log`: ("chain_mix", s, (keys, weights), t list, jump targets or None).
           otherwise      one 62-bit seed from torch's CPU generator keys the in-kernel draws.  `draw_log`: ("chain", s, seed,
                          t list), tiled ("chain_tile", ..., (hy, hx)), resampled ("chain_resample", s, seed, ..., jump targets)."""
-        t_seq = [int(t) for t in t_seq]
-        s = int(s)
-        few = self._few_step_cfg(s)                            # (raises with `resample` / CLIP guidance)
-        lands = q = None                                       # per step: the level it lands on, its multistep factor
-        if few is not None and t_seq:
-            from .functions import stride_schedule
-            t_seq, lands = stride_schedule(t_seq, few[0] if few[0] is not None else len(t_seq), few[1],
-                                           self._kappa(s) if few[1] == 'logsnr' else None)
-            if few[2] == 2:
-                q = self._solver_q(s, t_seq, lands)
-        lay = self._layout_entry(s, img)                       # (raises with `resample` / CLIP guidance)
-        lay_g = None                                           # per step: the strength of the pull
-        if lay is not None:
-            from .functions import layout_strengths
-            lay_g = layout_strengths(t_seq, lay[2], lay[3])
-            if not any(v > 0.0 for v in lay_g):
-                lay = lay_g = None
-        if lay is not None and q is not None:
-            raise NotImplementedError("solver_order = 2 with layout_maps: the multistep step through a layout pull is not built")
-        rs_cfg = self._resample_cfg()
-        jump_to = None                                         # per step of the EXPANDED walk: the level to jump to, or None
-        if rs_cfg is not None:
-            from .functions import resample_schedule
-            t_seq, jump_to = resample_schedule(t_seq, *rs_cfg)
-        sseeds = self._seeds_for(s, img.shape[0])
-        mix = self._mix_for(s, img.shape[0])
-        keep = self._keep_entry(s, img)
-        roi = bool(self.roi_guided_sampling and s < self.n_scales - 1)     # models.py:430-431
+        plan = RunPlan(self, img, s, t_seq)                    # (every validation and refusal: sampler.RunPlan)
+        s, n = plan.s, len(plan.steps)
         fast = ((self.noise_fn is None or self.chain_noise) and isinstance(self.denoise_fn, SinDDMNet)
-                and not self.save_interm and not self.clip_guided_sampling and (self.chain_guided or not roi)
-                and len(t_seq) > 0 and img.is_cuda and img.dtype == torch.float32 and img.dim() == 4
+                and not self.save_interm and not self.clip_guided_sampling and (self.chain_guided or plan.roi is None)
+                and n > 0 and img.is_cuda and img.dtype == torch.float32 and img.dim() == 4
                 and img.shape[1] == self.channels == 3)
         if not fast:
-            hist = torch.empty_like(img) if q is not None else None
-            for pos, i in enumerate(t_seq):
-                img = self._p_sample_host_t(img, i, s, step_pos=pos, jump_to=jump_to[pos] if jump_to else None,
-                                            land=lands[pos] if lands is not None else None,
-                                            q=q[pos] if q is not None else None, hist=hist)
-                self._dump_interm(img, s, f'output_t-{i:03}_s-{s}.png')
+            hist = torch.empty_like(img) if plan.order2 else None
+            for st in plan.steps:
+                img = self._p_sample_host_t(img, st.t, s, step_pos=st.pos, q=st.q, hist=hist, plan=plan)
+                self._dump_interm(img, s, f'output_t-{st.t:03}_s-{s}.png')
             return img
-        run = _ChainCall(self, img, s, t_seq, jump_to, roi=roi, keep=keep, lay=lay, lay_g=lay_g, lands=lands, q=q)
-        n, x, tiled = len(t_seq), run.x, run.tiled
-        if self.noise_fn is not None:
-            # recorded noise: pieces of as many steps as fit the byte budget; each piece's draws are fetched exactly as the
-            # step-by-step loop fetches them (one `_draw("step", ...)` per step, t = 0 included, in step order) and the
-            # next piece continues from the buffer the previous one ended in
+        run = _ChainCall(self, plan, img)
+        x, (kind, src) = run.x, plan.noise
+        per, seed, kw = n, 0, {}                               # in-kernel draws: one call for the whole run
+        if kind == "recorded":
+            # pieces of as many steps as fit the byte budget; each piece's draws are fetched exactly as the step-by-step loop
+            # fetches them (one `_draw("step", ...)` per step, t = 0 included, in step order, a `_draw("jump", ...)` after a
+            # step that jumps) and the next piece continues from the buffer the previous one ended in
             per = max(1, int(CHAIN_NOISE_BYTES) // (x.numel() * x.element_size()))
-            for i0 in range(0, n, per):
-                k = min(per, n - i0)
+        elif kind == "seeds":
+            kw = dict(sid0=noise_stream_id(s, "step", 0), seeds_dev=torch.tensor(src, dtype=torch.int64, device=x.device))
+        elif kind == "mix":
+            kw = dict(sid0=noise_stream_id(s, "step", 0), mix_dev=self._mix_tensors(src, x.device))
+        else:
+            # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
+            # sample, seeding only the CUDA generator (torch.cuda.manual_seed) does not
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
+        if kind != "recorded" and self.draw_log is not None:
+            self.draw_log.append(plan.log_entry(seed))         # (the draws an entry stands for: RunPlan.log_entry)
+        for i0 in range(0, n, per):
+            piece = plan.steps[i0:i0 + per]
+            if kind == "recorded":
                 # (tiled: the draws have the sample's own size and fill the centre of their slot; the halo of a slot is
                 # never used -- the halo of a step's output is overwritten with its wrapped centre)
-                noise = (torch.zeros if tiled else torch.empty)((k,) + tuple(x.shape), dtype=x.dtype, device=x.device)
-                jn = None                                      # the piece's jumps, one slot each in order of occurrence
-                if jump_to is not None:
-                    nj = max(1, sum(1 for l2 in jump_to[i0:i0 + k] if l2 is not None))
-                    jn = (torch.zeros if tiled else torch.empty)((nj,) + tuple(x.shape), dtype=x.dtype, device=x.device)
-                nj = 0
-                for j in range(k):
-                    run.centre(noise[j]).copy_(self._draw("step", img.shape, s, t_seq[i0 + j], x.device))
-                    if jump_to is not None and jump_to[i0 + j] is not None:
-                        run.centre(jn[nj]).copy_(self._draw("jump", img.shape, s, t_seq[i0 + j], x.device))
-                        nj += 1
-                run.call(i0, k, 0, noise=noise, jump_noise=jn)
-            return run.result()
-        if sseeds is not None:
-            if self.draw_log is not None:
-                # (draw i of sample b is sinddm_normal_fill(3 H W, seeds[b], noise_stream_id(s, 'step', i)), over the
-                # extended size when tiled)
-                self.draw_log.append(("chain_resample", s, list(sseeds), list(t_seq), list(jump_to)) if jump_to is not None
-                                     else ("chain_seeds", s, list(sseeds), list(t_seq)))
-            run.call(0, n, 0, sid0=noise_stream_id(s, "step", 0),
-                     seeds_dev=torch.tensor(sseeds, dtype=torch.int64, device=x.device))
-            return run.result()
-        if mix is not None:
-            if self.draw_log is not None:
-                # (draw i of sample b is the blend of sinddm_normal_fill(3 H W, keys[b][k], noise_stream_id(s, 'step', i)))
-                self.draw_log.append(("chain_mix", s, (mix[0], mix[1]), list(t_seq), list(jump_to) if jump_to is not None else None))
-            run.call(0, n, 0, sid0=noise_stream_id(s, "step", 0), mix_dev=self._mix_tensors(mix, x.device))
-            return run.result()
-        # the step noise is keyed on a 62-bit seed drawn from torch's CPU generator: torch.manual_seed() reproduces a
-        # sample, seeding only the CUDA generator (torch.cuda.manual_seed) does not
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
-        if self.draw_log is not None:
-            # (tiled: draw i of the run is sinddm_normal_fill(seed, i) over the EXTENDED (B,3,H+2hy,W+2hx) tensor)
-            if jump_to is not None:
-                # (the jump after step i draws sinddm_normal_fill(seed, i + 2^31) on top, over the same tensor)
-                self.draw_log.append(("chain_resample", s, seed, list(t_seq), list(jump_to)))
-            else:
-                self.draw_log.append(("chain_tile", s, seed, list(t_seq), run.halo) if tiled else ("chain", s, seed, list(t_seq)))
-        run.call(0, n, seed)
+                buf = lambda m: (torch.zeros if run.tiled else torch.empty)((m,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+                jn = buf(max(1, sum(st.jump is not None for st in piece))) if plan.jump_to is not None else None
+                kw = dict(noise=buf(len(piece)), jump_noise=jn)
+                jslots = iter(jn) if jn is not None else None  # (a piece's jumps: one slot each in order of occurrence)
+                for st, slot in zip(piece, kw["noise"]):
+                    run.centre(slot).copy_(self._draw("step", img.shape, s, st.t, x.device))
+                    if st.jump is not None:
+                        run.centre(next(jslots)).copy_(self._draw("jump", img.shape, s, st.t, x.device))
+            run.call(i0, len(piece), seed, **kw)
         return run.result()
 
     def _eps(self, x, t_dev, t_host, s):
@@ -1461,121 +1350,79 @@ class MultiScaleGaussianDiffusion(nn.Module):
             t_dev = torch.full((x.shape[0],), int(t_host), device=x.device, dtype=torch.long)
         return self.denoise_fn(x, t_dev, scale=s)                           # plug point, models.py:356
 
-    def _p_sample_host_t(self, x: torch.Tensor, t: int, s: int, clip_denoised: bool = True,
-                         repeat_noise: bool = False, step_pos: int = 0, jump_to: Optional[int] = None,
-                         land: Optional[int] = None, q: Optional[float] = None,
-                         hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _p_sample_host_t(self, x: torch.Tensor, t: int, s: int, clip_denoised: bool = True, repeat_noise: bool = False,
+                         step_pos: int = 0, jump_to: Optional[int] = None, land: Optional[int] = None, q: Optional[float] = None,
+                         hist: Optional[torch.Tensor] = None, plan: Optional[RunPlan] = None) -> torch.Tensor:
         """One reverse step with the timestep known on the host: net forward + ONE fused kernel.  `step_pos`: the step's
         position in its run -- with `sample_seeds` it selects the draw (noise_stream_id(s, 'step', step_pos)).  `jump_to`:
         the level a resampling jump takes the step's output back up to (sinddm_reverse_step_jump: step + jump in one kernel,
         a second draw of kind 'jump'), or None.  `land`: the level the step lands on (None: t - 1; `step_coefs_to`).  `q` /
         `hist`: the multistep factor of the step and the buffer that carries the previous step's clean estimate
-        (sinddm_reverse_step_ms: `hist` is written, and read when q != 0), or None."""
-        if (land is not None or q is not None) and (self.clip_guided_sampling or jump_to is not None):
-            raise NotImplementedError("a strided or multistep step under CLIP guidance or before a resampling jump")
+        (sinddm_reverse_step_ms: `hist` is written, and read when q != 0), or None.  `plan`: the run's plan when `_run_steps`
+        steps through it -- the step is its record `step_pos`; else the one-step plan of the arguments is built here."""
         if (q is None) != (hist is None):
             raise ValueError("a multistep step takes q and hist together")
-        keep = self._keep_entry(s, x)                                       # (raises under CLIP guidance)
-        lay = self._layout_entry(s, x)                                      # (so does this)
-        if jump_to is not None and self.clip_guided_sampling:
-            raise NotImplementedError("a resampling jump on a CLIP-guided step")
+        if plan is None:
+            plan, step_pos = RunPlan(self, x, s, [t], at=(step_pos, jump_to, land, q), clip_denoised=clip_denoised), 0
+        st = plan.steps[step_pos]
         if self.clip_guided_sampling:
             if self.clip_model is None or self.guidance_sub_iters is None or self.stop_guidance is None:
                 raise RuntimeError("clip_guided_sampling is set but clip_model / guidance_sub_iters / stop_guidance are not: "
                                    "CLIP is outside this build -- assign any object with zero_grad() and a differentiable "
                                    "calculate_clip_loss(image, text_embedds) (reference models.py:193-220, 367-421)")
-            return self._p_sample_guided(x.contiguous(), int(t), int(s), clip_denoised, repeat_noise, step_pos)
-        lib = _lib.load()
+            return self._p_sample_guided(x.contiguous(), st.t, int(s), clip_denoised, repeat_noise, st.pos)
         x = x.contiguous()
-        eps = self._eps(x, None, t, s)
+        eps = self._eps(x, None, st.t, s)
         if self.save_interm:                                                # models.py:360-366 (x_recon lives inside the fused kernel:
-            tt = torch.full((x.shape[0],), int(t), device=x.device, dtype=torch.long)   # recomputed here, for the dump only)
-            self._dump_x_recon(self.predict_start_from_noise(x, t=tt, s=s, noise=eps)[0], t, s)
-        if repeat_noise:
-            z = noise_like(x.shape, x.device, True).contiguous()
-        else:
-            z = self._draw("step", x.shape, s, t, x.device, step_pos)
-        k = self.step_coefs(t, s, clip_denoised) if land is None else self.step_coefs_to(t, land, s, clip_denoised, self.eta)
-        xt = None
-        if k.mode != 0:
-            xt = self.img_prev_upsample
-            if xt is None:
-                raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
-            xt = xt.contiguous()
+            tt = torch.full((x.shape[0],), st.t, device=x.device, dtype=torch.long)     # recomputed here, for the dump only)
+            self._dump_x_recon(self.predict_start_from_noise(x, t=tt, s=s, noise=eps)[0], st.t, s)
+        z = noise_like(x.shape, x.device, True).contiguous() if repeat_noise else self._draw("step", x.shape, s, st.t, x.device, st.pos)
+        z2 = self._draw("jump", x.shape, s, st.t, x.device, st.pos) if st.jump is not None else None
         out = torch.empty_like(x)
-        B_, C_, H_, W_ = x.shape
-        pull = lay is not None and int(t) >= lay[3]
-        if pull and q is not None:
-            raise NotImplementedError("a layout pull on a multistep step")
-        if pull and jump_to is not None:
-            raise NotImplementedError("a layout pull on a step that is followed by a resampling jump")
-        z2 = self._draw("jump", x.shape, s, t, x.device, step_pos) if jump_to is not None else None
-        ew = ec = None
-        if self.roi_guided_sampling and s < self.n_scales - 1:             # models.py:430-431
-            ew, ec = self.roi_edit_maps(s, H_, W_, x.device)
-        gain = self._layout_gain_for(B_, x.device) if pull else None
-        g = lay[2] if pull else 0.0
-        if ((ew is not None and ew.dim() == 3) or (keep is not None and (keep[0].dim() == 3 or keep[1].dim() == 4))
-                or (pull and lay[0].dim() == 4) or gain is not None):
+        if plan.per[0] or plan.per[1] or plan.per[2] or (st.g > 0.0 and (plan.per[3] or plan.gain is not None)):
             # per-sample maps: the single-step entries with B = 1 on each sample's slices (a cross-check route)
-            if ew is not None and ew.dim() == 3 and ew.shape[0] != B_:
-                raise ValueError(f"roi_bbs_batch has {ew.shape[0]} box lists, the batch {B_} samples")
-            row = lambda v, nd, b: v if v is None or v.dim() == nd else v[b]
-            gains = gain.cpu().numpy() if gain is not None else None
-            for b in range(B_):
-                keep_b = None if keep is None else (row(keep[0], 2, b), row(keep[1], 3, b))
-                lay_b = row(lay[0], 3, b) if pull else None
-                # (the strength the chain's kernel forms: the fp32 product g * gain[b])
-                g_b = float(np.float32(g) * gains[b]) if gains is not None else g
-                sl = lambda v: None if v is None else v[b:b + 1]
-                self._step_tail(sl(x), sl(eps), sl(xt), sl(z), sl(z2), sl(out), k, t, s, keep_b, lay_b, lay[1] if pull else 0, g_b,
-                                row(ew, 2, b), row(ec, 3, b), jump_to, land, q, sl(hist))
-            return out
-        self._step_tail(x, eps, xt, z, z2, out, k, t, s, keep, lay[0] if pull else None, lay[1] if pull else 0, g, ew, ec, jump_to,
-                        land, q, hist)
+            for b in range(x.shape[0]):
+                self._step_tail(plan, st, x, eps, z, z2, out, hist, b)
+        else:
+            self._step_tail(plan, st, x, eps, z, z2, out, hist)
         return out
 
-    def _step_tail(self, x, eps, xt, z, z2, out, k, t, s, keep, lay, N, g, ew, ec, jump_to, land=None, q=None, hist=None):
-        """The single-step entry that ends a step of `_p_sample_host_t`: `out` is written.  `keep` = (mask, x0) or None, `lay`
-        the layout picture of a conditioned step (block size N, strength g) or None, (ew, ec) the ROI maps or None, `jump_to`
-        the level of a resampling jump (second draw z2) or None -- all shared by the B samples of this call.  `land`: the level
-        the step lands on (None: t - 1), whose forward scalars the keep uses; (q, hist): a multistep step."""
-        lib = _lib.load()
+    def _step_tail(self, plan, st, x, eps, z, z2, out, hist, b=None):
+        """The single-step entry that ends the step `st` of `plan` on the route of `_p_sample_host_t`: `out` is written.  The
+        first that applies: a layout pull (st.g > 0), a resampling jump (second draw z2), a multistep step (`hist`), keep maps,
+        ROI maps, the plain step.  `b`: sample b alone -- slice b of every tensor, row b of every per-sample map (B = 1)."""
+        lib, xt, g = _lib.load(), plan.xt, st.g
+        ew, ec = plan.roi if plan.roi is not None else (None, None)
+        km, kx = plan.keep if plan.keep is not None else (None, None)
+        lay, N = plan.lay[:2] if st.g > 0.0 else (None, 0)
+        if b is not None:
+            x, eps, xt, z, z2, out, hist = (None if v is None else v[b:b + 1] for v in (x, eps, xt, z, z2, out, hist))
+            row = lambda v, nd: v if v is None or v.dim() == nd else v[b]
+            ew, km, ec, kx, lay = row(ew, 2), row(km, 2), row(ec, 3), row(kx, 3), row(lay, 3)
+            if plan.gain is not None:                          # (the strength the chain's kernel forms: the fp32 product)
+                g = float(np.float32(g) * plan.gain[b])
         B_, C_, H_, W_ = x.shape
-        st = _lib.stream_ptr(x.device)
-        row_ab = int(t) if land is None else int(land) + 1      # (row l + 1: the forward scalars of level l)
-        ka, kb = (float(v) for v in self._keep_ab_table()[row_ab]) if keep is not None else (1.0, 0.0)
-        km, kx = (_lib.ptr(keep[0]), _lib.ptr(keep[1])) if keep is not None else (None, None)
+        head = [_lib.ptr(v) for v in (x, eps, xt, z, out)] + [C.byref(st.k)]
+        maps = [_lib.ptr(ew), _lib.ptr(ec), _lib.ptr(km), _lib.ptr(kx), *st.ab]
+        shp = [B_, C_, H_ * W_, _lib.stream_ptr(x.device)]
         if lay is not None:
             # the conditioned step: block deltas of (layout - x_recon), then the step with c_eff = ec + g * U(D)
             delta = torch.empty(B_ * 3 * (-(-H_ // N)) * (-(-W_ // N)), dtype=x.dtype, device=x.device)
-            _lib.check(lib.sinddm_layout_delta(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(lay), _lib.ptr(delta),
-                                               C.byref(k), _lib.ptr(ew), _lib.ptr(ec), N, B_, H_, W_, 0, 0, st),
-                       "sinddm_layout_delta")
-            _lib.check(lib.sinddm_reverse_step_layout(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
-                                                      C.byref(k), _lib.ptr(delta), g, N, _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb,
-                                                      B_, H_, W_, 0, 0, int(bool(self.tile[0])), int(bool(self.tile[1])), st),
-                       "sinddm_reverse_step_layout")
-        elif jump_to is not None:
-            jc = _lib.JumpCoefs(1, *self._jump_table(s)(int(t) - 1, int(jump_to)))
-            _lib.check(lib.sinddm_reverse_step_jump(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(z2),
-                                                    _lib.ptr(out), C.byref(k), C.byref(jc), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb,
-                                                    B_, C_, H_ * W_, st), "sinddm_reverse_step_jump")
+            _lib.check(lib.sinddm_layout_delta(*head[:3], _lib.ptr(lay), _lib.ptr(delta), head[5], *maps[:2], N, B_, H_, W_, 0, 0,
+                                               shp[3]), "sinddm_layout_delta")
+            name, args = "sinddm_reverse_step_layout", [*head, _lib.ptr(delta), g, N, *maps, B_, H_, W_, 0, 0,
+                                                        int(bool(self.tile[0])), int(bool(self.tile[1])), shp[3]]
+        elif st.jump is not None:
+            name, args = "sinddm_reverse_step_jump", [*head[:4], _lib.ptr(z2), *head[4:], C.byref(st.jump), *maps, *shp]
         elif hist is not None:
-            _lib.check(lib.sinddm_reverse_step_ms(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out), C.byref(k),
-                                                  float(q), _lib.ptr(hist), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb, B_, C_,
-                                                  H_ * W_, st), "sinddm_reverse_step_ms")
-        elif keep is not None:
-            _lib.check(lib.sinddm_reverse_step_keep(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
-                                                    C.byref(k), _lib.ptr(ew), _lib.ptr(ec), km, kx, ka, kb, B_, C_, H_ * W_, st),
-                       "sinddm_reverse_step_keep")
+            name, args = "sinddm_reverse_step_ms", [*head, st.q, _lib.ptr(hist), *maps, *shp]
+        elif km is not None:
+            name, args = "sinddm_reverse_step_keep", [*head, *maps, *shp]
         elif ew is not None:
-            _lib.check(lib.sinddm_reverse_step_edit(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z),
-                                                    _lib.ptr(out), C.byref(k), _lib.ptr(ew), _lib.ptr(ec), B_, C_,
-                                                    H_ * W_, st), "sinddm_reverse_step_edit")
+            name, args = "sinddm_reverse_step_edit", [*head, *maps[:2], *shp]
         else:
-            _lib.check(lib.sinddm_reverse_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out),
-                                               C.byref(k), x.numel(), st), "sinddm_reverse_step")
+            name, args = "sinddm_reverse_step", [*head, x.numel(), shp[3]]
+        _lib.check(getattr(lib, name)(*args), name)
 
     @torch.no_grad()
     def p_sample(self, x, t, s, clip_denoised=True, repeat_noise=False):   # models.py:449-459
@@ -1587,10 +1434,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
         device = self.betas.device
         img = self._draw("init", shape, s, 0, device)
         self._dump_interm(img, s, f'input_noise_s-{s}.png')
-        if self.sample_limited_t and s < (self.n_scales - 1):
-            t_min = self.num_timesteps_ideal[s + 1]
-        else:
-            t_min = 0
+        t_min = self.num_timesteps_ideal[s + 1] if self.sample_limited_t and s < (self.n_scales - 1) else 0
         return self._run_steps(img, s, reversed(range(t_min, self.num_timesteps)))
 
     def _dump_interm(self, img, s, name, renorm=True):
@@ -1613,11 +1457,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_via_scale_loop(self, batch_size, img, s, custom_t=None):  # models.py:501-547
-        if custom_t is None:
-            total_t = self.num_timesteps_ideal[min(s, self.n_scales - 1)] - 1
-        else:
-            total_t = custom_t
-        total_t = int(total_t)
+        total_t = int(self.num_timesteps_ideal[min(s, self.n_scales - 1)] - 1 if custom_t is None else custom_t)
         self.img_prev_upsample = img                                        # x-tilde of this scale
         noise = self._draw("renoise", img.shape, s, 0, img.device)
         img = self._q_sample_impl(img, None, total_t, noise)                # models.py:518
@@ -1629,10 +1469,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
                 self.x_recon_prev = F.interpolate(self.x_recon_prev, size=mul_size, mode='bilinear')
             else:                                                           # a mask created at scale 0 is too noisy
                 self.clip_mask = None
-        if self.sample_limited_t and s < (self.n_scales - 1):
-            t_min = self.num_timesteps_ideal[s + 1]
-        else:
-            t_min = 0
+        t_min = self.num_timesteps_ideal[s + 1] if self.sample_limited_t and s < (self.n_scales - 1) else 0
         return self._run_steps(img, s, reversed(range(t_min, total_t)))
 
     def target_size(self, s, scale_mul=(1, 1), custom_sample=False, custom_img_size_idx=0, custom_image_size=None):

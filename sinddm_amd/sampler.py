@@ -1,0 +1,162 @@
+"""The host-side plan of one run of reverse steps at one scale: what `MultiScaleGaussianDiffusion._run_steps` and
+`_p_sample_host_t` run.  Plain Python: no device work of its own, no library call.  `RunPlan` resolves the schedule, the maps,
+the noise source and the halo ONCE and holds one `Step` record per reverse step; the chain route (`models._ChainCall`) packs
+records into the arrays of a library call (`pack_steps`), the step-by-step route walks them through the single-step entries.
+A new per-step scalar is derived in `RunPlan.__init__`, a new combination that is not built is a row of `NOT_BUILT`."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import Optional, Tuple
+
+from . import _lib
+from .functions import layout_strengths, resample_schedule, stride_schedule
+
+# The combinations of options that are not built, (option, the option it cannot go with) -> what NotImplementedError says.
+NOT_BUILT = {
+    ("keep_maps", "clip"): "keep_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has no "
+                           "known-region replacement",
+    ("layout_maps", "clip"): "layout_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has no "
+                             "layout pull",
+    ("resample", "clip"): "resample with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has no "
+                          "resampling jump",
+    ("few_step", "clip"): "sample_steps / solver_order / eta with clip_guided_sampling: the CLIP-guided step runs in eager "
+                          "torch ops on the reference's own schedule",
+    ("seed_mix", "clip"): "seed_mix with CLIP-guided sampling",
+    ("few_step", "resample"): "sample_steps / solver_order / eta with resample: a resampling jump inside a strided or multistep "
+                              "run is not built",
+    ("layout_maps", "resample"): "layout_maps with resample: the layout pull inside a resampling jump is not built",
+    ("layout_maps", "solver_order"): "solver_order = 2 with layout_maps: the multistep step through a layout pull is not built",
+    ("strided_step", "clip_or_jump"): "a strided or multistep step under CLIP guidance or before a resampling jump",
+}
+_ON = {"clip": lambda d: d.clip_guided_sampling, "resample": lambda d: d._resample_cfg() is not None}
+
+
+def refuse(d, opt: str, other: str, on: Optional[bool] = None):
+    """Raises NotImplementedError for the pair (opt, other) of NOT_BUILT when `other` is on (`on`; None: as `d` has it).  The
+    readers of the options (`_keep_entry`, `_layout_entry`, `_resample_cfg`, `_few_step_cfg`, `_mix_for`) call it where they
+    have always raised, `RunPlan` for what only a whole run or a single step shows."""
+    if _ON[other](d) if on is None else on:
+        raise NotImplementedError(NOT_BUILT[opt, other])
+
+
+@dataclass
+class Step:
+    """One reverse step of a run."""
+    pos: int                                   # position in the (expanded) run: the stream id of its draws
+    t: int                                     # the level the network is evaluated at
+    land: int                                  # the level the step lands on (-1: the clean image)
+    k: _lib.StepCoefs
+    ab: Tuple[float, float]                    # forward scalars of the known image at `land` ((1, 0) without keep maps)
+    jump_to: Optional[int]                     # the level a resampling jump takes the step's output back up to, or None
+    jump: Optional[_lib.JumpCoefs]
+    g: float                                   # strength of the layout pull (0: the step is not conditioned)
+    q: Optional[float]                         # multistep factor (None: a first-order run)
+
+
+class RunPlan:
+    """The reverse steps `t_seq` of scale s on `img` with the options `d` carries; `at` = (step_pos, jump_to, land, q) makes it
+    the plan of the ONE step `t_seq = [t]` as `_p_sample_host_t` is handed it, else the schedule is resolved from `d`.
+    Attributes: `steps` (the records), `t_seq` / `jump_to` (the expanded walk; `jump_to` None without resampling), `halo`,
+    `roi` (ew, ec) / `keep` (mask, x0) / `lay` (layout, N, strength, t_min) or None each, `per` (which of edit, keep mask, keep x0,
+    layout hold a slice per sample), `gain` (fp32 numpy or None), `xt` (x-tilde or None), `order2`, `noise` (kind, payload) with
+    kind 'recorded' / 'seeds' / 'mix' / 'torch' (None for a single step: its caller draws).
+
+    Everything is validated here, in this order; each reader raises ValueError for a malformed option, SinddmError for a map
+    that does not match `img`, and NotImplementedError (NOT_BUILT) where noted:
+      1. a single step (`at`): strided or multistep (with CLIP, a jump), a jump (with CLIP)
+      2. `_few_step_cfg` (with CLIP, resample), then functions.stride_schedule and `_solver_q`
+      3. `_layout_entry` (with CLIP, resample); the entry is dropped when no step of the run pulls; then with order 2 / a jump
+      4. `_resample_cfg` (with CLIP), then functions.resample_schedule
+      5. `_seeds_for`, `_mix_for` (with CLIP): the noise source
+      6. `_keep_entry` (with CLIP)
+      7. `roi_edit_maps` and its batch, `_layout_gain_for`
+      8. the per-step scalars; x-tilde must be set when a step reads it"""
+
+    def __init__(self, d, img, s: int, t_seq, *, at=None, clip_denoised: bool = True):
+        s, t_seq = int(s), [int(t) for t in t_seq]
+        B, clip = int(img.shape[0]), bool(d.clip_guided_sampling)
+        pos0, j, land, q1 = at if at is not None else (0, None, None, None)
+        if land is not None or q1 is not None:
+            refuse(d, "strided_step", "clip_or_jump", clip or j is not None)
+        if j is not None:
+            refuse(d, "resample", "clip")
+        lands, q, jump_to = ([f(v)] if v is not None else None for f, v in ((int, land), (float, q1), (int, j)))
+        few = d._few_step_cfg(s) if at is None else None
+        if few is not None and t_seq:
+            t_seq, lands = stride_schedule(t_seq, few[0] if few[0] is not None else len(t_seq), few[1],
+                                           d._kappa(s) if few[1] == 'logsnr' else None)
+            q = d._solver_q(s, t_seq, lands) if few[2] == 2 else None
+        lay = d._layout_entry(s, img)
+        g = layout_strengths(t_seq, lay[2], lay[3]) if lay is not None else None
+        if lay is not None and any(v > 0.0 for v in g):
+            refuse(d, "layout_maps", "solver_order", q is not None)
+            refuse(d, "layout_maps", "resample", jump_to is not None)
+        else:
+            lay = None
+        rs = d._resample_cfg() if at is None else None
+        if rs is not None:
+            t_seq, jump_to = resample_schedule(t_seq, *rs)
+        self.noise = None
+        if at is None:
+            seeds, mix = d._seeds_for(s, B), d._mix_for(s, B)
+            self.noise = (("recorded", None) if d.noise_fn is not None else ("seeds", seeds) if seeds is not None
+                          else ("mix", mix) if mix is not None else ("torch", None))
+        keep = d._keep_entry(s, img)
+        roi = None
+        if d.roi_guided_sampling and s < d.n_scales - 1 and not clip:       # models.py:430-431 (the CLIP step edits on its own)
+            roi = d.roi_edit_maps(s, int(img.shape[-2]), int(img.shape[-1]), img.device)
+            if roi[0].dim() == 3 and roi[0].shape[0] != B:                 # (raw pointers: B slices are read)
+                raise ValueError(f"roi_bbs_batch has {roi[0].shape[0]} box lists, the batch {B} samples")
+        gain = d._layout_gain_for(B, "cpu") if lay is not None else None
+        self.s, self.t_seq, self.jump_to, self.halo, self.order2 = s, t_seq, jump_to, d._tile_halo(), q is not None
+        self.roi, self.keep, self.lay, self.gain = roi, keep, lay, gain.numpy() if gain is not None else None
+        self.per = (int(roi is not None and roi[0].dim() == 3), int(keep is not None and keep[0].dim() == 3),
+                    int(keep is not None and keep[1].dim() == 4), int(lay is not None and lay[0].dim() == 4))
+        tab, jt = d._coef_table(s, clip_denoised), d._jump_table(s) if jump_to is not None else None
+        ab_tab = d._keep_ab_table() if keep is not None else None
+        self.steps = []
+        for i, t in enumerate(t_seq):
+            u = t - 1 if lands is None else lands[i]
+            l2 = jump_to[i] if jump_to is not None else None
+            self.steps.append(Step(
+                pos=pos0 + i, t=t, land=u,
+                k=tab[t] if lands is None else d.step_coefs_to(t, u, s, clip_denoised, d.eta),
+                # (row l + 1 holds the forward scalars of level l, row 0 those of the clean image)
+                ab=tuple(float(v) for v in ab_tab[u + 1]) if keep is not None else (1.0, 0.0),
+                jump_to=l2, jump=_lib.JumpCoefs(1, *jt(t - 1, l2)) if l2 is not None else None,
+                g=g[i] if lay is not None else 0.0, q=q[i] if q is not None else None))
+        self.xt = None
+        if not clip and any(st.k.mode != 0 for st in self.steps):
+            if d.img_prev_upsample is None:
+                raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
+            self.xt = d.img_prev_upsample.contiguous()
+
+    def log_entry(self, seed: int):
+        """The `draw_log` entry of the run on the chain route with in-kernel draws (`seed`: the torch-seeded run's): draw i is
+        sinddm_normal_fill over the sample (the EXTENDED one when tiled) at stream i, a jump's second draw 2^31 above it."""
+        kind, src = self.noise
+        t, jumps = list(self.t_seq), list(self.jump_to) if self.jump_to is not None else None
+        if kind == "mix":
+            return ("chain_mix", self.s, (src[0], src[1]), t, jumps)
+        key = list(src) if kind == "seeds" else seed
+        if jumps is not None:
+            return ("chain_resample", self.s, key, t, jumps)
+        if kind == "seeds":
+            return ("chain_seeds", self.s, key, t)
+        return ("chain_tile", self.s, key, t, self.halo) if any(self.halo) else ("chain", self.s, key, t)
+
+
+def pack_steps(plan: RunPlan, i0: int, k: int):
+    """The host arrays of the steps [i0, i0 + k) of `plan` as a chain call takes them: `coefs`, `tl`, and `ab` (2 per step), `jumps`,
+    `g`, `q` -- None each when the run does not have the option."""
+    st = plan.steps[i0:i0 + k]
+    arr = lambda ctype, vals: (ctype * len(vals))(*vals)
+    return SimpleNamespace(
+        coefs=arr(_lib.StepCoefs, [r.k for r in st]), tl=arr(C.c_int, [r.t for r in st]),
+        ab=arr(C.c_float, [v for r in st for v in r.ab]) if plan.keep is not None else None,
+        jumps=arr(_lib.JumpCoefs, [_lib.JumpCoefs(0, 0.0, 0.0, 0.0) if r.jump is None else r.jump for r in st])
+        if plan.jump_to is not None else None,
+        g=arr(C.c_float, [r.g for r in st]) if plan.lay is not None else None,
+        q=arr(C.c_float, [r.q for r in st]) if plan.order2 else None)

@@ -1,6 +1,7 @@
 """Every sinddm_sample_chain* entry fills one description and runs one body: a narrower entry is sinddm_sample_chain_batch with
-the same options and NULL for the rest, bit for bit, and `_run_steps` -- which calls sinddm_sample_chain_batch alone -- computes
-what the narrow entry of each route computes.  dim 20, B = 3, steps [t, 1, 0] with a mode-1 t, on 8x12 (the tail fused into the
+the same options and NULL for the rest, bit for bit, and `_run_steps` -- which calls sinddm_sample_chain_batch for every run
+without multistep factors (sinddm_sample_chain_solver) or a seed blend (sinddm_sample_chain_mix) -- computes what the narrow
+entry of each route computes.  dim 20, B = 3, steps [t, 1, 0] with a mode-1 t, on 8x12 (the tail fused into the
 network's last kernel: H W % 4 == 0) and 5x7 (unfused: H W % 4 != 0, and dim 20 does not pad its rows; 5x39 under the halo)."""
 import ctypes as C
 
