@@ -102,6 +102,28 @@ int sinddm_debug_wgrad_map(int Cin, int Cout, int64_t ntiles, int ncu, uint32_t*
  * maxima of both operands exist.  out = { kernel, workgroups, S = pixel splits per slab (0 where the Winograd launch table
  * splits per slab), 1 if the kernel adds into the staging slab }.  Returns 0 or a negative SINDDM_E_*. */
 int sinddm_debug_wgrad_plan(int taps, int Cin, int Cout, int B, int H, int W, int have_scr, int have_amax, int ncu, int out[4]);
+/* ONE weight-gradient launch on caller tensors, as that plan describes it (ncu <= 0: the current device's compute units; any
+ * other count runs the grid a device of that size would get -- the result must not depend on it):
+ *   gw[co][ci][tap] += sum_{b,y,x} dout[b][co][y][x] * in[b][ci][y + ky - 1][x + kx - 1] (zero padding; taps = 1: the centre tap),
+ *   gb[co] += sum dout (gb may be NULL).
+ * The hook decides nothing: wgrad_plan routes, wgrad_launch launches, plan_out receives the four numbers of
+ * sinddm_debug_wgrad_plan.  scratch (256-byte aligned, >= sinddm_debug_wgrad_scratch_bytes) is cut into the 64-float zero page,
+ * the [co][tap][ci] staging slab when have_scr is set and taps = 9, and with use_amax two [B][8] arrays of per-sample maxima
+ * that the hook fills from dout and in as block_backward does for a dO nobody published.
+ * use_amax follows production (block_backward_plan): maxima reach a weight gradient only where the 3x3 convs beside it can
+ * run on conv_wh -- its data gradient (C_out -> C_in), conv2's data gradient of the same block (C_out -> C_out) and, for a
+ * conv1, its forward conv (C_in -> C_out): taps = 9, a staging slab, W % 4 == 0, C_in % 80 == 0 and C_out % 80 == 0.  conv_wh's
+ * size thresholds (pixels, items per CU) are tuning and are not mirrored: the kernel is valid at any size.
+ * Returns SINDDM_E_BADARG / SINDDM_E_BADSHAPE before any launch for a null pointer, a dimension < 1, taps outside {1, 9}, a
+ * scratch that is too small or not 256-byte aligned, dout / in not 16-byte aligned where the plan takes a wide kernel (4 or 5)
+ * or use_amax is set, a use_amax the rule above excludes, and sizes beyond the kernels' 32-bit indexing (B H W >= 2^30,
+ * max(C_in, C_out) H W >= 2^28, 9 C_in C_out >= 2^31; with use_amax B > 65535, the maxima kernel's grid).  A runtime error of
+ * a device call comes back as the positive hipError_t.  plan_out is written only when the launch went out (return 0).
+ * For kernel-level tests; training never calls it. */
+int sinddm_debug_wgrad(int taps, int Cin, int Cout, int B, int H, int W, int ncu, int have_scr, int use_amax, const float* dout,
+                       const float* in, float* gw, float* gb, void* scratch, size_t scratch_bytes, int plan_out[4], void* stream);
+/* bytes of scratch that hook needs at most (with a staging slab and maxima); 0 for arguments it refuses */
+size_t sinddm_debug_wgrad_scratch_bytes(int taps, int Cin, int Cout, int B);
 /* Host-only: the same four numbers for the 17 weight-gradient launches of sinddm_net_backward of this shape, in launch
  * order -- the final 1x1, then for block 3, 2, 1, 0: conv2, the residual 1x1 (all four -1 under an identity residual),
  * conv1, depthwise (workgroups = C_in * B) -- into out[4 * launch + 0..3]; cap (ints in out) >= 68.  `ncu` sizes the

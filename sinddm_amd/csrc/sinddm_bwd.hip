@@ -1321,6 +1321,61 @@ int sinddm_debug_wgrad_plan(int taps, int Cin, int Cout, int B, int H, int W, in
     return 0;
 }
 
+// the three regions sinddm_debug_wgrad carves from its scratch, each rounded to 256 bytes
+static size_t wgrad_debug_slab_bytes(int Cin, int Cout) { return au((size_t)Cout * Cin * 9 * sizeof(float)); }
+static size_t wgrad_debug_amax_bytes(int B) { return au((size_t)B * AMAX_STRIDE * sizeof(float)); }
+
+size_t sinddm_debug_wgrad_scratch_bytes(int taps, int Cin, int Cout, int B) {
+    if ((taps != 1 && taps != 9) || Cin < 1 || Cout < 1 || B < 1 || (long long)Cin * Cout * 9 > 0x7fffffffLL) return 0;
+    return au(64 * sizeof(float)) + (taps == 9 ? wgrad_debug_slab_bytes(Cin, Cout) : 0) + 2 * wgrad_debug_amax_bytes(B);
+}
+
+int sinddm_debug_wgrad(int taps, int Cin, int Cout, int B, int H, int W, int ncu, int have_scr, int use_amax, const float* dout,
+                       const float* in, float* gw, float* gb, void* scratch, size_t scratch_bytes, int plan_out[4], void* stream) {
+    if (!dout || !in || !gw || !scratch || !plan_out) return SINDDM_E_BADARG;
+    if ((taps != 1 && taps != 9) || Cin < 1 || Cout < 1 || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    // what the kernels index with 32-bit integers: tiles and pixels of the launch, elements of the gradient, and one sample's
+    // operands as buffers whose out-of-range marker is 2^30 bytes (the generic kernel describes all channels of a sample)
+    if ((long long)B * H * W > 0x3fffffffLL || (long long)Cin * Cout * 9 > 0x7fffffffLL ||
+        (long long)(Cin > Cout ? Cin : Cout) * H * W * 4 >= 0x40000000LL)
+        return SINDDM_E_BADSHAPE;
+    if (use_amax) {
+        // the rule of block_backward_plan: maxima reach a weight gradient only beside 3x3 convs that conv3x3_route gives to
+        // conv_wh -- its own data gradient, conv2's data gradient of the same block and (conv1) its forward conv
+        if (taps != 9 || !have_scr || !wh_enabled() || !SINDDM_WGRAD_WH) return SINDDM_E_BADARG;
+        if (W % 4 != 0 || !wh_plan_ok(Cin, Cout) || !wh_plan_ok(Cout, Cin) || !wh_plan_ok(Cout, Cout)) return SINDDM_E_BADSHAPE;
+        if (B > 65535) return SINDDM_E_BADSHAPE;    // amax_tensor_launch puts the sample into gridDim.y
+    }
+    const size_t slab = have_scr && taps == 9 ? wgrad_debug_slab_bytes(Cin, Cout) : 0, amax = use_amax ? wgrad_debug_amax_bytes(B) : 0;
+    if (scratch_bytes < au(64 * sizeof(float)) + slab + 2 * amax) return SINDDM_E_BADARG;
+    const WgradPlan p = wgrad_plan(taps, Cin, Cout, B, H, W, have_scr != 0, use_amax != 0, ncu > 0 ? ncu : cu_count());
+    // 16-byte loads: the wide Winograd kernels' LDS-DMA and amax_tensor_kernel; the scratch regions are cut at 256 bytes
+    const uintptr_t al = p.kernel >= WGRAD_WINO_WIDE || use_amax ? 16 : 4;
+    if ((uintptr_t)scratch % 256 != 0 || (uintptr_t)gw % 4 != 0 || (uintptr_t)gb % 4 != 0 || (uintptr_t)dout % al != 0 ||
+        (uintptr_t)in % al != 0)
+        return SINDDM_E_BADARG;
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* base = static_cast<char*>(scratch);
+    float* zero = reinterpret_cast<float*>(base);
+    float* scr = slab ? reinterpret_cast<float*>(base + au(64 * sizeof(float))) : nullptr;
+    float* amax_d = amax ? reinterpret_cast<float*>(base + au(64 * sizeof(float)) + slab) : nullptr;
+    float* amax_i = amax ? amax_d + amax / sizeof(float) : nullptr;
+    // a runtime error comes back as wgrad_launch returns it: the positive hipError_t
+    hipError_t e = hipMemsetAsync(zero, 0, 64 * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    if (use_amax) {
+        e = hipMemsetAsync(amax_d, 0, 2 * amax, st);
+        if (e != hipSuccess) return (int)e;
+        int rc = amax_tensor_launch(dout, amax_d, B, (long long)Cout * H * W, st);
+        if (!rc) rc = amax_tensor_launch(in, amax_i, B, (long long)Cin * H * W, st);
+        if (rc) return rc;
+    }
+    const int rc = wgrad_launch(p, zero, dout, in, gw, gb, st, scr, amax_d, amax_i);
+    if (!rc) wgrad_report(p, plan_out);          // only a launch that went out is reported
+    return rc;
+}
+
 int sinddm_debug_wgrad_routes(int dim_arg, int B, int H, int W, int ncu, int* out, int cap) {
     NetPlan p = make_plan(dim_arg);
     if (!p.ok || !out || cap < 4 * 17 || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;

@@ -132,6 +132,15 @@ def test_existing_numeric_tests_cover_every_kernel():
     shapes.append((160, 8, 186, 248))
     seen = {launch[0] for s in shapes for launch in wgrad_routes(lib, *s)}
     assert set(range(GENERIC, WINO_H16 + 1)) <= seen, seen
+    # ... and by a test of ONE launch on exact inputs (tests/test_gpu_wgrad_kernels.py): the union over its table, per grid
+    from wgrad_util import c1_cases
+    for ncu in NCUS:
+        alone = set()
+        for kernel, taps, cin, cout, B, H, W, scr, amax, variant in c1_cases():
+            out = (C.c_int * 4)()
+            assert lib.sinddm_debug_wgrad_plan(taps, cin, cout, B, H, W, scr, amax, ncu, out) == 0
+            alone.add(out[0])
+        assert alone == set(range(GENERIC, WINO_H16 + 1)), (ncu, alone)
 
 
 def test_bad_arguments():
