@@ -603,6 +603,20 @@ int sinddm_l1_loss_fwd_bwd(const float* noise, const float* eps, float* loss_out
 int sinddm_l1_loss_crop_fwd_bwd(const float* noise, const float* eps_ext, float* loss_out, float* grad_out_ext,
                                 int BC, int H, int W, int halo_y, int halo_x, float grad_scale, void* stream);
 
+/* sinddm_l1_loss_crop_fwd_bwd with a per-pixel weight map -- masked training.  noise is (B,C,H,W); eps_ext and grad_out_ext
+ * are (B,C,H + 2 halo_y,W + 2 halo_x), a halo of (0,0) being the untiled case; weight is an (H,W) fp32 device map shared by
+ * samples and channels, finite and >= 0 (the caller's contract).  inv_norm = 1 / (B*C*sum(weight)), computed by the caller
+ * (float64 on the host, once per scale): the kernel makes one pass and divides nothing.
+ * loss_out[0] += inv_norm * sum over the centre of weight[y,x] * |noise - eps| (caller zeroes loss_out; a second call adds);
+ * if grad_out_ext != NULL it is written everywhere: (-sign(noise - eps) * inv_norm * grad_scale) * weight[y,x] on the centre,
+ * exactly 0 on the halo -- the buffer need not be cleared.  An element with weight == 0 is skipped: whatever its noise
+ * and eps hold (a NaN, an Inf) cannot reach the loss, and its gradient is exactly 0.
+ * SINDDM_E_BADARG: a null noise / eps_ext / weight / loss_out, non-positive sizes, H or W above 2^30, a negative halo, an
+ * element count beyond int64, an inv_norm that is not finite and positive. */
+int sinddm_l1_loss_weighted_fwd_bwd(const float* noise, const float* eps_ext, const float* weight, float* loss_out,
+                                    float* grad_out_ext, int B, int C, int H, int W, int halo_y, int halo_x, float inv_norm,
+                                    float grad_scale, void* stream);
+
 /* Fused optimizer / EMA over flat buffers of n floats.  mode bits: 1 = Adam update of p from g
  * (torch.optim.Adam defaults, reference trainer.py:134,208; step_size = lr/(1-beta1^k),
  * bc2_sqrt = sqrt(1-beta2^k)); 2 = ema := p (copy phase, trainer.py:156-158);

@@ -19,6 +19,16 @@ cylindrical panoramas (`--tile x --scale_mul 1 4`).  All five modes honour it.
 `--train_tile {none,x,y,xy}` (no reference flag) TRAINS with borders that wrap around on the named axes, so the weights have seen
 the seam `--tile` later asks them for; the intended pairing is `--mode train --tile xy --train_tile xy`.  It changes the
 training step only (`--tile` alone keeps sampling from zero-padding-trained weights), and is not stored in checkpoints.
+`--train_mask FILE` (no reference flag) TRAINS on the white part of FILE only (white = train on, black = ignore: a scratch, a
+watermark, an object to remove; the file is brought to the finest scale's size the way `--mask_path` is): the loss becomes the
+weighted mean over the valid pixels of every scale, and with `--train_mask_fill mean` (the default; `image` leaves the picture
+alone) the hole pixels of the training images are replaced by the mean of the valid ones.  `--train_mask_grow N [N ...]` (one
+value, or one per scale; default 0) grows the hole by N pixels of each scale before the loss is switched off.  The network's
+receptive field is a square of radius 16, so with N = 16 the weights provably never see the hole; coarse scales may not survive
+that (a scale left without a valid pixel is an error), so give one value per scale, for example `0 0 4 8 16`.  The pyramid
+files on disk stay as they are: their down-scaling smears hole content a few pixels outward, which is what N is for.  The
+intended pairing is `--mode train --train_mask hole.png`, then `--mode inpaint --mask_path hole.png`.  Like `--train_tile`
+the flags change the training step only (the other modes accept and ignore them) and are not stored in checkpoints.
 `inpaint` and `outpaint` (no reference modes) keep some pixels exactly and generate the rest to fit, by replacing the
 known region after every reverse step inside the step kernels: `--mode inpaint --mask_path FILE [--soft_mask]` fills the
 black part of the mask (white = keep the training image's pixel; the file is brought to the finest scale's size);
@@ -133,6 +143,10 @@ def build_parser():
     p.add_argument("--tile", choices=("none", "x", "y", "xy"), default="none")
     # the training half of --tile (MultiScaleGaussianDiffusion.train_tile): p_losses wraps the named axes around
     p.add_argument("--train_tile", choices=("none", "x", "y", "xy"), default="none")
+    # the training half of `inpaint` (MultiScaleGaussianDiffusion.train_weights): the loss ignores the black part of the mask
+    p.add_argument("--train_mask", type=str, default=None, metavar="FILE")
+    p.add_argument("--train_mask_grow", type=int, nargs="+", default=[0], metavar="N")
+    p.add_argument("--train_mask_fill", choices=("mean", "image"), default="mean")
     # no reference flags: per-sample noise seeds (MultiScaleGaussianDiffusion.sample_seeds) of every sampling mode
     g = p.add_mutually_exclusive_group()
     g.add_argument("--seeds", type=int, nargs="+", default=None)
@@ -200,6 +214,8 @@ def parse_args(argv=None):
         p.error("--resample and --jump_length must be >= 1")
     if args.sample_steps is not None and min(args.sample_steps) < 1:
         p.error("--sample_steps must be >= 1")
+    if min(args.train_mask_grow) < 0:
+        p.error("--train_mask_grow must be >= 0")
     if args.eta < 0.0:
         p.error("--eta must be >= 0")
     if not 1 <= args.layout_down <= 64:
@@ -266,13 +282,26 @@ def main():
 
     sample_t_list = ms_diffusion.num_timesteps_ideal[1:] if args.sample_t_list is None else args.sample_t_list
 
+    mask_kw = {}
+    if args.train_mask and args.mode == 'train':                           # (the other modes never train: nothing to mask)
+        import numpy as np
+        from PIL import Image
+        if len(args.train_mask_grow) not in (1, n_scales):
+            raise SystemExit(f"--train_mask_grow: {len(args.train_mask_grow)} values for {n_scales} scales (give one, or one per "
+                             "scale)")
+        h, w = ms_diffusion.image_sizes[n_scales - 1]
+        valid = torch.from_numpy((np.asarray(Image.open(args.train_mask).convert("L").resize((w, h), Image.NEAREST)) > 127)
+                                 .astype(np.float32))
+        mask_kw = dict(train_mask=valid, train_mask_fill=args.train_mask_fill,
+                       train_mask_grow=args.train_mask_grow[0] if len(args.train_mask_grow) == 1 else list(args.train_mask_grow))
+
     trainer = MultiscaleTrainer(
         ms_diffusion, folder=args.dataset_folder, n_scales=n_scales, scale_factor=scale_factor, image_sizes=sizes,
         train_batch_size=args.train_batch_size, train_lr=args.train_lr, train_num_steps=args.train_num_steps,
         gradient_accumulate_every=args.grad_accumulate, ema_decay=0.995, fp16=False,
         save_and_sample_every=args.save_and_sample_every, avg_window=args.avg_window,
         sched_milestones=sched_milestones, results_folder=results_folder, device=device,
-        train_tile=("y" in args.train_tile, "x" in args.train_tile))
+        train_tile=("y" in args.train_tile, "x" in args.train_tile), **mask_kw)
 
     # a sampling option (training is governed by --train_tile): every mode below samples with the EMA model
     trainer.ema_model.tile = ("y" in args.tile, "x" in args.tile)

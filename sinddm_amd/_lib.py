@@ -33,6 +33,7 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_solver", "sinddm_reverse_step_ms",
     "sinddm_q_sample_wrap", "sinddm_l1_loss_crop_fwd_bwd",
     "sinddm_sample_chain_mix", "sinddm_normal_fill_mix",
+    "sinddm_l1_loss_weighted_fwd_bwd",
 )
 
 
@@ -198,6 +199,7 @@ def load() -> C.CDLL:
         "sinddm_net_backward": (i, [p, p, p, p, p, p, p, i, i, i, i, p, sz, p]),
         "sinddm_l1_loss_fwd_bwd": (i, [p, p, p, p, i64, f, p]),
         "sinddm_l1_loss_crop_fwd_bwd": (i, [p, p, p, p, i, i, i, i, i, f, p]),
+        "sinddm_l1_loss_weighted_fwd_bwd": (i, [p, p, p, p, p, i, i, i, i, i, i, f, f, p]),
         "sinddm_adam_ema_step": (i, [p, p, p, p, p, f, f, f, f, f, f, f, i, i64, p]),
     }
     for name, (res, args) in sig.items():

@@ -124,3 +124,40 @@ def l1_loss_crop(noise, eps_ext, halo):
     """mean(|noise - centre(eps_ext)|) of tileable training: `eps_ext` is the network's output on the image extended by the
     wrapped halo `halo` = (halo_y, halo_x); its gradient has the extended shape and is 0 on the halo."""
     return _L1CropFn.apply(noise, eps_ext, halo)
+
+
+class _L1WeightedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, noise, eps_ext, weight, inv_norm, halo):
+        lib = _lib.load()
+        noise = noise.contiguous()
+        eps_ext = eps_ext.contiguous()
+        hy, hx = int(halo[0]), int(halo[1])
+        if noise.dim() != 4:
+            raise _lib.SinddmError(f"l1_loss_weighted: noise must be (B,C,H,W), got {tuple(noise.shape)}")
+        B, Cc, H, W = (int(v) for v in noise.shape)
+        if tuple(eps_ext.shape) != (B, Cc, H + 2 * hy, W + 2 * hx):
+            raise _lib.SinddmError(f"l1_loss_weighted: eps {tuple(eps_ext.shape)} is not noise {tuple(noise.shape)} extended "
+                                   f"by the halo {(hy, hx)}")
+        if tuple(weight.shape) != (H, W) or weight.dtype != torch.float32 or weight.device != eps_ext.device:
+            raise _lib.SinddmError(f"l1_loss_weighted: the weight map must be a {(H, W)} fp32 tensor on {eps_ext.device}, got "
+                                   f"{tuple(weight.shape)} {weight.dtype} on {weight.device}")
+        loss = torch.zeros((), dtype=torch.float32, device=eps_ext.device)
+        g = torch.empty_like(eps_ext)                  # the kernel writes the zeros of the halo and of the holes itself
+        _lib.check(lib.sinddm_l1_loss_weighted_fwd_bwd(_lib.ptr(noise), _lib.ptr(eps_ext), _lib.ptr(weight.contiguous()),
+                                                       _lib.ptr(loss), _lib.ptr(g), B, Cc, H, W, hy, hx, float(inv_norm), 1.0,
+                                                       _lib.stream_ptr(eps_ext.device)), "sinddm_l1_loss_weighted_fwd_bwd")
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (g,) = ctx.saved_tensors
+        return None, g * grad_loss, None, None, None
+
+
+def l1_loss_weighted(noise, eps_ext, weight, inv_norm, halo=(0, 0)):
+    """sum(w |noise - centre(eps_ext)|) * inv_norm of masked training: `weight` is the (H,W) fp32 map w >= 0 shared by samples
+    and channels, `inv_norm` = 1 / (B C sum w) from the caller; where w == 0 nothing is read and the gradient is exactly 0.
+    `halo` as in l1_loss_crop: (0, 0) is the untiled step."""
+    return _L1WeightedFn.apply(noise, eps_ext, weight, inv_norm, halo)

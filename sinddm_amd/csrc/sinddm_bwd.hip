@@ -855,6 +855,70 @@ __global__ __launch_bounds__(256) void l1_loss_crop_kernel(const float* __restri
     if (threadIdx.x == 0) atomicAdd(loss, ((red[0] + red[1]) + (red[2] + red[3])) * inv_n);
 }
 
+// l1_loss_crop_kernel with a per-pixel weight map w [H][W] (fp32, finite, >= 0; shared by samples and channels: H * W floats,
+// L2-resident) -- masked training.  loss += inv_norm * sum over the centre of w * |noise - eps|, inv_norm = 1 / (BC * sum w)
+// from the caller (float64 on the host, once per scale: no second pass and no division here); the gradient is
+// l1_grad_elem * w on the centre and 0 on the halo.  An element with w == 0 is SKIPPED by a select, never by a product: what
+// noise and eps hold there (a NaN, an Inf) cannot reach the loss, and its gradient is exactly 0.
+// The index walk and the shape of the reduction are l1_loss_crop_kernel's.  The block and the grid are not: this loss is
+// held to 1e-6 of the float64 sum, and the block partials meet in loss[0] by serial fp32 atomics, each rounding at the
+// running sum's ulp.  This reduction restated in numpy on 270 000 elements (a simulation with the atomics in random order,
+// not a device run of a 1024-block kernel): 1024 partials leave 6e-7 rms, beyond 1e-6 in 4 runs of 60; 128 leave 1.8e-7;
+// 64 leave 1.3e-7, and 1.9e-7 when a second call adds to the first -- a fifth of the bound.  So at most L1W_BLOCKS blocks
+// of L1W_THREADS threads, and the loads the missing blocks would have had in flight come from L1W_UNROLL independent
+// elements per thread instead: every address is clamped into its buffer, so all loads of a round are unconditional and
+// issue before the first use (a streaming kernel has nothing else to hide them under).  IDX is the type the element index
+// is divided in: unsigned wherever n_ext fits (two 32-bit divisions per element instead of two emulated 64-bit ones, which
+// with this few waves would be the kernel's time), long long beyond.
+constexpr int L1W_BLOCKS = 64;
+constexpr int L1W_THREADS = 512;
+constexpr int L1W_UNROLL = 8;
+
+template <typename IDX>
+__global__ __launch_bounds__(L1W_THREADS) void l1_loss_weighted_kernel(const float* __restrict__ noise,
+                                                                       const float* __restrict__ eps,
+                                                                       const float* __restrict__ wmap, float* __restrict__ loss,
+                                                                       float* __restrict__ grad, long long n_ext, int H, int W,
+                                                                       int hy, int hx, float inv_norm, float gscale) {
+    static_assert(L1W_THREADS == 512, "the pairwise sum of the wave partials below is written out for 8 waves");
+    __shared__ float red[L1W_THREADS / 64];
+    const int He = H + 2 * hy, We = W + 2 * hx;
+    const long long stride = (long long)gridDim.x * L1W_THREADS;
+    float s = 0.f;
+    for (long long i0 = (long long)blockIdx.x * L1W_THREADS + threadIdx.x; i0 < n_ext; i0 += stride * L1W_UNROLL) {
+        float nv[L1W_UNROLL], ev[L1W_UNROLL], wv[L1W_UNROLL];
+        bool live[L1W_UNROLL], centre[L1W_UNROLL];
+#pragma unroll
+        for (int u = 0; u < L1W_UNROLL; ++u) {
+            const long long i = i0 + u * stride;
+            live[u] = i < n_ext;
+            const long long ic = live[u] ? i : n_ext - 1;
+            const IDX row = (IDX)ic / (IDX)We;
+            const int x = (int)((IDX)ic - row * (IDX)We) - hx;
+            const IDX bc = row / (IDX)He;
+            const int y = (int)(row - bc * (IDX)He) - hy;
+            centre[u] = live[u] && y >= 0 && y < H && x >= 0 && x < W;
+            const int yc = min(max(y, 0), H - 1), xc = min(max(x, 0), W - 1);
+            wv[u] = wmap[(size_t)yc * W + xc];
+            nv[u] = noise[((size_t)bc * H + yc) * W + xc];
+            ev[u] = eps[ic];
+        }
+#pragma unroll
+        for (int u = 0; u < L1W_UNROLL; ++u) {
+            const bool on = centre[u] && wv[u] > 0.f;
+            const float d = nv[u] - ev[u];
+            s += on ? wv[u] * fabsf(d) : 0.f;
+            if (grad && live[u]) grad[i0 + u * stride] = on ? l1_grad_elem(d, inv_norm, gscale) * wv[u] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        atomicAdd(loss, (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) * inv_norm);
+}
+
 __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v,
                                                        float* __restrict__ ema, float step_size, float b1, float b2,
@@ -1219,6 +1283,26 @@ int sinddm_l1_loss_crop_fwd_bwd(const float* noise, const float* eps_ext, float*
     if (bx > 1024) bx = 1024;
     hipLaunchKernelGGL(l1_loss_crop_kernel, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream), noise, eps_ext,
                        loss_out, grad_out_ext, n_ext, H, W, halo_y, halo_x, 1.0f / (float)n, grad_scale);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sinddm_l1_loss_weighted_fwd_bwd(const float* noise, const float* eps_ext, const float* weight, float* loss_out,
+                                    float* grad_out_ext, int B, int C, int H, int W, int halo_y, int halo_x, float inv_norm,
+                                    float grad_scale, void* stream) {
+    if (!noise || !eps_ext || !weight || !loss_out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || halo_y < 0 || halo_x < 0 ||
+        halo_y > (1 << 20) || halo_x > (1 << 20) || H > (1 << 30) || W > (1 << 30) || !(inv_norm > 0.f) ||
+        !(inv_norm <= 3.402823466e+38f))
+        return SINDDM_E_BADARG;
+    // H, W <= 2^30 and a halo <= 2^20: the extended sizes fit an int; the element count must fit a long long
+    const long long bc = (long long)B * C, plane = (long long)(H + 2 * halo_y) * (W + 2 * halo_x);
+    if (bc > 0x7fffffffffffffffLL / plane) return SINDDM_E_BADARG;
+    const long long n_ext = bc * plane;
+    long long bx = (n_ext + L1W_THREADS - 1) / L1W_THREADS;
+    if (bx > L1W_BLOCKS) bx = L1W_BLOCKS;
+    auto kern = n_ext <= 0x7fffffffLL ? l1_loss_weighted_kernel<unsigned> : l1_loss_weighted_kernel<long long>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)bx), dim3(L1W_THREADS), 0, static_cast<hipStream_t>(stream), noise, eps_ext, weight,
+                       loss_out, grad_out_ext, n_ext, H, W, halo_y, halo_x, inv_norm, grad_scale);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }

@@ -174,6 +174,71 @@ def keep_mask_pyramid(mask, sizes, hard: bool = True, batch: bool = False) -> Li
     return out
 
 
+# ---- helpers of masked training (MultiScaleGaussianDiffusion.train_weights; no reference counterpart) ----------------
+def _grow_1d(hole: np.ndarray, g: int, axis: int, wrap: bool) -> np.ndarray:
+    """Boolean dilation of `hole` by `g` pixels to both sides along `axis`: across the border, modulo the size, with `wrap`;
+    stopping at it otherwise.  A windowed sum over the padded array: exact integer arithmetic."""
+    n = hole.shape[axis]
+    if g == 0:
+        return hole
+    g = min(g, n)                                        # g >= n covers the whole axis either way
+    pad = [(0, 0), (0, 0)]
+    pad[axis] = (g, g)
+    padded = np.pad(hole.astype(np.int64), pad, mode="wrap" if wrap else "constant")
+    c = np.cumsum(padded, axis=axis)
+    zero = np.zeros_like(np.take(c, [0], axis=axis))
+    c = np.concatenate([zero, c], axis=axis)
+    return (np.take(c, np.arange(2 * g + 1, 2 * g + 1 + n), axis=axis) - np.take(c, np.arange(0, n), axis=axis)) > 0
+
+
+def train_weight_pyramid(valid, sizes, grow=0, wrap=(False, False)) -> List[torch.Tensor]:
+    """The loss weights of masked training, one fp32 {0,1} (h, w) map per entry of `sizes`, on the device of `valid`.
+    `valid` is an (H, W) {0,1} map at the finest size, 1 = train on this pixel.  Each scale's map is
+    keep_mask_pyramid(hard=True) -- a coarse pixel whose footprint touches the hole is out -- with the hole then dilated by
+    `grow` pixels OF THAT SCALE (an int, or one value per scale) by a square structuring element: the network's receptive
+    field is a square of Chebyshev radius 16 (SINDDM_TILE_HALO), so with grow = 16 no pixel that trains has a hole pixel in
+    view, and the weights provably never see what the hole contains.  On an axis of `wrap` = (wrap_y, wrap_x) -- the
+    `train_tile` of the run -- the hole grows across the border, modulo the size; otherwise it stops there.
+    ValueError: a negative grow, a list of another length than `sizes`, a mask that is not (H, W), a scale left without a
+    valid pixel (named: coarse scales may not survive a large grow -- give one value per scale)."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    grows = [int(grow)] * len(sizes) if np.ndim(grow) == 0 else [int(g) for g in grow]
+    if len(grows) != len(sizes):
+        raise ValueError(f"train_weight_pyramid: {len(grows)} grow values for {len(sizes)} scales (give one, or one per scale)")
+    if any(g < 0 for g in grows):
+        raise ValueError(f"train_weight_pyramid: grow {grows} must be >= 0")
+    m = torch.as_tensor(valid)
+    if m.dim() != 2:
+        raise ValueError(f"train_weight_pyramid: the mask must be (H, W), got {tuple(m.shape)}")
+    out = []
+    for s, (hard, g) in enumerate(zip(keep_mask_pyramid(m, sizes, hard=True), grows)):
+        hole = hard.cpu().numpy() < 0.5
+        hole = _grow_1d(_grow_1d(hole, g, 0, bool(wrap[0])), g, 1, bool(wrap[1]))
+        if bool(hole.all()):
+            raise ValueError(f"train_weight_pyramid: scale {s} {sizes[s]} has no valid pixel left with grow = {g}")
+        out.append(torch.from_numpy((~hole).astype(np.float32)).to(m.device))
+    return out
+
+
+def fill_train_holes(img: torch.Tensor, hard_valid: torch.Tensor, fill: str = "mean") -> torch.Tensor:
+    """A copy of the (..., C, h, w) image(s) `img` of one scale with the hole pixels (`hard_valid` (h, w) == 0: the UN-grown
+    hard mask of the scale) replaced: fill = 'mean' writes the per-channel mean of the image's valid pixels (float64,
+    rounded to the image's dtype), so that what the network sees inside the hole is flat instead of the damage; 'image'
+    leaves the picture as it is.  The valid pixels are returned bit for bit."""
+    if fill not in ("mean", "image"):
+        raise ValueError(f"fill_train_holes: fill {fill!r} is neither 'mean' nor 'image'")
+    v = torch.as_tensor(hard_valid).to(img.device) > 0.5
+    if img.dim() < 3 or tuple(v.shape) != tuple(img.shape[-2:]):
+        raise ValueError(f"fill_train_holes: mask {tuple(v.shape)} against an image {tuple(img.shape)}")
+    if fill == "image" or bool(v.all()):
+        return img.clone()
+    if not bool(v.any()):
+        raise ValueError("fill_train_holes: no valid pixel to take the mean of")
+    img64 = img.to(torch.float64)
+    mean = torch.where(v, img64, torch.zeros_like(img64)).sum(dim=(-2, -1), keepdim=True) / float(v.sum())
+    return torch.where(v, img, mean.to(img.dtype).expand_as(img))
+
+
 def outpaint_offset(canvas, image, anchor=(0.5, 0.5)) -> Tuple[int, int]:
     """Top-left corner (y, x) of an (h, w) image placed on an (H, W) canvas: int(anchor * (canvas - image)) per axis;
     anchor (0, 0) = top left, (0.5, 0.5) = centred, (1, 1) = bottom right."""

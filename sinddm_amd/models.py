@@ -667,6 +667,14 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # then the circularly padded network's).  Separate from `tile`, which p_losses does not read; not
         # stored in checkpoints.
         self.train_tile = (False, False)
+        # masked training (no reference counterpart): None, or one (h,w) fp32 map per scale on the training device, finite and
+        # >= 0.  p_losses then takes sum(w e) / (B C sum w) instead of the mean over every pixel, e the loss type's
+        # per-element error: where w == 0 the image never reaches the weights -- and, the receptive field being a square of
+        # Chebyshev radius SINDDM_TILE_HALO, with w == 0 within that distance of a hole the weights provably never see what
+        # the hole contains (functions.train_weight_pyramid builds such maps).  Replace the list to change a
+        # map (the normaliser is cached per scale and map object).  Not stored in checkpoints.
+        self.train_weights = None
+        self._train_weight_norm = {}
         # known-region conditioning (inpainting / outpainting): None or {s: (mask (H,W), x0 (3,H,W))}, fp32, on the sample's
         # device.  At a scale with an entry every reverse step overwrites the pixels whose mask is 1 with the
         # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
@@ -1561,6 +1569,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         else:
             x_noisy = self._q_sample_impl(x_start, t, 0, noise)
         x_recon = self.denoise_fn(x_noisy, t, int(s))
+        if self.train_weights is not None:
+            return self._weighted_loss(noise, x_recon, x_start, x_orig, t, s, (0, 0))
         if self.loss_type == 'l1':                                          # what main.py:97 selects: fused loss + seed kernel
             from .autograd import l1_loss
             return l1_loss(noise, x_recon)
@@ -1591,6 +1601,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
         else:
             x_noisy = self._q_sample_wrap_impl(x_start, t, noise, halo)
         x_recon = self.denoise_fn(x_noisy, t, int(s))                       # extended
+        if self.train_weights is not None:
+            return self._weighted_loss(noise, x_recon, x_start, x_orig, t, s, halo)
         if self.loss_type == 'l1':
             from .autograd import l1_loss_crop
             return l1_loss_crop(noise, x_recon, halo)
@@ -1606,6 +1618,48 @@ class MultiScaleGaussianDiffusion(nn.Module):
         else:
             x_mix_prev = x_start
         return (x_mix_prev - x_recon).abs().mean()
+
+    def _train_weight(self, s, shape):
+        """(w, sum w) of scale `s` for a (B,C,H,W) batch: the map of `train_weights` and its float64 sum, taken on the host
+        once per scale and map object (one device-to-host copy, then none)."""
+        if int(s) >= len(self.train_weights):
+            raise _lib.SinddmError(f"train_weights holds {len(self.train_weights)} maps: none for scale {int(s)}")
+        w = self.train_weights[int(s)]
+        hw = (int(shape[2]), int(shape[3]))
+        if not torch.is_tensor(w) or tuple(w.shape) != hw or w.dtype != torch.float32:
+            raise _lib.SinddmError(f"train_weights[{int(s)}] must be a {hw} fp32 tensor, got "
+                                   f"{tuple(w.shape) if torch.is_tensor(w) else type(w).__name__}")
+        hit = self._train_weight_norm.get(int(s))
+        if hit is None or hit[0] is not w:
+            total = float(w.detach().to("cpu", torch.float64).sum())
+            if not (total > 0.0 and total < float("inf")):
+                raise _lib.SinddmError(f"train_weights[{int(s)}] sums to {total}: scale {int(s)} has no pixel to train on")
+            hit = self._train_weight_norm[int(s)] = (w, total)
+        return w, hit[1]
+
+    def _weighted_loss(self, noise, x_recon, x_start, x_orig, t, s, halo):
+        """The loss of p_losses / _p_losses_tiled under `train_weights`: sum(w e) / (B C sum w).  'l1' is one fused kernel
+        (sinddm_l1_loss_weighted_fwd_bwd: loss, gradient, the halo's and the holes' zeros); the two loss types main.py never
+        selects are torch ops on the centre, as they are without weights."""
+        w, total = self._train_weight(s, x_start.shape)
+        B, Cc, H, W = (int(v) for v in x_start.shape)
+        inv_norm = 1.0 / (B * Cc * total)
+        if self.loss_type == 'l1':
+            from .autograd import l1_loss_weighted
+            return l1_loss_weighted(noise, x_recon, w, inv_norm, halo)
+        hy, hx = halo
+        x_recon = x_recon[:, :, hy:hy + H, hx:hx + W]                       # (its backward zero-fills the halo)
+        if self.loss_type == 'l2':
+            return ((noise - x_recon) ** 2 * w).sum() * inv_norm
+        if int(s) > 0:
+            if int(t[0]) > 0:
+                g = extract(self.gammas[int(s) - 1].reshape(-1), t - 1, x_start.shape)
+                x_mix_prev = g * x_start + (1 - g) * x_orig
+            else:
+                x_mix_prev = x_orig
+        else:
+            x_mix_prev = x_start
+        return ((x_mix_prev - x_recon).abs() * w).sum() * inv_norm
 
     def forward(self, x, s, *args, **kwargs):                              # models.py:613-631
         s = int(s)

@@ -90,7 +90,7 @@ class MultiscaleTrainer(object):
                  image_sizes=None, train_batch_size=32, train_lr=2e-5, train_num_steps=100000,
                  gradient_accumulate_every=2, fp16=False, step_start_ema=2000, update_ema_every=10,
                  save_and_sample_every=25000, avg_window=100, sched_milestones=None, results_folder='./results',
-                 device=None, train_tile=(False, False)):
+                 device=None, train_tile=(False, False), train_mask=None, train_mask_grow=0, train_mask_fill='mean'):
         super().__init__()
         self.device = device
         self.sched_milestones = [10000, 30000, 60000, 80000, 90000] if sched_milestones is None else sched_milestones
@@ -139,6 +139,26 @@ class MultiscaleTrainer(object):
                 self.data_list.append((rep(item[0]), rep(item[1])))
             else:
                 self.data_list.append((rep(item), rep(item)))
+
+        # masked training: `train_mask` is an (H, W) {0,1} map at the finest size, 1 = train on this pixel.  The model that
+        # trains gets one loss-weight map per scale (the hole grown by `train_mask_grow` pixels of each scale, across the
+        # borders `train_tile` wraps), and with train_mask_fill = 'mean' the hole pixels of the training images -- the image
+        # and its _recon partner -- are replaced by the mean of their valid pixels ('image' leaves them).  The EMA copy
+        # never trains.  Every rank holds the same maps and normalises by its own B_local C sum(w); `loss_weight` does the rest.
+        self.train_mask_hard = None
+        if train_mask is not None:
+            from .functions import fill_train_holes, keep_mask_pyramid, train_weight_pyramid
+            if train_mask_fill not in ('mean', 'image'):
+                raise ValueError(f"train_mask_fill {train_mask_fill!r} is neither 'mean' nor 'image'")
+            sizes = [tuple(int(v) for v in self.model.image_sizes[i]) for i in range(n_scales)]      # (h, w) per scale
+            valid = torch.as_tensor(train_mask).detach().to('cpu', torch.float32)
+            if tuple(valid.shape) != sizes[-1]:
+                raise ValueError(f'train_mask {tuple(valid.shape)} is not the finest scale {sizes[-1]}')
+            weights = train_weight_pyramid(valid, sizes, grow=train_mask_grow, wrap=self.model.train_tile)
+            self.train_mask_hard = [m.to(self.device) for m in keep_mask_pyramid(valid, sizes, hard=True)]
+            self.model.train_weights = [w.to(self.device).contiguous() for w in weights]
+            self.data_list = [tuple(fill_train_holes(img, self.train_mask_hard[i], train_mask_fill).contiguous()
+                                    for img in pair) for i, pair in enumerate(self.data_list)]
 
         if fp16:
             raise NotImplementedError('apex mixed precision is never enabled by main.py (fp16=False, main.py:122)')
