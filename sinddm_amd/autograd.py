@@ -70,94 +70,60 @@ def net_forward_train(net, x, t, scale):
     return _NetTrainFn.apply(x, anchor, net, t, scale)
 
 
+def l1_entry(halo, weighted: bool) -> str:
+    """The library entry of the fused L1 loss: the weighted kernel under a map, else the cropping one under a halo, else the
+    plain mean.  The ONE owner of the rule: `_L1Fn` launches by it, `train_step.TrainStep` reports it."""
+    if weighted:
+        return "sinddm_l1_loss_weighted_fwd_bwd"
+    return "sinddm_l1_loss_crop_fwd_bwd" if halo[0] or halo[1] else "sinddm_l1_loss_fwd_bwd"
+
+
 class _L1Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, noise, eps):
+    def forward(ctx, noise, eps, weight, inv_norm, halo):
         lib = _lib.load()
         noise = noise.contiguous()
         eps = eps.contiguous()
+        hy, hx = int(halo[0]), int(halo[1])
+        name = l1_entry((hy, hx), weight is not None)
+        if name != "sinddm_l1_loss_fwd_bwd":               # (the plain mean takes any two tensors of one size)
+            if weight is not None and noise.dim() != 4:
+                raise _lib.SinddmError(f"l1_loss: noise must be (B,C,H,W) under a weight map, got {tuple(noise.shape)}")
+            H, W = int(noise.shape[-2]), int(noise.shape[-1])
+            if tuple(eps.shape) != (*noise.shape[:-2], H + 2 * hy, W + 2 * hx):
+                raise _lib.SinddmError(f"l1_loss: eps {tuple(eps.shape)} is not noise {tuple(noise.shape)} extended by the halo "
+                                       f"{(hy, hx)}")
+        if weight is not None:
+            if tuple(weight.shape) != (H, W) or weight.dtype != torch.float32 or weight.device != eps.device:
+                raise _lib.SinddmError(f"l1_loss: the weight map must be a {(H, W)} fp32 tensor on {eps.device}, got "
+                                       f"{tuple(weight.shape)} {weight.dtype} on {weight.device}")
+            weight = weight.contiguous()
         loss = torch.zeros((), dtype=torch.float32, device=eps.device)
-        g = torch.empty_like(eps)
-        _lib.check(lib.sinddm_l1_loss_fwd_bwd(_lib.ptr(noise), _lib.ptr(eps), _lib.ptr(loss), _lib.ptr(g), eps.numel(),
-                                              1.0, _lib.stream_ptr(eps.device)), "sinddm_l1_loss_fwd_bwd")
+        g = torch.empty_like(eps)                          # the kernels write the zeros of the halo and of the holes themselves
+        head, st = (_lib.ptr(noise), _lib.ptr(eps)), _lib.stream_ptr(eps.device)
+        if weight is not None:
+            args = (*head, _lib.ptr(weight), _lib.ptr(loss), _lib.ptr(g), int(noise.shape[0]), int(noise.shape[1]), H, W, hy, hx,
+                    float(inv_norm), 1.0, st)
+        elif hy or hx:
+            args = (*head, _lib.ptr(loss), _lib.ptr(g), noise.numel() // (H * W), H, W, hy, hx, 1.0, st)
+        else:
+            args = (*head, _lib.ptr(loss), _lib.ptr(g), eps.numel(), 1.0, st)
+        _lib.check(getattr(lib, name)(*args), name)
         ctx.save_for_backward(g)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         (g,) = ctx.saved_tensors
-        # d loss / d eps = -sign(noise - eps) / N, scaled by the upstream scalar (e.g. 1/grad_accumulate)
-        return None, g * grad_loss
-
-
-def l1_loss(noise, eps):
-    """mean(|noise - eps|)  (reference models.py:594)."""
-    return _L1Fn.apply(noise, eps)
-
-
-class _L1CropFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, noise, eps_ext, halo):
-        lib = _lib.load()
-        noise = noise.contiguous()
-        eps_ext = eps_ext.contiguous()
-        hy, hx = int(halo[0]), int(halo[1])
-        H, W = int(noise.shape[-2]), int(noise.shape[-1])
-        if tuple(eps_ext.shape) != (*noise.shape[:-2], H + 2 * hy, W + 2 * hx):
-            raise _lib.SinddmError(f"l1_loss_crop: eps {tuple(eps_ext.shape)} is not noise {tuple(noise.shape)} extended by "
-                                   f"the halo {(hy, hx)}")
-        loss = torch.zeros((), dtype=torch.float32, device=eps_ext.device)
-        g = torch.empty_like(eps_ext)                  # the kernel writes the halo's zeros itself
-        _lib.check(lib.sinddm_l1_loss_crop_fwd_bwd(_lib.ptr(noise), _lib.ptr(eps_ext), _lib.ptr(loss), _lib.ptr(g),
-                                                   noise.numel() // (H * W), H, W, hy, hx, 1.0,
-                                                   _lib.stream_ptr(eps_ext.device)), "sinddm_l1_loss_crop_fwd_bwd")
-        ctx.save_for_backward(g)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        (g,) = ctx.saved_tensors
-        return None, g * grad_loss, None
-
-
-def l1_loss_crop(noise, eps_ext, halo):
-    """mean(|noise - centre(eps_ext)|) of tileable training: `eps_ext` is the network's output on the image extended by the
-    wrapped halo `halo` = (halo_y, halo_x); its gradient has the extended shape and is 0 on the halo."""
-    return _L1CropFn.apply(noise, eps_ext, halo)
-
-
-class _L1WeightedFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, noise, eps_ext, weight, inv_norm, halo):
-        lib = _lib.load()
-        noise = noise.contiguous()
-        eps_ext = eps_ext.contiguous()
-        hy, hx = int(halo[0]), int(halo[1])
-        if noise.dim() != 4:
-            raise _lib.SinddmError(f"l1_loss_weighted: noise must be (B,C,H,W), got {tuple(noise.shape)}")
-        B, Cc, H, W = (int(v) for v in noise.shape)
-        if tuple(eps_ext.shape) != (B, Cc, H + 2 * hy, W + 2 * hx):
-            raise _lib.SinddmError(f"l1_loss_weighted: eps {tuple(eps_ext.shape)} is not noise {tuple(noise.shape)} extended "
-                                   f"by the halo {(hy, hx)}")
-        if tuple(weight.shape) != (H, W) or weight.dtype != torch.float32 or weight.device != eps_ext.device:
-            raise _lib.SinddmError(f"l1_loss_weighted: the weight map must be a {(H, W)} fp32 tensor on {eps_ext.device}, got "
-                                   f"{tuple(weight.shape)} {weight.dtype} on {weight.device}")
-        loss = torch.zeros((), dtype=torch.float32, device=eps_ext.device)
-        g = torch.empty_like(eps_ext)                  # the kernel writes the zeros of the halo and of the holes itself
-        _lib.check(lib.sinddm_l1_loss_weighted_fwd_bwd(_lib.ptr(noise), _lib.ptr(eps_ext), _lib.ptr(weight.contiguous()),
-                                                       _lib.ptr(loss), _lib.ptr(g), B, Cc, H, W, hy, hx, float(inv_norm), 1.0,
-                                                       _lib.stream_ptr(eps_ext.device)), "sinddm_l1_loss_weighted_fwd_bwd")
-        ctx.save_for_backward(g)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        (g,) = ctx.saved_tensors
+        # d loss / d eps = -sign(noise - eps) / N (times w / sum w under a map), scaled by the upstream scalar (e.g.
+        # 1/grad_accumulate); its shape is eps's: exactly 0 on the halo and where w == 0
         return None, g * grad_loss, None, None, None
 
 
-def l1_loss_weighted(noise, eps_ext, weight, inv_norm, halo=(0, 0)):
-    """sum(w |noise - centre(eps_ext)|) * inv_norm of masked training: `weight` is the (H,W) fp32 map w >= 0 shared by samples
-    and channels, `inv_norm` = 1 / (B C sum w) from the caller; where w == 0 nothing is read and the gradient is exactly 0.
-    `halo` as in l1_loss_crop: (0, 0) is the untiled step."""
-    return _L1WeightedFn.apply(noise, eps_ext, weight, inv_norm, halo)
+def l1_loss(noise, eps, halo=(0, 0), weight=None, inv_norm=None):
+    """mean(|noise - eps|)  (reference models.py:594) -- and the two losses of the training options, one fused kernel each:
+    with a `halo` = (halo_y, halo_x), `eps` is the network's output on the image extended by its wrapped halo and the mean is
+    taken over its centre (tileable training); with a `weight` -- the (H,W) fp32 map w >= 0 shared by samples and channels --
+    the loss is sum(w |noise - centre(eps)|) * inv_norm, `inv_norm` = 1 / (B C sum w) from the caller, and where w == 0 nothing
+    is read (masked training)."""
+    return _L1Fn.apply(noise, eps, weight, inv_norm, halo)

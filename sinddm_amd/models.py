@@ -6,6 +6,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
 
   SinDDMNet.forward          -> sinddm_net_forward        (models.py:134-151)
   q_sample / p_losses mix    -> sinddm_q_sample           (models.py:570-590)
+  p_losses' options          -> sinddm_q_sample_wrap, sinddm_l1_loss_crop_fwd_bwd / _weighted_fwd_bwd   (`train_tile`,
+                                `train_weights`; no reference line: one plan per step, train_step.TrainStep)
   p_sample tail              -> sinddm_reverse_step       (models.py:306-352,433-459)
   inter-scale upsample       -> sinddm_upsample_bilinear  (models.py:567)
   known pixels (`keep_maps`) -> sinddm_sample_chain_keep / sinddm_reverse_step_keep   (no reference line: RePaint-style
@@ -37,9 +39,11 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from .autograd import l1_loss
 from .functions import cosine_beta_schedule, default, exists, extract, noise_like
 from .sampler import RunPlan, pack_steps, refuse
 from .synth import net_param_shapes
+from .train_step import TrainStep
 
 
 # --------------------------------------------------------------------------------------------
@@ -665,14 +669,15 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # tileable TRAINING: (wrap_y, wrap_x) -- p_losses trains the network with circular padding on the wrapped axes, by
         # the same construction (x_noisy extended by its wrapped halo, the loss on the centre: every parameter gradient is
         # then the circularly padded network's).  Separate from `tile`, which p_losses does not read; not
-        # stored in checkpoints.
+        # stored in checkpoints.  Read by train_step.TrainStep (its `halo`), like `train_weights` below.
         self.train_tile = (False, False)
         # masked training (no reference counterpart): None, or one (h,w) fp32 map per scale on the training device, finite and
         # >= 0.  p_losses then takes sum(w e) / (B C sum w) instead of the mean over every pixel, e the loss type's
         # per-element error: where w == 0 the image never reaches the weights -- and, the receptive field being a square of
         # Chebyshev radius SINDDM_TILE_HALO, with w == 0 within that distance of a hole the weights provably never see what
-        # the hole contains (functions.train_weight_pyramid builds such maps).  Replace the list to change a
-        # map (the normaliser is cached per scale and map object).  Not stored in checkpoints.
+        # the hole contains (functions.train_weight_pyramid builds such maps).  A defective map is refused by
+        # train_step.TrainStep before the step launches anything.  Replace the list entry to change a map (the normaliser is
+        # cached per scale and map object: {s: (map, float64 sum)}, a plain attribute).  Not stored in checkpoints.
         self.train_weights = None
         self._train_weight_norm = {}
         # known-region conditioning (inpainting / outpainting): None or {s: (mask (H,W), x0 (3,H,W))}, fp32, on the sample's
@@ -1520,15 +1525,28 @@ class MultiScaleGaussianDiffusion(nn.Module):
         img = self.upsample(img, image_size)
         return self.p_sample_via_scale_loop(batch_size, img, s, custom_t=custom_t)
 
-    def _q_sample_impl(self, x0, t_dev, t_host, noise, x_orig=None, gamma_row=None):
+    def _q_sample_impl(self, x0, t_dev, t_host, noise, x_orig=None, gamma_row=None, halo=(0, 0)):
+        """x_t of q_sample / the gamma-mixed x_noisy of p_losses (sinddm_q_sample); with a `halo` = (hy, hx) the same, written
+        extended by its wrapped halo in one pass (sinddm_q_sample_wrap): (B,C,H + 2 hy,W + 2 hx)."""
         lib = _lib.load()
         x0 = x0.contiguous()
         noise = noise.contiguous()
+        if t_dev is not None:
+            t_dev = t_dev.to(device=x0.device, dtype=torch.int64).contiguous()
+        hy, hx = halo
+        if hy or hx:
+            B, Cc, H, W = x0.shape
+            out = torch.empty((B, Cc, H + 2 * hy, W + 2 * hx), dtype=x0.dtype, device=x0.device)
+            _lib.check(lib.sinddm_q_sample_wrap(_lib.ptr(x0), _lib.ptr(x_orig.contiguous()) if x_orig is not None else None,
+                                                _lib.ptr(noise), _lib.ptr(out), _lib.ptr(self.sqrt_alphas_cumprod),
+                                                _lib.ptr(self.sqrt_one_minus_alphas_cumprod),
+                                                _lib.ptr(gamma_row) if gamma_row is not None else None, _lib.ptr(t_dev),
+                                                int(t_host), B, Cc, H, W, hy, hx, _lib.stream_ptr(x0.device)),
+                       "sinddm_q_sample_wrap")
+            return out
         out = torch.empty_like(x0)
         B = x0.shape[0]
         n = x0.numel() // B
-        if t_dev is not None:
-            t_dev = t_dev.to(device=x0.device, dtype=torch.int64).contiguous()
         _lib.check(lib.sinddm_q_sample(_lib.ptr(x0), _lib.ptr(x_orig.contiguous()) if x_orig is not None else None,
                                        _lib.ptr(noise), _lib.ptr(out), _lib.ptr(self.sqrt_alphas_cumprod),
                                        _lib.ptr(self.sqrt_one_minus_alphas_cumprod),
@@ -1537,141 +1555,53 @@ class MultiScaleGaussianDiffusion(nn.Module):
                                        _lib.stream_ptr(x0.device)), "sinddm_q_sample")
         return out
 
-    def _q_sample_wrap_impl(self, x0, t_dev, noise, halo, x_orig=None, gamma_row=None):
-        """x_noisy of p_losses extended by its wrapped halo (sinddm_q_sample_wrap): (B,C,H + 2 hy,W + 2 hx)."""
-        lib = _lib.load()
-        x0 = x0.contiguous()
-        noise = noise.contiguous()
-        B, Cc, H, W = x0.shape
-        hy, hx = halo
-        out = torch.empty((B, Cc, H + 2 * hy, W + 2 * hx), dtype=x0.dtype, device=x0.device)
-        t_dev = t_dev.to(device=x0.device, dtype=torch.int64).contiguous()
-        _lib.check(lib.sinddm_q_sample_wrap(_lib.ptr(x0), _lib.ptr(x_orig.contiguous()) if x_orig is not None else None,
-                                            _lib.ptr(noise), _lib.ptr(out), _lib.ptr(self.sqrt_alphas_cumprod),
-                                            _lib.ptr(self.sqrt_one_minus_alphas_cumprod),
-                                            _lib.ptr(gamma_row) if gamma_row is not None else None, _lib.ptr(t_dev), 0,
-                                            B, Cc, H, W, hy, hx, _lib.stream_ptr(x0.device)), "sinddm_q_sample_wrap")
-        return out
-
     def q_sample(self, x_start, t, noise=None):                            # models.py:570-576
         noise = default(noise, lambda: torch.randn_like(x_start))
         return self._q_sample_impl(x_start, t, 0, noise)
 
     def p_losses(self, x_start, t, s, noise=None, x_orig=None):            # models.py:578-611
+        """The loss of one training step, as `train_step.TrainStep` describes it (every check runs there, before any launch).
+        With `train_tile` (no reference line: padding_mode='circular' on the reference's nn.Conv2d's while it trains) x_noisy is
+        written extended by its wrapped halo, the zero-padded training forward runs on the extended image and the loss is
+        taken on the centre: the gradient handed back is 0 on the halo, and every parameter gradient equals the circularly
+        padded network's.  With `train_weights` the loss is sum(w e) / (B C sum w) instead of the mean."""
         noise = default(noise, lambda: torch.randn_like(x_start))
-        if self.loss_type not in ('l1', 'l2', 'l1_pred_img'):
-            raise NotImplementedError()
-        if any(self.train_tile):
-            return self._p_losses_tiled(x_start, t, s, noise, x_orig)
-        if int(s) > 0:
-            gamma_row = self.gammas[int(s) - 1].reshape(-1).contiguous()    # NOT clamped to 0.55 in training
-            x_noisy = self._q_sample_impl(x_start, t, 0, noise, x_orig=x_orig, gamma_row=gamma_row)
-        else:
-            x_noisy = self._q_sample_impl(x_start, t, 0, noise)
-        x_recon = self.denoise_fn(x_noisy, t, int(s))
-        if self.train_weights is not None:
-            return self._weighted_loss(noise, x_recon, x_start, x_orig, t, s, (0, 0))
-        if self.loss_type == 'l1':                                          # what main.py:97 selects: fused loss + seed kernel
-            from .autograd import l1_loss
-            return l1_loss(noise, x_recon)
+        plan = TrainStep(self, x_start.shape, s)
+        x_orig = x_orig if plan.s > 0 else None
+        x_noisy = self._q_sample_impl(x_start, t, 0, noise, x_orig=x_orig, gamma_row=plan.gamma_row, halo=plan.halo)
+        x_recon = self.denoise_fn(x_noisy, t, plan.s)                       # (extended by the halo, like x_noisy)
+        return self._step_loss(plan, noise, x_recon, x_start, x_orig, t)
+
+    def _step_loss(self, plan, noise, x_recon, x_start, x_orig, t):
+        """The loss of the step `plan` on the network's output `x_recon` (extended by the plan's halo)."""
+        if plan.loss_type == 'l1':     # what main.py:97 selects: one fused kernel (loss, gradient, the halo's and the holes' zeros)
+            return l1_loss(noise, x_recon, plan.halo, plan.weight, plan.inv_norm)
         # the two loss types main.py never selects (models.py:595-607): the network's forward / backward are the HIP path
-        # (x_recon carries its autograd node), the loss itself is three elementwise torch ops
-        if self.loss_type == 'l2':
-            return F.mse_loss(noise, x_recon)
-        if int(s) > 0:
-            if int(t[0]) > 0:                                               # (the reference's host sync, models.py:599)
-                g = extract(self.gammas[int(s) - 1].reshape(-1), t - 1, x_start.shape)
-                x_mix_prev = g * x_start + (1 - g) * x_orig
-            else:
-                x_mix_prev = x_orig
-        else:
-            x_mix_prev = x_start
-        return (x_mix_prev - x_recon).abs().mean()
+        # (x_recon carries its autograd node), the loss itself is elementwise torch ops on the centre
+        (_, _, H, W), (hy, hx), w = plan.shape, plan.halo, plan.weight
+        if hy or hx:
+            x_recon = x_recon[:, :, hy:hy + H, hx:hx + W]                   # (its backward zero-fills the halo)
+        if plan.loss_type == 'l2':
+            return F.mse_loss(noise, x_recon) if w is None else ((noise - x_recon) ** 2 * w).sum() * plan.inv_norm
+        x_mix_prev = self._mix_prev(plan, x_start, x_orig, t)
+        return (x_mix_prev - x_recon).abs().mean() if w is None else ((x_mix_prev - x_recon).abs() * w).sum() * plan.inv_norm
 
-    def _p_losses_tiled(self, x_start, t, s, noise, x_orig):
-        """p_losses with wrap-around borders on the axes of `train_tile` (no reference line: padding_mode='circular' on the
-        reference's nn.Conv2d's while it trains).  x_noisy is written extended by its wrapped halo, the zero-padded training
-        forward runs on the extended image and the loss is taken on the centre: the gradient handed back is 0 on the halo,
-        and every parameter gradient equals the circularly padded network's."""
-        hy, hx = halo = (_lib.TILE_HALO if self.train_tile[0] else 0, _lib.TILE_HALO if self.train_tile[1] else 0)
-        H, W = int(x_start.shape[2]), int(x_start.shape[3])
-        if int(s) > 0:
-            gamma_row = self.gammas[int(s) - 1].reshape(-1).contiguous()    # NOT clamped to 0.55 in training
-            x_noisy = self._q_sample_wrap_impl(x_start, t, noise, halo, x_orig=x_orig, gamma_row=gamma_row)
-        else:
-            x_noisy = self._q_sample_wrap_impl(x_start, t, noise, halo)
-        x_recon = self.denoise_fn(x_noisy, t, int(s))                       # extended
-        if self.train_weights is not None:
-            return self._weighted_loss(noise, x_recon, x_start, x_orig, t, s, halo)
-        if self.loss_type == 'l1':
-            from .autograd import l1_loss_crop
-            return l1_loss_crop(noise, x_recon, halo)
-        x_recon = x_recon[:, :, hy:hy + H, hx:hx + W]                       # (its backward zero-fills the halo)
-        if self.loss_type == 'l2':
-            return F.mse_loss(noise, x_recon)
-        if int(s) > 0:
-            if int(t[0]) > 0:
-                g = extract(self.gammas[int(s) - 1].reshape(-1), t - 1, x_start.shape)
-                x_mix_prev = g * x_start + (1 - g) * x_orig
-            else:
-                x_mix_prev = x_orig
-        else:
-            x_mix_prev = x_start
-        return (x_mix_prev - x_recon).abs().mean()
-
-    def _train_weight(self, s, shape):
-        """(w, sum w) of scale `s` for a (B,C,H,W) batch: the map of `train_weights` and its float64 sum, taken on the host
-        once per scale and map object (one device-to-host copy, then none)."""
-        if int(s) >= len(self.train_weights):
-            raise _lib.SinddmError(f"train_weights holds {len(self.train_weights)} maps: none for scale {int(s)}")
-        w = self.train_weights[int(s)]
-        hw = (int(shape[2]), int(shape[3]))
-        if not torch.is_tensor(w) or tuple(w.shape) != hw or w.dtype != torch.float32:
-            raise _lib.SinddmError(f"train_weights[{int(s)}] must be a {hw} fp32 tensor, got "
-                                   f"{tuple(w.shape) if torch.is_tensor(w) else type(w).__name__}")
-        hit = self._train_weight_norm.get(int(s))
-        if hit is None or hit[0] is not w:
-            total = float(w.detach().to("cpu", torch.float64).sum())
-            if not (total > 0.0 and total < float("inf")):
-                raise _lib.SinddmError(f"train_weights[{int(s)}] sums to {total}: scale {int(s)} has no pixel to train on")
-            hit = self._train_weight_norm[int(s)] = (w, total)
-        return w, hit[1]
-
-    def _weighted_loss(self, noise, x_recon, x_start, x_orig, t, s, halo):
-        """The loss of p_losses / _p_losses_tiled under `train_weights`: sum(w e) / (B C sum w).  'l1' is one fused kernel
-        (sinddm_l1_loss_weighted_fwd_bwd: loss, gradient, the halo's and the holes' zeros); the two loss types main.py never
-        selects are torch ops on the centre, as they are without weights."""
-        w, total = self._train_weight(s, x_start.shape)
-        B, Cc, H, W = (int(v) for v in x_start.shape)
-        inv_norm = 1.0 / (B * Cc * total)
-        if self.loss_type == 'l1':
-            from .autograd import l1_loss_weighted
-            return l1_loss_weighted(noise, x_recon, w, inv_norm, halo)
-        hy, hx = halo
-        x_recon = x_recon[:, :, hy:hy + H, hx:hx + W]                       # (its backward zero-fills the halo)
-        if self.loss_type == 'l2':
-            return ((noise - x_recon) ** 2 * w).sum() * inv_norm
-        if int(s) > 0:
-            if int(t[0]) > 0:
-                g = extract(self.gammas[int(s) - 1].reshape(-1), t - 1, x_start.shape)
-                x_mix_prev = g * x_start + (1 - g) * x_orig
-            else:
-                x_mix_prev = x_orig
-        else:
-            x_mix_prev = x_start
-        return ((x_mix_prev - x_recon).abs() * w).sum() * inv_norm
+    def _mix_prev(self, plan, x_start, x_orig, t):
+        """The target of 'l1_pred_img' (models.py:597-606): the gamma mix of the level below t."""
+        if plan.s == 0:
+            return x_start
+        if int(t[0]) > 0:                                                   # (the reference's host sync, models.py:599)
+            g = extract(plan.gamma_row, t - 1, x_start.shape)
+            return g * x_start + (1 - g) * x_orig
+        return x_orig
 
     def forward(self, x, s, *args, **kwargs):                              # models.py:613-631
         s = int(s)
-        if s > 0:
-            x_orig, x_recon = x[0], x[1]
-            b, c, h, w = x_orig.shape
-            img_size = self.image_sizes[s]
-            assert h == img_size[0] and w == img_size[1], f'height and width of image must be {img_size}'
-            t = torch.randint(0, self.num_timesteps_trained[s], (b,), device=x_orig.device).long()
-            return self.p_losses(x_recon, t, s, x_orig=x_orig, *args, **kwargs)
-        b, c, h, w = x[0].shape
+        img = x[0]
+        x_orig = x[0] if s > 0 else None
+        x_start = x[1] if s > 0 else x[0]
+        b, c, h, w = img.shape
         img_size = self.image_sizes[s]
         assert h == img_size[0] and w == img_size[1], f'height and width of image must be {img_size}'
-        t = torch.randint(0, self.num_timesteps_trained[s], (b,), device=x[0].device).long()
-        return self.p_losses(x[0], t, s, *args, **kwargs)
+        t = torch.randint(0, self.num_timesteps_trained[s], (b,), device=img.device).long()
+        return self.p_losses(x_start, t, s, *args, x_orig=x_orig, **kwargs)

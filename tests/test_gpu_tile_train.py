@@ -18,51 +18,16 @@ import torch
 
 from conftest import rel_l2
 from fullrank_util import oracle_p_losses_autograd
-from oracle import sinddm_oracle as O
-from sinddm_amd.synth import hash_randn, he_state_dict
+from sinddm_amd.synth import hash_randn
 from tile_train_util import WRAPS, circular_p_losses_autograd, halo_of
+from train_step_util import DEV, inputs as _inputs, recorded_step, sched_and_diffusion as _sched_and_diffusion, step as _step
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 # (B, H, W, halo_y, halo_x) of tests 1 and 2.  5x7: the halo wraps more than once, one-float kernels (sinddm_q_sample's too:
 # 3*5*7 is odd); 9x32, 12x20, 8x36: the 16-byte kernels, one axis and both.  The fifth: sinddm_q_sample takes its 16-byte
 # kernel (3*4*7 % 4 == 0) while the fused kernel takes its one-float path (W = 7) -- the rounding must follow the former.
 SHAPES = [(2, 5, 7, 16, 16), (3, 9, 32, 0, 16), (1, 12, 20, 16, 0), (2, 8, 36, 16, 16), (2, 4, 7, 16, 16)]
-
-
-def _sched_and_diffusion(golden, dim, loss_type="l1"):
-    from sinddm_amd.models import MultiScaleGaussianDiffusion, SinDDMNet
-    meta = golden("g11_img_scales.json")["C1"]
-    net = SinDDMNet(dim=dim, multiscale=True, device=DEV).to(DEV)
-    sd = he_state_dict(dim)
-    net.load_state_dict(sd)
-    d = MultiScaleGaussianDiffusion(net, n_scales=meta["n_scales"], scale_factor=meta["scale_factor"],
-                                    image_sizes=[tuple(v) for v in meta["sizes"]], timesteps=meta["T"], train_full_t=True,
-                                    scale_losses=meta["rescale_losses"], loss_factor=1, loss_type=loss_type, device=DEV,
-                                    reblurring=True, omega=0).to(DEV)
-    sched = O.make_schedule(meta["T"], meta["n_scales"], meta["rescale_losses"], 1, train_full_t=True)
-    return net, d, sd, sched
-
-
-def _inputs(B, H, W, key):
-    """(x_start, x_orig, noise, t): an image-like pair in [-1, 1], N(0,1) noise, a different t per sample."""
-    x_start = hash_randn((B, 3, H, W), key).mul(0.5).clamp(-1, 1)
-    x_orig = hash_randn((B, 3, H, W), key + 1).mul(0.5).clamp(-1, 1)
-    noise = hash_randn((B, 3, H, W), key + 2)
-    t = torch.tensor([(7 + 24 * b) % 100 for b in range(B)])
-    return x_start, x_orig, noise, t
-
-
-def _step(net, d, x_start, x_orig, noise, t, s):
-    """p_losses + backward on the GPU: (loss as a float, {name: grad on the CPU})."""
-    net.bind_grads()
-    net.flat_grads.zero_()
-    kw = dict(x_orig=x_orig.to(DEV)) if s > 0 else {}
-    loss = d.p_losses(x_start.to(DEV), t.to(DEV), s, noise=noise.to(DEV), **kw)
-    loss.backward()
-    torch.cuda.synchronize()
-    return float(loss), {n: p.grad.detach().cpu().clone() for n, p in net.named_parameters()}
 
 
 # ---- 1: sinddm_q_sample_wrap ---------------------------------------------------------------------------------------------------
@@ -92,7 +57,7 @@ def test_q_sample_wrap_is_q_sample_then_wrap_halo(golden, B, H, W, hy, hx):
             assert torch.equal(one, two), (with_orig, t_host)
             assert bool(big[:guard].isnan().all()) and bool(big[-guard:].isnan().all())
     # the Python route of p_losses is this call
-    assert torch.equal(d._q_sample_wrap_impl(x0, t, nz, (hy, hx), x_orig=xo, gamma_row=gamma_row),
+    assert torch.equal(d._q_sample_impl(x0, t, 0, nz, x_orig=xo, gamma_row=gamma_row, halo=(hy, hx)),
                        d._wrap_pad(d._q_sample_impl(x0, t, 0, nz, x_orig=xo, gamma_row=gamma_row), hy, hx))
 
 
@@ -130,9 +95,9 @@ def test_l1_loss_crop(B, H, W, hy, hx):
     assert bool(big[:guard].isnan().all()) and bool(big[-guard:].isnan().all())
     assert abs(float(loss) - float(loss_ref)) <= 1e-6 * abs(float(loss_ref))
     # the autograd wrapper: the same numbers, scaled by the upstream gradient
-    from sinddm_amd.autograd import l1_loss_crop
+    from sinddm_amd.autograd import l1_loss
     e = eps_ext.clone().requires_grad_(True)
-    out = l1_loss_crop(noise, e, (hy, hx))
+    out = l1_loss(noise, e, (hy, hx))
     (out * 0.5).backward()
     assert abs(float(out) - float(loss_ref)) <= 1e-6 * abs(float(loss_ref))
     assert torch.equal(e.grad, g)
@@ -214,41 +179,21 @@ def test_other_loss_types(golden, lt):
 
 # ---- 6: nothing changes when off ------------------------------------------------------------------------------------------------------
 def _recorded_step(golden, touch, x_start, x_orig, noise, t, s, monkeypatch):
-    """One plain step on a fresh diffusion object, with everything that is reproducible run to run recorded: the loss, the
-    network's input (x_noisy) and output, the gradient handed to the network's backward -- and the flat gradient buffer."""
-    from sinddm_amd import autograd as A
+    """One plain step on a fresh diffusion object (train_step_util.recorded_step), during which the two library entries of
+    the tiled route refuse to run."""
     net, d, _, _ = _sched_and_diffusion(golden, 16)
     if touch:
         d.train_tile = (False, False)
-
-    def never(*a, **k):
-        raise AssertionError("the tiled route ran with train_tile off")
-
-    monkeypatch.setattr(d, "_p_losses_tiled", never)
-    monkeypatch.setattr(d, "_q_sample_wrap_impl", never)
-    monkeypatch.setattr(A, "l1_loss_crop", never)
-    rec = {}
-
-    def hook(mod, args, out):
-        rec["x_noisy"], rec["eps"] = args[0].detach().clone(), out.detach().clone()
-        out.register_hook(lambda g: rec.__setitem__("grad_eps", g.detach().clone()))
-
-    h = net.register_forward_hook(hook)
-    try:
-        rec["loss"], _ = _step(net, d, x_start, x_orig, noise, t, s)
-    finally:
-        h.remove()
-    rec["flat_grads"] = net.flat_grads.detach().cpu().clone()
-    rec["named"] = {n: (p.grad.data_ptr() - net.flat_grads.data_ptr()) // 4 for n, p in net.named_parameters()}
-    rec["numel"] = {n: p.numel() for n, p in net.named_parameters()}
-    return rec
+    return recorded_step(monkeypatch, net, d, x_start, x_orig, noise, t, s, ("sinddm_q_sample_wrap", "sinddm_l1_loss_crop_fwd_bwd"),
+                         "a kernel of the tiled route ran with train_tile off")
 
 
 @pytest.mark.parametrize("s", [0, 2])
 def test_off_is_the_untouched_step(golden, monkeypatch, s):
     """train_tile = (False, False) set explicitly against a diffusion object whose attribute was never touched (dim 16, B = 2,
-    7x12: 504 elements, so the loss is the sum of two workgroups' partial sums, which commutes).  None of the tiled route's
-    functions runs, and the loss, x_noisy, the network's output and the gradient handed to its backward are bit-equal.
+    7x12: 504 elements, so the loss is the sum of two workgroups' partial sums, which commutes).  Neither library entry
+    of the tiled route (sinddm_q_sample_wrap, sinddm_l1_loss_crop_fwd_bwd) is called, and the loss, x_noisy, the network's
+    output and the gradient handed to its backward are bit-equal.
 
     The flat gradient buffer is NOT compared bit for bit: the backward kernels accumulate with fp32 atomics whose order
     varies from run to run, on the untouched object against itself too.  Measured: 8 fresh objects running this same plain

@@ -21,14 +21,13 @@ import pytest
 import torch
 
 from conftest import rel_l2
-from oracle import sinddm_oracle as O
 from sinddm_amd import functions as F
-from sinddm_amd.synth import hash_randn, he_state_dict
+from sinddm_amd.synth import hash_randn
 from tile_train_util import halo_of
 from train_mask_util import l1_weighted_reference, radius_case, weighted_p_losses_autograd
+from train_step_util import DEV, inputs as _inputs, recorded_step, sched_and_diffusion as _sched_and_diffusion, step as _step
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NAME = "sinddm_l1_loss_weighted_fwd_bwd"
 
 SHAPES = [(1, 5, 7, 0, 0), (2, 9, 13, 16, 0), (3, 8, 64, 0, 16), (2, 33, 130, 16, 16), (2, 150, 300, 0, 0)]
@@ -106,9 +105,9 @@ def test_kernel_vs_numpy(B, H, W, hy, hx, kind):
     assert loss2 is loss and np.array_equal(g2.numpy(), g_ref)
     assert abs(float(loss2) - 2 * l_ref) <= 1e-6 * abs(2 * l_ref)
     # the autograd wrapper: the same numbers, scaled by the upstream gradient
-    from sinddm_amd.autograd import l1_loss_weighted
+    from sinddm_amd.autograd import l1_loss
     e = eps_ext.to(DEV).requires_grad_(True)
-    out = l1_loss_weighted(noise.to(DEV), e, w.to(DEV), inv, (hy, hx))
+    out = l1_loss(noise.to(DEV), e, (hy, hx), w.to(DEV), inv)
     (out * 0.5).backward()
     assert abs(float(out.detach()) - l_ref) <= 1e-6 * abs(l_ref)
     assert np.array_equal(e.grad.cpu().numpy(), g_ref)
@@ -166,40 +165,6 @@ def test_unit_weights_are_the_crop_kernel(B, H, W, hy, hx):
 
 
 # ---- 4: p_losses against the float64 restatement --------------------------------------------------------------------------------------
-def _sched_and_diffusion(golden, dim, loss_type="l1"):
-    from sinddm_amd.models import MultiScaleGaussianDiffusion, SinDDMNet
-    meta = golden("g11_img_scales.json")["C1"]
-    net = SinDDMNet(dim=dim, multiscale=True, device=DEV).to(DEV)
-    sd = he_state_dict(dim)
-    net.load_state_dict(sd)
-    d = MultiScaleGaussianDiffusion(net, n_scales=meta["n_scales"], scale_factor=meta["scale_factor"],
-                                    image_sizes=[tuple(v) for v in meta["sizes"]], timesteps=meta["T"], train_full_t=True,
-                                    scale_losses=meta["rescale_losses"], loss_factor=1, loss_type=loss_type, device=DEV,
-                                    reblurring=True, omega=0).to(DEV)
-    sched = O.make_schedule(meta["T"], meta["n_scales"], meta["rescale_losses"], 1, train_full_t=True)
-    return net, d, sd, sched
-
-
-def _inputs(B, H, W, key):
-    """(x_start, x_orig, noise, t): an image-like pair in [-1, 1], N(0,1) noise, a different t per sample."""
-    x_start = hash_randn((B, 3, H, W), key).mul(0.5).clamp(-1, 1)
-    x_orig = hash_randn((B, 3, H, W), key + 1).mul(0.5).clamp(-1, 1)
-    noise = hash_randn((B, 3, H, W), key + 2)
-    t = torch.tensor([(7 + 24 * b) % 100 for b in range(B)])
-    return x_start, x_orig, noise, t
-
-
-def _step(net, d, x_start, x_orig, noise, t, s):
-    """p_losses + backward on the GPU: (loss as a float, {name: grad on the CPU})."""
-    net.bind_grads()
-    net.flat_grads.zero_()
-    kw = dict(x_orig=x_orig.to(DEV)) if s > 0 else {}
-    loss = d.p_losses(x_start.to(DEV), t.to(DEV), s, noise=noise.to(DEV), **kw)
-    loss.backward()
-    torch.cuda.synchronize()
-    return float(loss), {n: p.grad.detach().cpu().clone() for n, p in net.named_parameters()}
-
-
 P_CASES = [(0, "off", "l1", 9, 12), (1, "off", "l1", 12, 20), (0, "xy", "l1", 9, 12), (1, "xy", "l1", 12, 20),
            (1, "off", "l2", 9, 12), (1, "xy", "l1_pred_img", 9, 12)]
 
@@ -255,37 +220,17 @@ def test_step_does_not_depend_on_what_the_hole_holds(golden):
 
 # ---- 6: nothing changes when off -------------------------------------------------------------------------------------------------------
 def _recorded_step(golden, touch, x_start, x_orig, noise, t, s, monkeypatch):
-    """One plain step on a fresh diffusion object, with everything that is reproducible run to run recorded.  `touch`: the
-    object first ran a WEIGHTED step, then had train_weights set back to None."""
-    from sinddm_amd import autograd as A
+    """One plain step on a fresh diffusion object (train_step_util.recorded_step), during which the weighted kernel's entry
+    refuses to run.  `touch`: the object first ran a WEIGHTED step, then had train_weights set back to None."""
     net, d, _, _ = _sched_and_diffusion(golden, 16)
     if touch:
         d.train_weights = [_weight_map("soft", 7, 12, 800).to(DEV)] * d.n_scales
         weighted, _ = _step(net, d, x_start, x_orig, noise, t, s)
         d.train_weights = None
-
-    def never(*a, **k):
-        raise AssertionError("the weighted route ran with train_weights = None")
-
-    rec = {}
-
-    def hook(mod, args, out):
-        rec["x_noisy"], rec["eps"] = args[0].detach().clone(), out.detach().clone()
-        out.register_hook(lambda g: rec.__setitem__("grad_eps", g.detach().clone()))
-
-    h = net.register_forward_hook(hook)
-    try:
-        with monkeypatch.context() as m:                                       # (undone on exit: the next object's weighted step)
-            m.setattr(d, "_weighted_loss", never)
-            m.setattr(A, "l1_loss_weighted", never)
-            rec["loss"], _ = _step(net, d, x_start, x_orig, noise, t, s)
-    finally:
-        h.remove()
+    rec = recorded_step(monkeypatch, net, d, x_start, x_orig, noise, t, s, (NAME,),
+                        "the weighted kernel ran with train_weights = None")
     if touch:
         assert weighted != rec["loss"]                                         # (the weighted step was another step)
-    rec["flat_grads"] = net.flat_grads.detach().cpu().clone()
-    rec["named"] = {n: (p.grad.data_ptr() - net.flat_grads.data_ptr()) // 4 for n, p in net.named_parameters()}
-    rec["numel"] = {n: p.numel() for n, p in net.named_parameters()}
     return rec
 
 
@@ -293,7 +238,7 @@ def _recorded_step(golden, touch, x_start, x_orig, noise, t, s, monkeypatch):
 def test_off_is_the_untouched_step(golden, monkeypatch, s):
     """train_weights = None, set explicitly after a weighted step, against a diffusion object whose attribute was never
     touched (dim 16, B = 2, 7x12: the loss is the sum of two workgroups' partial sums, which commutes).  The rule of
-    tests/test_gpu_tile_train.py::test_off_is_the_untouched_step: the weighted route does not run; the loss, x_noisy, the
+    tests/test_gpu_tile_train.py::test_off_is_the_untouched_step: sinddm_l1_loss_weighted_fwd_bwd is not called; the loss, x_noisy, the
     network's output and the gradient handed to its backward are bit-equal; the flat gradient buffer, which the backward
     kernels accumulate with fp32 atomics in an order that varies run to run, is held to 2e-6 rel-L2 per tensor -- as is the
     untouched object run twice."""

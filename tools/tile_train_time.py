@@ -64,7 +64,7 @@ def qsample_times(args, d, dev):
     x0, xo, nz = ((hash_randn((1, 3, H, W), 5 + k) * 0.5).to(dev).repeat(B, 1, 1, 1).contiguous() for k in range(3))
     t = torch.randint(0, d.num_timesteps, (B,), device=dev)
     gam = d.gammas[s - 1].reshape(-1).contiguous()
-    assert torch.equal(d._q_sample_wrap_impl(x0, t, nz, (hy, hx), x_orig=xo, gamma_row=gam),
+    assert torch.equal(d._q_sample_impl(x0, t, 0, nz, x_orig=xo, gamma_row=gam, halo=(hy, hx)),
                        d._wrap_pad(d._q_sample_impl(x0, t, 0, nz, x_orig=xo, gamma_row=gam), hy, hx))
     # the entry points themselves on preallocated buffers: as little host work per call as ctypes allows
     out = torch.empty_like(x0)
