@@ -72,6 +72,29 @@ int sinddm_debug_head(const float* packed, const float* g, const float* x_in, fl
  * (wgrad_wh.h); the 1x1 / depthwise / first-conv weight gradients stay fp32. */
 int sinddm_debug_train_path(int dim, int B, int H, int W);
 
+/* ONE 3x3 convolution (zero padding 1) on caller tensors through conv_wh, for kernel-level tests:
+ *   out = epilogue(conv2d(in, weights) + bias),  in (B, Cin, H, W), weights plain [Cout][Cin][3][3], out (B, Cout, H, W).
+ * variant: 0 = the kernel the library takes for this Cout, 1 = the kernel with items of 80 output channels, 2 = the
+ * kernel with items of 160 (conv_wr_kernel; Cout % 160 == 0).  ncu <= 0: the current device's compute units; any other
+ * count runs the grid a device of that size would get -- the result must not depend on it.
+ * Epilogue options as in the library's own launches: bias (Cout) or NULL; act 0 = none, 1 = GELU, 2 = multiply by
+ * GELU'(aux) (aux (B, Cout, H, W)); out_pre or NULL receives the value in front of the activation; resid (B, Cout, H, W) or
+ * NULL is added last and may be `out` itself; Wt = 0, or the true width of rows padded to W (W - 4 < Wt <= W): columns
+ * Wt .. W - 1 of `in` hold zeros and are written as zeros; amax_out or NULL: [B][8] floats zeroed by the caller, element
+ * [b][0] receives max |out[b]|.
+ * scratch (256-byte aligned, >= sinddm_debug_conv_wh_scratch_bytes) is cut into the packed binary16 weight image, the
+ * per-channel weight scales and the per-sample maxima of `in`, which the hook computes (wh_pack_launch, amax_tensor_launch).
+ * Returns SINDDM_E_BADARG / SINDDM_E_BADSHAPE before any device call for a null in / weights / out / scratch (or aux with
+ * act 2), a variant or act outside 0..2, W % 4 != 0, Cin < 32 or Cin % 16 != 0, Cout % 80 != 0, variant 2 with
+ * Cout % 160 != 0, B > 65535, one sample's input of 2^30 bytes or more, a scratch that is too small or misaligned, and
+ * tensors that are not 16-byte aligned.  conv_wh's size thresholds are tuning and are not mirrored: the kernels are valid
+ * at any size. */
+int sinddm_debug_conv_wh(int variant, int ncu, int B, int H, int W, int Wt, int Cin, int Cout, int act, const float* in,
+                         const float* weights, const float* bias, const float* resid, const float* aux, float* out,
+                         float* out_pre, float* amax_out, void* scratch, size_t scratch_bytes, void* stream);
+/* bytes of scratch that hook needs; 0 for channel counts or a batch it refuses */
+size_t sinddm_debug_conv_wh_scratch_bytes(int Cin, int Cout, int B);
+
 /* ONE SinDDMConvBlock (l = 0..3 of the plan of SinDDMNet(dim); reference SinDDM/models.py:51-80) forward + backward on
  * its own: x (B, C_in, H, W), cond_bias (B, C_in) = the block's per-sample condition (time_reshape(mlp(cond)),
  * models.py:74-76), grad_y (B, C_out, H, W).  Writes y, grad_x (may be NULL), dcond (B, C_in) = gradient of cond_bias, and

@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "sinddm_q_sample_wrap", "sinddm_l1_loss_crop_fwd_bwd",
     "sinddm_sample_chain_mix", "sinddm_normal_fill_mix",
     "sinddm_l1_loss_weighted_fwd_bwd",
+    "sinddm_debug_conv_wh", "sinddm_debug_conv_wh_scratch_bytes",
 )
 
 
@@ -189,6 +190,8 @@ def load() -> C.CDLL:
         "sinddm_debug_wgrad_plan": (i, [i, i, i, i, i, i, i, i, i, C.POINTER(C.c_int)]),
         "sinddm_debug_wgrad": (i, [i, i, i, i, i, i, i, i, i, p, p, p, p, p, sz, C.POINTER(C.c_int), p]),
         "sinddm_debug_wgrad_scratch_bytes": (sz, [i, i, i, i]),
+        "sinddm_debug_conv_wh": (i, [i, i, i, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, sz, p]),
+        "sinddm_debug_conv_wh_scratch_bytes": (sz, [i, i, i]),
         "sinddm_debug_head_offsets": (i, [i, C.POINTER(C.c_int64)]),
         "sinddm_debug_head": (i, [p, p, p, p, i, i, i, i, i, p]),
         "sinddm_debug_block_train": (i, [p, p, p, i, i, p, p, p, p, p, p, p, i, i, i, p, sz, p]),

@@ -81,6 +81,8 @@ constexpr int WH_VB = WH_REGION - WH_V;        // V buffer B: 88 576
 static_assert(WH_X <= WH_VB && WH_V + WH_X <= WH_REGION && WH_VB % 16 == 0, "exchange buffer beside either V buffer");
 constexpr int WH_TARGET_EXP = 10;              // scaled max |x| in [2^10, 2^11): |V| <= 20 max |x| stays below 65 504
 constexpr int WH_COB = 80;                     // output channels per item
+constexpr int WR_RING = 4;                     // U fragments in flight per multiplying wave of the 160-channel form (40 per chunk: the slots stay compile-time)
+static_assert(40 % WR_RING == 0 && WR_RING <= 10, "static ring slots");
 
 inline bool wh_shape_ok(int cin, int cout) { return cin >= 32 && cin % 16 == 0 && cout % WH_COB == 0; }   // (>= 2 chunks: the chunk stream looks two ahead)
 // f16 elements of the packed image: [co block][chunk][f 24][n 5][piece 2][k half 2][co 16][8]
@@ -212,7 +214,20 @@ __device__ __forceinline__ float wh_dpp_shl2(float old, float src) {      // lan
 // (HBM-latency LDS-DMA) and run the input transform.  Vector memory returns in order per wave, so a wave that waits for U
 // fragments out of L2 must not have tile requests in its queue: with the DMA in the multiplying waves every U refill
 // queued behind a tile request waited out the HBM round trip (first version: 12 700 cycles per chunk instead of ~2 500).
-__global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_xcd, int wg_per_xcd) {
+//
+// WR (round 30) = the form for launches with Cout % 160 == 0: an item covers 160 output channels of its tile, so the raw
+// tile is fetched and transformed once per tile instead of once per block of 80 channels.  A multiplying wave has no room
+// for 4 frequencies x 160 channels, but the vertical inverse transform is linear in its own accumulators: it keeps the two
+// output ROWS (2 x 32 tiles x 160 channels = the same 160 registers),
+//   Y0 = P0 + P1 + P2,   Y1 = P1 - P2 - P3,   P_fi = V_fi U_fi of one chunk (MFMAs into a fresh register set),
+// folded by VALU adds per chunk (see multiply_wr for why not inside the MFMAs).  The packed weight image is the same:
+// column tile n = 0..9 reads co block 2 cb + n / 5, fragment n % 5; the U ring holds WR_RING fragments.  The epilogue has
+// no vertical step and five passes; the residual of pass k + 1 is requested once pass k's accumulators have gone to LDS
+// (all ten column tiles up front would be 80 registers beside the accumulators).
+template <bool WR>
+__device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int wg_per_xcd) {
+    constexpr int NCT = WR ? 10 : 5;                         // 16-channel column tiles of an item
+    constexpr int NROW = WR ? 2 : 4;                         // accumulator sets: output rows (WR) / vertical frequencies
     typedef __attribute__((address_space(3))) float lds_f;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned char* const sbytes = reinterpret_cast<unsigned char*>(smem);
@@ -424,26 +439,68 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
 
         // ---- M phase (waves 0..5) ----
         // (zeroed for every wave: left undefined on the service path the array would be live around the item loop)
-        f32x4 acc[4][2][5];
+        f32x4 acc[NROW][2][NCT];
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
+        for (int a = 0; a < NROW; ++a)
 #pragma unroll
             for (int g = 0; g < 2; ++g)
 #pragma unroll
-                for (int n = 0; n < 5; ++n) acc[a][g][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int n = 0; n < NCT; ++n) acc[a][g][n] = f32x4{0.f, 0.f, 0.f, 0.f};
         // U fragment of (f, n): lane (co = l16, k group kq) = piece kq >> 1 of U[ci = 8 (kq & 1) + 0..7][co]: ONE lane-linear 1 KB
         // load per fragment, every byte distinct (the first version loaded [U_hi | U_hi] and [U_lo | U_lo]: two 1 KB requests of
         // which half the lanes were duplicates, and the vector-memory path of the CU, 64 bytes per clock, was the bound)
         const __amdgpu_buffer_rsrc_t rsw =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w3), 0, 0x7FFFFFF0, 0x00020000);
         const int wlane = lane * 16;
-        const int wbase = ((cb * nch) * 24 + fj) * 5 * 1024;            // + c * 24 * 5120 + (6 fi * 5 + n) * 1024
-        h16x8 ur[10];                                                    // ring: two frequencies (10 column tiles) ahead
+        const int wbase = (((WR ? 2 : 1) * cb * nch) * 24 + fj) * 5 * 1024;   // + c * 24 * 5120 + (6 fi * 5 + n) * 1024
+        const int wcb = nch * 24 * 5 * 1024;                             // (WR) the item's second co block of 80
+        h16x8 ur[10];                                                    // ring: two frequencies (10 column tiles) ahead; WR: WR_RING slots of it
         auto load_u = [&](int c, int fi, int n, int slot) {
-            const int so = wbase + (c * 24 * 5 + fi * 30 + n) * 1024;
+            const int so = wbase + (c * 24 * 5 + fi * 30 + (WR ? n % 5 : n)) * 1024 + (WR && n >= 5 ? wcb : 0);
             ur[slot] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, wlane, so, 0));
         };
-        auto multiply = [&](int c, const unsigned char* vb) {
+        // (WR) per vertical frequency fi and column tile the product P = V U of this chunk (both pieces: lo, then hi on top)
+        // goes into a fresh register set, and the VALU adds it to the rows it feeds: Y0 += P for fi = 0, 1, 2; Y1 += P for
+        // fi = 1, Y1 -= P for fi = 2, 3.  (Accumulating the rows inside the MFMAs -- C = Y0 for all three frequencies -- was
+        // built first and measured: three times the roundings at the magnitude of a whole row, 1.15-1.27 x the 80-channel
+        // kernel's error against float64, profiles/NOTES_r30.md.  This form rounds into a row once per frequency and chunk,
+        // as often as the 80-channel kernel rounds into its four accumulators, and needs no more MFMAs than that kernel.)
+        // (both multiply lambdas are generic in `c`: only the one its form calls is instantiated)
+        auto multiply_wr = [&](auto c, const unsigned char* vb) {
+            const unsigned char* A = vb + fj * 2048 + a_rd;
+            wh_static_for<4>([&](auto FI) {
+                constexpr int fi = decltype(FI)::value;
+                constexpr int fo = fi * 6 * 2048;
+                h16x8 ah0, ah1, al0, al1;
+                ah0 = *reinterpret_cast<const h16x8*>(A + fo);
+                ah1 = *reinterpret_cast<const h16x8*>(A + fo + 1024);
+                al0 = *reinterpret_cast<const h16x8*>(A + fo + 512);
+                al1 = *reinterpret_cast<const h16x8*>(A + fo + 1024 + 512);
+                wh_static_for<10>([&](auto NN) {
+                    constexpr int n = decltype(NN)::value;
+                    constexpr int q = fi * 10 + n, slot = q % WR_RING, qn = (q + WR_RING) % 40;
+                    const h16x8 u = ur[slot];
+                    const f32x4 zero{0.f, 0.f, 0.f, 0.f};
+                    __builtin_amdgcn_sched_barrier(0);
+                    f32x4 q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, u, zero, 0, 0, 0);
+                    f32x4 q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, u, zero, 0, 0, 0);
+                    q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, u, q0, 0, 0, 0);
+                    q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, u, q1, 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    // (the slot is free: the fragment WR_RING column tiles on, pinned behind the MFMAs that read it; behind the
+                    // last chunk the refill re-reads the last chunk's fragments, unused)
+                    if (q + WR_RING < 40) load_u(c, qn / 10, qn % 10, slot);
+                    else load_u(c + 1 < nch ? c + 1 : c, qn / 10, qn % 10, slot);
+                    __builtin_amdgcn_sched_barrier(0);
+                    // (the adds wait for the column tile's last MFMA: the SIMD's other wave has the matrix pipe meanwhile.  A
+                    // second product set, folded one column tile later, does not fit: the compiler spills)
+                    if constexpr (fi < 3) { acc[0][0][n] += q0; acc[0][1][n] += q1; }
+                    if constexpr (fi == 1) { acc[1][0][n] += q0; acc[1][1][n] += q1; }
+                    if constexpr (fi >= 2) { acc[1][0][n] -= q0; acc[1][1][n] -= q1; }
+                });
+            });
+        };
+        auto multiply = [&](auto c, const unsigned char* vb) {
             const unsigned char* A = vb + fj * 2048 + a_rd;
             wh_static_for<4>([&](auto FI) {
                 constexpr int fi = decltype(FI)::value;
@@ -480,17 +537,25 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
         };
 
         // the epilogue's operands of all five column tiles are requested up front (one exposed round trip per item, not one per pass); thread =
-        // (tile t = tid & 31, co16 = tid >> 5)
-        const int e_t = tid & 31, e_co = tid >> 5;
-        const int e_tr = e_t >> 3, e_tc = e_t & 7;
-        const int ey = y0 + 2 * e_tr, ex = x0 + 4 * e_tc;
-        f32x4 rsd[5][2];
-        float ek[5], ebv[5];
-        auto ep_operands = [&]() {
+        // (tile t = tid & 31, co16 = tid >> 5).  WR: the first pass's two column tiles up front, the next pass's during each pass
+        // (WR: the multiplying waves have no register to carry these through the chunk loop -- the compiler spilled them --
+        // so they are derived behind it, from a thread id the compiler cannot trace back)
+        int e_t, e_co, ey, ex;
+        auto ep_thread = [&]() {
+            int t = tid;
+            if constexpr (WR) asm volatile("" : "+v"(t));
+            e_t = t & 31; e_co = t >> 5;
+            const int e_tr = e_t >> 3, e_tc = e_t & 7;
+            ey = y0 + 2 * e_tr; ex = x0 + 4 * e_tc;
+        };
+        if constexpr (!WR) ep_thread();
+        f32x4 rsd[NCT][2];
+        float ek[NCT], ebv[NCT];
+        auto ep_operands = [&](auto N0, auto N1) {              // column tiles N0 .. N1 - 1
             const bool e_in = ex < W;
 #pragma unroll
-            for (int n = 0; n < 5; ++n) {
-                const int co = cb * WH_COB + n * 16 + e_co;
+            for (int n = decltype(N0)::value; n < decltype(N1)::value; ++n) {
+                const int co = cb * (NCT * 16) + n * 16 + e_co;
                 ek[n] = inv_sx * p.wsinv[co];
                 ebv[n] = p.bias ? p.bias[co] : 0.0f;
 #pragma unroll
@@ -502,6 +567,8 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
                 }
             }
         };
+        constexpr std::integral_constant<int, 0> ep_n0{};
+        constexpr std::integral_constant<int, WR ? 2 : 5> ep_n1{};   // what is requested behind the last chunk
 
         // ---- the two roles run their own loops (same number of barriers): nothing of the one is live in the other ----
         WH_SEG(0);
@@ -538,22 +605,26 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
                 wh_barrier();
                 if (c < 12) WH_SEG(3 + c);
             }
-            ep_operands();
+            if constexpr (WR) ep_thread();
+            ep_operands(ep_n0, ep_n1);
         } else {
             wh_static_for<10>([&](auto SL) {
                 constexpr int sl = decltype(SL)::value;
-                load_u(0, sl / 5, sl % 5, sl);
+                if constexpr (!WR) load_u(0, sl / 5, sl % 5, sl);
+                else if constexpr (sl < WR_RING) load_u(0, 0, sl, sl);
             });
             WH_SEG(1);
             if (j == 0) wh_barrier();
             WH_SEG(2);
             for (int c = 0; c < nch; ++c) {
-                multiply(c, vbuf(g + c));
+                if constexpr (WR) multiply_wr(c, vbuf(g + c));
+                else multiply(c, vbuf(g + c));
                 if (c == 3) WH_SEG(25);
                 wh_barrier();
                 if (c < 12) WH_SEG(3 + c);
             }
-            ep_operands();
+            if constexpr (WR) ep_thread();
+            ep_operands(ep_n0, ep_n1);
         }
         g += nch;
         WH_SEG(16);
@@ -563,12 +634,15 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
         // holds the next item's first chunk (buffer g & 1) ----
         // writer: acc[r][mg][n] = row r of D[tile = mg*16 + 4 kq + 0..3][co = l16] at horizontal frequency fj  ->  X[r][fj][co][tile]
         // reader: thread = (tile t = tid & 31, co16 = tid >> 5), once per column tile of the pass
-        const int e_wr = ((fj * 32 + l16) * WH_XS + 4 * kq) * 4;    // X[r][j][co 32][tile (stride 36)] byte offsets: writer (r = 0, fj, co = l16, tile 4 kq)
+        int e_lane = lane;                                          // (WR: derived here, not carried through the chunk loop -- see ep_thread)
+        if constexpr (WR) asm volatile("" : "+v"(e_lane));
+        const int e_wr = ((fj * 32 + (e_lane & 15)) * WH_XS + 4 * (e_lane >> 4)) * 4;   // X[r][j][co 32][tile (stride 36)] byte offsets: writer (r = 0, fj, co = l16, tile 4 kq)
         const int e_rd = (e_co * WH_XS + e_t) * 4;                  // reader (r = 0, j = 0, co16, tile)
         float amax = 0.f;
         WH_SEG(17);
-        if constexpr (!service) {
+        if constexpr (!service && !WR) {
             // vertical A^T (F(2,3)), in place: y0 = (m0 + m1) + m2 -> acc[0], y1 = (m1 - m2) - m3 -> acc[1]
+            // (WR: the accumulators are the two rows already)
 #pragma unroll
             for (int mg = 0; mg < 2; ++mg)
 #pragma unroll
@@ -577,9 +651,9 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
                     acc[1][mg][n] = acc[1][mg][n] - acc[2][mg][n] - acc[3][mg][n];
                 }
         }
-        wh_static_for<3>([&](auto PS) {
-            constexpr int n0 = 2 * decltype(PS)::value;           // column tiles n0, n0 + 1 (the last pass: 4 alone)
-            constexpr int nn = n0 + 2 <= 5 ? 2 : 1;
+        wh_static_for<(NCT + 1) / 2>([&](auto PS) {
+            constexpr int n0 = 2 * decltype(PS)::value;           // column tiles n0, n0 + 1 (the last pass of five: 4 alone)
+            constexpr int nn = n0 + 2 <= NCT ? 2 : 1;
             unsigned char* X = sV + ((g & 1) ? 0 : WH_V);
             if constexpr (!service) {
 #pragma unroll
@@ -590,6 +664,10 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
                         for (int mg = 0; mg < 2; ++mg)
                             *reinterpret_cast<f32x4*>(X + e_wr + (r * 6 * 32 + nl * 16) * (WH_XS * 4) + mg * 64) = acc[r][mg][n0 + nl];
             }
+            // (WR) the next pass's operands, into the registers this pass's accumulators have just left; a thread reads and
+            // writes the same pixels of a channel, so resid == out stays safe: resid[o] is still read before out[o] is stored
+            if constexpr (WR && n0 + 2 < NCT)
+                ep_operands(std::integral_constant<int, n0 + 2>{}, std::integral_constant<int, n0 + 4>{});
             wh_barrier();
             WH_SEG(18 + decltype(PS)::value);
             float q[nn][2][6];
@@ -603,7 +681,7 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
             wh_barrier();                                 // (every wave holds its values: the buffer is free for the next pass / the next item's V)
             wh_static_for<nn>([&](auto NL) {
                 constexpr int n = n0 + decltype(NL)::value;
-                const int co = cb * WH_COB + n * 16 + e_co;
+                const int co = cb * (NCT * 16) + n * 16 + e_co;
                 const float k = ek[n];
                 const float bv = ebv[n];
 #pragma unroll
@@ -647,6 +725,14 @@ __global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_
     else role_body(std::false_type{});
 }
 
+__global__ __launch_bounds__(512) void conv_wh_kernel(ConvArgs p, int items_per_xcd, int wg_per_xcd) {
+    wh_run<false>(p, items_per_xcd, wg_per_xcd);
+}
+// items of 160 output channels, two output rows per multiplying wave
+__global__ __launch_bounds__(512) void conv_wr_kernel(ConvArgs p, int items_per_xcd, int wg_per_xcd) {
+    wh_run<true>(p, items_per_xcd, wg_per_xcd);
+}
+
 #ifndef SINDDM_WH_MIN_ITEMS_PER_CU
 #define SINDDM_WH_MIN_ITEMS_PER_CU 12      // measured per pyramid scale (profiles/r05_scales.txt, r05_threshold_ab_full.txt): C2 133x177 at batch 16
 #endif
@@ -666,33 +752,60 @@ inline bool conv_wh_applies(bool fp32_convs, int B, int H, int W, int cin, int c
            (long long)SINDDM_WH_MIN_ITEMS_PER_CU * cu_count();
 }
 
-inline int conv_wh_launch(const ConvArgs& a_in, hipStream_t st) {
+#ifndef SINDDM_CONV_WR
+#define SINDDM_CONV_WR 1                   // 0: every launch keeps the 80-channel kernel (A/B builds)
+#endif
+constexpr int WR_COB = 2 * WH_COB;         // output channels per item of conv_wr_kernel
+#ifndef SINDDM_WR_MIN_ITEMS_PER_CU
+#define SINDDM_WR_MIN_ITEMS_PER_CU 12      // measured floor, in items of 160 channels (profiles/NOTES_r30.md section 5)
+#endif
+
+// Whether a network launch that conv_wh takes should run its 160-channel kernel: with half as many items per workgroup the
+// rounds get coarser, and at 6.4 items per compute unit (16 x 133x177) the launch is 1.2 % slower than on the 80-channel
+// kernel, at 12 (16 x 186x248) and above it is 3 to 4 % faster; nothing in between was measured, so the floor is the
+// lowest count that was seen to win.
+inline bool conv_wr_pays(int B, int H, int W, int cout) {
+    if (!SINDDM_CONV_WR || cout % WR_COB != 0) return false;
+    return (long long)B * ((W + WH_TW - 1) / WH_TW) * ((H + WH_TH - 1) / WH_TH) * (cout / WR_COB) >=
+           (long long)SINDDM_WR_MIN_ITEMS_PER_CU * cu_count();
+}
+
+// variant: 0 = the library's choice (the 160-channel kernel where Cout % 160 == 0), 1 = the 80-channel kernel,
+// 2 = the 160-channel kernel; ncu > 0 sizes the grid for a device of that many compute units (tests: the result does
+// not depend on it)
+inline int conv_wh_launch(const ConvArgs& a_in, hipStream_t st, int variant = 0, int ncu = 0) {
     ConvArgs a = a_in;
     if (!wh_shape_ok(a.Cin, a.Cout) || a.W % 4 != 0 || !a.wsinv || (long long)a.Cin * a.H * a.W * 4 >= 0x40000000LL)
         return SINDDM_E_BADSHAPE;
+    if (variant < 0 || variant > 2) return SINDDM_E_BADARG;
+    if (variant == 2 && a.Cout % WR_COB != 0) return SINDDM_E_BADSHAPE;
+    const bool wr = variant == 2 || (variant == 0 && SINDDM_CONV_WR && a.Cout % WR_COB == 0);
     ConvProfiler& prof = conv_profiler();
     const bool rec = prof.begin(st);
     a.nch3 = a.Cin / 16;
-    a.coblks = a.Cout / WH_COB;
+    a.coblks = a.Cout / (wr ? WR_COB : WH_COB);
     a.tilesX = (a.W + WH_TW - 1) / WH_TW;
     a.tilesY = (a.H + WH_TH - 1) / WH_TH;
     a.ntiles = a.B * a.tilesX * a.tilesY;
     a.tiles_per_xcd = (a.ntiles + 7) / 8;
     const int ipx = a.tiles_per_xcd * a.coblks;
-    int wpx = cu_count() / 8;
+    int wpx = (ncu > 0 ? ncu : cu_count()) / 8;
     if (wpx < 1) wpx = 1;
     if (wpx > ipx) wpx = ipx;
     static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wh_kernel),
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, WH_LDS);
+    static const hipError_t attr_rc_wr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wr_kernel),
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, WH_LDS);
     if (attr_rc != hipSuccess) return (int)attr_rc;
+    if (attr_rc_wr != hipSuccess) return (int)attr_rc_wr;
 #ifdef WH_TIMING
     static int wh_launch_no = 0;
     a.mtp = wh_launch_no++ % 8;                  // (the kernel does not read mtp otherwise: stamp row of this launch)
 #endif
-    hipLaunchKernelGGL(conv_wh_kernel, dim3(wpx * 8), dim3(512), WH_LDS, st, a, ipx, wpx);
+    hipLaunchKernelGGL(wr ? conv_wr_kernel : conv_wh_kernel, dim3(wpx * 8), dim3(512), WH_LDS, st, a, ipx, wpx);
     if (rec) {
         const double fl = 2.0 * a.B * a.H * (a.Wt > 0 ? a.Wt : a.W) * (double)a.Cout * 9.0 * a.Cin;   // algorithmic (direct-conv) FLOPs
-        // executed: four binary16 MFMA terms x 24 frequencies per 8 outputs, on whole 8x32 items
+        // executed: four binary16 MFMA terms x 24 frequencies per 8 outputs, on whole 8x32 items (either kernel)
         prof.end(st, 1, fl, 2.0 * a.ntiles * 32.0 * 24.0 * 4.0 * (double)a.Cout * a.Cin, 8);
     }
     SINDDM_LAUNCH_CHECK();

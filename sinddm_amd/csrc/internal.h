@@ -88,7 +88,9 @@ ConvKernel conv3x3_route(const NetPlan& P, const Conv3x3Images& c, int B, int H,
 // coblks and the m-tile count from the images at `packed`; the caller has set the tensors, act / aux / resid / bias, the
 // fused 1x1 fields of the direct kernel and the amax pointers.
 struct ConvArgs;
-int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st);
+// wh_variant (CONV_WH only): 0 = items of 160 output channels where C_out % 160 == 0 and the launch is large enough (conv_wr_pays), 1 = the
+// 80-channel kernel (training: its forward, see block_forward, and its data gradients, see block_backward).
+int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st, int wh_variant = 0);
 // the routes of one network evaluation: out[2 l + i] = conv i + 1 of block l (-1: not launched -- block 4's conv2 under
 // the collapsed head).  Wp = the row pitch the evaluation runs at; returns whether any route is CONV_WH.
 bool forward_routes(const NetPlan& P, bool train, int B, int H, int Wp, bool have_amax, int out[8]);

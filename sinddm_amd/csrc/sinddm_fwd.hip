@@ -996,12 +996,14 @@ ConvKernel conv3x3_route(const NetPlan& P, const Conv3x3Images& c, int B, int H,
     return first_conv && c.K == 3 && SINDDM_CONV_C3 ? CONV_C3 : CONV_DIRECT;
 }
 
-int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st) {
+int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st, int wh_variant) {
     a.coblks = c.coblks;
     switch (k) {
         case CONV_WH:
             a.w3 = packed + c.wh; a.wsinv = packed + c.wh_sinv;
-            return conv_wh_launch(a, st);
+            // (launches too small for items of 160 channels keep the 80-channel kernel: conv_wr_pays)
+            if (wh_variant == 0 && !conv_wr_pays(a.B, a.H, a.W, a.Cout)) wh_variant = 1;
+            return conv_wh_launch(a, st, wh_variant);
         case CONV_WINO4:
         case CONV_WINO3:
             a.w3 = packed + c.wino24; a.nch3 = conv3x3_nchw(c);
@@ -1044,6 +1046,10 @@ int block_forward(const NetPlan& P, int l, const float* params, const float* pac
     const BlockPlan& b = P.blk[l];
     const bool wha = route[0] == CONV_WH, whb = route[1] == CONV_WH;
     if ((wha || whb) && !amax) return SINDDM_E_BADARG;
+    // the training forward (the one that saves upre) keeps conv_wh's 80-channel kernel, as its data gradients do
+    // (block_backward): training computes what it computed, and the gates that pin it stay where they are.  Inference takes
+    // conv_wh_launch's choice -- items of 160 output channels where C_out % 160 == 0 (profiles/NOTES_r30.md)
+    const int wh_variant = upre ? 1 : 0;
     int rc = Wt > 0 ? dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
                                     Wt, st, W, W, wha ? amax : nullptr)
                     : dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
@@ -1065,7 +1071,7 @@ int block_forward(const NetPlan& P, int l, const float* params, const float* pac
         c1.act = 1; c1.zero = packed + P.pk_zero; c1.Wt = Wt;
         c1.bias = wha ? params + b.c1_b : packed + b.pk_b1;      // (conv_wh reads the plain bias row)
         if (wha) { c1.amax_in = amax; c1.amax_out = whb ? amax + 1 : nullptr; }
-        rc = conv3x3_launch((ConvKernel)route[0], b.c1, packed, c1, st);
+        rc = conv3x3_launch((ConvKernel)route[0], b.c1, packed, c1, st, wh_variant);
     }
     if (rc || route[1] < 0) return rc;
     // conv2 on the binary16 kernel reads the running max of g (slot amax + 1): conv_wh / the C_in = 3 kernel publish it
@@ -1094,7 +1100,7 @@ int block_forward(const NetPlan& P, int l, const float* params, const float* pac
         c2.resid = obuf; c2.bias = nullptr;          // in place: each thread reads resid[o] before writing out[o]
     }
     if (whb) c2.amax_in = amax + 1;
-    return conv3x3_launch((ConvKernel)route[1], b.c2, packed, c2, st);
+    return conv3x3_launch((ConvKernel)route[1], b.c2, packed, c2, st, wh_variant);
 }
 
 bool wh_enabled() { return SINDDM_CONV_WH != 0; }
@@ -1999,6 +2005,49 @@ int sinddm_debug_head(const float* packed, const float* g, const float* x_in, fl
                        static_cast<hipStream_t>(stream), head_eps(p, packed, g, x_in, H, Wp), eps_out, W);
     SINDDM_LAUNCH_CHECK();
     return 0;
+}
+
+// the three regions sinddm_debug_conv_wh carves from its scratch, each rounded to 256 bytes: packed image, wsinv, maxima
+static size_t wh_debug_round(size_t v) { return (v + 255) / 256 * 256; }
+static bool wh_debug_shape_ok(int Cin, int Cout, int B) { return B >= 1 && B <= 65535 && Cin >= 32 && Cin % 16 == 0 && Cout >= 80 && Cout % 80 == 0; }
+
+size_t sinddm_debug_conv_wh_scratch_bytes(int Cin, int Cout, int B) {
+    if (!wh_debug_shape_ok(Cin, Cout, B)) return 0;
+    return wh_debug_round((size_t)wh_image_halfs(Cin, Cout) * 2) + wh_debug_round((size_t)Cout * sizeof(float)) +
+           wh_debug_round((size_t)B * AMAX_STRIDE * sizeof(float));
+}
+
+int sinddm_debug_conv_wh(int variant, int ncu, int B, int H, int W, int Wt, int Cin, int Cout, int act, const float* in,
+                         const float* weights, const float* bias, const float* resid, const float* aux, float* out,
+                         float* out_pre, float* amax_out, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!in || !weights || !out || !scratch || (act == 2 && !aux)) return SINDDM_E_BADARG;
+    if (variant < 0 || variant > 2 || act < 0 || act > 2 || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0)
+        return SINDDM_E_BADARG;
+    if (W % 4 != 0 || !wh_debug_shape_ok(Cin, Cout, B) || (variant == 2 && Cout % 160 != 0)) return SINDDM_E_BADSHAPE;
+    if (Wt != 0 && (Wt > W || Wt <= W - 4)) return SINDDM_E_BADSHAPE;
+    // one sample's input is addressed as a 32-bit buffer; tiles of the launch as an int
+    if ((long long)Cin * H * W * 4 >= 0x40000000LL || (long long)B * ((H + 7) / 8) * ((W + 31) / 32) > 0x3fffffffLL)
+        return SINDDM_E_BADSHAPE;
+    if (scratch_bytes < sinddm_debug_conv_wh_scratch_bytes(Cin, Cout, B) || (uintptr_t)scratch % 256 != 0) return SINDDM_E_BADARG;
+    for (const void* q : {(const void*)in, (const void*)resid, (const void*)aux, (const void*)out, (const void*)out_pre})
+        if ((uintptr_t)q % 16 != 0) return SINDDM_E_BADARG;      // 16-byte loads and stores
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* base = static_cast<char*>(scratch);
+    void* img = base;
+    float* wsinv = reinterpret_cast<float*>(base + wh_debug_round((size_t)wh_image_halfs(Cin, Cout) * 2));
+    float* amax_in = wsinv + wh_debug_round((size_t)Cout * sizeof(float)) / sizeof(float);
+    int rc = wh_pack_launch(weights, wsinv, img, Cin, Cout, 0, st);
+    if (rc) return rc;
+    const hipError_t e = hipMemsetAsync(amax_in, 0, (size_t)B * AMAX_STRIDE * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    rc = amax_tensor_launch(in, amax_in, B, (long long)Cin * H * W, st);
+    if (rc) return rc;
+    ConvArgs a{};
+    a.in = in; a.resid = resid; a.aux = aux; a.bias = bias; a.out = out; a.out_pre = out_pre;
+    a.w3 = static_cast<const float*>(img); a.wsinv = wsinv; a.amax_in = amax_in; a.amax_out = amax_out;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act; a.Wt = Wt;
+    return conv_wh_launch(a, st, variant, ncu);
 }
 
 int sinddm_prof_end3(int kind, double* ms_total, int64_t* launches, double* flops_total, double* exec_flops_total,
