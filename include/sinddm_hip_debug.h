@@ -42,6 +42,36 @@ int sinddm_prof_end3(int kind, double* ms_total, int64_t* launches, double* flop
  * SINDDM_DIM_FP32_CONVS.  Returns 0 or a negative SINDDM_E_*.  Host-only.  The three hooks below are its entry 5. */
 int sinddm_debug_routes(int dim_arg, int train, int B, int H, int W, int out[16]);
 
+/* Host-only (no device call, decides nothing): everything ONE network evaluation of this shape decides, as the library's
+ * forward_plan reports it -- train = 0 of sinddm_net_forward / a step of sinddm_sample_chain*, train != 0 of
+ * sinddm_net_forward_train -- on `ncu` compute units (<= 0: the current device's, 256 where none answers).  out receives
+ * SINDDM_FWD_PLAN_INTS integers (cap = room in out; SINDDM_E_BADARG when it is smaller, out is NULL, a size is <= 0 or
+ * dim_arg is no network):
+ *   [0] Wp, the row pitch of the activations    [1] 1 if rows are padded (Wp != W)    [2] Wt (W when padded, else 0)
+ *   [3] H * W    [4] 1 under the collapsed head    [5] 1 if a conv takes conv_wh (the running maxima are zeroed and kept)
+ *   [6] fuse_tail: a plain sampler step ends inside the last launch    [7] rows_aligned ((H W) % 4 == 0, rows not padded)
+ *   [8], [9] the last launch of an evaluation that writes eps and its gridDim.x; [10], [11] of a step that fuses its tail:
+ *        0 = final_conv_reverse_step_pitch_kernel<HeadEps>, 1 = final_conv_reverse_step_kernel<HeadEps>, 2 = head_eps_kernel,
+ *        3 = final_conv_reverse_step_pitch_kernel<FinalConvEps>, 4 = final_conv1x1_pitch_kernel (3 and 4: padded rows
+ *        without the head, only with -DSINDDM_HEAD_COLLAPSE=0 or a plane of >= 2^28 floats),
+ *        5 = final_conv_reverse_step_kernel<FinalConvEps>, 6 = final_conv1x1_kernel
+ *   [12] enqueued operations of the evaluation as a sampler step runs it (sinddm_net_forward: + its cond_kernel)
+ *   [13] the chain's split rule: (8x32 tile, 80-channel block) items of a dim -> dim conv launch
+ *   [14] .. [21] byte offsets into the inference workspace (all 0 with train): conditioning rows, running maxima, the four
+ *        activation buffers, the padded input copy, and core_bytes = the end of the last = what sinddm_net_forward needs
+ *   [22] sinddm_workspace_bytes of the shape (0 with train)    [23] the CU count the plan was made for
+ *   [24 + 14 l + ..] block l:  +0, +1 the ConvKernel of conv1 / conv2 (sinddm_debug_routes' values, -1 not launched);
+ *        +2, +3 their conv_wh kernel (0 not conv_wh, 1 = items of 80 output channels, 2 = of 160);
+ *        running-max slots (-1 none): +4 published by the depthwise launch, +5 read by conv1, +6 published by conv1,
+ *        +7 1 if a separate max pass over g publishes conv2's slot, +8 read by conv2;
+ *        +9 the residual: 0 none (block 4 under the head), 1 identity, 2 the 1x1 fused into the direct 3x3 kernel, 3 a 1x1
+ *        launch in front of conv2;  +10 1 if conv1 reads the plain bias row;  +11 depthwise kernel (0 tiles, 1 rows),
+ *        +12, +13 its input / output row pitch */
+#define SINDDM_FWD_PLAN_BLOCK0 24
+#define SINDDM_FWD_PLAN_BLOCK_INTS 14
+#define SINDDM_FWD_PLAN_INTS (SINDDM_FWD_PLAN_BLOCK0 + 4 * SINDDM_FWD_PLAN_BLOCK_INTS)
+int sinddm_debug_forward_plan(int dim_arg, int train, int B, int H, int W, int ncu, int64_t* out, int cap);
+
 /* Which kernel generation the dim -> dim 3x3 convolutions of a launch of this shape take on the current device:
  * 4 = conv_wino4 (F(2x4,3x3), one wave per SIMD), 3 = conv_wino3 (F(2x4,3x3)), 2 = F(2x2,3x3) kernels, 0 = direct
  * implicit GEMM; negative = SINDDM_E_*.  Lets a test assert that it exercises the kernel it means to. */

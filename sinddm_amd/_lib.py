@@ -26,6 +26,7 @@ ABI_SYMBOLS = (
     "sinddm_normal_fill", "sinddm_wrap_halo", "sinddm_upsample_bilinear_wrap", "sinddm_sample_chain_tile",
     "sinddm_sample_chain_keep", "sinddm_reverse_step_keep", "sinddm_normal_fill_samples", "sinddm_sample_chain_seeds",
     "sinddm_debug_head_path", "sinddm_debug_head_offsets", "sinddm_debug_head", "sinddm_debug_routes",
+    "sinddm_debug_forward_plan",
     "sinddm_debug_wgrad_routes", "sinddm_debug_wgrad_plan", "sinddm_debug_wgrad", "sinddm_debug_wgrad_scratch_bytes",
     "sinddm_sample_chain_resample", "sinddm_reverse_step_jump",
     "sinddm_sample_chain_layout", "sinddm_layout_delta", "sinddm_reverse_step_layout",
@@ -193,6 +194,7 @@ def load() -> C.CDLL:
         "sinddm_debug_conv_wh": (i, [i, i, i, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, sz, p]),
         "sinddm_debug_conv_wh_scratch_bytes": (sz, [i, i, i]),
         "sinddm_debug_head_offsets": (i, [i, C.POINTER(C.c_int64)]),
+        "sinddm_debug_forward_plan": (i, [i, i, i, i, i, i, C.POINTER(C.c_int64), i]),
         "sinddm_debug_head": (i, [p, p, p, p, i, i, i, i, i, p]),
         "sinddm_debug_block_train": (i, [p, p, p, i, i, p, p, p, p, p, p, p, i, i, i, p, sz, p]),
         "sinddm_train_workspace_bytes": (sz, [i, i, i, i]),

@@ -47,14 +47,15 @@ inline bool wino_enabled() { return SINDDM_CONV_WINO != 0; }
 
 // CU count of the CURRENT device (kernel selection thresholds and persistent grid sizes).  Cached per device id: the
 // only mutable state of the library besides the debug profiler -- idempotent, and a race on it writes the same value.
-// (256, the MI355X's count, where no device answers: the host-only debug hooks)
+// (CU_COUNT_NO_DEVICE, the MI355X's count, where no device answers: the host-only debug hooks)
+constexpr int CU_COUNT_NO_DEVICE = 256;
 inline int cu_count() {
     static int cache[64] = {0};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return CU_COUNT_NO_DEVICE;
     int v = cache[dev];
     if (v <= 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return CU_COUNT_NO_DEVICE;
         cache[dev] = v;
     }
     return v;

@@ -744,12 +744,12 @@ __global__ __launch_bounds__(512) void conv_wr_kernel(ConvArgs p, int items_per_
 #define SINDDM_CONV_WH 1
 #endif
 // fp32_convs: the caller's per-call option SINDDM_DIM_FP32_CONVS (sinddm_hip.h) -- every 3x3 conv stays on the fp32 matrix pipe
-inline bool conv_wh_applies(bool fp32_convs, int B, int H, int W, int cin, int cout) {
+inline bool conv_wh_applies(bool fp32_convs, int B, int H, int W, int cin, int cout, int ncu) {
     if (!SINDDM_CONV_WH || fp32_convs || !wh_shape_ok(cin, cout) || W % 4 != 0) return false;
     if ((long long)cin * H * W * 4 >= 0x40000000LL) return false;      // (one sample's input is addressed as a 32-bit buffer)
     if ((long long)H * W < SINDDM_WH_MIN_PIXELS) return false;
     return (long long)B * ((W + WH_TW - 1) / WH_TW) * ((H + WH_TH - 1) / WH_TH) * (cout / WH_COB) >=
-           (long long)SINDDM_WH_MIN_ITEMS_PER_CU * cu_count();
+           (long long)SINDDM_WH_MIN_ITEMS_PER_CU * ncu;
 }
 
 #ifndef SINDDM_CONV_WR
@@ -764,10 +764,10 @@ constexpr int WR_COB = 2 * WH_COB;         // output channels per item of conv_w
 // rounds get coarser, and at 6.4 items per compute unit (16 x 133x177) the launch is 1.2 % slower than on the 80-channel
 // kernel, at 12 (16 x 186x248) and above it is 3 to 4 % faster; nothing in between was measured, so the floor is the
 // lowest count that was seen to win.
-inline bool conv_wr_pays(int B, int H, int W, int cout) {
+inline bool conv_wr_pays(int B, int H, int W, int cout, int ncu) {
     if (!SINDDM_CONV_WR || cout % WR_COB != 0) return false;
     return (long long)B * ((W + WH_TW - 1) / WH_TW) * ((H + WH_TH - 1) / WH_TH) * (cout / WR_COB) >=
-           (long long)SINDDM_WR_MIN_ITEMS_PER_CU * cu_count();
+           (long long)SINDDM_WR_MIN_ITEMS_PER_CU * ncu;
 }
 
 // variant: 0 = the library's choice (the 160-channel kernel where Cout % 160 == 0), 1 = the 80-channel kernel,

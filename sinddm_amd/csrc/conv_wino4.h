@@ -662,9 +662,9 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
 #define SINDDM_V4_MIN_ITEMS_PER_CU 2
 #endif
 
-inline bool conv_wino4_applies(int B, int H, int W, int coblks) {
+inline bool conv_wino4_applies(int B, int H, int W, int coblks, int ncu) {
     return (long long)B * ((W + W4_TW - 1) / W4_TW) * ((H + W4_TH - 1) / W4_TH) * coblks >=
-           (long long)SINDDM_V4_MIN_ITEMS_PER_CU * cu_count();
+           (long long)SINDDM_V4_MIN_ITEMS_PER_CU * ncu;
 }
 
 inline int conv_wino4_launch(const ConvArgs& a_in, hipStream_t st) {

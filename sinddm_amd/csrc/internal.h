@@ -1,6 +1,7 @@
 // Declarations shared between the forward and backward translation units of libsinddm_hip.so.
 #pragma once
 #include "common.h"
+#include "fwd_plan.h"
 
 namespace sinddm {
 
@@ -69,32 +70,24 @@ struct TrainBufs {
 };
 
 struct ChainStep;   // sampler-run extras (sinddm_fwd.hip)
+// One network evaluation.  Inference (tb == nullptr) carves `ws` by the plan's offsets and refuses a workspace below its
+// core_bytes before any launch; a sampler step (cs) brings the plan of its half-batch, every other call builds its own.
 int net_forward_impl(const NetPlan& P, const float* params, const float* packed, const float* x, const int64_t* t_dev,
                      int t_host, float scale, float* out, int B, int H, int W, void* ws, size_t ws_bytes,
                      hipStream_t st, const TrainBufs* tb, const ChainStep* cs = nullptr);
 
-// one SinDDMConvBlock forward (sinddm_fwd.hip); `cond` = the block's per-sample bias rows, stride in floats
-int block_forward(const NetPlan& P, int l, const float* params, const float* packed, const float* cur, const float* cond,
-                  int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, int B, int H, int W, hipStream_t st,
-                  const int route[2], int Wt = 0, float* amax = nullptr);
-// Which kernel a 3x3 conv launch takes -- THE routing rule (sinddm_fwd.hip), asked by the forward, the backward's data
-// gradients, the sampler's "stay whole" check and the debug hooks alike.  The values are the ones the hooks report and
-// ConvProfiler::gen records.  have_amax: the running-max scalars conv_wh needs exist for this launch (forward: the
-// evaluation has them; backward: conv1's data gradient only when conv2's took conv_wh); first_conv: a block's conv1
-// (only it may take the C_in = 3 kernel).
-enum ConvKernel { CONV_DIRECT = 0, CONV_C3 = 1, CONV_WINO2 = 2, CONV_WINO3 = 3, CONV_WINO4 = 4, CONV_WH = 8 };
-ConvKernel conv3x3_route(const NetPlan& P, const Conv3x3Images& c, int B, int H, int W, bool have_amax, bool first_conv);
+// One SinDDMConvBlock forward (sinddm_fwd.hip) as F describes block l: routes, conv_wh variants, running-max slots, the
+// residual form, the bias source and the row pitch are the plan's; `cond` = the block's per-sample bias rows, stride in
+// floats; `amax` = the evaluation's running maxima [B][AMAX_STRIDE] (may be null where the plan names no slot).
+int block_forward(const NetPlan& P, const ForwardPlan& F, int l, const float* params, const float* packed, const float* cur,
+                  const float* cond, int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, hipStream_t st,
+                  float* amax);
 // One launch of the routed kernel (every route but CONV_C3, which block_forward launches itself): fills w3, nch3, wsinv,
 // coblks and the m-tile count from the images at `packed`; the caller has set the tensors, act / aux / resid / bias, the
-// fused 1x1 fields of the direct kernel and the amax pointers.
+// fused 1x1 fields of the direct kernel and the amax pointers.  wh_variant (read on CONV_WH only) is resolved by the
+// caller: 1 = the 80-channel kernel (training: forward and data gradients), 2 = the 160-channel one (FwdBlock::wh_variant).
 struct ConvArgs;
-// wh_variant (CONV_WH only): 0 = items of 160 output channels where C_out % 160 == 0 and the launch is large enough (conv_wr_pays), 1 = the
-// 80-channel kernel (training: its forward, see block_forward, and its data gradients, see block_backward).
-int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st, int wh_variant = 0);
-// the routes of one network evaluation: out[2 l + i] = conv i + 1 of block l (-1: not launched -- block 4's conv2 under
-// the collapsed head).  Wp = the row pitch the evaluation runs at; returns whether any route is CONV_WH.
-bool forward_routes(const NetPlan& P, bool train, int B, int H, int Wp, bool have_amax, int out[8]);
-int forward_pitch(const NetPlan& P, int W);        // row pitch of an INFERENCE evaluation's activations
+int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st, int wh_variant);
 
 // conv_wh.h (the Winograd F(2x4) kernel with binary16 hi/lo frequency GEMMs) lives in sinddm_fwd.hip; the backward TU
 // packs a conv's images (transpose = 1: of its data gradient) and asks whether the kernel is compiled in through these

@@ -1083,15 +1083,18 @@ struct BlockBackward {
     WgradPlan w2, wres, w1;   // weight gradients of conv2, the residual 1x1 (wres.nwg == 0: identity residual) and conv1
     bool dw_rows;          // depthwise weight gradient on the register-window rows kernel (wide aligned images), else tiles
 };
-static BlockBackward block_backward_plan(const NetPlan& P, const BwdPack& k, int l, int B, int H, int W, bool have_amax, int ncu) {
+// F: the FWD_TRAIN plan of the forward this backward follows (its shape and CU count route the data gradients, its conv1
+// route says whether forward slot 2l exists); ncu sizes the weight-gradient grids only (a hook may ask for another device's).
+static BlockBackward block_backward_plan(const NetPlan& P, const BwdPack& k, const ForwardPlan& F, int l, bool have_amax, int ncu) {
     const BlockPlan& b = P.blk[l];
+    const int B = F.B, H = F.H, W = F.W;
     BlockBackward d{};
-    d.dg2 = conv3x3_route(P, k.dg2[l], B, H, W, have_amax, false);
+    d.dg2 = conv3x3_route(P, k.dg2[l], B, H, W, have_amax, false, F.ncu);
     d.wh2 = d.dg2 == CONV_WH;
-    d.dg1 = conv3x3_route(P, k.dg1[l], B, H, W, d.wh2, false);
+    d.dg1 = conv3x3_route(P, k.dg1[l], B, H, W, d.wh2, false, F.ncu);
     d.wh1 = d.dg1 == CONV_WH;
-    d.wha = d.wh1 && conv3x3_route(P, b.c1, B, H, W, true, true) == CONV_WH;
-    d.pub = l > 0 && conv3x3_route(P, k.dg2[l - 1], B, H, W, have_amax, false) == CONV_WH;
+    d.wha = d.wh1 && F.route[2 * l] == CONV_WH;
+    d.pub = l > 0 && conv3x3_route(P, k.dg2[l - 1], B, H, W, have_amax, false, F.ncu) == CONV_WH;
     d.w2 = wgrad_plan(9, b.cout, b.cout, B, H, W, true, d.wh2 && wh_enabled(), ncu);
     if (b.res_w >= 0) d.wres = wgrad_plan(1, b.cin, b.cout, B, H, W, false, false, ncu);
     d.w1 = wgrad_plan(9, b.cin, b.cout, B, H, W, true, d.wha && wh_enabled(), ncu);
@@ -1102,14 +1105,15 @@ static BlockBackward block_backward_plan(const NetPlan& P, const BwdPack& k, int
 // Backward of ONE SinDDMConvBlock (autograd of reference SinDDM/models.py:69-80): dO = gradient of the block output (scratch,
 // overwritten), xin = the block input, saved tensors of block l from `tb`; weight / bias gradients are ADDED into `grads`,
 // the per-sample condition gradient goes to tb.dcond, the input gradient to `dst` (skipped when null).  dU / dH: scratch.
-static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float* params, const float* packed_bwd,
+static int block_backward(const NetPlan& P, const BwdPack& k, const ForwardPlan& F, int l, const float* params, const float* packed_bwd,
                           const float* xin, float* dO, float* dU, float* dH, float* dst, float* grads, const TrainBufs& tb,
-                          int B, int H, int W, hipStream_t st, float* amax_b = nullptr, bool dO_published = false) {
+                          hipStream_t st, float* amax_b = nullptr, bool dO_published = false) {
     const BlockPlan& b = P.blk[l];
+    const int B = F.B, H = F.H, W = F.W;
     const float* zp = packed_bwd + k.zero;
     int rc;
     // `amax_b` = the backward half of tb.amax (zeroed by the caller); slot 2l comes from the kernel that wrote dO when `dO_published`
-    const BlockBackward d = block_backward_plan(P, k, l, B, H, W, amax_b != nullptr, cu_count());
+    const BlockBackward d = block_backward_plan(P, k, F, l, amax_b != nullptr, F.ncu);
     if (d.wh2 && !dO_published) {
         rc = amax_tensor_launch(dO, amax_b + 2 * l, B, (long long)b.cout * H * W, st);
         if (rc) return rc;
@@ -1132,7 +1136,7 @@ static int block_backward(const NetPlan& P, const BwdPack& k, int l, const float
         // (both data gradients keep conv_wh's 80-channel kernel: with the 160-channel one the input gradient of the closed-form
         // network at 8 x 186x248 sits 1.44e-5 from float64 against 7.2e-6 -- the fp32 path: 5.7e-6 -- and
         // test_gpu_train's gate of 1.5 x fails, although block by block on He weights it is the more accurate kernel;
-        // cause not found, profiles/NOTES_r30.md.  The training forward keeps it too: block_forward)
+        // cause not found, profiles/NOTES_r30.md.  The training forward keeps it too: FWD_TRAIN)
         rc = conv3x3_launch(d.dg2, k.dg2[l], packed_bwd, c, st, 1);
     }
     if (rc) return rc;
@@ -1173,10 +1177,11 @@ static int net_backward_impl(const NetPlan& P, const float* params, const float*
                              const float* grad_out, float* grads, float* grad_x, int B, int H, int W,
                              const TrainBufs& tb, hipStream_t st) {
     const BwdPack k = make_bwd_pack(P);
+    const ForwardPlan F = forward_plan(P, FWD_TRAIN, B, H, W, cu_count());
     const float* zp = packed_bwd + k.zero;
     int rc;
     // ---- final 1x1 conv: weight/bias grads, then data grad into s[0] ----
-    rc = wgrad_launch(wgrad_plan(1, P.half, CHANNELS, B, H, W, false, false, cu_count()), zp, grad_out, tb.o[3], grads + P.fin_w,
+    rc = wgrad_launch(wgrad_plan(1, P.half, CHANNELS, B, H, W, false, false, F.ncu), zp, grad_out, tb.o[3], grads + P.fin_w,
                       grads + P.fin_b, st);
     if (rc) return rc;
     int di = 0;   // index of the scratch buffer holding dOut of the current block
@@ -1191,7 +1196,7 @@ static int net_backward_impl(const NetPlan& P, const float* params, const float*
         float* dH = tb.s[(di + 2) & 3];
         float* dX = tb.s[(di + 3) & 3];
         float* dst = (l == 0) ? grad_x : dX;
-        rc = block_backward(P, k, l, params, packed_bwd, xin, dO, dU, dH, (l > 0 || grad_x) ? dst : nullptr, grads, tb, B, H, W, st,
+        rc = block_backward(P, k, F, l, params, packed_bwd, xin, dO, dU, dH, (l > 0 || grad_x) ? dst : nullptr, grads, tb, st,
                             amax_b, l < 3);
         if (rc) return rc;
         if (l > 0 || grad_x) di = (di + 3) & 3;
@@ -1330,12 +1335,12 @@ int sinddm_debug_routes(int dim_arg, int train, int B, int H, int W, int out[16]
     NetPlan p = make_plan(dim_arg);
     if (!p.ok || !out || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
     for (int i = 0; i < 16; ++i) out[i] = -1;
-    // (both evaluations have the running-max scalars: the workspace carves them)
-    forward_routes(p, train != 0, B, H, train ? W : forward_pitch(p, W), true, out);
+    const ForwardPlan F = forward_plan(p, train ? FWD_TRAIN : FWD_INFER, B, H, W, cu_count());
+    for (int i = 0; i < 8; ++i) out[i] = F.route[i];
     if (train) {
         const BwdPack k = make_bwd_pack(p);
         for (int l = 0; l < 4; ++l) {
-            const BlockBackward d = block_backward_plan(p, k, l, B, H, W, true, cu_count());
+            const BlockBackward d = block_backward_plan(p, k, F, l, true, F.ncu);
             out[8 + 2 * l] = d.dg2; out[8 + 2 * l + 1] = d.dg1;
         }
     }
@@ -1370,16 +1375,15 @@ int sinddm_debug_block_train(const float* params, const float* packed, const flo
     const BlockPlan& b = p.blk[l];
     const size_t HW = (size_t)H * W;
     if (hipMemsetAsync(tb.amax, 0, (size_t)2 * B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
-    const int route[2] = {conv3x3_route(p, b.c1, B, H, W, true, true), conv3x3_route(p, b.c2, B, H, W, true, false)};
-    int rc = block_forward(p, l, params, packed, x, cond_bias, b.cin, tb.h[l], tb.g[l], tb.o[l], tb.u[l], B, H, W, st, route, 0,
-                           tb.amax + 2 * l);
+    const ForwardPlan F = forward_plan(p, FWD_TRAIN, B, H, W, cu_count());
+    int rc = block_forward(p, F, l, params, packed, x, cond_bias, b.cin, tb.h[l], tb.g[l], tb.o[l], tb.u[l], st, tb.amax);
     if (rc) return rc;
     if (hipMemcpyAsync(y, tb.o[l], B * b.cout * HW * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return SINDDM_E_BADARG;
     if (hipMemcpyAsync(tb.s[0], grad_y, B * b.cout * HW * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return SINDDM_E_BADARG;
     const BwdPack k = make_bwd_pack(p);
-    rc = block_backward(p, k, l, params, packed_bwd, x, tb.s[0], tb.s[1], tb.s[2], grad_x, grad_params, tb, B, H, W, st,
+    rc = block_backward(p, k, F, l, params, packed_bwd, x, tb.s[0], tb.s[1], tb.s[2], grad_x, grad_params, tb, st,
                         tb.amax + (size_t)B * AMAX_STRIDE, false);
     if (rc) return rc;
     if (hipMemcpy2DAsync(dcond, b.cin * sizeof(float), tb.dcond + b.cond_off, p.cond_stride * sizeof(float),
@@ -1467,12 +1471,13 @@ int sinddm_debug_wgrad(int taps, int Cin, int Cout, int B, int H, int W, int ncu
 int sinddm_debug_wgrad_routes(int dim_arg, int B, int H, int W, int ncu, int* out, int cap) {
     NetPlan p = make_plan(dim_arg);
     if (!p.ok || !out || cap < 4 * 17 || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
-    if (ncu <= 0) ncu = cu_count();
+    const ForwardPlan F = forward_plan(p, FWD_TRAIN, B, H, W, cu_count());      // (the routes ask the device, see the header)
+    if (ncu <= 0) ncu = F.ncu;
     for (int i = 0; i < 4 * 17; ++i) out[i] = -1;
     wgrad_report(wgrad_plan(1, p.half, CHANNELS, B, H, W, false, false, ncu), out);
     const BwdPack k = make_bwd_pack(p);
     for (int l = 3; l >= 0; --l) {
-        const BlockBackward d = block_backward_plan(p, k, l, B, H, W, true, ncu);
+        const BlockBackward d = block_backward_plan(p, k, F, l, true, ncu);
         int* o = out + 4 * (1 + 4 * (3 - l));
         wgrad_report(d.w2, o);
         if (d.wres.nwg > 0) wgrad_report(d.wres, o + 4);

@@ -483,17 +483,13 @@ __global__ __launch_bounds__(256) void dwconv5_rows_kernel(const float* __restri
     if (amax) amax_publish(mx, amax + (size_t)b * AMAX_STRIDE);          // (every lane of a live wave gets here: no divergent exit above)
 }
 
-#ifndef SINDDM_DW_ROWS
-#define SINDDM_DW_ROWS 1
-#endif
-
 // pi / po: row pitch of the input / output planes (0 = W).  po > W: padded workspace rows, pads written as zeros.
 int dwconv_launch(const float* x, const float* w, const float* bias, const float* cond, int cond_stride,
                   const float* addt, int flip, float* out, int B, int C, int H, int W, hipStream_t st, int pi, int po,
                   float* amax) {
     if (pi <= 0) pi = W;
     if (po <= 0) po = W;
-    if (SINDDM_DW_ROWS && pi % 4 == 0 && po == pi && pi >= 192) {   // (a lane owns 4 columns: narrow images leave most of a wave idle)
+    if (dw_rows_applies(pi, po)) {
         const int bandsX = (pi + 255) / 256, bandsY = (H + 4 * DWR_ROWS - 1) / (4 * DWR_ROWS);
         hipLaunchKernelGGL(dwconv5_rows_kernel, dim3(bandsX * bandsY, C, B), dim3(256), 0, st, x, w, bias, cond, cond_stride,
                            addt, flip, out, C, H, pi, bandsX, W, amax);
@@ -868,58 +864,16 @@ __global__ __launch_bounds__(256) void q_sample_wrap_kernel(const float* __restr
 // =====================================================================================
 // whole-network forward orchestration
 // =====================================================================================
-struct FwdBuffers {
-    float* cond;    // [B][cond_stride]
-    float* buf[4];  // each B*dim*H*W
-};
+}  // namespace sinddm
+// the rules of one evaluation (fwd_plan.h), compiled here behind the kernel headers whose thresholds they read
+#define SINDDM_FWD_PLAN_DEFINE
+#include "fwd_plan.h"
+namespace sinddm {
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// conditioning rows: one per sample (sinddm_net_forward) or one per sampler step of a run (sinddm_sample_chain: every
-// sample of the batch shares the step's t, so a whole run of steps is embedded by ONE cond_kernel launch)
-constexpr int CHAIN_COND_ROWS = 1024;
-// ... followed by the running-max scalars of one network evaluation (split16.h: [sample][AMAX_STRIDE], slot 2 l + i = max
-// |input| of conv i of block l, maintained by that tensor's producer kernel, zeroed at the start of the evaluation)
-static size_t amax_region_bytes(int B) { return ((size_t)B * AMAX_STRIDE * sizeof(float) + 255) / 256 * 256; }
-static size_t cond_region_bytes(const NetPlan& P, int B) {
-    const int rows = B > CHAIN_COND_ROWS ? B : CHAIN_COND_ROWS;
-    return align_up((size_t)rows * P.cond_stride * sizeof(float), 256) + amax_region_bytes(B);
-}
-#ifndef SINDDM_PITCH
-#define SINDDM_PITCH 1        // 1: inference keeps its activations with rows padded to a multiple of 4 floats (W % 4 != 0 scales)
-#endif
-// row pitch of the library's own activation buffers in inference: W rounded up to 4 floats
-// Padded rows need every producer to write the pad columns as zeros (ConvArgs::Wt): the depthwise kernels, the C_in = 3
-// conv, the Winograd kernels of conv_wino2/3/4.h and conv_wh do; the direct implicit-GEMM kernel (conv_mfma.h) does not.  So the pitch is a property of the PLAN: rows are padded only when
-// block_forward routes every 3x3 conv of the network to a Wt-aware kernel (all channel counts multiples of 4, C_in = 3 or
-// >= 8) -- other widths (--dim 10, 20, 28 ...) keep plain rows and the kernels' edge variants.
-static bool plan_pads_rows(const NetPlan& P) {
-    if (!SINDDM_PITCH || !wino_enabled() || !SINDDM_CONV_C3) return false;
-    for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        if (b.cout % 4 != 0) return false;
-        if (b.cin != 3 && !(b.c1.wino2 >= 0 && b.cin % 4 == 0)) return false;
-    }
-    return true;
-}
-static int fwd_pitch(const NetPlan& P, int W) { return (W % 4 != 0 && plan_pads_rows(P)) ? (W + 3) / 4 * 4 : W; }
-static size_t fwd_xpad_bytes(const NetPlan& P, int B, int H, int W) {        // padded copy of the network input (only when the pitch differs)
-    return fwd_pitch(P, W) != W ? align_up((size_t)B * CHANNELS * H * fwd_pitch(P, W) * sizeof(float), 256) : 0;
-}
-// what one network evaluation of batch B carves from its workspace: conditioning rows, 4 activation buffers, padded input
-static size_t fwd_workspace_core(const NetPlan& P, int B, int H, int W) {
-    const size_t act = align_up((size_t)B * P.dim * H * fwd_pitch(P, W) * sizeof(float), 256);
-    return cond_region_bytes(P, B) + 4 * act + fwd_xpad_bytes(P, B, H, W);
-}
-// ... and what sinddm_workspace_bytes reports: room for a sampler run that splits the batch into two halves on two
-// streams (sinddm_sample_chain2): the shared conditioning table + two cores of half the batch
-static size_t fwd_workspace_bytes(const NetPlan& P, int B, int H, int W) {
-    return fwd_workspace_core(P, B, H, W) + 2 * cond_region_bytes(P, (B + 1) / 2) + 4096;
-}
-
-// sampler-run extras of net_forward_impl: the step's conditioning row (already computed, shared by the batch) and the
-// fused tail (final conv + reverse step)
+// sampler-run extras of net_forward_impl: the plan of the half-batch (built once per chain call), the step's conditioning
+// row (already computed, shared by the batch) and the fused tail (final conv + reverse step)
 struct ChainStep {
+    const ForwardPlan* plan;
     const float* cond_row;
     const float* x_tilde;
     float* x_next;
@@ -969,31 +923,8 @@ static int tail_rows_launch(const TailIO& io, const TailArgs& t, bool mid_quad, 
 #define TAIL_KERNEL(name) \
     [](auto E, auto N, auto K) { return &name<decltype(E)::value, decltype(N)::value, decltype(K)::value>; }
 
-// Where inference takes the collapsed head (head.h) instead of block 4's conv2 + residual projection + final_conv: the
-// activation rows are 16-byte aligned (Wp = the workspace pitch: W % 4 == 0, or the plan pads its rows), which is also
-// where a sampler run fuses its tail ((H W) % 4 == 0 or padded rows: sample_chain_impl); a plane stays below the buffer
-// loads' out-of-range offset.  Every other shape keeps its launches, kernel for kernel; training (`tb`) needs block 4's
-// output for backward.
-static bool head_applies(bool train, int H, int Wp) {
-    return SINDDM_HEAD_COLLAPSE && !train && Wp % 4 == 0 && (long long)H * Wp < (1LL << 28);
-}
 static HeadEps head_eps(const NetPlan& P, const float* packed, const float* g, const float* xin, int H, int Wp) {
     return HeadEps{g, xin, packed + P.pk_hc, packed + P.pk_hr, packed + P.pk_hb, P.half, P.dim, H, Wp};
-}
-
-// THE routing rule of the 3x3 convs (internal.h): conv_wh where the running maxima exist and its own rule takes the launch;
-// launches with enough work for every workgroup slot the F(2x4) kernels (25 % fewer MFMAs), the ones with several 8x32
-// items per CU conv_wino4's one-wave-per-SIMD form; then F(2x2) (its kernel stages a wave's four channel planes of a chunk
-// through one descriptor: K % 4 == 0 -- dim = 10, 20, 28 ... stay direct); the C_in = 3 kernel; the direct implicit GEMM.
-ConvKernel conv3x3_route(const NetPlan& P, const Conv3x3Images& c, int B, int H, int W, bool have_amax, bool first_conv) {
-    if (wino_enabled() && c.K % 4 == 0) {
-        if (have_amax && c.wh >= 0 && conv_wh_applies(P.fp32_convs, B, H, W, c.K, c.M)) return CONV_WH;
-        if (SINDDM_WINO_V3 && c.wino24 >= 0 &&
-            (long long)B * ((W + 31) / 32) * ((H + 3) / 4) * c.coblks >= SINDDM_V3_MIN_ITEMS_PER_CU * cu_count())
-            return SINDDM_WINO_V4 && conv_wino4_applies(B, H, W, c.coblks) ? CONV_WINO4 : CONV_WINO3;
-        if (c.wino2 >= 0) return CONV_WINO2;
-    }
-    return first_conv && c.K == 3 && SINDDM_CONV_C3 ? CONV_C3 : CONV_DIRECT;
 }
 
 int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st, int wh_variant) {
@@ -1001,8 +932,7 @@ int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, Co
     switch (k) {
         case CONV_WH:
             a.w3 = packed + c.wh; a.wsinv = packed + c.wh_sinv;
-            // (launches too small for items of 160 channels keep the 80-channel kernel: conv_wr_pays)
-            if (wh_variant == 0 && !conv_wr_pays(a.B, a.H, a.W, a.Cout)) wh_variant = 1;
+            if (wh_variant != 1 && wh_variant != 2) return SINDDM_E_BADARG;      // (the caller's plan resolves it)
             return conv_wh_launch(a, st, wh_variant);
         case CONV_WINO4:
         case CONV_WINO3:
@@ -1019,66 +949,45 @@ int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, Co
     }
 }
 
-bool forward_routes(const NetPlan& P, bool train, int B, int H, int Wp, bool have_amax, int out[8]) {
-    const bool head = head_applies(train, H, Wp);
-    bool any = false;
-    for (int l = 0; l < 4; ++l) {
-        out[2 * l] = conv3x3_route(P, P.blk[l].c1, B, H, Wp, have_amax, true);
-        out[2 * l + 1] = head && l == 3 ? -1 : conv3x3_route(P, P.blk[l].c2, B, H, Wp, have_amax, false);
-        any = any || out[2 * l] == CONV_WH || out[2 * l + 1] == CONV_WH;
-    }
-    return any;
-}
-int forward_pitch(const NetPlan& P, int W) { return fwd_pitch(P, W); }
-
 // One SinDDMConvBlock forward (reference SinDDM/models.py:69-80): depthwise 5x5 + per-sample condition -> hbuf, 3x3 conv +
 // GELU -> gbuf (pre-activation -> upre when the training forward saves it), 3x3 conv + residual (1x1 projection or
 // identity of `cur`) -> obuf.  `cond` = the block's per-sample bias rows ([B][cond_stride]; stride 0: one row for the batch).
-// route: the ConvKernel of conv1 and conv2 (forward_routes).  route[1] < 0: the block stops behind conv1 (block 4 in front of
-// the collapsed head, which reads gbuf and cur itself): no conv2, no residual projection, and conv1 does not publish the
-// running max that conv2 would read.
-// Wt > 0: padded workspace rows -- every tensor here (cur included) has row pitch W (a multiple of 4) and true width Wt.
-// amax = this block's two running-max scalars (input of conv1, input of conv2), maintained by the kernels that produce
-// those tensors for the convs that conv_wh takes.
-int block_forward(const NetPlan& P, int l, const float* params, const float* packed, const float* cur, const float* cond,
-                  int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, int B, int H, int W, hipStream_t st,
-                  const int route[2], int Wt, float* amax) {
+// Everything decided is F's (fwd_plan.h): this function fills argument structs and launches.  Every tensor here (cur
+// included) has row pitch F.Wp; F.Wt > 0: padded rows of true width F.Wt.  A block whose conv2 has no route (block 4 in
+// front of the collapsed head, which reads gbuf and cur itself) stops behind conv1.
+int block_forward(const NetPlan& P, const ForwardPlan& F, int l, const float* params, const float* packed, const float* cur,
+                  const float* cond, int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, hipStream_t st,
+                  float* amax) {
     const BlockPlan& b = P.blk[l];
-    const bool wha = route[0] == CONV_WH, whb = route[1] == CONV_WH;
-    if ((wha || whb) && !amax) return SINDDM_E_BADARG;
-    // the training forward (the one that saves upre) keeps conv_wh's 80-channel kernel, as its data gradients do
-    // (block_backward): training computes what it computed, and the gates that pin it stay where they are.  Inference takes
-    // conv_wh_launch's choice -- items of 160 output channels where C_out % 160 == 0 (profiles/NOTES_r30.md)
-    const int wh_variant = upre ? 1 : 0;
-    int rc = Wt > 0 ? dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
-                                    Wt, st, W, W, wha ? amax : nullptr)
-                    : dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
-                                    W, st, 0, 0, wha ? amax : nullptr);
+    const FwdBlock& f = F.blk[l];
+    const int B = F.B, H = F.H, W = F.Wp, Wt = F.Wt;
+    const ConvKernel k1 = (ConvKernel)F.route[2 * l], k2 = (ConvKernel)F.route[2 * l + 1];
+    if ((f.amax_dw >= 0 || f.amax_in[1] >= 0) && !amax) return SINDDM_E_BADARG;
+    auto slot = [&](int i) { return i >= 0 ? amax + i : nullptr; };
+    int rc = dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
+                           Wt > 0 ? Wt : W, st, f.dw_pi, f.dw_po, slot(f.amax_dw));
     if (rc) return rc;
-    if (route[0] == CONV_C3) {
+    if (k1 == CONV_C3) {
         // C_in = 3: dedicated VALU kernel straight from the PyTorch-layout weights
         const int nwg = ((H * W + 255) / 256) * B;
         int split = 1;                                       // channel groups: aim at >= ~2048 workgroups
         while (split < 8 && nwg * split < 2048 && b.cout % (split * 2) == 0) split *= 2;
         hipLaunchKernelGGL(conv3x3_c3_gelu_kernel, dim3((H * W + 255) / 256, B, split), dim3(256), 0, st, hbuf,
                            params + b.c1_w, params + b.c1_b, gbuf, upre, H, W, b.cout, b.cout / split, Wt > 0 ? Wt : W,
-                           whb ? amax + 1 : nullptr);
+                           slot(f.amax_out1));
         SINDDM_LAUNCH_CHECK();
     } else {
         ConvArgs c1{};
         c1.in = hbuf; c1.out = gbuf; c1.out_pre = upre;
         c1.B = B; c1.H = H; c1.W = W; c1.Cin = b.cin; c1.Cout = b.cout;
         c1.act = 1; c1.zero = packed + P.pk_zero; c1.Wt = Wt;
-        c1.bias = wha ? params + b.c1_b : packed + b.pk_b1;      // (conv_wh reads the plain bias row)
-        if (wha) { c1.amax_in = amax; c1.amax_out = whb ? amax + 1 : nullptr; }
-        rc = conv3x3_launch((ConvKernel)route[0], b.c1, packed, c1, st, wh_variant);
+        c1.bias = f.bias_plain ? params + b.c1_b : packed + b.pk_b1;
+        c1.amax_in = slot(f.amax_in[0]); c1.amax_out = slot(f.amax_out1);
+        rc = conv3x3_launch(k1, b.c1, packed, c1, st, f.wh_variant[0]);
     }
-    if (rc || route[1] < 0) return rc;
-    // conv2 on the binary16 kernel reads the running max of g (slot amax + 1): conv_wh / the C_in = 3 kernel publish it
-    // from their epilogues, the fp32 kernels do not (dim = 80 / 240: block 1 has C_in = dim / 2, not a multiple of 16, so conv1
-    // stays on an fp32 kernel while conv2 qualifies) -- one pass over g then
-    if (whb && !wha && route[0] != CONV_C3) {
-        rc = amax_tensor_launch(gbuf, amax + 1, B, (long long)b.cout * H * W, st);
+    if (rc || f.resid == RESID_NONE) return rc;
+    if (f.max_pass) {
+        rc = amax_tensor_launch(gbuf, slot(f.amax_in[1]), B, (long long)b.cout * H * W, st);
         if (rc) return rc;
     }
     ConvArgs c2{};
@@ -1086,11 +995,12 @@ int block_forward(const NetPlan& P, int l, const float* params, const float* pac
     c2.B = B; c2.H = H; c2.W = W; c2.Cin = b.cout; c2.Cout = b.cout;
     c2.act = 0; c2.zero = packed + P.pk_zero; c2.Wt = Wt;
     c2.bias = packed + b.pk_b2;
-    if (b.nchr == 0) c2.resid = cur;
-    else if (route[1] == CONV_DIRECT) {          // the direct kernel fuses the 1x1 residual projection
+    c2.amax_in = slot(f.amax_in[1]);
+    if (f.resid == RESID_IDENTITY) c2.resid = cur;
+    else if (f.resid == RESID_FUSED_DIRECT) {
         c2.in2 = cur; c2.Cin2 = b.cin; c2.w1 = packed + b.pk_res; c2.nch1 = b.nchr;
     } else {
-        // the Winograd kernels do not: it runs first on the 1x1 kernel and is added as `resid`
+        // the Winograd kernels do not fuse the projection: it runs first on the 1x1 kernel and is added as `resid`
         ConvArgs r1{};
         r1.in2 = cur; r1.Cin2 = b.cin; r1.w1 = packed + b.pk_res; r1.nch1 = b.nchr; r1.nch3 = 0;
         r1.bias = packed + b.pk_b2; r1.out = obuf; r1.Cout = b.cout; r1.coblks = b.coblks;
@@ -1099,8 +1009,7 @@ int block_forward(const NetPlan& P, int l, const float* params, const float* pac
         if (rc) return rc;
         c2.resid = obuf; c2.bias = nullptr;          // in place: each thread reads resid[o] before writing out[o]
     }
-    if (whb) c2.amax_in = amax + 1;
-    return conv3x3_launch((ConvKernel)route[1], b.c2, packed, c2, st, wh_variant);
+    return conv3x3_launch(k2, b.c2, packed, c2, st, f.wh_variant[1]);
 }
 
 bool wh_enabled() { return SINDDM_CONV_WH != 0; }
@@ -1131,34 +1040,48 @@ int amax_tensor_launch(const float* x, float* amax, int B, long long per_sample,
     return 0;
 }
 
+// The fused tail of a sampler step on the eps stage `e` (HeadEps or FinalConvEps), on padded or plain rows: the one place
+// that turns the step's options into a tail kernel's template arguments.
+template <class EPS>
+static void fused_tail_launch(const ForwardPlan& F, bool pitch, const EPS& e, const float* x, const ChainStep& cs, hipStream_t st) {
+    const dim3 grid(F.last_gx[1], F.B);
+    tail_dispatch(cs.tail, [&](auto E, auto N, auto K) {
+        if (pitch)
+            hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, EPS>),
+                               grid, dim3(256), 0, st, e, x, cs.x_tilde, cs.x_next, F.H, F.W, F.Wp, cs.tail);
+        else
+            hipLaunchKernelGGL((final_conv_reverse_step_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, EPS>),
+                               grid, dim3(256), 0, st, e, x, cs.x_tilde, cs.x_next, F.HW, cs.tail);
+    });
+}
+
 int net_forward_impl(const NetPlan& P, const float* params, const float* packed, const float* x, const int64_t* t_dev,
                      int t_host, float scale, float* out, int B, int H, int W, void* ws, size_t ws_bytes,
                      hipStream_t st, const TrainBufs* tb, const ChainStep* cs) {
-    FwdBuffers fb{};
+    const ForwardPlan own = cs ? ForwardPlan{} : forward_plan(P, tb ? FWD_TRAIN : FWD_INFER, B, H, W, cu_count());
+    const ForwardPlan& F = cs ? *cs->plan : own;
+    if (F.B != B || F.H != H || F.W != W) return SINDDM_E_BADARG;
+    float* cond = nullptr;
+    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
     float* xpad = nullptr;
-    float* amax = nullptr;       // eight running-max scalars per sample (split16.h)
+    float* amax = nullptr;       // AMAX_STRIDE running-max scalars per sample (split16.h)
     if (tb) {
-        fb.cond = tb->cond;
+        cond = tb->cond;
         amax = tb->amax;
     } else {
-        if (ws_bytes < fwd_workspace_core(P, B, H, W)) return SINDDM_E_WORKSPACE;
+        if (ws_bytes < F.core_bytes) return SINDDM_E_WORKSPACE;
         char* base = static_cast<char*>(ws);
-        fb.cond = reinterpret_cast<float*>(base);
-        base += cond_region_bytes(P, B);
-        amax = reinterpret_cast<float*>(base - amax_region_bytes(B));
-        const size_t act = align_up((size_t)B * P.dim * H * fwd_pitch(P, W) * sizeof(float), 256);
-        for (int i = 0; i < 4; ++i) fb.buf[i] = reinterpret_cast<float*>(base + i * act);
-        xpad = reinterpret_cast<float*>(base + 4 * act);
+        cond = reinterpret_cast<float*>(base + F.off_cond);
+        amax = reinterpret_cast<float*>(base + F.off_amax);
+        for (int i = 0; i < 4; ++i) buf[i] = reinterpret_cast<float*>(base + F.off_buf[i]);
+        xpad = reinterpret_cast<float*>(base + F.off_xpad);
     }
-    // padded rows: inference only (the training workspace keeps plain tensors: backward reads them with the plain kernels)
-    const int Wp = tb ? W : fwd_pitch(P, W);
-    const bool padded = Wp != W;
     int cond_stride = P.cond_stride;
-    if (cs) { fb.cond = const_cast<float*>(cs->cond_row); cond_stride = 0; }
+    if (cs) { cond = const_cast<float*>(cs->cond_row); cond_stride = 0; }
 
     CondArgs ca = cond_args(P, params);
     ca.t_dev = reinterpret_cast<const long long*>(t_dev); ca.t_host = t_host; ca.scale = scale;
-    ca.out = fb.cond;
+    ca.out = cond;
     ca.cond_vec = tb ? tb->cvec : nullptr; ca.hidden = tb ? tb->hpre : nullptr;
     ca.emb_out = tb ? tb->emb : nullptr; ca.mvec_out = tb ? tb->mvec : nullptr;
     if (!cs) {
@@ -1166,84 +1089,56 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
         SINDDM_LAUNCH_CHECK();
     }
 
-    // the routes of this evaluation's eight 3x3 convs.  The running-max scalars exist for the binary16 kernels: a launch
-    // shape none of them takes (coarse pyramid scales) neither maintains nor zeroes them
-    int route[8];
-    if (!forward_routes(P, tb != nullptr, B, H, Wp, amax != nullptr, route)) amax = nullptr;
-    else if (hipMemsetAsync(amax, 0, (size_t)B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
-    const bool head = route[7] < 0;
+    // The running-max scalars exist for the binary16 kernels: a launch shape none of them takes (coarse pyramid scales)
+    // neither maintains nor zeroes them
+    if (!F.any_wh) amax = nullptr;
+    else if (!amax || hipMemsetAsync(amax, 0, (size_t)B * AMAX_STRIDE * sizeof(float), st) != hipSuccess) return SINDDM_E_BADARG;
     const float* cur = x;
-    if (padded) {
+    if (F.padded) {
         const long long nrows = (long long)B * CHANNELS * H;
-        const long long nq = nrows * (Wp / 4);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, x, xpad, H, W, Wp, nrows);
+        const long long nq = nrows * (F.Wp / 4);
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, x, xpad, H, W, F.Wp, nrows);
         SINDDM_LAUNCH_CHECK();
         cur = xpad;
     }
-    int freeb[4] = {0, 1, 2, 3};
     int curb = -1;
     const float* head_g = nullptr;
     for (int l = 0; l < 4; ++l) {
-        const BlockPlan& b = P.blk[l];
-        // pick three scratch buffers different from the one holding `cur`
+        // three scratch buffers different from the one holding `cur`
         int sel[3], n = 0;
         for (int i = 0; i < 4 && n < 3; ++i)
-            if (freeb[i] != curb) sel[n++] = freeb[i];
-        float* hbuf = tb ? tb->h[l] : fb.buf[sel[0]];
-        float* gbuf = tb ? tb->g[l] : fb.buf[sel[1]];
-        float* obuf = tb ? tb->o[l] : fb.buf[sel[2]];
-        const int rc = block_forward(P, l, params, packed, cur, fb.cond + b.cond_off, cond_stride, hbuf, gbuf, obuf,
-                                     tb ? tb->u[l] : nullptr, B, H, Wp, st, route + 2 * l, padded ? W : 0,
-                                     amax ? amax + 2 * l : nullptr);
+            if (i != curb) sel[n++] = i;
+        float* hbuf = tb ? tb->h[l] : buf[sel[0]];
+        float* gbuf = tb ? tb->g[l] : buf[sel[1]];
+        float* obuf = tb ? tb->o[l] : buf[sel[2]];
+        const int rc = block_forward(P, F, l, params, packed, cur, cond + P.blk[l].cond_off, cond_stride, hbuf, gbuf, obuf,
+                                     tb ? tb->u[l] : nullptr, st, amax);
         if (rc) return rc;
-        if (route[2 * l + 1] < 0) { head_g = gbuf; break; }  // (the collapsed head: cur stays block 4's input)
+        if (F.route[2 * l + 1] < 0) { head_g = gbuf; break; }  // (the collapsed head: cur stays block 4's input)
         cur = obuf;
         curb = sel[2];
     }
-    const int HW = H * W;
-    if (head) {
-        // the collapsed head: eps from block 4's g and input, under the step's tail in a sampler run
-        const HeadEps he = head_eps(P, packed, head_g, cur, H, Wp);
-        const dim3 grid((unsigned)((H * (Wp / 4) + 255) / 256), B);
-        if (cs && cs->x_next && padded)
-            tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
-                hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, HeadEps>),
-                                   grid, dim3(256), 0, st, he, x, cs->x_tilde, cs->x_next, H, W, Wp, cs->tail);
-            });
-        else if (cs && cs->x_next)
-            tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
-                hipLaunchKernelGGL((final_conv_reverse_step_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, HeadEps>),
-                                   grid, dim3(256), 0, st, he, x, cs->x_tilde, cs->x_next, HW, cs->tail);
-            });
-        else
-            hipLaunchKernelGGL(head_eps_kernel, grid, dim3(256), 0, st, he, out, W);
-        SINDDM_LAUNCH_CHECK();
-        return 0;
+    // the last launch: eps from block 4's g and input (the collapsed head) or from block 4's output (final_conv), under the
+    // step's tail where a sampler step fuses it
+    const HeadEps he = head_eps(P, packed, head_g, cur, H, F.Wp);
+    const FinalConvEps fe{cur, params + P.fin_w, params + P.fin_b, P.half, (size_t)H * F.Wp};
+    const int which = cs && cs->x_next ? 1 : 0;
+    const dim3 grid(F.last_gx[which], B);
+    switch (F.last[which]) {
+        case LAST_HEAD_STEP_PITCH: fused_tail_launch(F, true, he, x, *cs, st); break;
+        case LAST_HEAD_STEP: fused_tail_launch(F, false, he, x, *cs, st); break;
+        case LAST_HEAD_EPS: hipLaunchKernelGGL(head_eps_kernel, grid, dim3(256), 0, st, he, out, W); break;
+        case LAST_FINAL_STEP_PITCH: fused_tail_launch(F, true, fe, x, *cs, st); break;
+        case LAST_FINAL_PITCH:
+            hipLaunchKernelGGL(final_conv1x1_pitch_kernel, grid, dim3(256), 0, st, cur, params + P.fin_w, params + P.fin_b, out,
+                               P.half, H, W, F.Wp);
+            break;
+        case LAST_FINAL_STEP: fused_tail_launch(F, false, fe, x, *cs, st); break;
+        case LAST_FINAL:
+            hipLaunchKernelGGL(final_conv1x1_kernel, grid, dim3(256), 0, st, cur, params + P.fin_w, params + P.fin_b, out, P.half,
+                               F.HW);
+            break;
     }
-    const FinalConvEps fe{cur, params + P.fin_w, params + P.fin_b, P.half, (size_t)H * Wp};
-    if (padded) {
-        const unsigned gx = (unsigned)((H * (Wp / 4) + 255) / 256);
-        if (cs && cs->x_next)
-            tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
-                hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, FinalConvEps>),
-                                   dim3(gx, B), dim3(256), 0, st, fe, x, cs->x_tilde, cs->x_next, H, W, Wp, cs->tail);
-            });
-        else
-            hipLaunchKernelGGL(final_conv1x1_pitch_kernel, dim3(gx, B), dim3(256), 0, st, cur, params + P.fin_w,
-                               params + P.fin_b, out, P.half, H, W, Wp);
-        SINDDM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (cs && cs->x_next && HW % 4 == 0) {
-        tail_dispatch(cs->tail, [&](auto E, auto N, auto K) {
-            hipLaunchKernelGGL((final_conv_reverse_step_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, FinalConvEps>),
-                               dim3((HW / 4 + 255) / 256, B), dim3(256), 0, st, fe, x, cs->x_tilde, cs->x_next, HW, cs->tail);
-        });
-        SINDDM_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(final_conv1x1_kernel, dim3(((HW + 3) / 4 + 255) / 256, B), dim3(256), 0, st, cur, params + P.fin_w,
-                       params + P.fin_b, out, P.half, HW);
     SINDDM_LAUNCH_CHECK();
     return 0;
 }
@@ -1271,7 +1166,8 @@ int64_t sinddm_packed_count(int dim) { NetPlan p = make_plan(dim); return p.ok ?
 size_t sinddm_workspace_bytes(int dim, int B, int H, int W) {
     NetPlan p = make_plan(dim);
     if (!p.ok || B <= 0 || H <= 0 || W <= 0) return 0;
-    return fwd_workspace_bytes(p, B, H, W);
+    // (no device is asked: the layout does not depend on the CU count)
+    return chain_workspace_bytes(forward_plan(p, FWD_INFER, B, H, W, CU_COUNT_NO_DEVICE), forward_plan(p, FWD_INFER, (B + 1) / 2, H, W, CU_COUNT_NO_DEVICE));
 }
 
 int sinddm_pack_weights(const float* params, float* packed, int dim, void* stream) {
@@ -1506,6 +1402,7 @@ static int layout_step_launch(const TailIO& io, const TailArgs& t, const LayoutA
 struct ChainSplit {
     bool on;
     int Bh[2];                           // samples per half (one half: {B, 0})
+    ForwardPlan fp[2];                   // the evaluation each half runs, step after step
     char* wsh[2];                        // each half's workspace ...
     size_t wsz[2];                       // ... and its size
     size_t hoff;                         // the second half's offset into x / x_alt / eps / x_tilde
@@ -1520,7 +1417,7 @@ struct ChainCtx {
     BatchStrides bs;
     LayoutArgs lay;                      // the geometry of a run that pulls (D, g, gain: per launch)
     const float* lay_gain;
-    bool fuse_tail;                      // the network's last kernel ends in the plain step: (H W) % 4 == 0, or padded rows
+    ForwardPlan fp;                      // one evaluation of the whole batch: fuse_tail, rows_aligned, the split rule's figures
     hipStream_t st, sx;
     float* cond_tab;                     // the conditioning region: one row per step of a run
     ChainSplit sp;
@@ -1545,31 +1442,33 @@ static int chain_split(ChainCtx& k) {
     const NetPlan& p = k.p;
     const int B = r.B, H = k.c.H, W = k.c.W;
     ChainSplit& s = k.sp;
-    const long long items = (long long)B * ((fwd_pitch(p, W) + 31) / 32) * ((H + 7) / 8) * 2;
-    const long long ncu = cu_count();
+    const ForwardPlan& whole = k.fp;
+    const long long items = whole.conv_items, ncu = whole.ncu;
     const long long rounds = (items + ncu - 1) / ncu;
-    bool split = k.sx != nullptr && k.sx != k.st && B >= 2 && k.fuse_tail && r.n_steps > 0 && items < SINDDM_SPLIT_ITEMS_HI * ncu &&
+    bool split = k.sx != nullptr && k.sx != k.st && B >= 2 && whole.fuse_tail && r.n_steps > 0 && items < SINDDM_SPLIT_ITEMS_HI * ncu &&
                  items >= SINDDM_SPLIT_ITEMS_LO * ncu && (rounds * ncu - items) * 25 >= rounds * ncu;
     // (a batch whose 3x3 convs take the binary16 kernels stays whole: its halves could fall below their items-per-CU
     // threshold and run on the fp32 kernels -- the same chain would then round differently with and without a second stream)
-    if (split && conv3x3_route(p, p.blk[2].c2, B, H, fwd_pitch(p, W), true, false) == CONV_WH)       // (the dim -> dim conv)
-        split = false;
-    // (the two halves carve their own cores behind the shared conditioning table: only if that really fits -- ADVICE r4)
-    if (split && cond_region_bytes(p, B) + fwd_workspace_core(p, (B + 1) / 2, H, W) + fwd_workspace_core(p, B - (B + 1) / 2, H, W) > r.ws_bytes)
-        split = false;
+    if (split && whole.route[5] == CONV_WH) split = false;                    // (conv2 of the dim -> dim block)
     s = ChainSplit{};
-    s.on = split;
-    s.Bh[0] = split ? (B + 1) / 2 : B; s.Bh[1] = split ? B - (B + 1) / 2 : 0;
+    s.Bh[0] = B;
+    s.fp[0] = whole;
     s.wsh[0] = static_cast<char*>(r.ws); s.wsz[0] = r.ws_bytes;
     if (split) {
-        s.wsh[0] = static_cast<char*>(r.ws) + cond_region_bytes(p, B);
-        s.wsz[0] = fwd_workspace_core(p, s.Bh[0], H, W);
-        s.wsh[1] = s.wsh[0] + s.wsz[0];
-        s.wsz[1] = fwd_workspace_core(p, s.Bh[1], H, W);
-        if (hipEventCreateWithFlags(&s.ev_go, hipEventDisableTiming) != hipSuccess) return SINDDM_E_BADARG;
-        if (hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) != hipSuccess) {
-            (void)hipEventDestroy(s.ev_go);
-            return SINDDM_E_BADARG;
+        const ForwardPlan h0 = forward_plan(p, FWD_INFER, (B + 1) / 2, H, W, whole.ncu), h1 = forward_plan(p, FWD_INFER, B - (B + 1) / 2, H, W, whole.ncu);
+        // (the two halves carve their own cores behind the shared conditioning table: only if that really fits)
+        split = whole.cond_bytes() + h0.core_bytes + h1.core_bytes <= r.ws_bytes;
+        if (split) {
+            s.on = true;
+            s.Bh[0] = h0.B; s.Bh[1] = h1.B;
+            s.fp[0] = h0; s.fp[1] = h1;
+            s.wsh[0] = static_cast<char*>(r.ws) + whole.cond_bytes(); s.wsz[0] = h0.core_bytes;
+            s.wsh[1] = s.wsh[0] + s.wsz[0]; s.wsz[1] = h1.core_bytes;
+            if (hipEventCreateWithFlags(&s.ev_go, hipEventDisableTiming) != hipSuccess) return SINDDM_E_BADARG;
+            if (hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) != hipSuccess) {
+                (void)hipEventDestroy(s.ev_go);
+                return SINDDM_E_BADARG;
+            }
         }
     }
     s.hoff = (size_t)s.Bh[0] * CHANNELS * H * W;
@@ -1585,8 +1484,9 @@ static int chain_half_step(const ChainCtx& k, const ChainStepPlan& s, int h) {
     const size_t o = h ? k.sp.hoff : 0;
     hipStream_t st = h ? k.sx : k.st;
     ChainStep cs{};
+    cs.plan = &k.sp.fp[h];
     cs.cond_row = s.cond_row;
-    cs.x_tilde = r.x_tilde ? r.x_tilde + o : nullptr; cs.x_next = k.fuse_tail && !s.jump && !s.pull && !s.ms ? s.nxt + o : nullptr;
+    cs.x_tilde = r.x_tilde ? r.x_tilde + o : nullptr; cs.x_next = k.fp.fuse_tail && !s.jump && !s.pull && !s.ms ? s.nxt + o : nullptr;
     cs.tail = s.t;
     const int b0 = cs.tail.b0 = h ? k.sp.Bh[0] : 0;
     if (k.c.sseeds) cs.tail.sseeds = k.c.sseeds + b0;
@@ -1612,7 +1512,7 @@ static int chain_half_step(const ChainCtx& k, const ChainStepPlan& s, int h) {
         if (rc == 0) rc = layout_step_launch(io, cs.tail, lh);
     } else if (s.ms) {
         rc = ms_launch(io, cs.tail, s.q, r.solver_hist + o);   // (the half's own part of the history)
-    } else if (!k.fuse_tail) {
+    } else if (!k.fp.fuse_tail) {
         rc = rows_launch(io, cs.tail);
     }
     if (rc == 0 && k.c.tiled) rc = wrap_halo_launch(io.out, nullptr, Bn * CHANNELS, r.Hc, r.Wc, r.halo_y, r.halo_x, st);
@@ -1698,20 +1598,20 @@ static int sample_chain_impl(const ChainRun& r) {
     const int H = k.c.H, W = k.c.W;
     k.p = make_plan(r.dim);
     if (!k.p.ok) return SINDDM_E_BADSHAPE;
+    k.fp = forward_plan(k.p, FWD_INFER, r.B, H, W, cu_count());
     // per-sample maps (batch_check.h): the strides of step_tail.h; all 0 without the block, and nothing below differs then
     if (const int rc = batch_strides(&r.batch, r.edit_w, r.edit_c, r.keep_m, r.keep_x0, r.layout, H, W,
-                                     (H * W) % 4 == 0 && fwd_pitch(k.p, W) == W, &k.bs))
+                                     k.fp.rows_aligned, &k.bs))
         return rc;
     if (k.c.lay_g) {                                           // (the layout block is read only by a run that pulls)
         k.lay = layout_geom(r.Hc, r.Wc, r.halo_y, r.halo_x, r.layout_down, false, false);
         k.lay.sl = k.bs.sl;
         k.lay_gain = r.batch.layout_gain;
     }
-    if (r.ws_bytes < fwd_workspace_bytes(k.p, r.B, H, W)) return SINDDM_E_WORKSPACE;
+    if (r.ws_bytes < chain_workspace_bytes(k.fp, forward_plan(k.p, FWD_INFER, (r.B + 1) / 2, H, W, k.fp.ncu))) return SINDDM_E_WORKSPACE;
     k.st = static_cast<hipStream_t>(r.stream);
     k.sx = static_cast<hipStream_t>(r.aux_stream);
     k.cond_tab = static_cast<float*>(r.ws);
-    k.fuse_tail = (H * W) % 4 == 0 || fwd_pitch(k.p, W) != W;           // (padded rows: their own fused tail kernel)
     if (const int rc = chain_split(k)) return rc;
     float* result = r.x;
     const int rc = chain_enqueue(k, &result);
@@ -1985,7 +1885,28 @@ int sinddm_debug_infer_path(int dim, int B, int H, int W) {
 int sinddm_debug_head_path(int dim, int B, int H, int W) {
     NetPlan p = make_plan(dim);
     if (!p.ok || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
-    return head_applies(false, H, fwd_pitch(p, W)) ? 1 : 0;
+    return forward_plan(p, FWD_INFER, B, H, W, cu_count()).head ? 1 : 0;
+}
+
+int sinddm_debug_forward_plan(int dim_arg, int train, int B, int H, int W, int ncu, int64_t* out, int cap) {
+    NetPlan p = make_plan(dim_arg);
+    if (!p.ok || !out || cap < SINDDM_FWD_PLAN_INTS || B <= 0 || H <= 0 || W <= 0) return SINDDM_E_BADARG;
+    if (ncu <= 0) ncu = cu_count();
+    const ForwardPlan F = forward_plan(p, train ? FWD_TRAIN : FWD_INFER, B, H, W, ncu);
+    const int64_t head[SINDDM_FWD_PLAN_BLOCK0] = {
+        F.Wp, F.padded, F.Wt, F.HW, F.head, F.any_wh, F.fuse_tail, F.rows_aligned, F.last[0], F.last_gx[0], F.last[1], F.last_gx[1],
+        F.n_launches, F.conv_items, (int64_t)F.off_cond, (int64_t)F.off_amax, (int64_t)F.off_buf[0], (int64_t)F.off_buf[1],
+        (int64_t)F.off_buf[2], (int64_t)F.off_buf[3], (int64_t)F.off_xpad, (int64_t)F.core_bytes,
+        train ? 0 : (int64_t)chain_workspace_bytes(F, forward_plan(p, FWD_INFER, (B + 1) / 2, H, W, ncu)), F.ncu};
+    for (int i = 0; i < SINDDM_FWD_PLAN_BLOCK0; ++i) out[i] = head[i];
+    for (int l = 0; l < 4; ++l) {
+        const FwdBlock& f = F.blk[l];
+        const int64_t blk[SINDDM_FWD_PLAN_BLOCK_INTS] = {F.route[2 * l], F.route[2 * l + 1], f.wh_variant[0], f.wh_variant[1], f.amax_dw,
+                                                         f.amax_in[0], f.amax_out1, f.max_pass, f.amax_in[1], f.resid, f.bias_plain,
+                                                         f.dw, f.dw_pi, f.dw_po};
+        for (int i = 0; i < SINDDM_FWD_PLAN_BLOCK_INTS; ++i) out[SINDDM_FWD_PLAN_BLOCK0 + l * SINDDM_FWD_PLAN_BLOCK_INTS + i] = blk[i];
+    }
+    return 0;
 }
 
 int sinddm_debug_head_offsets(int dim, int64_t out[3]) {
