@@ -625,6 +625,28 @@ int sinddm_adam_ema_step(float* p, const float* g, float* m, float* v, float* em
                          float beta1, float beta2, float eps, float bc2_sqrt, float ema_decay,
                          float reserved, int mode, int64_t n, void* stream);
 
+/* Patch nearest-neighbour field: for every P x P patch of `query` the nearest P x P patch of `ref` (csrc/patch_nnf.h).
+ *   query  (B or 1, 3, Hq, Wq): q_per_sample != 0 -> one image per sample, 0 -> one image shared by the B samples
+ *   ref    (B or 1, 3, Hr, Wr): r_per_sample likewise
+ *   wrap_q / wrap_r  bit 0 = y wraps, bit 1 = x wraps.  An axis of length n has n - P + 1 patch positions without wrap and n
+ *          with it (the patch then reads modulo n): the grids are (hq, wq) and (hr, wr).
+ *   ref_ok (hr, wr) fp32, shared by the samples, or NULL: a reference POSITION is admissible iff its entry is != 0
+ *   dist / idx  (B, hq, wq) each; idx is the linear position y * wr + x in the reference grid
+ * With K = 3 P^2, patch element order (c, dy, dx) and K padded by zeros to a multiple of 4, every (query, reference) pair
+ * has the ranking value r = |b|^2 - 2 a.b evaluated as ONE fp32 fmaf chain: |b|^2 = fmaf(b_k, b_k, .) over k from 0, then
+ * r = fmaf(-2 a_k, b_k, .) over k starting from |b|^2 (the fp32 matrix pipe is such a chain, bit for bit).  r does not
+ * depend on which tile, wave or workgroup evaluates it.  The winner is the admissible position with the smallest r, ties
+ * to the smallest idx; dist is then recomputed for the winner as fmaf(a_k - b_k, a_k - b_k, .) over k from 0: an identical
+ * patch gives exactly 0.0.  Bit-reproducible run to run and independent of B.  A query with no admissible reference
+ * position at all gets idx = -1 and dist = +inf.
+ * SINDDM_E_BADARG (before any device work): a null query / ref / dist / idx / workspace, B < 1, P outside {3, 5, 7}, a
+ * workspace smaller than sinddm_patch_nnf_workspace_bytes; SINDDM_E_BADSHAPE: an axis shorter than P, a grid of 2^31
+ * positions or more.  sinddm_patch_nnf_workspace_bytes returns 0 for arguments the call would refuse. */
+size_t sinddm_patch_nnf_workspace_bytes(int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r);
+int sinddm_patch_nnf(const float* query, int q_per_sample, const float* ref, int r_per_sample, const float* ref_ok,
+                     float* dist, int32_t* idx, int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

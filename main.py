@@ -58,6 +58,10 @@ A batch of independent jobs: `--mask_path`, `--input_image` and `--layout_streng
 or more pairs.  With N > 1 values the batch size must be a multiple of N and sample b gets value b % N (so `--seeds` sweeps
 line up: `--sample_batch_size 8 --mask_path a.png b.png --seed_base 0` fills each hole four times); every sample is then
 conditioned on its own maps inside the one chain call per scale.  One value is the command line as it was.
+`evaluate` (no reference mode) measures what the samples copy: `--mode evaluate [--eval_patch {3,5,7}] [--eval_scale S]` draws a
+batch the way `--mode sample` does (`--seeds`, `--tile`, `--scale_mul`, `--sample_steps` ... apply), computes the patch
+nearest-neighbour field between the batch of scale S (default: the finest) and that scale's training image in both
+directions, prints fidelity, coherence, coverage (and seam under `--tile`) and writes `patch_report.json` to the results folder.
 The CLIP-guided modes (clip_content, clip_style_*, clip_roi; main.py:153-255) are not wired to the command line: CLIP
 itself is outside this build.  Their drivers exist (`MultiscaleTrainer.clip_sampling` / `clip_roi_sampling`, the guidance
 branch of `p_mean_variance`) and take any scorer with the reference's ClipExtractor interface.
@@ -173,6 +177,9 @@ def build_parser():
     p.add_argument("--layout_strength", type=float, default=1.0, nargs="+", action=_OneOrMore)
     p.add_argument("--layout_t_min", type=int, default=0)
     p.add_argument("--layout_scales", type=int, nargs=2, default=None)
+    # no reference flags: the patch nearest-neighbour report of `evaluate` (MultiscaleTrainer.evaluate)
+    p.add_argument("--eval_patch", type=int, choices=(3, 5, 7), default=7)
+    p.add_argument("--eval_scale", type=int, default=None, metavar="S")
     return p
 
 
@@ -232,6 +239,8 @@ def parse_args(argv=None):
         p.error("--layout_t_min must be >= 0")
     if args.layout_scales is not None and not 0 <= args.layout_scales[0] <= args.layout_scales[1]:
         p.error("--layout_scales A B needs 0 <= A <= B")
+    if args.eval_scale is not None and args.eval_scale < 0:
+        p.error("--eval_scale must be >= 0")
     return args
 
 
@@ -389,9 +398,20 @@ def main():
                             strength=job_values(args.layout_strength, args.sample_batch_size),
                             t_min=args.layout_t_min, scales=args.layout_scales, scale_mul=scale_mul,
                             custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
+    elif args.mode == 'evaluate':
+        if args.eval_scale is not None and args.eval_scale >= n_scales:
+            raise SystemExit(f"--eval_scale {args.eval_scale} is past the {n_scales} scales")
+        report = trainer.evaluate(batch_size=args.sample_batch_size, scale=args.eval_scale, patch=args.eval_patch,
+                                  scale_mul=scale_mul, custom_sample=True, image_name=args.image_name,
+                                  custom_t_list=sample_t_list, **seed_kw)
+        if rank == 0:
+            for name in ("fidelity", "coherence", "coverage", "seam"):
+                if name + "_mean" in report:
+                    print(f"{name}: {report[name + '_mean']:.6g}")
+            print("wrote " + os.path.join(results_folder, "patch_report.json"))
     else:
         raise NotImplementedError(
-            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint and paint2image are built for MI355X; "
+            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint, paint2image and evaluate are built for MI355X; "
             "the CLIP-guided modes of the reference need CLIP autograd and are out of scope (SURVEY.md section 8)")
     if args.gif is not None and frames and rank == 0:
         from sinddm_amd.functions import write_gif

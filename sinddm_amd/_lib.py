@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_mix", "sinddm_normal_fill_mix",
     "sinddm_l1_loss_weighted_fwd_bwd",
     "sinddm_debug_conv_wh", "sinddm_debug_conv_wh_scratch_bytes",
+    "sinddm_patch_nnf_workspace_bytes", "sinddm_patch_nnf",
 )
 
 
@@ -206,6 +207,8 @@ def load() -> C.CDLL:
         "sinddm_l1_loss_crop_fwd_bwd": (i, [p, p, p, p, i, i, i, i, i, f, p]),
         "sinddm_l1_loss_weighted_fwd_bwd": (i, [p, p, p, p, p, i, i, i, i, i, i, f, f, p]),
         "sinddm_adam_ema_step": (i, [p, p, p, p, p, f, f, f, f, f, f, f, i, i64, p]),
+        "sinddm_patch_nnf_workspace_bytes": (sz, [i, i, i, i, i, i, i, i]),
+        "sinddm_patch_nnf": (i, [p, i, p, i, p, p, p, i, i, i, i, i, i, i, i, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name):

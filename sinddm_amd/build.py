@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(HERE, "..", "include")
 LIB = os.path.join(HERE, "libsinddm_hip.so")
 STAMP = LIB + ".sha256"
-SOURCES = ["sinddm_fwd.hip", "sinddm_bwd.hip"]
+SOURCES = ["sinddm_fwd.hip", "sinddm_bwd.hip", "patch_nnf.hip"]
 # -amdgpu-spill-vgpr-to-agpr=0: conv_wino4.h owns the AGPRs a0..a239 by number (inline asm); a VGPR spill must never land there
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-amdgpu-spill-vgpr-to-agpr=0",
          "-fPIC", "-shared"]
@@ -77,7 +77,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         return LIB
     if os.path.exists(STAMP):
         os.remove(STAMP)
-    # the two translation units compile side by side (the backward one carries 96 specialised copies of the
+    # the translation units compile side by side (the backward one carries 96 specialised copies of the
     # weight-gradient loop: ~100 s on its own), then one link
     import tempfile
     cflags = [f for f in FLAGS if f != "-shared"]

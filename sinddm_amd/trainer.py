@@ -389,6 +389,32 @@ class MultiscaleTrainer(object):
                 save_image(one, str(single_dir / t_tag) + f'_out_b{b}.png')
         return per_scale
 
+    @torch.no_grad()
+    def evaluate(self, samples=None, batch_size=16, scale=None, patch=7, **sample_kw) -> dict:
+        """What the samples copy: the patch nearest-neighbour field (metrics.patch_report) between the batch of `scale`
+        (default: the finest) and that scale's training image -- fidelity, coherence and coverage per sample, and `seam`
+        when `ema_model.tile` wraps an axis.  Without `samples` (the list `sample_scales` returns) the batch is drawn here:
+        `sample_scales(save_images=False, batch_size=batch_size, **sample_kw)`; a stretched sample (`scale_mul`) is simply
+        compared at its own size.  A masked model (`train_mask`) is never scored against its hole.  Returns the report;
+        rank 0 also writes it to `patch_report.json` in the results folder."""
+        import json
+        from .metrics import patch_report
+        s = self.n_scales - 1 if scale is None else int(scale)
+        if not 0 <= s < self.n_scales:
+            raise ValueError(f'evaluate: scale {s} outside 0 ... {self.n_scales - 1}')
+        if samples is None:
+            samples = self.sample_scales(batch_size=batch_size, save_images=False, **sample_kw)
+        batch = samples[s] if isinstance(samples, (list, tuple)) else samples
+        image = self.data_list[s][0][0]
+        valid = None if self.train_mask_hard is None else self.train_mask_hard[s]
+        report = patch_report(batch.to(self.device, torch.float32).contiguous(), image.to(torch.float32).contiguous(),
+                              patch=patch, tile=tuple(self.ema_model.tile), valid=valid)
+        report['scale'] = s
+        if sdist.rank() == 0:
+            with open(str(self.results_folder / 'patch_report.json'), 'w') as f:
+                json.dump(report, f, indent=1)
+        return report
+
     def _local_batch_maps(self, batch_size) -> dict:
         """This rank's rows of the per-sample conditioning on `ema_model`, as {attribute: value to set for the call}: every
         keep / layout map with a leading batch dimension, `layout_gain`, `roi_bbs_batch` and `roi_target_patch_batch` must have
