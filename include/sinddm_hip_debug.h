@@ -70,7 +70,26 @@ int sinddm_debug_routes(int dim_arg, int train, int B, int H, int W, int out[16]
 #define SINDDM_FWD_PLAN_BLOCK0 24
 #define SINDDM_FWD_PLAN_BLOCK_INTS 14
 #define SINDDM_FWD_PLAN_INTS (SINDDM_FWD_PLAN_BLOCK0 + 4 * SINDDM_FWD_PLAN_BLOCK_INTS)
+/* With cap >= SINDDM_FWD_PLAN_INTS_EXT the hook also writes, behind the integers above (whose positions never move),
+ *   [SINDDM_FWD_PLAN_INTS + l] block l's conv1 on the C_in = 3 route: 0 = conv1 takes another route, 1 = conv3x3_c3_gelu_kernel
+ *        (VALU), 2 = conv3x3_c3_mfma_kernel (fp32 matrix cores: inference, C_out % 16 == 0, row pitch % 4 == 0, at least 11
+ *        64-pixel row segments per compute unit, rows that fill their segments to 85 % or more). */
+#define SINDDM_FWD_PLAN_INTS_EXT (SINDDM_FWD_PLAN_INTS + 4)
 int sinddm_debug_forward_plan(int dim_arg, int train, int B, int H, int W, int ncu, int64_t* out, int cap);
+
+/* ONE first conv of the network (C_in = 3, 3x3, zero padding 1, + bias + GELU) on caller tensors, for kernel-level tests:
+ *   out = gelu(conv2d(in, weights) + bias),  in (B, 3, H, W), weights plain [Cout][3][3][3], bias (Cout), out (B, Cout, H, W).
+ * variant: 0 = the kernel the library's inference plan takes for this shape, 1 = conv3x3_c3_gelu_kernel (VALU),
+ * 2 = conv3x3_c3_mfma_kernel (fp32 matrix cores).  ncu <= 0: the current device's compute units; any other count sizes
+ * variant 0's choice and variant 2's persistent grid for a device of that size -- the result must not depend on it.
+ * Wt = 0, or the true width of rows padded to W (W - 4 < Wt <= W): columns Wt .. W - 1 of `in` hold zeros and are written
+ * as zeros; amax_out or NULL: [B][8] floats zeroed by the caller, element [b][0] receives max |out[b]|.
+ * Returns SINDDM_E_BADARG / SINDDM_E_BADSHAPE before any device call for a null in / weights / bias / out, a variant outside
+ * 0..2, a size < 1, B > 65535, a plane of 2^28 floats or a sample's output of 2^31 floats or more, a Wt outside the rule above;
+ * under variant 2 also SINDDM_E_BADSHAPE for the shapes that kernel does not take (Cout % 16 != 0, W % 4 != 0, Cout > 320)
+ * and SINDDM_E_BADARG for an `out` that is not 16-byte aligned.  Nothing is written then. */
+int sinddm_debug_first_conv(int variant, int ncu, int B, int H, int W, int Wt, int Cout, const float* in, const float* weights,
+                            const float* bias, float* out, float* amax_out, void* stream);
 
 /* Which kernel generation the dim -> dim 3x3 convolutions of a launch of this shape take on the current device:
  * 4 = conv_wino4 (F(2x4,3x3), one wave per SIMD), 3 = conv_wino3 (F(2x4,3x3)), 2 = F(2x2,3x3) kernels, 0 = direct

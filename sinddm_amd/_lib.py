@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_mix", "sinddm_normal_fill_mix",
     "sinddm_l1_loss_weighted_fwd_bwd",
     "sinddm_debug_conv_wh", "sinddm_debug_conv_wh_scratch_bytes",
+    "sinddm_debug_first_conv",
     "sinddm_patch_nnf_workspace_bytes", "sinddm_patch_nnf",
 )
 
@@ -194,6 +195,7 @@ def load() -> C.CDLL:
         "sinddm_debug_wgrad_scratch_bytes": (sz, [i, i, i, i]),
         "sinddm_debug_conv_wh": (i, [i, i, i, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, sz, p]),
         "sinddm_debug_conv_wh_scratch_bytes": (sz, [i, i, i]),
+        "sinddm_debug_first_conv": (i, [i, i, i, i, i, i, i, p, p, p, p, p, p]),
         "sinddm_debug_head_offsets": (i, [i, C.POINTER(C.c_int64)]),
         "sinddm_debug_forward_plan": (i, [i, i, i, i, i, i, C.POINTER(C.c_int64), i]),
         "sinddm_debug_head": (i, [p, p, p, p, i, i, i, i, i, p]),

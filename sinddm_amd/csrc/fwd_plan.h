@@ -52,6 +52,8 @@ enum LastLaunch {
 struct FwdBlock {
     int wh_variant[2];     // conv i + 1 on CONV_WH: conv_wh_launch's variant, 1 = items of 80 output channels, 2 = of 160
                            // (inference, C_out % 160 == 0, a launch at conv_wr_pays' floor); 0 on every other route
+    int c3_variant;        // conv1 on CONV_C3: 1 = conv3x3_c3_gelu_kernel (VALU), 2 = conv3x3_c3_mfma_kernel (conv_c3m.h: inference,
+                           // C_out % 16 == 0, rows of whole quads, a launch at c3m_pays' floor); 0 on every other route
     int amax_dw;           // the depthwise launch publishes max |h| here
     int amax_in[2];        // conv i + 1 reads this slot
     int amax_out1;         // conv1 (conv_wh's epilogue or the C_in = 3 kernel) publishes max |g| here
@@ -169,6 +171,7 @@ ForwardPlan forward_plan(const NetPlan& P, FwdMode mode, int B, int H, int W, in
         const int variant = !train && conv_wr_pays(B, H, F.Wp, b.cout, ncu) ? 2 : 1;      // (both convs have C_out = b.cout)
         f.wh_variant[0] = wha ? variant : 0;
         f.wh_variant[1] = whb ? variant : 0;
+        f.c3_variant = r1 != CONV_C3 ? 0 : !train && c3m_pays(B, H, F.Wp, b.cout, ncu) ? 2 : 1;
         f.amax_dw = f.amax_in[0] = wha ? 2 * l : -1;
         f.amax_in[1] = whb ? 2 * l + 1 : -1;
         f.amax_out1 = whb && (wha || r1 == CONV_C3) ? 2 * l + 1 : -1;

@@ -3,6 +3,7 @@
 #include "conv_mfma.h"
 #include "conv_wino4.h"
 #include "conv_wh.h"
+#include "conv_c3m.h"
 #include "internal.h"
 #include "step_tail.h"
 #include "chain_run.h"
@@ -586,8 +587,20 @@ __global__ __launch_bounds__(256) void conv3x3_c3_gelu_kernel(const float* __res
     if (amax) amax_publish(mx, amax + (size_t)b * AMAX_STRIDE);
 }
 
+// One launch of it (block_forward and the debug hook).  Wt: the true width of rows padded to W, else 0.
+static int conv_c3_valu_launch(const float* in, const float* w, const float* bias, float* out, float* out_pre, int B, int H, int W,
+                               int Cout, int Wt, float* amax, hipStream_t st) {
+    const int nwg = ((H * W + 255) / 256) * B;
+    int split = 1;                                       // channel groups: aim at >= ~2048 workgroups
+    while (split < 8 && nwg * split < 2048 && Cout % (split * 2) == 0) split *= 2;
+    hipLaunchKernelGGL(conv3x3_c3_gelu_kernel, dim3((H * W + 255) / 256, B, split), dim3(256), 0, st, in, w, bias, out, out_pre, H, W,
+                       Cout, Cout / split, Wt > 0 ? Wt : W, amax);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
+
 // =====================================================================================
-// final 1x1 conv (half -> 3)                      reference SinDDM/models.py:130-132,151
+// final 1x1 conv (half -> 3)                     reference SinDDM/models.py:130-132,151
 // =====================================================================================
 // Padded workspace rows (inference, W % 4 != 0): the library keeps its own activations with a row pitch Wp = W rounded up
 // to 4 floats, pad columns zero, so that every scale runs the aligned kernels (16-byte accesses, no edge masks in the
@@ -967,15 +980,13 @@ int block_forward(const NetPlan& P, const ForwardPlan& F, int l, const float* pa
     int rc = dwconv_launch(cur, params + b.dw_w, params + b.dw_b, cond, cond_stride, nullptr, 0, hbuf, B, b.cin, H,
                            Wt > 0 ? Wt : W, st, f.dw_pi, f.dw_po, slot(f.amax_dw));
     if (rc) return rc;
-    if (k1 == CONV_C3) {
+    if (k1 == CONV_C3 && f.c3_variant == 2) {
+        // C_in = 3 on the fp32 matrix cores (inference: nothing saves the pre-activation)
+        if (upre) return SINDDM_E_BADARG;
+        rc = conv_c3m_launch(hbuf, params + b.c1_w, params + b.c1_b, gbuf, B, H, W, b.cout, Wt, slot(f.amax_out1), st);
+    } else if (k1 == CONV_C3) {
         // C_in = 3: dedicated VALU kernel straight from the PyTorch-layout weights
-        const int nwg = ((H * W + 255) / 256) * B;
-        int split = 1;                                       // channel groups: aim at >= ~2048 workgroups
-        while (split < 8 && nwg * split < 2048 && b.cout % (split * 2) == 0) split *= 2;
-        hipLaunchKernelGGL(conv3x3_c3_gelu_kernel, dim3((H * W + 255) / 256, B, split), dim3(256), 0, st, hbuf,
-                           params + b.c1_w, params + b.c1_b, gbuf, upre, H, W, b.cout, b.cout / split, Wt > 0 ? Wt : W,
-                           slot(f.amax_out1));
-        SINDDM_LAUNCH_CHECK();
+        rc = conv_c3_valu_launch(hbuf, params + b.c1_w, params + b.c1_b, gbuf, upre, B, H, W, b.cout, Wt, slot(f.amax_out1), st);
     } else {
         ConvArgs c1{};
         c1.in = hbuf; c1.out = gbuf; c1.out_pre = upre;
@@ -1462,6 +1473,9 @@ static int chain_split(ChainCtx& k) {
             s.on = true;
             s.Bh[0] = h0.B; s.Bh[1] = h1.B;
             s.fp[0] = h0; s.fp[1] = h1;
+            // (the first conv's kernel is the whole batch's: a half below c3m_pays' floor would take the VALU kernel and the
+            // chain would round differently with and without a second stream; both kernels are valid at any batch)
+            for (int l = 0; l < 4; ++l) s.fp[0].blk[l].c3_variant = s.fp[1].blk[l].c3_variant = whole.blk[l].c3_variant;
             s.wsh[0] = static_cast<char*>(r.ws) + whole.cond_bytes(); s.wsz[0] = h0.core_bytes;
             s.wsh[1] = s.wsh[0] + s.wsz[0]; s.wsz[1] = h1.core_bytes;
             if (hipEventCreateWithFlags(&s.ev_go, hipEventDisableTiming) != hipSuccess) return SINDDM_E_BADARG;
@@ -1905,8 +1919,26 @@ int sinddm_debug_forward_plan(int dim_arg, int train, int B, int H, int W, int n
                                                          f.amax_in[0], f.amax_out1, f.max_pass, f.amax_in[1], f.resid, f.bias_plain,
                                                          f.dw, f.dw_pi, f.dw_po};
         for (int i = 0; i < SINDDM_FWD_PLAN_BLOCK_INTS; ++i) out[SINDDM_FWD_PLAN_BLOCK0 + l * SINDDM_FWD_PLAN_BLOCK_INTS + i] = blk[i];
+        if (cap >= SINDDM_FWD_PLAN_INTS_EXT) out[SINDDM_FWD_PLAN_INTS + l] = f.c3_variant;     // (a caller with room for them)
     }
     return 0;
+}
+
+int sinddm_debug_first_conv(int variant, int ncu, int B, int H, int W, int Wt, int Cout, const float* in, const float* weights,
+                            const float* bias, float* out, float* amax_out, void* stream) {
+    if (!in || !weights || !bias || !out || variant < 0 || variant > 2 || B <= 0 || H <= 0 || W <= 0 || Cout <= 0)
+        return SINDDM_E_BADARG;
+    if (B > 65535 || (long long)H * W >= (1LL << 28) || (long long)Cout * H * W >= (1LL << 31)) return SINDDM_E_BADSHAPE;
+    if (Wt != 0 && (Wt > W || Wt <= W - 4)) return SINDDM_E_BADSHAPE;
+    if (variant == 2 && !c3m_applies(B, H, W, Cout)) return SINDDM_E_BADSHAPE;
+    if (ncu <= 0) ncu = cu_count();
+    if (variant == 0) variant = c3m_pays(B, H, W, Cout, ncu) ? 2 : 1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (variant == 2) {
+        if ((uintptr_t)out % 16 != 0) return SINDDM_E_BADARG;              // 16-byte stores
+        return conv_c3m_launch(in, weights, bias, out, B, H, W, Cout, Wt, amax_out, st, ncu);
+    }
+    return conv_c3_valu_launch(in, weights, bias, out, nullptr, B, H, W, Cout, Wt, amax_out, st);
 }
 
 int sinddm_debug_head_offsets(int dim, int64_t out[3]) {
