@@ -108,6 +108,24 @@ int sinddm_q_sample_wrap(const float* x0, const float* x_orig, const float* nois
                          const int64_t* t_dev, int t_host, int B, int C, int H, int W, int halo_y, int halo_x,
                          void* stream);
 
+/* sinddm_q_sample read through one window per sample -- crop TRAINING (csrc/crop_train.h).  x0 / x_orig are
+ * the full (B,C,H,W) tensors of sinddm_q_sample; noise and out are (B,C,h,w); win is a device int32 (B,2) table of window
+ * origins (y0, x0), 0 <= y0 <= H - h and 0 <= x0 <= W - w (the caller's contract).  out[b,c,y,x] is the value sinddm_q_sample
+ * gives pixel (y0_b + y, x0_b + x) of sample b when its noise there is noise[b,c,y,x], bit for bit (the rounding is that of
+ * the kernel sinddm_q_sample launches for the full-size x0 / x_orig).  One pass; noise and out move as 16-byte accesses when
+ * w % 4 == 0 and both are 16-byte aligned, the gathered source rows dword by dword: no alignment of x0 is assumed.
+ * h == H and w == W is sinddm_q_sample itself (the table is not read).
+ * An origin outside its range cannot fault: the sources are read through buffer resources of exactly one sample's C*H*W
+ * floats.  The call still returns 0, and every element of out is then what the formula gives for a source that is either
+ * 0.0 (the offset left the sample's extent) or some other pixel of the same sample (it did not): defined, and useless.
+ * x_orig / gamma_row / t_dev / t_host as for sinddm_q_sample.
+ * SINDDM_E_BADARG: a null x0 / noise / out / table / win, x_orig without gamma_row, non-positive sizes, h > H or w > W,
+ * C*H*W >= 2^29. */
+int sinddm_q_sample_crop(const float* x0, const float* x_orig, const float* noise, float* out,
+                         const float* tab_sqrt_ac, const float* tab_sqrt_1m_ac, const float* gamma_row,
+                         const int64_t* t_dev, int t_host, const int32_t* win, int B, int C, int H, int W, int h, int w,
+                         void* stream);
+
 /* Per-step scalars of one reverse diffusion step (all samples share t, models.py:481,541). */
 typedef struct sinddm_step_coefs {
     int mode;            /* 0: s==0 or !reblurring (DDPM posterior, models.py:322-330)
@@ -616,6 +634,22 @@ int sinddm_l1_loss_crop_fwd_bwd(const float* noise, const float* eps_ext, float*
 int sinddm_l1_loss_weighted_fwd_bwd(const float* noise, const float* eps_ext, const float* weight, float* loss_out,
                                     float* grad_out_ext, int B, int C, int H, int W, int halo_y, int halo_x, float inv_norm,
                                     float grad_scale, void* stream);
+
+/* sinddm_l1_loss_weighted_fwd_bwd on one rectangle per sample -- crop training (csrc/crop_train.h).  noise, eps
+ * and grad_out are the window-size (B,C,h,w) tensors; rect is a device int32 (B,4) table (y_lo, y_hi, x_lo, x_hi), half open,
+ * in window coordinates; a rectangle may be empty.  weight is NULL (w = 1; win, Hm, Wm are then ignored) or
+ * the full-image (Hm,Wm) fp32 map, finite and >= 0, read at (y0_b + y, x0_b + x) with win the (B,2) origin table of
+ * sinddm_q_sample_crop (the address is clamped into the map).  inv_norm comes from the caller: 1 / (C * sum over samples
+ * and rectangles of w).
+ * loss_out[0] += inv_norm * sum over the rectangles of w * |noise - eps| (caller zeroes loss_out; a second call adds),
+ * summed as sinddm_l1_loss_weighted_fwd_bwd sums it; if grad_out != NULL it is written everywhere:
+ * (-sign(noise - eps) * inv_norm * grad_scale) * w inside a rectangle, exactly 0 outside it and where w == 0.  noise and eps
+ * are not loaded outside the rectangles, and an element with w == 0 is skipped: a NaN or an Inf there changes nothing.
+ * SINDDM_E_BADARG: a null noise / eps / rect / loss_out, non-positive sizes, h or w above 2^30, an element count beyond int64, an inv_norm that is not finite and positive; under a weight: a null win, a map
+ * smaller than the window. */
+int sinddm_l1_loss_rect_fwd_bwd(const float* noise, const float* eps, const float* weight, const int32_t* win,
+                                const int32_t* rect, float* loss_out, float* grad_out, int B, int C, int h, int w, int Hm,
+                                int Wm, float inv_norm, float grad_scale, void* stream);
 
 /* Fused optimizer / EMA over flat buffers of n floats.  mode bits: 1 = Adam update of p from g
  * (torch.optim.Adam defaults, reference trainer.py:134,208; step_size = lr/(1-beta1^k),

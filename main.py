@@ -29,6 +29,12 @@ that (a scale left without a valid pixel is an error), so give one value per sca
 files on disk stay as they are: their down-scaling smears hole content a few pixels outward, which is what N is for.  The
 intended pairing is `--mode train --train_mask hole.png`, then `--mode inpaint --mask_path hole.png`.  Like `--train_tile`
 the flags change the training step only (the other modes accept and ignore them) and are not stored in checkpoints.
+`--train_crop H W` (no reference flag) TRAINS on random windows: at every scale larger than H x W each sample of a batch
+sees its own window of at most H x W pixels, so a step costs what the window costs, not what the image costs.
+`--train_crop_margin N` (default 0) switches the loss off within N pixels of every window side that is not an image border;
+with N = 16, the network's receptive radius, a cropped step is provably a masked full-image step, and the window origins are
+drawn so that border pixels are supervised as often as interior ones.  Used with `--mode train` only, not stored in
+checkpoints, and not together with `--train_tile`.
 `inpaint` and `outpaint` (no reference modes) keep some pixels exactly and generate the rest to fit, by replacing the
 known region after every reverse step inside the step kernels: `--mode inpaint --mask_path FILE [--soft_mask]` fills the
 black part of the mask (white = keep the training image's pixel; the file is brought to the finest scale's size);
@@ -148,6 +154,9 @@ def build_parser():
     # the training half of --tile (MultiScaleGaussianDiffusion.train_tile): p_losses wraps the named axes around
     p.add_argument("--train_tile", choices=("none", "x", "y", "xy"), default="none")
     # the training half of `inpaint` (MultiScaleGaussianDiffusion.train_weights): the loss ignores the black part of the mask
+    # crop training (MultiScaleGaussianDiffusion.train_crop / train_crop_margin): random windows per sample
+    p.add_argument("--train_crop", type=int, nargs=2, default=None, metavar=("H", "W"))
+    p.add_argument("--train_crop_margin", type=int, default=0, metavar="N")
     p.add_argument("--train_mask", type=str, default=None, metavar="FILE")
     p.add_argument("--train_mask_grow", type=int, nargs="+", default=[0], metavar="N")
     p.add_argument("--train_mask_fill", choices=("mean", "image"), default="mean")
@@ -223,6 +232,12 @@ def parse_args(argv=None):
         p.error("--sample_steps must be >= 1")
     if min(args.train_mask_grow) < 0:
         p.error("--train_mask_grow must be >= 0")
+    if args.train_crop is not None and min(args.train_crop) < 1:
+        p.error("--train_crop H W must be >= 1")
+    if args.train_crop_margin < 0:
+        p.error("--train_crop_margin must be >= 0")
+    if args.train_crop is not None and args.train_tile != "none":
+        p.error("--train_crop does not go together with --train_tile: windows that wrap around the border are not built")
     if args.eta < 0.0:
         p.error("--eta must be >= 0")
     if not 1 <= args.layout_down <= 64:
@@ -303,6 +318,9 @@ def main():
                                  .astype(np.float32))
         mask_kw = dict(train_mask=valid, train_mask_fill=args.train_mask_fill,
                        train_mask_grow=args.train_mask_grow[0] if len(args.train_mask_grow) == 1 else list(args.train_mask_grow))
+
+    if args.train_crop is not None and args.mode == 'train':               # (likewise: only training crops)
+        mask_kw.update(train_crop=tuple(args.train_crop), train_crop_margin=args.train_crop_margin)
 
     trainer = MultiscaleTrainer(
         ms_diffusion, folder=args.dataset_folder, n_scales=n_scales, scale_factor=scale_factor, image_sizes=sizes,

@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "sinddm_debug_conv_wh", "sinddm_debug_conv_wh_scratch_bytes",
     "sinddm_debug_first_conv",
     "sinddm_patch_nnf_workspace_bytes", "sinddm_patch_nnf",
+    "sinddm_q_sample_crop", "sinddm_l1_loss_rect_fwd_bwd",
 )
 
 
@@ -208,6 +209,8 @@ def load() -> C.CDLL:
         "sinddm_l1_loss_fwd_bwd": (i, [p, p, p, p, i64, f, p]),
         "sinddm_l1_loss_crop_fwd_bwd": (i, [p, p, p, p, i, i, i, i, i, f, p]),
         "sinddm_l1_loss_weighted_fwd_bwd": (i, [p, p, p, p, p, i, i, i, i, i, i, f, f, p]),
+        "sinddm_q_sample_crop": (i, [p, p, p, p, p, p, p, p, i, p, i, i, i, i, i, i, p]),
+        "sinddm_l1_loss_rect_fwd_bwd": (i, [p, p, p, p, p, p, p, i, i, i, i, i, i, f, f, p]),
         "sinddm_adam_ema_step": (i, [p, p, p, p, p, f, f, f, f, f, f, f, i, i64, p]),
         "sinddm_patch_nnf_workspace_bytes": (sz, [i, i, i, i, i, i, i, i]),
         "sinddm_patch_nnf": (i, [p, i, p, i, p, p, p, i, i, i, i, i, i, i, i, p, sz, p]),

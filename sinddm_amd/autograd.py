@@ -70,9 +70,12 @@ def net_forward_train(net, x, t, scale):
     return _NetTrainFn.apply(x, anchor, net, t, scale)
 
 
-def l1_entry(halo, weighted: bool) -> str:
-    """The library entry of the fused L1 loss: the weighted kernel under a map, else the cropping one under a halo, else the
-    plain mean.  The ONE owner of the rule: `_L1Fn` launches by it, `train_step.TrainStep` reports it."""
+def l1_entry(halo, weighted: bool, rect: bool = False) -> str:
+    """The library entry of the fused L1 loss: the rectangle kernel under per-sample rectangles (crop training), else the
+    weighted kernel under a map, else the cropping one under a halo, else the plain mean.  The ONE owner of the rule: `_L1Fn`
+    launches by it, `train_step.TrainStep` reports it."""
+    if rect:
+        return "sinddm_l1_loss_rect_fwd_bwd"
     if weighted:
         return "sinddm_l1_loss_weighted_fwd_bwd"
     return "sinddm_l1_loss_crop_fwd_bwd" if halo[0] or halo[1] else "sinddm_l1_loss_fwd_bwd"
@@ -120,10 +123,55 @@ class _L1Fn(torch.autograd.Function):
         return None, g * grad_loss, None, None, None
 
 
-def l1_loss(noise, eps, halo=(0, 0), weight=None, inv_norm=None):
+class _L1RectFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, noise, eps, weight, inv_norm, windows, rects):
+        lib = _lib.load()
+        name = l1_entry((0, 0), weight is not None, True)
+        noise = noise.contiguous()
+        eps = eps.contiguous()
+        if noise.dim() != 4 or noise.shape != eps.shape:
+            raise _lib.SinddmError(f"l1_loss: noise {tuple(noise.shape)} and eps {tuple(eps.shape)} must be one (B,C,h,w) shape "
+                                   f"under rectangles")
+        B, Cc, h, w = (int(v) for v in noise.shape)
+        for tab, cols, what in ((rects, 4, "rects"), (windows, 2, "windows")):
+            if tab is None and what == "windows" and weight is None:
+                continue
+            if tab is None or tuple(tab.shape) != (B, cols) or tab.dtype != torch.int32 or tab.device != eps.device:
+                raise _lib.SinddmError(f"l1_loss: {what} must be an int32 {(B, cols)} table on {eps.device}")
+        Hm = Wm = 0
+        if weight is not None:
+            if weight.dim() != 2 or weight.dtype != torch.float32 or weight.device != eps.device or weight.shape[0] < h \
+                    or weight.shape[1] < w:
+                raise _lib.SinddmError(f"l1_loss: the weight map must be an fp32 (H,W) >= {(h, w)} tensor on {eps.device}, got "
+                                       f"{tuple(weight.shape)} {weight.dtype} on {weight.device}")
+            weight = weight.contiguous()
+            Hm, Wm = int(weight.shape[0]), int(weight.shape[1])
+        loss = torch.zeros((), dtype=torch.float32, device=eps.device)
+        g = torch.empty_like(eps)                          # the kernel writes the zeros outside the rectangles itself
+        _lib.check(getattr(lib, name)(_lib.ptr(noise), _lib.ptr(eps), _lib.ptr(weight),
+                                      _lib.ptr(windows.contiguous()) if windows is not None else None,
+                                      _lib.ptr(rects.contiguous()), _lib.ptr(loss), _lib.ptr(g), B, Cc, h, w, Hm, Wm,
+                                      float(inv_norm), 1.0, _lib.stream_ptr(eps.device)), name)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (g,) = ctx.saved_tensors
+        return None, g * grad_loss, None, None, None, None
+
+
+def l1_loss(noise, eps, halo=(0, 0), weight=None, inv_norm=None, windows=None, rects=None):
     """mean(|noise - eps|)  (reference models.py:594) -- and the two losses of the training options, one fused kernel each:
     with a `halo` = (halo_y, halo_x), `eps` is the network's output on the image extended by its wrapped halo and the mean is
     taken over its centre (tileable training); with a `weight` -- the (H,W) fp32 map w >= 0 shared by samples and channels --
     the loss is sum(w |noise - centre(eps)|) * inv_norm, `inv_norm` = 1 / (B C sum w) from the caller, and where w == 0 nothing
-    is read (masked training)."""
+    is read (masked training).  With `rects` -- an int32 (B,4) device table (y_lo, y_hi, x_lo, x_hi) -- noise and eps are
+    window-size (B,C,h,w) tensors, the loss is inv_norm * the sum over every sample's rectangle, and `weight`, if any, is the
+    FULL-image map read at the int32 (B,2) origins `windows` (crop training; no halo)."""
+    if rects is not None:
+        if halo[0] or halo[1]:
+            raise _lib.SinddmError("l1_loss: rectangles and a halo do not go together")
+        return _L1RectFn.apply(noise, eps, weight, inv_norm, windows, rects)
     return _L1Fn.apply(noise, eps, weight, inv_norm, halo)

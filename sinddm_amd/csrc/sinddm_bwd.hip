@@ -919,6 +919,11 @@ __global__ __launch_bounds__(L1W_THREADS) void l1_loss_weighted_kernel(const flo
         atomicAdd(loss, (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) * inv_norm);
 }
 
+// crop training: the weighted loss on per-sample rectangles (crop_train.h), behind l1_grad_elem and the L1W_* constants
+#define SINDDM_CROP_TRAIN_LOSS
+#include "crop_train.h"
+#undef SINDDM_CROP_TRAIN_LOSS
+
 __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v,
                                                        float* __restrict__ ema, float step_size, float b1, float b2,
@@ -1314,6 +1319,13 @@ int sinddm_l1_loss_weighted_fwd_bwd(const float* noise, const float* eps_ext, co
                        loss_out, grad_out_ext, n_ext, H, W, halo_y, halo_x, inv_norm, grad_scale);
     SINDDM_LAUNCH_CHECK();
     return 0;
+}
+
+int sinddm_l1_loss_rect_fwd_bwd(const float* noise, const float* eps, const float* weight, const int32_t* win,
+                                const int32_t* rect, float* loss_out, float* grad_out, int B, int C, int h, int w, int Hm, int Wm,
+                                float inv_norm, float grad_scale, void* stream) {
+    return l1_loss_rect_launch(noise, eps, weight, win, rect, loss_out, grad_out, B, C, h, w, Hm, Wm, inv_norm, grad_scale,
+                               static_cast<hipStream_t>(stream));
 }
 
 int sinddm_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, float step_size, float beta1,

@@ -1220,6 +1220,15 @@ static int q_sample_route(int B, long long n, bool al) {
     return (long long)B * (n / 4) >= 4LL * 1024 * 2048 ? Q_ROUND_QUAD_UN4 : Q_ROUND_QUAD;   // >= 8 workgroups of 1024 quads per CU
 }
 
+}  // extern "C"
+// crop training: sinddm_q_sample through a per-sample window (crop_train.h), behind q_sample_elem and q_sample_route
+namespace sinddm {
+#define SINDDM_CROP_TRAIN_Q
+#include "crop_train.h"
+#undef SINDDM_CROP_TRAIN_Q
+}  // namespace sinddm
+extern "C" {
+
 int sinddm_q_sample(const float* x0, const float* x_orig, const float* noise, float* out, const float* tab_sqrt_ac,
                     const float* tab_sqrt_1m_ac, const float* gamma_row, const int64_t* t_dev, int t_host, int B,
                     int64_t n, void* stream) {
@@ -1274,6 +1283,17 @@ int sinddm_q_sample_wrap(const float* x0, const float* x_orig, const float* nois
                            tab_sqrt_1m_ac, gamma_row, td, t_host, nq, C, H, W, halo_y, halo_x, round);
     SINDDM_LAUNCH_CHECK();
     return 0;
+}
+
+int sinddm_q_sample_crop(const float* x0, const float* x_orig, const float* noise, float* out, const float* tab_sqrt_ac,
+                         const float* tab_sqrt_1m_ac, const float* gamma_row, const int64_t* t_dev, int t_host,
+                         const int32_t* win, int B, int C, int H, int W, int h, int w, void* stream) {
+    if (h == H && w == W && win)       // the whole image: sinddm_q_sample itself (it validates the rest; the origins are 0 by contract)
+        return sinddm_q_sample(x0, x_orig, noise, out, tab_sqrt_ac, tab_sqrt_1m_ac, gamma_row, t_dev, t_host, B,
+                               (C > 0 && H > 0 && W > 0) ? (int64_t)C * H * W : 0, stream);
+    return q_sample_crop_launch(x0, x_orig, noise, out, tab_sqrt_ac, tab_sqrt_1m_ac, gamma_row,
+                                reinterpret_cast<const long long*>(t_dev), t_host, win, B, C, H, W, h, w,
+                                static_cast<hipStream_t>(stream));
 }
 
 // the launch behind sinddm_reverse_step / _edit / _keep (each validates its own arguments): B samples of chw elements,

@@ -239,6 +239,67 @@ def fill_train_holes(img: torch.Tensor, hard_valid: torch.Tensor, fill: str = "m
     return torch.where(v, img, mean.to(img.dtype).expand_as(img))
 
 
+# ---- helpers of crop training (MultiScaleGaussianDiffusion.train_crop; no reference counterpart) ----------
+def crop_window(size, crop) -> Tuple[int, int]:
+    """The window (h, w) = (min(ch, H), min(cw, W)) of a scale of `size` = (H, W) under `crop` = (ch, cw)."""
+    return min(int(crop[0]), int(size[0])), min(int(crop[1]), int(size[1]))
+
+
+def crop_windows(gen, B: int, size, crop, margin: int) -> torch.Tensor:
+    """The clamped draw: a CPU int64 (B, 2) table of window origins (y0, x0).  Per cropped axis (window h < size H), with
+    L = h - 2 margin: o' uniform over the integers -(L-1) .. H - h + (L-1) from the torch.Generator `gen`, y0 = clamp(o', 0,
+    H - h); an axis the window spans gets 0.  Every pixel of the axis then lies in the valid range (`crop_rects`) of at least
+    L and at most 3 L of the H - h + 2 L - 1 draws, where a uniform y0 would leave a border pixel to a single one.
+    ValueError: L < 1 on a cropped axis."""
+    cols = []
+    for n, k in zip(size, crop_window(size, crop)):
+        n = int(n)
+        if k == n:
+            cols.append(torch.zeros(int(B), dtype=torch.int64))
+            continue
+        L = k - 2 * int(margin)
+        if L < 1:
+            raise ValueError(f"crop_windows: a window of {k} leaves nothing inside a margin of {margin}")
+        o = torch.randint(-(L - 1), n - k + (L - 1) + 1, (int(B),), generator=gen, dtype=torch.int64)
+        cols.append(o.clamp_(0, n - k))
+    return torch.stack(cols, dim=1)
+
+
+def crop_rects(windows, size, crop, margin: int) -> torch.Tensor:
+    """The valid rectangles of `windows` ((B, 2) origins), in window coordinates: a CPU int64 (B, 4) table (y_lo, y_hi, x_lo,
+    x_hi), half open.  A side of a window that lies on the image border is closed and keeps its pixels; every other side is
+    open and loses `margin` rows or columns (the network's zero padding lies there)."""
+    win = torch.as_tensor(windows).detach().to("cpu", torch.int64).reshape(-1, 2)
+    m, cols = int(margin), []
+    for axis, (n, k) in enumerate(zip(size, crop_window(size, crop))):
+        o = win[:, axis]
+        cols += [torch.where(o == 0, 0, m), torch.where(o == int(n) - k, k, k - m)]
+    return torch.stack(cols, dim=1)
+
+
+def summed_area_table(w: torch.Tensor) -> torch.Tensor:
+    """The float64 (H + 1, W + 1) summed-area table of an (H, W) map, on the CPU: sat[y, x] = sum of w[:y, :x]."""
+    w64 = torch.as_tensor(w).detach().to("cpu", torch.float64)
+    sat = torch.zeros(w64.shape[0] + 1, w64.shape[1] + 1, dtype=torch.float64)
+    sat[1:, 1:] = w64.cumsum(0).cumsum(1)
+    return sat
+
+
+def crop_norm(windows, rects, sat=None) -> float:
+    """sum over the samples of the total weight of their valid rectangles -- what a cropped step divides by, times C.
+    Without a map (`sat` None) it is area arithmetic; with one, `sat` is `summed_area_table(map)` and every sample costs four
+    look-ups at the full-image corners of its rectangle.  Host integers and float64: no device work."""
+    win = torch.as_tensor(windows).detach().to("cpu", torch.int64).reshape(-1, 2)
+    r = torch.as_tensor(rects).detach().to("cpu", torch.int64).reshape(-1, 4)
+    hh, ww = (r[:, 1] - r[:, 0]).clamp_(min=0), (r[:, 3] - r[:, 2]).clamp_(min=0)
+    if sat is None:
+        return float(int((hh * ww).sum()))
+    y0, x0 = win[:, 0] + r[:, 0], win[:, 1] + r[:, 2]
+    y1, x1 = y0 + hh, x0 + ww
+    tot = sat[y1, x1] - sat[y0, x1] - sat[y1, x0] + sat[y0, x0]
+    return float(torch.where((hh * ww) > 0, tot, torch.zeros_like(tot)).sum())
+
+
 def outpaint_offset(canvas, image, anchor=(0.5, 0.5)) -> Tuple[int, int]:
     """Top-left corner (y, x) of an (h, w) image placed on an (H, W) canvas: int(anchor * (canvas - image)) per axis;
     anchor (0, 0) = top left, (0.5, 0.5) = centred, (1, 1) = bottom right."""

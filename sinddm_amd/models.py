@@ -7,7 +7,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
   SinDDMNet.forward          -> sinddm_net_forward        (models.py:134-151)
   q_sample / p_losses mix    -> sinddm_q_sample           (models.py:570-590)
   p_losses' options          -> sinddm_q_sample_wrap, sinddm_l1_loss_crop_fwd_bwd / _weighted_fwd_bwd   (`train_tile`,
-                                `train_weights`; no reference line: one plan per step, train_step.TrainStep)
+                                `train_weights`; no reference line: one plan per step, train_step.TrainStep);
+                                sinddm_q_sample_crop, sinddm_l1_loss_rect_fwd_bwd   (`train_crop`: a window per sample)
   p_sample tail              -> sinddm_reverse_step       (models.py:306-352,433-459)
   inter-scale upsample       -> sinddm_upsample_bilinear  (models.py:567)
   known pixels (`keep_maps`) -> sinddm_sample_chain_keep / sinddm_reverse_step_keep   (no reference line: RePaint-style
@@ -40,7 +41,7 @@ from torch import nn
 
 from . import _lib
 from .autograd import l1_loss
-from .functions import cosine_beta_schedule, default, exists, extract, noise_like
+from .functions import cosine_beta_schedule, crop_windows, default, exists, extract, noise_like
 from .sampler import RunPlan, pack_steps, refuse
 from .synth import net_param_shapes
 from .train_step import TrainStep
@@ -680,6 +681,19 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # cached per scale and map object: {s: (map, float64 sum)}, a plain attribute).  Not stored in checkpoints.
         self.train_weights = None
         self._train_weight_norm = {}
+        # crop training (no reference counterpart): None, or (ch, cw) -- at every scale larger than that, each
+        # sample of a p_losses batch sees its own (min(ch,H), min(cw,W)) window of x_start / x_orig, the network runs on the
+        # windows, and the loss is taken on each window minus `train_crop_margin` rows / columns along every side that is not
+        # an image border.  With a margin >= SINDDM_TILE_HALO the step equals full-image masked steps (the statement of
+        # DESIGN.md 4).  The origins: p_losses' `windows` argument, else `crop_fn(crop_step, s, B) -> (B,2)` (the trainer sets
+        # `crop_step` to its step), else the clamped draw of functions.crop_windows from a private CPU generator seeded
+        # torch.initial_seed() + rank on first use.  Not together with `train_tile`; not stored in checkpoints.
+        self.train_crop = None
+        self.train_crop_margin = 0
+        self.crop_fn = None
+        self.crop_step = 0
+        self._crop_gen = None
+        self._train_crop_sat = {}
         # known-region conditioning (inpainting / outpainting): None or {s: (mask (H,W), x0 (3,H,W))}, fp32, on the sample's
         # device.  At a scale with an entry every reverse step overwrites the pixels whose mask is 1 with the
         # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
@@ -1525,14 +1539,30 @@ class MultiScaleGaussianDiffusion(nn.Module):
         img = self.upsample(img, image_size)
         return self.p_sample_via_scale_loop(batch_size, img, s, custom_t=custom_t)
 
-    def _q_sample_impl(self, x0, t_dev, t_host, noise, x_orig=None, gamma_row=None, halo=(0, 0)):
+    def _q_sample_impl(self, x0, t_dev, t_host, noise, x_orig=None, gamma_row=None, halo=(0, 0), crop=None, windows=None):
         """x_t of q_sample / the gamma-mixed x_noisy of p_losses (sinddm_q_sample); with a `halo` = (hy, hx) the same, written
-        extended by its wrapped halo in one pass (sinddm_q_sample_wrap): (B,C,H + 2 hy,W + 2 hx)."""
+        extended by its wrapped halo in one pass (sinddm_q_sample_wrap): (B,C,H + 2 hy,W + 2 hx); with a `crop` = (h, w) and
+        the int32 (B,2) device table `windows`, read through one window per sample (sinddm_q_sample_crop): `noise` and the
+        result are (B,C,h,w)."""
         lib = _lib.load()
         x0 = x0.contiguous()
         noise = noise.contiguous()
         if t_dev is not None:
             t_dev = t_dev.to(device=x0.device, dtype=torch.int64).contiguous()
+        if crop is not None:
+            B, Cc, H, W = x0.shape
+            h, w = crop
+            if tuple(noise.shape) != (B, Cc, h, w):
+                raise _lib.SinddmError(f"q_sample: noise {tuple(noise.shape)} is not the window batch {(B, Cc, h, w)}")
+            out = torch.empty_like(noise)
+            _lib.check(lib.sinddm_q_sample_crop(_lib.ptr(x0), _lib.ptr(x_orig.contiguous()) if x_orig is not None else None,
+                                                _lib.ptr(noise), _lib.ptr(out), _lib.ptr(self.sqrt_alphas_cumprod),
+                                                _lib.ptr(self.sqrt_one_minus_alphas_cumprod),
+                                                _lib.ptr(gamma_row) if gamma_row is not None else None,
+                                                _lib.ptr(t_dev) if t_dev is not None else None, int(t_host),
+                                                _lib.ptr(windows), B, Cc, H, W, h, w, _lib.stream_ptr(x0.device)),
+                       "sinddm_q_sample_crop")
+            return out
         hy, hx = halo
         if hy or hx:
             B, Cc, H, W = x0.shape
@@ -1559,21 +1589,65 @@ class MultiScaleGaussianDiffusion(nn.Module):
         noise = default(noise, lambda: torch.randn_like(x_start))
         return self._q_sample_impl(x_start, t, 0, noise)
 
-    def p_losses(self, x_start, t, s, noise=None, x_orig=None):            # models.py:578-611
+    def _draw_windows(self, s, shape):
+        """The (B,2) window origins of a cropped step at scale s: `crop_fn`, else the clamped draw (functions.crop_windows) from
+        the private generator -- a host draw, no device sync; under data parallelism every rank draws its own."""
+        B, _, H, W = shape
+        if self.crop_fn is not None:
+            return self.crop_fn(self.crop_step, int(s), int(B))
+        if self._crop_gen is None:
+            from . import dist as sdist
+            self._crop_gen = torch.Generator()
+            self._crop_gen.manual_seed(sdist.seed_for_rank(torch.initial_seed() % (2 ** 62)))
+        return crop_windows(self._crop_gen, B, (H, W), self.train_crop, self.train_crop_margin)
+
+    def p_losses(self, x_start, t, s, noise=None, x_orig=None, windows=None):   # models.py:578-611
         """The loss of one training step, as `train_step.TrainStep` describes it (every check runs there, before any launch).
         With `train_tile` (no reference line: padding_mode='circular' on the reference's nn.Conv2d's while it trains) x_noisy is
         written extended by its wrapped halo, the zero-padded training forward runs on the extended image and the loss is
         taken on the centre: the gradient handed back is 0 on the halo, and every parameter gradient equals the circularly
-        padded network's.  With `train_weights` the loss is sum(w e) / (B C sum w) instead of the mean."""
-        noise = default(noise, lambda: torch.randn_like(x_start))
-        plan = TrainStep(self, x_start.shape, s)
+        padded network's.  With `train_weights` the loss is sum(w e) / (B C sum w) instead of the mean.  With
+        `train_crop`, at a scale larger than the crop, x_noisy is one window per sample (`windows`: (B,2) origins, else
+        `crop_fn`, else the clamped draw), `noise` has the window's size, and the loss is
+        sum_b sum_c sum_{p in V_b} w(p) e / (C sum_b sum_{p in V_b} w(p)) over the valid rectangles V_b."""
+        plan = TrainStep(self, x_start.shape, s, windows=windows, draw=lambda: self._draw_windows(s, x_start.shape))
         x_orig = x_orig if plan.s > 0 else None
+        if plan.crop is not None:
+            win, rects = plan.tables(x_start.device)
+            noise = default(noise, lambda: torch.randn(plan.ext_shape, dtype=x_start.dtype, device=x_start.device))
+            x_noisy = self._q_sample_impl(x_start, t, 0, noise, x_orig=x_orig, gamma_row=plan.gamma_row, crop=plan.crop,
+                                          windows=win)
+            x_recon = self.denoise_fn(x_noisy, t, plan.s)                   # (window size, like x_noisy)
+            return self._step_loss(plan, noise, x_recon, x_start, x_orig, t, win, rects)
+        noise = default(noise, lambda: torch.randn_like(x_start))
         x_noisy = self._q_sample_impl(x_start, t, 0, noise, x_orig=x_orig, gamma_row=plan.gamma_row, halo=plan.halo)
         x_recon = self.denoise_fn(x_noisy, t, plan.s)                       # (extended by the halo, like x_noisy)
         return self._step_loss(plan, noise, x_recon, x_start, x_orig, t)
 
-    def _step_loss(self, plan, noise, x_recon, x_start, x_orig, t):
-        """The loss of the step `plan` on the network's output `x_recon` (extended by the plan's halo)."""
+    def _step_loss(self, plan, noise, x_recon, x_start, x_orig, t, win=None, rects=None):
+        """The loss of the step `plan` on the network's output `x_recon` (extended by the plan's halo, or of the plan's crop:
+        `win` / `rects` are then the plan's tables on the device)."""
+        if plan.crop is not None:
+            if plan.loss_type == 'l1':
+                return l1_loss(noise, x_recon, (0, 0), plan.weight, plan.inv_norm, win, rects)
+            # 'l2' and 'l1_pred_img' as below: torch ops, on a per-sample (B,1,h,w) weight built from the tables on the device
+            (B, _, _, _), (h, w) = plan.shape, plan.crop
+            ys = torch.arange(h, device=win.device)[None, :, None]
+            xs = torch.arange(w, device=win.device)[None, None, :]
+            r = rects.long()
+            wb = ((ys >= r[:, 0, None, None]) & (ys < r[:, 1, None, None]) & (xs >= r[:, 2, None, None])
+                  & (xs < r[:, 3, None, None])).to(x_recon.dtype)
+            gy, gx = win[:, 0, None, None].long() + ys, win[:, 1, None, None].long() + xs        # full-image positions
+            if plan.weight is not None:
+                wb = wb * plan.weight[gy, gx]
+            wb = wb[:, None]
+            if plan.loss_type == 'l2':
+                return ((noise - x_recon) ** 2 * wb).sum() * plan.inv_norm
+            target = self._mix_prev(plan, x_start, x_orig, t)
+            bi = torch.arange(B, device=win.device)[:, None, None, None]
+            ci = torch.arange(target.shape[1], device=win.device)[None, :, None, None]
+            target = target[bi, ci, gy[:, None], gx[:, None]]                 # the same windows of the target
+            return ((target - x_recon).abs() * wb).sum() * plan.inv_norm
         if plan.loss_type == 'l1':     # what main.py:97 selects: one fused kernel (loss, gradient, the halo's and the holes' zeros)
             return l1_loss(noise, x_recon, plan.halo, plan.weight, plan.inv_norm)
         # the two loss types main.py never selects (models.py:595-607): the network's forward / backward are the HIP path

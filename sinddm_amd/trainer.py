@@ -90,7 +90,8 @@ class MultiscaleTrainer(object):
                  image_sizes=None, train_batch_size=32, train_lr=2e-5, train_num_steps=100000,
                  gradient_accumulate_every=2, fp16=False, step_start_ema=2000, update_ema_every=10,
                  save_and_sample_every=25000, avg_window=100, sched_milestones=None, results_folder='./results',
-                 device=None, train_tile=(False, False), train_mask=None, train_mask_grow=0, train_mask_fill='mean'):
+                 device=None, train_tile=(False, False), train_mask=None, train_mask_grow=0, train_mask_fill='mean',
+                 train_crop=None, train_crop_margin=0):
         super().__init__()
         self.device = device
         self.sched_milestones = [10000, 30000, 60000, 80000, 90000] if sched_milestones is None else sched_milestones
@@ -103,6 +104,11 @@ class MultiscaleTrainer(object):
         # tileable training (wrap_y, wrap_x): the model that trains wraps its borders in p_losses.  The EMA copy never
         # trains; how it SAMPLES is its own `tile` setting.
         self.model.train_tile = (bool(train_tile[0]), bool(train_tile[1]))
+        # crop training: (ch, cw) or None, and the margin the loss keeps from a window's open sides -- like `train_tile`, set
+        # on the model that trains only (the EMA copy keeps None) and not stored in checkpoints.  train_step.TrainStep
+        # refuses what does not fit (a crop with train_tile, a window within two margins) at the first step.
+        self.model.train_crop = None if train_crop is None else (int(train_crop[0]), int(train_crop[1]))
+        self.model.train_crop_margin = int(train_crop_margin)
         self.update_ema_every = update_ema_every
         self.step_start_ema = step_start_ema
         self.save_and_sample_every = save_and_sample_every
@@ -273,6 +279,7 @@ class MultiscaleTrainer(object):
             s = self._pick_scale(s_weights)
             for _ in range(self.gradient_accumulate_every):
                 data = self.data_list[s]
+                self.model.crop_step = self.step                 # (what a crop_fn is called with)
                 loss = self.model(data, s)
                 if dp:
                     loss = loss * self.loss_weight       # shard mean -> this shard's share of the global-batch mean
