@@ -564,6 +564,54 @@ int sinddm_sample_chain_mix(const float* params, const float* packed, float* x, 
                             const sinddm_solver_opts* so /*host, may be NULL*/,
                             const sinddm_mix_opts* mx /*host, may be NULL*/);
 
+/* ---- per-pixel edit strength: the known-region keep, gated by level ---------------------------------------------------- */
+/* With the block the mask plane of `keep` is read as a HOLD LEVEL h(p) in [0, 1] instead of a blend weight, and step i of the
+ * call has a threshold thr[i] in (0, 1].  The step then uses, in place of m[p] in every formula of the keep block above
+ * (the jump's x0h included),
+ *     m_eff(p) = h(p) >= thr[i] ? 1.0f : 0.0f                 one fp32 compare, h as loaded, thr[i] as passed; h == thr is kept
+ * so a pixel is either replaced by the forward-diffused known image of the step's level or left to the model, and WHICH of
+ * the two may change from step to step: a pixel kept down to level l and released afterwards is a q-sample of the known image
+ * at level l, denoised from there in the context of its neighbours -- SDEdit from level l for that pixel.  The
+ * host chooses the thresholds; the sampler's rule is thr = 1 - (land + 1) / (t_top + 1) (functions.gate_thresholds).
+ *   - Gating switches the soft blend off: a hold level strictly between 0 and 1 never blends, it only sets the release step.
+ *   - `plain` and `kept` are computed by the same instructions gated and ungated: step i of the gated call equals, bit for
+ *     bit, the ungated step whose mask is (h >= thr[i]) as 0.0f / 1.0f.  A binary mask makes the gate invisible: h = 1 passes
+ *     every threshold in (0, 1], h = 0 passes none.
+ *   - Which steps read a draw does not change: z is drawn (or its slot of opts->noise read) when sigma != 0 or keep_b != 0,
+ *     whatever the gate decides for any pixel.
+ *   - Per-sample hold levels ride on sinddm_batch_opts::keep_mask_per_sample; under a halo the plane arrives wrapped; ROI
+ *     maps, seeds and blends, recorded draws, jumps, layout pulls, the multistep step and the two-stream split work as before
+ *     (the threshold is one more per-step host scalar beside `ab`); results with / without aux_stream are identical. */
+typedef struct sinddm_gate_opts {
+    const float* thr;    /* HOST, n_steps floats, each in (0, 1] */
+} sinddm_gate_opts;
+
+/* sinddm_sample_chain_mix with the gate (every chain entry fills one internal description; they differ only in the options
+ * they can express).  gt = NULL or gt->thr = NULL: the same launches, the same numbers as sinddm_sample_chain_mix.  The gated
+ * call launches the kernels of the ungated one.
+ * SINDDM_E_BADARG (before any device work): a thr[i] outside (0, 1] or NaN; the block without keep maps. */
+int sinddm_sample_chain_gate(const float* params, const float* packed, float* x, float* x_alt, float* eps,
+                             const float* x_tilde, const sinddm_step_coefs* coefs /*host*/, const int* t_list /*host*/,
+                             int n_steps, float scale, uint64_t seed, uint64_t stream_id0, int dim, int B, int H, int W,
+                             void* ws, size_t ws_bytes, void* stream, void* aux_stream, int* result_in_alt /*host*/,
+                             const sinddm_chain_opts* opts /*host, may be NULL*/, int halo_y, int halo_x,
+                             const sinddm_keep_opts* keep /*host, may be NULL*/,
+                             const uint64_t* sample_seeds /*device, B entries, 8-byte aligned, or NULL*/,
+                             const sinddm_resample_opts* rs /*host, may be NULL*/,
+                             const sinddm_layout_opts* lo /*host, may be NULL*/,
+                             const sinddm_batch_opts* bo /*host, may be NULL*/,
+                             const sinddm_solver_opts* so /*host, may be NULL*/,
+                             const sinddm_mix_opts* mx /*host, may be NULL*/,
+                             const sinddm_gate_opts* gt /*host, may be NULL*/);
+
+/* sinddm_reverse_step_keep with the gate: keep_m is the hold level, the step uses (keep_m[p] >= thr) as its mask.  The
+ * step-by-step route and the cross-check of the chain call.  SINDDM_E_BADARG: what sinddm_reverse_step_keep refuses; thr
+ * outside (0, 1] or NaN. */
+int sinddm_reverse_step_keep_gate(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                                  const sinddm_step_coefs* coefs /*host*/, const float* edit_w, const float* edit_c /*both or neither, may be NULL*/,
+                                  const float* keep_m, const float* keep_x0, float keep_a, float keep_b,
+                                  int B, int C, int HW, void* stream, float thr);
+
 /* The block delta on its own: delta[B][3][h][w] from the step's inputs.  H x W is the CENTRE size (as in the chain calls);
  * x_t, eps, x_tilde are B*3*(H + 2 halo_y)*(W + 2 halo_x) floats, layout / edit_c one sample of that, edit_w one plane.
  * edit_w / edit_c both-or-neither.  x_tilde is read in modes 1 and 2 only.

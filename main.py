@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Command line of the MI355X SinDDM hot-path build: same flags as the reference's main.py
 (reference main.py:13-58) for the modes that run on the hot path: `train`, `sample`, `style_transfer`,
-`harmonization` and `roi`.
+`harmonization` and `roi`, plus the modes the reference does not have (below).
 
     python main.py --scope balloons --mode train  --dataset_folder ./datasets/balloons/ --image_name balloons.png
     python main.py --scope balloons --mode sample --dataset_folder ./datasets/balloons/ --image_name balloons.png \
@@ -41,6 +41,15 @@ black part of the mask (white = keep the training image's pixel; the file is bro
 `--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.  `--resample R --jump_length J`
 (both modes; defaults 1 1 = no jumps) add RePaint's resampling: at every noise level that is a multiple of J the run jumps
 back up by J levels and comes down again, R times in all, so that the generated region is shaped with the known one in view.
+`edit` (no reference mode) edits a picture with a strength per pixel: `--mode edit --edit_map FILE [FILE ...] [--edit_image FILE
+[FILE ...]]`.  The map is a gray picture brought to the finest target size, read as value / 255: black = leave the pixel alone,
+white = redraw it freely, gray = re-noise it to that share of every scale's levels and let the model take it from there (each
+pixel its own SDEdit start level: "leave the sky, retouch the trees a little, redraw the foreground").  `--edit_image` is the
+picture being edited (a path, or a name inside the dataset folder; default: the training image).  Inside the step kernels a
+pixel stays pinned to the forward-diffused picture until the run is down to its level (`keep_gated`: still one library call per
+scale); a black-and-white map is `inpaint` with the inverted mask, bit for bit.  `--tile`, `--seeds` and the blend flags,
+`--resample` / `--jump_length`, `--sample_steps` / `--solver_order` and `--scale_mul` (with `--edit_image`) apply.  (The
+reference's `--strength` is a CLIP flag: hence `--edit_map`.)
 `--sample_steps N [N ...]` (no reference flag; one value, or one per scale) evaluates the network at no more than N levels per
 scale instead of all of them, `--sample_spacing {t,logsnr}` chooses which, `--solver_order 2` takes the second-order multistep
 step that makes few steps accurate, `--eta F` scales the noise of a scale-0 step (1 = the reference's, 0 = deterministic).  Every
@@ -60,8 +69,8 @@ to sample B, or around sample BASE on a closed circle of radius R (default 0.5).
 is sample b; `--blend_from_scale S` lets the scales below S use each frame's first seed alone (a shared coarse layout with
 detail that moves); `--gif MS` also writes the finest scale's frames as one animated GIF, MS milliseconds per frame, a loop
 repeating for ever.  Every sampling mode honours them.
-A batch of independent jobs: `--mask_path`, `--input_image` and `--layout_strength` take one or more values and `--anchor` one
-or more pairs.  With N > 1 values the batch size must be a multiple of N and sample b gets value b % N (so `--seeds` sweeps
+A batch of independent jobs: `--mask_path`, `--input_image`, `--edit_map`, `--edit_image` and `--layout_strength` take one or more
+values and `--anchor` one or more pairs.  With N > 1 values the batch size must be a multiple of N and sample b gets value b % N (so `--seeds` sweeps
 line up: `--sample_batch_size 8 --mask_path a.png b.png --seed_base 0` fills each hole four times); every sample is then
 conditioned on its own maps inside the one chain call per scale.  One value is the command line as it was.
 `evaluate` (no reference mode) measures what the samples copy: `--mode evaluate [--eval_patch {3,5,7}] [--eval_scale S]` draws a
@@ -102,6 +111,8 @@ _FLAGS = [
     ("roi_target", None, int, "+"), ("roi_bbs", None, int, "+"),
     # known-region sampling: the mask file of `inpaint`, the placement of the training image on the canvas of `outpaint`
     ("mask_path", None, str, None), ("anchor", [0.5, 0.5], float, 2),
+    # per-pixel edit strength: the gray strength map of `edit` (white = redraw freely, black = keep) and the picture it edits
+    ("edit_map", None, str, None), ("edit_image", None, str, None),
 ]
 
 
@@ -126,7 +137,7 @@ class _Pairs(argparse.Action):
         setattr(namespace, self.dest, pairs[0] if len(pairs) == 1 else Jobs(pairs))
 
 
-_PER_JOB = ("mask_path", "input_image", "layout_strength", "anchor")     # the flags that take one value per job
+_PER_JOB = ("mask_path", "input_image", "layout_strength", "anchor", "edit_map", "edit_image")   # the flags that take one value per job
 
 
 def job_values(value, batch_size):
@@ -256,6 +267,8 @@ def parse_args(argv=None):
         p.error("--layout_scales A B needs 0 <= A <= B")
     if args.eval_scale is not None and args.eval_scale < 0:
         p.error("--eval_scale must be >= 0")
+    if args.mode == "edit" and not args.edit_map:
+        p.error("--mode edit needs --edit_map FILE (a gray picture: white = redraw freely, black = keep the pixel)")
     return args
 
 
@@ -416,6 +429,29 @@ def main():
                             strength=job_values(args.layout_strength, args.sample_batch_size),
                             t_min=args.layout_t_min, scales=args.layout_scales, scale_mul=scale_mul,
                             custom_t_list=sample_t_list, save_unbatched=True, **seed_kw)
+    elif args.mode == 'edit':
+        import numpy as np
+        from PIL import Image
+        h, w = ms_diffusion.target_size(n_scales - 1, scale_mul)
+        find = lambda name: name if os.path.exists(name) else os.path.join(args.dataset_folder, name)
+        load_map = lambda f: torch.from_numpy(np.asarray(Image.open(find(f)).convert("L").resize((w, h), Image.BILINEAR),
+                                                         dtype=np.float32).copy()).div(255)
+
+        def load_pic(f):
+            pic = np.asarray(Image.open(find(f)).convert("RGB").resize((w, h), Image.LANCZOS), dtype=np.float32)
+            return torch.from_numpy(pic.transpose(2, 0, 1).copy()).div(255).mul(2).sub(1)
+
+        def per_job(value, load):                                          # one tensor, or one per sample
+            names = job_values(value, args.sample_batch_size)
+            if not isinstance(names, list):
+                return load(names)
+            files = {f: load(f) for f in value}
+            return torch.stack([files[f] for f in names])
+
+        frames = trainer.edit(per_job(args.edit_map, load_map),
+                              image=per_job(args.edit_image, load_pic) if args.edit_image else None,
+                              batch_size=args.sample_batch_size, scale_mul=scale_mul, custom_t_list=sample_t_list,
+                              save_unbatched=True, resample=args.resample, jump_length=args.jump_length, **seed_kw)
     elif args.mode == 'evaluate':
         if args.eval_scale is not None and args.eval_scale >= n_scales:
             raise SystemExit(f"--eval_scale {args.eval_scale} is past the {n_scales} scales")
@@ -429,7 +465,7 @@ def main():
             print("wrote " + os.path.join(results_folder, "patch_report.json"))
     else:
         raise NotImplementedError(
-            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint, paint2image and evaluate are built for MI355X; "
+            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint, paint2image, edit and evaluate are built for MI355X; "
             "the CLIP-guided modes of the reference need CLIP autograd and are out of scope (SURVEY.md section 8)")
     if args.gif is not None and frames and rank == 0:
         from sinddm_amd.functions import write_gif

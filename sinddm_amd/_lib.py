@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "sinddm_debug_first_conv",
     "sinddm_patch_nnf_workspace_bytes", "sinddm_patch_nnf",
     "sinddm_q_sample_crop", "sinddm_l1_loss_rect_fwd_bwd",
+    "sinddm_sample_chain_gate", "sinddm_reverse_step_keep_gate",
 )
 
 
@@ -106,6 +107,12 @@ class MixOpts(C.Structure):
     _fields_ = [("keys", C.c_void_p), ("weights", C.c_void_p), ("K", C.c_int)]
 
 
+class GateOpts(C.Structure):
+    """Mirror of `sinddm_gate_opts` (include/sinddm_hip.h): `thr` a HOST array of one threshold in (0, 1] per step of the
+    call; the keep mask is then a hold level and a step keeps the pixels whose level is >= its threshold."""
+    _fields_ = [("thr", C.POINTER(C.c_float))]
+
+
 class SinddmError(RuntimeError):
     pass
 
@@ -165,6 +172,9 @@ def load() -> C.CDLL:
         "sinddm_sample_chain_mix": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
                                                 C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts),
                                                 C.POINTER(SolverOpts), C.POINTER(MixOpts)]),
+        "sinddm_sample_chain_gate": (i, chain + [C.POINTER(ChainOpts), i, i, C.POINTER(KeepOpts), p,
+                                                 C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts),
+                                                 C.POINTER(SolverOpts), C.POINTER(MixOpts), C.POINTER(GateOpts)]),
         "sinddm_normal_fill_mix": (i, [p, i, i64, p, p, i, C.c_uint64, p]),
         "sinddm_reverse_step_ms": (i, [p, p, p, p, p, C.POINTER(StepCoefs), f, p, p, p, p, p, f, f, i, i, i, p]),
         "sinddm_layout_delta": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, i, i, i, p]),
@@ -174,6 +184,7 @@ def load() -> C.CDLL:
                                          p]),
         "sinddm_normal_fill_samples": (i, [p, i, i64, p, C.c_uint64, p]),
         "sinddm_reverse_step_keep": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, p, p, f, f, i, i, i, p]),
+        "sinddm_reverse_step_keep_gate": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, p, p, f, f, i, i, i, p, f]),
         "sinddm_wrap_halo": (i, [p, p, i, i, i, i, i, p]),
         "sinddm_upsample_bilinear_wrap": (i, [p, p, i, i, i, i, i, i, i, p]),
         "sinddm_normal_fill": (i, [p, i64, C.c_uint64, C.c_uint64, p]),

@@ -53,6 +53,8 @@ struct ChainRun {
     const uint64_t* mix_keys;            // NULL: the call without the block
     const float* mix_w;
     int mix_K;
+    // sinddm_gate_opts
+    const float* gate_thr;               // HOST, one per step, each in (0, 1]; NULL: the call without the block
 };
 
 // the 21 arguments every entry shares; the options start out absent
@@ -90,6 +92,13 @@ inline void chain_run_set(ChainRun& r, const sinddm_mix_opts* mx) {
     if (mx && mx->keys) { r.mix_keys = mx->keys; r.mix_w = mx->weights; r.mix_K = mx->K; }
 }
 
+inline void chain_run_set(ChainRun& r, const sinddm_gate_opts* gt) {
+    if (gt) r.gate_thr = gt->thr;
+}
+
+// a gate threshold the tails can take: in (0, 1] (0 is the tails' "ungated"; a NaN fails both compares)
+inline bool gate_valid(float thr) { return thr > 0.0f && thr <= 1.0f; }
+
 // a jump description the kernels can take: r in (0, 1], s >= 0, d only where x-tilde exists; never after a mode-2 step
 inline bool jump_valid(const sinddm_jump_coefs& j, const sinddm_step_coefs& k) {
     return k.mode != 2 && j.r > 0.0f && j.r <= 1.0f && j.s >= 0.0f && (k.mode != 0 || j.d == 0.0f);
@@ -110,7 +119,7 @@ struct ChainChecked {
 };
 
 // Every check of a chain call that comes before the plan, in the order that decides which of two defects is reported.
-// 0, or the SINDDM_E_* to return; nothing is dereferenced but the HOST arrays coefs / jumps / layout_g / solver_q.
+// 0, or the SINDDM_E_* to return; nothing is dereferenced but the HOST arrays coefs / jumps / layout_g / solver_q / gate_thr.
 inline int chain_check(const ChainRun& r, ChainChecked* out) {
     const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
     *out = ChainChecked{};
@@ -132,6 +141,12 @@ inline int chain_check(const ChainRun& r, ChainChecked* out) {
     const bool past_int = 3LL * c.H * c.W > 0x7fffffffLL;      // (3: the sample's channels)
     if ((r.edit_w == nullptr) != (r.edit_c == nullptr) || (r.keep_m == nullptr) != (r.keep_x0 == nullptr)) return SINDDM_E_BADARG;
     if (r.keep_m && !r.keep_ab) return SINDDM_E_BADARG;
+    // the level gate: a threshold per step, read by the KEEP tails beside `ab` -- nothing to gate without the maps
+    if (r.gate_thr) {
+        if (!r.keep_m) return SINDDM_E_BADARG;
+        for (int i = 0; i < r.n_steps; ++i)
+            if (!gate_valid(r.gate_thr[i])) return SINDDM_E_BADARG;
+    }
     if ((r.edit_w || r.keep_m) && past_int) return SINDDM_E_BADSHAPE;                    // (the maps are indexed with ints)
     // per-sample seeds: recorded draws win over them, as they win over `seed`; the kernels then never see the array
     c.sseeds = r.noise ? nullptr : reinterpret_cast<const unsigned long long*>(r.sample_seeds);

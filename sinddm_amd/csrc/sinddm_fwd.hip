@@ -1593,6 +1593,7 @@ static int chain_enqueue(const ChainCtx& k, float** result) {
             t.km = r.keep_m; t.kx = r.keep_x0;
             t.sew = k.bs.sew; t.sec = k.bs.sec; t.skm = k.bs.skm; t.skx = k.bs.skx;
             t.ka = r.keep_m ? r.keep_ab[2 * i] : 1.0f; t.kb = r.keep_m ? r.keep_ab[2 * i + 1] : 0.0f;
+            t.kthr = r.gate_thr ? r.gate_thr[i] : 0.0f;          // (0: the mask is the blend weight it has always been)
             s.jump = k.c.jumps && k.c.jumps[i].on;
             if (s.jump) {
                 s.jp.r = k.c.jumps[i].r; s.jp.s = k.c.jumps[i].s; s.jp.d = k.c.jumps[i].d;
@@ -1753,6 +1754,17 @@ int sinddm_sample_chain_mix(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_i
     r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
     return sample_chain_impl(r);
 }
+
+int sinddm_sample_chain_gate(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_in_alt, const sinddm_chain_opts* opts, int halo_y,
+                             int halo_x, const sinddm_keep_opts* keep, const uint64_t* sample_seeds, const sinddm_resample_opts* rs,
+                             const sinddm_layout_opts* lo, const sinddm_batch_opts* bo, const sinddm_solver_opts* so,
+                             const sinddm_mix_opts* mx, const sinddm_gate_opts* gt) {
+    ChainRun r = CHAIN_SHARED(aux_stream);
+    chain_run_set(r, opts); chain_run_set(r, keep); chain_run_set(r, rs); chain_run_set(r, lo); chain_run_set(r, bo);
+    chain_run_set(r, so); chain_run_set(r, mx); chain_run_set(r, gt);
+    r.halo_y = halo_y; r.halo_x = halo_x; r.sample_seeds = sample_seeds;
+    return sample_chain_impl(r);
+}
 #undef CHAIN_SHARED
 #undef CHAIN_SHARED_PARAMS
 
@@ -1794,6 +1806,16 @@ int sinddm_reverse_step_keep(const float* x_t, const float* eps, const float* x_
                              const float* keep_x0, float keep_a, float keep_b, int B, int C, int HW, void* stream) {
     const StepCall sc = step_call(x_t, eps, x_tilde, noise, out, coefs, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b, keep_m != nullptr,
                                   B, C, HW, stream);
+    return sc.rc ? sc.rc : plain_step_launch(sc);
+}
+
+// (the gate is sinddm_reverse_step_keep's kernel with the threshold in its TailArgs)
+int sinddm_reverse_step_keep_gate(const float* x_t, const float* eps, const float* x_tilde, const float* noise, float* out,
+                                  const sinddm_step_coefs* coefs, const float* edit_w, const float* edit_c, const float* keep_m,
+                                  const float* keep_x0, float keep_a, float keep_b, int B, int C, int HW, void* stream, float thr) {
+    StepCall sc = step_call(x_t, eps, x_tilde, noise, out, coefs, edit_w, edit_c, keep_m, keep_x0, keep_a, keep_b,
+                            keep_m != nullptr && gate_valid(thr), B, C, HW, stream);
+    sc.t.kthr = thr;
     return sc.rc ? sc.rc : plain_step_launch(sc);
 }
 

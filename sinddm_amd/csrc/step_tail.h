@@ -27,6 +27,7 @@ struct TailArgs {
     const unsigned long long* mkeys;    // MIX    the blend tables of THIS launch's samples (device): key[b*K + k], w[b*K + k]
     const float* mw;
     int mK;                             // MIX    seeds per sample, 1 .. SINDDM_MIX_MAX
+    float kthr;                         // KEEP   the step's gate threshold in (0, 1] (sinddm_gate_opts::thr), or 0: ungated
 };
 // Where a tail's N(0,1) draws come from, the NOISE option of every tail kernel: Philox of one key per launch or per sample
 // (the kernels the chain always ran), recorded draws read from `nz`, or a BLEND of K per-sample Philox streams (philox_mix4).
@@ -75,6 +76,14 @@ __device__ __forceinline__ float keep_blend(const sinddm_step_coefs& k, float pl
     const float target = k.mode == 1 ? k.gamma_tm1 * xb + (1.0f - k.gamma_tm1) * k0 : k0;
     const float kept = ka * target + kb * z;
     return m * kept + (1.0f - m) * plain;
+}
+
+// KEEP, gated: with a step threshold the mask plane is a HOLD LEVEL h(p) and the step keeps a pixel iff h(p) >= thr, fully;
+// a.kthr == 0 (no threshold) hands the blend weight through as it was loaded.  Applied where m is loaded, never inside
+// keep_blend or tail_eval: `plain` and `kept` are the same instruction sequence gated and ungated.  The threshold is
+// wave-uniform: one compare and one select per pixel, no load, no new instantiation.
+__device__ __forceinline__ float keep_gate(const TailArgs& a, float m) {
+    return a.kthr > 0.0f ? (m >= a.kthr ? 1.0f : 0.0f) : m;
 }
 
 // THE step of one element, the only place it is written: every kernel below calls it per lane, so all of them round alike.
@@ -208,7 +217,7 @@ __global__ __launch_bounds__(256) void reverse_step_kernel(const float* __restri
         const int q = (EDIT || KEEP) ? (int)(i - b * chw) : 0;
         const float xb = a.k.mode != 0 ? xtil[i] : 0.0f;
         out[i] = tail_eval<EDIT, KEEP>(a, xt[i], eps[i], xb, a.nz[i], EDIT ? map_slice(a.ew, b, a.sew)[q % hw] : 1.0f,
-                                       EDIT ? map_slice(a.ec, b, a.sec)[q] : 0.0f, KEEP ? map_slice(a.km, b, a.skm)[q % hw] : 0.0f,
+                                       EDIT ? map_slice(a.ec, b, a.sec)[q] : 0.0f, KEEP ? keep_gate(a, map_slice(a.km, b, a.skm)[q % hw]) : 0.0f,
                                        KEEP ? map_slice(a.kx, b, a.skx)[q] : 0.0f);
     }
 }
@@ -229,7 +238,7 @@ __global__ __launch_bounds__(256) void reverse_step_kernel(const float* __restri
 //          over per-sample seeds on the host: no launch has both.  An int since the blend: DRAW_PHILOX (the draw above),
 //          DRAW_RECORDED (this), DRAW_MIX (z is the row's blend of K Philox streams, philox_mix4; rows are samples, as with
 //          per-sample seeds, and the exception below does not apply).
-//   KEEP   the known-region replacement of keep_blend: m = km[p], k0 = kx[ch * HW + p]
+//   KEEP   the known-region replacement of keep_blend: m = km[p] (through keep_gate), k0 = kx[ch * HW + p]
 template <bool EDIT, int NOISE, bool KEEP>
 __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __restrict__ xt, const float* __restrict__ eps,
                                                                 const float* __restrict__ xtil, float* __restrict__ out,
@@ -249,7 +258,11 @@ __global__ __launch_bounds__(256) void reverse_step_rows_kernel(const float* __r
         float w[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
         if (EDIT) quad_maps(a.ew, a.ec, a.sew, a.sec, i0, 0, nv, chw, hw, w, c);
         float m[4] = {0.f, 0.f, 0.f, 0.f}, k0[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, i0, 0, nv, chw, hw, m, k0);
+        if (KEEP) {
+            quad_maps(a.km, a.kx, a.skm, a.skx, i0, 0, nv, chw, hw, m, k0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m[j] = keep_gate(a, m[j]);
+        }
         if (!per_sample && nv < 4) {     // the exception above
             for (int j = 0; j < nv; ++j) {
                 const float xb = a.k.mode != 0 ? xtil[i0 + j] : 0.f;
@@ -371,7 +384,7 @@ __device__ __forceinline__ StreamQuad stream_quad(const TailArgs& a, const Strea
     if (KEEP) quad_maps(a.km, a.kx, a.skm, a.skx, iv, s.jlo, s.jhi, row.chw, row.hw, m, k0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        s.w[j] = w[j]; s.c[j] = c[j]; s.m[j] = m[j]; s.k0[j] = k0[j];
+        s.w[j] = w[j]; s.c[j] = c[j]; s.m[j] = KEEP ? keep_gate(a, m[j]) : m[j]; s.k0[j] = k0[j];
     }
     return s;
 }
@@ -635,7 +648,11 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_kernel(EPS eps, c
     f32x4 mw{1.f, 1.f, 1.f, 1.f};
     if (EDIT) mw = *reinterpret_cast<const f32x4*>(map_slice(t.ew, b, t.sew) + p);
     f32x4 mk{0.f, 0.f, 0.f, 0.f};
-    if (KEEP) mk = *reinterpret_cast<const f32x4*>(map_slice(t.km, b, t.skm) + p);
+    if (KEEP) {
+        mk = *reinterpret_cast<const f32x4*>(map_slice(t.km, b, t.skm) + p);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) mk[j] = keep_gate(t, mk[j]);
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const long long i0 = ((long long)b * 3 + c) * HW + p;
@@ -714,7 +731,7 @@ __global__ __launch_bounds__(256) void final_conv_reverse_step_pitch_kernel(EPS 
                 }
                 // (the blend after the step, its maps read in place, as this kernel always had it: see the plain-row kernel)
                 const float o = tail_eval<EDIT, false>(t, xt[i0 + j], e[c][j], xb, z, mw, mc, 0.f, 0.f);
-                out[i0 + j] = KEEP ? keep_blend(t.k, o, z, xb, km[pp], kx[(size_t)c * HW + pp], t.ka, t.kb) : o;
+                out[i0 + j] = KEEP ? keep_blend(t.k, o, z, xb, keep_gate(t, km[pp]), kx[(size_t)c * HW + pp], t.ka, t.kb) : o;
             }
         }
     }

@@ -174,6 +174,58 @@ def keep_mask_pyramid(mask, sizes, hard: bool = True, batch: bool = False) -> Li
     return out
 
 
+# ---- helpers of per-pixel edit strength (MultiscaleTrainer.edit; no reference counterpart) ---------------------------
+def gate_thresholds(lands: Sequence[int], t_top: int) -> np.ndarray:
+    """The per-step thresholds of a level-gated keep run (sinddm_gate_opts), their ONE owner: for a step that lands on level
+    `land` (-1: the clean image) of a run whose highest level is `t_top`,
+        thr = 1 - (land + 1) / (t_top + 1)
+    evaluated in float64 and stored as fp32.  A pixel of hold level h = 1 - strength is kept by the step iff h >= thr, i.e.
+    iff strength <= (land + 1) / (t_top + 1): strength 0 is kept through to the clean image (thr = 1 exactly on landing
+    clean), strength 1 is never kept (thr > 0 always), strength c is released when the run has c (t_top + 1) levels left.
+    The rule reads the landing level alone, so strided schedules and resampling jumps need nothing special: after a jump
+    back up a released pixel is pinned again until the run comes back down to its level.  Every land must lie in
+    [-1, t_top - 1], which keeps every threshold inside (0, 1]."""
+    top = int(t_top)
+    u = np.asarray([int(v) for v in lands], dtype=np.int64)
+    if top < 0 or (u.size and (int(u.min()) < -1 or int(u.max()) > top - 1)):
+        raise ValueError(f"gate_thresholds: lands {u.tolist()} outside [-1, t_top - 1] for t_top = {t_top}")
+    thr = (1.0 - (u.astype(np.float64) + 1.0) / float(top + 1)).astype(np.float32)
+    assert bool(np.all((thr > 0.0) & (thr <= 1.0)))
+    return thr
+
+
+def hold_pyramid(strength, sizes, batch: bool = False) -> List[torch.Tensor]:
+    """A finest-size strength map (H, W) in [0, 1] (0 = keep the known image, 1 = redraw freely) brought to every (h, w) of
+    `sizes` by area averaging, returned as the HOLD LEVEL 1 - strength the gated keep reads: one fp32 (h, w) tensor per scale
+    on the map's device.  The footprints are `_area_weights`' with the division done last (the overlaps are integers in
+    units of 1 / n_out), so a constant map stays constant and a {0, 1} map on regions that are whole footprints stays {0, 1},
+    exactly.  `batch`: a (B, H, W) stack, one job per sample, gives (B, h, w) tensors: row b is what the call returns for map
+    b alone (it has to be asked for, as in `keep_mask_pyramid`)."""
+    m = torch.as_tensor(strength)
+    if batch:
+        if m.dim() != 3 or m.shape[0] < 1:
+            raise ValueError(f"hold_pyramid: a batch of strength maps must be (B, H, W), got {tuple(m.shape)}")
+        rows = [hold_pyramid(m[b], sizes) for b in range(m.shape[0])]
+        return [torch.stack([r[i] for r in rows]) for i in range(len(rows[0]))]
+    if m.dim() != 2:
+        raise ValueError(f"hold_pyramid: strength must be (H, W), got {tuple(m.shape)}")
+    device = m.device
+    full = m.detach().to("cpu", torch.float64).numpy()
+    if not bool(np.all((full >= 0.0) & (full <= 1.0))):                     # (a NaN fails both)
+        raise ValueError("hold_pyramid: strength outside [0, 1]")
+    H, W = full.shape
+    out = []
+    for h, w in sizes:
+        h, w = int(h), int(w)
+        if h > H or w > W or h < 1 or w < 1:
+            raise ValueError(f"hold_pyramid: scale {(h, w)} does not fit the strength map {full.shape}")
+        # (weights * n_in are the integer overlaps: sums of a {0, 1} map are exact, and a whole footprint gives H * W)
+        num = np.rint(_area_weights(h, H) * H) @ full @ np.rint(_area_weights(w, W) * W).T
+        avg = num / (float(H) * float(W))
+        out.append(torch.from_numpy(np.clip(1.0 - avg, 0.0, 1.0).astype(np.float32)).to(device))
+    return out
+
+
 # ---- helpers of masked training (MultiScaleGaussianDiffusion.train_weights; no reference counterpart) ----------------
 def _grow_1d(hole: np.ndarray, g: int, axis: int, wrap: bool) -> np.ndarray:
     """Boolean dilation of `hole` by `g` pixels to both sides along `axis`: across the border, modulo the size, with `wrap`;

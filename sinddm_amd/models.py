@@ -13,6 +13,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
   inter-scale upsample       -> sinddm_upsample_bilinear  (models.py:567)
   known pixels (`keep_maps`) -> sinddm_sample_chain_keep / sinddm_reverse_step_keep   (no reference line: RePaint-style
                                 replacement of the known region after every reverse step)
+  edit strength (`keep_gated`) -> sinddm_sample_chain_gate / sinddm_reverse_step_keep_gate   (no reference line: the keep
+                                gated per pixel by the step's level -- each pixel its own SDEdit start level)
   tileable sampling (`tile`) -> sinddm_sample_chain_tile / sinddm_wrap_halo / sinddm_upsample_bilinear_wrap
                                 (no reference line: padding_mode='circular' on its nn.Conv2d's)
   per-sample noise seeds     -> sinddm_sample_chain_seeds / sinddm_normal_fill_samples   (`sample_seeds`; no reference
@@ -480,8 +482,8 @@ class SinDDMNet(nn.Module):
 # --------------------------------------------------------------------------------------------
 class _ChainCall:
     """The buffers and option blocks of one chain run of `MultiScaleGaussianDiffusion._run_steps`: the steps of `plan` (a
-    sampler.RunPlan) on `img`, through sinddm_sample_chain_batch -- the entry that can express every option; one that is off
-    goes in as NULL, which is the call without it, launch for launch.  Every tensor and ctypes array the library reads through
+    sampler.RunPlan) on `img`, through sinddm_sample_chain_batch -- or the later entry that can express the run's options
+    (_solver, _mix, _gate); one that is off goes in as NULL, which is the call without it, launch for launch.  Every tensor and ctypes array the library reads through
     a raw pointer is an attribute here, so it lives as long as the object."""
 
     def __init__(self, d, plan, img):
@@ -505,6 +507,7 @@ class _ChainCall:
         self.edit = [wrap(m) for m in plan.roi] if plan.roi is not None else (None, None)
         self.opts = _lib.ChainOpts(_lib.ptr(self.edit[0]), _lib.ptr(self.edit[1]), None)
         self.kopts = self.lopts = self.bopts = self.sopts = self.hist = None
+        self.gopts = _lib.GateOpts() if plan.gated else None
         if plan.keep is not None:
             self.keep = [wrap(m) for m in plan.keep]
             self.kopts = _lib.KeepOpts(_lib.ptr(self.keep[0]), _lib.ptr(self.keep[1]), None)
@@ -531,7 +534,7 @@ class _ChainCall:
         p = self.host = pack_steps(self.plan, i0, k)            # (the per-step host arrays of this piece)
         self.opts.noise = _lib.ptr(noise)
         for blk, name, v in ((self.kopts, "ab", p.ab), (self.ropts, "jumps", p.jumps), (self.ropts, "noise", _lib.ptr(jump_noise)),
-                             (self.lopts, "g", p.g), (self.sopts, "q", p.q)):
+                             (self.lopts, "g", p.g), (self.sopts, "q", p.q), (self.gopts, "thr", p.thr)):
             if blk is not None:
                 setattr(blk, name, v)
         in_alt = C.c_int(0)
@@ -539,8 +542,11 @@ class _ChainCall:
                 _lib.ptr(self.xt), p.coefs, p.tl, k, float(self.s), seed, sid0, net.dim_arg, x.shape[0], self.Hc, self.Wc,
                 self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr(x.device), self.aux, C.byref(in_alt), C.byref(self.opts),
                 *self.halo, ref(self.kopts), _lib.ptr(seeds_dev), ref(self.ropts), ref(self.lopts), ref(self.bopts)]
-        if mix_dev is not None:                                # (the blended run: the one entry that can say it)
-            mopts = _lib.MixOpts(_lib.ptr(mix_dev[0]), _lib.ptr(mix_dev[1]), int(mix_dev[0].shape[1]))
+        mopts = _lib.MixOpts(_lib.ptr(mix_dev[0]), _lib.ptr(mix_dev[1]), int(mix_dev[0].shape[1])) if mix_dev is not None else None
+        if self.gopts is not None:                             # (the gated run: the one entry that can say it)
+            _lib.check(self.lib.sinddm_sample_chain_gate(*args, ref(self.sopts), ref(mopts), C.byref(self.gopts)),
+                       "sinddm_sample_chain_gate")
+        elif mix_dev is not None:                              # (the blended run: the one entry that can say it)
             _lib.check(self.lib.sinddm_sample_chain_mix(*args, ref(self.sopts), C.byref(mopts)), "sinddm_sample_chain_mix")
         elif self.sopts is not None:                           # (the multistep run: the one entry that can say it)
             _lib.check(self.lib.sinddm_sample_chain_solver(*args, C.byref(self.sopts)), "sinddm_sample_chain_solver")
@@ -699,6 +705,13 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
         # values between 0 and 1 blend.  A sampling option, like `tile`; not available with CLIP guidance.
         self.keep_maps = None
+        # per-pixel edit strength: False, or True -- the mask of every `keep_maps` entry is then a HOLD LEVEL h in [0, 1]
+        # (1 - strength; functions.hold_pyramid) and a reverse step that lands on level u of a run whose top level is t_top
+        # keeps the pixels with  h >= 1 - (u + 1) / (t_top + 1)  (functions.gate_thresholds; sinddm_sample_chain_gate): a
+        # pixel is pinned to the forward-diffused known image down to its own level and left to the model from there --
+        # SDEdit per pixel.  No soft blend; {0, 1} maps give the ungated run bit for bit.  Needs the scale's `keep_maps`
+        # entry; a sampling option like `keep_maps`, not stored in checkpoints; not available with CLIP guidance.
+        self.keep_gated = False
         # per-sample noise seeds: None (the draws come from torch's generators, as ever), a sequence of B ints in [0, 2^63)
         # (one seed per sample, used at every scale) or a [n_scales][B] nested sequence (row s at scale s; `vary_seeds`).
         # With seeds every N(0,1) draw of sample b -- initial, re-noise, every reverse step -- is a function of
@@ -1294,6 +1307,9 @@ class MultiScaleGaussianDiffusion(nn.Module):
                          network input instead (`_eps`) and steps the centre: the cross-check of the tiled chain.
           `keep_maps`    the scale's mask and known image and the per-step forward scalars: known pixels are replaced inside
                          every step.
+          `keep_gated`   the mask is a hold level and every step carries a threshold (functions.gate_thresholds of its landing
+                         level and the run's top level): the step keeps the pixels at or above it (sinddm_sample_chain_gate).
+                         Same kernels, same launches, same draws and `draw_log` entries as the `keep_maps` run.
           `resample`     (R, J), R > 1: `t_seq` is expanded by functions.resample_schedule; a step that is followed by a jump
                          ends in the step + jump kernel instead of its fused tail.
           `layout_maps`  the steps with t >= layout_t_min run unfused (network, block-delta kernel, layout tail), the others
@@ -1379,18 +1395,20 @@ class MultiScaleGaussianDiffusion(nn.Module):
 
     def _p_sample_host_t(self, x: torch.Tensor, t: int, s: int, clip_denoised: bool = True, repeat_noise: bool = False,
                          step_pos: int = 0, jump_to: Optional[int] = None, land: Optional[int] = None, q: Optional[float] = None,
-                         hist: Optional[torch.Tensor] = None, plan: Optional[RunPlan] = None) -> torch.Tensor:
+                         hist: Optional[torch.Tensor] = None, plan: Optional[RunPlan] = None,
+                         t_top: Optional[int] = None) -> torch.Tensor:
         """One reverse step with the timestep known on the host: net forward + ONE fused kernel.  `step_pos`: the step's
         position in its run -- with `sample_seeds` it selects the draw (noise_stream_id(s, 'step', step_pos)).  `jump_to`:
         the level a resampling jump takes the step's output back up to (sinddm_reverse_step_jump: step + jump in one kernel,
         a second draw of kind 'jump'), or None.  `land`: the level the step lands on (None: t - 1; `step_coefs_to`).  `q` /
         `hist`: the multistep factor of the step and the buffer that carries the previous step's clean estimate
-        (sinddm_reverse_step_ms: `hist` is written, and read when q != 0), or None.  `plan`: the run's plan when `_run_steps`
+        (sinddm_reverse_step_ms: `hist` is written, and read when q != 0), or None.  `t_top`: the highest level of the run the
+        step belongs to -- with `keep_gated` it sets the step's threshold (functions.gate_thresholds).  `plan`: the run's plan when `_run_steps`
         steps through it -- the step is its record `step_pos`; else the one-step plan of the arguments is built here."""
         if (q is None) != (hist is None):
             raise ValueError("a multistep step takes q and hist together")
         if plan is None:
-            plan, step_pos = RunPlan(self, x, s, [t], at=(step_pos, jump_to, land, q), clip_denoised=clip_denoised), 0
+            plan, step_pos = RunPlan(self, x, s, [t], at=(step_pos, jump_to, land, q, t_top), clip_denoised=clip_denoised), 0
         st = plan.steps[step_pos]
         if self.clip_guided_sampling:
             if self.clip_model is None or self.guidance_sub_iters is None or self.stop_guidance is None:
@@ -1417,7 +1435,9 @@ class MultiScaleGaussianDiffusion(nn.Module):
     def _step_tail(self, plan, st, x, eps, z, z2, out, hist, b=None):
         """The single-step entry that ends the step `st` of `plan` on the route of `_p_sample_host_t`: `out` is written.  The
         first that applies: a layout pull (st.g > 0), a resampling jump (second draw z2), a multistep step (`hist`), keep maps,
-        ROI maps, the plain step.  `b`: sample b alone -- slice b of every tensor, row b of every per-sample map (B = 1)."""
+        ROI maps, the plain step.  `b`: sample b alone -- slice b of every tensor, row b of every per-sample map (B = 1).
+        A gated step (st.thr) ends in sinddm_reverse_step_keep_gate; the pull, jump and multistep entries take no threshold
+        and get the step's own mask (hold level >= st.thr) as 0 / 1, which is what the gate hands the chain's kernels."""
         lib, xt, g = _lib.load(), plan.xt, st.g
         ew, ec = plan.roi if plan.roi is not None else (None, None)
         km, kx = plan.keep if plan.keep is not None else (None, None)
@@ -1428,6 +1448,9 @@ class MultiScaleGaussianDiffusion(nn.Module):
             ew, km, ec, kx, lay = row(ew, 2), row(km, 2), row(ec, 3), row(kx, 3), row(lay, 3)
             if plan.gain is not None:                          # (the strength the chain's kernel forms: the fp32 product)
                 g = float(np.float32(g) * plan.gain[b])
+        gate_entry = st.thr is not None and lay is None and st.jump is None and hist is None
+        if st.thr is not None and not gate_entry:
+            km = (km >= st.thr).to(km.dtype).contiguous()      # (an fp32 compare: st.thr is an fp32 value)
         B_, C_, H_, W_ = x.shape
         head = [_lib.ptr(v) for v in (x, eps, xt, z, out)] + [C.byref(st.k)]
         maps = [_lib.ptr(ew), _lib.ptr(ec), _lib.ptr(km), _lib.ptr(kx), *st.ab]
@@ -1443,6 +1466,8 @@ class MultiScaleGaussianDiffusion(nn.Module):
             name, args = "sinddm_reverse_step_jump", [*head[:4], _lib.ptr(z2), *head[4:], C.byref(st.jump), *maps, *shp]
         elif hist is not None:
             name, args = "sinddm_reverse_step_ms", [*head, st.q, _lib.ptr(hist), *maps, *shp]
+        elif gate_entry:
+            name, args = "sinddm_reverse_step_keep_gate", [*head, *maps, *shp, st.thr]
         elif km is not None:
             name, args = "sinddm_reverse_step_keep", [*head, *maps, *shp]
         elif ew is not None:

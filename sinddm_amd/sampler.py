@@ -11,12 +11,14 @@ from types import SimpleNamespace
 from typing import Optional, Tuple
 
 from . import _lib
-from .functions import layout_strengths, resample_schedule, stride_schedule
+from .functions import gate_thresholds, layout_strengths, resample_schedule, stride_schedule
 
 # The combinations of options that are not built, (option, the option it cannot go with) -> what NotImplementedError says.
 NOT_BUILT = {
     ("keep_maps", "clip"): "keep_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has no "
                            "known-region replacement",
+    ("keep_gated", "clip"): "keep_gated with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has no "
+                            "known-region replacement to gate",
     ("layout_maps", "clip"): "layout_maps with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has no "
                              "layout pull",
     ("resample", "clip"): "resample with clip_guided_sampling: the CLIP-guided step runs in eager torch ops and has no "
@@ -53,15 +55,18 @@ class Step:
     jump: Optional[_lib.JumpCoefs]
     g: float                                   # strength of the layout pull (0: the step is not conditioned)
     q: Optional[float]                         # multistep factor (None: a first-order run)
+    thr: Optional[float] = None                # gate threshold in (0, 1], an fp32 value (None: the run is not gated)
 
 
 class RunPlan:
-    """The reverse steps `t_seq` of scale s on `img` with the options `d` carries; `at` = (step_pos, jump_to, land, q) makes it
-    the plan of the ONE step `t_seq = [t]` as `_p_sample_host_t` is handed it, else the schedule is resolved from `d`.
+    """The reverse steps `t_seq` of scale s on `img` with the options `d` carries; `at` = (step_pos, jump_to, land, q[, t_top])
+    makes it the plan of the ONE step `t_seq = [t]` as `_p_sample_host_t` is handed it (`t_top`: the highest level of the run the
+    step belongs to, which a gated step needs), else the schedule is resolved from `d`.
     Attributes: `steps` (the records), `t_seq` / `jump_to` (the expanded walk; `jump_to` None without resampling), `halo`,
     `roi` (ew, ec) / `keep` (mask, x0) / `lay` (layout, N, strength, t_min) or None each, `per` (which of edit, keep mask, keep x0,
-    layout hold a slice per sample), `gain` (fp32 numpy or None), `xt` (x-tilde or None), `order2`, `noise` (kind, payload) with
-    kind 'recorded' / 'seeds' / 'mix' / 'torch' (None for a single step: its caller draws).
+    layout hold a slice per sample), `gain` (fp32 numpy or None), `xt` (x-tilde or None), `order2`, `gated` (`keep_gated`: every
+    record carries `thr`, functions.gate_thresholds of its `land` and the run's top level before any resampling expansion),
+    `noise` (kind, payload) with kind 'recorded' / 'seeds' / 'mix' / 'torch' (None for a single step: its caller draws).
 
     Everything is validated here, in this order; each reader raises ValueError for a malformed option, SinddmError for a map
     that does not match `img`, and NotImplementedError (NOT_BUILT) where noted:
@@ -70,14 +75,17 @@ class RunPlan:
       3. `_layout_entry` (with CLIP, resample); the entry is dropped when no step of the run pulls; then with order 2 / a jump
       4. `_resample_cfg` (with CLIP), then functions.resample_schedule
       5. `_seeds_for`, `_mix_for` (with CLIP): the noise source
-      6. `_keep_entry` (with CLIP)
+      6. `keep_gated` (with CLIP), `_keep_entry` (with CLIP); `keep_gated` without keep maps for the scale, or on a single
+         step without `t_top`: ValueError
       7. `roi_edit_maps` and its batch, `_layout_gain_for`
       8. the per-step scalars; x-tilde must be set when a step reads it"""
 
     def __init__(self, d, img, s: int, t_seq, *, at=None, clip_denoised: bool = True):
         s, t_seq = int(s), [int(t) for t in t_seq]
         B, clip = int(img.shape[0]), bool(d.clip_guided_sampling)
-        pos0, j, land, q1 = at if at is not None else (0, None, None, None)
+        pos0, j, land, q1, t_top = (tuple(at) + (None,))[:5] if at is not None else (0, None, None, None, None)
+        if at is None and t_seq:
+            t_top = max(t_seq)                                 # (of the run as handed over: before striding and resampling)
         if land is not None or q1 is not None:
             refuse(d, "strided_step", "clip_or_jump", clip or j is not None)
         if j is not None:
@@ -103,7 +111,14 @@ class RunPlan:
             seeds, mix = d._seeds_for(s, B), d._mix_for(s, B)
             self.noise = (("recorded", None) if d.noise_fn is not None else ("seeds", seeds) if seeds is not None
                           else ("mix", mix) if mix is not None else ("torch", None))
+        gated = bool(d.keep_gated)
+        if gated:
+            refuse(d, "keep_gated", "clip")
         keep = d._keep_entry(s, img)
+        if gated and keep is None:
+            raise ValueError(f"keep_gated without keep_maps for scale {s}: there is no known region to gate")
+        if gated and t_seq and t_top is None:
+            raise ValueError("keep_gated: a single step needs t_top, the highest level of its run")
         roi = None
         if d.roi_guided_sampling and s < d.n_scales - 1 and not clip:       # models.py:430-431 (the CLIP step edits on its own)
             roi = d.roi_edit_maps(s, int(img.shape[-2]), int(img.shape[-1]), img.device)
@@ -116,9 +131,12 @@ class RunPlan:
                     int(keep is not None and keep[1].dim() == 4), int(lay is not None and lay[0].dim() == 4))
         tab, jt = d._coef_table(s, clip_denoised), d._jump_table(s) if jump_to is not None else None
         ab_tab = d._keep_ab_table() if keep is not None else None
+        self.gated = gated
+        lands_all = [t - 1 for t in t_seq] if lands is None else list(lands)
+        thr = gate_thresholds(lands_all, t_top) if gated and t_seq else None
         self.steps = []
         for i, t in enumerate(t_seq):
-            u = t - 1 if lands is None else lands[i]
+            u = lands_all[i]
             l2 = jump_to[i] if jump_to is not None else None
             self.steps.append(Step(
                 pos=pos0 + i, t=t, land=u,
@@ -126,7 +144,8 @@ class RunPlan:
                 # (row l + 1 holds the forward scalars of level l, row 0 those of the clean image)
                 ab=tuple(float(v) for v in ab_tab[u + 1]) if keep is not None else (1.0, 0.0),
                 jump_to=l2, jump=_lib.JumpCoefs(1, *jt(t - 1, l2)) if l2 is not None else None,
-                g=g[i] if lay is not None else 0.0, q=q[i] if q is not None else None))
+                g=g[i] if lay is not None else 0.0, q=q[i] if q is not None else None,
+                thr=float(thr[i]) if thr is not None else None))
         self.xt = None
         if not clip and any(st.k.mode != 0 for st in self.steps):
             if d.img_prev_upsample is None:
@@ -150,7 +169,7 @@ class RunPlan:
 
 def pack_steps(plan: RunPlan, i0: int, k: int):
     """The host arrays of the steps [i0, i0 + k) of `plan` as a chain call takes them: `coefs`, `tl`, and `ab` (2 per step), `jumps`,
-    `g`, `q` -- None each when the run does not have the option."""
+    `g`, `q`, `thr` -- None each when the run does not have the option."""
     st = plan.steps[i0:i0 + k]
     arr = lambda ctype, vals: (ctype * len(vals))(*vals)
     return SimpleNamespace(
@@ -159,4 +178,5 @@ def pack_steps(plan: RunPlan, i0: int, k: int):
         jumps=arr(_lib.JumpCoefs, [_lib.JumpCoefs(0, 0.0, 0.0, 0.0) if r.jump is None else r.jump for r in st])
         if plan.jump_to is not None else None,
         g=arr(C.c_float, [r.g for r in st]) if plan.lay is not None else None,
-        q=arr(C.c_float, [r.q for r in st]) if plan.order2 else None)
+        q=arr(C.c_float, [r.q for r in st]) if plan.order2 else None,
+        thr=arr(C.c_float, [r.thr for r in st]) if plan.gated else None)

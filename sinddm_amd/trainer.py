@@ -679,6 +679,58 @@ class MultiscaleTrainer(object):
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
                                  seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix)
 
+    # ---- per-pixel edit strength: every pixel its own SDEdit start level (no reference counterpart) ----
+    @torch.no_grad()
+    def edit(self, strength, image=None, batch_size=16, scale_mul=(1, 1), custom_t_list=None, seeds=None,
+             vary_from_scale=None, seed_mix=None, resample=1, jump_length=1, save_unbatched=False, save_images=True):
+        """Edit a picture with a strength per pixel: `strength` is (H, W) in [0, 1] at the finest target size
+        (`ema_model.target_size(n_scales - 1, scale_mul)`), 0 = leave the pixel alone, 1 = redraw it from scratch, c in
+        between = re-noise it to the share c of the scale's levels and let the model take it from there (SDEdit with a start
+        level per pixel).  `image` is the (3, H, W) picture in [-1, 1] being edited; None: the training image of every scale
+        (`data_list`, as `inpaint` uses it; `scale_mul` must then be (1, 1)).  The picture reaches the scales by area averaging
+        (`functions._layout_pyramid`), the strength as the hold level 1 - strength (`functions.hold_pyramid`).  At every
+        scale a reverse step that lands on level u keeps -- overwrites with the forward-diffused picture of level u, as
+        `inpaint` does -- the pixels with strength <= (u + 1) / (t_top + 1) and leaves the others to the model
+        (`ema_model.keep_maps` + `keep_gated` -> `sinddm_gate_opts` of the chain call: still one library call per scale).  A
+        {0, 1} map is `inpaint(1 - strength)` bit for bit.  `resample` / `jump_length`: as for `inpaint` (after a jump back up
+        a released pixel is pinned again until the run is back at its level).  No image-quality claim is made.
+        `strength` may be (batch_size, H, W) and `image` (batch_size, 3, H, W): one job per sample (`sinddm_batch_opts`).
+        Returns the per-scale batches and writes PNGs like `sample_scales`."""
+        from .functions import _layout_pyramid, hold_pyramid
+        em, B = self.ema_model, int(batch_size)
+        st = torch.as_tensor(strength)
+        sizes = [tuple(em.target_size(s, scale_mul)) for s in range(self.n_scales)]
+        fine = sizes[-1]
+        if tuple(st.shape) not in (fine, (B,) + fine):
+            raise ValueError(f'edit: strength {tuple(st.shape)} is not the finest target size {fine} (or {B} of them)')
+        st = st.to(torch.float32)
+        if not bool(((st >= 0.0) & (st <= 1.0)).all()):
+            raise ValueError('edit: strength outside [0, 1]')
+        if image is None:
+            if tuple(float(v) for v in scale_mul) != (1.0, 1.0):
+                raise ValueError(f'edit: scale_mul {tuple(scale_mul)} needs an image (the training pyramid has its own sizes)')
+            known = [self.data_list[s][0][0].contiguous() for s in range(self.n_scales)]
+        else:
+            img = torch.as_tensor(image)
+            if tuple(img.shape) not in ((3,) + fine, (B, 3) + fine):
+                raise ValueError(f'edit: image {tuple(img.shape)} must be (3, {fine[0]}, {fine[1]}), the finest target size, '
+                                 f'or {B} of them')
+            img = img.to(torch.float32)
+            if not bool(((img >= -1.0) & (img <= 1.0)).all()):
+                raise ValueError('edit: image outside [-1, 1]')
+            known = [k.to(self.device).contiguous() for k in _layout_pyramid(img, sizes)]
+        holds = hold_pyramid(st, sizes, batch=st.dim() == 3)
+        maps = {s: (holds[s].to(self.device).contiguous(), known[s]) for s in range(self.n_scales)}
+        em.keep_gated = True
+        try:
+            # ((1, 1) goes in as `inpaint` hands it over: no scale_mul)
+            sm = {} if tuple(float(v) for v in scale_mul) == (1.0, 1.0) else {'scale_mul': tuple(scale_mul)}
+            return self._sample_kept(maps, 'edit', resample=resample, jump_length=jump_length, **sm, batch_size=batch_size, custom_t_list=custom_t_list, save_unbatched=save_unbatched,
+                                     save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale,
+                                     seed_mix=seed_mix)
+        finally:
+            em.keep_gated = False
+
     # ---- layout conditioning: redraw a rough picture in the training image's texture (no reference counterpart) ----
     @torch.no_grad()
     def paint2image(self, layout, batch_size=16, down=8, strength=1.0, t_min=0, scales=None, scale_mul=(1, 1), seeds=None,
