@@ -729,6 +729,40 @@ int sinddm_patch_nnf(const float* query, int q_per_sample, const float* ref, int
                      float* dist, int32_t* idx, int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same field ranked by a distance scaled per reference position (GPNN's completeness normalisation).  The arguments
+ * are those of sinddm_patch_nnf plus
+ *   ref_scale (B or 1, hr, wr) fp32: scale_per_sample != 0 -> one map per sample, 0 -> one map shared by the B samples.
+ * With r the ranking chain of sinddm_patch_nnf, na_i = |a_i|^2 = fmaf(a_k, a_k, .) over k from 0, t = r + na_i (ONE fp32
+ * add: the K padding slot of the chain carries na_i against a multiplier of 1, one further step of the same chain) and s_j
+ * the scale of position j, the ranking value is v = fmaxf(t, 0) * s_j (one fp32 multiply).  The winner is the admissible
+ * position with the smallest v, ties to the smallest idx; v does not depend on tile, wave, workgroup, reference split or B.
+ * dist is the UNSCALED distance of the winner, recomputed as sinddm_patch_nnf does; idx = -1 and dist = +inf when no
+ * position is admissible.  Precondition: every s_j is finite and > 0 (the caller checks; the entry does not read the map
+ * on the host).  ref_scale == NULL is sinddm_patch_nnf, bit for bit (either workspace size will do then).
+ * Refusals as sinddm_patch_nnf, against sinddm_patch_nnf_scaled_workspace_bytes (|a|^2 of every query on top). */
+size_t sinddm_patch_nnf_scaled_workspace_bytes(int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r);
+int sinddm_patch_nnf_scaled(const float* query, int q_per_sample, const float* ref, int r_per_sample, const float* ref_ok,
+                            const float* ref_scale, int scale_per_sample, float* dist, int32_t* idx, int B, int Hq, int Wq,
+                            int Hr, int Wr, int P, int wrap_q, int wrap_r, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* Patch vote (csrc/patch_vote.h): every pixel becomes the mean of the reference patches that the field puts over it.
+ *   idx    (B, hq, wq) int32: a field as sinddm_patch_nnf writes it (linear positions in the (hr, wr) reference grid; the
+ *          grids follow from the sizes, P and wrap_q / wrap_r as there).  An entry < 0 or >= hr wr names no patch.
+ *   ref    (B or 1, 3, Hr, Wr), r_per_sample as there;  base / out (B, 3, Hq, Wq)
+ *   weight (B or 1, Hq, Wq) fp32 or NULL: w_per_sample != 0 -> one map per sample
+ * For pixel (y, x) and channel c, over dy = 0 .. P-1 (outer) and dx = 0 .. P-1 (inner): the patch position (y - dy, x - dx)
+ * is taken modulo the size on a wrapped query axis and skipped when it lies outside the grid otherwise, or when its entry
+ * names no patch; else ref[c, ry + dy, rx + dx] with (ry, rx) = (idx / wr, idx % wr), modulo the size on a wrapped
+ * reference axis, is added: plain fp32 adds in that order, cnt counts them.  mean = sum / (float)cnt (correctly rounded),
+ * g = blend * weight[y, x] (blend alone without a map); g == 1 writes mean, g == 0 or cnt == 0 writes base, anything else
+ * fmaf(g, mean - base, base).  A gather without atomics: bit-reproducible.  out may alias base (a pixel reads only its own).
+ * SINDDM_E_BADARG (before any device work): a null idx / ref / base / out, B < 1, P outside {3, 5, 7}, a blend outside
+ * [0, 1] or not finite; SINDDM_E_BADSHAPE: an axis shorter than P, an image of 2^31 pixels or more. */
+int sinddm_patch_vote(const int32_t* idx, const float* ref, int r_per_sample, const float* base, const float* weight,
+                      int w_per_sample, float* out, int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r,
+                      float blend, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,12 @@ conditioned on its own maps inside the one chain call per scale.  One value is t
 batch the way `--mode sample` does (`--seeds`, `--tile`, `--scale_mul`, `--sample_steps` ... apply), computes the patch
 nearest-neighbour field between the batch of scale S (default: the finest) and that scale's training image in both
 directions, prints fidelity, coherence, coverage (and seam under `--tile`) and writes `patch_report.json` to the results folder.
+`--patch_refine ITERS` (no reference flag; `--mode sample` and `--mode evaluate` only) acts on that report: after the chain of
+every scale in `--patch_refine_scales A B` (default: all) the batch is snapped to that scale's training image by ITERS
+patch-vote iterations -- every `--patch_refine_patch {3,5,7}` patch is replaced by its nearest training patch and every pixel
+becomes the mean of the patches that cover it (the EM step of GPNN) -- before the next scale re-noises and redraws it.
+`--patch_refine_alpha A` ranks with GPNN's completeness normalisation D / (A 3P^2 + min D) (coverage in place of plain
+fidelity); `--patch_refine_blend B` in [0, 1] moves only the share B of the way.  Off by default.
 The CLIP-guided modes (clip_content, clip_style_*, clip_roi; main.py:153-255) are not wired to the command line: CLIP
 itself is outside this build.  Their drivers exist (`MultiscaleTrainer.clip_sampling` / `clip_roi_sampling`, the guidance
 branch of `p_mean_variance`) and take any scorer with the reference's ClipExtractor interface.
@@ -200,6 +206,12 @@ def build_parser():
     # no reference flags: the patch nearest-neighbour report of `evaluate` (MultiscaleTrainer.evaluate)
     p.add_argument("--eval_patch", type=int, choices=(3, 5, 7), default=7)
     p.add_argument("--eval_scale", type=int, default=None, metavar="S")
+    # no reference flags: patch-vote refinement between the scales (MultiscaleTrainer.sample_scales(patch_refine=...))
+    p.add_argument("--patch_refine", type=int, default=None, metavar="ITERS")
+    p.add_argument("--patch_refine_patch", type=int, choices=(3, 5, 7), default=7)
+    p.add_argument("--patch_refine_alpha", type=float, default=None, metavar="A")
+    p.add_argument("--patch_refine_blend", type=float, default=1.0, metavar="B")
+    p.add_argument("--patch_refine_scales", type=int, nargs=2, default=None, metavar=("A", "B"))
     return p
 
 
@@ -267,6 +279,26 @@ def parse_args(argv=None):
         p.error("--layout_scales A B needs 0 <= A <= B")
     if args.eval_scale is not None and args.eval_scale < 0:
         p.error("--eval_scale must be >= 0")
+    args.patch_refine_opt = None
+    if args.patch_refine is None:
+        if (args.patch_refine_patch != 7 or args.patch_refine_alpha is not None or args.patch_refine_blend != 1.0
+                or args.patch_refine_scales is not None):
+            p.error("--patch_refine_patch / _alpha / _blend / _scales need --patch_refine ITERS")
+    else:
+        if args.mode not in ("sample", "evaluate"):
+            p.error(f"--patch_refine goes with --mode sample and --mode evaluate, not with --mode {args.mode}")
+        if args.patch_refine < 1:
+            p.error("--patch_refine ITERS must be >= 1")
+        a, b = args.patch_refine_alpha, args.patch_refine_blend
+        if a is not None and not (a > 0.0 and a != float("inf")):
+            p.error("--patch_refine_alpha must be finite and > 0")
+        if not 0.0 <= b <= 1.0:
+            p.error("--patch_refine_blend must be in [0, 1]")
+        sc = args.patch_refine_scales
+        if sc is not None and not 0 <= sc[0] <= sc[1]:
+            p.error("--patch_refine_scales A B needs 0 <= A <= B")
+        args.patch_refine_opt = dict(iters=args.patch_refine, patch=args.patch_refine_patch, alpha=a, blend=b,
+                                     scales=None if sc is None else (sc[0], sc[1]))
     if args.mode == "edit" and not args.edit_map:
         p.error("--mode edit needs --edit_map FILE (a gray picture: white = redraw freely, black = keep the pixel)")
     return args
@@ -359,6 +391,8 @@ def main():
             raise SystemExit(f"--blend_from_scale {args.blend_from_scale} is past the {n_scales} scales")
         seed_kw = dict(seed_mix=mix_from_scale(args.seed_mix, args.blend_from_scale, n_scales) if args.blend_from_scale > 0
                        else args.seed_mix)
+    # (without --patch_refine the argument is not passed at all: the old command lines run the old call)
+    refine_kw = {} if args.patch_refine_opt is None else dict(patch_refine=args.patch_refine_opt)
     frames = None                                                          # the per-scale batches of the sampling modes
     if args.mode == 'train':
         trainer.train()
@@ -367,7 +401,7 @@ def main():
     elif args.mode == 'sample':
         frames = trainer.sample_scales(scale_mul=scale_mul, custom_sample=True, image_name=args.image_name,
                               batch_size=args.sample_batch_size, custom_t_list=sample_t_list, save_unbatched=True,
-                              **seed_kw)
+                              **refine_kw, **seed_kw)
     elif args.mode in ('style_transfer', 'harmonization'):                 # reference main.py:296-322
         i2i_folder = os.path.join(args.dataset_folder, 'i2i')
         start_s = n_scales - 1                                             # start the diffusion at the last scale
@@ -457,7 +491,7 @@ def main():
             raise SystemExit(f"--eval_scale {args.eval_scale} is past the {n_scales} scales")
         report = trainer.evaluate(batch_size=args.sample_batch_size, scale=args.eval_scale, patch=args.eval_patch,
                                   scale_mul=scale_mul, custom_sample=True, image_name=args.image_name,
-                                  custom_t_list=sample_t_list, **seed_kw)
+                                  custom_t_list=sample_t_list, **refine_kw, **seed_kw)
         if rank == 0:
             for name in ("fidelity", "coherence", "coverage", "seam"):
                 if name + "_mean" in report:

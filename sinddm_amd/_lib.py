@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "sinddm_patch_nnf_workspace_bytes", "sinddm_patch_nnf",
     "sinddm_q_sample_crop", "sinddm_l1_loss_rect_fwd_bwd",
     "sinddm_sample_chain_gate", "sinddm_reverse_step_keep_gate",
+    "sinddm_patch_nnf_scaled_workspace_bytes", "sinddm_patch_nnf_scaled", "sinddm_patch_vote",
 )
 
 
@@ -225,6 +226,9 @@ def load() -> C.CDLL:
         "sinddm_adam_ema_step": (i, [p, p, p, p, p, f, f, f, f, f, f, f, i, i64, p]),
         "sinddm_patch_nnf_workspace_bytes": (sz, [i, i, i, i, i, i, i, i]),
         "sinddm_patch_nnf": (i, [p, i, p, i, p, p, p, i, i, i, i, i, i, i, i, p, sz, p]),
+        "sinddm_patch_nnf_scaled_workspace_bytes": (sz, [i, i, i, i, i, i, i, i]),
+        "sinddm_patch_nnf_scaled": (i, [p, i, p, i, p, p, i, p, p, i, i, i, i, i, i, i, i, p, sz, p]),
+        "sinddm_patch_vote": (i, [p, p, i, p, p, i, p, i, i, i, i, i, i, i, i, f, p]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name):

@@ -24,6 +24,10 @@
 #define SINDDM_NNF_QB 4       // with four independent accumulators; 1 / 2 leave registers for two waves per SIMD
 #endif
 
+#ifndef SINDDM_NNF_QB_SCALED  // the scaled search's own: P = 7 at QB = 4 has no register left for the staged scale
+#define SINDDM_NNF_QB_SCALED(P) ((P) == 7 ? 3 : 4)
+#endif
+
 namespace sinddm {
 namespace nnf {
 
@@ -82,6 +86,23 @@ __global__ __launch_bounds__(256) void nnf_prepare_kernel(const float* __restric
     nb[i] = acc;
 }
 
+// |a|^2 of every query position, an fmaf chain in k order (the scaled ranking's third term)
+template <int P>
+__global__ __launch_bounds__(256) void nnf_qnorm_kernel(const float* __restrict__ query, float* __restrict__ na, int Hq, int Wq,
+                                                        int wq, long long Mq, long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int s = (int)(i / Mq), m = (int)(i - (long long)s * Mq);
+    const float* img = query + (size_t)s * 3 * Hq * Wq;
+    const int y = m / wq, x = m - y * wq;
+    float acc = 0.0f;
+    for (int k = 0; k < Geo<P>::K; ++k) {
+        const float a = patch_elem<P>(img, Hq, Wq, y, x, k);
+        acc = fmaf(a, a, acc);
+    }
+    na[i] = acc;
+}
+
 template <int P>
 __global__ __launch_bounds__(256) void nnf_finish_kernel(const float* __restrict__ query, int q_per_sample,
                                                          const float* __restrict__ ref, int r_per_sample,
@@ -111,14 +132,22 @@ __global__ __launch_bounds__(256) void nnf_finish_kernel(const float* __restrict
 }
 
 // grid (query tiles, reference splits, B).  Chunk c of the reference is position row c / ncx, positions (c % ncx) XT ...
-template <int P, int QB>
+// SC (the scaled ranking of sinddm_patch_nnf_scaled): K = 3 P^2 is 3 mod 4 for every odd P, so the A fragment has exactly one
+// padding slot (lane group 3 of the last k step) and the B fragment reads the padding row for it.  With |a|^2 in the slot
+// and ones in the row the accumulator ends as fl(r + |a|^2) with no further instruction; the epilogue clamps it at 0 and
+// multiplies by the scale of the tile's column, staged behind |b|^2.  `na` is |a|^2 per query, `sc` the scale per position.
+template <int P, int QB, bool SC = false>
 __global__ __launch_bounds__(THREADS, QB <= 2 ? 2 : 1) void nnf_search_kernel(const float* __restrict__ query, int q_per_sample,
                                                              const float* __restrict__ ref, int r_per_sample,
                                                              const float* __restrict__ nb, unsigned long long* __restrict__ keys,
                                                              int Hq, int Wq, int Hr, int Wr, int wq, int Mq, int wr, int N,
-                                                             int ncx, int nchunks, int chunks_per_split) {
+                                                             int ncx, int nchunks, int chunks_per_split,
+                                                             const float* __restrict__ na = nullptr,
+                                                             const float* __restrict__ sc = nullptr, int s_per_sample = 0) {
     using G = Geo<P>;
-    __shared__ float lds[2 * G::BUF];
+    static_assert(G::K % 4 == 3, "one padding slot");
+    constexpr int BUF = G::BUF + (SC ? XT : 0);        // + the scales of the chunk's positions
+    __shared__ float lds[2 * BUF];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
     const int sample = blockIdx.z;
@@ -142,6 +171,9 @@ __global__ __launch_bounds__(THREADS, QB <= 2 ? 2 : 1) void nnf_search_kernel(co
             const int k = 4 * s + g;
             a[qb][s] = k < G::K ? -2.0f * patch_elem<P>(qimg, Hq, Wq, yq, xq, k) : 0.0f;
         }
+        if constexpr (SC) {
+            if (g == 3) a[qb][G::NS - 1] = na[(q_per_sample ? (size_t)sample * Mq : 0) + m];
+        }
     }
     float best[QB][4];
     int bidx[QB][4];
@@ -155,6 +187,9 @@ __global__ __launch_bounds__(THREADS, QB <= 2 ? 2 : 1) void nnf_search_kernel(co
 
     // ---- staging of a chunk: global -> registers (before the multiply), registers -> LDS (after it) ----
     float st[G::NLOAD], st_nb = 0.0f;
+    [[maybe_unused]] float st_sc = 1.0f;
+    [[maybe_unused]] const float* scs = nullptr;
+    if constexpr (SC) scs = sc + (s_per_sample ? (size_t)sample * N : 0);
     auto fetch = [&](int c) {
         const int y = c / ncx, x0 = (c - y * ncx) * XT;
 #pragma unroll
@@ -173,6 +208,9 @@ __global__ __launch_bounds__(THREADS, QB <= 2 ? 2 : 1) void nnf_search_kernel(co
             st[i] = v;
         }
         if (tid < XT) st_nb = (x0 + tid < wr) ? nbs[(size_t)y * wr + x0 + tid] : __builtin_inff();
+        if constexpr (SC) {
+            if (tid < XT) st_sc = (x0 + tid < wr) ? scs[(size_t)y * wr + x0 + tid] : 1.0f;
+        }
     };
     auto stash = [&](float* buf) {
 #pragma unroll
@@ -182,11 +220,14 @@ __global__ __launch_bounds__(THREADS, QB <= 2 ? 2 : 1) void nnf_search_kernel(co
             if (e < G::ROWS * G::COLS) buf[row * G::RS + col] = st[i];
         }
         if (tid < XT) buf[G::STRIP + tid] = st_nb;
+        if constexpr (SC) {
+            if (tid < XT) buf[G::BUF + tid] = st_sc;
+        }
     };
 
-    for (int i = tid; i < G::RS; i += THREADS) {       // the zero row of both buffers, written once
-        lds[G::ROWS * G::RS + i] = 0.0f;
-        lds[G::BUF + G::ROWS * G::RS + i] = 0.0f;
+    for (int i = tid; i < G::RS; i += THREADS) {       // the padding row of both buffers, written once: zeros (SC: ones)
+        lds[G::ROWS * G::RS + i] = SC ? 1.0f : 0.0f;
+        lds[BUF + G::ROWS * G::RS + i] = SC ? 1.0f : 0.0f;
     }
     fetch(c_begin);
     stash(lds);
@@ -199,13 +240,15 @@ __global__ __launch_bounds__(THREADS, QB <= 2 ? 2 : 1) void nnf_search_kernel(co
     for (int th = 1; th < 4; ++th) sel[th] = j + g + (g >= th ? G::RS - P : 0);
 
     for (int c = c_begin; c < c_end; ++c) {
-        const float* buf = lds + ((c - c_begin) & 1) * G::BUF;
+        const float* buf = lds + ((c - c_begin) & 1) * BUF;
         if (c + 1 < c_end) fetch(c + 1);
         const int y = c / ncx, x0 = (c - y * ncx) * XT;
 #pragma unroll
         for (int t = 0; t < XT / 16; ++t) {
             if (x0 + t * 16 >= wr) break;
             const float nbv = buf[G::STRIP + t * 16 + j];
+            [[maybe_unused]] float scv = 1.0f;
+            if constexpr (SC) scv = buf[G::BUF + t * 16 + j];
             f32x4 acc[QB];
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb) acc[qb] = f32x4{nbv, nbv, nbv, nbv};
@@ -222,13 +265,14 @@ __global__ __launch_bounds__(THREADS, QB <= 2 ? 2 : 1) void nnf_search_kernel(co
             for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float r = acc[qb][e];
+                    float r = acc[qb][e];
+                    if constexpr (SC) r = fmaxf(r, 0.0f) * scv;   // an inadmissible position stays +inf: the scale is > 0
                     const bool lt = r < best[qb][e];   // strict: of equal values the first, i.e. the smallest idx, stays
                     best[qb][e] = lt ? r : best[qb][e];
                     bidx[qb][e] = lt ? n : bidx[qb][e];
                 }
         }
-        if (c + 1 < c_end) stash(lds + ((c + 1 - c_begin) & 1) * G::BUF);
+        if (c + 1 < c_end) stash(lds + ((c + 1 - c_begin) & 1) * BUF);
         __syncthreads();
     }
 
@@ -267,11 +311,21 @@ inline size_t workspace_bytes(int B, int Hq, int Wq, int Hr, int Wr, int P, int 
     return align256((size_t)B * hr * wr * sizeof(float)) + align256((size_t)B * hq * wq * sizeof(unsigned long long));
 }
 
-template <int P>
+// the scaled search adds |a|^2 of every query position behind the keys
+inline size_t workspace_bytes_scaled(int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r) {
+    const size_t base = workspace_bytes(B, Hq, Wq, Hr, Wr, P, wrap_q, wrap_r);
+    if (!base) return 0;
+    long long hq, wq;
+    geometry(Hq, Wq, P, wrap_q, &hq, &wq);
+    return base + align256((size_t)B * hq * wq * sizeof(float));
+}
+
+// SC: `ref_scale` (s_per_sample ? B : 1, hr, wr) ranks by max(r + |a|^2, 0) * scale; the workspace is the scaled one
+template <int P, bool SC = false>
 int launch(const float* query, int q_per_sample, const float* ref, int r_per_sample, const float* ref_ok, float* dist,
            int32_t* idx, int B, int Hq, int Wq, int Hr, int Wr, int hq, int wq, int hr, int wr, void* workspace,
-           hipStream_t st) {
-    constexpr int QB = SINDDM_NNF_QB;
+           hipStream_t st, const float* ref_scale = nullptr, int s_per_sample = 0) {
+    constexpr int QB = SC ? SINDDM_NNF_QB_SCALED(P) : SINDDM_NNF_QB;
     const int Mq = hq * wq, N = hr * wr;
     float* nb = (float*)workspace;
     unsigned long long* keys = (unsigned long long*)((char*)workspace + align256((size_t)B * N * sizeof(float)));
@@ -280,6 +334,13 @@ int launch(const float* query, int q_per_sample, const float* ref, int r_per_sam
     nnf_prepare_kernel<P><<<dim3((unsigned)((n_prep + 255) / 256)), dim3(256), 0, st>>>(ref, ref_ok, nb, keys, Hr, Wr, hr, wr,
                                                                                          n_nb, n_keys);
     SINDDM_LAUNCH_CHECK();
+    [[maybe_unused]] float* na = nullptr;
+    if constexpr (SC) {
+        na = (float*)((char*)keys + align256((size_t)B * Mq * sizeof(unsigned long long)));
+        const long long n_na = (long long)(q_per_sample ? B : 1) * Mq;
+        nnf_qnorm_kernel<P><<<dim3((unsigned)((n_na + 255) / 256)), dim3(256), 0, st>>>(query, na, Hq, Wq, wq, Mq, n_na);
+        SINDDM_LAUNCH_CHECK();
+    }
     const int qtiles = (Mq + 64 * QB - 1) / (64 * QB);
     const int ncx = (wr + XT - 1) / XT, nchunks = hr * ncx;
     // split the reference over workgroups until the device has two rounds of them (65535: the grid's y / z limit)
@@ -290,10 +351,11 @@ int launch(const float* query, int q_per_sample, const float* ref, int r_per_sam
     splits = (nchunks + per - 1) / per;
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb_ = B - b0 < 65535 ? B - b0 : 65535;
-        nnf_search_kernel<P, QB><<<dim3(qtiles, splits, nb_), dim3(THREADS), 0, st>>>(
+        nnf_search_kernel<P, QB, SC><<<dim3(qtiles, splits, nb_), dim3(THREADS), 0, st>>>(
             query + (q_per_sample ? (size_t)b0 * 3 * Hq * Wq : 0), q_per_sample, ref + (r_per_sample ? (size_t)b0 * 3 * Hr * Wr : 0),
             r_per_sample, nb + (r_per_sample ? (size_t)b0 * N : 0), keys + (size_t)b0 * Mq, Hq, Wq, Hr, Wr, wq, Mq, wr, N, ncx,
-            nchunks, per);
+            nchunks, per, SC ? na + (q_per_sample ? (size_t)b0 * Mq : 0) : nullptr,
+            SC ? ref_scale + (s_per_sample ? (size_t)b0 * N : 0) : nullptr, s_per_sample);
         SINDDM_LAUNCH_CHECK();
     }
     nnf_finish_kernel<P><<<dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, st>>>(query, q_per_sample, ref, r_per_sample, keys,

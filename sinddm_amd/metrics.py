@@ -46,10 +46,12 @@ def position_ok(valid: torch.Tensor, patch: int, wrap: Sequence[bool]) -> torch.
 
 
 def patch_nnf(query: torch.Tensor, ref: torch.Tensor, patch: int = 7, wrap_query=(False, False), wrap_ref=(False, False),
-              ref_valid: Optional[torch.Tensor] = None):
+              ref_valid: Optional[torch.Tensor] = None, ref_scale: Optional[torch.Tensor] = None):
     """Nearest reference patch of every query patch.  `query` (B or 1, 3, Hq, Wq) and `ref` (B or 1, 3, Hr, Wr) are fp32
     device tensors (a batch of 1 is shared by the samples of the other); `wrap_*` = (y, x) says which axes wrap around;
     `ref_valid` is an (Hr, Wr) pixel map, 1 = usable: a reference position is admissible iff all P x P pixels of its patch are.
+    `ref_scale` (B or 1, hr, wr) fp32, finite and > 0: rank by max(d, 0) * ref_scale[position] instead of by d
+    (`sinddm_patch_nnf_scaled`: GPNN's completeness normalisation); `dist` stays the unscaled distance of the winner.
     Returns (dist (B, hq, wq) fp32: the squared distance to the winner, yx (B, 2, hq, wq) int32: its position)."""
     for name, t in (("query", query), ("ref", ref)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -75,6 +77,8 @@ def patch_nnf(query: torch.Tensor, ref: torch.Tensor, patch: int = 7, wrap_query
         ok = position_ok(ref_valid.to(ref.device), patch, wrap_ref)
         if not bool(ok.any()):
             raise SinddmError("patch_nnf: ref_valid leaves no admissible reference position")
+    if ref_scale is not None:
+        return _patch_nnf_scaled(query, ref, patch, wrap_query, wrap_ref, ok, ref_scale, B, (hq, wq), (hr, wr))
     lib = _lib.load()
     wq_bits, wr_bits = _wrap_bits(wrap_query), _wrap_bits(wrap_ref)
     nbytes = lib.sinddm_patch_nnf_workspace_bytes(B, Hq, Wq, Hr, Wr, patch, wq_bits, wr_bits)
@@ -88,6 +92,47 @@ def patch_nnf(query: torch.Tensor, ref: torch.Tensor, patch: int = 7, wrap_query
                                   _lib.ptr(idx), B, Hq, Wq, Hr, Wr, patch, wq_bits, wr_bits, _lib.ptr(ws), nbytes,
                                   _lib.stream_ptr(query.device))
     _lib.check(rc, "sinddm_patch_nnf")
+    yx = torch.stack([torch.div(idx, wr, rounding_mode="floor"), idx % wr], dim=1).to(torch.int32)
+    return dist, yx
+
+
+def check_ref_scale(ref_scale, B: int, ref_grid: Sequence[int]) -> torch.Tensor:
+    """The precondition of `sinddm_patch_nnf_scaled`, checked here because the entry cannot: a float32 (B or 1, hr, wr) (or
+    (hr, wr)) map whose every entry is finite and > 0.  Returns it with the batch dimension."""
+    hr, wr = ref_grid
+    if not isinstance(ref_scale, torch.Tensor) or ref_scale.dtype != torch.float32:
+        raise SinddmError("patch_nnf: ref_scale must be a float32 tensor")
+    if ref_scale.dim() == 2:
+        ref_scale = ref_scale[None]
+    if ref_scale.dim() != 3 or tuple(ref_scale.shape[1:]) != (hr, wr) or ref_scale.shape[0] not in (1, B):
+        raise SinddmError(f"patch_nnf: ref_scale must be (B or 1, {hr}, {wr}), got {tuple(ref_scale.shape)}")
+    if not bool((torch.isfinite(ref_scale) & (ref_scale > 0)).all()):
+        raise SinddmError("patch_nnf: every ref_scale must be finite and > 0")
+    return ref_scale
+
+
+def _patch_nnf_scaled(query, ref, patch, wrap_query, wrap_ref, ok, ref_scale, B, qgrid, rgrid):
+    """The scaled route of `patch_nnf` (arguments already checked there)."""
+    (hq, wq), (hr, wr) = qgrid, rgrid
+    ref_scale = check_ref_scale(ref_scale, B, (hr, wr))
+    if ref_scale.device != query.device:
+        raise SinddmError("patch_nnf: ref_scale must be on the device of query")
+    ref_scale = ref_scale.contiguous()
+    Hq, Wq, Hr, Wr = query.shape[2], query.shape[3], ref.shape[2], ref.shape[3]
+    lib = _lib.load()
+    wq_bits, wr_bits = _wrap_bits(wrap_query), _wrap_bits(wrap_ref)
+    nbytes = lib.sinddm_patch_nnf_scaled_workspace_bytes(B, Hq, Wq, Hr, Wr, patch, wq_bits, wr_bits)
+    if nbytes == 0:
+        raise SinddmError(f"patch_nnf: unsupported shape {(B, Hq, Wq)} against {(Hr, Wr)}")
+    with torch.cuda.device(query.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+        dist = torch.empty(B, hq, wq, dtype=torch.float32, device=query.device)
+        idx = torch.empty(B, hq, wq, dtype=torch.int32, device=query.device)
+        rc = lib.sinddm_patch_nnf_scaled(_lib.ptr(query), int(query.shape[0] == B), _lib.ptr(ref), int(ref.shape[0] == B),
+                                         _lib.ptr(ok), _lib.ptr(ref_scale), int(ref_scale.shape[0] == B and B > 1),
+                                         _lib.ptr(dist), _lib.ptr(idx), B, Hq, Wq, Hr, Wr, patch, wq_bits, wr_bits,
+                                         _lib.ptr(ws), nbytes, _lib.stream_ptr(query.device))
+    _lib.check(rc, "sinddm_patch_nnf_scaled")
     yx = torch.stack([torch.div(idx, wr, rounding_mode="floor"), idx % wr], dim=1).to(torch.int32)
     return dist, yx
 

@@ -31,6 +31,11 @@ NOT_BUILT = {
     ("layout_maps", "resample"): "layout_maps with resample: the layout pull inside a resampling jump is not built",
     ("layout_maps", "solver_order"): "solver_order = 2 with layout_maps: the multistep step through a layout pull is not built",
     ("strided_step", "clip_or_jump"): "a strided or multistep step under CLIP guidance or before a resampling jump",
+    ("patch_refine", "keep_maps"): "patch_refine with keep_maps: a vote that respects the known region is not built "
+                                   "(MultiscaleTrainer.refine takes a weight map)",
+    ("patch_refine", "layout_maps"): "patch_refine with layout_maps: the vote between the scales of a layout-conditioned run "
+                                     "is not built",
+    ("patch_refine", "roi"): "patch_refine with ROI guidance: the vote between the scales of an ROI-guided run is not built",
 }
 _ON = {"clip": lambda d: d.clip_guided_sampling, "resample": lambda d: d._resample_cfg() is not None}
 

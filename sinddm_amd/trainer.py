@@ -322,7 +322,7 @@ class MultiscaleTrainer(object):
     def sample_scales(self, scale_mul=None, batch_size=16, custom_sample=False, custom_image_size_idxs=None,
                       custom_scales=None, image_name='', start_noise=True, custom_t_list=None, desc=None,
                       save_unbatched=True, save_images=True, seeds=None, vary_from_scale=None,
-                      seed_mix=None) -> List[torch.Tensor]:
+                      seed_mix=None, patch_refine=None) -> List[torch.Tensor]:
         """Drive the sampler over all scales (behaviour of reference trainer.py:226-285).  Under torch.distributed the
         batch is sharded over ranks as independent chains and gathered with one all-gather per scale (RCCL over xGMI
         on MI355X); returns the list of per-scale (global) sample batches.
@@ -333,8 +333,22 @@ class MultiscaleTrainer(object):
         too: `batch_size` rows, of which a rank takes its own shard's for the duration of the call (`dist.shard_rows`).
         `seed_mix`: in place of `seeds`, the GLOBAL blend tables (keys, weights), [batch_size][K] or
         [n_scales][batch_size][K] (`ema_model.seed_mix` for the duration of the call; `models.interp_seeds`, `loop_seeds`,
-        `mix_from_scale`): sample b is frame b, and a rank takes the rows of its own shard like its seeds."""
+        `mix_from_scale`): sample b is frame b, and a rank takes the rows of its own shard like its seeds.
+        `patch_refine`: a `refine.PatchRefine` or a dict of its fields (`iters`, `patch`, `alpha`, `blend`, `scales` = (a, b)).
+        After the chain of every scale in [a, b] the rank's own shard is snapped to that scale's training image by `iters`
+        field-and-vote iterations (`refine.patch_refine`; wrapped axes as `ema_model.tile`, holes of `train_mask` never
+        copied from) before it is gathered and before the next scale upsamples it.  The iterations are independent per
+        sample, so a sharded run makes the images of the single process.  With `keep_maps`, `layout_maps` or ROI guidance
+        on `ema_model` it raises NotImplementedError (`sampler.NOT_BUILT`)."""
         em = self.ema_model
+        if patch_refine is not None:
+            from .refine import PatchRefine
+            from .sampler import NOT_BUILT
+            patch_refine = PatchRefine.of(patch_refine)
+            for other, on in (('keep_maps', em.keep_maps is not None), ('layout_maps', em.layout_maps is not None),
+                              ('roi', bool(em.roi_guided_sampling))):
+                if on:
+                    raise NotImplementedError(NOT_BUILT['patch_refine', other])
         local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=True)
         local_mix = self._local_mix(seed_mix, seeds, batch_size, sharded=True)
         local_maps = self._local_batch_maps(batch_size)
@@ -380,6 +394,9 @@ class MultiscaleTrainer(object):
                 else:                                   # start from the training image of that scale instead of noise
                     seed_img = Image.open(self.input_paths[s] + '/' + image_name).convert('RGB')
                     cur = image_to_tensor(seed_img).repeat(mine, 1, 1, 1).to(self.device)
+                if patch_refine is not None and patch_refine.covers(s):
+                    cur = self.refine(cur, scale=s, patch=patch_refine.patch, iters=patch_refine.iters,
+                                      alpha=patch_refine.alpha, blend=patch_refine.blend)[0]
                 whole = sdist.gather_batch(cur, batch_size)          # identity on a single process
                 per_scale.append(whole)
                 if writer:
@@ -421,6 +438,26 @@ class MultiscaleTrainer(object):
             with open(str(self.results_folder / 'patch_report.json'), 'w') as f:
                 json.dump(report, f, indent=1)
         return report
+
+    @torch.no_grad()
+    def refine(self, samples=None, scale=None, **kw):
+        """Snap a batch to the training image's patches: `refine.patch_refine` of the batch of `scale` (default: the finest)
+        against that scale's training image, with `ema_model.tile` as the wrapped axes and the hard `train_mask` as `valid`
+        (a hole is never copied from).  `samples`: a batch, or the list `sample_scales` returns; without it a batch is drawn
+        here (`batch_size`, default 16).  `kw` (`patch`, `iters`, `alpha`, `blend`, `weight`, `history`) goes to
+        `patch_refine`, whose result is returned: (x, energy[, iterates])."""
+        from .refine import patch_refine
+        s = self.n_scales - 1 if scale is None else int(scale)
+        if not 0 <= s < self.n_scales:
+            raise ValueError(f'refine: scale {s} outside 0 ... {self.n_scales - 1}')
+        batch_size = kw.pop('batch_size', 16)
+        if samples is None:
+            samples = self.sample_scales(batch_size=batch_size, save_images=False)
+        batch = samples[s] if isinstance(samples, (list, tuple)) else samples
+        image = self.data_list[s][0][0]
+        valid = None if self.train_mask_hard is None else self.train_mask_hard[s]
+        return patch_refine(batch.to(self.device, torch.float32).contiguous(), image.to(torch.float32).contiguous(),
+                            tile=tuple(self.ema_model.tile), valid=valid, **kw)
 
     def _local_batch_maps(self, batch_size) -> dict:
         """This rank's rows of the per-sample conditioning on `ema_model`, as {attribute: value to set for the call}: every
