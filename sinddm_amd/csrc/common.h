@@ -12,9 +12,7 @@ namespace sinddm {
 #ifndef SINDDM_WINO_V3        // 1: inference 3x3 convs of big launches on the F(2x4,3x3) kernel (conv_wino3.h)
 #define SINDDM_WINO_V3 1
 #endif
-#ifndef SINDDM_V3_MIN_ITEMS_PER_CU   // launches with at least this many (tile, 80-channel block) items per CU take conv_wino3.h
-#define SINDDM_V3_MIN_ITEMS_PER_CU 1
-#endif
+constexpr int SINDDM_V3_MIN_ITEMS_PER_CU = 1;   // launches with at least this many (tile, 80-channel block) items per CU take conv_wino3.h
 #ifndef SINDDM_WINO_V4        // 1: launches with several 8x32 items per CU on the one-wave-per-SIMD F(2x4,3x3) kernel (conv_wino4.h)
 #define SINDDM_WINO_V4 1
 #endif
@@ -38,9 +36,6 @@ namespace sinddm {
 #endif
 #ifndef SINDDM_WGRAD_WIDE     // 1: W % 4 == 0 launches of the Winograd weight gradient on wgrad_wino_wide_kernel (16-byte DMA)
 #define SINDDM_WGRAD_WIDE 1
-#endif
-#ifndef SINDDM_WGRAD_ABL      // timing ablation bits of the weight-gradient kernels (results WRONG when != 0)
-#define SINDDM_WGRAD_ABL 0
 #endif
 
 inline bool wino_enabled() { return SINDDM_CONV_WINO != 0; }

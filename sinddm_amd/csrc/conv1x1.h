@@ -143,9 +143,6 @@ __global__ __launch_bounds__(C1_THREADS) void conv1x1_mfma_kernel(ConvArgs p, in
 //   * same epilogue contract as above (bias, GELU / GELU'(aux) *, residual, 16-byte stores).
 // -------------------------------------------------------------------------------------------------------------------
 
-#ifndef C1B_ABL
-#define C1B_ABL 0        // timing ablations (wrong results): 1 no B loads in the loop, 2 no A reads in the loop, 4 no epilogue memory ops
-#endif
 template <int MTT, int ACT, int TAIL, int RES = 1>   // TAIL = 1 when H*W % 4 != 0: a lane's 4 pixels can straddle the end of a plane; RES = 0: no residual operand
 __global__ __launch_bounds__(C1_THREADS, 2) void conv1x1_all_kernel(ConvArgs p, int tiles_per_img, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) float smem[];       // [nks][MTT][64]
@@ -244,16 +241,14 @@ __global__ __launch_bounds__(C1_THREADS, 2) void conv1x1_all_kernel(ConvArgs p, 
             for (int i = 0; i < C1B_PF; ++i) {
                 const int ks = k0 + i;
                 const f32x4 bv = bq[i];
-                if (!(C1B_ABL & 1)) {
-                    const bool wrap = k0 + C1B_PF >= nks_pad;           // (uniform) last group: the next tile's first k-steps
-                    TileCtx lc;
-                    lc.rs = wrap ? nctx.rs : ctx.rs;
-                    lc.pxo = wrap ? nctx.pxo : ctx.pxo;
-                    bq[i] = load_b(lc, wrap ? i : ks + C1B_PF);
-                }
+                const bool wrap = k0 + C1B_PF >= nks_pad;               // (uniform) last group: the next tile's first k-steps
+                TileCtx lc;
+                lc.rs = wrap ? nctx.rs : ctx.rs;
+                lc.pxo = wrap ? nctx.pxo : ctx.pxo;
+                bq[i] = load_b(lc, wrap ? i : ks + C1B_PF);
                 const int kn = ks + 1 < nks_pad ? ks + 1 : 0;           // (the wrap-around read is never used)
 #pragma unroll
-                for (int mt = 0; mt < MTT; ++mt) aa[(i + 1) & 1][mt] = (C1B_ABL & 2) ? aa[i & 1][mt] + 1.f : smem[(kn * MTT + mt) * 64 + lane];
+                for (int mt = 0; mt < MTT; ++mt) aa[(i + 1) & 1][mt] = smem[(kn * MTT + mt) * 64 + lane];
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int mt = 0; mt < MTT; ++mt)
@@ -285,7 +280,6 @@ __global__ __launch_bounds__(C1_THREADS, 2) void conv1x1_all_kernel(ConvArgs p, 
                 unsigned o = px0 < HW ? (unsigned)((co0 + mt * 16 + kq * 4 + r) * HW + px0) * 4u : OOB;
                 asm volatile("" : "+v"(o));
                 off[slot][r] = o;
-                if (C1B_ABL & 4) { rv[slot][r] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
                 if constexpr (RES) rv[slot][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, (int)o, 0, 0));
                 if constexpr (ACT == 2) uv[slot][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_aux, (int)o, 0, 0));
             }
@@ -318,7 +312,6 @@ __global__ __launch_bounds__(C1_THREADS, 2) void conv1x1_all_kernel(ConvArgs p, 
                     for (int j = 0; j < 4; ++j) v[j] *= gelu_erf_grad(uv[mt & 1][r][j]);
                 }
                 if constexpr (RES) v += rv[mt & 1][r];
-                if (C1B_ABL & 4) { if (v[0] + v[1] + v[2] + v[3] == 123.4f) p.out[tid] = v[1]; continue; }
                 const unsigned o = off[mt & 1][r];
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, (int)(straddle ? OOB : o), 0, 0);
                 if (tail_tile && straddle) {             // (one lane of the image's last tile)

@@ -22,22 +22,15 @@
 
 namespace sinddm {
 
-#ifndef SINDDM_C3M_MG
-#define SINDDM_C3M_MG 1
-#endif
-constexpr int C3M_MG = SINDDM_C3M_MG;              // m-tiles per pass over the B operands (the weight image is padded to whole passes)
+constexpr int C3M_MG = 1;                          // m-tiles per pass over the B operands (the weight image is padded to whole passes)
 constexpr int C3M_KS = 7;                          // k-steps: 27 taps + the bias tap
 constexpr int C3M_RS = 68;                         // row stride of the input image (66 columns used)
 constexpr int C3M_IMG = 9 * C3M_RS + 4;            // per wave: 3 planes x 3 rows, + four 1.0f for the bias tap
-#ifndef SINDDM_C3M_WG_PER_CU
-#define SINDDM_C3M_WG_PER_CU 4                      // persistent grid: 16 waves per compute unit (19 KB of LDS per workgroup)
-#endif
+constexpr int SINDDM_C3M_WG_PER_CU = 4;            // persistent grid: 16 waves per compute unit (19 KB of LDS per workgroup)
 #ifndef SINDDM_C3_MFMA
 #define SINDDM_C3_MFMA 1
 #endif
-#ifndef SINDDM_C3M_MIN_ITEMS_PER_CU
-#define SINDDM_C3M_MIN_ITEMS_PER_CU 11             // floor in 64-pixel items per compute unit (profiles/NOTES_r33.md section 3)
-#endif
+constexpr int SINDDM_C3M_MIN_ITEMS_PER_CU = 11;    // floor in 64-pixel items per compute unit (profiles/NOTES_r33.md section 3)
 
 inline int c3m_groups(int cout) { return (cout / 16 + C3M_MG - 1) / C3M_MG; }
 inline size_t c3m_lds_bytes(int cout) { return ((size_t)C3M_KS * c3m_groups(cout) * C3M_MG * 64 + 4 * C3M_IMG) * sizeof(float); }

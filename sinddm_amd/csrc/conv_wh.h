@@ -47,24 +47,7 @@ __device__ __forceinline__ void wh_static_for(F&& f) {
     wh_static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-// Compile-time timing ablations (-DWH_ABL=bits; results are WRONG, never ship):
-//   1 no raw-tile requests   2 no input transform   4 U fragments loaded once per item   8 no MFMAs   16 no epilogue loads / stores
-#ifndef WH_ABL
-#define WH_ABL 0
-#endif
-#ifndef WH_MIXLO
-#define WH_MIXLO 1             // lo piece by v_fma_mixlo/hi_f16 (1) or v_fma_mix_f32 x 2 + v_cvt_pk_f16_f32 (0)
-#endif
-#ifndef WH_NT
-#define WH_NT 6                // bit 0: raw-tile loads non-temporal (measured: +8 %, the co blocks' sharing in L2 is lost), bit 1: epilogue residual loads, bit 2: output stores -- of tensors beyond the 256 MB last-level cache only (C3: -1.2 %, C2: +0.6 % without that rule)
-#endif
-#ifdef WH_TIMING
-// s_memtime stamps of every workgroup's third item (debug builds only; tools/wh_seg.py): [launch % 8][workgroup][wave][32]
-__device__ unsigned long long g_wh_seg[8 * 256 * 8 * 32];
-#define WH_SEG(slot) do { if (j == 2) g_wh_seg[((p.mtp * 256 + blockIdx.x) * 8 + wv) * 32 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WH_SEG(slot) do {} while (0)
-#endif
+constexpr int WH_NT = 6;        // bit 0: raw-tile loads non-temporal (measured: +8 %, the co blocks' sharing in L2 is lost), bit 1: epilogue residual loads, bit 2: output stores -- of tensors beyond the 256 MB last-level cache only (C3: -1.2 %, C2: +0.6 % without that rule)
 constexpr int WH_TH = 8, WH_TW = 32;
 constexpr int WH_RS = 40;                      // LDS row stride of the raw tile: image columns x0-4 .. x0+35 (ten aligned 16-byte groups)
 constexpr int WH_PS = 408;                     // plane stride (floats): 10 x 40 + 8 (4 PS = 32 (mod 64): the two channel quads of a lane pair hit disjoint banks)
@@ -84,7 +67,7 @@ constexpr int WH_COB = 80;                     // output channels per item
 constexpr int WR_RING = 4;                     // U fragments in flight per multiplying wave of the 160-channel form (40 per chunk: the slots stay compile-time)
 static_assert(40 % WR_RING == 0 && WR_RING <= 10, "static ring slots");
 
-inline bool wh_shape_ok(int cin, int cout) { return cin >= 32 && cin % 16 == 0 && cout % WH_COB == 0; }   // (>= 2 chunks: the chunk stream looks two ahead)
+inline bool wh_shape_ok(int cin, int cout) { return wh_plan_ok(cin, cout); }   // (>= 2 chunks: the chunk stream looks two ahead)
 // f16 elements of the packed image: [co block][chunk][f 24][n 5][piece 2][k half 2][co 16][8]
 inline long long wh_image_halfs(int cin, int cout) { return (long long)(cout / WH_COB) * (cin / 16) * 24 * 5 * 512; }
 
@@ -196,7 +179,7 @@ inline int wh_pack_launch(const float* w, float* wsinv, void* img, int cin, int 
 
 // Workgroup barrier that publishes LDS only.  __syncthreads() also drains vmcnt: in this kernel that would wait out the U
 // fragments in flight for the next chunk at every chunk barrier, and the output stores of the previous pass at every epilogue
-// barrier (measured: 4 300 cycles per epilogue pass, tools/wh_seg.py).  The LDS-DMA of the service waves is published by
+// barrier (measured: 4 300 cycles per epilogue pass, profiles/NOTES_r05.md).  The LDS-DMA of the service waves is published by
 // their own s_waitcnt vmcnt in front of the barrier.
 __device__ __forceinline__ void wh_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -297,7 +280,7 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
     // two loads per channel (lanes 0..63, then lanes 0..35; out of the image = out-of-range offset = zeros), into 64 REGISTERS,
     // and writes them to LDS one iteration later.  (LDS-DMA was tried first: an LDS-DMA instruction costs the issuing wave
     // 150-400 cycles whatever its size, the instructions in flight are few, and its traffic halved the rate of the U loads of the
-    // multiplying waves -- tools/wh_seg.py: 3 600 - 7 000 cycles per chunk.  The service waves own 200 idle registers: those are
+    // multiplying waves -- profiles/NOTES_r05.md: 3 600 - 7 000 cycles per chunk.  The service waves own 200 idle registers: those are
     // the look-ahead buffer, and only the wave that loaded a plane reads it, so no other wave waits on these loads.)
     auto stage_offsets = [&](const Item& it, int (&vo)[2]) {
 #pragma unroll
@@ -315,8 +298,8 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int so = (c * 16 + (sv & 1) * 8 + k) * HW * 4;
-            stg[2 * k] = (WH_ABL & 1) ? f32x4{0.f, 0.f, 0.f, 0.f} : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo[0], so, (WH_NT & 1) ? 2 : 0));
-            stg[2 * k + 1] = (WH_ABL & 1) ? f32x4{0.f, 0.f, 0.f, 0.f} : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo[1], so, (WH_NT & 1) ? 2 : 0));
+            stg[2 * k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo[0], so, (WH_NT & 1) ? 2 : 0));
+            stg[2 * k + 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo[1], so, (WH_NT & 1) ? 2 : 0));
         }
     };
     auto stage_write = [&](unsigned char* raw) {
@@ -334,11 +317,9 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
     Item cur = decode(0);
     if (!cur.ok) return;
     int svoff[2] = {OOB, OOB};
-#ifndef WH_SVC_PRIO
-#define WH_SVC_PRIO 2
-#endif
     // (the service waves are the longest pole of a chunk and share their SIMDs with multiplying waves that mostly wait for
     // memory: they win the issue arbitration)
+    constexpr int WH_SVC_PRIO = 2;
     if constexpr (service) __builtin_amdgcn_s_setprio(WH_SVC_PRIO);
     if constexpr (service) {                                 // the first item's first chunk
         stage_offsets(cur, svoff);
@@ -372,7 +353,6 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
 
         // ---- T phase of one chunk (service waves): raw buffer -> V buffer ----
         auto transform = [&](const unsigned char* raw, unsigned char* vb, float sxv) {
-            if (WH_ABL & 2) return;
             const f32x2 sx2{sxv, sxv};
             const unsigned char* rpB = raw + t_rdB;
             const unsigned char* rpE = raw + t_rdE;
@@ -419,13 +399,8 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
                         hi[pr][j] = __builtin_convertvector(sc, h16x2);
                         // (remainder by v_fma_mix_f32 with the binary16 piece as an operand: v * sx is exact, so
                         // fma(v, sx, -hi) = sc - hi exactly; one instruction per value instead of a conversion and half a packed subtract)
-#if WH_MIXLO
                         // ... and rounded to binary16 by the same instruction (v_fma_mixlo_f16 / v_fma_mixhi_f16: one rounding of the exact remainder)
                         lo[pr][j] = h16x2{(_Float16)__builtin_fmaf(v[j].x, sxv, -(float)hi[pr][j].x), (_Float16)__builtin_fmaf(v[j].y, sxv, -(float)hi[pr][j].y)};
-#else
-                        const f32x2 rem{__builtin_fmaf(v[j].x, sxv, -(float)hi[pr][j].x), __builtin_fmaf(v[j].y, sxv, -(float)hi[pr][j].y)};
-                        lo[pr][j] = __builtin_convertvector(rem, h16x2);
-#endif
                     }
                 }
 #pragma unroll
@@ -515,22 +490,16 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
                     constexpr int slot = (fi & 1) * 5 + n;
                     const h16x8 u = ur[slot];
                     __builtin_amdgcn_sched_barrier(0);
-                    if (WH_ABL & 8) {
-                        asm volatile("" ::"v"(ah0), "v"(ah1), "v"(al0), "v"(al1), "v"(u));
-                    } else {
-                        acc[fi][0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, u, acc[fi][0][n], 0, 0, 0);
-                        acc[fi][1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, u, acc[fi][1][n], 0, 0, 0);
-                        acc[fi][0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, u, acc[fi][0][n], 0, 0, 0);
-                        acc[fi][1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, u, acc[fi][1][n], 0, 0, 0);
-                    }
+                    acc[fi][0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, u, acc[fi][0][n], 0, 0, 0);
+                    acc[fi][1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, u, acc[fi][1][n], 0, 0, 0);
+                    acc[fi][0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, u, acc[fi][0][n], 0, 0, 0);
+                    acc[fi][1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, u, acc[fi][1][n], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     // (the slot is free: refill it with the same column tile two frequencies on.  Pinned behind the MFMAs that
                     // read it -- left to the scheduler all loads of a chunk are hoisted to its top.  Behind the last chunk the
                     // refill re-reads the last chunk's fragments: no branch, the values are not used)
-                    if (!(WH_ABL & 4)) {
-                        if (fi < 2) load_u(c, fi + 2, n, slot);
-                        else load_u(c + 1 < nch ? c + 1 : c, fi - 2, n, slot);
-                    }
+                    if (fi < 2) load_u(c, fi + 2, n, slot);
+                    else load_u(c + 1 < nch ? c + 1 : c, fi - 2, n, slot);
                     __builtin_amdgcn_sched_barrier(0);
                 });
             });
@@ -561,7 +530,7 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
 #pragma unroll
                 for (int pp = 0; pp < 2; ++pp) {
                     rsd[n][pp] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (p.resid && !(WH_ABL & 16) && e_in && ey + pp < H)
+                    if (p.resid && e_in && ey + pp < H)
                         rsd[n][pp] = ((WH_NT & 2) && big_out) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.resid + ((size_t)b * p.Cout + co) * HW + (size_t)(ey + pp) * W + ex))
                                                  : *reinterpret_cast<const f32x4*>(p.resid + ((size_t)b * p.Cout + co) * HW + (size_t)(ey + pp) * W + ex);
                 }
@@ -571,7 +540,6 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
         constexpr std::integral_constant<int, WR ? 2 : 5> ep_n1{};   // what is requested behind the last chunk
 
         // ---- the two roles run their own loops (same number of barriers): nothing of the one is live in the other ----
-        WH_SEG(0);
         if constexpr (service) {
             const __amdgpu_buffer_rsrc_t rsnx = in_rsrc(nxt.ok ? nxt.b : b);
             float sxn = 0.f, inv_n = 0.f;
@@ -582,11 +550,9 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
                 stage_write(sRaw);
                 if (nch > 1) stage_load(rsin, svoff, 1);
                 else if (nxt.ok) { stage_offsets(nxt, svoff); stage_load(rsnx, svoff, 0); }
-                WH_SEG(1);
                 transform(sRaw, vbuf(g), sx);
                 wh_barrier();
             }
-            WH_SEG(2);
             for (int c = 0; c < nch; ++c) {
                 // stream chunk k + 1 (loaded one iteration ago) goes to LDS -- the one raw buffer: only this wave reads these
                 // planes, and it has finished T(k) --, chunk k + 2 is requested, chunk k + 1 transformed while the others multiply
@@ -598,12 +564,9 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
                         if (c + 2 == nch) stage_offsets(nxt, svoff);
                         if (c + 2 == nch || nch > 1) stage_load(rsnx, svoff, c + 2 - nch);
                     }
-                    if (c == 3) WH_SEG(24);
                     transform(sRaw, vbuf(g + c + 1), c + 1 < nch ? sx : sxn);
-                    if (c == 3) WH_SEG(25);
                 }
                 wh_barrier();
-                if (c < 12) WH_SEG(3 + c);
             }
             if constexpr (WR) ep_thread();
             ep_operands(ep_n0, ep_n1);
@@ -613,21 +576,16 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
                 if constexpr (!WR) load_u(0, sl / 5, sl % 5, sl);
                 else if constexpr (sl < WR_RING) load_u(0, 0, sl, sl);
             });
-            WH_SEG(1);
             if (j == 0) wh_barrier();
-            WH_SEG(2);
             for (int c = 0; c < nch; ++c) {
                 if constexpr (WR) multiply_wr(c, vbuf(g + c));
                 else multiply(c, vbuf(g + c));
-                if (c == 3) WH_SEG(25);
                 wh_barrier();
-                if (c < 12) WH_SEG(3 + c);
             }
             if constexpr (WR) ep_thread();
             ep_operands(ep_n0, ep_n1);
         }
         g += nch;
-        WH_SEG(16);
 
         // ---- epilogue: the multiplying waves apply the vertical A^T to their own frequency column in registers, then hand the
         // two rows over through LDS, two column tiles per pass (3 passes): ONE exchange buffer, beside the V buffer that already
@@ -639,7 +597,6 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
         const int e_wr = ((fj * 32 + (e_lane & 15)) * WH_XS + 4 * (e_lane >> 4)) * 4;   // X[r][j][co 32][tile (stride 36)] byte offsets: writer (r = 0, fj, co = l16, tile 4 kq)
         const int e_rd = (e_co * WH_XS + e_t) * 4;                  // reader (r = 0, j = 0, co16, tile)
         float amax = 0.f;
-        WH_SEG(17);
         if constexpr (!service && !WR) {
             // vertical A^T (F(2,3)), in place: y0 = (m0 + m1) + m2 -> acc[0], y1 = (m1 - m2) - m3 -> acc[1]
             // (WR: the accumulators are the two rows already)
@@ -669,7 +626,6 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
             if constexpr (WR && n0 + 2 < NCT)
                 ep_operands(std::integral_constant<int, n0 + 2>{}, std::integral_constant<int, n0 + 4>{});
             wh_barrier();
-            WH_SEG(18 + decltype(PS)::value);
             float q[nn][2][6];
 #pragma unroll
             for (int nl = 0; nl < nn; ++nl)
@@ -691,7 +647,6 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
                     const float s12 = z[1] + z[2], d12 = z[1] - z[2], s34 = z[3] + z[4], d34 = z[3] - z[4];
                     f32x4 v{z[0] + s12 + s34, d12 + 2.f * d34, s12 + 4.f * s34, d12 + 8.f * d34 + z[5]};
                     const int y = ey + pp;
-                    if ((WH_ABL & 16) && v[0] != 123.456f) continue;
                     if (y < H && ex < W) {
                         const size_t o = ((size_t)b * p.Cout + co) * HW + (size_t)y * W + ex;
                         v = v * k + bv;
@@ -716,7 +671,6 @@ __device__ __forceinline__ void wh_run(const ConvArgs& p, int items_per_xcd, int
             });
         });
         if (p.amax_out) amax_publish(amax, p.amax_out + (size_t)b * AMAX_STRIDE);
-        WH_SEG(23);
         if (!nxt.ok) break;
         cur = nxt;
     }
@@ -733,13 +687,9 @@ __global__ __launch_bounds__(512) void conv_wr_kernel(ConvArgs p, int items_per_
     wh_run<true>(p, items_per_xcd, wg_per_xcd);
 }
 
-#ifndef SINDDM_WH_MIN_ITEMS_PER_CU
-#define SINDDM_WH_MIN_ITEMS_PER_CU 12      // measured per pyramid scale (profiles/r05_scales.txt, r05_threshold_ab_full.txt): C2 133x177 at batch 16
-#endif
-#ifndef SINDDM_WH_MIN_PIXELS
-#define SINDDM_WH_MIN_PIXELS 12000          // (12.75 items per CU) wins on conv_wh, C3 76x95 at batch 64 (15 per CU, 7 220 pixels: the whole working set of a launch
+constexpr int SINDDM_WH_MIN_ITEMS_PER_CU = 12;  // measured per pyramid scale (profiles/r05_scales.txt, r05_threshold_ab_full.txt): C2 133x177 at batch 16
+constexpr int SINDDM_WH_MIN_PIXELS = 12000;      // (12.75 items per CU) wins on conv_wh, C3 76x95 at batch 64 (15 per CU, 7 220 pixels: the whole working set of a launch
                                            // lives in the last-level cache and conv_wino4's memory phases are cheap) loses 10 %
-#endif
 #ifndef SINDDM_CONV_WH
 #define SINDDM_CONV_WH 1
 #endif
@@ -756,9 +706,7 @@ inline bool conv_wh_applies(bool fp32_convs, int B, int H, int W, int cin, int c
 #define SINDDM_CONV_WR 1                   // 0: every launch keeps the 80-channel kernel (A/B builds)
 #endif
 constexpr int WR_COB = 2 * WH_COB;         // output channels per item of conv_wr_kernel
-#ifndef SINDDM_WR_MIN_ITEMS_PER_CU
-#define SINDDM_WR_MIN_ITEMS_PER_CU 12      // measured floor, in items of 160 channels (profiles/NOTES_r30.md section 5)
-#endif
+constexpr int SINDDM_WR_MIN_ITEMS_PER_CU = 12;  // measured floor, in items of 160 channels (profiles/NOTES_r30.md section 5)
 
 // Whether a network launch that conv_wh takes should run its 160-channel kernel: with half as many items per workgroup the
 // rounds get coarser, and at 6.4 items per compute unit (16 x 133x177) the launch is 1.2 % slower than on the 80-channel
@@ -798,10 +746,6 @@ inline int conv_wh_launch(const ConvArgs& a_in, hipStream_t st, int variant = 0,
                                                              hipFuncAttributeMaxDynamicSharedMemorySize, WH_LDS);
     if (attr_rc != hipSuccess) return (int)attr_rc;
     if (attr_rc_wr != hipSuccess) return (int)attr_rc_wr;
-#ifdef WH_TIMING
-    static int wh_launch_no = 0;
-    a.mtp = wh_launch_no++ % 8;                  // (the kernel does not read mtp otherwise: stamp row of this launch)
-#endif
     hipLaunchKernelGGL(wr ? conv_wr_kernel : conv_wh_kernel, dim3(wpx * 8), dim3(512), WH_LDS, st, a, ipx, wpx);
     if (rec) {
         const double fl = 2.0 * a.B * a.H * (a.Wt > 0 ? a.Wt : a.W) * (double)a.Cout * 9.0 * a.Cin;   // algorithmic (direct-conv) FLOPs

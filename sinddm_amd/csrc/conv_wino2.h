@@ -40,38 +40,6 @@
 
 namespace sinddm {
 
-// Compile-time timing ablations (-DW2_ABL=bits; results are WRONG, never ship):
-//   1 no raw-tile DMA   2 weights loaded once   4 no LDS reads   8 no epilogue   16 no input-transform VALU
-//   32 raw patches read from the exchange area (LDS the DMA never writes)   64 no chunk barrier   128 chunk barrier
-//   without its waitcnt
-#ifndef W2_ABL
-#define W2_ABL 0
-#endif
-#ifndef W2_THEAD
-#define W2_THEAD 0           // (experiment) transform at the head of the k-step that uses it (no LDS wait in a head): +-0
-#endif
-#ifndef W2_ADB
-#define W2_ADB 0             // (experiment) double-buffered A registers: all weight loads at the head of the k-step
-#endif
-#ifndef W2_WMERGE
-#define W2_WMERGE 0          // (experiment) 2 + 1 merged waits per k-step instead of 5 + 3: measured -1.4 % (waits come earlier)
-#endif
-#ifndef W2_STAGE
-#define W2_STAGE 1           // raw tiles of the big launches through registers (0: LDS-DMA, as the small launches do)
-#endif
-#ifdef W2_TIMING
-// s_memtime stamps of workgroups 8 and 9 (debug builds only; tools/w2_timing.py): [wg][item][slot][wave]
-__device__ unsigned long long g_w2_dbg[2 * 4 * 40 * 4];
-#endif
-#ifdef W2_PHASE
-// per workgroup HW_ID | XCC_ID << 32, then (epilogue start, end) of its first 9 items (tools/w2_phase.py)
-__device__ unsigned long long g_w2_phase[1024 * 20];
-// per workgroup and wave: 16 stamps inside the epilogue of item 3 (tools/w2_phase.py seg)
-__device__ unsigned long long g_w2_seg[1024 * 4 * 16];
-#define W2_SEG(slot) do { if (seg) g_w2_seg[(blockIdx.x * 4 + wi) * 16 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define W2_SEG(slot) do {} while (0)
-#endif
 constexpr int W2_THREADS = 256;
 constexpr int W2_TW = 32, W2_TH = 4;           // pixel tile
 // LDS image of a channel's halo tile: 6 rows (y0-1 .. y0+4) of 40 floats = image columns x0-4 .. x0+35, i.e. ten
@@ -178,7 +146,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
         const __amdgpu_buffer_rsrc_t rs =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sbase), 0, live ? HW * 4 : 0, 0x00020000);
         float* pl = buf + kc * W2_PS;
-        if (W2_ABL & 1) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)pl, 16, (int)goff, 0, 0, 0);
     };
     auto issue = [&](int ib, int c, bool valid, float* buf) {
@@ -198,11 +165,9 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
     auto plane_ptr = [&](int ib) { return p.in + ((size_t)ib * p.Cin + wi * 4) * HW; };   // (sample, channel 4 wi)
     __amdgpu_buffer_rsrc_t rs_st;                   // planes of the chunk being staged (Cin % 4 == 0: all four or none)
     auto stage_load = [&](int slot, int g) {
-        if (W2_ABL & 1) return;
         stg[slot] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_st, (int)goff, g * (int)HW4, 0));
     };
     auto stage_store = [&](int slot, float* buf, int g) {
-        if (W2_ABL & 1) return;
         *reinterpret_cast<f32x4*>(buf + (wi * 4 + g) * W2_PS + lane * 4) = stg[slot];
     };
 
@@ -217,12 +182,13 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
         const int pcb = mg / MTP, pmt = mg - pcb * MTP;
         return (pcb * nch * 4 + wi) * (4096 * MTP) + pmt * 1024;
     };
-    f32x4 a[2][MT];                                                // A operands of the current k-step ([1]: W2_ADB double buffer)
+    // A operands of the current k-step, in a[0].  (Row 1 is unused: declared as a flat a[MT] the EDGE >= 1 instantiations come
+    // out with two scalar register pairs exchanged -- the same instructions, but not the same bytes.)
+    f32x4 a[2][MT];
     // g = k-step index inside the item; g == nks_total means "k-step 0 of the next item" (output-channel block ncb):
     // the weight stream, like the raw-tile stream, runs across items without a branch inside a k-step -- a chunk stays
     // one basic block, which the register allocator needs to accumulate in place
     auto load_w = [&](int mt, int cb, int ncb, int g) {
-        if ((W2_ABL & 2) && g > 0) return;
         const bool wrap = g >= nks_total;
         const int gg = wrap ? 0 : g;
         // the packed image is blocked by MTP m-tiles per output-channel block; an item covers MT of them (MT == MTP
@@ -239,10 +205,7 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
     //   weight loads of the k-step before the barrier and memory operations complete in order, so vmcnt(MT) covers it;
     //   (b) this wave's LDS reads of the current chunk done: lgkmcnt(0).
     auto chunk_barrier = [&]() {
-        if (W2_ABL & 64) return;
-        if (W2_ABL & 128) { asm volatile("s_barrier" ::: "memory"); return; }
-        if (W2_STAGE && MT >= 3) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); return; }
-        if (W2_ADB && MT >= 3) { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(3 * MT) : "memory"); return; }
+        if (MT >= 3) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); return; }
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(MT) : "memory");
     };
     auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
@@ -251,7 +214,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
     auto read_raw = [&](const float* base, f32x4 (&ra)[NT], f32x4 (&rb)[NT]) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            if (W2_ABL & 4) { ra[nt] = f32x4{1.f, 2.f, 3.f, 4.f}; rb[nt] = f32x4{(float)lane, 1.f, 0.f, 2.f}; continue; }
             const float* qa = base + oa + nt * 2 * W2_RS;
             const float* qb = base + ob + nt * 2 * W2_RS;
 #pragma unroll
@@ -264,7 +226,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
     auto transform = [&](const f32x4 (&ra)[NT], const f32x4 (&rb)[NT], float (&v)[NT][4], const bool (&cm)[4]) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            if (W2_ABL & 4) { v[nt][0] = ra[nt][0]; v[nt][1] = rb[nt][0]; v[nt][2] = ra[nt][2]; v[nt][3] = rb[nt][1]; continue; }
             // columns right of the image edge hold the next row's pixels (the 16-byte groups run past it): zero padding
             float r0 = fmaf(sgn, rb[nt][0], ra[nt][0]), r1 = fmaf(sgn, rb[nt][1], ra[nt][1]);
             float r2 = fmaf(sgn, rb[nt][2], ra[nt][2]), r3 = fmaf(sgn, rb[nt][3], ra[nt][3]);
@@ -291,20 +252,11 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
     const float* sstage = plane_ptr(it.b) + (size_t)16 * HW;   // planes of the chunk to stage next (chunk 1 of the item)
     int nb = 0;                                    // raw buffer holding the current chunk (runs across items)
     float v[2][NT][4];                             // B operands, double buffered by k-step parity (runs across items)
-    // W2_THEAD (big launches): the raw patches of a k-step are read at the head of the PREVIOUS k-step and transformed at
-    // the head of their own -- no LDS round trip in a head, one B-operand set; they stay in registers across the epilogue
-    f32x4 pra[NT], prb[NT];
-    if (W2_THEAD && MT >= 3) {
-        read_raw(smem, pra, prb);
-    } else {
+    {
         f32x4 ra[NT], rb[NT];
         read_raw(smem, ra, rb);
         transform(ra, rb, v[0], cm);
     }
-#ifdef W2_TIMING
-    int dbg_item = 0;
-    const int dbg_wg = blockIdx.x == 8 ? 0 : 1;
-#endif
 
     for (;;) {
         Wino2Item nx;
@@ -313,10 +265,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
         if (!have_next) nx = it;
         const int wb_nx = wbase(nx.cb);
         const float* base_nx = plane_ptr(nx.b);
-#ifdef W2_TIMING
-        const bool dbg = (blockIdx.x == 8 || blockIdx.x == 8 + 8 * 32) && dbg_item < 4 && lane == 0;
-        if (dbg) g_w2_dbg[((dbg_wg * 4 + dbg_item) * 40 + 39) * 4 + wi] = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4);
-#endif
         f32x4 acc[MT][NT][4];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -341,9 +289,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
             // (opaque: the optimizer must not peel or unswitch the chunk loop on it -- two copies of the body do not fit
             // the register file)
             const bool last = __builtin_amdgcn_readfirstlane(c + 1 == nch) != 0;
-#ifdef W2_TIMING
-            if (dbg && c < 12) g_w2_dbg[((dbg_wg * 4 + dbg_item) * 40 + 3 * c + 0) * 4 + wi] = __builtin_amdgcn_s_memtime();
-#endif
             if (last) make_goff(nx);
             const int dsrc = last ? nx.b : it.b;
             const int dch = last ? 0 : c + 1;
@@ -353,7 +298,7 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
             // the next item's first)
             constexpr int W_KS = 1024 * MTP, W_CH = 4 * 4096 * MTP;
             const int w_k[4] = {wcur + W_KS, wcur + 2 * W_KS, wcur + 3 * W_KS, last ? wb_nx : wcur + W_CH};
-            if constexpr (MT >= 3 && W2_STAGE) {
+            if constexpr (MT >= 3) {
                 if (last) sstage = base_nx;
                 const bool live = dval && dch * 16 + wi * 4 < p.Cin;
                 rs_st = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sstage), 0, live ? 4 * (int)HW4 : 0, 0x00020000);
@@ -363,13 +308,7 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
                 const int g = c * 4 + ks;
                 if (ks == 3) {
                     __builtin_amdgcn_sched_barrier(0);
-#ifdef W2_TIMING
-                    if (dbg && c < 12) g_w2_dbg[((dbg_wg * 4 + dbg_item) * 40 + 3 * c + 1) * 4 + wi] = __builtin_amdgcn_s_memtime();
-#endif
                     chunk_barrier();
-#ifdef W2_TIMING
-                    if (dbg && c < 12) g_w2_dbg[((dbg_wg * 4 + dbg_item) * 40 + 3 * c + 2) * 4 + wi] = __builtin_amdgcn_s_memtime();
-#endif
                 }
                 const float* rsrc_ = ks < 3 ? cur + (ks + 1) * 4 * W2_PS : nxt;
                 f32x4 ra[NT], rb[NT];
@@ -383,44 +322,21 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
                     // the A refills between the m-tiles): the partner wave's burst covers this wave's head.  (A fine-grained
                     // version -- one LDS read / three VALU pinned behind every MFMA of m-tiles 0 and 2 -- measured 1 % slower
                     // at two waves per SIMD and no faster for a lone wave.)
-#if W2_STAGE
                     if (ks == 1) { stage_store(0, nxt, 0); stage_store(1, nxt, 1); }
                     if (ks == 2) { stage_store(0, nxt, 2); stage_store(1, nxt, 3); }
-#else
-                    if (ks == 0) issue(dsrc, dch, dval, nxt);
-#endif
-#if W2_THEAD
-                    transform(pra, prb, v[0], cm);                   // this k-step's operands (raw data read a k-step ago)
-                    __builtin_amdgcn_sched_barrier(0);
-                    read_raw(rsrc_, pra, prb);                       // the next k-step's raw patches
-#else
                     read_raw(rsrc_, ra, rb);
-#endif
-#if W2_STAGE
                     if (ks == 0) { stage_load(0, 0); stage_load(1, 1); }
                     if (ks == 1) { stage_load(0, 2); stage_load(1, 3); }
-#endif
-#if W2_ADB
-                    // all five A refills of the NEXT k-step here, into the other register set: the burst below is pure MFMA
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-                        a[(ks + 1) & 1][mt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wlane + mt * 1024, w_k[ks], 0));
-#endif
-#if !W2_THEAD
                     transform(ra, rb, v[(ks + 1) & 1], mk);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
                         for (int q = 0; q < 8; ++q)
-                            acc[mt][q >> 2][q & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[W2_ADB ? (ks & 1) : 0][mt][q & 3], v[W2_THEAD ? 0 : (ks & 1)][q >> 2][q & 3],
+                            acc[mt][q >> 2][q & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0][mt][q & 3], v[ks & 1][q >> 2][q & 3],
                                                                                           acc[mt][q >> 2][q & 3], 0, 0, 0);
-#if !W2_ADB
-                        if (!((W2_ABL & 2) && g + 1 > 0))
-                            a[0][mt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wlane + mt * 1024, w_k[ks], 0));
+                        a[0][mt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wlane + mt * 1024, w_k[ks], 0));
                         __builtin_amdgcn_sched_barrier(0);
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 } else {
@@ -443,37 +359,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
         }
 
         // ---- output transform + epilogue: column half in registers, row half through LDS, 32 channels per pass ----
-#ifdef W2_TIMING
-        if (dbg) g_w2_dbg[((dbg_wg * 4 + dbg_item) * 40 + 36) * 4 + wi] = __builtin_amdgcn_s_memtime();
-#endif
-#ifdef W2_PHASE
-        const bool ph = wi == 0 && lane == 0 && p.Cin == 160 && p.Cout == 160 && (l - 1) < 9 && blockIdx.x < 1024;
-        if (ph) {
-            if (l == 1) g_w2_phase[blockIdx.x * 20] = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4) |
-                                                        ((unsigned long long)__builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 20) << 32);
-            g_w2_phase[blockIdx.x * 20 + 2 * (l - 1) + 1] = __builtin_amdgcn_s_memtime();
-        }
-#endif
-        if (W2_ABL & 8) {
-            float sink = 0.f;                                   // keep every accumulator chain alive
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) sink += acc[mt][nt][j][0] + acc[mt][nt][j][1] + acc[mt][nt][j][2] + acc[mt][nt][j][3];
-            if (sink == 123.456f) p.out[tid] = sink;
-            if (!have_next) break;
-            it = nx;
-            wb_it = wb_nx;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) cm[c] = cmn[c];
-            continue;
-        }
-#ifdef W2_PHASE
-        const bool seg = lane == 0 && p.Cin == 160 && p.Cout == 160 && l == 4 && blockIdx.x < 1024;
-#endif
-        W2_SEG(0);
         const int tile = tid & 31;                     // reader role: 2x2 tile (tile-row, tile-col) ...
         const int tr = tile >> 4, tc = tile & 15;
         const int cg = tid >> 5;                       // ... and channels cg + 8k of a pass
@@ -519,7 +404,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
         // an 8-byte store covers pixels (x, x+1); in the last odd column only pixel x exists: 4-byte store instead
         // (only when W is odd -- EDGE = 2 builds; issued unconditionally there, with an out-of-range offset where unused)
         auto st2 = [&](const __amdgpu_buffer_rsrc_t& r, unsigned o, f32x2 vv) {
-            if (W2_ABL & 512) { if (vv[0] == 123.4f) p.out[tid] = vv[1]; return; }
             if constexpr (EDGE == 2) {
                 unsigned o2 = x1ok ? o : OOB, o1 = x1ok ? OOB : o;
                 asm volatile("" : "+v"(o2), "+v"(o1));
@@ -537,7 +421,6 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (!in_block(m0, k)) continue;
-                if (W2_ABL & 256) { bs_v[k] = 0.f; rs_v[k][0] = rs_v[k][1] = f32x2{0.f, 0.f}; ax_v[k][0] = ax_v[k][1] = f32x2{1.f, 1.f}; continue; }
                 bs_v[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                     rs_bias, (it.cb * (MT * 16) + m0 * 16 + cg + 8 * k) * 4, 0, 0));
 #pragma unroll
@@ -566,9 +449,7 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
                 }
             }
             if (m0 == 0) prefetch(0);                              // (its accumulators are dead: registers are free)
-            W2_SEG(1 + (m0 / 2) * 5);
             lds_barrier();
-            W2_SEG(2 + (m0 / 2) * 5);
             f32x2 yv[4][2];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -580,9 +461,7 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
                 yv[k][0] = t[0] + t[1] + t[2];                     // Y[pp][q] = sum_i A^T[pp][i] t[i][q]
                 yv[k][1] = t[1] - t[2] - t[3];
             }
-            W2_SEG(3 + (m0 / 2) * 5);
             lds_barrier();                                         // the exchange area is free for the next pass
-            W2_SEG(4 + (m0 / 2) * 5);
             f32x2 val[4][2];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -611,15 +490,7 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
                     st2(rs_out, o, padded ? val[k][pp] * pm : val[k][pp]);
                 }
             }
-            W2_SEG(5 + (m0 / 2) * 5);
         }
-#ifdef W2_TIMING
-        if (dbg) g_w2_dbg[((dbg_wg * 4 + dbg_item) * 40 + 37) * 4 + wi] = __builtin_amdgcn_s_memtime();
-        ++dbg_item;
-#endif
-#ifdef W2_PHASE
-        if (ph) g_w2_phase[blockIdx.x * 20 + 2 * (l - 1) + 2] = __builtin_amdgcn_s_memtime();
-#endif
         if (!have_next) break;
         it = nx;                                   // goff already describes nx
         wb_it = wb_nx;
@@ -630,11 +501,7 @@ __global__ __launch_bounds__(W2_THREADS, 2) void conv_wino2_kernel(ConvArgs p, i
 
 template <int MT, int MTP, int EDGE>
 inline void conv_wino2_launch_e(const ConvArgs& a, unsigned grid, int ipx, int wpx, hipStream_t st) {
-#ifdef W2_ONE_WG
-    constexpr size_t lds = 100 * 1024;                       // (experiment) only one workgroup fits a CU
-#else
     constexpr size_t lds = W2_LDS_FLOATS * sizeof(float);
-#endif
     switch (a.act & 0xff) {
         case 1: hipLaunchKernelGGL((conv_wino2_kernel<MT, 1, MTP, EDGE>), dim3(grid), dim3(W2_THREADS), lds, st, a, ipx, wpx); break;
         case 2: hipLaunchKernelGGL((conv_wino2_kernel<MT, 2, MTP, EDGE>), dim3(grid), dim3(W2_THREADS), lds, st, a, ipx, wpx); break;
@@ -667,11 +534,7 @@ inline int conv_wino2_launch(const ConvArgs& a_in, int mt, hipStream_t st) {
     }
     // persistent launch: two 4-wave workgroups per CU, each walking its share of the XCD's work items
     const int ipx = a.tiles_per_xcd * a.coblks;                  // work items per XCD
-#ifdef W2_ONE_WG
-    int wpx = cu_count() / 8;
-#else
     int wpx = cu_count() / 8 * 2;                          // workgroups per XCD
-#endif
     if (wpx < 1) wpx = 1;
     if (wpx > ipx) wpx = ipx;
     const unsigned grid = (unsigned)(wpx * 8);

@@ -48,38 +48,11 @@ __device__ __forceinline__ void w4_static_for(F&& f) {
     w4_static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-// Compile-time timing ablations (-DW4_ABL=bits; results are WRONG, never ship):
-//   1 no raw-tile staging   2 weights loaded once   4 no raw-patch LDS reads   8 no epilogue   16 no input transform
-//   128 raw-tile requests of a chunk contiguous (tile-major what-if)   256 epilogue without global loads / stores (2048: without the loads, 4096: without the stores)   512 ... without its LDS writes   1024 ... without its LDS reads
-#ifndef W4_ABL
-#define W4_ABL 0
-#endif
-#ifdef W4_TIMING
-// s_memtime stamps of every workgroup's item 3 (debug builds only; tools/w4_seg.py): [launch % 8][workgroup][wave][32]
-__device__ unsigned long long g_w4_seg[8 * 256 * 4 * 32];
-#define W4_SEG(slot) do { if (seg) g_w4_seg[((p.mtp * 256 + blockIdx.x) * 4 + wi) * 32 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define W4_SEG(slot) do {} while (0)
-#endif
-#ifdef W4_KSTAMP
-// s_memtime stamps inside the k-steps of chunk 2 of every workgroup's item 3 (debug builds; tools/w4_kstamp.py):
-// [launch % 8][workgroup][wave][k-step 4][stamp 16]
-__device__ unsigned long long g_w4_ks[8 * 256 * 4 * 64];
-#define W4_KS(ks, i) do { if (kst) g_w4_ks[((p.mtp * 256 + blockIdx.x) * 4 + wi) * 64 + (ks) * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define W4_KS(ks, i) do {} while (0)
-#endif
-#ifndef W4_STG_SLOT
-#define W4_STG_SLOT 24         // first of the four slots of k-steps 0 / 1 in which the raw-tile groups of the next chunk are requested
-#endif
-#ifndef W4_PF_KS
-#define W4_PF_KS 3            // k-step / slot of a chunk in which the epilogue's pass-0 operands are requested (slot -1: at the
-#define W4_PF_SLOT 58         // top of the epilogue instead).  Late in the LAST chunk: what is queued behind these loads
-#endif                        // (vector memory returns in order) is only needed after the epilogue
+constexpr int W4_PF_KS = 3;     // k-step / slot of a chunk in which the epilogue's pass-0 operands are requested (slot -1: at the
+constexpr int W4_PF_SLOT = 58;  // top of the epilogue instead).  Late in the LAST chunk: what is queued behind these loads
+                                // (vector memory returns in order) is only needed after the epilogue
 constexpr int W4_PF_AHEAD = 1;  // the epilogue's per-pass operands are requested one pass ahead (two: no gain, profiles/r04_w4_stagger_prefetch_ab.txt)
-#ifndef W4_XF_SLOT
-#define W4_XF_SLOT 40          // the slot of a k-step behind whose MFMA the input-transform burst of the next k-step sits
-#endif
+constexpr int W4_XF_SLOT = 40;  // the slot of a k-step behind whose MFMA the input-transform burst of the next k-step sits
 // The 240 accumulator registers are the AGPRs a0 .. a239, addressed by NUMBER from inline asm: tile T = (h * 5 + mt) * 6 + j
 // lives in a[4T : 4T+3].  (Left to the register allocator, a third of the MFMAs came out with dst != src and every
 // chunk iteration paid 300-500 v_accvgpr copies to undo the permutation at the loop back edge.)  The compiler never
@@ -220,15 +193,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
     const unsigned HW4 = (unsigned)HW * 4u;
     auto plane_ptr = [&](int ib) { return p.in + ((size_t)ib * p.Cin + wi * 4) * HW; };
     __amdgpu_buffer_rsrc_t rs_st;
-    int lin_soff = 0;
-    auto tile_lin = [&](const Wino4Item& g) { return (g.y0 / W4_TH) * p.tilesX + g.x0 / W4_TW; };
     auto stage_load = [&](int n) __attribute__((always_inline)) {                  // n = 2 g + s: group s of channel wi*4 + g
-        if (W4_ABL & 1) return;
-        // (128: the chunk's eight requests of a wave read ONE contiguous 8 KB of the image -- what a tile-major activation
-        // layout would make of the ten 160-byte row segments x 4 planes; same bytes, same sharing between the two blocks)
-        if (W4_ABL & 128) stg[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_st, lane * 16 + n * 1024, lin_soff, 0));
-        else
-        stg[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_st, (W4_ABL & 64) ? lane * 16 : (int)goff[n & 1], (n >> 1) * (int)HW4, 0));
+        stg[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_st, (int)goff[n & 1], (n >> 1) * (int)HW4, 0));
     };
     // LDS writes of a staged group: four ds_write_b32 at (register + IMMEDIATE) -- left to the compiler they became
     // ds_write2_b32 pairs whose 8-bit offsets need a v_add_u32 per pair, i.e. lone VALU in the MFMA stream.  (The asm
@@ -241,7 +207,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
     // (ONE write per MFMA slot -- NE = 4 n + e: tools/ubench/mfma_fillers.hip: two LDS writes in a gap are free, four cost 16 cycles)
     auto stage_store = [&](auto NE) __attribute__((always_inline)) {
         constexpr int n = decltype(NE)::value >> 2, e = decltype(NE)::value & 3;
-        if (W4_ABL & 1) return;
         constexpr int off = (n >> 1) * W4_PS * 4;
         static_assert(off + 12 < 65536, "ds_write_b32 immediate offset");
         const unsigned addr = swb[n & 1];                   // (locals: asm operands do not capture in a generic lambda)
@@ -284,31 +249,26 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         // (pins: everything below stays behind this point -- the loads have landed -- and in front of the next MFMA)
         asm volatile("" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(ra[5]));
         asm volatile("" : "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]), "+v"(rb[4]), "+v"(rb[5]));
-        if (W4_ABL & 16) {
+        f32x2 r[6];
 #pragma unroll
-            for (int c = 0; c < 6; ++c) v[c] = ra[c];
-        } else {
-            f32x2 r[6];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                r[c] = sgn2 * rb[c] + ra[c];
-                // (columns 0 and 1 of a tile that has any pixel inside the image are inside it)
-                if (EDGE && c >= 2) {
-                    const bool ok = c < nvalid;
-                    r[c].x = ok ? r[c].x : 0.f;
-                    r[c].y = ok ? r[c].y : 0.f;
-                }
+        for (int c = 0; c < 6; ++c) {
+            r[c] = sgn2 * rb[c] + ra[c];
+            // (columns 0 and 1 of a tile that has any pixel inside the image are inside it)
+            if (EDGE && c >= 2) {
+                const bool ok = c < nvalid;
+                r[c].x = ok ? r[c].x : 0.f;
+                r[c].y = ok ? r[c].y : 0.f;
             }
-            // F(4,3) B^T:  [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
-            const f32x2 s24 = r[4] - 4.f * r[2], s13 = r[3] - 4.f * r[1];
-            const f32x2 u24 = r[4] - r[2], d31 = r[3] - r[1];
-            v[0] = 4.f * r[0] + (r[4] - 5.f * r[2]);
-            v[1] = s24 + s13;
-            v[2] = s24 - s13;
-            v[3] = u24 + 2.f * d31;
-            v[4] = u24 - 2.f * d31;
-            v[5] = 4.f * r[1] + (r[5] - 5.f * r[3]);
         }
+        // F(4,3) B^T:  [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
+        const f32x2 s24 = r[4] - 4.f * r[2], s13 = r[3] - 4.f * r[1];
+        const f32x2 u24 = r[4] - r[2], d31 = r[3] - r[1];
+        v[0] = 4.f * r[0] + (r[4] - 5.f * r[2]);
+        v[1] = s24 + s13;
+        v[2] = s24 - s13;
+        v[3] = u24 + 2.f * d31;
+        v[4] = u24 - 2.f * d31;
+        v[5] = 4.f * r[1] + (r[5] - 5.f * r[3]);
         asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
     };
 
@@ -407,7 +367,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         }
     };
     auto ep_store = [&](const __amdgpu_buffer_rsrc_t& r, int pp, int soff, f32x4 vv) __attribute__((always_inline)) {
-        if (W4_ABL & (256 | 4096)) { asm volatile("" ::"v"(vv)); return; }
         const u32x4 u = __builtin_bit_cast(u32x4, vv);
         if constexpr (EE == 0) {
             // (store + one wait state as ONE asm: a 16-byte buffer store reads its data registers after it has issued,
@@ -433,10 +392,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
     const float* xread = sX + tile * 16 + kqr * 4 + hf * 2;
 
     for (;;) {
-#ifdef W4_TIMING
-        const bool seg = l == 3 && blockIdx.x < 256;
-#endif
-        W4_SEG(0);
         Wino4Item nx;
         l += 1;
         const bool have_next = decode(l, nx);
@@ -465,7 +420,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         auto ep_fetch = [&](auto SET, int m0, const __amdgpu_buffer_rsrc_t& rop, const __amdgpu_buffer_rsrc_t& rbias)
                             __attribute__((always_inline)) {
             constexpr int set = decltype(SET)::value;
-            if (W4_ABL & (256 | 2048)) return;
             if (ACT != 2)
                 bsv[set] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rbias, cg * 4, (cb_ch + m0 * 16) * 4, 0));
 #pragma unroll
@@ -475,9 +429,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         };
         auto chunk = [&](int c, auto ZC) __attribute__((always_inline)) {
             constexpr bool zc = decltype(ZC)::value;     // the item's first chunk: its k-step 0 starts the sums (C = 0)
-#ifdef W4_KSTAMP
-            const bool kst = l == 4 && c == 2 && blockIdx.x < 256;
-#endif
             const bool last = __builtin_amdgcn_readfirstlane(c + 1 == nch) != 0;
             if (last) make_goff(nx);
             const int dch = last ? 0 : c + 1;
@@ -487,11 +438,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
             const int w_pre[4] = {wcur + 2 * W3_KS_BYTES, wcur + 3 * W3_KS_BYTES, wnext, wnext + W3_KS_BYTES};
             if (last) sstage = base_nx;
             const bool live = dval && dch * 16 + wi * 4 < p.Cin;
-            rs_st = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sstage), 0, live && !(W4_ABL & 32) ? 4 * (int)HW4 : 0, 0x00020000);
-            if (W4_ABL & 128) {
-                rs_st = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(last ? base_nx : plane_ptr(it.b)), 0, live ? (1 << 26) : 0, 0x00020000);
-                lin_soff = ((last ? tile_lin(nx) : tile_lin(it)) * nch + dch) * 8192;
-            }
+            rs_st = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sstage), 0, live ? 4 * (int)HW4 : 0, 0x00020000);
             w4_static_for<4>([&](auto KS) __attribute__((always_inline)) {
                 constexpr int ks = decltype(KS)::value;
                 if constexpr (ks == 3) {
@@ -511,10 +458,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
                 // 60 slots: one MFMA + the non-VALU fillers dealt to its gap
                 w4_static_for<2 * MT * W3_NF>([&](auto S) __attribute__((always_inline)) {
                     constexpr int s = decltype(S)::value;
-                    if constexpr (s % 8 == 0) W4_KS(ks, s / 8);                   // stamps 0..7: slots 0, 8, .. 56
-                    if constexpr (s == W4_XF_SLOT + 1) W4_KS(ks, 9);             // behind the transform burst
-                    if constexpr (s == 59) W4_KS(ks, 10);
-                    if constexpr (s >= 42 && s <= 46) W4_KS(ks, 11 + s - 42);       // slots 42..46 one by one
                     constexpr int idx = s >> 1, h = s & 1;
                     constexpr int pos = idx + (idx >= 15 ? 1 : 0);          // slot of the packed order (15 and 31 are padding)
                     constexpr int e = w3_pos_e(pos);
@@ -522,12 +465,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
                     if constexpr ((pos >> 2 & 3) != 3) w4_mfma<(h * MT + mt) * W3_NF + j, zc && ks == 0>(aq[ks & 1][pos >> 2][pos & 3], v[ks & 1][j][h]);
                     else w4_mfma<(h * MT + mt) * W3_NF + j, zc && ks == 0>(aq3[ks & 1][pos >> 4][pos & 3], v[ks & 1][j][h]);
                     // raw-patch reads of the next k-step: slots 0..23
-                    if constexpr (s < 24 && !(W4_ABL & 4)) {
+                    if constexpr (s < 24) {
                         constexpr int hh = s & 1, m = s >> 1, cc = m >> 1, wh = m & 1;
                         raw[wh][cc][hh] = lds_ld(rd[wh][hh], rd_off + cc);
                     }
                     // input transform of the next k-step: one packed burst
-                    if constexpr (s == W4_XF_SLOT) W4_KS(ks, 8);
                     if constexpr (s == W4_XF_SLOT) xf_burst(raw[0], raw[1], v[(ks + 1) & 1], mk);
                     // raw-tile staging of the next chunk, four 16-byte groups per batch: loaded in k-step 0 / 1, written
                     // to LDS a k-step later
@@ -542,11 +484,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
                     // pass-0 operands of the epilogue, requested late in the item's LAST chunk (W4_PF_KS, W4_PF_SLOT: ahead of
                     // their use) behind a uniform branch (issued in every chunk through an empty descriptor, twelve such
                     // loads cost ~600 cycles per chunk)
-                    if constexpr (ks == W4_PF_KS && s == W4_PF_SLOT && !(W4_ABL & 8)) {
+                    if constexpr (ks == W4_PF_KS && s == W4_PF_SLOT) {
                         if (last) ep_fetch(std::integral_constant<int, 0>{}, 0, rs_op, rs_bias);
                     }
                     // weight refills: a group is free behind the MFMAs of its last slot
-                    if constexpr (!(W4_ABL & 2) && h == 1 && ((pos & 3) == 3 || pos == 14 || pos == 30)) load_a(ks & 1, pos >> 2, w_pre[ks]);
+                    if constexpr (h == 1 && ((pos & 3) == 3 || pos == 14 || pos == 30)) load_a(ks & 1, pos >> 2, w_pre[ks]);
                     __builtin_amdgcn_sched_barrier(0);
                 });
             });
@@ -556,7 +498,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         chunk(0, std::true_type{});
         for (int c = 1; c < nch; ++c) chunk(c, std::false_type{});
 
-        W4_SEG(1);
         // ---- output transform + epilogue, one m-tile (16 channels) per pass.  Writer half (every wave, its frequency row
         // i): the m-tile's 48 accumulators are read FOUR CHANNELS AT A TIME (the registers of an accumulator tile), the
         // column transform A4 (6 -> 4) runs as packed fp32 on those channel vectors and each of the four results goes to LDS
@@ -564,7 +505,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         // and finishes (bias, residual / GELU / GELU', stores).  Two exchange buffers: m-tile p + 1 is transformed and
         // written between the issue of p's LDS reads and their use -- one barrier per pass.  The accumulators are not
         // zeroed: the next item's first k-step runs with C = 0. ----
-        if (!(W4_ABL & 8)) {
         // (the accumulators of m-tiles 0 / 1 were last written 36+ MFMAs ago; the nops cover the tail of the matrix pipe)
         asm volatile("s_nop 15\n\ts_nop 15");
         if constexpr (W4_PF_SLOT < 0) ep_fetch(std::integral_constant<int, 0>{}, 0, rs_op, rs_bias);
@@ -584,7 +524,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
                 const f32x4 s12 = m_[1] + m_[2], d12 = n4 * m_[2] + m_[1], s34 = m_[3] + m_[4], d34 = n4 * m_[4] + m_[3];
                 float* d = xwrite + (m0 & 1) * W4_XB + h * 16 * 16;
                 const f32x4 t0 = m_[0] + s12 + s34, t1 = 2.f * d34 + d12, t2 = 4.f * s34 + s12, t3 = 8.f * d34 + d12 + m_[5];
-                if (W4_ABL & 512) { asm volatile("" ::"v"(t0), "v"(t1), "v"(t2), "v"(t3)); return; }
                 *reinterpret_cast<f32x4*>(d) = t0;
                 *reinterpret_cast<f32x4*>(d + 512) = t1;
                 *reinterpret_cast<f32x4*>(d + 1024) = t2;
@@ -595,22 +534,19 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         w4_static_for<MT>([&](auto M0) __attribute__((always_inline)) {
             constexpr int m0 = decltype(M0)::value;
             constexpr int set = m0 % NS;
-            W4_SEG(2 + 3 * m0);
             // operands of a LATER pass, W4_PF_AHEAD passes ahead of their use (into the set the previous pass has just used)
             if constexpr (m0 + W4_PF_AHEAD < MT)
                 ep_fetch(std::integral_constant<int, (m0 + W4_PF_AHEAD) % NS>{}, m0 + W4_PF_AHEAD, rs_op, rs_bias);
             lds_barrier();                          // m-tile m0 is in its buffer; the other buffer has been read
-            W4_SEG(3 + 3 * m0);
             const float* xr = xread + (m0 & 1) * W4_XB;
             f32x2 tt[4][4];                         // [i][column] x channel pair
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    tt[i][q] = (W4_ABL & 1024) ? f32x2{n1.x * (i + q), n1.y} : *reinterpret_cast<const f32x2*>(xr + (i * 4 + q) * 512);
+                    tt[i][q] = *reinterpret_cast<const f32x2*>(xr + (i * 4 + q) * 512);
             // (behind the reads in the LDS queue, and beside their latency: the next m-tile's writer half)
             if constexpr (m0 + 1 < MT) colxf(std::integral_constant<int, m0 + 1>{});
-            W4_SEG(4 + 3 * m0);
             f32x2 y0[4], y1[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -645,8 +581,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
         // reader geometry of the next item (VALU here, where nothing is hidden anyway, instead of in its main loop)
         ep_geo(nx, vo_nx);
         if (padded) pm = pad_mask(nx);
-        W4_SEG(20);
-        }
         if (!have_next) break;
         it = nx;                                   // goff already describes nx
 #pragma unroll
@@ -658,9 +592,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(ConvArgs p, int item
     }
 }
 
-#ifndef SINDDM_V4_MIN_ITEMS_PER_CU   // launches with at least this many (8x32 tile, 80-channel block) items per CU take conv_wino4.h
-#define SINDDM_V4_MIN_ITEMS_PER_CU 2
-#endif
+constexpr int SINDDM_V4_MIN_ITEMS_PER_CU = 2;   // launches with at least this many (8x32 tile, 80-channel block) items per CU take conv_wino4.h
 
 inline bool conv_wino4_applies(int B, int H, int W, int coblks, int ncu) {
     return (long long)B * ((W + W4_TW - 1) / W4_TW) * ((H + W4_TH - 1) / W4_TH) * coblks >=
@@ -676,10 +608,6 @@ inline int conv_wino4_launch(const ConvArgs& a_in, hipStream_t st) {
     a.ntiles = a.B * a.tilesX * a.tilesY;
     a.tiles_per_xcd = (a.ntiles + 7) / 8;
     a.mtp = W3_MT;
-#if defined(W4_TIMING) || defined(W4_KSTAMP)
-    static int w4_launch_no = 0;
-    a.mtp = w4_launch_no++ % 8;                  // (the kernel does not read mtp: stamp row of this launch)
-#endif
     const int ipx = a.tiles_per_xcd * a.coblks;
     int wpx = cu_count() / 8;              // one workgroup per CU
     if (wpx < 1) wpx = 1;

@@ -34,7 +34,6 @@ struct WgradArgs {
     int B, H, W, Cin, Cout;
     int coblks, ciblks, S;
     int tilesX, tilesY, ntiles;
-    int abl;             // ablation bits (tuning only): 1 = skip the steady-state DMA, 2 = skip the epilogue
     int scr;             // 1: gw is a [co][tap][ci] staging slab (wgrad3x3_kernel only)
 };
 
@@ -276,7 +275,7 @@ __global__ __launch_bounds__(W3_THREADS) void wgrad3x3_kernel(WgradArgs p) {
         dma_barrier();          // DMA of `tile` landed (dma_barrier: vmcnt(0) + barrier); previous tile consumed
         const float* cur = smem + (it & 1) * W3_BUF;
         float* nxt = smem + ((it + 1) & 1) * W3_BUF;
-        const bool pf = tile + p.S < p.ntiles && !(p.abl & 1);
+        const bool pf = tile + p.S < p.ntiles;
         TileAddr ta{};
         if (pf) ta = tile_addr(tile + p.S);
         if (!active) {
@@ -325,7 +324,7 @@ __global__ __launch_bounds__(W3_THREADS) void wgrad3x3_kernel(WgradArgs p) {
     // ---- every wave owns its slab: one atomic per element; the pixel splits meet in L2 / memory ----
     // scr != 0: [co][tap][ci] staging slab, 16 lanes of a wave hit one 64-byte line (coalesced atomics);
     // scr == 0: straight into the [co][ci][tap] gradient (36-byte lane stride).
-    if (active && !(p.abl & 2)) {
+    if (active) {
         const int ci = ci0 + cit * 16 + l16;
         if (ci < p.Cin) {
 #pragma unroll
@@ -498,7 +497,7 @@ static int wgrad_launch(const WgradPlan& p, const float* zero, const float* dout
         a.B = p.B; a.H = p.H; a.W = p.W; a.Cin = p.Cin; a.Cout = p.Cout;
         a.coblks = p.coblks; a.ciblks = p.ciblks; a.S = p.S;
         a.tilesX = p.tilesX; a.tilesY = p.tilesY; a.ntiles = p.ntiles;
-        a.abl = SINDDM_WGRAD_ABL; a.scr = p.staged;
+        a.scr = p.staged;
         const bool m2 = mt_for(p.Cout) == 2;
         void (*const kernel)(WgradArgs) = p.kernel == WGRAD_SLAB1 ? wgrad1x1_kernel : p.kernel == WGRAD_SLAB3 ? wgrad3x3_kernel
             : p.taps == 9 ? (m2 ? wgrad_mfma_kernel<2, 9> : wgrad_mfma_kernel<1, 9>)

@@ -282,15 +282,9 @@ __global__ __launch_bounds__(128) void cond_kernel(CondArgs a) {
 // kernel is as much VALU- as bandwidth-limited (25 FMA per 8 bytes).  With flip=1 the taps are mirrored (transposed
 // conv = data gradient) and `addt` is added to the result (residual-path gradient).
 // =====================================================================================
-#ifndef DW_RW_
-#define DW_RW_ 4
-#endif
-constexpr int DW_RW = DW_RW_;             // output rows per wave
+constexpr int DW_RW = 4;                  // output rows per wave
 constexpr int DW_TH = 4 * DW_RW, DW_TW = 128, DW_RS = DW_TW + 4, DW_HR = DW_TH + 4;
-#ifndef DW_NX_
-#define DW_NX_ 2
-#endif
-constexpr int DW_NX = DW_NX_;   // x-tiles per workgroup: all their loads are in flight together (latency-bound otherwise)
+constexpr int DW_NX = 2;        // x-tiles per workgroup: all their loads are in flight together (latency-bound otherwise)
 
 __global__ __launch_bounds__(256) void dwconv5_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ bias, const float* __restrict__ cond,
@@ -398,10 +392,7 @@ __global__ __launch_bounds__(256) void dwconv5_kernel(const float* __restrict__ 
 // input row, then tap column); the 25 taps are wave-uniform (scalar registers).  Every load of a lane is independent of its
 // FMAs, so many rows are in flight per wave.  (Side quads from memory instead, profiles/NOTES_r22.md: +4 % time, three
 // times the L1 requests.)
-#ifndef DWR_ROWS_
-#define DWR_ROWS_ 16     // (16 rows re-read 4 halo rows: 170 VGPRs, two waves per SIMD, and still faster than 12 or 8 rows at three or four)
-#endif
-constexpr int DWR_ROWS = DWR_ROWS_;
+constexpr int DWR_ROWS = 16;   // (16 rows re-read 4 halo rows: 170 VGPRs, two waves per SIMD, and still faster than 12 or 8 rows at three or four)
 
 // lane i takes `src` of lane i - 1 (wave_shr:1) / lane i + 1 (wave_shl:1); the lane without such a neighbour keeps `old`
 __device__ __forceinline__ float dpp_wave_shr1(float old, float src) {
@@ -1880,40 +1871,6 @@ int sinddm_reverse_step_layout(const float* x_t, const float* eps, const float* 
     return sc.rc ? sc.rc : layout_step_launch(sc.io, sc.t, la);
 }
 
-#ifdef W2_PHASE
-int sinddm_debug_w2_seg(unsigned long long* host_dst, int n) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_w2_seg), sizeof(unsigned long long) * n);
-}
-int sinddm_debug_w2_phase(unsigned long long* host_dst, int n) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_w2_phase), sizeof(unsigned long long) * n);
-}
-#endif
-#ifdef WH_TIMING
-int sinddm_debug_wh_seg(unsigned long long* host_dst, int n) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_wh_seg), sizeof(unsigned long long) * n);
-}
-#endif
-#ifdef W4_TIMING
-int sinddm_debug_w4_seg(unsigned long long* host_dst, int n) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_w4_seg), sizeof(unsigned long long) * n);
-}
-#endif
-#ifdef W4_KSTAMP
-int sinddm_debug_w4_ks(unsigned long long* host_dst, int n) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_w4_ks), sizeof(unsigned long long) * n);
-}
-#endif
-#ifdef W2_TIMING
-int sinddm_debug_w2_timing(unsigned long long* host_dst, int n) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_w2_dbg), sizeof(unsigned long long) * n);
-}
-#endif
-#ifdef SINDDM_WINO_TIMING
-int sinddm_debug_wino_timing(unsigned long long* host_dst, int n) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_wino_dbg), sizeof(unsigned long long) * n);
-}
-#endif
-
 int sinddm_prof_begin(void) {
     ConvProfiler& p = conv_profiler();
     p.on = true;
@@ -2004,7 +1961,7 @@ int sinddm_debug_head(const float* packed, const float* g, const float* x_in, fl
 
 // the three regions sinddm_debug_conv_wh carves from its scratch, each rounded to 256 bytes: packed image, wsinv, maxima
 static size_t wh_debug_round(size_t v) { return (v + 255) / 256 * 256; }
-static bool wh_debug_shape_ok(int Cin, int Cout, int B) { return B >= 1 && B <= 65535 && Cin >= 32 && Cin % 16 == 0 && Cout >= 80 && Cout % 80 == 0; }
+static bool wh_debug_shape_ok(int Cin, int Cout, int B) { return B >= 1 && B <= 65535 && wh_plan_ok(Cin, Cout) && Cout >= 80; }
 
 size_t sinddm_debug_conv_wh_scratch_bytes(int Cin, int Cout, int B) {
     if (!wh_debug_shape_ok(Cin, Cout, B)) return 0;

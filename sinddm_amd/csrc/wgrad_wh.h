@@ -29,11 +29,6 @@ namespace sinddm {
 using wgh8 = __attribute__((ext_vector_type(8))) _Float16;
 using wgh4 = __attribute__((ext_vector_type(4))) _Float16;
 
-// compile-time timing ablations (-DWGH_ABL=bits; results are WRONG, never ship):
-//   1 no DMA traffic (empty descriptors)   2 no LDS operand reads   4 no DMA instructions   8 no MFMAs   16 no split (one conversion per value)
-#ifndef WGH_ABL
-#define WGH_ABL 0
-#endif
 constexpr int WGH_TARGET_EXP = 12;
 
 __device__ __forceinline__ int wgh_shift_for(float m) {
@@ -48,13 +43,11 @@ __device__ __forceinline__ float wgh_pow2(int s) { return __uint_as_float((unsig
 // (volatile, as ww_ld2: no compiler-inserted vmcnt wait in front of reads of an LDS-DMA destination; the tile barrier publishes)
 __device__ __forceinline__ f32x4 wgh_ld4(const float* q) {
     typedef const volatile __attribute__((address_space(3))) f32x4* lds_v4;
-    if (WGH_ABL & 2) return f32x4{1.f, 2.f, 3.f, 4.f};
     return *(lds_v4)q;
 }
 __device__ __forceinline__ void wgh_split(f32x4 v, float sc, wgh4& hi, wgh4& lo) {
     const f32x4 s = v * sc;
     hi = __builtin_convertvector(s, wgh4);
-    if (WGH_ABL & 16) { lo = hi; return; }
     // remainder as one fused multiply-add per value with the binary16 piece as an operand (v_fma_mix_f32): v * sc is exact
     // (power of two), so fma(v, sc, -hi) = s - hi exactly
     f32x4 r;
@@ -200,11 +193,9 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wh_kernel(WwArgs p) {
             // This tile's three DMA instructions of this wave have landed (vector memory returns in order: at most the three of
             // tile + 1 are still in flight -- they keep two tile times to land); every wave is done with the reads of tile - 1.
             asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            const TileAddr ta = next_tile(tile + 2 < t_end && !(WGH_ABL & 1));
-            if (!(WGH_ABL & 4)) {
+            const TileAddr ta = next_tile(tile + 2 < t_end);
 #pragma unroll
-                for (int sl = 0; sl < 3; ++sl) issue(ta, b2, sl);
-            }
+            for (int sl = 0; sl < 3; ++sl) issue(ta, b2, sl);
             const float* buf = b0;
             // ---- B fragments of the tile: V of 16 input channels per n-tile, this lane's 4 tiles ----
             wgh8 bv[NNT];             // [V_hi (4 tiles) | V_lo (4 tiles)]
@@ -249,7 +240,6 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wh_kernel(WwArgs p) {
                 const wgh8 al = __builtin_shufflevector(lo, lo, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
                 for (int nt = 0; nt < NNT; ++nt) {
-                    if (WGH_ABL & 8) { acc[mt][nt].x += (float)ah[0] + (float)al[5] + (float)bv[nt][1]; continue; }
                     acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bv[nt], acc[mt][nt], 0, 0, 0);     // dM_lo x (V_hi + V_lo)
                     acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bv[nt], acc[mt][nt], 0, 0, 0);     // dM_hi x (V_hi + V_lo)
                 }

@@ -25,17 +25,10 @@
 
 namespace sinddm {
 
-// compile-time timing ablations (-DSINDDM_WW_ABL=bits; results are wrong): 1 no DMA traffic after the first tiles (instructions still issue, empty descriptor), 2 no operand reads, 4 no DMA instructions
-#ifndef SINDDM_WW_ABL
-#define SINDDM_WW_ABL 0
-#endif
-
 constexpr int WW_STAGES = 3;                         // LDS ring: tile T is read while T+1 is visible and T+2 is in flight
-#ifndef WW_SPLIT_C0
-#define WW_SPLIT_C0 1      // fixed per-tile cost of a slab (DMA issue, barrier) in n-tile units.  Training step, same box:
+constexpr int WW_SPLIT_C0 = 1;   // fixed per-tile cost of a slab (DMA issue, barrier) in n-tile units.  Training step, same box:
                              // one split count for all slabs 45.9 ms; cost = n-tiles + 8 / 4 / 2: 45.0 / 44.6 / 44.3; pipelined loop with
                              // + 4 / 2 / 1 / 0: 43.3 / 42.9 / 42.65 / 47.6 (a 16-channel slab's tile is bound by its 96 DMA instructions)
-#endif
 constexpr int WW_THREADS = 1024;
 constexpr int WW_CO = 80, WW_CI = 48;
 constexpr int WW_TW = 16, WW_TH = 4;                 // pixel tile = 2 x 8 2x2-tiles (4 k-steps of 4 tile columns)
@@ -318,16 +311,14 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_kernel(WwArgs p) {
 #pragma unroll
             for (int mt = 0; mt < 5; ++mt) {
                 const float* q = qd + mt * 16 * WW_PSO;
-                if (SINDDM_WW_ABL & 2) a[mt] = as0 * (float)(j + mt);
-                else if constexpr (aterms == 4) a[mt] = as0 * q[oa0] + as1 * q[oa1] + as2 * q[oa2] + as3 * q[oa3];
+                if constexpr (aterms == 4) a[mt] = as0 * q[oa0] + as1 * q[oa1] + as2 * q[oa2] + as3 * q[oa3];
                 else if constexpr (aterms == 2) a[mt] = as0 * q[oa0] + as1 * q[oa1];
                 else a[mt] = as0 * q[oa0];
             }
 #pragma unroll
             for (int nt = 0; nt < NNT; ++nt) {
                 const float* qx = buf + bbase + nt * 16 * WW_PSI + (j >> 1) * 36 + (j & 1) * 4;
-                bv[nt] = (SINDDM_WW_ABL & 2) ? b00 * (float)(j - nt)
-                                             : b00 * qx[ob00] + b01 * qx[ob01] + b10 * qx[ob10] + b11 * qx[ob11];
+                bv[nt] = b00 * qx[ob00] + b01 * qx[ob01] + b10 * qx[ob10] + b11 * qx[ob11];
             }
         };
         float a[2][5], bv[2][NNT];
@@ -335,13 +326,11 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_kernel(WwArgs p) {
         build(b0, 0, a[0], bv[0]);
         for (int tile = t_begin; tile < t_end; ++tile) {
             dma_barrier();            // tile + 1 landed and is visible; every wave is done with the reads of tile - 1
-            const TileAddr ta = (SINDDM_WW_ABL & 1) ? tile_addr_or_null(false) : tile_addr_or_null(tile + 2 < t_end);
+            const TileAddr ta = tile_addr_or_null(tile + 2 < t_end);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {              // k-step: tile columns 4j .. 4j+3 (lane group kq)
-                if (!(SINDDM_WW_ABL & 4)) {
-                    issue_group(ta, b2, j);
-                    if (j < 2) issue_group(ta, b2, j + 4);
-                }
+                issue_group(ta, b2, j);
+                if (j < 2) issue_group(ta, b2, j + 4);
                 if (j < 3) build(b0, j + 1, a[(j + 1) & 1], bv[(j + 1) & 1]);
                 else build(b1, 0, a[0], bv[0]);        // (behind the last tile: values nobody uses)
                 if constexpr (XI == 5) {               // frequency (1,1): dM = sum of the 2x2 block = the bias gradient
@@ -527,16 +516,14 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_wide_kernel(WwArgs p) {
             const int tr = j >> 1, jc = j & 1;
 #pragma unroll
             for (int mt = 0; mt < 5; ++mt) {
-                if (SINDDM_WW_ABL & 2) continue;
                 const float* qd = buf + abase + (mt * 4 + 2 * tr) * 256 + 128 * jc;
                 if constexpr (NRA == 2) { ra[mt][0] = ww_ld2(qd); ra[mt][1] = ww_ld2(qd + 256); }
                 else ra[mt][0] = ww_ld2(qd + (need_r0 ? 0 : 256));
             }
         };
-        auto comb_a = [&](int j, const f32x2 (&ra)[5][NRA], float (&a)[5]) {
+        auto comb_a = [&](const f32x2 (&ra)[5][NRA], float (&a)[5]) {
 #pragma unroll
             for (int mt = 0; mt < 5; ++mt) {
-                if (SINDDM_WW_ABL & 2) { a[mt] = (float)(j + mt); continue; }
                 if constexpr (NRA == 2) a[mt] = colmix(fi == 1 ? ra[mt][0] + ra[mt][1] : ra[mt][0] - ra[mt][1], 1.f);
                 else a[mt] = colmix(ra[mt][0], need_r0 ? 1.f : -1.f);
             }
@@ -545,7 +532,6 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_wide_kernel(WwArgs p) {
             const int tr = j >> 1, jc = j & 1;
 #pragma unroll
             for (int nt = 0; nt < NNT; ++nt) {
-                if (SINDDM_WW_ABL & 2) continue;
                 const int o0 = nt * 2304 + 64 * (6 * (2 * tr + pa0) + 2 * jc);
                 const int o1 = nt * 2304 + 64 * (6 * (2 * tr + pa1) + 2 * jc);
                 rb[nt][0] = ww_ld2(buf + vb0 + o0);
@@ -556,10 +542,9 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_wide_kernel(WwArgs p) {
                 }
             }
         };
-        auto comb_b = [&](int j, const f32x2 (&rb)[NNT][NRB], float (&bv)[NNT]) {
+        auto comb_b = [&](const f32x2 (&rb)[NNT][NRB], float (&bv)[NNT]) {
 #pragma unroll
             for (int nt = 0; nt < NNT; ++nt) {
-                if (SINDDM_WW_ABL & 2) { bv[nt] = (float)(j - nt); continue; }
                 const f32x2 u = sa0 * rb[nt][0] + sa1 * rb[nt][1];
                 if constexpr (two_pairs) {
                     const f32x2 v = sa0 * rb[nt][2] + sa1 * rb[nt][3];
@@ -578,15 +563,15 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_wide_kernel(WwArgs p) {
         f32x2 ra[5][NRA], rb[NNT][NRB];
         dma_barrier();                // tile t_begin landed
         load_a(b0, 0, ra); load_b(b0, 0, rb);
-        comb_a(0, ra, a[0]); comb_b(0, rb, bv[0]);
+        comb_a(ra, a[0]); comb_b(rb, bv[0]);
         for (int tile = t_begin; tile < t_end; ++tile) {
             dma_barrier();            // tile + 1 landed and is visible; every wave is done with the reads of tile - 1
-            const TileAddr ta = next_tile(tile + 2 < t_end && !(SINDDM_WW_ABL & 1));
+            const TileAddr ta = next_tile(tile + 2 < t_end);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {              // k-step: tile columns 4j .. 4j+3 (lane group kq)
                 const float* nbuf = j < 3 ? b0 : b1;   // next k-step's tile (behind the last tile: values nobody uses)
                 const int nj = (j + 1) & 3;
-                if (j < 3 && !(SINDDM_WW_ABL & 4)) issue(ta, b2, j);
+                if (j < 3) issue(ta, b2, j);
                 load_a(nbuf, nj, ra);
                 if (NNT == 1) load_b(nbuf, nj, rb);
                 if constexpr (XI == 5) {               // frequency (1,1): dM = sum of the 2x2 block = the bias gradient
@@ -596,7 +581,7 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_wide_kernel(WwArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_nt(0, a[j & 1], bv[j & 1]);
                 __builtin_amdgcn_sched_barrier(0);
-                comb_a(nj, ra, a[(j + 1) & 1]);
+                comb_a(ra, a[(j + 1) & 1]);
                 if (NNT > 1) {
                     load_b(nbuf, nj, rb);
                     __builtin_amdgcn_sched_barrier(0);
@@ -604,7 +589,7 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad_wino_wide_kernel(WwArgs p) {
                     for (int nt = 1; nt < NNT; ++nt) mfma_nt(nt, a[j & 1], bv[j & 1]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                comb_b(nj, rb, bv[(j + 1) & 1]);
+                comb_b(rb, bv[(j + 1) & 1]);
             }
             float* t = b0; b0 = b1; b1 = b2; b2 = t;
         }

@@ -10,7 +10,7 @@
 // (profiles/NOTES_r04.md section 9).  Experimental: compiled only with -DSINDDM_WINO_F44_BUILD=1, dispatched only behind
 // sinddm_debug_set_f44().  Its loads are asm the compiler does not track ("=v" outputs, AGPR destinations, LDS-DMA) with
 // the kernel's own vmcnt bookkeeping: correct in this build, but nothing stops a compiler from copying such a value
-// before the kernel's wait (the -DW4_TIMING / -DW4_KSTAMP builds of this file fault) -- pin the registers before shipping.
+// before the kernel's wait (builds of this file with s_memtime stamps inside the k-steps faulted) -- pin the registers before shipping.
 //
 // Skeleton of conv_wino4.h (one persistent 4-wave workgroup per CU, a wave owns its SIMD and 512 registers, an item is
 // an 8x32-pixel tile x 80 output channels, raw halo tile 16 channels x 10 rows x 40 columns double-buffered in LDS,
@@ -120,13 +120,6 @@ constexpr int W6_A3 = 226;                      // ring stage 3: fragments 0..27
 constexpr int W6_G3 = 7;                        // first group of stage 3 that lives in VGPRs
 constexpr int W6_G1 = 6;                        // first group of stage 1 whose refill an item's last chunk leaves to the end of the epilogue
 
-// timing ablations (-DW6_ABL=bits; results are WRONG, never ship): 1 no raw-tile staging  2 no weight refills  4 no raw-patch reads  16 no input transform  64 raw-tile requests to one L2-resident kilobyte
-#ifndef W6_ABL
-#define W6_ABL 0
-#endif
-#ifndef W4_SEG_ITEM
-#define W4_SEG_ITEM 3             // (-DW4_TIMING builds: the item of every workgroup whose segments are stamped)
-#endif
 #ifndef W6_XF_SLOT
 #define W6_XF_SLOT 30          // the slot behind whose MFMA the input-transform burst of the next k-step sits
 #endif
@@ -209,7 +202,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
     // DMA instruction n = 0..6 of a chunk: groups 64 n .. 64 n + 63 of this wave's region
     auto dma_n = [&](auto N, const __amdgpu_buffer_rsrc_t& rs) __attribute__((always_inline)) {
         constexpr int n = decltype(N)::value;
-        if (W6_ABL & 1) return;
         w6_dma<1024 * n>(dbase ^ rbuf, rs, goffd[n]);
     };
     // descriptor of chunk t of image b (empty beyond the last channel / when there is no such item)
@@ -262,7 +254,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
     // by the 39 of k-steps 0..2.  DMA -> chunk barrier: the last request (slot 20 of k-step 0) is followed by 7 + 12 + 12
     // refills (LAST: 7 + 6 + 12).
     auto chunk_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-    static_assert(!(W6_ABL & 2), "the vmcnt bookkeeping counts the weight refills");
     auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     // ---- input transform: 25 patch values -> the nine B operands of the block ----
@@ -286,11 +277,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
     auto xf_burst = [&](float (&vo_)[W6_NF]) __attribute__((always_inline)) {
 #pragma unroll
         for (int r = 0; r < 5; ++r) asm volatile("" : "+v"(raw[r][0]), "+v"(raw[r][1]), "+v"(raw[r][2]), "+v"(raw[r][3]), "+v"(raw[r][4]));
-        if (W6_ABL & 16) {
-#pragma unroll
-            for (int f = 0; f < W6_NF; ++f) vo_[f] = raw[f / 3][f % 3];
-            return;
-        }
         // rows: packed over column pairs (0,1), (2,3), (4,4)
         f32x2 P[5][3], O[3][3];
 #pragma unroll
@@ -392,10 +378,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
     const float* xread = sX + phalf * (2 * 3 * 256) + tile16 * 16 + kqr * 4 + hf * 2;
 
     for (;;) {
-#ifdef W4_TIMING
-        const bool seg = l == W4_SEG_ITEM && blockIdx.x < 256;
-#endif
-        W4_SEG(0);
         Wino4Item nx;
         l += 1;
         const bool have_next = decode(l, nx);
@@ -433,9 +415,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
         auto chunk = [&](int c, auto ZC, auto LAST) __attribute__((always_inline)) {
             constexpr bool zc = decltype(ZC)::value;
             constexpr bool last = decltype(LAST)::value;
-#ifdef W4_KSTAMP
-            const bool kst = l == 4 && c == 2 && blockIdx.x < 256;
-#endif
             const int wnext = last ? wb_nx : wcur + W6_CH_BYTES;
             // (stage ks is refilled with k-step ks of the next chunk / item)
             // raw tiles: k-step 0 issues the last 13 requests of chunk c + 1 (behind the last chunk: the next item's chunk 0),
@@ -470,9 +449,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
                 w4_static_for<W6_NPOS>([&](auto S) __attribute__((always_inline)) {
                     constexpr int pos = decltype(S)::value;
                     constexpr int f = pos % W6_NF;
-                    if constexpr (pos % 5 == 0) W4_KS(ks, pos / 5);                // stamps 0..8: slots 0, 5, .. 40
-                    if constexpr (pos == 44) W4_KS(ks, 9);
-                    if constexpr (pos == W6_XF_SLOT + 1) W4_KS(ks, 11);             // behind the transform burst
                     if constexpr (pos == 0) w6_wait<ks == 0 ? 40 : ks == 1 ? 43 : ks == 2 ? (last ? 37 : 43) : (last ? 33 : 39)>();
                     if constexpr (zc && ks == 1 && pos == 4 * W6_G1) w6_wait<26>();
                     if constexpr (ks < 2) {
@@ -486,8 +462,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
                         else w6_mfma<pos, false>(aq3s, v[ks & 1][f]);
                     }
                     // raw-patch reads of the next k-step: slots 0..24
-                    if constexpr (pos < 25 && !(W6_ABL & 4)) raw[pos / 5][pos % 5] = lds_ld(rdr[pos / 5], rd_off + pos % 5);
-                    if constexpr (pos == W6_XF_SLOT) W4_KS(ks, 10);
+                    if constexpr (pos < 25) raw[pos / 5][pos % 5] = lds_ld(rdr[pos / 5], rd_off + pos % 5);
                     if constexpr (pos == W6_XF_SLOT) xf_burst(v[(ks + 1) & 1]);
                     // raw-tile requests: one every ten slots
                     if constexpr (ks == 0 && pos % 10 == 0 && pos <= 20) dma_n(std::integral_constant<int, 4 + pos / 10>{}, rsd);
@@ -499,7 +474,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
                         }
                     }
                     // weight refills: a group is free behind the MFMA of its last slot
-                    if constexpr (!(W6_ABL & 2) && ((pos & 3) == 3 || pos == 44)) {
+                    if constexpr ((pos & 3) == 3 || pos == 44) {
                         // (the VGPR part of stage 3 is not needed before the next item's k-step 3, the second half of stage 1 not
                         // before the middle of its k-step 1: in an item's last chunk their refills wait until the epilogue -- which
                         // is where the register pressure peaks -- is over)
@@ -518,7 +493,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
         for (int c = 1; c + 1 < nch; ++c) chunk(c, std::false_type{}, std::false_type{});
         chunk(nch - 1, std::false_type{}, std::true_type{});
 
-        W4_SEG(1);
         // ---- output transform + epilogue, one m-tile (16 channels) per pass ----
         asm volatile("s_nop 15\n\ts_nop 15");
         // (the epilogue's descriptors are built here: carried through the main loop they were scalar spills)
@@ -558,10 +532,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
         w4_static_for<MT>([&](auto M0) __attribute__((always_inline)) {
             constexpr int m0 = decltype(M0)::value;
             constexpr int set = m0 & 1;
-            W4_SEG(2 + 3 * m0);
             if constexpr (m0 + 1 < MT) ep_fetch(std::integral_constant<int, (m0 + 1) & 1>{}, m0 + 1, rs_op, rs_bias);
             lds_barrier();                          // m-tile m0 is in its buffer; the other buffer has been read
-            W4_SEG(3 + 3 * m0);
             const float* xr = xread + (m0 & 1) * W6_XB;
             // (one output row at a time: twelve 8-byte reads -- the two a-halves of T[p][0..5] -- are live at once, not 24)
             f32x2 y[2][4];                          // [output row][column] x channel pair
@@ -582,7 +554,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
                 yo[2] = 4.f * s34 + s12;
                 yo[3] = 8.f * d34 + d12 + t[5];
             };
-            W4_SEG(4 + 3 * m0);
             cols(xa0, y[0]);
             {
                 f32x2 xa1[2][6];
@@ -621,7 +592,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino6_kernel(ConvArgs p, int item
         w4_static_for<W6_Q - W6_G3>([&](auto Q) __attribute__((always_inline)) {
             load_a(std::integral_constant<int, 3>{}, std::integral_constant<int, W6_G3 + decltype(Q)::value>{}, wb_nx + 3 * W6_KS_BYTES);
         });
-        W4_SEG(20);
         if (!have_next) break;
         it = nx;
         wb_it = wb_nx;
@@ -660,10 +630,6 @@ inline int conv_wino6_launch(const ConvArgs& a_in, hipStream_t st) {
     a.ntiles = a.B * a.tilesX * a.tilesY;
     a.tiles_per_xcd = (a.ntiles + 7) / 8;
     a.mtp = W6_MT;
-#if defined(W4_TIMING) || defined(W4_KSTAMP)
-    static int w6_launch_no = 0;
-    a.mtp = w6_launch_no++ % 8;                  // (the kernel does not read mtp: stamp row of this launch)
-#endif
     const int ipx = a.tiles_per_xcd * a.coblks;
     int wpx = wino2_cu_count() / 8;
     if (wpx < 1) wpx = 1;

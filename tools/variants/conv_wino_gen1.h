@@ -2,17 +2,6 @@
 // (SINDDM_WINO_V2 = 1) and the packed Winograd image has the second generation's layout.  Included by conv_wino.h only in
 // -DSINDDM_WINO_V2=0 variant builds (tools/build_variant.sh); not part of the default library.
 #pragma once
-// Compile-time timing ablations of the Winograd kernel (-DSINDDM_WINO_ABL=bits; results are WRONG, never ship):
-//   1 no LDS reads / V transform   2 weights loaded once   4 raw-tile DMA only for the first chunk
-//   8 no chunk barrier             16 no epilogue
-#ifndef SINDDM_WINO_ABL
-#define SINDDM_WINO_ABL 0
-#endif
-
-#ifdef SINDDM_WINO_TIMING
-// per-wave s_memtime stamps of the first work items of workgroup 0 (debug builds only; tools/wino_timing.py)
-__device__ unsigned long long g_wino_dbg[2 * 16 * 16 * 4];
-#endif
 
 constexpr int WN_THREADS = 1024;
 constexpr int WN_KC = 16;                      // input channels per chunk (4 k-steps)
@@ -127,7 +116,6 @@ __global__ __launch_bounds__(WN_THREADS) void conv_wino_kernel(ConvArgs p, int i
     // (chunk c, k-step ks) -> global k-step index; nothing is loaded (or multiplied) past the last real one
     auto load_w = [&](int slot, int cb, int c, int ks) {
         const int gk = c * NKS + ks;
-        if ((SINDDM_WINO_ABL & 2) && gk >= 2) return;
         if (gk >= nks_total) return;
         const int so = ((cb * nch16 + (gk >> 2)) * 16 + xi) * (4 * MT * 64 * 4) + (gk & 3) * (MT * 64 * 4);
 #pragma unroll
@@ -146,9 +134,6 @@ __global__ __launch_bounds__(WN_THREADS) void conv_wino_kernel(ConvArgs p, int i
     const int tr = lane >> 4, tc = lane & 15;   // epilogue role of a lane: 2x2 tile (tile-row, tile-col)
     const int lt = lane < WG::NTILES ? lane : 0;
 
-#ifdef SINDDM_WINO_TIMING
-    int dbg_item = 0;
-#endif
     for (;;) {
         f32x4 acc[MT][NTR];
 #pragma unroll
@@ -163,10 +148,6 @@ __global__ __launch_bounds__(WN_THREADS) void conv_wino_kernel(ConvArgs p, int i
         //   after k-step NKS-2      : load k-step 0 of the next chunk
         //   k-step NKS-1, barrier, then load k-step 1 of the next chunk -- needed one k-step later
         for (int c = 0; c < nch; ++c) {
-#ifdef SINDDM_WINO_TIMING
-            const bool dbg = blockIdx.x == 8 && dbg_item < 2 && c < 16 && lane == 0;
-            if (dbg) g_wino_dbg[((dbg_item * 16 + c) * 16 + xi) * 4 + 0] = __builtin_amdgcn_s_memtime();
-#endif
             const float* cur = smem + (c & 1) * WN_IN_LIN;
             const bool more = c + 1 < nch;
             if (c > 0) load_w(1, it.cb, c, 1);
@@ -182,10 +163,9 @@ __global__ __launch_bounds__(WN_THREADS) void conv_wino_kernel(ConvArgs p, int i
                 const bool live = (CPC == 1) || (c * NKS + ks < nks_total);
 #pragma unroll
                 for (int nt = 0; nt < NTR; ++nt) {
-                    const float bv = (SINDDM_WINO_ABL & 1) ? (float)(ks + nt) * s00
-                                                           : s00 * r4[0] + s01 * r4[1] + s10 * r4[2] + s11 * r4[3];
+                    const float bv = s00 * r4[0] + s01 * r4[1] + s10 * r4[2] + s11 * r4[3];
                     // next group (same k-step next tile-row, or first tile-row of the next k-step)
-                    if (!(SINDDM_WINO_ABL & 1) && (nt + 1 < NTR || ks + 1 < NKS)) {
+                    if (nt + 1 < NTR || ks + 1 < NKS) {
                         const int nks = (nt + 1 < NTR) ? ks : ks + 1;
                         const int nnt = (nt + 1 < NTR) ? nt + 1 : 0;
                         const float* q = cur + nks * 4 * WN_PS + nnt * 2 * WN_RS;
@@ -196,28 +176,16 @@ __global__ __launch_bounds__(WN_THREADS) void conv_wino_kernel(ConvArgs p, int i
                         for (int mt = 0; mt < MT; ++mt)
                             acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ks & 1][mt], bv, acc[mt][nt], 0, 0, 0);
                     }
-#ifdef SINDDM_WINO_TIMING
-                    if (ks == 0 && nt == 0 && dbg) g_wino_dbg[((dbg_item * 16 + c) * 16 + xi) * 4 + 3] = __builtin_amdgcn_s_memtime();
-#endif
                 }
                 if (ks < NKS - 2) load_w(ks & 1, it.cb, c, ks + 2);
-                if (ks == 1 && more && !(SINDDM_WINO_ABL & 4)) issue(it, c + 1, smem + ((c + 1) & 1) * WN_IN_LIN);
+                if (ks == 1 && more) issue(it, c + 1, smem + ((c + 1) & 1) * WN_IN_LIN);
                 if (ks == NKS - 2 && more) load_w(0, it.cb, c + 1, 0);
             }
             // pin the schedule here: left alone, the compiler sinks the last k-step's MFMAs below the barrier and
             // rotates the accumulators through spare registers (3.5% slower, measured A/B on one box)
             __builtin_amdgcn_sched_barrier(0);
-#ifdef SINDDM_WINO_TIMING
-            if (dbg) g_wino_dbg[((dbg_item * 16 + c) * 16 + xi) * 4 + 1] = __builtin_amdgcn_s_memtime();
-#endif
-            if (!(SINDDM_WINO_ABL & 8)) dma_barrier();
-#ifdef SINDDM_WINO_TIMING
-            if (dbg) g_wino_dbg[((dbg_item * 16 + c) * 16 + xi) * 4 + 2] = __builtin_amdgcn_s_memtime();
-#endif
+            dma_barrier();
         }
-#ifdef SINDDM_WINO_TIMING
-        ++dbg_item;
-#endif
 
         // next work item: start its first raw tile and weight registers now, so that they arrive while this
         // item's epilogue runs (raw buffer 0 is free: every wave passed the last chunk barrier)
@@ -230,88 +198,79 @@ __global__ __launch_bounds__(WN_THREADS) void conv_wino_kernel(ConvArgs p, int i
             issue(nx, 0, smem);
         }
 
-        if (!(SINDDM_WINO_ABL & 16)) {
-            // ---- output transform + epilogue, MPP 16-channel M tiles per pass ----
+        // ---- output transform + epilogue, MPP 16-channel M tiles per pass ----
 #pragma unroll
-            for (int m0 = 0; m0 < MT; m0 += MPP) {
-                // C layout: col = lane&15 -> tile-col, row = (lane>>4)*4 + r -> channel within the M tile
+        for (int m0 = 0; m0 < MT; m0 += MPP) {
+            // C layout: col = lane&15 -> tile-col, row = (lane>>4)*4 + r -> channel within the M tile
 #pragma unroll
-                for (int h = 0; h < MPP; ++h) {
-                    if (m0 + h < MT) {
+            for (int h = 0; h < MPP; ++h) {
+                if (m0 + h < MT) {
 #pragma unroll
-                        for (int nt = 0; nt < NTR; ++nt)
+                    for (int nt = 0; nt < NTR; ++nt)
 #pragma unroll
-                            for (int r = 0; r < 4; ++r)
-                                sM[(xi * (16 * MPP) + h * 16 + kq * 4 + r) * WN_MSTRIDE + nt * 16 + l16] = acc[m0 + h][nt][r];
-                    }
+                        for (int r = 0; r < 4; ++r)
+                            sM[(xi * (16 * MPP) + h * 16 + kq * 4 + r) * WN_MSTRIDE + nt * 16 + l16] = acc[m0 + h][nt][r];
                 }
-                // residual operands of this pass are fetched before the exchange so that their latency overlaps it
-                float rs_v[MPP][4];
-                size_t obase[MPP];
-#pragma unroll
-                for (int h = 0; h < MPP; ++h) {
-                    const int co = it.cb * (MT * 16) + (m0 + h) * 16 + xi;
-                    obase[h] = ((size_t)it.b * p.Cout + co) * HW + (size_t)(it.y0 + 2 * tr) * W + it.x0 + 2 * tc;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) rs_v[h][k] = 0.f;
-                    if (p.resid && m0 + h < MT && co < p.Cout && lane < WG::NTILES) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int y = it.y0 + 2 * tr + (k >> 1), x = it.x0 + 2 * tc + (k & 1);
-                            if (y < H && x < W) rs_v[h][k] = p.resid[obase[h] + (size_t)(k >> 1) * W + (k & 1)];
-                        }
-                    }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int h = 0; h < MPP; ++h) {
-                    if (m0 + h >= MT) break;
-                    const int col = (m0 + h) * 16 + xi;              // this wave's channel of the M tile
-                    const int co = it.cb * (MT * 16) + col;
-                    float m[16];
-#pragma unroll
-                    for (int f = 0; f < 16; ++f) m[f] = sM[(f * (16 * MPP) + h * 16 + xi) * WN_MSTRIDE + lt];
-                    if (co < p.Cout && lane < WG::NTILES) {
-                        // t[p][j] = sum_i A^T[p][i] m[i][j];  Y[p][q] = sum_j t[p][j] A^T[q][j]
-                        float t0[4], t1[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            t0[j] = m[0 * 4 + j] + m[1 * 4 + j] + m[2 * 4 + j];
-                            t1[j] = m[1 * 4 + j] - m[2 * 4 + j] - m[3 * 4 + j];
-                        }
-                        float yv[4];
-                        yv[0] = t0[0] + t0[1] + t0[2];
-                        yv[1] = t0[1] - t0[2] - t0[3];
-                        yv[2] = t1[0] + t1[1] + t1[2];
-                        yv[3] = t1[1] - t1[2] - t1[3];
-                        const float bvs = p.bias ? p.bias[it.cb * (MT * 16) + col] : 0.0f;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int y = it.y0 + 2 * tr + (k >> 1), x = it.x0 + 2 * tc + (k & 1);
-                            if (y < H && x < W) {
-                                const size_t o = obase[h] + (size_t)(k >> 1) * W + (k & 1);
-                                float v = yv[k] + bvs;
-                                if (ACT == 1) {
-                                    if (p.out_pre) p.out_pre[o] = v;
-                                    v = gelu_erf(v);
-                                } else if (ACT == 2) {
-                                    v *= gelu_erf_grad(p.aux[o]);
-                                }
-                                v += rs_v[h][k];
-                                p.out[o] = v;
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
             }
-        } else {
-            float sink = 0.f;                                   // keep every accumulator chain alive
+            // residual operands of this pass are fetched before the exchange so that their latency overlaps it
+            float rs_v[MPP][4];
+            size_t obase[MPP];
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
+            for (int h = 0; h < MPP; ++h) {
+                const int co = it.cb * (MT * 16) + (m0 + h) * 16 + xi;
+                obase[h] = ((size_t)it.b * p.Cout + co) * HW + (size_t)(it.y0 + 2 * tr) * W + it.x0 + 2 * tc;
 #pragma unroll
-                for (int nt = 0; nt < NTR; ++nt) sink += acc[mt][nt][0] + acc[mt][nt][1] + acc[mt][nt][2] + acc[mt][nt][3];
-            if (sink == 123.456f) p.out[tid] = sink;
+                for (int k = 0; k < 4; ++k) rs_v[h][k] = 0.f;
+                if (p.resid && m0 + h < MT && co < p.Cout && lane < WG::NTILES) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int y = it.y0 + 2 * tr + (k >> 1), x = it.x0 + 2 * tc + (k & 1);
+                        if (y < H && x < W) rs_v[h][k] = p.resid[obase[h] + (size_t)(k >> 1) * W + (k & 1)];
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int h = 0; h < MPP; ++h) {
+                if (m0 + h >= MT) break;
+                const int col = (m0 + h) * 16 + xi;              // this wave's channel of the M tile
+                const int co = it.cb * (MT * 16) + col;
+                float m[16];
+#pragma unroll
+                for (int f = 0; f < 16; ++f) m[f] = sM[(f * (16 * MPP) + h * 16 + xi) * WN_MSTRIDE + lt];
+                if (co < p.Cout && lane < WG::NTILES) {
+                    // t[p][j] = sum_i A^T[p][i] m[i][j];  Y[p][q] = sum_j t[p][j] A^T[q][j]
+                    float t0[4], t1[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        t0[j] = m[0 * 4 + j] + m[1 * 4 + j] + m[2 * 4 + j];
+                        t1[j] = m[1 * 4 + j] - m[2 * 4 + j] - m[3 * 4 + j];
+                    }
+                    float yv[4];
+                    yv[0] = t0[0] + t0[1] + t0[2];
+                    yv[1] = t0[1] - t0[2] - t0[3];
+                    yv[2] = t1[0] + t1[1] + t1[2];
+                    yv[3] = t1[1] - t1[2] - t1[3];
+                    const float bvs = p.bias ? p.bias[it.cb * (MT * 16) + col] : 0.0f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int y = it.y0 + 2 * tr + (k >> 1), x = it.x0 + 2 * tc + (k & 1);
+                        if (y < H && x < W) {
+                            const size_t o = obase[h] + (size_t)(k >> 1) * W + (k & 1);
+                            float v = yv[k] + bvs;
+                            if (ACT == 1) {
+                                if (p.out_pre) p.out_pre[o] = v;
+                                v = gelu_erf(v);
+                            } else if (ACT == 2) {
+                                v *= gelu_erf_grad(p.aux[o]);
+                            }
+                            v += rs_v[h][k];
+                            p.out[o] = v;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
         }
         if (!have_next) break;
         it = nx;
