@@ -763,6 +763,62 @@ int sinddm_patch_vote(const int32_t* idx, const float* ref, int r_per_sample, co
                       int w_per_sample, float* out, int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r,
                       float blend, void* stream);
 
+/* ---- denoising-score maps: the training L1 loss per pixel, on any image, inside one call ------------------------------ */
+/* What the model finds implausible (csrc/score_tail.h).  At one scale, for a batch y (B,3,H,W), at a scale
+ * > 0 its blurred image y_prev (the scale below, upsampled: training's x_recon / x_start), levels t_0 .. t_{n-1} (one per
+ * evaluation, shared by the batch) and a weight plane w (HW floats; NULL: 1), evaluation i computes per sample b
+ *     mix  = y_prev ? gamma_row[t_i] * y_prev + (1 - gamma_row[t_i]) * y : y       (gamma NOT clamped: training's mix)
+ *     x_t  = sqrt_ac[t_i] * mix + sqrt_1m_ac[t_i] * z_i          bit for bit what sinddm_q_sample(x0 = y_prev (y at scale 0),
+ *                                                                x_orig = y (NULL at scale 0), noise = z_i) writes into a
+ *                                                                16-byte aligned tensor for the same B
+ *     eps  = SinDDMNet(x_t, t_i, scale)                          the INFERENCE evaluation: the plan and the launches of a
+ *                                                                sampler step of the shape (sinddm_sample_chain, one stream)
+ *     m[p] = w[p] > 0 ? w[p] * ((|z - eps|[0][p] + |z - eps|[1][p]) + |z - eps|[2][p]) : 0      fp32, each op rounded once
+ *     map_out[b][p]   = m_0[p] + m_1[p] + ...                    fp32 running sum in the order of the evaluations
+ *     level_out[i][b] = sum over p of m_i[p]                     of exactly the fp32 values m_i[p] that went into the map:
+ *                       fp32 inside a block of 1024 pixels in a fixed tree, the block partials in float64 in a fixed order,
+ *                       rounded once -- no float atomics, the same bits every run, within 1e-6 relative of the float64 sum
+ * A pixel with w == 0 is skipped by a select: it is exactly 0 in map_out, absent from level_out, and what eps holds there
+ * cannot reach either.  z_i follows the noise contract above ("per-sample noise seeds"): with sample_seeds element e of sample
+ * b is element e of sinddm_normal_fill(3*H*W, sample_seeds[b], stream_id0 + i); without, element e of the whole batch is
+ * element e of sinddm_normal_fill(B*3*H*W, seed, stream_id0 + i), as in sinddm_sample_chain.  The draws are made inside the
+ * kernels: on shapes whose sampler step fuses its tail, the last launch of evaluation i scores it and writes x_t of evaluation
+ * i + 1, so an evaluation is the network's launches and nothing else -- no noise tensor, no eps tensor, no q_sample launch;
+ * other shapes write eps into the workspace and run one scoring launch and one draw launch per evaluation behind it.  The
+ * embeddings of t_list take one cond_kernel launch per arithmetic run of levels, as in the chain (evenly spaced levels: one).
+ * What a seeded row depends on: its draws depend on its seed alone.  The ROUNDING of x_t is that of the kernel sinddm_q_sample
+ * launches for the same B, which changes with B at one place: from B * (3*H*W / 4) >= 2^23 quads on (and 3*H*W % 4 == 0) the
+ * mix fuses its other product.  Below that size -- every batch of the configurations here -- a seeded row's x_t is the same
+ * bits at any batch size and position; across it, x_t may move by an ulp, as sinddm_q_sample's own output does.  As everywhere
+ * in the library, the convolutions' kernels may change with B too, so maps agree across batch sizes to fp32 rounding. */
+typedef struct sinddm_score_opts {
+    const float*    weight;        /* device, HW floats, 16-byte aligned, or NULL (= 1); shared by all samples */
+    const uint64_t* sample_seeds;  /* device, B entries, 8-byte aligned, or NULL */
+} sinddm_score_opts;
+
+/* Bytes of scratch sinddm_score_chain needs: sinddm_workspace_bytes(dim, B, H, W), and behind it the block partials of the
+ * level sums and, on shapes without a fused tail, one eps tensor.  0 for arguments the call would refuse. */
+size_t sinddm_score_workspace_bytes(int dim, int B, int H, int W, int n_evals);
+
+/* Only enqueues work on `stream`: no host synchronisation, no allocation, no global state.  map_out / level_out are
+ * overwritten (prior contents, NaN included, do not matter); x_t is scratch and holds x_t of the last evaluation on return.
+ * y, y_prev, x_t and map_out are 16-byte aligned.  n_evals is at most 1024 (the conditioning rows of a chain call).
+ * Every refusal comes before any device work:
+ * SINDDM_E_BADARG: a null params / packed / y / x_t / table / t_list / map_out / level_out / ws, y_prev without gamma_row or
+ * the reverse, n_evals outside 1 .. 1024, a negative level, non-positive sizes, a misaligned pointer (the tensors above,
+ * opts->weight to 16 bytes, opts->sample_seeds to 8); SINDDM_E_BADSHAPE: what the chain refuses (dim, 3*H*W >= 2^31,
+ * B > 65535); SINDDM_E_WORKSPACE: ws_bytes < sinddm_score_workspace_bytes. */
+int sinddm_score_chain(const float* params, const float* packed,
+                       const float* y, const float* y_prev /* NULL at scale 0 */,
+                       float* x_t /* (B,3,H,W) scratch; on return x_t of the last evaluation */,
+                       const float* tab_sqrt_ac, const float* tab_sqrt_1m_ac,
+                       const float* gamma_row /* NULL iff y_prev is NULL */,
+                       const int* t_list /* host */, int n_evals, float scale,
+                       uint64_t seed, uint64_t stream_id0,
+                       float* map_out /* (B,H,W) */, float* level_out /* (n_evals,B) */,
+                       int dim, int B, int H, int W, void* ws, size_t ws_bytes, void* stream,
+                       const sinddm_score_opts* opts /* host, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,15 @@ patch-vote iterations -- every `--patch_refine_patch {3,5,7}` patch is replaced 
 becomes the mean of the patches that cover it (the EM step of GPNN) -- before the next scale re-noises and redraws it.
 `--patch_refine_alpha A` ranks with GPNN's completeness normalisation D / (A 3P^2 + min D) (coverage in place of plain
 fidelity); `--patch_refine_blend B` in [0, 1] moves only the share B of the way.  Off by default.
+`score` (no reference mode) asks the MODEL: `--mode score [--input_image FILE ...] [--score_levels N] [--score_draws R]
+[--score_scales A B]` evaluates the training L1 loss |z - eps| per pixel with the trained weights, at N noise levels per scale
+(default 10, spread over the levels the scale was trained on) and R noise draws per level (default 4; `--seeds` names them), on
+the scales A ... B (default: all).  Without `--input_image` it scores the training pyramid: `score_report.json` is the
+checkpoint's per-scale / per-level loss table.  With pictures (paths, or names inside the dataset folder, brought to the finest
+size) each is scored side by side with the training image, `score_s{S}.png` shows the maps, and `score_edit_map.png` -- the
+finest map normalised against the training image's own (median -> 0, maximum -> 1) -- is a gray strength map that
+`--mode edit --edit_map score_edit_map.png` takes as it is: redraw what the model finds implausible, keep the rest.  `--tile`
+is refused (the wrapped-halo score is not built); `--train_mask` keeps the hole out of the score.
 The CLIP-guided modes (clip_content, clip_style_*, clip_roi; main.py:153-255) are not wired to the command line: CLIP
 itself is outside this build.  Their drivers exist (`MultiscaleTrainer.clip_sampling` / `clip_roi_sampling`, the guidance
 branch of `p_mean_variance`) and take any scorer with the reference's ClipExtractor interface.
@@ -131,6 +140,7 @@ class _OneOrMore(argparse.Action):
 
     def __call__(self, parser, namespace, values, option_string=None):
         setattr(namespace, self.dest, values[0] if len(values) == 1 else Jobs(values))
+        setattr(namespace, self.dest + "_given", True)          # (the flag was on the command line: a default never passes here)
 
 
 class _Pairs(argparse.Action):
@@ -212,6 +222,10 @@ def build_parser():
     p.add_argument("--patch_refine_alpha", type=float, default=None, metavar="A")
     p.add_argument("--patch_refine_blend", type=float, default=1.0, metavar="B")
     p.add_argument("--patch_refine_scales", type=int, nargs=2, default=None, metavar=("A", "B"))
+    # no reference flags: the denoising-score maps of `score` (MultiscaleTrainer.score)
+    p.add_argument("--score_levels", type=int, default=10, metavar="N")
+    p.add_argument("--score_draws", type=int, default=4, metavar="R")
+    p.add_argument("--score_scales", type=int, nargs=2, default=None, metavar=("A", "B"))
     return p
 
 
@@ -270,6 +284,8 @@ def parse_args(argv=None):
             p.error("--layout_strength must be in [0, 1]")
     for name in _PER_JOB:
         v = getattr(args, name)
+        if args.mode == "score" and name == "input_image":           # (the pictures `score` scores are not a sample batch)
+            continue
         if isinstance(v, Jobs) and args.sample_batch_size % len(v):
             p.error(f"--{name}: {len(v)} values need --sample_batch_size to be a multiple of {len(v)}, got "
                     f"{args.sample_batch_size}")
@@ -299,6 +315,16 @@ def parse_args(argv=None):
             p.error("--patch_refine_scales A B needs 0 <= A <= B")
         args.patch_refine_opt = dict(iters=args.patch_refine, patch=args.patch_refine_patch, alpha=a, blend=b,
                                      scales=None if sc is None else (sc[0], sc[1]))
+    args.score_images = None
+    if args.mode == "score":
+        if args.score_levels < 1 or args.score_draws < 1:
+            p.error("--score_levels and --score_draws must be >= 1")
+        if args.score_scales is not None and not 0 <= args.score_scales[0] <= args.score_scales[1]:
+            p.error("--score_scales A B needs 0 <= A <= B")
+        # (`score` scores the training pyramid alone unless --input_image is GIVEN: the flag's default is the reference's file
+        # name of the i2i modes; _OneOrMore marks a flag that was on the command line)
+        if getattr(args, "input_image_given", False):
+            args.score_images = args.input_image
     if args.mode == "edit" and not args.edit_map:
         p.error("--mode edit needs --edit_map FILE (a gray picture: white = redraw freely, black = keep the pixel)")
     return args
@@ -352,7 +378,7 @@ def main():
     sample_t_list = ms_diffusion.num_timesteps_ideal[1:] if args.sample_t_list is None else args.sample_t_list
 
     mask_kw = {}
-    if args.train_mask and args.mode == 'train':                           # (the other modes never train: nothing to mask)
+    if args.train_mask and args.mode in ('train', 'score'):                # (`score` keeps the hole out of its maps; the other modes never train: nothing to mask)
         import numpy as np
         from PIL import Image
         if len(args.train_mask_grow) not in (1, n_scales):
@@ -497,9 +523,33 @@ def main():
                 if name + "_mean" in report:
                     print(f"{name}: {report[name + '_mean']:.6g}")
             print("wrote " + os.path.join(results_folder, "patch_report.json"))
+    elif args.mode == 'score':
+        if args.score_scales is not None and args.score_scales[1] >= n_scales:
+            raise SystemExit(f"--score_scales {args.score_scales} is past the {n_scales} scales")
+        image = None
+        if args.score_images is not None:
+            import numpy as np
+            from PIL import Image
+            h, w = ms_diffusion.image_sizes[n_scales - 1]
+            names = list(args.score_images) if isinstance(args.score_images, Jobs) else [args.score_images]
+
+            def load(name):
+                path = name if os.path.exists(name) else os.path.join(args.dataset_folder, name)
+                pic = np.asarray(Image.open(path).convert("RGB").resize((w, h), Image.LANCZOS), dtype=np.float32)
+                return torch.from_numpy(pic.transpose(2, 0, 1).copy()).div(255).mul(2).sub(1)
+
+            image = torch.stack([load(f) for f in names])
+        if args.seeds is not None and len(args.seeds) < args.score_draws:
+            raise SystemExit(f"--mode score: {len(args.seeds)} seeds for --score_draws {args.score_draws} (one seed per draw)")
+        report, _ = trainer.score(image=image, levels=args.score_levels, draws=args.score_draws, scales=args.score_scales,
+                                  seeds=None if args.seeds is None else args.seeds[:args.score_draws])
+        if rank == 0:
+            for row in report["scales"]:
+                print(f"scale {row['scale']}: " + "  ".join(f"{v:.6g}" for v in row["mean"]))
+            print("wrote " + os.path.join(results_folder, "score_report.json"))
     else:
         raise NotImplementedError(
-            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint, paint2image, edit and evaluate are built for MI355X; "
+            f"mode {args.mode!r}: train, sample, style_transfer, harmonization, roi, inpaint, outpaint, paint2image, edit, evaluate and score are built for MI355X; "
             "the CLIP-guided modes of the reference need CLIP autograd and are out of scope (SURVEY.md section 8)")
     if args.gif is not None and frames and rank == 0:
         from sinddm_amd.functions import write_gif

@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "sinddm_q_sample_crop", "sinddm_l1_loss_rect_fwd_bwd",
     "sinddm_sample_chain_gate", "sinddm_reverse_step_keep_gate",
     "sinddm_patch_nnf_scaled_workspace_bytes", "sinddm_patch_nnf_scaled", "sinddm_patch_vote",
+    "sinddm_score_workspace_bytes", "sinddm_score_chain",
 )
 
 
@@ -48,6 +49,7 @@ ABI_VERSION = 3               # SINDDM_ABI_VERSION of include/sinddm_hip.h this 
 DIM_FP32_CONVS = 0x10000     # SINDDM_DIM_FP32_CONVS of include/sinddm_hip.h: option bit of every `dim` argument
 JUMP_STREAM = 1 << 31        # SINDDM_JUMP_STREAM of include/sinddm_hip.h: a jump's z2 draw is the step's stream id plus this
 MIX_MAX = 4                  # SINDDM_MIX_MAX of include/sinddm_hip.h: seeds per blended sample
+SCORE_MAX_EVALS = 1024       # evaluations per sinddm_score_chain call (CHAIN_COND_ROWS of csrc/fwd_plan.h)
 TILE_HALO = 16               # SINDDM_TILE_HALO of include/sinddm_hip.h: the network's receptive radius = halo of a wrapped axis
 
 
@@ -112,6 +114,12 @@ class GateOpts(C.Structure):
     """Mirror of `sinddm_gate_opts` (include/sinddm_hip.h): `thr` a HOST array of one threshold in (0, 1] per step of the
     call; the keep mask is then a hold level and a step keeps the pixels whose level is >= its threshold."""
     _fields_ = [("thr", C.POINTER(C.c_float))]
+
+
+class ScoreOpts(C.Structure):
+    """Mirror of `sinddm_score_opts` (include/sinddm_hip.h): `weight` an (H,W) float32 device plane or None (= 1),
+    `sample_seeds` a device table of one uint64 seed per sample or None."""
+    _fields_ = [("weight", C.c_void_p), ("sample_seeds", C.c_void_p)]
 
 
 class SinddmError(RuntimeError):
@@ -229,6 +237,9 @@ def load() -> C.CDLL:
         "sinddm_patch_nnf_scaled_workspace_bytes": (sz, [i, i, i, i, i, i, i, i]),
         "sinddm_patch_nnf_scaled": (i, [p, i, p, i, p, p, i, p, p, i, i, i, i, i, i, i, i, p, sz, p]),
         "sinddm_patch_vote": (i, [p, p, i, p, p, i, p, i, i, i, i, i, i, i, i, f, p]),
+        "sinddm_score_workspace_bytes": (sz, [i, i, i, i, i]),
+        "sinddm_score_chain": (i, [p, p, p, p, p, p, p, p, C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64, p, p, i, i, i, i,
+                                   p, sz, p, C.POINTER(ScoreOpts)]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name):

@@ -96,6 +96,18 @@ inline void chain_run_set(ChainRun& r, const sinddm_gate_opts* gt) {
     if (gt) r.gate_thr = gt->thr;
 }
 
+// The run of levels that ONE cond_kernel launch embeds, from position i0 of a host list of n: the longest stretch, at most `cap`
+// entries, whose t is an arithmetic progression (the sampler's always is); *dt is its step (0 for a single entry).  Asked by
+// the sampler chain and by the score chain, so that the two cut a list alike.
+inline int cond_run_len(const int* t_list, int i0, int n, int cap, int* dt) {
+    *dt = 0;
+    if (i0 + 1 >= n || cap < 2) return 1;
+    *dt = t_list[i0 + 1] - t_list[i0];
+    int len = 2;
+    while (i0 + len < n && len < cap && t_list[i0 + len] - t_list[i0 + len - 1] == *dt) ++len;
+    return len;
+}
+
 // a gate threshold the tails can take: in (0, 1] (0 is the tails' "ungated"; a NaN fails both compares)
 inline bool gate_valid(float thr) { return thr > 0.0f && thr <= 1.0f; }
 

@@ -745,6 +745,8 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
 }
 
 // (the reverse-step kernels and the Philox generator: step_tail.h)
+// the score tail: q_sample_elem on in-kernel draws behind the network's last launch
+#include "score_tail.h"
 
 // one axis of the bilinear source lookup: taps i0 / i1 and the weight of i1
 //   !WRAP  ATen area_pixel_compute_source_index(align_corners=False): max(scale*(dst+0.5)-0.5, 0), fp32
@@ -882,6 +884,7 @@ struct ChainStep {
     const float* x_tilde;
     float* x_next;
     TailArgs tail;     // the step's scalars and options (step_tail.h)
+    const ScoreArgs* score;   // a score evaluation (score_tail.h): the fused last launch scores instead of stepping; `tail` is not read
 };
 
 // The options of a tail launch as compile-time constants: calls f(EDIT, NOISE, KEEP) with std::true_type / std::false_type
@@ -1047,6 +1050,11 @@ int amax_tensor_launch(const float* x, float* amax, int B, long long per_sample,
 template <class EPS>
 static void fused_tail_launch(const ForwardPlan& F, bool pitch, const EPS& e, const float* x, const ChainStep& cs, hipStream_t st) {
     const dim3 grid(F.last_gx[1], F.B);
+    if (cs.score) {                                            // the same launch shape, ending in the score tail
+        if (pitch) hipLaunchKernelGGL(final_conv_score_pitch_kernel<EPS>, grid, dim3(256), 0, st, e, F.H, F.W, F.Wp, *cs.score);
+        else hipLaunchKernelGGL(final_conv_score_kernel<EPS>, grid, dim3(256), 0, st, e, F.HW, *cs.score);
+        return;
+    }
     tail_dispatch(cs.tail, [&](auto E, auto N, auto K) {
         if (pitch)
             hipLaunchKernelGGL((final_conv_reverse_step_pitch_kernel<decltype(E)::value, decltype(N)::value, decltype(K)::value, EPS>),
@@ -1556,12 +1564,8 @@ static int chain_enqueue(const ChainCtx& k, float** result) {
     int n_jumped = 0;                                          // jumps so far: the slot of the jumps' noise
     if (k.c.tiled) rc = wrap_halo_launch(r.x, nullptr, r.B * CHANNELS, r.Hc, r.Wc, r.halo_y, r.halo_x, k.st);      // (ordered before both halves: ev_go)
     for (int i0 = 0; i0 < r.n_steps && rc == 0;) {
-        int len = 1, dt = 0;
-        if (i0 + 1 < r.n_steps) {
-            dt = r.t_list[i0 + 1] - r.t_list[i0];
-            len = 2;
-            while (i0 + len < r.n_steps && len < CHAIN_COND_ROWS && r.t_list[i0 + len] - r.t_list[i0 + len - 1] == dt) ++len;
-        }
+        int dt = 0;
+        const int len = cond_run_len(r.t_list, i0, r.n_steps, CHAIN_COND_ROWS, &dt);
         CondArgs ca = cond_args(k.p, r.params);
         ca.t_host = r.t_list[i0]; ca.t_step = dt; ca.scale = r.scale;
         ca.out = k.cond_tab;
@@ -1758,6 +1762,114 @@ int sinddm_sample_chain_gate(CHAIN_SHARED_PARAMS, void* aux_stream, int* result_
 }
 #undef CHAIN_SHARED
 #undef CHAIN_SHARED_PARAMS
+
+// ---- the score chain (score_tail.h): the evaluations of a sampler run, each ending in the score tail ---------------------
+// Its workspace: the chain's own layout (the conditioning table and one core; what sinddm_workspace_bytes reports), and
+// behind it the block partials of the level sums [n_evals][B][gx] and, where the shape has no fused tail, one eps tensor.
+struct ScoreLayout {
+    size_t off_part, off_eps, total;
+    unsigned gx;                         // blocks per sample of the launch that scores: the last launch's, or score_rows_kernel's
+};
+static unsigned score_rows_gx(long long hw) {
+    const long long gx = ((hw + 3) / 4 + 255) / 256;
+    return (unsigned)(gx > 256 ? 256 : gx);
+}
+static ScoreLayout score_layout(const ForwardPlan& whole, const ForwardPlan& half, int n_evals) {
+    const auto align256 = [](size_t v) { return (v + 255) / 256 * 256; };
+    ScoreLayout L{};
+    L.gx = whole.fuse_tail ? whole.last_gx[1] : score_rows_gx(whole.HW);
+    L.off_part = align256(chain_workspace_bytes(whole, half));
+    L.off_eps = L.off_part + align256((size_t)n_evals * whole.B * L.gx * sizeof(float));
+    L.total = L.off_eps + (whole.fuse_tail ? 0 : align256((size_t)whole.B * CHANNELS * whole.HW * sizeof(float)));
+    return L;
+}
+// the shapes the score call takes (what the chain takes with per-sample seeds: a sample's quads and the rows' grids are ints)
+static bool score_shape_ok(const NetPlan& p, int B, int H, int W) { return p.ok && 3LL * H * W <= 0x7fffffffLL && B <= 65535; }
+
+size_t sinddm_score_workspace_bytes(int dim, int B, int H, int W, int n_evals) {
+    NetPlan p = make_plan(dim);
+    if (B <= 0 || H <= 0 || W <= 0 || n_evals < 1 || n_evals > CHAIN_COND_ROWS || !score_shape_ok(p, B, H, W)) return 0;
+    return score_layout(forward_plan(p, FWD_INFER, B, H, W, CU_COUNT_NO_DEVICE),
+                        forward_plan(p, FWD_INFER, (B + 1) / 2, H, W, CU_COUNT_NO_DEVICE), n_evals).total;
+}
+
+int sinddm_score_chain(const float* params, const float* packed, const float* y, const float* y_prev, float* x_t,
+                       const float* tab_sqrt_ac, const float* tab_sqrt_1m_ac, const float* gamma_row, const int* t_list,
+                       int n_evals, float scale, uint64_t seed, uint64_t stream_id0, float* map_out, float* level_out, int dim,
+                       int B, int H, int W, void* ws, size_t ws_bytes, void* stream, const sinddm_score_opts* opts) {
+    const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (!params || !packed || !y || !x_t || !tab_sqrt_ac || !tab_sqrt_1m_ac || !t_list || !map_out || !level_out || !ws ||
+        B <= 0 || H <= 0 || W <= 0)
+        return SINDDM_E_BADARG;
+    if ((y_prev == nullptr) != (gamma_row == nullptr)) return SINDDM_E_BADARG;
+    if (n_evals < 1 || n_evals > CHAIN_COND_ROWS) return SINDDM_E_BADARG;
+    for (int i = 0; i < n_evals; ++i)
+        if (t_list[i] < 0) return SINDDM_E_BADARG;
+    const float* weight = opts ? opts->weight : nullptr;
+    const uint64_t* sseeds = opts ? opts->sample_seeds : nullptr;
+    if (((bits(y) | bits(y_prev) | bits(x_t) | bits(map_out) | bits(weight)) & 15) != 0 || (bits(sseeds) & 7) != 0 ||
+        (bits(level_out) & 3) != 0)
+        return SINDDM_E_BADARG;
+    const NetPlan p = make_plan(dim);
+    if (!score_shape_ok(p, B, H, W)) return SINDDM_E_BADSHAPE;
+    const ForwardPlan fp = forward_plan(p, FWD_INFER, B, H, W, cu_count());      // the plan a sampler step of the shape gets
+    const ScoreLayout L = score_layout(fp, forward_plan(p, FWD_INFER, (B + 1) / 2, H, W, fp.ncu), n_evals);
+    if (ws_bytes < L.total) return SINDDM_E_WORKSPACE;
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* base = static_cast<char*>(ws);
+    float* cond_tab = reinterpret_cast<float*>(base);
+    float* part = reinterpret_cast<float*>(base + L.off_part);
+    float* eps = fp.fuse_tail ? nullptr : reinterpret_cast<float*>(base + L.off_eps);
+    const int HW = fp.HW;
+    ScoreArgs sa{};
+    sa.y = y; sa.yprev = y_prev; sa.w = weight; sa.xt = x_t; sa.map = map_out;
+    sa.tabA = tab_sqrt_ac; sa.tabB = tab_sqrt_1m_ac; sa.gam = gamma_row;
+    sa.seed = (unsigned long long)seed; sa.sseeds = reinterpret_cast<const unsigned long long*>(sseeds);
+    sa.round = q_sample_route(B, 3LL * HW, true);
+    const dim3 rows_grid(score_rows_gx(HW), (unsigned)B);
+    // x_t of evaluation i from stream stream_id0 + i, in a launch of its own
+    const auto draw = [&](int i) {
+        ScoreArgs d = sa;
+        d.step = (unsigned long long)(stream_id0 + (uint64_t)i);
+        if (HW % 4 == 0) hipLaunchKernelGGL(score_draw_kernel<true>, rows_grid, dim3(256), 0, st, HW, d, t_list[i]);
+        else hipLaunchKernelGGL(score_draw_kernel<false>, rows_grid, dim3(256), 0, st, HW, d, t_list[i]);
+        return hipGetLastError() != hipSuccess ? SINDDM_E_BADARG : 0;
+    };
+    if (const int rc = draw(0)) return rc;
+    for (int i0 = 0; i0 < n_evals;) {                          // runs of levels in arithmetic progression, as chain_enqueue cuts them
+        int dt = 0;
+        const int len = cond_run_len(t_list, i0, n_evals, CHAIN_COND_ROWS, &dt);
+        CondArgs ca = cond_args(p, params);
+        ca.t_host = t_list[i0]; ca.t_step = dt; ca.scale = scale;
+        ca.out = cond_tab;
+        hipLaunchKernelGGL(cond_kernel, dim3(len), dim3(128), 0, st, ca);
+        SINDDM_LAUNCH_CHECK();
+        for (int i = i0; i < i0 + len; ++i) {
+            sa.step = (unsigned long long)(stream_id0 + (uint64_t)i);
+            sa.t_next = fp.fuse_tail && i + 1 < n_evals ? t_list[i + 1] : -1;
+            sa.first = i == 0;
+            sa.part = part + (size_t)i * B * L.gx;
+            ChainStep cs{};
+            cs.plan = &fp;
+            cs.cond_row = cond_tab + (size_t)(i - i0) * p.cond_stride;
+            cs.x_next = fp.fuse_tail ? x_t : nullptr;          // (non-NULL: the plan's fused last launch)
+            cs.score = &sa;
+            int rc = net_forward_impl(p, params, packed, x_t, nullptr, t_list[i], scale, eps, B, H, W, ws, ws_bytes, st, nullptr, &cs);
+            if (rc) return rc;
+            if (!fp.fuse_tail) {
+                hipLaunchKernelGGL(score_rows_kernel, rows_grid, dim3(256), 0, st, eps, HW, sa);
+                SINDDM_LAUNCH_CHECK();
+                if (i + 1 < n_evals && (rc = draw(i + 1)) != 0) return rc;
+            }
+        }
+        i0 += len;
+    }
+    const int rows = n_evals * B;
+    hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, part, level_out, rows, (int)L.gx);
+    SINDDM_LAUNCH_CHECK();
+    return 0;
+}
 
 // What the single-step entries over a batch shape (B samples of C planes of hw elements) share: the step's TailArgs (the
 // keep scalars count only beside the keep maps: (1, 0) without them), its TailIO, and the checks in the order every entry

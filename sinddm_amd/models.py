@@ -1694,6 +1694,68 @@ class MultiScaleGaussianDiffusion(nn.Module):
             return g * x_start + (1 - g) * x_orig
         return x_orig
 
+    @torch.no_grad()
+    def denoise_score(self, y, s, y_prev=None, levels=None, draws=1, seeds=None, weight=None):
+        """What the model finds implausible in `y`, per pixel (no reference counterpart; score.py, sinddm_score_chain): the
+        training L1 loss  |z - eps(x_t, t, s)|  of the (B,3,H,W) batch `y` at scale `s`, evaluated with the inference network
+        at every level of `levels` (default: score.score_levels(num_timesteps_trained[s], 10); each validated against the
+        levels the scale was trained on) over `draws` noise draws.  `y_prev` is the blurred image of the scale -- the scale
+        below upsampled, training's x_recon -- required at s > 0 and refused at s == 0.  Returns (map, table):
+            map    (B,H,W)        the mean of |z - eps| over levels, draws and channels, times `weight`; under a weight it
+                                  is divided by nothing else: holes are exactly 0
+            table  (n_levels,B)   per level, the mean over draws, channels and pixels -- over sum(weight) under a weight
+        `weight`: an (H,W) float32 plane on y's device, finite and >= 0, shared by the batch (the hard train mask: a masked
+        model is not scored against its hole).  The draws are folded into the batch: row b * draws + r is sample b under its
+        r-th draw, so coarse scales fill the GPU, and one library call (per 1024 levels) does the rest on the current stream.
+        `seeds`: None (one key from torch's CPU generator for the call) or B * draws ints in [0, 2^63), row-major as above: a
+        row's draws then depend on its seed alone, and its map on nothing else up to fp32 rounding (the kernels a batch
+        takes, and above 2^23 quads per call the rounding of x_t, may change with the batch size: include/sinddm_hip.h).
+        A weight that is not finite, negative somewhere or zero everywhere is refused.
+        Stream ids: score.score_stream_id(s, position in `levels`).
+        `tile` on any axis: NotImplementedError (the wrapped-halo score is not built)."""
+        from .score import check_score_args, score_stream_id
+        y = torch.as_tensor(y)
+        s, levels, draws, seeds = check_score_args(self, y, s, y_prev, levels, draws, seeds, weight)
+        lib, net = _lib.load(), self.denoise_fn
+        B, _, H, W = (int(v) for v in y.shape)
+        R = B * draws
+        rep = (lambda t: t.repeat_interleave(draws, dim=0).contiguous()) if draws > 1 else (lambda t: t.contiguous())
+        yr = rep(y)
+        pr = rep(y_prev) if y_prev is not None else None
+        x_t = torch.empty_like(yr)
+        smap = torch.empty((R, H, W), dtype=torch.float32, device=y.device)
+        if seeds is not None:
+            key, seeds_dev = 0, torch.tensor(seeds, dtype=torch.int64, device=y.device)
+        else:
+            key, seeds_dev = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64)), None
+        wt = weight.contiguous() if weight is not None else None
+        opts = _lib.ScoreOpts(_lib.ptr(wt), _lib.ptr(seeds_dev))
+        gamma_row = self.gammas[s - 1].contiguous() if s > 0 else None
+        packed = net.packed_weights()
+        total = torch.zeros((R, H, W), dtype=torch.float32, device=y.device) if len(levels) > _lib.SCORE_MAX_EVALS else None
+        tables = []
+        for i0 in range(0, len(levels), _lib.SCORE_MAX_EVALS):
+            piece = levels[i0:i0 + _lib.SCORE_MAX_EVALS]
+            n = len(piece)
+            ws = _workspace(y.device, lib.sinddm_score_workspace_bytes(net.dim_arg, R, H, W, n))
+            lev = torch.empty((n, R), dtype=torch.float32, device=y.device)
+            tl = (C.c_int * n)(*piece)
+            _lib.check(lib.sinddm_score_chain(_lib.ptr(net.flat_params), _lib.ptr(packed), _lib.ptr(yr), _lib.ptr(pr),
+                                              _lib.ptr(x_t), _lib.ptr(self.sqrt_alphas_cumprod),
+                                              _lib.ptr(self.sqrt_one_minus_alphas_cumprod), _lib.ptr(gamma_row), tl, n, float(s),
+                                              key, score_stream_id(s, i0), _lib.ptr(smap), _lib.ptr(lev), net.dim_arg, R, H, W,
+                                              ws.data_ptr(), ws.numel(), _lib.stream_ptr(y.device), C.byref(opts)),
+                       "sinddm_score_chain")
+            tables.append(lev)
+            if total is not None:
+                total += smap
+        if total is not None:
+            smap = total
+        norm = float(weight.double().sum()) if weight is not None else float(H * W)
+        table = torch.cat(tables).view(len(levels), B, draws).mean(dim=2) / (3.0 * norm)
+        smap = smap.view(B, draws, H, W).mean(dim=1) / (3.0 * len(levels))
+        return smap, table
+
     def forward(self, x, s, *args, **kwargs):                              # models.py:613-631
         s = int(s)
         img = x[0]

@@ -459,6 +459,75 @@ class MultiscaleTrainer(object):
         return patch_refine(batch.to(self.device, torch.float32).contiguous(), image.to(torch.float32).contiguous(),
                             tile=tuple(self.ema_model.tile), valid=valid, **kw)
 
+    @torch.no_grad()
+    def score(self, image=None, levels=10, draws=4, scales=None, seeds=None):
+        """What the model thinks of a picture: the denoising score (`ema_model.denoise_score`, score.py) of the training
+        pyramid and, with `image`, of that picture side by side with it.
+            image   None: the checkpoint's own table -- per scale and per level, the loss of the trained weights on the images
+                    they were trained on (`data_list`: each scale's picture and its blurred partner, the FILES of the pyramid).
+                    (3,H,W) or (N,3,H,W) in [-1, 1] at the finest size: the picture(s) reach the scales through
+                    score.score_pyramid (area averages; each blurred partner is the scale below, upsampled) and are scored in
+                    one batch with the training image: row 0 is the training image, rows 1 ... N the pictures.
+            levels  an int (that many levels per scale, score.score_levels over the levels the scale was trained on) or a list
+            draws   noise draws per level (folded into the batch)
+            scales  None (all) or (A, B), inclusive
+            seeds   None, or `draws` ints in [0, 2^63): every row of every scale is scored under these same draws (common
+                    random numbers: the picture and the training image differ by their content alone)
+        The hard `train_mask` is the weight plane: a masked model is never scored against its hole, as in `evaluate`; the
+        holes are exact zeros in every map, and the edit map's median and maximum are taken over the valid pixels only.
+        Returns (report, maps): maps[s] is the (1 + N, H_s, W_s) score map of scale s; report holds, per scale, the levels, the
+        per-level table and the mean of every row.  Every rank computes; rank 0 writes `score_report.json`, `score_s{S}.png`
+        (the rows' maps over the training image's maximum) and, for a picture, `score_edit_map.png`: score.score_edit_map of
+        the finest scored scale, a gray strength map that `--mode edit --edit_map` takes as it is (one per picture:
+        `score_edit_map_{n}.png` from the second on).  No detection-rate claim is made."""
+        import json
+        from .score import score_edit_map, score_levels, score_pyramid
+        em, n = self.ema_model, self.n_scales
+        a, b = (0, n - 1) if scales is None else (int(scales[0]), int(scales[1]))
+        if not 0 <= a <= b < n:
+            raise ValueError(f'score: scales {(a, b)} outside 0 ... {n - 1}')
+        draws = int(draws)
+        if seeds is not None and len(seeds) != draws:
+            raise ValueError(f'score: {len(seeds)} seeds for {draws} draws')
+        sizes = [tuple(int(v) for v in em.image_sizes[s]) for s in range(n)]
+        pics = None
+        if image is not None:
+            img = torch.as_tensor(image).to(torch.float32)
+            if not bool(((img >= -1.0) & (img <= 1.0)).all()):
+                raise ValueError('score: image outside [-1, 1]')
+            pics = score_pyramid(img.to(self.device), sizes)
+        report, maps = {'scales': [], 'draws': draws}, {}
+        for s in range(a, b + 1):
+            y = self.data_list[s][0][:1].to(torch.float32)
+            yp = self.data_list[s][1][:1].to(torch.float32) if s > 0 else None
+            if pics is not None:
+                y = torch.cat([y, pics[s][0]])
+                yp = torch.cat([yp, pics[s][1]]) if s > 0 else None
+            lv = score_levels(em.num_timesteps_trained[s], levels) if isinstance(levels, int) else [int(t) for t in levels]
+            weight = None if self.train_mask_hard is None else self.train_mask_hard[s].to(torch.float32).contiguous()
+            rows = int(y.shape[0])
+            row_seeds = None if seeds is None else [int(v) for _ in range(rows) for v in seeds]
+            smap, table = em.denoise_score(y.contiguous(), s, y_prev=yp, levels=lv, draws=draws, seeds=row_seeds, weight=weight)
+            maps[s] = smap
+            report['scales'].append({'scale': s, 'size': list(sizes[s]), 'levels': lv,
+                                     'table': table.t().cpu().tolist(),            # [row][level]
+                                     'mean': table.mean(dim=0).cpu().tolist()})    # per row: row 0 = the training image
+        if sdist.rank() == 0:
+            with open(str(self.results_folder / 'score_report.json'), 'w') as f:
+                json.dump(report, f, indent=1)
+            for s, m in maps.items():
+                top = m[0].max().clamp_min(1e-30)
+                save_image((m / top)[:, None], str(self.results_folder / f'score_s{s}.png'), nrow=m.shape[0])
+            if pics is not None:
+                for k in range(1, maps[b].shape[0]):
+                    # (under a train mask the holes of both maps are exact zeros: the normalisation leaves them out)
+                    valid = None if self.train_mask_hard is None else self.train_mask_hard[b] > 0
+                    em_map = score_edit_map(maps[b][k], maps[b][0], valid=valid).cpu()
+                    arr = em_map.mul(255).add(0.5).clamp(0, 255).to(torch.uint8).numpy()
+                    name = 'score_edit_map.png' if k == 1 else f'score_edit_map_{k - 1}.png'
+                    Image.fromarray(arr, mode='L').save(str(self.results_folder / name))
+        return report, maps
+
     def _local_batch_maps(self, batch_size) -> dict:
         """This rank's rows of the per-sample conditioning on `ema_model`, as {attribute: value to set for the call}: every
         keep / layout map with a leading batch dimension, `layout_gain`, `roi_bbs_batch` and `roi_target_patch_batch` must have
