@@ -542,6 +542,22 @@ typedef struct sinddm_mix_opts {
 int sinddm_normal_fill_mix(float* out, int B, int64_t n, const uint64_t* keys /*device, B*K*/,
                            const float* weights /*device, B*K*/, int K, uint64_t stream_id, void* stream);
 
+/* The window of a seeded draw: the noise contract at any WINDOW of the sample.  out is (n_slots, B, 3, h, w).  Element
+ * (i, b, c, y, x) is element
+ *     e = c*H*W + (oy_b + y)*W + (ox_b + x)
+ * of the blend  sum_k weights[b*K+k] * sinddm_normal_fill(3*H*W, keys[b*K+k], stream_ids[i])  with the arithmetic of
+ * sinddm_normal_fill_mix (K = 1 with weights = NULL: sinddm_normal_fill_samples), bit for bit: the window (h, w) = (H, W)
+ * at (0, 0) is the fill itself.  A run on the windows of a batch therefore draws, element for element, what the run on the
+ * whole samples draws there (windowed known-region sampling).  One launch fills all slots.
+ * origins: device int32 (B,2) = (oy_b, ox_b), not read on the host: the caller guarantees 0 <= oy <= H - h and
+ * 0 <= ox <= W - w, the kernel clamps to that range and never leaves `out`.  stream_ids: device uint64, n_slots entries.
+ * SINDDM_E_BADARG (before any device work): out / stream_ids / origins / keys NULL, weights NULL with K != 1, stream_ids or
+ * keys not 8-byte, out / origins / weights not 4-byte aligned, n_slots, B, h or w <= 0, K outside 1 .. SINDDM_MIX_MAX;
+ * SINDDM_E_BADSHAPE: h > H, w > W, 3*H*W >= 2^31, B > 65535. */
+int sinddm_normal_fill_window(float* out, int n_slots, const uint64_t* stream_ids /*device, n_slots*/, int B, int H, int W,
+                              const int32_t* origins /*device, B*2*/, int h, int w, const uint64_t* keys /*device, B*K*/,
+                              const float* weights /*device, B*K, may be NULL when K == 1*/, int K, void* stream);
+
 /* sinddm_sample_chain_solver with a blend (every chain entry fills one internal description; they differ only in the options
  * they can express).  mx = NULL or mx->keys = NULL: the same launches, the same numbers as sinddm_sample_chain_solver.  With
  * the block, step i of the call adds to element e of sample b  sigma_i * z  with z the blend above at stream id

@@ -41,6 +41,9 @@ black part of the mask (white = keep the training image's pixel; the file is bro
 `--mode outpaint --scale_mul h w [--anchor y x]` grows the canvas around the training image.  `--resample R --jump_length J`
 (both modes; defaults 1 1 = no jumps) add RePaint's resampling: at every noise level that is a multiple of J the run jumps
 back up by J levels and comes down again, R times in all, so that the generated region is shaped with the known one in view.
+`--keep_window [N]` (`inpaint`, `outpaint`, `edit`; default N = 16) runs every scale on the window around the pixels that may
+change -- their bounding box grown by N -- with the noise of the full run: with N >= 16, the network's receptive radius, the
+picture of a seed is the one the full run draws, and the run costs what its hole costs.  Not with `--tile`.
 `edit` (no reference mode) edits a picture with a strength per pixel: `--mode edit --edit_map FILE [FILE ...] [--edit_image FILE
 [FILE ...]]`.  The map is a gray picture brought to the finest target size, read as value / 255: black = leave the pixel alone,
 white = redraw it freely, gray = re-noise it to that share of every scale's levels and let the model take it from there (each
@@ -203,6 +206,8 @@ def build_parser():
     # no reference flags: RePaint's resampling jumps of `inpaint` / `outpaint` (MultiScaleGaussianDiffusion.resample)
     p.add_argument("--resample", type=int, default=1)
     p.add_argument("--jump_length", type=int, default=1)
+    # no reference flag: windowed known-region sampling of `inpaint` / `outpaint` / `edit` (MultiScaleGaussianDiffusion.keep_window)
+    p.add_argument("--keep_window", type=int, nargs="?", const=16, default=None, metavar="N")
     # no reference flags: few-step sampling (MultiScaleGaussianDiffusion.sample_steps / sample_spacing / solver_order / eta)
     p.add_argument("--sample_steps", type=int, nargs="+", default=None)
     p.add_argument("--sample_spacing", choices=("t", "logsnr"), default="t")
@@ -265,6 +270,11 @@ def parse_args(argv=None):
         p.error("--vary_from_scale must be >= 0")
     if args.resample < 1 or args.jump_length < 1:
         p.error("--resample and --jump_length must be >= 1")
+    if args.keep_window is not None:
+        if args.mode not in ("inpaint", "outpaint", "edit"):
+            p.error("--keep_window applies to --mode inpaint, outpaint and edit")
+        if args.keep_window < 0:
+            p.error("--keep_window N must be >= 0")
     if args.sample_steps is not None and min(args.sample_steps) < 1:
         p.error("--sample_steps must be >= 1")
     if min(args.train_mask_grow) < 0:
@@ -462,13 +472,13 @@ def main():
             known = load(paths)
         frames = trainer.inpaint(known, batch_size=args.sample_batch_size,
                         hard=not args.soft_mask, custom_t_list=sample_t_list, save_unbatched=True,
-                        resample=args.resample, jump_length=args.jump_length, **seed_kw)
+                        resample=args.resample, jump_length=args.jump_length, window=args.keep_window, **seed_kw)
     elif args.mode == 'outpaint':
         anchor = job_values(args.anchor, args.sample_batch_size)
         anchor = [tuple(a) for a in anchor] if isinstance(args.anchor, Jobs) else tuple(anchor)
         frames = trainer.outpaint(scale_mul, anchor=anchor, batch_size=args.sample_batch_size,
                          custom_t_list=sample_t_list, save_unbatched=True, resample=args.resample,
-                         jump_length=args.jump_length, **seed_kw)
+                         jump_length=args.jump_length, window=args.keep_window, **seed_kw)
     elif args.mode == 'paint2image':
         import numpy as np
         from PIL import Image
@@ -511,7 +521,8 @@ def main():
         frames = trainer.edit(per_job(args.edit_map, load_map),
                               image=per_job(args.edit_image, load_pic) if args.edit_image else None,
                               batch_size=args.sample_batch_size, scale_mul=scale_mul, custom_t_list=sample_t_list,
-                              save_unbatched=True, resample=args.resample, jump_length=args.jump_length, **seed_kw)
+                              save_unbatched=True, resample=args.resample, jump_length=args.jump_length,
+                              window=args.keep_window, **seed_kw)
     elif args.mode == 'evaluate':
         if args.eval_scale is not None and args.eval_scale >= n_scales:
             raise SystemExit(f"--eval_scale {args.eval_scale} is past the {n_scales} scales")

@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "sinddm_sample_chain_gate", "sinddm_reverse_step_keep_gate",
     "sinddm_patch_nnf_scaled_workspace_bytes", "sinddm_patch_nnf_scaled", "sinddm_patch_vote",
     "sinddm_score_workspace_bytes", "sinddm_score_chain",
+    "sinddm_normal_fill_window",
 )
 
 
@@ -185,6 +186,7 @@ def load() -> C.CDLL:
                                                  C.POINTER(ResampleOpts), C.POINTER(LayoutOpts), C.POINTER(BatchOpts),
                                                  C.POINTER(SolverOpts), C.POINTER(MixOpts), C.POINTER(GateOpts)]),
         "sinddm_normal_fill_mix": (i, [p, i, i64, p, p, i, C.c_uint64, p]),
+        "sinddm_normal_fill_window": (i, [p, i, p, i, i, i, p, i, i, p, p, i, p]),
         "sinddm_reverse_step_ms": (i, [p, p, p, p, p, C.POINTER(StepCoefs), f, p, p, p, p, p, f, f, i, i, i, p]),
         "sinddm_layout_delta": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, p, i, i, i, i, i, i, p]),
         "sinddm_reverse_step_layout": (i, [p, p, p, p, p, C.POINTER(StepCoefs), p, f, i, p, p, p, p, f, f, i, i, i, i, i, i, i,

@@ -2167,3 +2167,7 @@ int sinddm_wrap_halo(float* ext, const float* src, int BC, int H, int W, int hal
 }
 
 }  // extern "C"
+
+// the window of a seeded draw: sinddm_normal_fill_window (its kernel and the entry).  Last in the unit: every kernel above
+// keeps its place in the code object.
+#include "window_fill.h"

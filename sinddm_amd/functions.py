@@ -352,6 +352,49 @@ def crop_norm(windows, rects, sat=None) -> float:
     return float(torch.where((hh * ww) > 0, tot, torch.zeros_like(tot)).sum())
 
 
+# ---- the window of a known-region run (MultiScaleGaussianDiffusion.keep_window; no reference counterpart) ----
+def keep_windows(free, margin: int = 16, batch=None):
+    """The windows a known-region run has to compute: `free` is a bool (H, W) or (B, H, W) map, True where the pixel is not held
+    for the whole run (mask < 1 under `keep_maps`, hold level < 1 under `keep_gated`).  Per sample the bounding box of the free
+    pixels is grown by `margin` on every side and clipped to the image; the common size (h, w) is the largest such box, w
+    rounded up to a multiple of 4 where that is still <= W (the cropped rows stay on the step tails' 16-byte path); sample b's
+    origin is (min(y0_b, H - h), min(x0_b, W - w)), so that its grown box lies inside its window; a sample without a free
+    pixel gets (0, 0).  Returns None when no sample has a free pixel or when (h, w) == (H, W) -- the run is then the full
+    run -- else (h, w, origins), origins an int32 CPU (B, 2) tensor; a shared (H, W) map gives one origin, replicated
+    `batch` times (once without `batch`).  With margin >= 16, the network's receptive radius (_lib.TILE_HALO), the free pixels
+    of the windowed run are the full run's.  SinddmError: `margin` not an integer >= 0."""
+    from ._lib import SinddmError
+    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or int(margin) < 0:
+        raise SinddmError(f"keep_windows: margin {margin!r} is not an integer >= 0")
+    g = int(margin)
+    f = torch.as_tensor(free).detach().to("cpu")
+    if f.dim() not in (2, 3):
+        raise SinddmError(f"keep_windows: free map {tuple(f.shape)} is neither (H, W) nor (B, H, W)")
+    shared = f.dim() == 2
+    f = (f[None] if shared else f) != 0
+    H, W = int(f.shape[1]), int(f.shape[2])
+    boxes = []                                              # per sample (y0, y1, x0, x1) of the grown box, or None
+    for fb in f:
+        rows, cols = torch.nonzero(fb.any(dim=1)).reshape(-1), torch.nonzero(fb.any(dim=0)).reshape(-1)
+        if rows.numel() == 0:
+            boxes.append(None)
+            continue
+        boxes.append((max(int(rows[0]) - g, 0), min(int(rows[-1]) + 1 + g, H), max(int(cols[0]) - g, 0),
+                      min(int(cols[-1]) + 1 + g, W)))
+    live = [b for b in boxes if b is not None]
+    if not live:
+        return None
+    h, w = max(b[1] - b[0] for b in live), max(b[3] - b[2] for b in live)
+    if -(-w // 4) * 4 <= W:
+        w = -(-w // 4) * 4
+    if (h, w) == (H, W):
+        return None
+    origins = torch.tensor([(0, 0) if b is None else (min(b[0], H - h), min(b[2], W - w)) for b in boxes], dtype=torch.int32)
+    if shared:
+        origins = origins.repeat(int(batch) if batch is not None else 1, 1)
+    return h, w, origins
+
+
 def outpaint_offset(canvas, image, anchor=(0.5, 0.5)) -> Tuple[int, int]:
     """Top-left corner (y, x) of an (h, w) image placed on an (H, W) canvas: int(anchor * (canvas - image)) per axis;
     anchor (0, 0) = top left, (0.5, 0.5) = centred, (1, 1) = bottom right."""

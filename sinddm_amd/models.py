@@ -21,6 +21,8 @@ checkpoints work unchanged, while every per-step tensor op runs in libsinddm_hip
                                 line: the reference never seeds its generator)
   seed blending (`seed_mix`) -> sinddm_sample_chain_mix / sinddm_normal_fill_mix   (no reference line: a sample's draw as
                                 a fixed combination of the draws of K seeds -- interpolations and loops between samples)
+  windowed keep (`keep_window`) -> sinddm_normal_fill_window   (no reference line: a known-region run evaluated on the
+                                window around its free pixels, with the draws of the full run)
   few-step sampling          -> strided step scalars (`step_coefs_to`) through every chain entry; `solver_order = 2`:
                                 sinddm_sample_chain_solver / sinddm_reverse_step_ms   (no reference line: the reference
                                 evaluates the network at every level)
@@ -564,6 +566,97 @@ class _ChainCall:
         return self.centre(self.x).contiguous() if self.tiled else self.x
 
 
+class _KeepWindow:
+    """The windows of one windowed known-region run of `MultiScaleGaussianDiffusion._run_steps` (`plan.window` set): `plan` /
+    `img` are the run cropped to one (h, w) window per sample -- the steps of the full plan, every map gathered through the
+    windows and therefore per-sample, the noise kind 'window' with its keys resolved -- which either route runs as it runs
+    any plan; `fill` / `draw` make its draws, `leave` puts the result back into the full-size sample.  Gathers and the
+    scatter are plain advanced indexing: they are outside the step loop."""
+
+    def __init__(self, d, full, img):
+        import copy
+        self.d, self.full = d, full
+        h, w, org = full.window
+        B, Cc, H, W = (int(v) for v in img.shape)
+        dev = img.device
+        self.B, self.hw, self.HW, self.dev = B, (int(h), int(w)), (H, W), dev
+        self.org = org.to(device=dev, dtype=torch.int32).contiguous()
+        o = self.org.long()
+        self.bi, self.ci = torch.arange(B, device=dev)[:, None, None, None], torch.arange(Cc, device=dev)[None, :, None, None]
+        self.ys = (o[:, 0, None] + torch.arange(h, device=dev))[:, None, :, None]
+        self.xs = (o[:, 1, None] + torch.arange(w, device=dev))[:, None, None, :]
+        xt = full.xt
+        if xt is not None and (xt.shape != img.shape or xt.dtype != img.dtype or xt.device != dev):
+            raise _lib.SinddmError(f"img_prev_upsample {tuple(xt.shape)} {xt.dtype} {xt.device} does not match the "
+                                   f"running sample {tuple(img.shape)} {img.dtype} {dev}")
+        src = full.noise[1]
+        if src is None:
+            # an unseeded windowed run: every sample its own fresh 62-bit seed from torch's CPU generator
+            src = ([[int(v)] for v in torch.randint(0, 2 ** 62, (B,), dtype=torch.int64).tolist()], None)
+        self.keys, self.weights = src
+        self.kd = torch.tensor(self.keys, dtype=torch.int64, device=dev)
+        self.wd = torch.tensor(self.weights, dtype=torch.float32, device=dev) if self.weights is not None else None
+        p = self.plan = copy.copy(full)
+        p.win, p.noise = self, ("window", src)
+        p.keep = (self.crop_plane(full.keep[0]), self.crop(full.keep[1]))
+        p.roi = (self.crop_plane(full.roi[0]), self.crop(full.roi[1])) if full.roi is not None else None
+        p.xt = self.crop(xt) if xt is not None else None
+        p.per = (int(p.roi is not None), 1, 1, 0)
+        self.img = self.crop(img)
+
+    def crop(self, t):
+        """(B, C, H, W) or a shared (C, H, W) -> the (B, C, h, w) windows."""
+        t = t if t.dim() == 4 else t[None].expand((self.B,) + tuple(t.shape))
+        return t[self.bi, self.ci, self.ys, self.xs].contiguous()
+
+    def crop_plane(self, t):
+        """(B, H, W) or a shared (H, W) -> the (B, h, w) windows."""
+        t = t if t.dim() == 3 else t[None].expand((self.B,) + tuple(t.shape))
+        return t[self.bi[:, 0], self.ys[:, 0], self.xs[:, 0]].contiguous()
+
+    def fill(self, sids):
+        """(len(sids), B, 3, h, w): slot i holds the windows of the run's draw at stream id sids[i] (one launch)."""
+        lib, (h, w), (H, W) = _lib.load(), self.hw, self.HW
+        ids = torch.tensor([int(v) for v in sids], dtype=torch.int64, device=self.dev)
+        out = torch.empty((len(sids), self.B, 3, h, w), dtype=torch.float32, device=self.dev)
+        _lib.check(lib.sinddm_normal_fill_window(_lib.ptr(out), len(sids), _lib.ptr(ids), self.B, H, W, _lib.ptr(self.org), h, w,
+                                                 _lib.ptr(self.kd), _lib.ptr(self.wd), int(self.kd.shape[1]),
+                                                 _lib.stream_ptr(self.dev)), "sinddm_normal_fill_window")
+        return out
+
+    def draw(self, kind, st):
+        """The 'step' / 'jump' draw of step `st` on the step-by-step route (logged like `_draw` logs its draws)."""
+        z = self.fill([noise_stream_id(self.plan.s, kind, st.pos)])[0]
+        if self.d.draw_log is not None:
+            self.d.draw_log.append((kind, int(self.plan.s), int(st.t), z.clone()))
+        return z
+
+    def leave(self, out):
+        """The full-size result: the windows `out` inside, and outside what the full run leaves there -- every pixel out there
+        is held (mask / hold level 1), so it is the kept value of the run's last step, ka * target + kb * z_last: the known
+        image itself, bit for bit, when the run lands on the clean image; else the single-step keep entry on the last
+        step's full-size draw under a mask of ones (the value does not depend on the network)."""
+        d, full, B, (H, W) = self.d, self.full, self.B, self.HW
+        last, kx = full.steps[-1], full.keep[1]
+        if tuple(last.ab) == (1.0, 0.0) and last.k.mode != 1:
+            res = (kx if kx.dim() == 4 else kx[None].expand(B, -1, -1, -1)).clone()
+        else:
+            lib = _lib.load()
+            seeds, mix = ([k[0] for k in self.keys], None) if self.weights is None else (None, (self.keys, self.weights))
+            z = d._keyed_normal(seeds, mix, (B, 3, H, W), noise_stream_id(full.s, "step", last.pos), self.dev)
+            zero, ones, res = torch.zeros_like(z), torch.ones((H, W), dtype=z.dtype, device=self.dev), torch.empty_like(z)
+            rows = [slice(b, b + 1) for b in range(B)] if kx.dim() == 4 else [slice(0, B)]
+            for r in rows:
+                xt = full.xt[r] if full.xt is not None else None
+                _lib.check(lib.sinddm_reverse_step_keep(_lib.ptr(zero[r]), _lib.ptr(zero[r]), _lib.ptr(xt), _lib.ptr(z[r]),
+                                                        _lib.ptr(res[r]), C.byref(last.k), None, None, _lib.ptr(ones),
+                                                        _lib.ptr(kx[r.start] if kx.dim() == 4 else kx), *last.ab,
+                                                        r.stop - r.start, 3, H * W, _lib.stream_ptr(self.dev)),
+                           "sinddm_reverse_step_keep")
+        res[self.bi, self.ci, self.ys, self.xs] = out
+        return res
+
+
 class MultiScaleGaussianDiffusion(nn.Module):
     """Multi-scale DDPM with SinDDM's re-blurring (reference SinDDM/models.py:155-631)."""
 
@@ -712,6 +805,14 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # SDEdit per pixel.  No soft blend; {0, 1} maps give the ungated run bit for bit.  Needs the scale's `keep_maps`
         # entry; a sampling option like `keep_maps`, not stored in checkpoints; not available with CLIP guidance.
         self.keep_gated = False
+        # windowed known-region sampling: None, or a margin in pixels (an int >= 0).  A scale with a `keep_maps` entry is then
+        # run on one window per sample -- the bounding box of its free pixels (mask / hold level < 1) grown by the margin,
+        # functions.keep_windows -- and every draw is the full run's at the element's absolute position
+        # (sinddm_normal_fill_window), so with a margin >= _lib.TILE_HALO, the receptive radius, the image of a seed is the
+        # full run's image; everything outside the windows is the kept value, in closed form.  A run costs
+        # what its hole costs.  A scale whose window spans it runs as ever.  Needs the scale's `keep_maps` entry; not with
+        # `tile`, `layout_maps`, CLIP guidance or `noise_fn` (sampler.NOT_BUILT).  Not stored in checkpoints.
+        self.keep_window = None
         # per-sample noise seeds: None (the draws come from torch's generators, as ever), a sequence of B ints in [0, 2^63)
         # (one seed per sample, used at every scale) or a [n_scales][B] nested sequence (row s at scale s; `vary_seeds`).
         # With seeds every N(0,1) draw of sample b -- initial, re-noise, every reverse step -- is a function of
@@ -1321,7 +1422,19 @@ class MultiScaleGaussianDiffusion(nn.Module):
                          keep their shape with those levels as the t list.  `solver_order` = 2: every step runs unfused and
                          ends in the multistep kernel (sinddm_sample_chain_solver).  Not with `resample`; order 2 not with
                          `layout_maps`.
-        The noise is one of four:
+          `keep_window`  with keep maps whose free pixels fit a window smaller than the scale (functions.keep_windows): the
+                         run's inputs -- state, x-tilde, mask or hold plane, known image, ROI maps -- are gathered through
+                         one window per sample, every map family becomes per-sample, the same steps run on the (B, 3, h, w)
+                         tensors on either route, and the result is scattered into the value the full run leaves outside
+                         the windows: the kept value of the last step, the known image itself when the run lands on the
+                         clean image (`_KeepWindow`).  Not with `tile`, `layout_maps`, CLIP guidance or `noise_fn`.
+        The noise is one of five:
+          windowed       recorded buffers in pieces of at most CHAIN_NOISE_BYTES, each filled by ONE
+                         sinddm_normal_fill_window call at the ids noise_stream_id(s, 'step', pos) of its steps (a second one
+                         at the 'jump' ids of its jumps): the draws the full run of `sample_seeds` / `seed_mix` makes at the
+                         same absolute positions.  Unseeded: B fresh 62-bit per-sample seeds from torch's CPU generator
+                         (unrelated to the unseeded full run of the same torch.manual_seed).  `draw_log`: ("chain_window", s,
+                         seeds or (keys, weights), t list, jump targets or None, (h, w), origins).
           `noise_fn` + `chain_noise`   the draws the step-by-step loop would fetch, in its order ('step' per step, 'jump' per
                          jump), handed over as buffers of at most CHAIN_NOISE_BYTES: one call per piece.
           `sample_seeds` sample b's step at position i of the run draws sinddm_normal_fill(3 H W, seed_b,
@@ -1332,6 +1445,9 @@ class MultiScaleGaussianDiffusion(nn.Module):
           otherwise      one 62-bit seed from torch's CPU generator keys the in-kernel draws.  `draw_log`: ("chain", s, seed,
                          t list), tiled ("chain_tile", ..., (hy, hx)), resampled ("chain_resample", s, seed, ..., jump targets)."""
         plan = RunPlan(self, img, s, t_seq)                    # (every validation and refusal: sampler.RunPlan)
+        win = _KeepWindow(self, plan, img) if plan.window is not None else None
+        if win is not None:
+            plan, img = win.plan, win.img                      # (the same steps on the windows; scattered back by `leave`)
         s, n = plan.s, len(plan.steps)
         fast = ((self.noise_fn is None or self.chain_noise) and isinstance(self.denoise_fn, SinDDMNet)
                 and not self.save_interm and not self.clip_guided_sampling and (self.chain_guided or plan.roi is None)
@@ -1342,11 +1458,11 @@ class MultiScaleGaussianDiffusion(nn.Module):
             for st in plan.steps:
                 img = self._p_sample_host_t(img, st.t, s, step_pos=st.pos, q=st.q, hist=hist, plan=plan)
                 self._dump_interm(img, s, f'output_t-{st.t:03}_s-{s}.png')
-            return img
+            return img if win is None else win.leave(img)
         run = _ChainCall(self, plan, img)
         x, (kind, src) = run.x, plan.noise
         per, seed, kw = n, 0, {}                               # in-kernel draws: one call for the whole run
-        if kind == "recorded":
+        if kind in ("recorded", "window"):
             # pieces of as many steps as fit the byte budget; each piece's draws are fetched exactly as the step-by-step loop
             # fetches them (one `_draw("step", ...)` per step, t = 0 included, in step order, a `_draw("jump", ...)` after a
             # step that jumps) and the next piece continues from the buffer the previous one ended in
@@ -1363,6 +1479,12 @@ class MultiScaleGaussianDiffusion(nn.Module):
             self.draw_log.append(plan.log_entry(seed))         # (the draws an entry stands for: RunPlan.log_entry)
         for i0 in range(0, n, per):
             piece = plan.steps[i0:i0 + per]
+            if kind == "window":
+                # the draws of exactly these steps, each one library call: the steps' slots, then the slots of the jumps
+                jumps = [noise_stream_id(s, "jump", st.pos) for st in piece if st.jump is not None]
+                kw = dict(noise=win.fill([noise_stream_id(s, "step", st.pos) for st in piece]),
+                          jump_noise=(win.fill(jumps) if jumps else torch.empty((1,) + tuple(x.shape), dtype=x.dtype, device=x.device))
+                          if plan.jump_to is not None else None)
             if kind == "recorded":
                 # (tiled: the draws have the sample's own size and fill the centre of their slot; the halo of a slot is
                 # never used -- the halo of a step's output is overwritten with its wrapped centre)
@@ -1375,7 +1497,7 @@ class MultiScaleGaussianDiffusion(nn.Module):
                     if st.jump is not None:
                         run.centre(next(jslots)).copy_(self._draw("jump", img.shape, s, st.t, x.device))
             run.call(i0, len(piece), seed, **kw)
-        return run.result()
+        return run.result() if win is None else win.leave(run.result())
 
     def _eps(self, x, t_dev, t_host, s):
         hy, hx = self._tile_halo()
@@ -1421,8 +1543,10 @@ class MultiScaleGaussianDiffusion(nn.Module):
         if self.save_interm:                                                # models.py:360-366 (x_recon lives inside the fused kernel:
             tt = torch.full((x.shape[0],), st.t, device=x.device, dtype=torch.long)     # recomputed here, for the dump only)
             self._dump_x_recon(self.predict_start_from_noise(x, t=tt, s=s, noise=eps)[0], st.t, s)
-        z = noise_like(x.shape, x.device, True).contiguous() if repeat_noise else self._draw("step", x.shape, s, st.t, x.device, st.pos)
-        z2 = self._draw("jump", x.shape, s, st.t, x.device, st.pos) if st.jump is not None else None
+        # (a windowed run's draws are the full run's at the window's absolute positions: `_KeepWindow.draw`)
+        draw = plan.win.draw if plan.win is not None else (lambda kind, st: self._draw(kind, x.shape, s, st.t, x.device, st.pos))
+        z = noise_like(x.shape, x.device, True).contiguous() if repeat_noise else draw("step", st)
+        z2 = draw("jump", st) if st.jump is not None else None
         out = torch.empty_like(x)
         if plan.per[0] or plan.per[1] or plan.per[2] or (st.g > 0.0 and (plan.per[3] or plan.gain is not None)):
             # per-sample maps: the single-step entries with B = 1 on each sample's slices (a cross-check route)

@@ -11,7 +11,7 @@ from types import SimpleNamespace
 from typing import Optional, Tuple
 
 from . import _lib
-from .functions import gate_thresholds, layout_strengths, resample_schedule, stride_schedule
+from .functions import gate_thresholds, keep_windows, layout_strengths, resample_schedule, stride_schedule
 
 # The combinations of options that are not built, (option, the option it cannot go with) -> what NotImplementedError says.
 NOT_BUILT = {
@@ -36,6 +36,12 @@ NOT_BUILT = {
     ("patch_refine", "layout_maps"): "patch_refine with layout_maps: the vote between the scales of a layout-conditioned run "
                                      "is not built",
     ("patch_refine", "roi"): "patch_refine with ROI guidance: the vote between the scales of an ROI-guided run is not built",
+    ("keep_window", "tile"): "keep_window with tile: a window across the wrapped border of a tiled run is not built",
+    ("keep_window", "layout_maps"): "keep_window with layout_maps: the block means of the layout pull do not survive a crop",
+    ("keep_window", "clip"): "keep_window with clip_guided_sampling: the CLIP-guided step runs in eager torch ops on the "
+                             "whole image",
+    ("keep_window", "noise_fn"): "keep_window with a caller's noise_fn: the windowed run draws by absolute position from "
+                                 "per-sample seeds",
 }
 _ON = {"clip": lambda d: d.clip_guided_sampling, "resample": lambda d: d._resample_cfg() is not None}
 
@@ -71,7 +77,20 @@ class RunPlan:
     `roi` (ew, ec) / `keep` (mask, x0) / `lay` (layout, N, strength, t_min) or None each, `per` (which of edit, keep mask, keep x0,
     layout hold a slice per sample), `gain` (fp32 numpy or None), `xt` (x-tilde or None), `order2`, `gated` (`keep_gated`: every
     record carries `thr`, functions.gate_thresholds of its `land` and the run's top level before any resampling expansion),
-    `noise` (kind, payload) with kind 'recorded' / 'seeds' / 'mix' / 'torch' (None for a single step: its caller draws).
+    `noise` (kind, payload) with kind 'recorded' / 'seeds' / 'mix' / 'torch' / 'window' (None for a single step: its caller
+    draws), `window` (functions.keep_windows of the run's free pixels under `keep_window`: (h, w, origins), or None -- not
+    asked for, no free pixel, a window that spans the scale, a single step -- which is today's run field by field), `win`
+    (None; on the cropped copy of the plan that `_run_steps` runs, the models._KeepWindow that makes its draws) and `full_hw`,
+    the sample's own (H, W).
+
+    The windowed run (`window` set): `_run_steps` gathers every input through the per-sample windows, runs the same steps on
+    the (B, 3, h, w) tensors and scatters the result into the value the full run leaves outside them.  Its noise kind is
+    'window': every draw is sinddm_normal_fill_window at the step's stream id, i.e. the draw the full run of `sample_seeds`
+    or `seed_mix` makes at the element's ABSOLUTE position; the payload is (keys [B][K], weights [B][K] or None for plain
+    seeds).  An UNSEEDED windowed run has payload None here: `_run_steps` draws B fresh 62-bit per-sample seeds from torch's
+    CPU generator and keys every sample on its own -- it is therefore unrelated to the unseeded full run of the same
+    torch.manual_seed (which keys the whole batch on one seed and the batch-flat index), but windowed runs of one
+    torch.manual_seed agree with each other.
 
     Everything is validated here, in this order; each reader raises ValueError for a malformed option, SinddmError for a map
     that does not match `img`, and NotImplementedError (NOT_BUILT) where noted:
@@ -116,6 +135,9 @@ class RunPlan:
             seeds, mix = d._seeds_for(s, B), d._mix_for(s, B)
             self.noise = (("recorded", None) if d.noise_fn is not None else ("seeds", seeds) if seeds is not None
                           else ("mix", mix) if mix is not None else ("torch", None))
+        windowed = at is None and getattr(d, "keep_window", None) is not None
+        if windowed:
+            refuse(d, "keep_window", "clip")
         gated = bool(d.keep_gated)
         if gated:
             refuse(d, "keep_gated", "clip")
@@ -124,6 +146,13 @@ class RunPlan:
             raise ValueError(f"keep_gated without keep_maps for scale {s}: there is no known region to gate")
         if gated and t_seq and t_top is None:
             raise ValueError("keep_gated: a single step needs t_top, the highest level of its run")
+        self.window, self.win, self.full_hw = None, None, (int(img.shape[-2]), int(img.shape[-1]))
+        if windowed:
+            self.window = self._window_for(d, s, keep, lay, B)
+            if self.window is not None:
+                src = self.noise[1]
+                self.noise = ("window", None if src is None else ([[int(v)] for v in src], None) if self.noise[0] == "seeds"
+                              else (src[0], src[1]))
         roi = None
         if d.roi_guided_sampling and s < d.n_scales - 1 and not clip:       # models.py:430-431 (the CLIP step edits on its own)
             roi = d.roi_edit_maps(s, int(img.shape[-2]), int(img.shape[-1]), img.device)
@@ -157,11 +186,29 @@ class RunPlan:
                 raise _lib.SinddmError("img_prev_upsample is not set (call sample_via_scale / p_sample_via_scale_loop)")
             self.xt = d.img_prev_upsample.contiguous()
 
+    @staticmethod
+    def _window_for(d, s: int, keep, lay, B: int):
+        """functions.keep_windows of the run under `keep_window`, after its refusals."""
+        margin = d.keep_window
+        if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0:
+            raise _lib.SinddmError(f"keep_window = {margin!r}: None or a margin, an integer >= 0")
+        if keep is None:
+            raise _lib.SinddmError(f"keep_window without keep_maps for scale {s}: there is no known region to window around")
+        refuse(d, "keep_window", "tile", any(d.tile))
+        refuse(d, "keep_window", "layout_maps", lay is not None)
+        refuse(d, "keep_window", "noise_fn", d.noise_fn is not None)
+        return keep_windows(keep[0] < 1, margin, batch=B)
+
     def log_entry(self, seed: int):
         """The `draw_log` entry of the run on the chain route with in-kernel draws (`seed`: the torch-seeded run's): draw i is
-        sinddm_normal_fill over the sample (the EXTENDED one when tiled) at stream i, a jump's second draw 2^31 above it."""
+        sinddm_normal_fill over the sample (the EXTENDED one when tiled) at stream i, a jump's second draw 2^31 above it.  A
+        windowed run: ("chain_window", s, seeds or (keys, weights), t list, jump targets or None, (h, w), origins) -- the draws
+        of the seeded run's entry, of which the window is taken."""
         kind, src = self.noise
         t, jumps = list(self.t_seq), list(self.jump_to) if self.jump_to is not None else None
+        if kind == "window":                                   # (`seed` unused: the payload holds the keys, drawn or given)
+            key = [k[0] for k in src[0]] if src[1] is None else (src[0], src[1])
+            return ("chain_window", self.s, key, t, jumps, tuple(self.window[:2]), self.window[2])
         if kind == "mix":
             return ("chain_mix", self.s, (src[0], src[1]), t, jumps)
         key = list(src) if kind == "seeds" else seed

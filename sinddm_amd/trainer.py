@@ -708,23 +708,25 @@ class MultiscaleTrainer(object):
             em.roi_bbs_batch = None
 
     # ---- known-region sampling: some pixels are given, the rest is generated to fit (no reference counterpart) ----
-    def _sample_kept(self, keep_maps, tag, resample=1, jump_length=1, **kw):
+    def _sample_kept(self, keep_maps, tag, resample=1, jump_length=1, window=None, **kw):
         em = self.ema_model
         R, J = int(resample), int(jump_length)
         if R < 1 or J < 1:
             raise ValueError(f'{tag}: resample {resample} / jump_length {jump_length} must be >= 1')
         em.keep_maps = keep_maps
         em.resample = (R, J) if R > 1 else None
+        em.keep_window = window
         try:
             return self.sample_scales(custom_sample=False, image_name='', start_noise=True,
                                       desc=f'{tag}_{str(datetime.datetime.now()).replace(":", "_")}', **kw)
         finally:
             em.keep_maps = None
             em.resample = None
+            em.keep_window = None
 
     @torch.no_grad()
     def inpaint(self, mask, batch_size=16, hard=True, custom_t_list=None, save_unbatched=False, save_images=True,
-                seeds=None, vary_from_scale=None, resample=1, jump_length=1, seed_mix=None):
+                seeds=None, vary_from_scale=None, resample=1, jump_length=1, seed_mix=None, window=None):
         """Fill a hole in the training image: `mask` is (H, W) at the finest scale's size, 1 = keep the training image's
         pixel, 0 = generate.  At every scale the known image is that scale's training image and the mask comes from
         `functions.keep_mask_pyramid` (`hard`: a coarse pixel is kept only if its whole footprint is known); after every
@@ -736,7 +738,12 @@ class MultiscaleTrainer(object):
         evaluations on the resampled stretches).  The defaults (1, 1) are the run without jumps, bit for bit.  No
         image-quality claim is made.
         A (batch_size, H, W) stack of masks gives every sample its own hole: one job per sample, still one library call per
-        scale (`sinddm_batch_opts`).  Returns the per-scale batches and writes PNGs like `sample_scales`."""
+        scale (`sinddm_batch_opts`).
+        `window` = None, or a margin in pixels (16, the network's receptive radius, makes it exact): at every scale the
+        network then runs on each sample's window "bounding box of the pixels that may change, grown by the margin" only, with
+        the draws of the full run (`ema_model.keep_window`, functions.keep_windows, sinddm_normal_fill_window): the run
+        costs what its hole costs.  `outpaint` and `edit` take the same argument.
+        Returns the per-scale batches and writes PNGs like `sample_scales`."""
         from .functions import keep_mask_pyramid
         em = self.ema_model
         m = torch.as_tensor(mask)
@@ -748,11 +755,11 @@ class MultiscaleTrainer(object):
                 for s in range(self.n_scales)}
         return self._sample_kept(maps, 'inpaint', resample=resample, jump_length=jump_length, batch_size=batch_size,
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
-                                 seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix)
+                                 seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix, window=window)
 
     @torch.no_grad()
     def outpaint(self, scale_mul, anchor=(0.5, 0.5), batch_size=16, custom_t_list=None, save_unbatched=False,
-                 save_images=True, seeds=None, vary_from_scale=None, resample=1, jump_length=1, seed_mix=None):
+                 save_images=True, seeds=None, vary_from_scale=None, resample=1, jump_length=1, seed_mix=None, window=None):
         """Grow the canvas around the training image: at every scale the sample has `target_size(s, scale_mul)`, the
         scale's own training image sits unresampled at int(anchor * (canvas - image)) and is kept (mask 1 on that
         rectangle), the rest is generated.  `scale_mul` < 1 on an axis is a ValueError.  `resample` / `jump_length`: as for
@@ -783,12 +790,13 @@ class MultiscaleTrainer(object):
         return self._sample_kept(maps, 'outpaint', resample=resample, jump_length=jump_length, scale_mul=tuple(scale_mul),
                                  batch_size=batch_size,
                                  custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
-                                 seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix)
+                                 seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix, window=window)
 
     # ---- per-pixel edit strength: every pixel its own SDEdit start level (no reference counterpart) ----
     @torch.no_grad()
     def edit(self, strength, image=None, batch_size=16, scale_mul=(1, 1), custom_t_list=None, seeds=None,
-             vary_from_scale=None, seed_mix=None, resample=1, jump_length=1, save_unbatched=False, save_images=True):
+             vary_from_scale=None, seed_mix=None, resample=1, jump_length=1, save_unbatched=False, save_images=True,
+             window=None):
         """Edit a picture with a strength per pixel: `strength` is (H, W) in [0, 1] at the finest target size
         (`ema_model.target_size(n_scales - 1, scale_mul)`), 0 = leave the pixel alone, 1 = redraw it from scratch, c in
         between = re-noise it to the share c of the scale's levels and let the model take it from there (SDEdit with a start
@@ -833,7 +841,7 @@ class MultiscaleTrainer(object):
             sm = {} if tuple(float(v) for v in scale_mul) == (1.0, 1.0) else {'scale_mul': tuple(scale_mul)}
             return self._sample_kept(maps, 'edit', resample=resample, jump_length=jump_length, **sm, batch_size=batch_size, custom_t_list=custom_t_list, save_unbatched=save_unbatched,
                                      save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale,
-                                     seed_mix=seed_mix)
+                                     seed_mix=seed_mix, window=window)
         finally:
             em.keep_gated = False
 
