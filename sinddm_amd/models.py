@@ -34,6 +34,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from contextlib import contextmanager
 from functools import partial
 from pathlib import Path
 from typing import Dict, Optional, Tuple
@@ -46,7 +47,7 @@ from torch import nn
 from . import _lib
 from .autograd import l1_loss
 from .functions import cosine_beta_schedule, crop_windows, default, exists, extract, noise_like
-from .sampler import RunPlan, pack_steps, refuse
+from .sampler import SAMPLING_OPTIONS, RunPlan, pack_steps, refuse, sampling_defaults
 from .synth import net_param_shapes
 from .train_step import TrainStep
 
@@ -680,7 +681,6 @@ class MultiScaleGaussianDiffusion(nn.Module):
         # the hot-path build; the guidance BRANCH of p_mean_variance (models.py:367-431) is implemented against the
         # interface the reference uses: `clip_model` is any object with zero_grad() and a differentiable
         # calculate_clip_loss(image in [0,1], text_embedds) -> scalar (stock PyTorch-ROCm autograd).
-        self.clip_guided_sampling = False
         self.guidance_sub_iters = None
         self.stop_guidance = None
         self.quantile = 0.8
@@ -697,7 +697,6 @@ class MultiScaleGaussianDiffusion(nn.Module):
         self.x_recon_prev = None
         self.clip_roi_bb = []
         self.omega = omega
-        self.roi_guided_sampling = False
         self.roi_bbs = []
         self.roi_bbs_stat = []
         self.roi_target_patch = []
@@ -752,20 +751,6 @@ class MultiScaleGaussianDiffusion(nn.Module):
 
         self._host_tabs: Optional[dict] = None
         self._host_ver = None
-        # optional noise hook for parity tests: fn(kind, shape, s, t, device) -> tensor
-        self.noise_fn = None
-        # replay aid: when set to a list, every host-side draw ('init' / 'renoise', the tensor itself) and every fused
-        # run of reverse steps (('chain', s, seed, [t...]): the in-kernel draws are sinddm_normal_fill(seed, i)) is logged
-        self.draw_log = None
-        self.two_streams = True       # coarse scales as two half-batches on two streams (sinddm_sample_chain2)
-        self.chain_noise = False      # True: runs with a `noise_fn` take the chain call too (draws handed over as buffers)
-        self.chain_guided = True      # False: ROI-guided runs take the step-by-step route (A/B measurements, bisecting)
-        # tileable sampling: (wrap_y, wrap_x) -- on a wrapped axis the sample's borders wrap around, i.e. the network is
-        # evaluated as if every convolution padded circularly there (the reference: padding_mode='circular' on its
-        # nn.Conv2d's).  The convolution kernels only know zero padding: the image is extended by a wrapped halo of
-        # _lib.TILE_HALO pixels (the network's receptive radius) and the centre is kept.  A sampling option: training is
-        # unchanged.
-        self.tile = (False, False)
         # tileable TRAINING: (wrap_y, wrap_x) -- p_losses trains the network with circular padding on the wrapped axes, by
         # the same construction (x_noisy extended by its wrapped halo, the loss on the centre: every parameter gradient is
         # then the circularly padded network's).  Separate from `tile`, which p_losses does not read; not
@@ -793,77 +778,30 @@ class MultiScaleGaussianDiffusion(nn.Module):
         self.crop_step = 0
         self._crop_gen = None
         self._train_crop_sat = {}
-        # known-region conditioning (inpainting / outpainting): None or {s: (mask (H,W), x0 (3,H,W))}, fp32, on the sample's
-        # device.  At a scale with an entry every reverse step overwrites the pixels whose mask is 1 with the
-        # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
-        # values between 0 and 1 blend.  A sampling option, like `tile`; not available with CLIP guidance.
-        self.keep_maps = None
-        # per-pixel edit strength: False, or True -- the mask of every `keep_maps` entry is then a HOLD LEVEL h in [0, 1]
-        # (1 - strength; functions.hold_pyramid) and a reverse step that lands on level u of a run whose top level is t_top
-        # keeps the pixels with  h >= 1 - (u + 1) / (t_top + 1)  (functions.gate_thresholds; sinddm_sample_chain_gate): a
-        # pixel is pinned to the forward-diffused known image down to its own level and left to the model from there --
-        # SDEdit per pixel.  No soft blend; {0, 1} maps give the ungated run bit for bit.  Needs the scale's `keep_maps`
-        # entry; a sampling option like `keep_maps`, not stored in checkpoints; not available with CLIP guidance.
-        self.keep_gated = False
-        # windowed known-region sampling: None, or a margin in pixels (an int >= 0).  A scale with a `keep_maps` entry is then
-        # run on one window per sample -- the bounding box of its free pixels (mask / hold level < 1) grown by the margin,
-        # functions.keep_windows -- and every draw is the full run's at the element's absolute position
-        # (sinddm_normal_fill_window), so with a margin >= _lib.TILE_HALO, the receptive radius, the image of a seed is the
-        # full run's image; everything outside the windows is the kept value, in closed form.  A run costs
-        # what its hole costs.  A scale whose window spans it runs as ever.  Needs the scale's `keep_maps` entry; not with
-        # `tile`, `layout_maps`, CLIP guidance or `noise_fn` (sampler.NOT_BUILT).  Not stored in checkpoints.
-        self.keep_window = None
-        # per-sample noise seeds: None (the draws come from torch's generators, as ever), a sequence of B ints in [0, 2^63)
-        # (one seed per sample, used at every scale) or a [n_scales][B] nested sequence (row s at scale s; `vary_seeds`).
-        # With seeds every N(0,1) draw of sample b -- initial, re-noise, every reverse step -- is a function of
-        # (seed of b, noise_stream_id, element index inside the sample) alone: the sample does not depend on its batch, its
-        # position in it, the two-stream split or the rank that runs it.  Not together with `noise_fn`.
-        self.sample_seeds = None
-        # seed blending: None, or (keys, weights) -- two [B][K] nested sequences, or [n_scales][B][K] like `sample_seeds`
-        # (`mix_from_scale`) -- K <= 4 seeds in [0, 2^63) and K finite weights per sample whose squares add up to 1.  Every
-        # N(0,1) draw of sample b is then  sum_k weights[b][k] * (the draw sample_seeds = keys[b][k] would give):  N(0,1)
-        # again, and a function of the row alone, like a seeded sample.  Rows on an arc interpolate between two samples
-        # (`interp_seeds`), rows on a circle make a closed loop (`loop_seeds`).  Not together with `sample_seeds` or
-        # `noise_fn`; not with CLIP guidance.
-        self.seed_mix = None
-        # RePaint's resampling for known-region sampling: None or (R, J), both >= 1.  At anchor levels (multiples of J) the run
-        # jumps back up by J levels and comes down again, until the stretch has been walked R times (the schedule:
-        # functions.resample_schedule; the upward move: sinddm_sample_chain_resample).  R = 1 is None.  A sampling option,
-        # like `keep_maps` (which it is meant for, and does not require); not available with CLIP guidance.
-        self.resample = None
-        # layout conditioning (paint-to-image): None or {s: (3, H_s, W_s) fp32 tensor on the sample's device}.  At a scale with
-        # an entry, every reverse step with t >= layout_t_min pulls the low spatial frequencies of the predicted clean image
-        # towards the layout's, with strength layout_strength in [0, 1]; "low" is the band below the block size
-        # layout_down[s] (1 ... 64; functions.layout_blocks gives one physical band for all scales).  Strength and t_min are
-        # one number or a dict per scale.  The contract: include/sinddm_hip.h (sinddm_layout_opts).  A sampling option like
-        # `keep_maps`; not available with CLIP guidance or together with `resample`.
-        self.layout_maps = None
-        self.layout_down = {}
-        self.layout_strength = 1.0
-        self.layout_t_min = 0
-        # per-sample conditioning: a batch of B independent edit jobs per run.  Every map above may carry a leading batch
-        # dimension -- keep_maps[s] = (mask (H,W) or (B,H,W), x0 (3,H,W) or (B,3,H,W)), the two independent of each other;
-        # layout_maps[s] (3,H,W) or (B,3,H,W) -- and sample b is then conditioned on row b alone, whatever its position in
-        # the batch, the two-stream split or the rank that runs it (sinddm_sample_chain_batch).  `layout_gain`: None or B
-        # floats in [0, 1], sample b's factor on the layout strength.  `roi_bbs_batch` / `roi_target_patch_batch`: None or
-        # B box lists / B patch lists (each what `roi_bbs` / `roi_target_patch` is for the whole batch; without the
-        # second, every sample takes `roi_target_patch`).  The t schedule, `resample`, `tile`, `layout_down` and
-        # `layout_t_min` stay one per run.
-        self.layout_gain = None
-        self.roi_bbs_batch = None
-        self.roi_target_patch_batch = None
-        # few-step sampling.  `sample_steps`: None (the network is evaluated at every level of every scale, as in the
-        # reference), an int (at most that many evaluations per scale) or one value per scale (None: every level).
-        # `sample_spacing`: which levels are kept -- 't' equally spaced in t, 'logsnr' equally spaced in log kappa
-        # (functions.stride_schedule).  `solver_order`: 1 the step as it is (at a scale > 0 the DDIM form with SinDDM's
-        # re-blur mix, at scale 0 the DDIM form with `eta`), 2 the second-order multistep step on top of it
-        # (sinddm_sample_chain_solver).  `eta`: the noise of a scale-0 step as a share of the posterior's, 1.0 the
-        # reference's DDPM step, 0 deterministic; `omega` stays the knob of the finer scales.  Sampling options like `tile`;
-        # not stored in checkpoints; not with CLIP guidance or `resample`; order 2 not with `layout_maps`.
-        self.sample_steps = None
-        self.sample_spacing = 't'
-        self.solver_order = 1
-        self.eta = 1.0
+        # the sampling options: sampler.sampling_defaults lists and describes them, `sampling()` below sets them for a block
+        for name, value in sampling_defaults().items():
+            setattr(self, name, value)
+
+    def sampling(self, **options):
+        """Context manager: the sampling options `options` (names of sampler.sampling_defaults; any other name is a TypeError
+        before anything is set) for the length of the block, which is handed this model.  On the way out, by return or by
+        exception, every named attribute is the very object it was on the way in -- not a copy, not the default.  Scopes
+        nest.  No value is looked at: the readers of the options validate, as ever, when a run starts."""
+        unknown = sorted(set(options) - SAMPLING_OPTIONS)
+        if unknown:
+            raise TypeError(f"sampling(): {', '.join(unknown)}: not a sampling option (sampler.sampling_defaults)")
+
+        @contextmanager
+        def scope():
+            found = {name: getattr(self, name) for name in options}
+            for name, value in options.items():
+                setattr(self, name, value)
+            try:
+                yield self
+            finally:
+                for name, value in found.items():
+                    setattr(self, name, value)
+        return scope()
 
     # ---- host copies of the per-t tables (scalar kernel arguments; no device sync per step) ----
     _TABS = ('alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',

@@ -46,6 +46,109 @@ NOT_BUILT = {
 _ON = {"clip": lambda d: d.clip_guided_sampling, "resample": lambda d: d._resample_cfg() is not None}
 
 
+def sampling_defaults() -> dict:
+    """The sampling options: every attribute a run reads off the diffusion object, name -> the value that means "option off".
+    A fresh dict with fresh mutable values per call.  `MultiScaleGaussianDiffusion.__init__` assigns exactly these, as plain
+    attributes; `MultiScaleGaussianDiffusion.sampling(**options)` sets some of them for the length of a `with` block.  None
+    of them is stored in checkpoints; the training options (`train_tile`, `train_weights`, `train_crop`, ...) are not here."""
+    return {
+        # tileable sampling: (wrap_y, wrap_x) -- on a wrapped axis the sample's borders wrap around, i.e. the network is
+        # evaluated as if every convolution padded circularly there (the reference: padding_mode='circular' on its
+        # nn.Conv2d's).  The convolution kernels only know zero padding: the image is extended by a wrapped halo of
+        # _lib.TILE_HALO pixels (the network's receptive radius) and the centre is kept.  A sampling option: training is
+        # unchanged.
+        "tile": (False, False),
+        # known-region conditioning (inpainting / outpainting): None or {s: (mask (H,W), x0 (3,H,W))}, fp32, on the sample's
+        # device.  At a scale with an entry every reverse step overwrites the pixels whose mask is 1 with the
+        # forward-diffused known image `x0` of the step's noise level, inside the step kernel (sinddm_sample_chain_keep);
+        # values between 0 and 1 blend.  A sampling option, like `tile`; not available with CLIP guidance.
+        "keep_maps": None,
+        # per-pixel edit strength: False, or True -- the mask of every `keep_maps` entry is then a HOLD LEVEL h in [0, 1]
+        # (1 - strength; functions.hold_pyramid) and a reverse step that lands on level u of a run whose top level is t_top
+        # keeps the pixels with  h >= 1 - (u + 1) / (t_top + 1)  (functions.gate_thresholds; sinddm_sample_chain_gate): a
+        # pixel is pinned to the forward-diffused known image down to its own level and left to the model from there --
+        # SDEdit per pixel.  No soft blend; {0, 1} maps give the ungated run bit for bit.  Needs the scale's `keep_maps`
+        # entry; a sampling option like `keep_maps`, not stored in checkpoints; not available with CLIP guidance.
+        "keep_gated": False,
+        # windowed known-region sampling: None, or a margin in pixels (an int >= 0).  A scale with a `keep_maps` entry is then
+        # run on one window per sample -- the bounding box of its free pixels (mask / hold level < 1) grown by the margin,
+        # functions.keep_windows -- and every draw is the full run's at the element's absolute position
+        # (sinddm_normal_fill_window), so with a margin >= _lib.TILE_HALO, the receptive radius, the image of a seed is the
+        # full run's image (DESIGN.md 4); everything outside the windows is the kept value, in closed form.  A run costs
+        # what its hole costs.  A scale whose window spans it runs as ever.  Needs the scale's `keep_maps` entry; not with
+        # `tile`, `layout_maps`, CLIP guidance or `noise_fn` (NOT_BUILT).  Not stored in checkpoints.
+        "keep_window": None,
+        # per-sample noise seeds: None (the draws come from torch's generators, as ever), a sequence of B ints in [0, 2^63)
+        # (one seed per sample, used at every scale) or a [n_scales][B] nested sequence (row s at scale s; `vary_seeds`).
+        # With seeds every N(0,1) draw of sample b -- initial, re-noise, every reverse step -- is a function of
+        # (seed of b, noise_stream_id, element index inside the sample) alone: the sample does not depend on its batch, its
+        # position in it, the two-stream split or the rank that runs it.  Not together with `noise_fn`.
+        "sample_seeds": None,
+        # seed blending: None, or (keys, weights) -- two [B][K] nested sequences, or [n_scales][B][K] like `sample_seeds`
+        # (`mix_from_scale`) -- K <= 4 seeds in [0, 2^63) and K finite weights per sample whose squares add up to 1.  Every
+        # N(0,1) draw of sample b is then  sum_k weights[b][k] * (the draw sample_seeds = keys[b][k] would give):  N(0,1)
+        # again, and a function of the row alone, like a seeded sample.  Rows on an arc interpolate between two samples
+        # (`interp_seeds`), rows on a circle make a closed loop (`loop_seeds`).  Not together with `sample_seeds` or
+        # `noise_fn`; not with CLIP guidance.
+        "seed_mix": None,
+        # RePaint's resampling for known-region sampling: None or (R, J), both >= 1.  At anchor levels (multiples of J) the run
+        # jumps back up by J levels and comes down again, until the stretch has been walked R times (the schedule:
+        # functions.resample_schedule; the upward move: sinddm_sample_chain_resample).  R = 1 is None.  A sampling option,
+        # like `keep_maps` (which it is meant for, and does not require); not available with CLIP guidance.
+        "resample": None,
+        # layout conditioning (paint-to-image): None or {s: (3, H_s, W_s) fp32 tensor on the sample's device}.  At a scale with
+        # an entry, every reverse step with t >= layout_t_min pulls the low spatial frequencies of the predicted clean image
+        # towards the layout's, with strength layout_strength in [0, 1]; "low" is the band below the block size
+        # layout_down[s] (1 ... 64; functions.layout_blocks gives one physical band for all scales).  Strength and t_min are
+        # one number or a dict per scale.  The contract: include/sinddm_hip.h (sinddm_layout_opts).  A sampling option like
+        # `keep_maps`; not available with CLIP guidance or together with `resample`.
+        "layout_maps": None,
+        "layout_down": {},
+        "layout_strength": 1.0,
+        "layout_t_min": 0,
+        # per-sample conditioning: a batch of B independent edit jobs per run.  Every map above may carry a leading batch
+        # dimension -- keep_maps[s] = (mask (H,W) or (B,H,W), x0 (3,H,W) or (B,3,H,W)), the two independent of each other;
+        # layout_maps[s] (3,H,W) or (B,3,H,W) -- and sample b is then conditioned on row b alone, whatever its position in
+        # the batch, the two-stream split or the rank that runs it (sinddm_sample_chain_batch).  `layout_gain`: None or B
+        # floats in [0, 1], sample b's factor on the layout strength.  `roi_bbs_batch` / `roi_target_patch_batch`: None or
+        # B box lists / B patch lists (each what `roi_bbs` / `roi_target_patch` is for the whole batch; without the
+        # second, every sample takes `roi_target_patch`).  The t schedule, `resample`, `tile`, `layout_down` and
+        # `layout_t_min` stay one per run.
+        "layout_gain": None,
+        "roi_bbs_batch": None,
+        "roi_target_patch_batch": None,
+        # few-step sampling.  `sample_steps`: None (the network is evaluated at every level of every scale, as in the
+        # reference), an int (at most that many evaluations per scale) or one value per scale (None: every level).
+        # `sample_spacing`: which levels are kept -- 't' equally spaced in t, 'logsnr' equally spaced in log kappa
+        # (functions.stride_schedule).  `solver_order`: 1 the step as it is (at a scale > 0 the DDIM form with SinDDM's
+        # re-blur mix, at scale 0 the DDIM form with `eta`), 2 the second-order multistep step on top of it
+        # (sinddm_sample_chain_solver).  `eta`: the noise of a scale-0 step as a share of the posterior's, 1.0 the
+        # reference's DDPM step, 0 deterministic; `omega` stays the knob of the finer scales.  Sampling options like `tile`;
+        # not stored in checkpoints; not with CLIP guidance or `resample`; order 2 not with `layout_maps`.
+        "sample_steps": None,
+        "sample_spacing": 't',
+        "solver_order": 1,
+        "eta": 1.0,
+        # optional noise hook for parity tests: fn(kind, shape, s, t, device) -> tensor
+        "noise_fn": None,
+        # replay aid: when set to a list, every host-side draw ('init' / 'renoise', the tensor itself) and every fused
+        # run of reverse steps (('chain', s, seed, [t...]): the in-kernel draws are sinddm_normal_fill(seed, i)) is logged
+        "draw_log": None,
+        "two_streams": True,       # coarse scales as two half-batches on two streams (sinddm_sample_chain2)
+        "chain_noise": False,      # True: runs with a `noise_fn` take the chain call too (draws handed over as buffers)
+        "chain_guided": True,      # False: ROI-guided runs take the step-by-step route (A/B measurements, bisecting)
+        # ROI guidance (reference models.py:430-431): True -- at every scale but the finest the predicted clean image is pulled
+        # towards `roi_target_patch` inside the boxes `roi_bbs` (or sample b's `roi_bbs_batch[b]`), which stay plain state.
+        "roi_guided_sampling": False,
+        # CLIP guidance (reference models.py:367-431): True -- the guidance branch of p_mean_variance runs, in eager torch
+        # ops, against `clip_model` and the rest of the reference's CLIP state, which stays plain state.
+        "clip_guided_sampling": False,
+    }
+
+
+SAMPLING_OPTIONS = frozenset(sampling_defaults())
+
+
 def refuse(d, opt: str, other: str, on: Optional[bool] = None):
     """Raises NotImplementedError for the pair (opt, other) of NOT_BUILT when `other` is on (`on`; None: as `d` has it).  The
     readers of the options (`_keep_entry`, `_layout_entry`, `_resample_cfg`, `_few_step_cfg`, `_mix_for`) call it where they
@@ -135,7 +238,7 @@ class RunPlan:
             seeds, mix = d._seeds_for(s, B), d._mix_for(s, B)
             self.noise = (("recorded", None) if d.noise_fn is not None else ("seeds", seeds) if seeds is not None
                           else ("mix", mix) if mix is not None else ("torch", None))
-        windowed = at is None and getattr(d, "keep_window", None) is not None
+        windowed = at is None and d.keep_window is not None
         if windowed:
             refuse(d, "keep_window", "clip")
         gated = bool(d.keep_gated)

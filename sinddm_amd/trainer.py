@@ -349,9 +349,7 @@ class MultiscaleTrainer(object):
                               ('roi', bool(em.roi_guided_sampling))):
                 if on:
                     raise NotImplementedError(NOT_BUILT['patch_refine', other])
-        local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=True)
-        local_mix = self._local_mix(seed_mix, seeds, batch_size, sharded=True)
-        local_maps = self._local_batch_maps(batch_size)
+        options = self._call_options(seeds, vary_from_scale, seed_mix, batch_size, sharded=True)
         # --- what to run: one (scale, size index, start timestep) triple per stage ---
         scales = list(range(self.n_scales)) if custom_scales is None else list(custom_scales)
         size_idx = list(range(self.n_scales)) if custom_image_size_idxs is None else list(custom_image_size_idxs)
@@ -376,15 +374,7 @@ class MultiscaleTrainer(object):
                              'without chains (every rank must join the all-gather)')
         mine = sdist.local_batch(batch_size)
         per_scale, cur, shown = [], None, None
-        prev_seeds, prev_mix = em.sample_seeds, em.seed_mix
-        prev_maps = {k: getattr(em, k) for k in local_maps}
-        if local_seeds is not None:
-            em.sample_seeds = local_seeds
-        if local_mix is not None:
-            em.seed_mix = local_mix
-        for k, v in local_maps.items():
-            setattr(em, k, v)
-        try:
+        with em.sampling(**options):
             for stage, s in enumerate(scales):
                 if stage > 0:
                     cur = em.sample_via_scale(mine, cur, s=s, scale_mul=stretch, custom_sample=custom_sample,
@@ -402,10 +392,6 @@ class MultiscaleTrainer(object):
                 if writer:
                     shown = (whole + 1) * 0.5
                     save_image(shown, str(out_dir / t_tag) + f'_out_s{stage}_{tag}_sm_{stretch[0]}_{stretch[1]}.png', nrow=4)
-        finally:
-            em.sample_seeds, em.seed_mix = prev_seeds, prev_mix
-            for k, v in prev_maps.items():
-                setattr(em, k, v)
         if writer and save_unbatched and shown is not None:
             single_dir = Path(str(self.results_folder / f'final_samples_unbatched_{tag}'))
             single_dir.mkdir(parents=True, exist_ok=True)
@@ -595,6 +581,17 @@ class MultiscaleTrainer(object):
             return out[0]
         return [k for k, _ in out], [v for _, v in out]
 
+    def _call_options(self, seeds, vary_from_scale, seed_mix, batch_size, sharded) -> dict:
+        """What a driver call hands `ema_model.sampling(...)`: `sample_seeds` / `seed_mix` when the call gives `seeds` /
+        `seed_mix` (without them what `ema_model` carries stays in force) and, for the drivers that shard the batch over
+        ranks, this rank's rows of the per-sample conditioning.  A key is there only when the call overrides it."""
+        out = {'sample_seeds': self._local_seeds(seeds, vary_from_scale, batch_size, sharded),
+               'seed_mix': self._local_mix(seed_mix, seeds, batch_size, sharded)}
+        out = {k: v for k, v in out.items() if v is not None}
+        if sharded:
+            out.update(self._local_batch_maps(batch_size))
+        return out
+
     # ---- application drivers of the reference that run entirely on the hot path (SURVEY 8(f) row 4) ----
     def _i2i_source(self, input_folder, input_file, mask, hist_ref_path, image_name, use_hist, auto_scale, mode, device):
         """Host-side preparation of harmonization / style transfer: the (optionally shrunk, optionally histogram
@@ -629,8 +626,7 @@ class MultiscaleTrainer(object):
         import os
         device = self.device if device is None else device
         em = self.ema_model
-        local_seeds = self._local_seeds(seeds, vary_from_scale, batch_size, sharded=False)
-        local_mix = self._local_mix(seed_mix, seeds, batch_size, sharded=False)
+        options = self._call_options(seeds, vary_from_scale, seed_mix, batch_size, sharded=False)
         t_starts = em.num_timesteps_ideal if custom_t is None else custom_t
         src, keep = self._i2i_source(input_folder, input_file, mask, hist_ref_path, image_name, use_hist, auto_scale,
                                      mode, device)
@@ -646,12 +642,7 @@ class MultiscaleTrainer(object):
             out_dir.mkdir(parents=True, exist_ok=True)
         last = self.n_scales - 1
         outs, shown = [], None
-        prev_seeds, prev_mix = em.sample_seeds, em.seed_mix
-        if local_seeds is not None:
-            em.sample_seeds = local_seeds
-        if local_mix is not None:
-            em.seed_mix = local_mix
-        try:
+        with em.sampling(**options):
             for s in range(start_s, self.n_scales):
                 # target size of this scale: the (possibly shrunk) input divided by scale_factor^(scales still to go)
                 hw = src_hw / (self.scale_factor ** (last - s))
@@ -665,8 +656,6 @@ class MultiscaleTrainer(object):
                     stem = input_file.rsplit(".", 1)[0]
                     save_image(shown, str(out_dir / f'{stem}_i2i_s_{s}_t_{t_tag}_hist_{"on" if use_hist else "off"}_{stamp}.png'),
                                nrow=4)
-        finally:
-            em.sample_seeds, em.seed_mix = prev_seeds, prev_mix
         if save_images and save_unbatched:
             single_dir = Path(str(self.results_folder / f'unbatched_i2i_s{start_s}_t_{t_tag}_{stamp}'))
             single_dir.mkdir(parents=True, exist_ok=True)
@@ -690,22 +679,19 @@ class MultiscaleTrainer(object):
         em = self.ema_model
         if per_sample and len(roi_bb_list) != int(batch_size):
             raise ValueError(f'roi_guided_sampling: {len(roi_bb_list)} box lists for batch_size={int(batch_size)}')
-        em.roi_guided_sampling = True
-        em.roi_bbs = [] if per_sample else roi_bb_list
-        em.roi_bbs_batch = [list(bbs) for bbs in roi_bb_list] if per_sample else None
-        em.roi_target_patch = []       # (the reference appends on every call; a fresh list per call is what it means)
+        boxes = [list(bbs) for bbs in roi_bb_list] if per_sample else None
+        patches = []                   # (the reference appends on every call; a fresh list per call is what it means)
         for scale in range(self.n_scales):
             bb = [int(bb_i / np.power(self.scale_factor, self.n_scales - scale - 1)) for bb_i in target_roi]
-            em.roi_target_patch.append(extract_patch(self.data_list[scale][0][0][None, :, :, :], bb))
-        try:
+            patches.append(extract_patch(self.data_list[scale][0][0][None, :, :, :], bb))
+        # (the boxes and the patches stay on the model after the call, as in the reference)
+        em.roi_bbs, em.roi_target_patch = [] if per_sample else roi_bb_list, patches
+        with em.sampling(roi_guided_sampling=True, roi_bbs_batch=boxes):
             return self.sample_scales(scale_mul=scale_mul, custom_sample=False, image_name='', batch_size=batch_size,
                                       custom_t_list=custom_t_list,
                                       desc=f'roi_{str(datetime.datetime.now()).replace(":", "_")}',
                                       save_unbatched=save_unbatched, start_noise=True, save_images=save_images,
                                       seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix)
-        finally:
-            em.roi_guided_sampling = False
-            em.roi_bbs_batch = None
 
     # ---- known-region sampling: some pixels are given, the rest is generated to fit (no reference counterpart) ----
     def _sample_kept(self, keep_maps, tag, resample=1, jump_length=1, window=None, **kw):
@@ -713,16 +699,9 @@ class MultiscaleTrainer(object):
         R, J = int(resample), int(jump_length)
         if R < 1 or J < 1:
             raise ValueError(f'{tag}: resample {resample} / jump_length {jump_length} must be >= 1')
-        em.keep_maps = keep_maps
-        em.resample = (R, J) if R > 1 else None
-        em.keep_window = window
-        try:
+        with em.sampling(keep_maps=keep_maps, resample=(R, J) if R > 1 else None, keep_window=window):
             return self.sample_scales(custom_sample=False, image_name='', start_noise=True,
                                       desc=f'{tag}_{str(datetime.datetime.now()).replace(":", "_")}', **kw)
-        finally:
-            em.keep_maps = None
-            em.resample = None
-            em.keep_window = None
 
     @torch.no_grad()
     def inpaint(self, mask, batch_size=16, hard=True, custom_t_list=None, save_unbatched=False, save_images=True,
@@ -835,15 +814,12 @@ class MultiscaleTrainer(object):
             known = [k.to(self.device).contiguous() for k in _layout_pyramid(img, sizes)]
         holds = hold_pyramid(st, sizes, batch=st.dim() == 3)
         maps = {s: (holds[s].to(self.device).contiguous(), known[s]) for s in range(self.n_scales)}
-        em.keep_gated = True
-        try:
-            # ((1, 1) goes in as `inpaint` hands it over: no scale_mul)
-            sm = {} if tuple(float(v) for v in scale_mul) == (1.0, 1.0) else {'scale_mul': tuple(scale_mul)}
-            return self._sample_kept(maps, 'edit', resample=resample, jump_length=jump_length, **sm, batch_size=batch_size, custom_t_list=custom_t_list, save_unbatched=save_unbatched,
-                                     save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale,
-                                     seed_mix=seed_mix, window=window)
-        finally:
-            em.keep_gated = False
+        # ((1, 1) goes in as `inpaint` hands it over: no scale_mul)
+        sm = {} if tuple(float(v) for v in scale_mul) == (1.0, 1.0) else {'scale_mul': tuple(scale_mul)}
+        with em.sampling(keep_gated=True):
+            return self._sample_kept(maps, 'edit', resample=resample, jump_length=jump_length, **sm, batch_size=batch_size,
+                                     custom_t_list=custom_t_list, save_unbatched=save_unbatched, save_images=save_images,
+                                     seeds=seeds, vary_from_scale=vary_from_scale, seed_mix=seed_mix, window=window)
 
     # ---- layout conditioning: redraw a rough picture in the training image's texture (no reference counterpart) ----
     @torch.no_grad()
@@ -856,7 +832,7 @@ class MultiscaleTrainer(object):
         pixels at the finest scale, the same physical band at every scale (`functions.layout_blocks`); the layout reaches
         each scale by area averaging (`functions._layout_pyramid`).  `scales` = (first, last) limits the conditioned scales
         (inclusive; default all).  Runs `sample_scales` with `ema_model.layout_maps` / `layout_down` / `layout_strength` /
-        `layout_t_min` set (`sinddm_layout_opts` of the chain call: still one library call per scale) and clears them afterwards.
+        `layout_t_min` set for the call (`sinddm_layout_opts` of the chain call: still one library call per scale).
         strength = 0 is `sample_scales` itself, bit for bit.  No image-quality claim is made.
         `layout` may be (batch_size, 3, H, W), one picture per sample, and `strength` a list of `batch_size` values: their
         maximum becomes the shared per-step strength and value / maximum the sample's `layout_gain`
@@ -876,19 +852,14 @@ class MultiscaleTrainer(object):
             raise ValueError(f'paint2image: scales {scales} outside 0 ... {self.n_scales - 1}')
         blocks = layout_blocks(down, self.scale_factor, self.n_scales)
         pyr = _layout_pyramid(lay.to(torch.float32), sizes)
-        em.layout_maps = {s: pyr[s].to(self.device).contiguous() for s in range(first, last + 1)}
-        em.layout_down = {s: blocks[s] for s in range(first, last + 1)}
-        em.layout_strength, em.layout_t_min = float(strength), int(t_min)
-        em.layout_gain = gain
-        try:
+        maps = {s: pyr[s].to(self.device).contiguous() for s in range(first, last + 1)}
+        with em.sampling(layout_maps=maps, layout_down={s: blocks[s] for s in range(first, last + 1)},
+                         layout_strength=float(strength), layout_t_min=int(t_min), layout_gain=gain):
             return self.sample_scales(scale_mul=tuple(scale_mul), custom_sample=False, image_name='', start_noise=True,
                                       desc=f'paint2image_{str(datetime.datetime.now()).replace(":", "_")}',
                                       batch_size=batch_size, custom_t_list=custom_t_list, save_unbatched=save_unbatched,
                                       save_images=save_images, seeds=seeds, vary_from_scale=vary_from_scale,
                                       seed_mix=seed_mix)
-        finally:
-            em.layout_maps, em.layout_down, em.layout_strength, em.layout_t_min = None, {}, 1.0, 0
-            em.layout_gain = None
 
     # ---- CLIP-driven modes of the reference.  CLIP itself (clip/, text2live_util/) is not part of this build; the
     # driver takes any `clip_model` with the interface the reference uses: get_text_embedding(text, template=...),
@@ -899,11 +870,15 @@ class MultiscaleTrainer(object):
         em = self.ema_model
         if guidance_sub_iters is None:
             guidance_sub_iters = [*reversed(range(self.n_scales))]
+        embedds_hr = clip_model.get_text_embedding(text_input, template=templates[0])
+        embedds_lr = clip_model.get_text_embedding(text_input, template=templates[1])
+        n_aug = getattr(clip_model, "cfg", {}).get("n_aug", 0)
+        desc = (f"clip_{text_input.replace(' ', '_')}_n_aug{n_aug}_str_{strength}_gsi_" + '_'.join(str(e) for e in guidance_sub_iters)
+                + f'_ff{1 - quantile}' + f'_{str(datetime.datetime.now()).replace(":", "_")}')
+        # (the CLIP state stays on the model after the call, as in the reference)
         em.clip_strength = strength
         em.clip_text = text_input
-        em.text_embedds_hr = clip_model.get_text_embedding(text_input, template=templates[0])
-        em.text_embedds_lr = clip_model.get_text_embedding(text_input, template=templates[1])
-        em.clip_guided_sampling = True
+        em.text_embedds_hr, em.text_embedds_lr = embedds_hr, embedds_lr
         em.guidance_sub_iters = guidance_sub_iters
         em.quantile = quantile
         em.stop_guidance = stop_guidance
@@ -912,11 +887,8 @@ class MultiscaleTrainer(object):
         em.llambda = llambda
         em.clip_mask = None
         em.x_recon_prev = None
-        n_aug = getattr(clip_model, "cfg", {}).get("n_aug", 0)
-        desc = (f"clip_{text_input.replace(' ', '_')}_n_aug{n_aug}_str_{strength}_gsi_" + '_'.join(str(e) for e in guidance_sub_iters)
-                + f'_ff{1 - quantile}' + f'_{str(datetime.datetime.now()).replace(":", "_")}')
-        try:
-            if not start_noise:                                             # clip_style_trans: start from the last two scales
+        with em.sampling(clip_guided_sampling=True):
+            if not start_noise:                                            # clip_style_trans: start from the last two scales
                 return self.sample_scales(scale_mul=scale_mul, custom_sample=True,
                                           custom_scales=[self.n_scales - 2, self.n_scales - 1],
                                           custom_image_size_idxs=[self.n_scales - 2, self.n_scales - 1],
@@ -925,8 +897,6 @@ class MultiscaleTrainer(object):
             return self.sample_scales(scale_mul=scale_mul, custom_sample=False, image_name='', batch_size=sample_batch_size,
                                       custom_t_list=custom_t_list, desc=desc, save_unbatched=save_unbatched,
                                       start_noise=start_noise)
-        finally:
-            em.clip_guided_sampling = False
 
     def clip_roi_sampling(self, clip_model, text_input, strength, sample_batch_size, num_clip_iters=100,
                           num_denoising_steps=2, clip_roi_bb=None, save_unbatched=False, template='lr',

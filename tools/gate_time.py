@@ -9,8 +9,8 @@ Timing: one process times ONE variant of `_run_steps` at one scale with `keep_ma
 `keep_gated` (sinddm_sample_chain_gate: the same kernels with a threshold per step).  One warm-up run, then `--runs` timed runs of
 `--steps` reverse steps each (t = steps - 1 ... 0); host clock around a device-synchronised call, divided by the number of
 steps: ms per network evaluation + tail.  C2 scale 1 is 67x90, scale 4 is 186x248.
-`--tree DIR` takes the package of another checkout (its own library beside its own sources), e.g. the parent commit, which has
-the ungated variant only.  Alternate fresh processes of the variants on one box.
+`--tree DIR` takes the package of another checkout (its own library beside its own sources, with `sampling()`), e.g. the parent
+commit.  Alternate fresh processes of the variants on one box.
 `--digest`: the SHA-256 of the result of an ungated keep run of `_run_steps` on the four shapes of the tail kernels (plain fused,
 padded rows with two streams, padded rows, unfused; three steps incl. t = 0; torch.manual_seed fixed) -- run it with this tree
 and with `--tree` of the parent and compare: the option must not move a byte of the run without it.  Prints one JSON line."""
@@ -44,10 +44,10 @@ def setup(config, dim, s, B, dev):
     net, d = build_diffusion(config, dim, dev)
     H, W = d.image_sizes[s]
     k0 = (hash_randn((3, H, W), 300 + s) * 0.6).clamp(-1, 1)
-    d.keep_maps = {s: (hold_map(H, W).to(dev).contiguous(), k0.to(dev).contiguous())}
+    maps = {s: (hold_map(H, W).to(dev).contiguous(), k0.to(dev).contiguous())}
     x0 = (hash_randn((B, 3, H, W), 31 + s) * 0.8).to(dev)
     d.img_prev_upsample = (hash_randn((B, 3, H, W), 32 + s) * 0.5).clamp(-1, 1).to(dev)
-    return d, x0, (H, W)
+    return d, maps, x0, (H, W)
 
 
 def main():
@@ -73,28 +73,27 @@ def main():
     if args.digest:
         res["digest"] = {}
         for cfg, dim, s, B, aux, ts in SHAPES:
-            d, x0, (H, W) = setup(cfg, dim, s, B, dev)
-            d.two_streams = aux
+            d, maps, x0, (H, W) = setup(cfg, dim, s, B, dev)
             torch.manual_seed(1234 + s)
-            y = d._run_steps(x0.clone(), s, ts)
-            torch.cuda.synchronize()
+            with d.sampling(keep_maps=maps, two_streams=aux):
+                y = d._run_steps(x0.clone(), s, ts)
+                torch.cuda.synchronize()
             assert bool(torch.isfinite(y).all())
             res["digest"][f"{cfg}_dim{dim}_s{s}_{H}x{W}_B{B}"] = hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest()
     else:
         s, B = args.scale, args.batch
-        d, x0, (H, W) = setup(args.config, args.dim, s, B, dev)
-        if args.variant == "gated":
-            d.keep_gated = True
+        d, maps, x0, (H, W) = setup(args.config, args.dim, s, B, dev)
         ts = list(range(args.steps - 1, -1, -1))
         torch.manual_seed(7)
 
         def run():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            y = d._run_steps(x0.clone(), s, ts)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            km, kx = d.keep_maps[s]
+            with d.sampling(keep_maps=maps, keep_gated=args.variant == "gated"):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                y = d._run_steps(x0.clone(), s, ts)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+            km, kx = maps[s]
             known = (km == 1).expand(B, H, W)[:, None].expand(B, 3, H, W)
             assert bool(torch.isfinite(y).all()) and torch.equal(y[known], kx.expand(B, 3, H, W)[known])     # t = 0 ends the run
             return dt / len(ts)

@@ -13,6 +13,7 @@ re-noise + every reverse step of the scale).
 sources) -- a commit from before the option: alternate such runs with runs of this tree on one box to see whether the plain path
 moved.  Prints one JSON line."""
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -69,13 +70,9 @@ def main():
     torch.manual_seed(7)
 
     def run(name):
-        if variants[name] is not None:
-            d.keep_maps = variants[name]
-        try:
+        # (plain sets nothing: a `--tree` from before `sampling()` runs it)
+        with d.sampling(keep_maps=variants[name]) if variants[name] is not None else contextlib.nullcontext():
             per, img = timed_sample(d, args.batch)
-        finally:
-            if variants[name] is not None:
-                d.keep_maps = None
         if variants[name] is not None:                         # the kept pixels of the finest scale are the known image
             m, k0 = variants[name][d.n_scales - 1]
             assert torch.equal(img[:, :, m == 1], k0[None].expand_as(img)[:, :, m == 1])

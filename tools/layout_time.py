@@ -43,17 +43,19 @@ def main():
     x0 = (hash_randn((args.batch, 3, H, W), 31 + s) * 0.8).to(dev)
     d.img_prev_upsample = (hash_randn((args.batch, 3, H, W), 32 + s) * 0.5).clamp(-1, 1).to(dev)
     t_min = {"plain": None, "all": 0, "half": n // 2}[args.mode]
+    opts = {}
     if t_min is not None:
-        d.layout_maps = {s: (hash_randn((3, H, W), 83) * 0.6).clamp(-1, 1).to(dev)}
-        d.layout_down, d.layout_strength, d.layout_t_min = {s: args.down}, 1.0, t_min
+        opts = dict(layout_maps={s: (hash_randn((3, H, W), 83) * 0.6).clamp(-1, 1).to(dev)}, layout_down={s: args.down},
+                    layout_strength=1.0, layout_t_min=t_min)
     torch.manual_seed(7)
 
     def run():
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        y = d._run_steps(x0, s, t_seq)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
+        with d.sampling(**opts):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            y = d._run_steps(x0, s, t_seq)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
         assert bool(torch.isfinite(y).all())
         return dt
 

@@ -17,6 +17,7 @@ Times are host clocks around device-synchronised `_run_steps` calls, so they inc
 sources) -- a commit from before the option: alternate such runs with runs of this tree on one box to see whether the plain path
 moved.  Prints one JSON line."""
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -67,22 +68,19 @@ def main():
         rec_z = torch.randn((B, 3, H, W), device=dev) if "recorded" in variants else None
 
         def run(name):
+            opts = {}
             if name == "seeded":
-                d.sample_seeds = seeds
+                opts = dict(sample_seeds=seeds)
             elif name.startswith("mix"):
-                d.seed_mix = mix(int(name[3:]))
+                opts = dict(seed_mix=mix(int(name[3:])))
             elif name == "recorded":
-                d.noise_fn, d.chain_noise = (lambda kind, shape, ss, tt, dv: rec_z), True
-            try:
+                opts = dict(noise_fn=lambda kind, shape, ss, tt, dv: rec_z, chain_noise=True)
+            with d.sampling(**opts) if opts else contextlib.nullcontext():     # (plain: a `--tree` from before `sampling()`)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 y = d._run_steps(x0, s, ts)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
-            finally:
-                if not args.plain_only:
-                    d.sample_seeds = d.seed_mix = d.noise_fn = None
-                    d.chain_noise = False
             assert bool(torch.isfinite(y).all())
             return dt / args.steps * 1e3
 

@@ -14,6 +14,7 @@ Times are host clocks around device-synchronised `_run_steps` calls, so the seed
 sources) -- a commit from before the option: alternate such runs with runs of this tree on one box to see whether the plain path
 moved.  Prints one JSON line."""
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -57,17 +58,13 @@ def main():
         ts = list(reversed(range(args.steps)))
 
         def run(name):
-            if name == "seeded":
-                d.sample_seeds = seeds
-            try:
+            # (plain sets nothing: a `--tree` from before `sampling()` runs it)
+            with d.sampling(sample_seeds=seeds) if name == "seeded" else contextlib.nullcontext():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 y = d._run_steps(x0, s, ts)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
-            finally:
-                if name == "seeded":
-                    d.sample_seeds = None
             assert bool(torch.isfinite(y).all())
             return dt / args.steps * 1e3
 

@@ -26,10 +26,9 @@ VARIANTS = (("off", (False, False)), ("x", (False, True)), ("xy", (True, True)))
 
 def timed_sample(d, batch, tile):
     """One sample over the full pyramid; returns seconds per scale."""
-    d.tile = tile
     per_scale = []
     img = None
-    try:
+    with d.sampling(tile=tile):
         for s in range(d.n_scales):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -37,8 +36,6 @@ def timed_sample(d, batch, tile):
             torch.cuda.synchronize()
             per_scale.append(time.perf_counter() - t0)
             assert tuple(img.shape[2:]) == tuple(d.image_sizes[s]) and bool(torch.isfinite(img).all())
-    finally:
-        d.tile = (False, False)
     return per_scale
 
 

@@ -87,10 +87,8 @@ def main():
     m = torch.ones(H, W, device=dev)
     y0, x0 = (H - side) // 2, (W - side) // 2
     m[y0:y0 + side, x0:x0 + side] = 0
-    d.keep_maps = {s: (m, (hash_randn((3, H, W), 40) * 0.6).clamp(-1, 1).to(dev))}
-    d.sample_seeds = [1000 + b for b in range(B)]
+    keep = {s: (m, (hash_randn((3, H, W), 40) * 0.6).clamp(-1, 1).to(dev))}
     d.img_prev_upsample = (hash_randn((B, 3, H, W), 42 + s) * 0.4).clamp(-1, 1).to(dev) if s > 0 else None
-    d.keep_window = 16 if N else None
     x = (hash_randn((B, 3, H, W), 43 + s) * 0.8).to(dev)
     levels = list(range(n - 1, -1, -1))
     res = {"tool": "time_window", "device": torch.cuda.get_device_name(0), "variant": args.variant, "config": args.config,
@@ -103,48 +101,49 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / per
 
-    if args.variant == "keep":
-        plan = RunPlan(d, x, s, levels)
-        assert (plan.window is None) == (N == 0) and (N == 0 or plan.window[:2] == (N, N)), plan.window
-        run = lambda: d._run_steps(x.clone(), s, levels)
-        assert bool(torch.isfinite(run()).all())               # warm-up: workspace, code objects
-        per = [timed(run, n) for _ in range(args.runs)]
-        res.update(evals=n, ms_per_eval_runs=[round(1e3 * v, 4) for v in per], ms_per_eval_median=round(1e3 * statistics.median(per), 4))
-        if N:
+    with d.sampling(keep_maps=keep, sample_seeds=[1000 + b for b in range(B)], keep_window=16 if N else None):
+        if args.variant == "keep":
+            plan = RunPlan(d, x, s, levels)
+            assert (plan.window is None) == (N == 0) and (N == 0 or plan.window[:2] == (N, N)), plan.window
+            run = lambda: d._run_steps(x.clone(), s, levels)
+            assert bool(torch.isfinite(run()).all())               # warm-up: workspace, code objects
+            per = [timed(run, n) for _ in range(args.runs)]
+            res.update(evals=n, ms_per_eval_runs=[round(1e3 * v, 4) for v in per], ms_per_eval_median=round(1e3 * statistics.median(per), 4))
+            if N:
+                win = _KeepWindow(d, plan, x)
+                ids = [noise_stream_id(s, "step", i) for i in range(n)]
+                win.fill(ids)
+                fill = [timed(lambda: win.fill(ids), n) for _ in range(args.runs)]
+                res.update(fill_ms_per_eval_median=round(1e3 * statistics.median(fill), 4),
+                           fill_share=round(statistics.median(fill) / statistics.median(per), 4))
+        else:
+            lib, reps = _lib.load(), args.reps
+            plan = RunPlan(d, x, s, levels)
             win = _KeepWindow(d, plan, x)
-            ids = [noise_stream_id(s, "step", i) for i in range(n)]
-            win.fill(ids)
-            fill = [timed(lambda: win.fill(ids), n) for _ in range(args.runs)]
-            res.update(fill_ms_per_eval_median=round(1e3 * statistics.median(fill), 4),
-                       fill_share=round(statistics.median(fill) / statistics.median(per), 4))
-    else:
-        lib, reps = _lib.load(), args.reps
-        plan = RunPlan(d, x, s, levels)
-        win = _KeepWindow(d, plan, x)
-        sid = noise_stream_id(s, "step", 0)
-        seeds = torch.tensor(d.sample_seeds, dtype=torch.int64, device=dev)
-        full = torch.empty((B, 3, H, W), device=dev)
-        ids, out = torch.tensor([sid], dtype=torch.int64, device=dev), torch.empty((1, B, 3, N, N), device=dev)
-        st = _lib.stream_ptr(dev)
+            sid = noise_stream_id(s, "step", 0)
+            seeds = torch.tensor(d.sample_seeds, dtype=torch.int64, device=dev)
+            full = torch.empty((B, 3, H, W), device=dev)
+            ids, out = torch.tensor([sid], dtype=torch.int64, device=dev), torch.empty((1, B, 3, N, N), device=dev)
+            st = _lib.stream_ptr(dev)
 
-        def window_fill():
-            for _ in range(reps):
-                _lib.check(lib.sinddm_normal_fill_window(_lib.ptr(out), 1, _lib.ptr(ids), B, H, W, _lib.ptr(win.org), N, N,
-                                                         _lib.ptr(win.kd), None, 1, st), "sinddm_normal_fill_window")
+            def window_fill():
+                for _ in range(reps):
+                    _lib.check(lib.sinddm_normal_fill_window(_lib.ptr(out), 1, _lib.ptr(ids), B, H, W, _lib.ptr(win.org), N, N,
+                                                             _lib.ptr(win.kd), None, 1, st), "sinddm_normal_fill_window")
 
-        def full_fill_and_slice():
-            for _ in range(reps):
-                _lib.check(lib.sinddm_normal_fill_samples(_lib.ptr(full), B, 3 * H * W, _lib.ptr(seeds), sid, st),
-                           "sinddm_normal_fill_samples")
-                win.crop(full)
+            def full_fill_and_slice():
+                for _ in range(reps):
+                    _lib.check(lib.sinddm_normal_fill_samples(_lib.ptr(full), B, 3 * H * W, _lib.ptr(seeds), sid, st),
+                               "sinddm_normal_fill_samples")
+                    win.crop(full)
 
-        window_fill(), full_fill_and_slice()
-        assert torch.equal(out[0], win.crop(full))             # (the two routes make the same numbers)
-        a = [timed(window_fill, reps) for _ in range(args.runs)]
-        b = [timed(full_fill_and_slice, reps) for _ in range(args.runs)]
-        res.update(reps=reps, window_fill_us=round(1e6 * statistics.median(a), 2),
-                   full_fill_and_slice_us=round(1e6 * statistics.median(b), 2),
-                   window_fill_us_runs=[round(1e6 * v, 2) for v in a], full_fill_and_slice_us_runs=[round(1e6 * v, 2) for v in b])
+            window_fill(), full_fill_and_slice()
+            assert torch.equal(out[0], win.crop(full))             # (the two routes make the same numbers)
+            a = [timed(window_fill, reps) for _ in range(args.runs)]
+            b = [timed(full_fill_and_slice, reps) for _ in range(args.runs)]
+            res.update(reps=reps, window_fill_us=round(1e6 * statistics.median(a), 2),
+                       full_fill_and_slice_us=round(1e6 * statistics.median(b), 2),
+                       window_fill_us_runs=[round(1e6 * v, 2) for v in a], full_fill_and_slice_us_runs=[round(1e6 * v, 2) for v in b])
     line = json.dumps(res)
     print(line)
     if args.out:
