@@ -762,6 +762,28 @@ int sinddm_patch_nnf_scaled(const float* query, int q_per_sample, const float* r
                             int Hr, int Wr, int P, int wrap_q, int wrap_r, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* The field searched in a window around a prior position (csrc/patch_local.h): a refinement that costs what its window
+ * costs.  query, ref, ref_ok, ref_scale, the grids (hq, wq) / (hr, wr), wrap_q / wrap_r and P as in sinddm_patch_nnf(_scaled);
+ * there is no workspace.
+ *   prior  (B, hq, wq) int32: for every query position a linear position py * wr + px in the reference grid.  An entry < 0
+ *          or >= hr wr means "no prior": that query gets idx = -1 and dist = +inf and reads nothing of the reference.
+ *   radius R, 0 <= R <= 16: the candidates of a query are the positions (py + dy, px + dx), |dy|, |dx| <= R, taken modulo
+ *          the grid on a wrapped reference axis and dropped when outside the grid otherwise; positions inadmissible under
+ *          ref_ok are dropped too.  R = 0 evaluates the prior itself: the energy of a given field.
+ * The ranking value of a candidate is the exact-form distance sinddm_patch_nnf reports for its winner, d = fmaf(a_k - b_k,
+ * a_k - b_k, .) over k from 0 in element order (c, dy, dx), ONE fp32 chain; with ref_scale it is v = d * s_j (one fp32
+ * multiply; every s_j finite and > 0 as there).  The winner is the candidate with the smallest value, ties to the smallest
+ * linear idx; a wrapped window that reaches a position twice counts it once.  dist is the unscaled d of the winner.  So
+ *   an identical patch inside the window gives exactly 0.0;
+ *   dist is bit-equal to what sinddm_patch_nnf writes for the same (query, position) pair;
+ *   the result is bit-reproducible and independent of B, of the tile and of which wave or lane evaluated a candidate;
+ *   a query with no admissible candidate gets idx = -1 and dist = +inf.
+ * SINDDM_E_BADARG (before any device work): a null query / ref / prior / dist / idx, B < 1, P outside {3, 5, 7}, a radius
+ * outside 0 .. 16; SINDDM_E_BADSHAPE: an axis shorter than P, a grid of 2^31 positions or more. */
+int sinddm_patch_nnf_local(const float* query, int q_per_sample, const float* ref, int r_per_sample, const float* ref_ok,
+                           const float* ref_scale, int scale_per_sample, const int32_t* prior, int radius, float* dist,
+                           int32_t* idx, int B, int Hq, int Wq, int Hr, int Wr, int P, int wrap_q, int wrap_r, void* stream);
+
 /* Patch vote (csrc/patch_vote.h): every pixel becomes the mean of the reference patches that the field puts over it.
  *   idx    (B, hq, wq) int32: a field as sinddm_patch_nnf writes it (linear positions in the (hr, wr) reference grid; the
  *          grids follow from the sizes, P and wrap_q / wrap_r as there).  An entry < 0 or >= hr wr names no patch.

@@ -86,6 +86,8 @@ patch-vote iterations -- every `--patch_refine_patch {3,5,7}` patch is replaced 
 becomes the mean of the patches that cover it (the EM step of GPNN) -- before the next scale re-noises and redraws it.
 `--patch_refine_alpha A` ranks with GPNN's completeness normalisation D / (A 3P^2 + min D) (coverage in place of plain
 fidelity); `--patch_refine_blend B` in [0, 1] moves only the share B of the way.  Off by default.
+`--patch_refine_radius R` (0 .. 16) searches exhaustively only at the first refined scale: every later search looks in a
+window of R positions around the previous field, carried from iteration to iteration and from scale to scale.
 `score` (no reference mode) asks the MODEL: `--mode score [--input_image FILE ...] [--score_levels N] [--score_draws R]
 [--score_scales A B]` evaluates the training L1 loss |z - eps| per pixel with the trained weights, at N noise levels per scale
 (default 10, spread over the levels the scale was trained on) and R noise draws per level (default 4; `--seeds` names them), on
@@ -227,6 +229,7 @@ def build_parser():
     p.add_argument("--patch_refine_alpha", type=float, default=None, metavar="A")
     p.add_argument("--patch_refine_blend", type=float, default=1.0, metavar="B")
     p.add_argument("--patch_refine_scales", type=int, nargs=2, default=None, metavar=("A", "B"))
+    p.add_argument("--patch_refine_radius", type=int, default=None, metavar="R")
     # no reference flags: the denoising-score maps of `score` (MultiscaleTrainer.score)
     p.add_argument("--score_levels", type=int, default=10, metavar="N")
     p.add_argument("--score_draws", type=int, default=4, metavar="R")
@@ -308,8 +311,8 @@ def parse_args(argv=None):
     args.patch_refine_opt = None
     if args.patch_refine is None:
         if (args.patch_refine_patch != 7 or args.patch_refine_alpha is not None or args.patch_refine_blend != 1.0
-                or args.patch_refine_scales is not None):
-            p.error("--patch_refine_patch / _alpha / _blend / _scales need --patch_refine ITERS")
+                or args.patch_refine_scales is not None or args.patch_refine_radius is not None):
+            p.error("--patch_refine_patch / _alpha / _blend / _scales / _radius need --patch_refine ITERS")
     else:
         if args.mode not in ("sample", "evaluate"):
             p.error(f"--patch_refine goes with --mode sample and --mode evaluate, not with --mode {args.mode}")
@@ -325,6 +328,10 @@ def parse_args(argv=None):
             p.error("--patch_refine_scales A B needs 0 <= A <= B")
         args.patch_refine_opt = dict(iters=args.patch_refine, patch=args.patch_refine_patch, alpha=a, blend=b,
                                      scales=None if sc is None else (sc[0], sc[1]))
+        if args.patch_refine_radius is not None:               # (absent: the option dict every earlier command line made)
+            if not 0 <= args.patch_refine_radius <= 16:
+                p.error("--patch_refine_radius R must be in 0 .. 16")
+            args.patch_refine_opt["radius"] = args.patch_refine_radius
     args.score_images = None
     if args.mode == "score":
         if args.score_levels < 1 or args.score_draws < 1:

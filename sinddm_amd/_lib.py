@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "sinddm_patch_nnf_scaled_workspace_bytes", "sinddm_patch_nnf_scaled", "sinddm_patch_vote",
     "sinddm_score_workspace_bytes", "sinddm_score_chain",
     "sinddm_normal_fill_window",
+    "sinddm_patch_nnf_local",
 )
 
 
@@ -239,6 +240,7 @@ def load() -> C.CDLL:
         "sinddm_patch_nnf_scaled_workspace_bytes": (sz, [i, i, i, i, i, i, i, i]),
         "sinddm_patch_nnf_scaled": (i, [p, i, p, i, p, p, i, p, p, i, i, i, i, i, i, i, i, p, sz, p]),
         "sinddm_patch_vote": (i, [p, p, i, p, p, i, p, i, i, i, i, i, i, i, i, f, p]),
+        "sinddm_patch_nnf_local": (i, [p, i, p, i, p, p, i, p, i, p, p, i, i, i, i, i, i, i, i, p]),
         "sinddm_score_workspace_bytes": (sz, [i, i, i, i, i]),
         "sinddm_score_chain": (i, [p, p, p, p, p, p, p, p, C.POINTER(C.c_int), i, f, C.c_uint64, C.c_uint64, p, p, i, i, i, i,
                                    p, sz, p, C.POINTER(ScoreOpts)]),

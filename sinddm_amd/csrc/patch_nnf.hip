@@ -1,6 +1,7 @@
-// Third translation unit of libsinddm_hip.so: the patch nearest-neighbour field (patch_nnf.h), its scaled ranking and the
-// patch vote (patch_vote.h), and their C entries.
+// Third translation unit of libsinddm_hip.so: the patch nearest-neighbour field (patch_nnf.h), its scaled ranking, the
+// windowed search around a prior (patch_local.h) and the patch vote (patch_vote.h), and their C entries.
 #include "patch_nnf.h"
+#include "patch_local.h"
 #include "patch_vote.h"
 
 #include <cmath>
@@ -50,6 +51,24 @@ extern "C" int sinddm_patch_nnf_scaled(const float* query, int q_per_sample, con
         case 3: return nnf::launch<3, true>(query, q_per_sample, ref, r_per_sample, ref_ok, dist, idx, B, Hq, Wq, Hr, Wr, (int)hq, (int)wq, (int)hr, (int)wr, workspace, st, ref_scale, scale_per_sample);
         case 5: return nnf::launch<5, true>(query, q_per_sample, ref, r_per_sample, ref_ok, dist, idx, B, Hq, Wq, Hr, Wr, (int)hq, (int)wq, (int)hr, (int)wr, workspace, st, ref_scale, scale_per_sample);
         default: return nnf::launch<7, true>(query, q_per_sample, ref, r_per_sample, ref_ok, dist, idx, B, Hq, Wq, Hr, Wr, (int)hq, (int)wq, (int)hr, (int)wr, workspace, st, ref_scale, scale_per_sample);
+    }
+}
+
+extern "C" int sinddm_patch_nnf_local(const float* query, int q_per_sample, const float* ref, int r_per_sample,
+                                      const float* ref_ok, const float* ref_scale, int scale_per_sample, const int32_t* prior,
+                                      int radius, float* dist, int32_t* idx, int B, int Hq, int Wq, int Hr, int Wr, int P,
+                                      int wrap_q, int wrap_r, void* stream) {
+    if (!query || !ref || !prior || !dist || !idx || B < 1) return SINDDM_E_BADARG;
+    if (P != 3 && P != 5 && P != 7) return SINDDM_E_BADARG;
+    if (radius < 0 || radius > nnf::LOCAL_MAX_RADIUS) return SINDDM_E_BADARG;
+    long long hq, wq, hr, wr;
+    if (!nnf::geometry(Hq, Wq, P, wrap_q, &hq, &wq) || !nnf::geometry(Hr, Wr, P, wrap_r, &hr, &wr)) return SINDDM_E_BADSHAPE;
+    if (hq * wq >= (1ll << 31) || hr * wr >= (1ll << 31)) return SINDDM_E_BADSHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    switch (P) {
+        case 3: return nnf::launch_local<3>(query, q_per_sample, ref, r_per_sample, ref_ok, ref_scale, scale_per_sample, prior, radius, dist, idx, B, Hq, Wq, Hr, Wr, (int)hq, (int)wq, (int)hr, (int)wr, wrap_r, st);
+        case 5: return nnf::launch_local<5>(query, q_per_sample, ref, r_per_sample, ref_ok, ref_scale, scale_per_sample, prior, radius, dist, idx, B, Hq, Wq, Hr, Wr, (int)hq, (int)wq, (int)hr, (int)wr, wrap_r, st);
+        default: return nnf::launch_local<7>(query, q_per_sample, ref, r_per_sample, ref_ok, ref_scale, scale_per_sample, prior, radius, dist, idx, B, Hq, Wq, Hr, Wr, (int)hq, (int)wq, (int)hr, (int)wr, wrap_r, st);
     }
 }
 

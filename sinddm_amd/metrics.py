@@ -137,6 +137,76 @@ def _patch_nnf_scaled(query, ref, patch, wrap_query, wrap_ref, ok, ref_scale, B,
     return dist, yx
 
 
+MAX_RADIUS = 16
+
+
+def check_radius(radius, what="patch_nnf_local") -> int:
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MAX_RADIUS:
+        raise SinddmError(f"{what}: radius must be an integer in 0 .. {MAX_RADIUS}, got {radius!r}")
+    return radius
+
+
+def patch_nnf_local(query: torch.Tensor, ref: torch.Tensor, prior: torch.Tensor, radius: int, patch: int = 7,
+                    wrap_query=(False, False), wrap_ref=(False, False), ref_valid: Optional[torch.Tensor] = None,
+                    ref_scale: Optional[torch.Tensor] = None):
+    """`patch_nnf` searched in a window: every query patch is compared with the reference positions within `radius` (0 .. 16)
+    of its `prior` position only (`sinddm_patch_nnf_local`, csrc/patch_local.h).  `prior`: (B, 2, hq, wq) int32 coordinates
+    as `patch_nnf` returns them, or (B, hq, wq) int32 linear positions (its batch may be the only one that is not 1: one
+    query searched around several priors); a (-1, .) pair or an entry outside the reference
+    grid means "no prior" and gives dist = +inf, yx = (-1, wr - 1) (the linear position -1, as the vote reads it).  The
+    other arguments, the ranking with `ref_scale` and the returned (dist, yx) are `patch_nnf`'s; `dist` of a winner is
+    bit-equal to what `patch_nnf` reports for the same pair."""
+    radius = check_radius(radius)
+    for name, t in (("query", query), ("ref", ref)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise SinddmError(f"patch_nnf_local: {name} must be on a ROCm device (no CPU fallback)")
+        if t.dim() != 4 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise SinddmError(f"patch_nnf_local: {name} must be a (B, 3, H, W) float32 tensor, got {tuple(t.shape)} {t.dtype}")
+    if patch not in PATCHES:
+        raise SinddmError(f"patch_nnf_local: patch must be one of {PATCHES}, got {patch}")
+    if not isinstance(prior, torch.Tensor) or prior.dtype != torch.int32 or prior.device != query.device:
+        raise SinddmError("patch_nnf_local: prior must be an int32 tensor on the device of query")
+    Bq, Br = query.shape[0], ref.shape[0]
+    B = max(Bq, Br, prior.shape[0] if prior.dim() else 1)     # (one query image may be searched around several priors)
+    if Bq not in (1, B) or Br not in (1, B) or ref.device != query.device:
+        raise SinddmError(f"patch_nnf_local: batches of {Bq} and {Br} on {query.device} / {ref.device} do not go together")
+    Hq, Wq, Hr, Wr = query.shape[2], query.shape[3], ref.shape[2], ref.shape[3]
+    if min(Hq, Wq, Hr, Wr) < patch:
+        raise SinddmError(f"patch_nnf_local: an axis of {(Hq, Wq)} / {(Hr, Wr)} is shorter than the patch ({patch})")
+    hq, wq = grid_size((Hq, Wq), patch, wrap_query)
+    hr, wr = grid_size((Hr, Wr), patch, wrap_ref)
+    if prior.dim() == 4 and prior.shape[1] == 2:
+        lin = prior[:, 0] * wr + prior[:, 1]
+        off = (prior[:, 0] < 0) | (prior[:, 0] >= hr) | (prior[:, 1] < 0) | (prior[:, 1] >= wr)
+        prior = torch.where(off, torch.full_like(lin, -1), lin).to(torch.int32)
+    if prior.dim() != 3 or tuple(prior.shape) != (B, hq, wq):
+        raise SinddmError(f"patch_nnf_local: prior must be ({B}, {hq}, {wq}) or ({B}, 2, {hq}, {wq}), got {tuple(prior.shape)}")
+    query, ref, prior = query.contiguous(), ref.contiguous(), prior.contiguous()
+    ok = None
+    if ref_valid is not None:
+        if tuple(ref_valid.shape) != (Hr, Wr):
+            raise SinddmError(f"patch_nnf_local: ref_valid must be ({Hr}, {Wr}), got {tuple(ref_valid.shape)}")
+        ok = position_ok(ref_valid.to(ref.device), patch, wrap_ref)
+    per_sample_scale = 0
+    if ref_scale is not None:
+        ref_scale = check_ref_scale(ref_scale, B, (hr, wr))
+        if ref_scale.device != query.device:
+            raise SinddmError("patch_nnf_local: ref_scale must be on the device of query")
+        ref_scale = ref_scale.contiguous()
+        per_sample_scale = int(ref_scale.shape[0] == B and B > 1)
+    lib = _lib.load()
+    with torch.cuda.device(query.device):
+        dist = torch.empty(B, hq, wq, dtype=torch.float32, device=query.device)
+        idx = torch.empty(B, hq, wq, dtype=torch.int32, device=query.device)
+        rc = lib.sinddm_patch_nnf_local(_lib.ptr(query), int(Bq == B), _lib.ptr(ref), int(Br == B), _lib.ptr(ok),
+                                        _lib.ptr(ref_scale), per_sample_scale, _lib.ptr(prior), radius, _lib.ptr(dist),
+                                        _lib.ptr(idx), B, Hq, Wq, Hr, Wr, patch, _wrap_bits(wrap_query), _wrap_bits(wrap_ref),
+                                        _lib.stream_ptr(query.device))
+    _lib.check(rc, "sinddm_patch_nnf_local")
+    yx = torch.stack([torch.div(idx, wr, rounding_mode="floor"), idx % wr], dim=1).to(torch.int32)
+    return dist, yx
+
+
 def nnf_stats(dist: torch.Tensor, yx: torch.Tensor, patch: int, ref_grid: Sequence[int], wrap_query=(False, False),
               wrap_ref=(False, False)) -> dict:
     """Numbers of a field (`dist` (B, h, w), `yx` (B, 2, h, w)) against a reference grid of `ref_grid` = (hr, wr) positions;

@@ -334,12 +334,15 @@ class MultiscaleTrainer(object):
         `seed_mix`: in place of `seeds`, the GLOBAL blend tables (keys, weights), [batch_size][K] or
         [n_scales][batch_size][K] (`ema_model.seed_mix` for the duration of the call; `models.interp_seeds`, `loop_seeds`,
         `mix_from_scale`): sample b is frame b, and a rank takes the rows of its own shard like its seeds.
-        `patch_refine`: a `refine.PatchRefine` or a dict of its fields (`iters`, `patch`, `alpha`, `blend`, `scales` = (a, b)).
+        `patch_refine`: a `refine.PatchRefine` or a dict of its fields (`iters`, `patch`, `alpha`, `blend`, `scales` = (a, b),
+        `radius`).
         After the chain of every scale in [a, b] the rank's own shard is snapped to that scale's training image by `iters`
         field-and-vote iterations (`refine.patch_refine`; wrapped axes as `ema_model.tile`, holes of `train_mask` never
         copied from) before it is gathered and before the next scale upsamples it.  The iterations are independent per
-        sample, so a sharded run makes the images of the single process.  With `keep_maps`, `layout_maps` or ROI guidance
-        on `ema_model` it raises NotImplementedError (`sampler.NOT_BUILT`)."""
+        sample, so a sharded run makes the images of the single process.  With a `radius` only the first covered
+        scale searches exhaustively: its last field, carried to the sizes of the next covered scale (`refine.carry_field`), is
+        the prior of that scale's windowed search, and so on up the pyramid -- per sample as well.  With `keep_maps`,
+        `layout_maps` or ROI guidance on `ema_model` it raises NotImplementedError (`sampler.NOT_BUILT`)."""
         em = self.ema_model
         if patch_refine is not None:
             from .refine import PatchRefine
@@ -374,6 +377,7 @@ class MultiscaleTrainer(object):
                              'without chains (every rank must join the all-gather)')
         mine = sdist.local_batch(batch_size)
         per_scale, cur, shown = [], None, None
+        carried = None                                  # (field, sample size, image size) of the last refined scale
         with em.sampling(**options):
             for stage, s in enumerate(scales):
                 if stage > 0:
@@ -384,7 +388,18 @@ class MultiscaleTrainer(object):
                 else:                                   # start from the training image of that scale instead of noise
                     seed_img = Image.open(self.input_paths[s] + '/' + image_name).convert('RGB')
                     cur = image_to_tensor(seed_img).repeat(mine, 1, 1, 1).to(self.device)
-                if patch_refine is not None and patch_refine.covers(s):
+                if patch_refine is not None and patch_refine.covers(s) and patch_refine.radius is not None:
+                    from .refine import carry_field
+                    sizes = (tuple(cur.shape[2:]), tuple(self.data_list[s][0][0].shape[1:]))
+                    prior = None
+                    if carried is not None:
+                        prior = carry_field(carried[0], patch_refine.patch, carried[1], sizes[0], carried[2], sizes[1],
+                                            wrap_query=tuple(em.tile))
+                    cur, _, yx = self.refine(cur, scale=s, patch=patch_refine.patch, iters=patch_refine.iters,
+                                             alpha=patch_refine.alpha, blend=patch_refine.blend, radius=patch_refine.radius,
+                                             prior=prior, field=True)
+                    carried = (yx,) + sizes
+                elif patch_refine is not None and patch_refine.covers(s):
                     cur = self.refine(cur, scale=s, patch=patch_refine.patch, iters=patch_refine.iters,
                                       alpha=patch_refine.alpha, blend=patch_refine.blend)[0]
                 whole = sdist.gather_batch(cur, batch_size)          # identity on a single process
@@ -430,8 +445,8 @@ class MultiscaleTrainer(object):
         """Snap a batch to the training image's patches: `refine.patch_refine` of the batch of `scale` (default: the finest)
         against that scale's training image, with `ema_model.tile` as the wrapped axes and the hard `train_mask` as `valid`
         (a hole is never copied from).  `samples`: a batch, or the list `sample_scales` returns; without it a batch is drawn
-        here (`batch_size`, default 16).  `kw` (`patch`, `iters`, `alpha`, `blend`, `weight`, `history`) goes to
-        `patch_refine`, whose result is returned: (x, energy[, iterates])."""
+        here (`batch_size`, default 16).  `kw` (`patch`, `iters`, `alpha`, `blend`, `weight`, `history`, `radius`, `prior`,
+        `field`) goes to `patch_refine`, whose result is returned: (x, energy[, iterates][, yx])."""
         from .refine import patch_refine
         s = self.n_scales - 1 if scale is None else int(scale)
         if not 0 <= s < self.n_scales:

@@ -2,7 +2,7 @@
 """Time sinddm_patch_nnf against a torch formulation of the same result on the same GPU, in one process, alternating.
 
     python tools/nnf_bench.py [--runs 7] [--patch 7] [--shapes 16x186x248 16x48x64] [--lib tools/ab/libnnf_x.so ...]
-                              [--scaled] [--vote] [--no-torch]
+                              [--scaled] [--vote] [--no-torch] [--local 4 8 16]
 
 Per shape B x H x W (query and reference of the same size, one shared reference) every route is warmed up once and then
 timed `--runs` times in turn (route A, route B, route A, ...) with device events; the report is the median, the min .. max
@@ -13,7 +13,10 @@ The torch route: F.unfold of both images, then per sample and per chunk of queri
 the references -- the M x N matrix goes through HBM chunk by chunk.  Its distances are compared with the library's first.
 `--scaled` adds the library's sinddm_patch_nnf_scaled with a random scale map in [0.5, 2) (same FLOP count); `--vote` adds
 sinddm_patch_vote on the library's own field and a device copy of the bytes the vote streams (the field, base and out:
-28 bytes per pixel; the gathered reference reads are not counted), both reported in GB/s."""
+28 bytes per pixel; the gathered reference reads are not counted), both reported in GB/s.  `--local R ...` adds, per radius,
+sinddm_patch_nnf_local with a coherent prior (the identity field plus a jitter of -1 .. 1 per axis) and with a random prior,
+in turn with the exhaustive route of the same process; they report candidate pairs per second, B M (2R + 1)^2 / time, and
+the share of their winners that are the exhaustive route's."""
 import argparse
 import ctypes as C
 import json
@@ -42,6 +45,9 @@ def bind(path):
         lib.sinddm_patch_nnf_scaled.argtypes = [p, i, p, i, p, p, i, p, p, i, i, i, i, i, i, i, i, p, sz, p]
         lib.sinddm_patch_vote.restype = i
         lib.sinddm_patch_vote.argtypes = [p, p, i, p, p, i, p, i, i, i, i, i, i, i, i, C.c_float, p]
+    if hasattr(lib, "sinddm_patch_nnf_local"):
+        lib.sinddm_patch_nnf_local.restype = i
+        lib.sinddm_patch_nnf_local.argtypes = [p, i, p, i, p, p, i, p, i, p, p, i, i, i, i, i, i, i, i, p]
     return lib
 
 
@@ -75,6 +81,30 @@ def scaled_route(lib, q, r, P):
         rc = lib.sinddm_patch_nnf_scaled(q.data_ptr(), 1, r.data_ptr(), 0, None, scale.data_ptr(), 0, dist.data_ptr(),
                                          idx.data_ptr(), B, H, W, Hr, Wr, P, 0, 0, ws.data_ptr(), n,
                                          torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, rc
+        return dist, idx
+    return run
+
+
+def local_priors(B, h, w, device):
+    """(coherent: the identity field plus a jitter of -1 .. 1 per axis, clamped into the grid; random), (B, h, w) int32."""
+    g = torch.Generator(device="cpu").manual_seed(3)
+    yy, xx = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+    jy, jx = torch.randint(-1, 2, (B, h, w), generator=g), torch.randint(-1, 2, (B, h, w), generator=g)
+    coherent = (yy[None] + jy).clamp(0, h - 1) * w + (xx[None] + jx).clamp(0, w - 1)
+    rand = torch.randint(0, h * w, (B, h, w), generator=g)
+    return coherent.to(torch.int32).to(device), rand.to(torch.int32).to(device)
+
+
+def local_route(lib, q, r, P, radius, prior):
+    B, _, H, W = q.shape
+    Hr, Wr = r.shape[2:]
+    dist = torch.empty(B, H - P + 1, W - P + 1, device=q.device)
+    idx = torch.empty(B, H - P + 1, W - P + 1, dtype=torch.int32, device=q.device)
+
+    def run():
+        rc = lib.sinddm_patch_nnf_local(q.data_ptr(), 1, r.data_ptr(), 0, None, None, 0, prior.data_ptr(), radius, dist.data_ptr(),
+                                        idx.data_ptr(), B, H, W, Hr, Wr, P, 0, 0, torch.cuda.current_stream().cuda_stream)
         assert rc == 0, rc
         return dist, idx
     return run
@@ -135,6 +165,7 @@ def main():
     ap.add_argument("--scaled", action="store_true")
     ap.add_argument("--vote", action="store_true")
     ap.add_argument("--no-torch", dest="torch", action="store_false")
+    ap.add_argument("--local", type=int, nargs="*", default=[], metavar="R")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -158,6 +189,16 @@ def main():
             vote, copy, nbytes = vote_routes(libs[0][1], q, r, P, outs["library"][1])
             routes += [("vote", vote), ("copy", copy)]
             moved = {"vote": nbytes, "copy": nbytes}
+        pairs, agree = {}, {}
+        if args.local:
+            coherent, rand = local_priors(B, H - P + 1, W - P + 1, dev)
+            for radius in args.local:
+                for kind, prior in (("coherent", coherent), ("random", rand)):
+                    name = f"local R={radius} {kind}"
+                    run = local_route(libs[0][1], q, r, P, radius, prior)
+                    routes.append((name, run))
+                    pairs[name] = B * (H - P + 1) * (W - P + 1) * (2 * radius + 1) ** 2
+                    agree[name] = float((run()[1] == outs["library"][1]).float().mean())
         for name, run in routes[len(outs):]:
             run()
         torch.cuda.synchronize()
@@ -182,6 +223,12 @@ def main():
                 print(json.dumps({"shape": shape, "patch": P, "route": name, "runs": len(ts), "median_ms": round(med, 4),
                                   "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "bytes": moved[name],
                                   "gb_per_s": round(moved[name] / med * 1e-6, 1)}), flush=True)
+                continue
+            if name in pairs:
+                print(json.dumps({"shape": shape, "patch": P, "route": name, "runs": len(ts), "median_ms": round(med, 4),
+                                  "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "pairs": pairs[name],
+                                  "gpairs_per_s": round(pairs[name] / med * 1e-6, 2),
+                                  "winners_equal_exhaustive": round(agree[name], 4)}), flush=True)
                 continue
             rec = {"shape": shape, "patch": P, "route": name, "runs": len(ts), "median_ms": round(med, 4), "min_ms": round(min(ts), 4),
                    "max_ms": round(max(ts), 4), "tflops": round(flop / med * 1e-9, 2),
