@@ -34,6 +34,9 @@ extern "C" {
 #define SINDDM_DIM_FP32_CONVS 0x10000  /* keep every 3x3 convolution on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32 Winograd
                                         * kernels) instead of the binary16 hi/lo kernel (conv_wh.h): for A/B measurements and
                                         * parity tests of the two paths; results agree to fp32 rounding (tests/test_gpu_h2.py) */
+#define SINDDM_DIM_HEAD_XIN 0x20000    /* the collapsed inference head reads block 4's whole input (dim planes) even where block 3's
+                                        * second conv could hand it the 3-plane projection W_r x_in from its epilogue: for A/B
+                                        * measurements and parity tests of the two forms (tests/test_gpu_head_proj.py) */
 
 /* Receptive radius of SinDDMNet in pixels: per block depthwise 5x5 (2) + 3x3 (1) + 3x3 (1) = 4, four blocks = 16; the
  * 1x1 convolutions add nothing.  The zero-padded network evaluated on an image extended by a wrapped halo of this many

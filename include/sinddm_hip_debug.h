@@ -75,6 +75,11 @@ int sinddm_debug_routes(int dim_arg, int train, int B, int H, int W, int out[16]
  *        (VALU), 2 = conv3x3_c3_mfma_kernel (fp32 matrix cores: inference, C_out % 16 == 0, row pitch % 4 == 0, at least 11
  *        64-pixel row segments per compute unit, rows that fill their segments to 85 % or more). */
 #define SINDDM_FWD_PLAN_INTS_EXT (SINDDM_FWD_PLAN_INTS + 4)
+/* ... and with cap >= SINDDM_FWD_PLAN_INTS_EXT2, behind those,
+ *   [SINDDM_FWD_PLAN_INTS_EXT] head_proj: 1 if block 3's second conv (conv_wr_kernel, C_out = 160) forms the head's projection
+ *        W_r x_in of its output in its epilogue and the head reads those 3 planes instead of block 4's input (the collapsed
+ *        head, that conv on conv_wh with items of 160 channels, dim = 160, no SINDDM_DIM_HEAD_XIN); 0: the head reads x_in. */
+#define SINDDM_FWD_PLAN_INTS_EXT2 (SINDDM_FWD_PLAN_INTS_EXT + 1)
 int sinddm_debug_forward_plan(int dim_arg, int train, int B, int H, int W, int ncu, int64_t* out, int cap);
 
 /* ONE first conv of the network (C_in = 3, 3x3, zero padding 1, + bias + GELU) on caller tensors, for kernel-level tests:
@@ -143,6 +148,17 @@ int sinddm_debug_conv_wh(int variant, int ncu, int B, int H, int W, int Wt, int 
                          float* out_pre, float* amax_out, void* scratch, size_t scratch_bytes, void* stream);
 /* bytes of scratch that hook needs; 0 for channel counts or a batch it refuses */
 size_t sinddm_debug_conv_wh_scratch_bytes(int Cin, int Cout, int B);
+
+/* The same convolution through conv_wr_kernel (variant 2) with Cout = 160, no activation, and the epilogue's projection:
+ *   out = conv2d(in, weights) + bias + resid,   proj_out[b][o][y][x] = sum_co proj_w[co][o] * out[b][co][y][x],  o = 0..2,
+ * proj_w (160, 3), proj_out (B, 3, H, W), 16-byte aligned.  The sum runs over the fp32 values the kernel stores, in a fixed
+ * order per pixel (head.h, SUMMATION ORDER), so it does not depend on ncu, the batch or the call.  Pad columns (Wt .. W - 1)
+ * of proj_out are written as zeros.  proj_out = NULL (then proj_w may be NULL too): the plain conv, bit for bit what
+ * sinddm_debug_conv_wh(variant 2, act 0) writes.  bias, resid may be NULL; resid may be `out`.  Scratch and refusals as
+ * sinddm_debug_conv_wh, plus SINDDM_E_BADSHAPE for Cout != 160 and SINDDM_E_BADARG for proj_out without proj_w. */
+int sinddm_debug_conv_wr_proj(int ncu, int B, int H, int W, int Wt, int Cin, int Cout, const float* in, const float* weights,
+                              const float* bias, const float* resid, const float* proj_w, float* out, float* proj_out,
+                              void* scratch, size_t scratch_bytes, void* stream);
 
 /* ONE SinDDMConvBlock (l = 0..3 of the plan of SinDDMNet(dim); reference SinDDM/models.py:51-80) forward + backward on
  * its own: x (B, C_in, H, W), cond_bias (B, C_in) = the block's per-sample condition (time_reshape(mlp(cond)),

@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "sinddm_q_sample_wrap", "sinddm_l1_loss_crop_fwd_bwd",
     "sinddm_sample_chain_mix", "sinddm_normal_fill_mix",
     "sinddm_l1_loss_weighted_fwd_bwd",
-    "sinddm_debug_conv_wh", "sinddm_debug_conv_wh_scratch_bytes",
+    "sinddm_debug_conv_wh", "sinddm_debug_conv_wh_scratch_bytes", "sinddm_debug_conv_wr_proj",
     "sinddm_debug_first_conv",
     "sinddm_patch_nnf_workspace_bytes", "sinddm_patch_nnf",
     "sinddm_q_sample_crop", "sinddm_l1_loss_rect_fwd_bwd",
@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
 
 ABI_VERSION = 3               # SINDDM_ABI_VERSION of include/sinddm_hip.h this binding was written against
 DIM_FP32_CONVS = 0x10000     # SINDDM_DIM_FP32_CONVS of include/sinddm_hip.h: option bit of every `dim` argument
+DIM_HEAD_XIN = 0x20000       # SINDDM_DIM_HEAD_XIN: the collapsed head reads block 4's input, not the conv epilogue's 3-plane projection
 JUMP_STREAM = 1 << 31        # SINDDM_JUMP_STREAM of include/sinddm_hip.h: a jump's z2 draw is the step's stream id plus this
 MIX_MAX = 4                  # SINDDM_MIX_MAX of include/sinddm_hip.h: seeds per blended sample
 SCORE_MAX_EVALS = 1024       # evaluations per sinddm_score_chain call (CHAIN_COND_ROWS of csrc/fwd_plan.h)
@@ -219,6 +220,7 @@ def load() -> C.CDLL:
         "sinddm_debug_wgrad_scratch_bytes": (sz, [i, i, i, i]),
         "sinddm_debug_conv_wh": (i, [i, i, i, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, sz, p]),
         "sinddm_debug_conv_wh_scratch_bytes": (sz, [i, i, i]),
+        "sinddm_debug_conv_wr_proj": (i, [i, i, i, i, i, i, i, p, p, p, p, p, p, p, p, sz, p]),
         "sinddm_debug_first_conv": (i, [i, i, i, i, i, i, i, p, p, p, p, p, p]),
         "sinddm_debug_head_offsets": (i, [i, C.POINTER(C.c_int64)]),
         "sinddm_debug_forward_plan": (i, [i, i, i, i, i, i, C.POINTER(C.c_int64), i]),

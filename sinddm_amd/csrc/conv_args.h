@@ -28,6 +28,8 @@ struct ConvArgs {
     float* amax_out;     // optional per-sample device scalars [b * AMAX_STRIDE]: running max |out[b]| (guarded atomicMax), for the conv that reads `out` next
     int Wt;              // 0, or the TRUE image width when rows are padded to W (a multiple of 4) inside the library's own
                          // workspace: columns Wt .. W-1 of every input row hold zeros and are written as zeros
+    const float* proj_w; // (conv_wh.h, the 160-channel kernel with Cout == 160) [Cout][3]: a 3-plane projection of `out` ...
+    float* proj_out;     // ... [B][3][H][W] = sum_co proj_w[co][o] * out[co], formed in the epilogue; nullptr = none
 };
 
 // geometry for NT 16-pixel tiles per wave (4 waves along N, tile width 32)

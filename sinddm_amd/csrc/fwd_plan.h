@@ -75,6 +75,8 @@ struct ForwardPlan {
     int route[8];          // ConvKernel of conv i + 1 of block l at [2 l + i]; -1: not launched (block 4's conv2 under the head)
     bool any_wh;           // a route is CONV_WH: the evaluation zeroes and maintains the running maxima
     bool head;             // the collapsed inference head (head.h) replaces block 4's conv2 + projection + final_conv
+    bool head_proj;        // ... and reads W_r x_in as 3 planes from block 3's conv2 (conv_wr_kernel's epilogue) instead of x_in:
+                           // that conv on CONV_WH variant 2 with C_out = 160, so one item holds every channel of a pixel
     FwdBlock blk[4];
     LastLaunch last[2];    // [1]: the step fuses its tail, [0]: the evaluation writes eps ([1] == [0] where no fused kernel exists)
     unsigned last_gx[2];   // gridDim.x of each (gridDim.y = B)
@@ -182,6 +184,11 @@ ForwardPlan forward_plan(const NetPlan& P, FwdMode mode, int B, int H, int W, in
         f.dw = dw_rows_applies(f.dw_pi, f.dw_po) ? DW_ROWS : DW_TILES;
         F.n_launches += 2 + (f.max_pass ? 1 : 0) + (r2 >= 0 ? 1 : 0) + (f.resid == RESID_1X1_FRONT ? 1 : 0);
     }
+    // The head's projection of block 4's input, from the epilogue that holds it in registers.  Wider nets keep the x_in
+    // form: their items cover 160 of the channels.  (A split chain never routes CONV_WH -- chain_split -- so the two halves
+    // of a batch cannot disagree.)
+    F.head_proj = SINDDM_HEAD_PROJ && !P.head_xin && F.head && F.route[5] == CONV_WH && F.blk[2].wh_variant[1] == 2 &&
+                  P.blk[2].cout == WR_COB;
     // the last launch: a thread owns a quad of a row (aligned rows) or four consecutive pixels of a plane
     const unsigned row_quads = (unsigned)((H * (F.Wp / 4) + 255) / 256);
     F.fuse_tail = F.HW % 4 == 0 || F.padded;

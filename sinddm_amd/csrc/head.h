@@ -14,6 +14,9 @@ namespace sinddm {
 #ifndef SINDDM_HEAD_COLLAPSE      // 1: inference evaluates block 4's conv2 + residual projection + final_conv as the collapsed head
 #define SINDDM_HEAD_COLLAPSE 1
 #endif
+#ifndef SINDDM_HEAD_PROJ          // 1: where block 3's conv2 runs conv_wr_kernel over all of its channels, its epilogue forms W_r x_in
+#define SINDDM_HEAD_PROJ 1        //    and the head reads those 3 planes instead of the dim planes of x_in (fwd_plan.h: head_proj)
+#endif
 
 // channels per partial sum of the head (see HeadEps)
 constexpr int HEAD_GROUP = 16;
@@ -73,13 +76,19 @@ inline int head_pack_launch(const NetPlan& P, const float* params, float* packed
 //     for every group of HEAD_GROUP input channels of g, ascending:   p = 0
 //         for ci ascending, ky = 0..2, kx = 0..2:                     p = fma(W_c[o][ci][ky][kx], g[ci][y+ky-1][x+kx-1], p)
 //         e = e + p
+//   the x_in form (er == nullptr):
 //     for every group of HEAD_GROUP channels of x_in, ascending:      p = 0
 //         for ci ascending:                                           p = fma(W_r[o][ci], x_in[ci][y][x], p)
 //         e = e + p
+//   the projected form (er set: conv_wr_kernel's epilogue has formed W_r x_in while it held x_in in registers, conv_wh.h):
+//     e = e + er[o][y][x],   er[o] = sum over c16 = 0..15 ascending of s(c16),
+//         s(c16) = 0;  for n = 0..9 ascending:                        s = fma(W_r[o][16 n + c16], x_in[16 n + c16][y][x], s)
+// Both orders are fixed per pixel; they differ from each other by fp32 rounding of a 160-term sum.
 // Every product is an explicit fmaf, so the compiler has nothing to contract differently from one instantiation to the
 // next.  The partial sums per 16 channels are the most accurate of the forms tried (profiles/NOTES_r13.md); the twelve
 // accumulators of a thread (3 channels x 4 pixels) are independent chains, which is what hides the FMA latency.
-// The weights are wave-uniform: scalar operands.
+// The weights are wave-uniform: scalar operands; so is the choice of the form (one branch per thread, no second set of
+// instantiations of the kernels that take a HeadEps).
 struct HeadEps {
     const float* g;      // [B][half][H][Wp]   GELU(conv1) of block 4
     const float* xin;    // [B][dim][H][Wp]    block 4's input
@@ -87,6 +96,7 @@ struct HeadEps {
     const float* wr;     // [dim][3]
     const float* bc;     // [3]
     int half, dim, H, Wp;
+    const float* er;     // [B][3][H][Wp]      W_r x_in, formed by the producer of x_in -- or nullptr: xin is read
 
     __device__ __forceinline__ void operator()(int b, int q, f32x4 (&e)[3]) const {
         const int qpr = Wp >> 2;
@@ -119,6 +129,13 @@ struct HeadEps {
                 v[r][5] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, orr[r], 0, 0));
             }
         };
+        // (the projected form's three quads are requested in front of the g loop: no round trip of their own behind it)
+        f32x4 erq[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        if (er) {
+            const float* eb = er + (size_t)b * CHANNELS * plane + (size_t)q * 4;
+#pragma unroll
+            for (int o = 0; o < 3; ++o) erq[o] = *reinterpret_cast<const f32x4*>(eb + (size_t)o * plane);
+        }
         float in[3][6];
         fetch(0, in);
         f32x4 p[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -145,6 +162,11 @@ struct HeadEps {
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int k = 0; k < 6; ++k) in[r][k] = nx[r][k];
+        }
+        if (er) {
+#pragma unroll
+            for (int o = 0; o < 3; ++o) e[o] += erq[o];
+            return;
         }
         const float* xb = xin + (size_t)b * dim * plane + (size_t)q * 4;
         for (int c0 = 0; c0 < dim; c0 += HEAD_GROUP) {

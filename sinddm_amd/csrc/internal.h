@@ -79,9 +79,10 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
 // One SinDDMConvBlock forward (sinddm_fwd.hip) as F describes block l: routes, conv_wh variants, running-max slots, the
 // residual form, the bias source and the row pitch are the plan's; `cond` = the block's per-sample bias rows, stride in
 // floats; `amax` = the evaluation's running maxima [B][AMAX_STRIDE] (may be null where the plan names no slot).
+// head_er (block 3 under F.head_proj, else null): [B][3][H][Wp], where conv2 leaves the head's projection of its output.
 int block_forward(const NetPlan& P, const ForwardPlan& F, int l, const float* params, const float* packed, const float* cur,
                   const float* cond, int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, hipStream_t st,
-                  float* amax);
+                  float* amax, float* head_er = nullptr);
 // One launch of the routed kernel (every route but CONV_C3, which block_forward launches itself): fills w3, nch3, wsinv,
 // coblks and the m-tile count from the images at `packed`; the caller has set the tensors, act / aux / resid / bias, the
 // fused 1x1 fields of the direct kernel and the amax pointers.  wh_variant (read on CONV_WH only) is resolved by the

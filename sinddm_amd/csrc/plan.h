@@ -85,6 +85,7 @@ struct NetPlan {
     int64_t tensor_off[64];
     int cond_stride;   // floats per sample of the cond-bias vector (sum of cin, padded to 4)
     bool fp32_convs;   // per-call option SINDDM_DIM_FP32_CONVS: no launch takes the binary16 hi/lo kernels
+    bool head_xin;     // per-call option SINDDM_DIM_HEAD_XIN: the collapsed head reads block 4's input itself (fwd_plan.h: head_proj stays off)
     bool ok;
 };
 
@@ -94,7 +95,8 @@ inline NetPlan make_plan(int dim_arg) {
     NetPlan p{};
     const int dim = dim_arg & 0xFFFF;
     p.fp32_convs = (dim_arg & 0x10000) != 0;
-    if (dim_arg < 0 || (dim_arg >> 17) != 0) { p.ok = false; return p; }
+    p.head_xin = (dim_arg & 0x20000) != 0;
+    if (dim_arg < 0 || (dim_arg >> 18) != 0) { p.ok = false; return p; }
     p.ok = dim >= 2 && dim % 2 == 0 && dim <= 1024;
     p.dim = dim;
     p.half = dim / 2;

@@ -930,8 +930,10 @@ static int tail_rows_launch(const TailIO& io, const TailArgs& t, bool mid_quad, 
 #define TAIL_KERNEL(name) \
     [](auto E, auto N, auto K) { return &name<decltype(E)::value, decltype(N)::value, decltype(K)::value>; }
 
-static HeadEps head_eps(const NetPlan& P, const float* packed, const float* g, const float* xin, int H, int Wp) {
-    return HeadEps{g, xin, packed + P.pk_hc, packed + P.pk_hr, packed + P.pk_hb, P.half, P.dim, H, Wp};
+// er: the projection W_r x_in where block 3's conv2 has formed it (ForwardPlan::head_proj), else nullptr: the head reads xin
+static HeadEps head_eps(const NetPlan& P, const float* packed, const float* g, const float* xin, int H, int Wp,
+                        const float* er = nullptr) {
+    return HeadEps{g, xin, packed + P.pk_hc, packed + P.pk_hr, packed + P.pk_hb, P.half, P.dim, H, Wp, er};
 }
 
 int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, ConvArgs a, hipStream_t st, int wh_variant) {
@@ -964,7 +966,7 @@ int conv3x3_launch(ConvKernel k, const Conv3x3Images& c, const float* packed, Co
 // front of the collapsed head, which reads gbuf and cur itself) stops behind conv1.
 int block_forward(const NetPlan& P, const ForwardPlan& F, int l, const float* params, const float* packed, const float* cur,
                   const float* cond, int cond_stride, float* hbuf, float* gbuf, float* obuf, float* upre, hipStream_t st,
-                  float* amax) {
+                  float* amax, float* head_er) {
     const BlockPlan& b = P.blk[l];
     const FwdBlock& f = F.blk[l];
     const int B = F.B, H = F.H, W = F.Wp, Wt = F.Wt;
@@ -1001,6 +1003,10 @@ int block_forward(const NetPlan& P, const ForwardPlan& F, int l, const float* pa
     c2.act = 0; c2.zero = packed + P.pk_zero; c2.Wt = Wt;
     c2.bias = packed + b.pk_b2;
     c2.amax_in = slot(f.amax_in[1]);
+    if (head_er) {                                         // (block 3 under F.head_proj: the head's 3 planes of this conv's output)
+        if (l != 2 || !F.head_proj) return SINDDM_E_BADARG;
+        c2.proj_w = packed + P.pk_hr; c2.proj_out = head_er;
+    }
     if (f.resid == RESID_IDENTITY) c2.resid = cur;
     else if (f.resid == RESID_FUSED_DIRECT) {
         c2.in2 = cur; c2.Cin2 = b.cin; c2.w1 = packed + b.pk_res; c2.nch1 = b.nchr;
@@ -1113,16 +1119,24 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     }
     int curb = -1;
     const float* head_g = nullptr;
+    float* head_er = nullptr;    // F.head_proj: block 3's conv2 leaves W_r x_in here, 3 planes in front of its own (dead) hbuf
+    int erb = -1;
     for (int l = 0; l < 4; ++l) {
-        // three scratch buffers different from the one holding `cur`
-        int sel[3], n = 0;
+        // three scratch buffers different from the one holding `cur` -- and, for block 4, from the one holding the projection
+        // (its obuf is unused under the head)
+        int sel[3] = {-1, -1, -1}, n = 0;
         for (int i = 0; i < 4 && n < 3; ++i)
-            if (i != curb) sel[n++] = i;
+            if (i != curb && i != erb) sel[n++] = i;
         float* hbuf = tb ? tb->h[l] : buf[sel[0]];
         float* gbuf = tb ? tb->g[l] : buf[sel[1]];
-        float* obuf = tb ? tb->o[l] : buf[sel[2]];
+        float* obuf = tb ? tb->o[l] : sel[2] >= 0 ? buf[sel[2]] : nullptr;
+        if (F.head_proj && l == 2) {
+            // conv1 has consumed h3 when conv2 runs; g3 is still read by other workgroups of that launch, so not gbuf
+            head_er = hbuf;
+            erb = sel[0];
+        }
         const int rc = block_forward(P, F, l, params, packed, cur, cond + P.blk[l].cond_off, cond_stride, hbuf, gbuf, obuf,
-                                     tb ? tb->u[l] : nullptr, st, amax);
+                                     tb ? tb->u[l] : nullptr, st, amax, l == 2 ? head_er : nullptr);
         if (rc) return rc;
         if (F.route[2 * l + 1] < 0) { head_g = gbuf; break; }  // (the collapsed head: cur stays block 4's input)
         cur = obuf;
@@ -1130,7 +1144,7 @@ int net_forward_impl(const NetPlan& P, const float* params, const float* packed,
     }
     // the last launch: eps from block 4's g and input (the collapsed head) or from block 4's output (final_conv), under the
     // step's tail where a sampler step fuses it
-    const HeadEps he = head_eps(P, packed, head_g, cur, H, F.Wp);
+    const HeadEps he = head_eps(P, packed, head_g, cur, H, F.Wp, head_er);
     const FinalConvEps fe{cur, params + P.fin_w, params + P.fin_b, P.half, (size_t)H * F.Wp};
     const int which = cs && cs->x_next ? 1 : 0;
     const dim3 grid(F.last_gx[which], B);
@@ -2032,6 +2046,7 @@ int sinddm_debug_forward_plan(int dim_arg, int train, int B, int H, int W, int n
         for (int i = 0; i < SINDDM_FWD_PLAN_BLOCK_INTS; ++i) out[SINDDM_FWD_PLAN_BLOCK0 + l * SINDDM_FWD_PLAN_BLOCK_INTS + i] = blk[i];
         if (cap >= SINDDM_FWD_PLAN_INTS_EXT) out[SINDDM_FWD_PLAN_INTS + l] = f.c3_variant;     // (a caller with room for them)
     }
+    if (cap >= SINDDM_FWD_PLAN_INTS_EXT2) out[SINDDM_FWD_PLAN_INTS_EXT] = F.head_proj;
     return 0;
 }
 
@@ -2081,9 +2096,11 @@ size_t sinddm_debug_conv_wh_scratch_bytes(int Cin, int Cout, int B) {
            wh_debug_round((size_t)B * AMAX_STRIDE * sizeof(float));
 }
 
-int sinddm_debug_conv_wh(int variant, int ncu, int B, int H, int W, int Wt, int Cin, int Cout, int act, const float* in,
+// proj_w / proj_out: sinddm_debug_conv_wr_proj's two tensors (variant 2, Cout = 160), else null
+static int wh_debug_conv(int variant, int ncu, int B, int H, int W, int Wt, int Cin, int Cout, int act, const float* in,
                          const float* weights, const float* bias, const float* resid, const float* aux, float* out,
-                         float* out_pre, float* amax_out, void* scratch, size_t scratch_bytes, void* stream) {
+                         float* out_pre, float* amax_out, const float* proj_w, float* proj_out, void* scratch,
+                         size_t scratch_bytes, void* stream) {
     if (!in || !weights || !out || !scratch || (act == 2 && !aux)) return SINDDM_E_BADARG;
     if (variant < 0 || variant > 2 || act < 0 || act > 2 || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0)
         return SINDDM_E_BADARG;
@@ -2093,7 +2110,8 @@ int sinddm_debug_conv_wh(int variant, int ncu, int B, int H, int W, int Wt, int 
     if ((long long)Cin * H * W * 4 >= 0x40000000LL || (long long)B * ((H + 7) / 8) * ((W + 31) / 32) > 0x3fffffffLL)
         return SINDDM_E_BADSHAPE;
     if (scratch_bytes < sinddm_debug_conv_wh_scratch_bytes(Cin, Cout, B) || (uintptr_t)scratch % 256 != 0) return SINDDM_E_BADARG;
-    for (const void* q : {(const void*)in, (const void*)resid, (const void*)aux, (const void*)out, (const void*)out_pre})
+    for (const void* q : {(const void*)in, (const void*)resid, (const void*)aux, (const void*)out, (const void*)out_pre,
+                          (const void*)proj_out})
         if ((uintptr_t)q % 16 != 0) return SINDDM_E_BADARG;      // 16-byte loads and stores
 
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2111,7 +2129,24 @@ int sinddm_debug_conv_wh(int variant, int ncu, int B, int H, int W, int Wt, int 
     a.in = in; a.resid = resid; a.aux = aux; a.bias = bias; a.out = out; a.out_pre = out_pre;
     a.w3 = static_cast<const float*>(img); a.wsinv = wsinv; a.amax_in = amax_in; a.amax_out = amax_out;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act; a.Wt = Wt;
+    a.proj_w = proj_w; a.proj_out = proj_out;
     return conv_wh_launch(a, st, variant, ncu);
+}
+
+int sinddm_debug_conv_wh(int variant, int ncu, int B, int H, int W, int Wt, int Cin, int Cout, int act, const float* in,
+                         const float* weights, const float* bias, const float* resid, const float* aux, float* out,
+                         float* out_pre, float* amax_out, void* scratch, size_t scratch_bytes, void* stream) {
+    return wh_debug_conv(variant, ncu, B, H, W, Wt, Cin, Cout, act, in, weights, bias, resid, aux, out, out_pre, amax_out,
+                         nullptr, nullptr, scratch, scratch_bytes, stream);
+}
+
+int sinddm_debug_conv_wr_proj(int ncu, int B, int H, int W, int Wt, int Cin, int Cout, const float* in, const float* weights,
+                              const float* bias, const float* resid, const float* proj_w, float* out, float* proj_out,
+                              void* scratch, size_t scratch_bytes, void* stream) {
+    if (proj_out && !proj_w) return SINDDM_E_BADARG;
+    if (Cout != WR_COB) return Cout <= 0 ? SINDDM_E_BADARG : SINDDM_E_BADSHAPE;
+    return wh_debug_conv(2, ncu, B, H, W, Wt, Cin, Cout, 0, in, weights, bias, resid, nullptr, out, nullptr, nullptr,
+                         proj_out ? proj_w : nullptr, proj_out, scratch, scratch_bytes, stream);
 }
 
 int sinddm_prof_end3(int kind, double* ms_total, int64_t* launches, double* flops_total, double* exec_flops_total,

@@ -289,6 +289,9 @@ class SinDDMNet(nn.Module):
     # launches on the fp32 matrix pipe -- A/B measurements and parity tests (set it on an instance, or on the class for every
     # net a test builds); no reference counterpart
     fp32_convs = False
+    # ... and SINDDM_DIM_HEAD_XIN: True keeps the collapsed head on block 4's whole input where block 3's second conv would
+    # hand it the 3-plane projection from its epilogue (dim = 160 at the finest scales) -- the same uses
+    head_xin = False
 
     def __init__(self, dim, out_dim=None, channels=3, with_time_emb=True, multiscale=False, device=None):
         super().__init__()
@@ -468,7 +471,7 @@ class SinDDMNet(nn.Module):
     @property
     def dim_arg(self) -> int:
         """The `dim` argument of the launching C-ABI calls: the width + this net's option bits."""
-        return self.dim | (_lib.DIM_FP32_CONVS if self.fp32_convs else 0)
+        return self.dim | (_lib.DIM_FP32_CONVS if self.fp32_convs else 0) | (_lib.DIM_HEAD_XIN if self.head_xin else 0)
 
     def forward(self, x, time, scale=None):
         """eps = net(x, time, scale) -- same call signature as the reference (models.py:134)."""
